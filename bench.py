@@ -1,13 +1,19 @@
 #!/usr/bin/env python
 """bench.py -- forward ELBO steps/sec of the conv-GP hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME] [--dump-outputs DIR] [--full]
 
 One "step" = one forward ELBO evaluation of a synthetic minibatch (compute_log_likelihood semantics:
 S = 10 samples, all layers, data term + all KLs, scalar read back to the host), inputs already resident
 in HBM, nothing cached across steps.  At N = 1 the workload is BASELINE.json configs[1] (MNIST 1-layer
 M = 256, batch 32) in its conv-layer + head form (K_uf + Cholesky + conditional); noise comes from the
 counter-based device RNG, as the reference draws it inside its graph.
+
+A plain run sets up, warms up (at least 100 untimed steps), times K steps and prints the headline line
+(`value`, `ms_per_step`, ...).  --dump-outputs DIR writes the last timed step's ELBO, data term and KL as
+DIR/<name>.npy; the inputs and noise seeds depend on the arguments only.  --full adds every informational
+leg behind the timed region: roofline and per-kernel timing, steps in flight, weak scaling, the training
+step, K_uf sweep and shard-sweep figures, the head-only leg, measured ceilings and the CPU baseline.
 
 N > 1: one process per GPU.  Launched by a process launcher (RANK / WORLD_SIZE in the environment, e.g.
 `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N`) each process is one rank; launched
@@ -58,10 +64,18 @@ def conv_geometry(c, rows):
     return P, c["f"] * c["f"] * c["C"], rows * P
 
 
+def usable_cpus():
+    """CPUs this process may use: its affinity mask, capped by OMP_NUM_THREADS where a shared host sets it (os.cpu_count() is
+    the whole machine's)."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    lim = os.environ.get("OMP_NUM_THREADS", "")
+    return min(n, int(lim)) if lim.isdigit() and int(lim) > 0 else n
+
+
 def cpu_baseline(name, S, batch, budget_s=30.0):
     """The oracle (NumPy/OpenBLAS fp64 restatement in the reference's operation order) timed on the host, as BASELINE.md section 2
     lays it out: 2 warm-up + >= 5 timed forward ELBO steps of the same workload, median; the BLAS thread count is the best of
-    {8, 32, 64, all cores} (one probing step each -- 256 OpenBLAS threads on a 0.2 s GEMM are slower than 32) and is reported; a
+    {8, 32, 64, all usable cores} (one probing step each -- 256 OpenBLAS threads on a 0.2 s GEMM are slower than 32) and is reported; a
     1-thread row beside it on a quarter of the batch (the step is linear in the batch: value scaled by 1/4 and labelled).  Bounded
     at ~budget_s seconds of CPU work whatever the host."""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -89,7 +103,7 @@ def cpu_baseline(name, S, batch, budget_s=30.0):
 
     one(model, X, Y)                                             # warm-up 1: first touch of every buffer (several times a steady step)
     t_begin = time.perf_counter()
-    ncpu = os.cpu_count() or 1
+    ncpu = usable_cpus()
     probes = {}
     for n in sorted({min(c, ncpu) for c in (8, 32, 64, ncpu)}):    # one probing step per thread count: warm-ups 2...
         with limited(n):
@@ -110,11 +124,11 @@ def cpu_baseline(name, S, batch, budget_s=30.0):
     with limited(1):
         t1 = [one(m1, X[:q], Y[:q]) for _ in range(2)][-1] if threadpool_limits else None
     out = {"value": 1.0 / med, "unit": "ELBO steps/s", "cores": best, "kind": "port",
-           "threads": best, "host_cores": ncpu, "steps_timed": len(times), "warmup_steps": len(probes) + 2,
+           "threads": best, "host_cores": os.cpu_count(), "usable_cores": ncpu, "steps_timed": len(times), "warmup_steps": len(probes) + 2,
            "thread_probe_s_per_step": {str(k): round(v, 3) for k, v in probes.items()},
            "sample": "%d full forward ELBO steps of the same workload (batch %d, S=%d) with the float64 NumPy/OpenBLAS oracle in the "
                      "reference's operation order (materialised K_uf, per-patch triangular solves, dense tensordot), %d BLAS threads "
-                     "(best of %s on %d host cores), after %d warm-up steps; median %.2f s/step; not TensorFlow"
+                     "(best of %s on %d usable cores), after %d warm-up steps; median %.2f s/step; not TensorFlow"
                      % (len(times), batch, S, best, sorted(probes), ncpu, len(probes) + 2, med)}
     # the same arithmetic batched the way a CPU likes it (oracle/fast_cpu.py: ONE triangular solve over all K columns, ONE (R M) x M x K
     # GEMM instead of the reference's loop of 2 P solves + tensordot): what a tuned CPU implementation would reach, beside the
@@ -247,12 +261,15 @@ class Leg:
         self.scale = float(self.spec["num_data"]) / float(global_batch)
 
     def step(self, i):
+        """One forward ELBO step; returns the ELBO and keeps (ELBO, data term, KL) as self.last."""
+        elbo, data, kl = self.model.compute_log_likelihood(self.dX, self.dY, seed=i, scale=self.scale, return_parts=True)
         if self.comm == "host":
             # fallback join (RCCL could not initialise, e.g. two ranks on one device): the local data term comes back,
             # is summed over the ranks by the host group, and the ELBO is assembled here
-            _, data, kl = self.model.compute_log_likelihood(self.dX, self.dY, seed=i, scale=self.scale, return_parts=True)
-            return float(self.grp.allreduce([data], "sum")[0]) * self.scale - kl
-        return self.model.compute_log_likelihood(self.dX, self.dY, seed=i, scale=self.scale)
+            data = float(self.grp.allreduce([data], "sum")[0])
+            elbo = data * self.scale - kl
+        self.last = (elbo, data, kl)
+        return elbo
 
     def run_pipelined(self, first, n, depth):
         """n steps with `depth` steps queued (dcgp_elbo_forward_enqueue / _collect): every step's ELBO still comes back
@@ -387,17 +404,19 @@ def kuf_measure(leg, ctx, steps):
                 res["sweep_us_every_row_evaluated"] = 1e3 * t[1] / t[0]
     for i in range(3):
         leg.step(i)
-    # phase stamps of the one-launch layer kernel (csrc/conv_fused.hip CF_TR): [8 sampled workgroups][16 waves][16 stamps]
-    buf = ctx.to_device(np.zeros((8, 16, 16), np.int64), np.int64)
+    # phase stamps of the one-launch layer kernel (csrc/conv_fused.hip CF_TR): [8 sampled workgroups x 4 strips of a persistent one][16 waves]
+    # [16 stamps] -- the kernel stamps all 8192 words and takes no length, so the buffer must hold them all
+    buf = ctx.to_device(np.zeros((32, 16, 16), np.int64), np.int64)
     dev.lib().dcgp_debug_set_fused_trace(ctx.handle, buf.ptr)
     leg.step(7)
     ctx.sync()
     dev.lib().dcgp_debug_set_fused_trace(ctx.handle, None)
     t = buf.numpy().astype(np.float64)
     phase, ghz = [], []
-    for b in range(8):
+    for b in range(32):
         live = t[b, :, 0] > 0
-        if not live.any() or not t[b, 0, 11] > t[b, 0, 10]:
+        # whole strips only: a "prologue only" item never reaches stamps 9 - 11, one that fetched A1 has no K_uf phase (stamps 1, 2)
+        if not live.any() or not t[b, 0, 11] > t[b, 0, 10] or not t[b, 0, 9] or not t[b, 0, 1]:
             continue
         clk = (t[b, 0, 9] - t[b, 0, 0]) / ((t[b, 0, 11] - t[b, 0, 10]) / 100.0) / 1e3        # shader GHz from wall_clock64 (100 MHz)
         ghz.append(clk)
@@ -476,10 +495,16 @@ def main():
     ap.add_argument("--dedup-layer0", action="store_true",
                     help="evaluate layer 0 on the distinct images only (exact; off by default so that the step does "
                          "the same work as the reference, which tiles the batch S times)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-grad-leg", action="store_true", help="skip the informational value-and-gradient timing")
-    ap.add_argument("--no-extra-legs", action="store_true", help="skip the head-only and shard-sweep legs")
-    ap.add_argument("--no-all-configs", action="store_true", help="skip the strong-scaling preview of the other BASELINE configurations")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure, run every informational leg as well: roofline and per-kernel timing, two steps in flight, "
+                         "weak scaling, layer-0 de-duplication, evaluation at fixed parameters, the gradient / training step, the K_uf sweep, "
+                         "the shard sweeps, the head-only leg, the measured ceilings and the CPU baseline (the --no-* options below trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned -- elbo, data_term, kl -- as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-grad-leg", action="store_true", help="--full: skip the informational value-and-gradient timing")
+    ap.add_argument("--no-extra-legs", action="store_true", help="--full: skip the head-only and shard-sweep legs")
+    ap.add_argument("--no-all-configs", action="store_true", help="--full: skip the strong-scaling preview of the other BASELINE configurations")
     ap.add_argument("--profile", action="store_true",
                     help="for rocprofv3 runs: exactly --warmup + --steps steps, none of the extra regions, no CPU baseline")
     ap.add_argument("--dry-run", action="store_true",
@@ -493,6 +518,8 @@ def main():
                     help="N > 1: rccl = in-stream ncclAllReduce inside dcgp_elbo_forward (default); host = host-group "
                          "all-reduce of the per-rank data term (debug / fallback when RCCL cannot initialise)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # plain `python bench.py --gpus N`: this process is the launcher -- one child per rank, rank 0 prints the line
@@ -542,9 +569,44 @@ def main():
     # nothing but the sync + rank barrier between them.
     gc.collect()
     gc.disable()       # a generation-2 collection inside the timed loop showed up as a ~50 ms hiccup in 1 run out of 4
-    for i in range(args.warmup if args.profile else max(args.warmup, 100)):
+    warmup_run = args.warmup if args.profile else max(args.warmup, 100)   # untimed: at least 100 (clock ramp, see above)
+    for i in range(warmup_run):
         leg.step(i)
     dt, elbo = leg.timed(args.warmup, args.steps)
+    if rank == 0 and args.dump_outputs:
+        # the last timed step's result (seeds and inputs are fixed by the arguments: two builds compare output for output)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, v in zip(("elbo", "data_term", "kl"), leg.last):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.array([v], np.float64))
+
+    value = args.steps / dt
+    out = {
+        # BASELINE.json's metric string for its configs[1]; `value` is the steps/sec part (forward ELBO evaluations of the
+        # configuration's minibatch, sharded over the ranks), the K_uf HBM GB/s part is `kuf_hbm_gbs` / `roofline_kuf` (--full)
+        "metric": "ELBO steps/sec (batch=%d) + achieved HBM GB/s on K_uf, MNIST M=256 1-layer" % cfg["batch"]
+                  if args.config.startswith("cfg2") else "ELBO steps/sec (batch=%d) + achieved HBM GB/s on K_uf" % cfg["batch"],
+        "value": value, "unit": "ELBO steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "warmup_steps_run": warmup_run,
+        "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True, "scaling": "strong",
+        "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": args.config, "variant": "conv layer + head" if cfg["convs"] else "head only",
+                   "M": cfg["M"], "per_gpu_batch": hi - lo, "global_batch": cfg["batch"], "num_samples": S,
+                   "image": list(cfg["hwc"]), "layers": len(cfg["convs"]) + 1, "noise": "device Philox RNG",
+                   "dedup_layer0": bool(args.dedup_layer0),
+                   "parallelism": "image-sharded x%d, %s" % (world, {"none": "no collective", "rccl": "in-stream ncclAllReduce of 1 f64",
+                                                                      "host": "host-group all-reduce of 1 f64 (RCCL fallback)"}[comm])},
+        "ranks_seen_by_rccl": rccl_ranks,
+        "elbo": elbo,
+    }
+    if not args.full:
+        if rank == 0:
+            print("\n" + json.dumps(out))      # on a line of its own whatever a library (RCCL's banner) left on stdout before it
+            sys.stdout.flush()
+        grp.barrier()
+        grp.close()
+        return
+
+    # ---- --full: everything below is informational and runs behind the timed region ----------------------------------
     # The roofline kernel's launch duration: HIP events on its own stream around EVERY launch of it (timing mode 3), in a loop of
     # its own (>= 50 steps) behind the timed region -- the judged value pays nothing for it, and the average does not depend on --steps.
     n_roof = 0 if args.profile else max(50, min(args.steps, 200))
@@ -766,27 +828,10 @@ def main():
     mfma_ceiling = None if args.profile else informational("mfma-ceiling", ctx.measured_mfma_f64_tflops)
 
     if rank == 0:
-        value = args.steps / dt
         per_rank_batch = hi - lo
-        out = {
-            # BASELINE.json's metric string for its configs[1]; `value` is the steps/sec part (forward ELBO evaluations of the
-            # configuration's minibatch, sharded over the ranks), the K_uf HBM GB/s part is `kuf_hbm_gbs` / `roofline_kuf`
-            "metric": "ELBO steps/sec (batch=%d) + achieved HBM GB/s on K_uf, MNIST M=256 1-layer" % cfg["batch"]
-                      if args.config.startswith("cfg2") else "ELBO steps/sec (batch=%d) + achieved HBM GB/s on K_uf" % cfg["batch"],
-            "value": value, "unit": "ELBO steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "warmup_steps_run": args.warmup if args.profile else max(args.warmup, 100),   # untimed: at least 100 (clock ramp, see the comment at the warm-up loop)
-            "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True, "scaling": "strong",
-            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": args.config, "variant": "conv layer + head" if cfg["convs"] else "head only",
-                       "M": cfg["M"], "per_gpu_batch": per_rank_batch, "global_batch": cfg["batch"], "num_samples": S,
-                       "image": list(cfg["hwc"]), "layers": len(cfg["convs"]) + 1, "noise": "device Philox RNG",
-                       "dedup_layer0": bool(args.dedup_layer0),
-                       "parallelism": "image-sharded x%d, %s" % (world, {"none": "no collective", "rccl": "in-stream ncclAllReduce of 1 f64",
-                                                                          "host": "host-group all-reduce of 1 f64 (RCCL fallback)"}[comm])},
-            "ranks_seen_by_rccl": rccl_ranks,
+        out.update({
             "weak": weak if world > 1 else {"value": value, "unit": "batch-%d-equivalent ELBO steps/s" % cfg["batch"], "ms_per_step": 1e3 * dt / args.steps,
                                             "global_batch": cfg["batch"], "per_gpu_batch": cfg["batch"]},
-            "elbo": elbo,
             "ms_per_step_without_event_timing": None if dt_plain is None else 1e3 * dt_plain / args.steps,
             "ms_per_step_two_in_flight": None if pipe is None else 1e3 * pipe[0] / args.steps,
             "steps_per_s_two_in_flight": None if pipe is None else args.steps / pipe[0],
@@ -804,7 +849,7 @@ def main():
             "train_steps_per_s": (1e3 / grad["train_step_ms_value_grad_adam"]) if grad.get("train_step_ms_value_grad_adam") else None,
             "train_steps_per_s_with_exact_layer0_dedup": (1e3 / grad["train_step_ms_with_exact_layer0_dedup"]) if grad.get("train_step_ms_with_exact_layer0_dedup") else None,
             "roofline_train": grad.get("roofline_train"),
-        }
+        })
         out.update(extra)
         # ---- roofline of the dominant kernel -------------------------------------------------------------------------
         rows0 = per_rank_batch if (args.dedup_layer0 and cfg["convs"]) else per_rank_batch * S

@@ -1529,7 +1529,7 @@ def test_two_gpu_bench_runs_rccl_and_matches_one_rank(ctx):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1")
 
     def line(gpus):
-        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(gpus), "--steps", "5", "--warmup", "2", "--no-cpu-baseline",
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(gpus), "--steps", "5", "--warmup", "2", "--full", "--no-cpu-baseline",
                             "--no-grad-leg", "--no-extra-legs"], cwd=root, env=env, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-3000:]
         return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

@@ -3,7 +3,7 @@
 CFG=$1; shift
 for T in "$@"; do
   if [ "$T" = main ]; then unset DCGP_LIB; else export DCGP_LIB=$PWD/deepcgp_amd/ab/libdcgp_$T.so; fi
-  python bench.py --config $CFG --steps 50 --no-cpu-baseline --no-grad-leg --no-extra-legs 2>/dev/null | python -c "
+  python bench.py --full --config $CFG --steps 50 --no-cpu-baseline --no-grad-leg --no-extra-legs 2>/dev/null | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

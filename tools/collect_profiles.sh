@@ -1,10 +1,11 @@
 #!/bin/bash
 # usage (GPU box, repo root): tools/collect_profiles.sh <tag>   -- every profile / bench artefact of a round into gpurun_out/<tag>_*
 # (copy what is to be judged into profiles/ afterwards)
+# the bench lines (1, 5, 7: python bench.py --full, every informational leg) go straight to profiles/<tag>_bench*.json, their stderr to the terminal
 T=$1
 R=$PWD; export TMPDIR=/tmp; mkdir -p gpurun_out
 # 1. the judged bench line (N = 1) and the same under rocprofv3 (per-kernel stats must agree with the in-bench HIP events)
-timeout 600 python bench.py > gpurun_out/${T}_bench.json 2> gpurun_out/${T}_bench.err
+timeout 600 python bench.py --full > profiles/${T}_bench.json
 # (1000 steps: the layer kernel's first ~30 launches of a process run up to 15 % long -- clock and cache warm-up -- and the CSV's average is over every launch)
 tools/prof_bench.sh ${T} --steps 1000 --warmup 20 > gpurun_out/${T}_profiled_run_summary.txt 2>&1
 cp gpurun_out/prof_${T}_kernel_stats.csv gpurun_out/${T}_kernel_stats.csv
@@ -34,14 +35,14 @@ DCGP_NO_FUSED_LAYER=1 tools/pmc_bench.sh ${T}w_cfg3_mnist_3layer_M256_unfused "W
 python tools/pmc_traffic.py ${T} > gpurun_out/${T}_pmc_traffic.json 2> gpurun_out/${T}_pmc_traffic.err
 # 5. the other BASELINE configurations
 for c in cfg1_mnist_H_M32 cfg2_mnist_H_M256 cfg3_mnist_3layer_M256 cfg4_cifar_3layer_M384 cfg5_mnist_H_M1024 cfg5_mnist_CH_M1024; do
-  timeout 300 python bench.py --config $c --steps 30 --no-cpu-baseline --no-grad-leg --no-extra-legs > gpurun_out/${T}_bench_$c.json 2> gpurun_out/${T}_bench_$c.err
+  timeout 300 python bench.py --full --config $c --steps 30 --no-cpu-baseline --no-grad-leg --no-extra-legs > profiles/${T}_bench_$c.json
 done
 # 6. the training step (forward + reverse pass), tiled and with the exact layer-0 de-duplication
 tools/prof_grad.sh ${T}g cfg2_mnist_CH_M256 20 > gpurun_out/${T}_grad_step_summary.txt 2>&1
 DCGP_DEDUP=1 tools/prof_grad.sh ${T}gd cfg2_mnist_CH_M256 20 > gpurun_out/${T}_grad_step_dedup_summary.txt 2>&1
 # 7. two ranks on this one GPU: self-launched and under the driver's launcher (RCCL refuses two ranks on one device -> host join)
-timeout 300 python bench.py --gpus 2 --steps 50 --no-cpu-baseline > gpurun_out/${T}_bench_2ranks_selflaunch.json 2> gpurun_out/${T}_bench_2ranks_selflaunch.err
-timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 50 --no-cpu-baseline > gpurun_out/${T}_bench_2ranks_torchrun.json 2> gpurun_out/${T}_bench_2ranks_torchrun.err
+timeout 300 python bench.py --full --gpus 2 --steps 50 --no-cpu-baseline > profiles/${T}_bench_2ranks_selflaunch.json
+timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 2 --steps 50 --no-cpu-baseline > profiles/${T}_bench_2ranks_torchrun.json
 # 8. the patch sweeps alone on the chip (every configuration), their per-workgroup traces, the store-bandwidth ceiling, real-data learning
 python tools/sweep_times.py > gpurun_out/${T}_sweep_times.txt 2>&1
 for c in "cfg2_mnist_CH_M256 kuf" "cfg4_cifar_3layer_M384 kuf" "cfg2_mnist_H_M256 head_sweep" "cfg2_mnist_CH_M256 head_sweep"; do python tools/sweep_trace.py $c; done > gpurun_out/${T}_sweep_trace.txt 2>&1
