@@ -184,6 +184,16 @@ int varexp_rows(dcgp_ctx* ctx, const double* mu, const double* var, const int32_
                 double eps, double* out_rows, int predict);
 const double* gauss_hermite_table(dcgp_ctx* ctx);   // [40]: 20 nodes then 20 weights (device)
 
+// evaluate.hip: the test-set evaluation tail.  eval_tail: one launch per batch of n images x S samples (head mean / var rows [S*n][K]):
+// per image at index lo + i of the whole set the log predictive density, the sample-mean probabilities (p_mean may be nullptr) and
+// ok = 1 / 0 (arg-max == label) or -1 (label outside [0, K)).  eval_sum: one launch behind the last batch, res[4] = {correct count,
+// sum of the log densities, first non-positive pivot of the status words in st, labels outside [0, K)}.
+constexpr int kEvalMaxSlots = 8192;   // S * K + K doubles of LDS per workgroup (64 KB)
+struct EvalStatus { const int* info[16]; int ninfo[16]; int ngroups = 0; };
+int eval_tail(dcgp_ctx* ctx, const double* mu, const double* var, const int32_t* y, int n, int S, int K, double eps, long lo,
+              double* logdens, double* p_mean, int* ok);
+int eval_sum(dcgp_ctx* ctx, const double* logdens, const int* ok, long n, const EvalStatus& st, double* res);
+
 // deterministic single-block sum of n doubles, scaled: out[0] = scale * sum
 int reduce_sum(dcgp_ctx* ctx, const double* in, long n, double scale, double* out);
 constexpr int REDUCE_JOBS_MAX = 12;

@@ -58,6 +58,7 @@ int ensure_events(dcgp_model* m) {
     HIP_TRY(ctx, hipEventCreateWithFlags(&m->ev_sweep[b], hipEventDisableTiming));
     HIP_TRY(ctx, hipEventCreateWithFlags(&m->ev_factor[b], hipEventDisableTiming));
     HIP_TRY(ctx, hipEventCreateWithFlags(&m->ev_kl[b], hipEventDisableTiming));
+    HIP_TRY(ctx, hipEventCreateWithFlags(&m->ev_eval[b], hipEventDisableTiming));
     for (auto& e : m->ev_prep[b]) HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
   }
   m->events_ok = true;
@@ -860,6 +861,92 @@ int dcgp_model_predict_y(dcgp_model* model, const double* X, int N, int S, const
   }
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return read_info(model, info_host);
+}
+
+}  // extern "C"
+
+namespace {
+// A test set in batches of `batch` images, enqueued back to back on the main stream: per batch forward_all (the parameter-only chain
+// only where factor_reuse does not let it stand) and ONE eval_tail launch; behind the last batch one eval_sum launch and one 32-byte
+// read-back -- the call's only stream synchronisation.
+//   Buffer reuse between batches: the head's mean / var (model->outs), the sweeps' scratch and d_kd are written by batch b + 1 on the
+//   main stream, behind batch b's tail; the Kdiag excursion to the auxiliary stream forks from the main stream at that point
+//   (layer_impl.h: ev_aux).  The chain of a batch (factor_reuse 0, or the first batch) writes the parameter-only state of its bank
+//   on its own stream: done_ev[bank] -- recorded on the main stream behind the tail of the last batch on that bank -- orders it.
+//   Workspaces: batch 0 is the largest, every later request is served by what it grew.
+int evaluate_impl(dcgp_model* model, const double* X, const int32_t* y, int N_total, int batch, int S, const double* const* zs,
+                  uint64_t seed, double* out_logdens, double* out_p_mean, double* out_host, int* info_host, const char* who) {
+  if (!model) return DCGP_ERR_ARG;
+  dcgp_ctx* ctx = model->ctx;
+  if (info_host) *info_host = 0;
+  if (!X || !y || N_total <= 0 || batch <= 0 || S <= 0 || !out_host)
+    return ctx_fail(ctx, DCGP_ERR_ARG, "%s: bad args (N %d, batch %d, S %d)", who, N_total, batch, S);
+  if (!model->has_head) return ctx_fail(ctx, DCGP_ERR_ARG, "model has no head layer");
+  const int nl = (int)model->layers.size();
+  const int K = model->layers[nl - 1]->R;
+  if (K < 2) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: the last layer has %d outputs, RobustMax needs >= 2", who, K);
+  if ((long)S * K + K > kEvalMaxSlots) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: S = %d samples of %d classes exceed the tail's LDS", who, S, K);
+  const LayerState& L0 = *model->layers[0];
+  const long in_len = (long)L0.v.H * L0.v.W * L0.v.C;   // one image of X
+  // the per-image results of the whole set: requested once, before batch 0
+  const std::string mp = "m" + std::to_string(model->id) + "_";
+  double* ld = out_logdens ? out_logdens : (double*)ws_get(ctx, mp + "eval_logdens", (size_t)N_total * sizeof(double));
+  int* ok = (int*)ws_get(ctx, mp + "eval_ok", (size_t)N_total * sizeof(int));
+  double* res = (double*)ws_get(ctx, mp + "eval_res", 4 * sizeof(double));
+  if (!ld || !ok || !res) return DCGP_ERR_ALLOC;
+  DCGP_TRY(ensure_events(model));
+  StreamGuard guard(ctx);
+  std::vector<const double*> zb(nl, nullptr);
+  const int nb = (N_total + batch - 1) / batch;
+  for (int b = 0; b < nb; ++b) {
+    const long lo = (long)b * batch;
+    const int n = (int)(N_total - lo < batch ? N_total - lo : batch);
+    // noise: per layer the batches' [S][n_b][D_l] tables back to back, batch b's from S * lo * D_l on
+    for (int l = 0; l < nl && zs; ++l) {
+      const LayerState& L = *model->layers[l];
+      const long D = L.is_head ? L.R : (long)L.v.P * L.R;
+      zb[l] = zs[l] ? zs[l] + (long)S * lo * D : nullptr;
+    }
+    int rows = 0;
+    DCGP_TRY(forward_all(model, X + lo * in_len, n, S, zs ? zb.data() : nullptr, seed + (uint64_t)b, 0, false, false, &rows));
+    const auto& o = model->outs[nl - 1];
+    if (rows != S * n || o.width != K) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: head rows %d x %d, expected %d x %d", who, rows, o.width, S * n, K);
+    DCGP_TRY(eval_tail(ctx, o.mean, o.var, y + lo, n, S, K, model->eps, lo, ld, out_p_mean, ok));
+    HIP_TRY(ctx, hipEventRecord(model->ev_eval[model->bank], ctx->stream));
+    DCGP_TRY(forward_done(model, model->ev_eval[model->bank]));
+  }
+  EvalStatus st;   // the status words of the factorisations the batches used (with factor reuse: the chain of an earlier call)
+  auto& groups = model->groups[model->bank];
+  if (groups.size() > 16) return ctx_fail(ctx, DCGP_ERR_ARG, "model: too many factor groups");
+  st.ngroups = (int)groups.size();
+  for (int q = 0; q < st.ngroups; ++q) { st.info[q] = groups[q].d_info; st.ninfo[q] = (int)groups[q].K.size(); }
+  DCGP_TRY(eval_sum(ctx, ld, ok, N_total, st, res));
+  double h[4];
+  HIP_TRY(ctx, hipMemcpyAsync(h, res, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  if (h[3] > 0) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: %d labels outside [0, %d)", who, (int)h[3], K);
+  const int bad = (int)h[2];
+  if (info_host) *info_host = bad;
+  if (bad) return ctx_fail(ctx, DCGP_ERR_NOT_PD, "Cholesky: matrix not positive definite at column %d", bad);
+  out_host[0] = h[0];
+  out_host[1] = h[1];
+  return DCGP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int dcgp_model_predict_density(dcgp_model* model, const double* X, const int32_t* y, int N, int S,
+                               const double* const* z_per_layer, uint64_t seed, double* out_logdens, int* info_host) {
+  if (model && !out_logdens) return ctx_fail(model->ctx, DCGP_ERR_ARG, "predict_density: out_logdens is NULL");
+  double sums[2];
+  return evaluate_impl(model, X, y, N, N, S, z_per_layer, seed, out_logdens, nullptr, sums, info_host, "predict_density");
+}
+
+int dcgp_model_evaluate(dcgp_model* model, const double* X, const int32_t* y, int N_total, int batch, int S,
+                        const double* const* z_per_layer, uint64_t seed, double* out_logdens, double* out_p_mean,
+                        double* out_host, int* info_host) {
+  return evaluate_impl(model, X, y, N_total, batch, S, z_per_layer, seed, out_logdens, out_p_mean, out_host, info_host, "evaluate");
 }
 
 int dcgp_model_layer_output(dcgp_model* model, int layer, double* out_sample, double* out_mean, double* out_var,

@@ -28,6 +28,7 @@ struct dcgp_model {
   int bank = 0;                                  // bank of the most recent forward
   hipEvent_t ev_sweep[2] = {}, ev_factor[2] = {}, ev_kl[2] = {}, ev_prep[2][8] = {};
   hipEvent_t done_ev[2] = {};                    // not owned: the event that marks the end of the last step on the bank (a result-ring event)
+  hipEvent_t ev_eval[2] = {};                    // per bank: the end of a dcgp_model_evaluate batch (its done_ev while the call enqueues)
   bool done_valid[2] = {false, false};
   bool events_ok = false;
   // the KL pieces computed inside the tail launch (layers whose sums prep_solve left behind): per bank, set by forward_all
@@ -67,6 +68,7 @@ struct dcgp_model {
       if (ev_sweep[b]) hipEventDestroy(ev_sweep[b]);
       if (ev_factor[b]) hipEventDestroy(ev_factor[b]);
       if (ev_kl[b]) hipEventDestroy(ev_kl[b]);
+      if (ev_eval[b]) hipEventDestroy(ev_eval[b]);
       for (auto& e : ev_prep[b]) if (e) hipEventDestroy(e);
     }
     for (auto& o : outs) { hipFree(o.sample); hipFree(o.mean); hipFree(o.var); }

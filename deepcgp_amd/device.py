@@ -104,6 +104,8 @@ _SIGS = {
     "dcgp_model_chain_skips": [_vp, C.POINTER(_u64)],
     "dcgp_model_natgrad_step": [_vp, _d, _ip],
     "dcgp_model_predict_y": [_vp, _vp, _i, _i, C.POINTER(_vp), _u64, _vp, _vp, _ip],
+    "dcgp_model_predict_density": [_vp, _vp, _vp, _i, _i, C.POINTER(_vp), _u64, _vp, _ip],
+    "dcgp_model_evaluate": [_vp, _vp, _vp, _i, _i, _i, C.POINTER(_vp), _u64, _vp, _vp, _dp, _ip],
     "dcgp_model_layer_output": [_vp, _i, _vp, _vp, _vp, _ip, _ip],
     "dcgp_gemm_strided": [_vp, _vp, C.c_long, C.c_long, C.c_long, _vp, C.c_long, C.c_long, C.c_long, _vp, C.c_long, C.c_long,
                           _i, _i, _i, _i, _d, _i, _vp, C.c_long, C.c_long, _vp, C.c_long, C.c_long, _i],

@@ -1,6 +1,7 @@
 """DGP_Base -- the model-level counterpart of doubly_stochastic_dgp.dgp.DGP_Base as the reference uses
 it (/root/reference/conv_gp/models.py:65-70, conv_gp/utils/tensorboard.py:22-35, conv_gp/utils/log.py:62):
-``propagate``, ``predict_y``, ``compute_log_likelihood`` and ``parameters``.  The whole forward ELBO of a
+``propagate``, ``predict_y``, ``compute_log_likelihood`` and ``parameters``, plus DS-DGP's other prediction methods
+(``predict_f``, ``predict_all_layers``, ``predict_density``) and a one-call test-set ``evaluate``.  The whole forward ELBO of a
 minibatch is ONE call into the HIP library (``dcgp_elbo_forward``); parameters live on the device and
 are pushed when changed (``sync_parameters``)."""
 import ctypes as C
@@ -10,6 +11,23 @@ import numpy as np
 from . import device as dev
 from .kernels import JITTER
 from .layers import ConvLayer, SVGP_Layer
+
+
+def batched_noise(zs, N, S, batch_size, dims=None):
+    """Explicit noise of a whole set, per layer ``[S, N, D]`` (indexed by image, as ``dist.shard_batch`` slices it), in the layout
+    ``dcgp_model_evaluate`` reads: per layer the batches' ``[S, n_b, D]`` tables back to back, batch b = images
+    ``[b * batch_size, min((b + 1) * batch_size, N))``.  ``dims``: the layers' D (a table of another size raises).  Returns one
+    flat array (or None) per layer."""
+    if zs is None:
+        return None
+    out = []
+    for i, z in enumerate(zs):
+        if z is None:
+            out.append(None)
+            continue
+        z = np.reshape(z, (S, N, -1 if dims is None else dims[i]))
+        out.append(np.concatenate([z[:, lo:lo + batch_size].reshape(-1) for lo in range(0, N, batch_size)]) if N else np.zeros(0))
+    return out
 
 
 class Parameter:
@@ -453,6 +471,78 @@ class DGP_Base:
         if np.shape(X)[0] == 0:
             return np.zeros((0, self.layers[-1].num_outputs))
         return self._predict(X, S, zs, seed, False, True)[1]
+
+    def predict_f(self, X, S, zs=None, seed=0):
+        """(Fmean, Fvar) of the last layer, each S x N x num_classes (doubly_stochastic_dgp DGP_Base.predict_f)."""
+        _, Fmeans, Fvars = self.propagate(X, S=S, zs=zs, seed=seed)
+        return Fmeans[-1], Fvars[-1]
+
+    def predict_all_layers(self, X, S, zs=None, seed=0):
+        """(Fs, Fmeans, Fvars) of every layer (doubly_stochastic_dgp DGP_Base.predict_all_layers): what ``propagate`` returns."""
+        return self.propagate(X, S=S, zs=zs, seed=seed)
+
+    def _out_dims(self):
+        return [l.num_outputs for l in self.layers]
+
+    def _eval_call(self, X, Y, S, batch_size, seed, flat_zs, want_p_mean, density_only=False):
+        self._build()
+        ctx, L = self._ctx, dev.lib()
+        X = np.ascontiguousarray(np.reshape(X, (np.shape(X)[0], -1)), np.float64)
+        N, K = X.shape[0], self.layers[-1].num_outputs
+        Y = np.ascontiguousarray(np.reshape(Y, (-1,)), np.int32)
+        if X.shape[1] != self.X.shape[1]:
+            raise ValueError("images of %d values, the model takes %d" % (X.shape[1], self.X.shape[1]))
+        if Y.size != N:
+            raise ValueError("%d labels for %d images" % (Y.size, N))
+        dX, dY = ctx.to_device(X), ctx.to_device(Y, np.int32)     # the whole set crosses the bus once
+        arr, keep = None, []
+        if flat_zs is not None:
+            arr = (C.c_void_p * len(self.layers))()
+            for i, z in enumerate(flat_zs):
+                if z is not None:
+                    keep.append(ctx.to_device(z))
+                    arr[i] = keep[-1].ptr
+        ld = ctx.empty((N,))
+        pm = ctx.empty((N, K)) if want_p_mean else None
+        info = C.c_int(0)
+        if density_only:
+            rc = L.dcgp_model_predict_density(self._model, dX.ptr, dY.ptr, N, int(S), arr, int(seed), ld.ptr, C.byref(info))
+            ctx._check(rc, info)
+            return ld.numpy(), None, None
+        out = (C.c_double * 2)()
+        rc = L.dcgp_model_evaluate(self._model, dX.ptr, dY.ptr, N, int(batch_size), int(S), arr, int(seed), ld.ptr,
+                                   pm.ptr if pm else None, out, C.byref(info))
+        ctx._check(rc, info)
+        return ld.numpy(), (pm.numpy() if pm else None), (out[0], out[1])
+
+    def predict_density(self, X, Y, S, zs=None, seed=0):
+        """Log predictive density of each label, N x 1: logsumexp_s log p(y | f_s) - log S (doubly_stochastic_dgp
+        DGP_Base.predict_density with the RobustMax likelihood).  One device call; ``zs`` per layer [S, N, D]."""
+        N = np.shape(X)[0]
+        if N == 0:
+            return np.zeros((0, 1))
+        ld, _, _ = self._eval_call(X, Y, S, N, seed, batched_noise(zs, N, S, N, self._out_dims()), False, density_only=True)
+        return ld.reshape(N, 1)
+
+    def evaluate(self, X, Y, S=5, batch_size=32, seed=0, zs=None, per_image=False):
+        """A whole test set in one device call (dcgp_model_evaluate): batches of ``batch_size`` images, batch i drawing its noise
+        from ``seed + i`` as ``AccuracyLogger`` does, or from ``zs`` (per layer [S, N, D], indexed by image over the whole set).
+        Returns {"accuracy", "mean_log_density", "n"}, with ``per_image`` also "log_density" [N] and "p_mean" [N, K] (the
+        sample-mean class probabilities).  Rank-local: nothing is reduced across ranks."""
+        N = np.shape(X)[0]
+        if int(batch_size) <= 0:
+            raise ValueError("batch_size must be positive, got %r" % (batch_size,))
+        if N == 0:
+            out = {"accuracy": 0.0, "mean_log_density": float("nan"), "n": 0}
+            if per_image:
+                out["log_density"], out["p_mean"] = np.zeros(0), np.zeros((0, self.layers[-1].num_outputs))
+            return out
+        ld, pm, (correct, total) = self._eval_call(X, Y, S, batch_size, seed, batched_noise(zs, N, S, int(batch_size), self._out_dims()),
+                                                 per_image)
+        out = {"accuracy": correct / N, "mean_log_density": total / N, "n": N}
+        if per_image:
+            out["log_density"], out["p_mean"] = ld, pm
+        return out
 
     def KL(self):
         return float(sum(l.KL() for l in self.layers))

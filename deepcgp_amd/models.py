@@ -155,6 +155,42 @@ class AccuracyLogger(object):
         return correct / max(self.Y_test.size, 1)
 
 
+class TestLogDensityLogger(object):
+    """Mean test log predictive density with AccuracyLogger's batching (32 images, five samples, batch i drawing from seed + i):
+    ``DGP_Base.evaluate``, the whole set in one device call."""
+    title = 'test_log_likelihood'
+    __test__ = False   # (not a pytest class despite the name)
+
+    def __init__(self, X_test, Y_test, batch_size=32, num_samples=5):
+        self.X_test, self.Y_test = X_test, np.reshape(Y_test, (-1,))
+        self.batch_size, self.num_samples = int(batch_size), int(num_samples)
+
+    def __call__(self, model, seed=0):
+        return model.evaluate(self.X_test, self.Y_test, S=self.num_samples, batch_size=self.batch_size, seed=seed)["mean_log_density"]
+
+
+class LogLikelihoodLogger(object):
+    """The reference's ``train_log_likelihood`` column (conv_gp/utils/tensorboard.py:15-42): the ELBO of batches of 64 of the training
+    set, ceil(min(5000, n) / 64) of them from row 0 on, summed and divided by batches * 64 (the reference's divisor, also for a short
+    last batch).  Batch i draws its noise from seed + i; up to four batches are kept in flight (``enqueue_log_likelihood``)."""
+    title = 'train_log_likelihood'
+    batch_size = 64
+    in_flight = 4      # dcgp_model::RING
+
+    def __call__(self, model, seed=0):
+        compute_on = min(5000, model.X.shape[0])
+        batches = -(-compute_on // self.batch_size)
+        total, tickets = 0.0, []
+        for i in range(batches):
+            sl = slice(i * self.batch_size, (i + 1) * self.batch_size)     # the reference's slices of model.X / model.Y
+            if len(tickets) == self.in_flight:
+                total += model.collect_log_likelihood(tickets.pop(0))
+            tickets.append(model.enqueue_log_likelihood(model.X[sl], model.Y[sl], seed=seed + i))
+        for t in tickets:
+            total += model.collect_log_likelihood(t)
+        return total / (batches * self.batch_size)
+
+
 def identity_conv(NHWC_X, filter_size, feature_maps_in, feature_maps_out, stride, count=1000):
     """Propagate random images through IdentityConv2dMean to initialise the next layer
     (conv_gp/models.py:29-33, conv_gp/mean_functions.py:6-26)."""

@@ -288,6 +288,22 @@ int dcgp_model_propagate(dcgp_model* model, const double* X, int N, int S,
 int dcgp_model_predict_y(dcgp_model* model, const double* X, int N, int S,
                          const double* const* z_per_layer_host, uint64_t seed,
                          double* out_p, double* out_p_mean, int* info_host);
+/* DS-DGP DGP_Base.predict_density(X, Y, S): per image logsumexp_s log p(y | f_s) - log S, RobustMax likelihood. out_logdens [N], device.
+ * The class probabilities are dcgp_model_predict_y's; y [N] int32 in [0, K) (device), else DCGP_ERR_ARG.                              */
+int dcgp_model_predict_density(dcgp_model* model, const double* X, const int32_t* y, int N, int S,
+                               const double* const* z_per_layer, uint64_t seed, double* out_logdens, int* info_host);
+/* A whole test set in batches of `batch` images, enqueued back to back, ONE stream synchronisation per call -- the loops of the reference's
+ * AccuracyLogger (conv_gp/utils/log.py:50-67) and of a test log density over DS-DGP DGP_Base.predict_density, one device call.
+ * Batch b = images [b*batch, min((b+1)*batch, N_total)), noise from seed + b (AccuracyLogger's convention), or from
+ * z_per_layer: per layer one device buffer holding the batches' [S][n_b][D] tables back to back.
+ * out_logdens [N_total], out_p_mean [N_total][K]: device, either may be NULL. out_host[2] = {correct count, sum of logdens}.
+ * "Correct": the first arg-max of the sample-mean probabilities (bit-identical to predict_y's out_p_mean) equals the label.
+ * Factor reuse (dcgp_model_set_factor_reuse) as for predict_y: in modes 1 and 2 the parameter-only chain runs at most once per call.
+ * Rank-local: with a communicator attached nothing is reduced across ranks; each rank evaluates the images it is given.
+ * Labels outside [0, K) are DCGP_ERR_ARG (checked on the device, reported after the sync), so are batch <= 0 and K < 2.            */
+int dcgp_model_evaluate(dcgp_model* model, const double* X, const int32_t* y, int N_total, int batch, int S,
+                        const double* const* z_per_layer, uint64_t seed, double* out_logdens, double* out_p_mean,
+                        double* out_host, int* info_host);
 /* Parameter-only state across steps.  The reference's evaluation loops run hundreds of batches at ONE parameter state (AccuracyLogger /
  * LogLikelihoodLogger, conv_gp/utils/log.py:55-68; conv_gp/utils/tensorboard.py:22-42), and every session.run of them factors every Kuu again.
  * Here a step records the parameter version its chain (operand preparation, factorisations, inverses, G / alpha, KL pieces) ran at; every call that writes
