@@ -1,6 +1,7 @@
 // ops.hip -- single-operator C-ABI entry points (the Level-1 Python classes call these one by one;
 // the model-level path in model.hip strings the same building blocks together without host round trips).
 #include "layer_impl.h"
+#include "gemm_gen.h"
 
 namespace {
 
@@ -33,6 +34,20 @@ __global__ void finalize_api_kernel(const double* __restrict__ s1p, int nrb1, co
   out_mean[((long)n * P + p) * R + r] = mu[(long)r * ldk + j];
 }
 
+// out_var[b][n][n'][r] = (Kff[b][n][n'] - S1[b][n][n']) + S2[b][r][n][n']   (S2 == nullptr: no q_sqrt term)
+__global__ void full_cov_assemble_kernel(const double* __restrict__ Kff, const double* __restrict__ S1, const double* __restrict__ S2,
+                                         int B, int N, int R, double* __restrict__ out_var) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long NN = (long)N * N;
+  if (idx >= (long)B * NN * R) return;
+  const int r = (int)(idx % R);
+  const long e = idx / R;   // b * NN + n * N + n'
+  const long b = e / NN, nn = e % NN;
+  double v = Kff[e] - S1[e];
+  if (S2) v += S2[(b * R + r) * NN + nn];
+  out_var[idx] = v;
+}
+
 __global__ void additive_kdiag_kernel(int N, int P, double variance, const double* __restrict__ w, double* __restrict__ out) {
   __shared__ double s;
   if (threadIdx.x == 0) {
@@ -51,8 +66,10 @@ struct TmpGp {
   ~TmpGp() { fg.release(); }
 };
 
+// d_info_deferred != nullptr: no synchronisation here -- the factorisation's info word stays on the device (*d_info_deferred) for the
+// caller to read behind its own work (a factor that failed leaves NaNs or garbage in what follows, which the caller then discards)
 int tmp_gp_build(dcgp_ctx* ctx, TmpGp& t, const std::string& pfx, int M, int R, const double* Kmm, const double* q_mu,
-                 const double* q_sqrt, int* info_host, int prep_white = -1) {
+                 const double* q_sqrt, int* info_host, int prep_white = -1, int** d_info_deferred = nullptr) {
   const int Mp = round_up(M, 16);
   const size_t mm = (size_t)Mp * Mp;
   GpMats& g = t.g;
@@ -72,11 +89,15 @@ int tmp_gp_build(dcgp_ctx* ctx, TmpGp& t, const std::string& pfx, int M, int R, 
     t.fg.Mp = Mp;
     t.fg.K = {g.K}; t.fg.Linv = {g.Linv}; t.fg.LinvT = {g.LinvT};
     DCGP_TRY(t.fg.run(ctx));
-    int info = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&info, t.fg.d_info, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (info_host) *info_host = info;
-    if (info) return ctx_fail(ctx, DCGP_ERR_NOT_PD, "Cholesky: matrix not positive definite at column %d", info);
+    if (d_info_deferred) {
+      *d_info_deferred = t.fg.d_info;
+    } else {
+      int info = 0;
+      HIP_TRY(ctx, hipMemcpyAsync(&info, t.fg.d_info, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+      if (info_host) *info_host = info;
+      if (info) return ctx_fail(ctx, DCGP_ERR_NOT_PD, "Cholesky: matrix not positive definite at column %d", info);
+    }
     if (prep_white == 1) { g.G = g.Lq; g.alpha = g.qmu; }
     if (prep_white >= 0) DCGP_TRY(cond_prep(ctx, g, prep_white, q_sqrt != nullptr));
   }
@@ -274,6 +295,72 @@ int dcgp_svgp_conditional(dcgp_ctx* ctx, const double* Kuf, const double* Ku, co
   fa.out_mean = out_mean; fa.out_var = out_var;
   DCGP_TRY(finalize_layer(ctx, fa));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return DCGP_OK;
+}
+
+// SVGP_Layer.conditional_ND(full_cov=True) for B independent input sets against one q(u).  With A1 = inv(L) Kuf_b, G_r = inv(L) Lq_r
+// and alpha = inv(L) q_mu (cond_prep; G = Lq, alpha = q_mu whitened) the DS-DGP form reads
+//   mean_b = A1^T alpha,   var_{b,r} = (Kff_b - A1^T A1) + T_{b,r}^T T_{b,r},   T_{b,r} = G_r^T A1 (= Lq_r^T A, A = A1 or inv(L)^T A1):
+// batched device GEMMs -- A1, the mean, A1^T A1, then T_{b,r} one launch per r (G_r differs by r, the batch runs over b) and all
+// T^T T in one: 3 + R + 1 launches with q_sqrt -- and one assembling launch; the factorisation's info word is read behind them (one synchronisation).
+int dcgp_svgp_conditional_full_cov(dcgp_ctx* ctx, const double* Kuf, const double* Ku, const double* Kff, const double* q_mu,
+                                   const double* q_sqrt, int white, int B, int M, int N, int R, double* out_mean, double* out_var,
+                                   int* info_host) {
+  ARG_CHECK(ctx && Kuf && Ku && Kff && q_mu && out_mean && out_var && B > 0 && M > 0 && N > 0 && R > 0, "svgp_conditional_full_cov: bad args");
+  ARG_CHECK((long)B * R <= 65535, "svgp_conditional_full_cov: B * R too large");
+  if (info_host) *info_host = 0;
+  TmpGp t;
+  int* d_info = nullptr;
+  DCGP_TRY(tmp_gp_build(ctx, t, "op_svgpf_", M, R, Ku, q_mu, q_sqrt, info_host, white ? 1 : 0, &d_info));
+  const int Mp = t.g.Mp;
+  const long MN = (long)M * N, NN = (long)N * N;
+  double* A1 = (double*)ws_get(ctx, "op_svgpf_A1", (size_t)B * MN * sizeof(double));
+  double* S1 = (double*)ws_get(ctx, "op_svgpf_S1", (size_t)B * NN * sizeof(double));
+  double* T = q_sqrt ? (double*)ws_get(ctx, "op_svgpf_T", (size_t)B * R * MN * sizeof(double)) : nullptr;
+  double* S2 = q_sqrt ? (double*)ws_get(ctx, "op_svgpf_S2", (size_t)B * R * NN * sizeof(double)) : nullptr;
+  if (!A1 || !S1 || (q_sqrt && (!T || !S2))) return DCGP_ERR_ALLOC;
+  GenGemm g;   // A1_b = inv(L) Kuf_b
+  g.A = t.g.Linv; g.a_rs = Mp; g.a_cs = 1; g.a_bs = 0;
+  g.B = Kuf; g.b_rs = N; g.b_cs = 1; g.b_bs = MN;
+  g.C = A1; g.c_rs = N; g.c_bs = MN;
+  g.M = M; g.N = N; g.K = M; g.batch = B;
+  DCGP_TRY(gemm_gen(ctx, g));
+  g = GenGemm();   // mean_b = A1_b^T alpha  [N][R]
+  g.A = A1; g.a_rs = 1; g.a_cs = N; g.a_bs = MN;
+  g.B = t.g.alpha; g.b_rs = t.g.Rp; g.b_cs = 1; g.b_bs = 0;
+  g.C = out_mean; g.c_rs = R; g.c_bs = (long)N * R;
+  g.M = N; g.N = R; g.K = M; g.batch = B;
+  DCGP_TRY(gemm_gen(ctx, g));
+  g = GenGemm();   // S1_b = A1_b^T A1_b
+  g.A = A1; g.a_rs = 1; g.a_cs = N; g.a_bs = MN;
+  g.B = A1; g.b_rs = N; g.b_cs = 1; g.b_bs = MN;
+  g.C = S1; g.c_rs = N; g.c_bs = NN;
+  g.M = N; g.N = N; g.K = M; g.batch = B;
+  DCGP_TRY(gemm_gen(ctx, g));
+  if (q_sqrt) {
+    for (int r = 0; r < R; ++r) {   // T_{b,r} = G_r^T A1_b  ([b][r][M][N])
+      g = GenGemm();
+      g.A = t.g.G + (long)r * Mp * Mp; g.a_rs = 1; g.a_cs = Mp; g.a_bs = 0;
+      g.B = A1; g.b_rs = N; g.b_cs = 1; g.b_bs = MN;
+      g.C = T + (long)r * MN; g.c_rs = N; g.c_bs = (long)R * MN;
+      g.M = M; g.N = N; g.K = M; g.batch = B;
+      DCGP_TRY(gemm_gen(ctx, g));
+    }
+    g = GenGemm();   // S2_{b,r} = T_{b,r}^T T_{b,r}
+    g.A = T; g.a_rs = 1; g.a_cs = N; g.a_bs = MN;
+    g.B = T; g.b_rs = N; g.b_cs = 1; g.b_bs = MN;
+    g.C = S2; g.c_rs = N; g.c_bs = NN;
+    g.M = N; g.N = N; g.K = M; g.batch = B * R;
+    DCGP_TRY(gemm_gen(ctx, g));
+  }
+  const long tot = (long)B * NN * R;
+  hipLaunchKernelGGL(full_cov_assemble_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream, Kff, S1, S2, B, N, R, out_var);
+  LAUNCH_CHECK(ctx);
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->h_info, d_info, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  const int info = ctx->h_info[0];
+  if (info_host) *info_host = info;
+  if (info) return ctx_fail(ctx, DCGP_ERR_NOT_PD, "Cholesky: matrix not positive definite at column %d", info);
   return DCGP_OK;
 }
 

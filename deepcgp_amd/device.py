@@ -73,6 +73,9 @@ _SIGS = {
     "dcgp_convkernel_kdiag": [_vp, _vp, _i, _i, _i, _i, _i, _i, _d, _d, _vp, _vp],
     "dcgp_additive_kdiag": [_vp, _i, _i, _d, _vp, _vp],
     "dcgp_svgp_conditional": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _ip],
+    "dcgp_convkernel_k": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _d, _d, _vp, _i, _vp],
+    "dcgp_svgp_conditional_full_cov": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _ip],
+    "dcgp_reparam_full_cov": [_vp, _vp, _vp, _vp, _i, _i, _i, _d, _vp, _ip],
     "dcgp_gauss_kl": [_vp, _vp, _vp, _vp, _i, _i, _dp, _ip],
     "dcgp_robustmax_varexp": [_vp, _vp, _vp, _vp, _i, _i, _d, _vp],
     "dcgp_robustmax_predict": [_vp, _vp, _vp, _i, _i, _d, _vp],

@@ -414,9 +414,10 @@ class DGP_Base:
                 l.kern.patch_weights = pull(li, "w", np.shape(l.kern.patch_weights))
 
     def propagate(self, X, full_cov=False, S=1, zs=None, seed=0):
-        """(Fs, Fmeans, Fvars): per layer S x N x D_l arrays (doubly_stochastic_dgp DGP_Base.propagate)."""
+        """(Fs, Fmeans, Fvars): per layer S x N x D_l arrays (doubly_stochastic_dgp DGP_Base.propagate); full_cov=True: see
+        ``_propagate_full_cov`` (Fvars S x N x N x D_l)."""
         if full_cov:
-            raise NotImplementedError("full_cov=True is outside the accelerated hot path")
+            return self._propagate_full_cov(X, S, zs, seed)
         self._build()
         ctx, L = self._ctx, dev.lib()
         X = np.ascontiguousarray(np.reshape(X, (np.shape(X)[0], -1)), np.float64)
@@ -440,6 +441,58 @@ class DGP_Base:
         finally:
             L.dcgp_model_set_keep_outputs(self._model, 0)
         return Fs, Fm, Fv
+
+    def _propagate_full_cov(self, X, S, zs, seed):
+        """DGP_Base.propagate(full_cov=True): every layer's conditional with full N x N covariances over the inputs, sampled with
+        mean + chol(var + jitter I) z.  The parameters are first pulled from the device model, so the result describes what it holds.
+        Hidden conv layers run their full-cov conditional (layer 0 once, tiled over the S identical copies of X); the head runs
+        the image-pair K and the batched conditional, one call each for all S samples; the samples come from one
+        dcgp_reparam_full_cov launch per layer.  Noise: ``zs[l]`` [S, N, D_l] where given, else np.random.default_rng(seed) --
+        these draws cannot match the on-device draws the mean-field path makes for the same seed.  Rank-local."""
+        self.pull_parameters()
+        from .layers import reparameterize_full_cov
+        X = np.asarray(X, np.float64)
+        X = np.ascontiguousarray(X.reshape(X.shape[0], int(np.prod(X.shape[1:]))))
+        N, S = X.shape[0], int(S)
+        rng = np.random.default_rng(seed)
+        Fs, Fmeans, Fvars = [], [], []
+        F = np.tile(X[None], [S, 1, 1])
+        nl = len(self.layers)
+        for li, layer in enumerate(self.layers):
+            D = layer.num_outputs
+            if N == 0:
+                F = np.zeros((S, 0, D))
+                Fs.append(F), Fmeans.append(np.zeros((S, 0, D))), Fvars.append(np.zeros((S, 0, 0, D)))
+                continue
+            head = li == nl - 1
+            if li == 0:   # S identical copies of X
+                if head:
+                    m, v = layer._conditional_full_cov(X[None])
+                    m, v = m[0], v[0]
+                else:
+                    m, v = layer.conditional_ND(X, full_cov=True)
+                mean, var = np.tile(m[None], [S, 1, 1]), np.tile(v[None], [S, 1, 1, 1])
+            elif head:
+                mean, var = layer._conditional_full_cov(F)
+            else:
+                mv = [layer.conditional_ND(F[s_], full_cov=True) for s_ in range(S)]
+                mean, var = np.stack([m for m, _ in mv]), np.stack([v for _, v in mv])
+            z = zs[li] if zs is not None and zs[li] is not None else None
+            z = rng.standard_normal((S, N, D)) if z is None else np.reshape(np.asarray(z, np.float64), (S, N, D))
+            F = reparameterize_full_cov(mean, var, z)
+            Fs.append(F), Fmeans.append(mean), Fvars.append(var)
+        return Fs, Fmeans, Fvars
+
+    def predict_f_full_cov(self, X, S, zs=None, seed=0):
+        """(Fmean S x N x num_classes, Fvar S x N x N x num_classes) of the last layer (doubly_stochastic_dgp
+        DGP_Base.predict_f_full_cov); noise as in ``propagate(full_cov=True)``.  Rank-local."""
+        _, Fmeans, Fvars = self._propagate_full_cov(X, S, zs, seed)
+        return Fmeans[-1], Fvars[-1]
+
+    def predict_all_layers_full_cov(self, X, S, zs=None, seed=0):
+        """(Fs, Fmeans, Fvars) of every layer with full covariances (doubly_stochastic_dgp DGP_Base.predict_all_layers_full_cov):
+        what ``propagate(full_cov=True)`` returns.  Rank-local."""
+        return self._propagate_full_cov(X, S, zs, seed)
 
     def _predict(self, X, S, zs, seed, want_samples, want_mean):
         self._build()

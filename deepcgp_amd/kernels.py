@@ -121,8 +121,8 @@ class ArcCosine:
 
 
 class AdditivePatchKernel:
-    """K(x, x') = mean_i w_i k(x[i], x'[i]) (conv_gp/kernels.py:15-77); Kzx / Kdiag / Kzz only --
-    the full K() of the reference is off the training path."""
+    """K(x, x') = mean_i w_i k(x[i], x'[i]) (conv_gp/kernels.py:15-77).  Kzx / Kdiag / Kzz serve the training path; the full
+    ``K`` (prediction with full covariances) runs on the image-pair kernel of csrc/head_full.hip."""
 
     kernel_type = 1
 
@@ -173,11 +173,46 @@ class AdditivePatchKernel:
     def Kzz(self, Z):
         return self.base_kernel.K(Z)
 
+    def K(self, ND_X, X2=None):
+        """N x N2 covariance (conv_gp/kernels.py:34-51): K[n, n'] = (1/P) sum_p w_p k(x_{n,p}, x2_{n',p}).  X2 is reshaped like X,
+        which is what the reference evidently intends: its :40 names an undefined ``patches`` where X2 is None."""
+        X = self._reshape_X(ND_X)
+        X2 = None if X2 is None else self._reshape_X(X2)
+        return self._K_batched(X[None], None if X2 is None else X2[None])[0]
+
+    def _K_batched(self, X, X2=None):
+        """K of B independent image sets in one launch (dcgp_convkernel_k): X [B, N, H, W, C], X2 [B, N2, H, W, C] or None
+        (then symmetric: K[b] == K[b].T bit for bit) -> [B, N, N2].  RBF base kernel only (the heads of conv_gp/models.py:178-185)."""
+        bk = self.base_kernel
+        if not isinstance(bk, RBF) or bk.ARD:
+            raise NotImplementedError("the full K of a patch kernel needs a scalar-lengthscale RBF base kernel")
+        X = np.ascontiguousarray(X, np.float64)
+        B, N, H, W, Cc = X.shape
+        if X2 is not None:
+            X2 = np.ascontiguousarray(X2, np.float64)
+            if X2.shape[0] != B or X2.shape[2:] != X.shape[2:]:
+                raise ValueError("X2 of shape %s does not match X of shape %s" % (X2.shape, X.shape))
+        N2 = N if X2 is None else X2.shape[1]
+        if B == 0 or N == 0 or N2 == 0:
+            return np.zeros((B, N, N2))
+        ctx = dev.get_context()
+        dX, dw, out = ctx.to_device(X), ctx.to_device(self.patch_weights), ctx.empty((B, N, N2))
+        dX2 = ctx.to_device(X2) if X2 is not None else None
+        ctx._check(dev.lib().dcgp_convkernel_k(ctx.handle, dX.ptr, dX2.ptr if dX2 else None, B, N, N2, H, W, Cc, self.view.filter_size,
+                                               self.view.stride, bk.variance, bk.lengthscales, dw.ptr, int(self.kernel_type == 1), out.ptr))
+        return out.numpy()
+
 
 class ConvKernel(AdditivePatchKernel):
     """Weighted convolutional kernel of the classification head (conv_gp/kernels.py:79-136)."""
 
     kernel_type = 0
+
+    def K(self, ND_X, X2=None):
+        """N x N2 covariance (conv_gp/kernels.py:81-104): K[n, n'] = (1/P^2) sum_{p,p'} w_p w_p' k(x_{n,p}, x2_{n',p'}), without
+        ever forming the NP x N2P patch Gram.  X2 is reshaped like X, which is what the reference evidently intends: its :90
+        extracts patches from X2 without that reshape."""
+        return AdditivePatchKernel.K(self, ND_X, X2)
 
     def Kdiag(self, ND_X):
         ctx = dev.get_context()

@@ -53,6 +53,23 @@ def reparameterize(mean, var, z, full_cov=False):
     return out.numpy()
 
 
+def reparameterize_full_cov(mean, var, z):
+    """reparameterize(mean, var, z, full_cov=True) for all S x D matrices in one launch (dcgp_reparam_full_cov): mean, z S x N x D,
+    var S x N x N x D.  N > 128 (a factor no longer fits one workgroup's LDS) takes the host loop of ``reparameterize``."""
+    mean, var, z = (np.ascontiguousarray(a, np.float64) for a in (mean, var, z))
+    S, N, D = mean.shape
+    if var.shape != (S, N, N, D) or z.shape != (S, N, D):
+        raise ValueError("expected var %s and z %s, got %s and %s" % ((S, N, N, D), (S, N, D), var.shape, z.shape))
+    if S == 0 or N == 0 or D == 0:
+        return mean.copy()
+    if N > 128:
+        return reparameterize(mean, var, z, full_cov=True)
+    ctx = dev.get_context()
+    dm, dv, dz, out, info = ctx.to_device(mean), ctx.to_device(var), ctx.to_device(z), ctx.empty((S, N, D)), C.c_int(0)
+    ctx._check(dev.lib().dcgp_reparam_full_cov(ctx.handle, dm.ptr, dv.ptr, dz.ptr, S, N, D, JITTER, out.ptr, C.byref(info)), info)
+    return out.numpy()
+
+
 class MultiOutputConvKernel:
     """conv_gp/layers.py:12-50."""
 
@@ -342,7 +359,8 @@ class SVGP_Layer(Layer):
 
     def conditional_ND(self, X, full_cov=False):
         if full_cov:
-            raise NotImplementedError("full_cov=True is outside the accelerated hot path")
+            mean, var = self._conditional_full_cov(np.asarray(X, np.float64)[None])
+            return mean[0], var[0]
         ctx = dev.get_context()
         X = np.ascontiguousarray(X, np.float64)
         N, M, R = X.shape[0], self.num_inducing, self.num_outputs
@@ -355,6 +373,31 @@ class SVGP_Layer(Layer):
         mean, var, info = ctx.empty((N, R)), ctx.empty((N, R)), C.c_int(0)
         rc = dev.lib().dcgp_svgp_conditional(ctx.handle, d[0].ptr, d[1].ptr, d[2].ptr, d[3].ptr, d[4].ptr,
                                              int(self.white), M, N, R, mean.ptr, var.ptr, C.byref(info))
+        ctx._check(rc, info)
+        return mean.numpy(), var.numpy()
+
+    def _conditional_full_cov(self, X):
+        """conditional_ND(full_cov=True) of B input sets at once: X [B, N, D] -> mean [B, N, R], var [B, N, N, R] (DS-DGP's
+        [N, N, R] layout per set).  Patch heads: Kff by the image-pair kernel, one launch for all B; the dense RBF-ARD head: RBF.K.
+        The conditional itself is one device call (dcgp_svgp_conditional_full_cov)."""
+        X = np.ascontiguousarray(X, np.float64)
+        B, N = X.shape[:2]
+        M, R = self.num_inducing, self.num_outputs
+        if B == 0 or N == 0:
+            return np.zeros((B, N, R)), np.zeros((B, N, N, R))
+        Xf = X.reshape(B * N, -1)
+        Ku = _Kuu(self.feature, self.kern, jitter=JITTER)
+        Kuf = np.ascontiguousarray(np.transpose(_Kuf(self.feature, self.kern, Xf).reshape(M, B, N), (1, 0, 2)))
+        if hasattr(self.kern, "_K_batched"):
+            X4 = self.kern._reshape_X(Xf)
+            Kff = self.kern._K_batched(X4.reshape((B, N) + X4.shape[1:]))
+        else:
+            Kff = np.stack([self.kern.K(X[b]) for b in range(B)])
+        ctx = dev.get_context()
+        d = [ctx.to_device(a) for a in (Kuf, Ku, Kff, self.q_mu, self.q_sqrt)]
+        mean, var, info = ctx.empty((B, N, R)), ctx.empty((B, N, N, R)), C.c_int(0)
+        rc = dev.lib().dcgp_svgp_conditional_full_cov(ctx.handle, d[0].ptr, d[1].ptr, d[2].ptr, d[3].ptr, d[4].ptr, int(self.white),
+                                                      B, M, N, R, mean.ptr, var.ptr, C.byref(info))
         ctx._check(rc, info)
         return mean.numpy(), var.numpy()
 

@@ -141,6 +141,29 @@ int dcgp_svgp_conditional(dcgp_ctx* ctx, const double* Kuf, const double* Ku, co
                           const double* q_mu, const double* q_sqrt, int white, int M, int N, int R,
                           double* out_mean, double* out_var, int* info_host);
 
+/* ---- full covariances of the head (prediction only) ----------------------------------------- */
+/* ConvKernel.K (conv_gp/kernels.py:81-104), additive == 0:
+ *     out[b,n,n'] = (1/P^2) sum_{p,p'} w[p] w[p'] k(x[b,n,p], x2[b,n',p'])
+ * AdditivePatchKernel.K (conv_gp/kernels.py:34-51), additive != 0:
+ *     out[b,n,n'] = (1/P) sum_p w[p] k(x[b,n,p], x2[b,n',p])
+ * RBF base kernel.  X [B,N,H,W,C], X2 [B,N2,H,W,C] or NULL (X2 = X, N2 = N: only n <= n' is computed and mirrored, so each
+ * out[b] is symmetric bit for bit), w [P] -> out [B,N,N2].  Deterministic: no floating-point atomics.                      */
+int dcgp_convkernel_k(dcgp_ctx* ctx, const double* X, const double* X2, int B, int N, int N2, int H, int W, int C, int f,
+                      int stride, double variance, double lengthscale, const double* w, int additive, double* out);
+/* doubly_stochastic_dgp SVGP_Layer.conditional_ND(X, full_cov=True) for B input sets against one q(u):
+ * Kuf [B,M,N], Ku [M,M] (jitter already added), Kff [B,N,N], q_mu [M,R], q_sqrt [R,M,M] (lower triangle used) or NULL.
+ * out_mean [B,N,R]; out_var [B,N,N,R] = Kff - A1^T A1 + (Lq_r^T A)^T (Lq_r^T A), A1 = inv(Lu) Kuf, A = A1 (white) or
+ * inv(Lu)^T A1.  A Ku that is not positive definite: DCGP_ERR_NOT_PD with the 1-based column in *info_host.                */
+int dcgp_svgp_conditional_full_cov(dcgp_ctx* ctx, const double* Kuf, const double* Ku, const double* Kff, const double* q_mu,
+                                   const double* q_sqrt, int white, int B, int M, int N, int R, double* out_mean,
+                                   double* out_var, int* info_host);
+/* doubly_stochastic_dgp.utils.reparameterize(mean, var, z, full_cov=True) (the full_cov branch of DGP_Base.propagate):
+ * out[s,:,d] = mean[s,:,d] + chol(var[s,:,:,d] + jitter I) z[s,:,d] for all S x D matrices in one launch.
+ * mean, z, out [S,N,D]; var [S,N,N,D] (lower triangle used).  N <= 128 (DCGP_ERR_ARG beyond).  A matrix that is not
+ * positive definite: DCGP_ERR_NOT_PD, *info_host = its 1-based failing column.                                          */
+int dcgp_reparam_full_cov(dcgp_ctx* ctx, const double* mean, const double* var, const double* z, int S, int N, int D,
+                          double jitter, double* out, int* info_host);
+
 /* ---- KL, likelihood, sampling --------------------------------------------------------------- */
 /* gpflow.kullback_leiblers.gauss_kl(q_mu, q_sqrt, K) (call sites conv_gp/layers.py:145,147);
  * K == NULL is the whitened prior.  q_mu [M,R], q_sqrt [R,M,M], K [M,M].                         */
