@@ -1174,7 +1174,7 @@ int layer_fills(Bk& bk, LayerState& L) {
     return DCGP_OK;
   }
   HIP_TRY(bk.ctx, hipMemsetAsync(L.gZ, 0, (size_t)L.M * L.v.L * sizeof(double), bk.ctx->stream));
-  HIP_TRY(bk.ctx, hipMemsetAsync(L.gw, 0, ((size_t)L.v.P + 3 + (L.is_head ? (size_t)L.v.L : 0)) * sizeof(double), bk.ctx->stream));   // gw, gscal, gard
+  HIP_TRY(bk.ctx, hipMemsetAsync(L.gw, 0, ((size_t)L.v.P + 3 + (L.is_head ? (size_t)L.v.L : 0) + L.lik_slots) * sizeof(double), bk.ctx->stream));   // gw, gscal, gard, glik
   if (!L.has_qsqrt) HIP_TRY(bk.ctx, hipMemsetAsync(L.gq_sqrt, 0, (size_t)L.R * L.M * L.M * sizeof(double), bk.ctx->stream));
   return DCGP_OK;
 }
@@ -1511,7 +1511,7 @@ int grad_kl_early(dcgp_model* m, bool enqueue, bool wait_fork) {
   return rc;
 }
 
-int model_backward(dcgp_model* m, const double* X, const int32_t* y, int N, double scale, int dedup_layer0) {
+int model_backward(dcgp_model* m, const double* X, const int32_t* y, int N, double scale, int dedup_layer0, const double* yf) {
   dcgp_ctx* ctx = m->ctx;
   const int nl = (int)m->layers.size(), S = m->S;
   if (!m->keep_outputs) return ctx_fail(ctx, DCGP_ERR_ARG, "grad: the forward pass must keep the layer outputs");
@@ -1534,10 +1534,18 @@ int model_backward(dcgp_model* m, const double* X, const int32_t* y, int N, doub
   double* gm = (double*)ws_get(ctx, mp + "g_gm_head", (size_t)rows * H.R * sizeof(double));
   double* gv = (double*)ws_get(ctx, mp + "g_gv_head", (size_t)rows * H.R * sizeof(double));
   NEED(gm); NEED(gv);
-  if (H.R > RM_KMAX) return ctx_fail(ctx, DCGP_ERR_ARG, "grad: at most %d classes", RM_KMAX);
-  hipLaunchKernelGGL(robustmax_grad_kernel, dim3((rows + RM_ROWS - 1) / RM_ROWS), dim3(256), 0, ctx->stream, oh.mean, oh.var, y, rows, N, H.R,
-                     m->eps, gh, weight, gm, gv);
-  LAUNCH_CHECK(ctx);
+  double* gs2 = nullptr;   // Gaussian likelihood: d / d variance, moved into the head's block (glik) once its zero fill is behind us
+  if (yf) {
+    if (!m->d_lik || !H.lik_slots) return ctx_fail(ctx, DCGP_ERR_ARG, "grad: Gaussian targets on a model without the Gaussian likelihood");
+    gs2 = (double*)ws_get(ctx, mp + "g_lik", sizeof(double));
+    NEED(gs2);
+    DCGP_TRY(gauss_grad(ctx, oh.mean, oh.var, yf, rows, H.R, N, m->d_lik, weight, gm, gv, gs2));
+  } else {
+    if (H.R > RM_KMAX) return ctx_fail(ctx, DCGP_ERR_ARG, "grad: at most %d classes", RM_KMAX);
+    hipLaunchKernelGGL(robustmax_grad_kernel, dim3((rows + RM_ROWS - 1) / RM_ROWS), dim3(256), 0, ctx->stream, oh.mean, oh.var, y, rows, N, H.R,
+                       m->eps, gh, weight, gm, gv);
+    LAUNCH_CHECK(ctx);
+  }
   bool dedup_done = false;   // layer 0's (dmean, dvar) already summed over the S replicas
   for (int li = nl - 1; li >= 0; --li) {
     LayerState& L = *m->layers[li];
@@ -1590,6 +1598,7 @@ int model_backward(dcgp_model* m, const double* X, const int32_t* y, int N, doub
     }
   }
   if (bk.side_pending) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_kl, 0));   // the one join of the step: every layer's side-stream tail
+  if (gs2) HIP_TRY(ctx, hipMemcpyAsync(H.glik, gs2, sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));   // (behind every fill of the block)
   m->grad_scattered = false;
   if (ctx->comm) {
     // One in-stream collective per layer over its contiguous gradient block (RCCL over xGMI).  A training step in exchange mode 1: a
@@ -1623,7 +1632,7 @@ static int opt_enqueue(dcgp_model* model, const char* who, bool sgd, double lr, 
 static int opt_readback(dcgp_model* model);
 
 static int elbo_grad_run(dcgp_model* model, const double* X, const int32_t* y, int N, double scale, const double* const* z_per_layer_host,
-                         uint64_t seed, int dedup_layer0, double* out_host, int* info_host, const AdamReq* adam) {
+                         uint64_t seed, int dedup_layer0, double* out_host, int* info_host, const AdamReq* adam, const double* yf = nullptr) {
   dcgp_ctx* ctx = model->ctx;
   const bool keep = model->keep_outputs;
   model->keep_outputs = true;   // the reverse pass reads every layer's (sample, mean, var)
@@ -1637,10 +1646,10 @@ static int elbo_grad_run(dcgp_model* model, const double* X, const int32_t* y, i
   if (info_host) *info_host = 0;
   const auto host_t0 = std::chrono::steady_clock::now();
   int rc = model->enq_seq != model->col_seq ? ctx_fail(ctx, DCGP_ERR_ARG, "elbo_grad: enqueued steps are still to be collected")
-                                             : elbo_forward_enqueue_impl(model, X, y, N, scale, z_per_layer_host, seed, dedup_layer0, &ticket);
+                                             : elbo_forward_enqueue_impl(model, X, y, N, scale, z_per_layer_host, seed, dedup_layer0, &ticket, false, yf);
   const bool enqueued = rc == DCGP_OK;
   if (rc == DCGP_OK && model->gkl_state) rc = grad_kl_early(model, true, model->gkl_state == 2);
-  if (rc == DCGP_OK) rc = model_backward(model, X, y, N, scale, dedup_layer0);
+  if (rc == DCGP_OK) rc = model_backward(model, X, y, N, scale, dedup_layer0, yf);
   // (the update reads the step's factorisation status word on the device: a failed step leaves the parameters as they were)
   if (rc == DCGP_OK && adam)
     rc = opt_enqueue(model, "train_step_adam", false, adam->lr_t, adam->beta1, adam->beta2, adam->eps, model->d_scal + 64 * model->bank + 43, 0);
@@ -1681,10 +1690,33 @@ int dcgp_elbo_grad(dcgp_model* model, const double* X, const int32_t* y, int N, 
 // One training step in one call: value, gradient and the Adam update (dcgp_model_adam_step's arguments; t == 0: the model's own step
 // count), enqueued back to back with one wait at the end -- what session.run(minimise_op) is to the reference (conv_gp/experiment.py:84-108).
 // A step whose factorisation fails returns DCGP_ERR_NOT_PD and leaves parameters, moments and step count untouched.
+static int train_step_adam_run(dcgp_model* model, const double* X, const int32_t* y, int N, double scale, const double* const* z_per_layer_host,
+                               uint64_t seed, int dedup_layer0, double lr, double beta1, double beta2, double eps, int t, double* out_host,
+                               int* info_host, const double* yf);
+
+int dcgp_elbo_grad_f64y(dcgp_model* model, const double* X, const double* y, int N, double scale, const double* const* z_per_layer_host,
+                        uint64_t seed, int dedup_layer0, double* out_host, int* info_host) {
+  if (!model || !X || !y || N <= 0 || !out_host) return model ? ctx_fail(model->ctx, DCGP_ERR_ARG, "elbo_grad_f64y: bad args") : DCGP_ERR_ARG;
+  return elbo_grad_run(model, X, nullptr, N, scale, z_per_layer_host, seed, dedup_layer0, out_host, info_host, nullptr, y);
+}
+
+int dcgp_model_train_step_adam_f64y(dcgp_model* model, const double* X, const double* y, int N, double scale, const double* const* z_per_layer_host,
+                                    uint64_t seed, int dedup_layer0, double lr, double beta1, double beta2, double eps, int t, double* out_host,
+                                    int* info_host) {
+  if (!model || !X || !y || N <= 0 || !out_host) return model ? ctx_fail(model->ctx, DCGP_ERR_ARG, "train_step_adam_f64y: bad args") : DCGP_ERR_ARG;
+  return train_step_adam_run(model, X, nullptr, N, scale, z_per_layer_host, seed, dedup_layer0, lr, beta1, beta2, eps, t, out_host, info_host, y);
+}
+
 int dcgp_model_train_step_adam(dcgp_model* model, const double* X, const int32_t* y, int N, double scale, const double* const* z_per_layer_host,
                                uint64_t seed, int dedup_layer0, double lr, double beta1, double beta2, double eps, int t, double* out_host,
                                int* info_host) {
   if (!model || !X || !y || N <= 0 || !out_host) return model ? ctx_fail(model->ctx, DCGP_ERR_ARG, "train_step_adam: bad args") : DCGP_ERR_ARG;
+  return train_step_adam_run(model, X, y, N, scale, z_per_layer_host, seed, dedup_layer0, lr, beta1, beta2, eps, t, out_host, info_host, nullptr);
+}
+
+static int train_step_adam_run(dcgp_model* model, const double* X, const int32_t* y, int N, double scale, const double* const* z_per_layer_host,
+                               uint64_t seed, int dedup_layer0, double lr, double beta1, double beta2, double eps, int t, double* out_host,
+                               int* info_host, const double* yf) {
   if (t < 0 || !(lr > 0) || !(beta1 >= 0 && beta1 < 1) || !(beta2 >= 0 && beta2 < 1) || !(eps > 0))
     return ctx_fail(model->ctx, DCGP_ERR_ARG, "train_step_adam: bad optimiser arguments");
   const int t_use = t == 0 ? model->adam_t + 1 : t;
@@ -1692,7 +1724,7 @@ int dcgp_model_train_step_adam(dcgp_model* model, const double* X, const int32_t
   a.lr_t = lr * sqrt(1.0 - pow(beta2, (double)t_use)) / (1.0 - pow(beta1, (double)t_use));
   a.beta1 = beta1; a.beta2 = beta2; a.eps = eps;
   for (auto& l : model->layers) DCGP_TRY(l->ensure_grads());   // (the optimiser's group table is built before the first reverse pass has run)
-  DCGP_TRY(elbo_grad_run(model, X, y, N, scale, z_per_layer_host, seed, dedup_layer0, out_host, info_host, &a));
+  DCGP_TRY(elbo_grad_run(model, X, y, N, scale, z_per_layer_host, seed, dedup_layer0, out_host, info_host, &a, yf));
   model->adam_t = t_use;
   return DCGP_OK;
 }
@@ -1700,6 +1732,14 @@ int dcgp_model_train_step_adam(dcgp_model* model, const double* X, const int32_t
 int dcgp_model_get_grad(dcgp_model* model, int layer, const char* which, double* out_host, size_t count) {
   if (!model || !which || !out_host) return DCGP_ERR_ARG;
   dcgp_ctx* ctx = model->ctx;
+  if (!strcmp(which, "likelihood_variance")) {   // model-wide, `layer` is ignored: the last slot of the head's gradient block
+    const LayerState* H = model->has_head ? model->layers.back().get() : nullptr;
+    if (model->lik_kind != 1 || !H || !H->glik) return ctx_fail(ctx, DCGP_ERR_ARG, "get_grad(likelihood_variance): no Gaussian-likelihood gradient (dcgp_elbo_grad_f64y first)");
+    if (count != 1) return ctx_fail(ctx, DCGP_ERR_ARG, "get_grad(likelihood_variance): expected 1 value");
+    HIP_TRY(ctx, hipMemcpyAsync(out_host, H->glik, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return DCGP_OK;
+  }
   if (layer < 0 || layer >= (int)model->layers.size()) return ctx_fail(ctx, DCGP_ERR_ARG, "get_grad: no layer %d", layer);
   LayerState& L = *model->layers[layer];
   if (!L.gZ) return ctx_fail(ctx, DCGP_ERR_ARG, "get_grad: call dcgp_elbo_grad first");
@@ -1805,6 +1845,11 @@ static int opt_enqueue(dcgp_model* model, const char* who, bool sgd, double lr, 
     if (L.is_head && L.w) DCGP_TRY(add(L.w, L.gw, L.aw, (long)L.v.P, 0, -1, nullptr, (L.frozen & 8u) != 0));
     DCGP_TRY(add(L.hyp, L.gscal, L.ahyp, 3, 1, li, nullptr, (L.frozen & 16u) != 0));
     if (L.ard) DCGP_TRY(add(L.ard, L.gard, L.aard, (long)L.v.L, 1, -1, L.in_scale, (L.frozen & 16u) != 0));   // dense head: per-dimension lengthscales and the staging scale 1 / l
+    if (L.glik) {   // Gaussian likelihood variance: the last slot of the head's block, moments beside it on the device
+      if (!model->d_lik) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: the head's block has a likelihood slot but the model no Gaussian likelihood", who);
+      double* lik_mv[2] = {model->d_lik + 1, model->d_lik + 2};
+      DCGP_TRY(add(model->d_lik, L.glik, lik_mv, 1, 1, -1, nullptr, model->lik_frozen));
+    }
   }
   a.first_block[a.ng] = nb;
   if (nb <= 0) return DCGP_OK;
@@ -1878,6 +1923,11 @@ int dcgp_model_sgd_step(dcgp_model* model, double lr) {
 
 int dcgp_model_set_trainable(dcgp_model* model, int layer, const char* which, int on) {
   if (!model || !which) return DCGP_ERR_ARG;
+  if (!strcmp(which, "likelihood_variance")) {   // model-wide, `layer` is ignored
+    if (model->lik_kind != 1) return ctx_fail(model->ctx, DCGP_ERR_ARG, "set_trainable(likelihood_variance): not a Gaussian-likelihood model");
+    model->lik_frozen = !on;
+    return DCGP_OK;
+  }
   if (layer < 0 || layer >= (int)model->layers.size()) return ctx_fail(model->ctx, DCGP_ERR_ARG, "set_trainable: no layer %d", layer);
   LayerState& L = *model->layers[layer];
   unsigned bit = 0;
@@ -1894,6 +1944,13 @@ int dcgp_model_set_trainable(dcgp_model* model, int layer, const char* which, in
 int dcgp_model_get_param(dcgp_model* model, int layer, const char* which, double* out_host, size_t count) {
   if (!model || !which || !out_host) return DCGP_ERR_ARG;
   dcgp_ctx* ctx = model->ctx;
+  if (!strcmp(which, "likelihood_variance")) {   // model-wide, `layer` is ignored
+    if (model->lik_kind != 1) return ctx_fail(ctx, DCGP_ERR_ARG, "get_param(likelihood_variance): not a Gaussian-likelihood model");
+    if (count != 1) return ctx_fail(ctx, DCGP_ERR_ARG, "get_param(likelihood_variance): expected 1 value");
+    HIP_TRY(ctx, hipMemcpyAsync(out_host, model->d_lik, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return DCGP_OK;
+  }
   if (layer < 0 || layer >= (int)model->layers.size()) return ctx_fail(ctx, DCGP_ERR_ARG, "get_param: no layer %d", layer);
   LayerState& L = *model->layers[layer];
   const double* src = nullptr;

@@ -194,6 +194,21 @@ int eval_tail(dcgp_ctx* ctx, const double* mu, const double* var, const int32_t*
               double* logdens, double* p_mean, int* ok);
 int eval_sum(dcgp_ctx* ctx, const double* logdens, const int* ok, long n, const EvalStatus& st, double* res);
 
+// gaussian.hip: the Gaussian likelihood's tails (targets y [n_labels][K] float64, row r reads y[r % n_labels]; s2 the variance's device word).
+// gauss_elbo_tail: elbo_tail's counterpart (same scal / fin / KlTail contract).  gauss_grad: gm, gv [rows][K] and gs2[0] = d / d s2, all
+// times weight.  gauss_predict: out_mean = mu, out_var = var + s2 (either may be nullptr).  gauss_eval_tail / gauss_eval_sum: eval_tail /
+// eval_sum's counterparts (per image the log density summed over K, per (image, k) the log density (ld_nd, may be nullptr) and the
+// sample-mean prediction (y_mean, may be nullptr), per image the squared error; res[4] = {sum of squared errors, sum of log densities,
+// first non-positive pivot, 0}).
+int gauss_elbo_tail(dcgp_ctx* ctx, const double* mu, const double* var, const double* y, int n_rows, int n_labels, int K, const double* s2,
+                    double* ve_rows, double inv_s, double* scal, const ElboFinish& fin, const KlTail* kl = nullptr);
+int gauss_grad(dcgp_ctx* ctx, const double* mu, const double* var, const double* y, int rows, int K, int n_labels, const double* s2,
+               double weight, double* gm, double* gv, double* gs2);
+int gauss_predict(dcgp_ctx* ctx, const double* mu, const double* var, long n, const double* s2, double* out_mean, double* out_var);
+int gauss_eval_tail(dcgp_ctx* ctx, const double* mu, const double* var, const double* y, int n, int S, int K, const double* s2, long lo,
+                    double* logdens, double* ld_nd, double* y_mean, double* sqerr);
+int gauss_eval_sum(dcgp_ctx* ctx, const double* logdens, const double* sqerr, long n, const EvalStatus& st, double* res);
+
 // deterministic single-block sum of n doubles, scaled: out[0] = scale * sum
 int reduce_sum(dcgp_ctx* ctx, const double* in, long n, double scale, double* out);
 constexpr int REDUCE_JOBS_MAX = 12;

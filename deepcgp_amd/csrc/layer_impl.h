@@ -123,7 +123,10 @@ struct LayerState {
     pstage = dalloc(grad_block_count() + kGradBlockPad);
     return pstage ? DCGP_OK : ctx_fail(ctx, DCGP_ERR_ALLOC, "layer: staging allocation failed");
   }
-  size_t grad_block_count() const { return (size_t)M * v.L + (size_t)M * R + (size_t)R * M * M + (size_t)v.P + 3 + (is_head ? (size_t)v.L : 0); }
+  // head of a Gaussian-likelihood model: one more slot at the very end of the block, d ELBO / d likelihood variance (glik)
+  int lik_slots = 0;
+  double* glik = nullptr;
+  size_t grad_block_count() const { return (size_t)M * v.L + (size_t)M * R + (size_t)R * M * M + (size_t)v.P + 3 + (is_head ? (size_t)v.L : 0) + (size_t)lik_slots; }
   int ensure_grads() {
     if (gZ) return DCGP_OK;
     double* blk = dalloc(grad_block_count() + kGradBlockPad);   // (padding: the sharded exchange rounds the block up to ranks x shard)
@@ -131,6 +134,7 @@ struct LayerState {
     if (!blk || !gslots) return ctx_fail(ctx, DCGP_ERR_ALLOC, "layer: gradient allocation failed");
     gZ = blk; gq_mu = gZ + (size_t)M * v.L; gq_sqrt = gq_mu + (size_t)M * R; gw = gq_sqrt + (size_t)R * M * M; gscal = gw + v.P;
     gard = is_head ? gscal + 3 : nullptr;   // [L] d / d ARD lengthscales (dense head), zero otherwise
+    glik = lik_slots ? gscal + 3 + (is_head ? v.L : 0) : nullptr;
     return DCGP_OK;
   }
   int ensure_adam() {

@@ -586,6 +586,13 @@ int dcgp_model_set_param(dcgp_model* model, int layer, const char* which, const 
     model->eps = value_host[0];
     return DCGP_OK;
   }
+  if (!strcmp(which, "likelihood_variance")) {   // model-wide, `layer` is ignored
+    if (model->lik_kind != 1) return ctx_fail(ctx, DCGP_ERR_ARG, "set_param(likelihood_variance): not a Gaussian-likelihood model");
+    if (count != 1 || !(value_host[0] > 1e-6)) return ctx_fail(ctx, DCGP_ERR_ARG, "set_param(likelihood_variance): one value > 1e-6");
+    HIP_TRY(ctx, hipMemcpyAsync(model->d_lik, value_host, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return DCGP_OK;
+  }
   if (layer < 0 || layer >= (int)model->layers.size()) return ctx_fail(ctx, DCGP_ERR_ARG, "set_param: no layer %d", layer);
   LayerState& L = *model->layers[layer];
   auto expect = [&](size_t n) { return count == n ? DCGP_OK : ctx_fail(ctx, DCGP_ERR_ARG, "set_param(%s): expected %zu values, got %zu", which, n, count); };
@@ -634,7 +641,7 @@ int dcgp_model_set_param(dcgp_model* model, int layer, const char* which, const 
 int dcgp_elbo_forward(dcgp_model* model, const double* X, const int32_t* y, int N, double scale,
                       const double* const* z_per_layer_host, uint64_t seed, int dedup_layer0, double* out_host,
                       int* info_host) {
-  return elbo_forward_impl(model, X, y, N, scale, z_per_layer_host, seed, dedup_layer0, out_host, info_host);
+  return elbo_forward_impl(model, X, y, N, scale, z_per_layer_host, seed, dedup_layer0, out_host, info_host);   // (a Gaussian model: DCGP_ERR_ARG)
 }
 
 int dcgp_elbo_forward_enqueue(dcgp_model* model, const double* X, const int32_t* y, int N, double scale,
@@ -647,13 +654,53 @@ int dcgp_elbo_forward_collect(dcgp_model* model, uint64_t ticket, double* out_ho
   return elbo_forward_collect_impl(model, ticket, out_host, info_host);
 }
 
+int dcgp_elbo_forward_f64y(dcgp_model* model, const double* X, const double* y, int N, double scale,
+                           const double* const* z_per_layer_host, uint64_t seed, int dedup_layer0, double* out_host,
+                           int* info_host) {
+  if (model && !y) return ctx_fail(model->ctx, DCGP_ERR_ARG, "elbo_forward_f64y: y is NULL");
+  return elbo_forward_impl(model, X, nullptr, N, scale, z_per_layer_host, seed, dedup_layer0, out_host, info_host, y);
+}
+
+int dcgp_elbo_forward_enqueue_f64y(dcgp_model* model, const double* X, const double* y, int N, double scale,
+                                   const double* const* z_per_layer_host, uint64_t seed, int dedup_layer0, uint64_t* ticket) {
+  if (model && !y) return ctx_fail(model->ctx, DCGP_ERR_ARG, "elbo_forward_enqueue_f64y: y is NULL");
+  return elbo_forward_enqueue_impl(model, X, nullptr, N, scale, z_per_layer_host, seed, dedup_layer0, ticket, true, y);
+}
+
+int dcgp_model_set_likelihood(dcgp_model* model, int kind, double variance) {
+  if (!model) return DCGP_ERR_ARG;
+  dcgp_ctx* ctx = model->ctx;
+  if (kind != 0 && kind != 1) return ctx_fail(ctx, DCGP_ERR_ARG, "set_likelihood: kind 0 (RobustMax) or 1 (Gaussian), got %d", kind);
+  if (kind == 1 && !(variance > 1e-6)) return ctx_fail(ctx, DCGP_ERR_ARG, "set_likelihood: the Gaussian variance must be > 1e-6 (softplus + 1e-6)");
+  if (!model->has_head) return ctx_fail(ctx, DCGP_ERR_ARG, "set_likelihood: set the head first");
+  LayerState& H = *model->layers.back();
+  if (H.gZ && H.lik_slots != kind) return ctx_fail(ctx, DCGP_ERR_ARG, "set_likelihood: the likelihood is fixed once a gradient was taken");
+  if (model->enq_seq != model->col_seq) return ctx_fail(ctx, DCGP_ERR_ARG, "set_likelihood: enqueued steps are still to be collected");
+  ++model->param_version;
+  model->lik_kind = kind;
+  H.lik_slots = kind;
+  if (kind == 0) return DCGP_OK;
+  if (!model->d_lik) {   // {variance, Adam m, Adam v}
+    if (hipMalloc((void**)&model->d_lik, 3 * sizeof(double)) != hipSuccess) return ctx_fail(ctx, DCGP_ERR_ALLOC, "set_likelihood: device allocation failed");
+    const double init[3] = {variance, 0.0, 0.0};
+    HIP_TRY(ctx, hipMemcpyAsync(model->d_lik, init, sizeof init, hipMemcpyHostToDevice, ctx->stream));
+  } else {
+    HIP_TRY(ctx, hipMemcpyAsync(model->d_lik, &variance, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  }
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return DCGP_OK;
+}
+
 }  // extern "C"
 
 int elbo_forward_enqueue_impl(dcgp_model* model, const double* X, const int32_t* y, int N, double scale,
                               const double* const* z_per_layer_host, uint64_t seed, int dedup_layer0, uint64_t* ticket,
-                              bool pipelined) {
-  if (!model || !X || !y || N <= 0 || !ticket) return model ? ctx_fail(model->ctx, DCGP_ERR_ARG, "elbo_forward: bad args") : DCGP_ERR_ARG;
+                              bool pipelined, const double* yf) {
+  if (!model || !X || !(y || yf) || N <= 0 || !ticket) return model ? ctx_fail(model->ctx, DCGP_ERR_ARG, "elbo_forward: bad args") : DCGP_ERR_ARG;
   dcgp_ctx* ctx = model->ctx;
+  if ((model->lik_kind == 1) != (yf != nullptr))
+    return ctx_fail(ctx, DCGP_ERR_ARG, model->lik_kind == 1 ? "elbo_forward: a Gaussian-likelihood model takes float64 targets (the _f64y entry points)"
+                                                            : "elbo_forward: a RobustMax model takes int32 labels, not float64 targets");
   if (model->enq_seq - model->col_seq >= (uint64_t)dcgp_model::RING)
     return ctx_fail(ctx, DCGP_ERR_ARG, "elbo_forward_enqueue: %d steps in flight, collect the oldest first", dcgp_model::RING);
   if (!model->h_ring) {
@@ -698,11 +745,13 @@ int elbo_forward_enqueue_impl(dcgp_model* model, const double* X, const int32_t*
     // 0.1416 -> 0.1462, conv + head +2 us (profiles/r06_tail_ride_and_prep_ab.txt): two levels of agent-scope release/acquire at the end of 200
     // workgroups cost more than the 13 us launch they replace.)
     // expectations, their sum, the KL pieces where the chain left their ingredients, and the ELBO assembly in one launch
-    DCGP_TRY(elbo_tail(ctx, o.mean, o.var, y, rows, N, H.R, model->eps, model->d_ve, inv_s, scal, fin, klt));
+    if (yf) DCGP_TRY(gauss_elbo_tail(ctx, o.mean, o.var, yf, rows, N, H.R, model->d_lik, model->d_ve, inv_s, scal, fin, klt));
+    else DCGP_TRY(elbo_tail(ctx, o.mean, o.var, y, rows, N, H.R, model->eps, model->d_ve, inv_s, scal, fin, klt));
   } else {
     // multi-GPU: the data term is summed over the ranks between the reduction and the assembly
     ElboFinish none;
-    DCGP_TRY(elbo_tail(ctx, o.mean, o.var, y, rows, N, H.R, model->eps, model->d_ve, inv_s, scal, none, klt));
+    if (yf) DCGP_TRY(gauss_elbo_tail(ctx, o.mean, o.var, yf, rows, N, H.R, model->d_lik, model->d_ve, inv_s, scal, none, klt));
+    else DCGP_TRY(elbo_tail(ctx, o.mean, o.var, y, rows, N, H.R, model->eps, model->d_ve, inv_s, scal, none, klt));
     // A step kept in flight: collective and assembly go to the comm stream behind one event, and the main stream is free for the next step's
     // data path at once -- in stream, a 1-double ncclAllReduce (~20 us of latency over xGMI, more when a rank is late) sat in front of the next
     // step's layer kernel.  What it reads (scal of this bank, the chain's status words) stays untouched until the bank's next writer, which
@@ -794,12 +843,12 @@ int elbo_forward_collect_impl(dcgp_model* model, uint64_t ticket, double* out_ho
 
 int elbo_forward_impl(dcgp_model* model, const double* X, const int32_t* y, int N, double scale,
                       const double* const* z_per_layer_host, uint64_t seed, int dedup_layer0, double* out_host,
-                      int* info_host) {
+                      int* info_host, const double* yf) {
   if (!model || !out_host) return model ? ctx_fail(model->ctx, DCGP_ERR_ARG, "elbo_forward: bad args") : DCGP_ERR_ARG;
   if (model->enq_seq != model->col_seq) return ctx_fail(model->ctx, DCGP_ERR_ARG, "elbo_forward: enqueued steps are still to be collected");
   if (info_host) *info_host = 0;
   uint64_t ticket = 0;
-  DCGP_TRY(elbo_forward_enqueue_impl(model, X, y, N, scale, z_per_layer_host, seed, dedup_layer0, &ticket));
+  DCGP_TRY(elbo_forward_enqueue_impl(model, X, y, N, scale, z_per_layer_host, seed, dedup_layer0, &ticket, false, yf));
   return elbo_forward_collect_impl(model, ticket, out_host, info_host);
 }
 
@@ -839,6 +888,7 @@ int dcgp_model_predict_y(dcgp_model* model, const double* X, int N, int S, const
   if (!model || !X || N <= 0 || S <= 0 || (!out_p && !out_p_mean))
     return model ? ctx_fail(model->ctx, DCGP_ERR_ARG, "predict_y: bad args") : DCGP_ERR_ARG;
   dcgp_ctx* ctx = model->ctx;
+  if (model->lik_kind != 0) return ctx_fail(ctx, DCGP_ERR_ARG, "predict_y: class probabilities of a Gaussian-likelihood model (dcgp_model_predict_mean_var)");
   if (info_host) *info_host = 0;
   int rows = 0;
   StreamGuard guard(ctx);
@@ -863,6 +913,23 @@ int dcgp_model_predict_y(dcgp_model* model, const double* X, int N, int S, const
   return read_info(model, info_host);
 }
 
+int dcgp_model_predict_mean_var(dcgp_model* model, const double* X, int N, int S, const double* const* z_per_layer_host,
+                                uint64_t seed, double* out_mean, double* out_var, int* info_host) {
+  if (!model || !X || N <= 0 || S <= 0 || (!out_mean && !out_var))
+    return model ? ctx_fail(model->ctx, DCGP_ERR_ARG, "predict_mean_var: bad args") : DCGP_ERR_ARG;
+  dcgp_ctx* ctx = model->ctx;
+  if (model->lik_kind != 1) return ctx_fail(ctx, DCGP_ERR_ARG, "predict_mean_var: not a Gaussian-likelihood model (dcgp_model_predict_y)");
+  if (info_host) *info_host = 0;
+  int rows = 0;
+  StreamGuard guard(ctx);
+  DCGP_TRY(forward_all(model, X, N, S, z_per_layer_host, seed, 0, false, false, &rows));
+  DCGP_TRY(forward_done(model, nullptr));   // this call synchronises the stream before it returns
+  auto& o = model->outs.back();
+  DCGP_TRY(gauss_predict(ctx, o.mean, o.var, (long)rows * o.width, model->d_lik, out_mean, out_var));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return read_info(model, info_host);
+}
+
 }  // extern "C"
 
 namespace {
@@ -874,26 +941,33 @@ namespace {
 //   (layer_impl.h: ev_aux).  The chain of a batch (factor_reuse 0, or the first batch) writes the parameter-only state of its bank
 //   on its own stream: done_ev[bank] -- recorded on the main stream behind the tail of the last batch on that bank -- orders it.
 //   Workspaces: batch 0 is the largest, every later request is served by what it grew.
+// yf (Gaussian model, y == nullptr): targets [N_total][K]; out_p_mean is then the sample-mean prediction [N_total][K], out_ld_nd (may be
+// nullptr) the log density per (image, output), and out_host[0] the sum of the squared errors of the sample-mean prediction.
 int evaluate_impl(dcgp_model* model, const double* X, const int32_t* y, int N_total, int batch, int S, const double* const* zs,
-                  uint64_t seed, double* out_logdens, double* out_p_mean, double* out_host, int* info_host, const char* who) {
+                  uint64_t seed, double* out_logdens, double* out_p_mean, double* out_host, int* info_host, const char* who,
+                  const double* yf = nullptr, double* out_ld_nd = nullptr) {
   if (!model) return DCGP_ERR_ARG;
   dcgp_ctx* ctx = model->ctx;
   if (info_host) *info_host = 0;
-  if (!X || !y || N_total <= 0 || batch <= 0 || S <= 0 || !out_host)
+  if (!X || !(y || yf) || N_total <= 0 || batch <= 0 || S <= 0 || !out_host)
     return ctx_fail(ctx, DCGP_ERR_ARG, "%s: bad args (N %d, batch %d, S %d)", who, N_total, batch, S);
+  if ((model->lik_kind == 1) != (yf != nullptr))
+    return ctx_fail(ctx, DCGP_ERR_ARG, model->lik_kind == 1 ? "%s: a Gaussian-likelihood model takes float64 targets (the _f64y entry points)"
+                                                            : "%s: a RobustMax model takes int32 labels, not float64 targets", who);
   if (!model->has_head) return ctx_fail(ctx, DCGP_ERR_ARG, "model has no head layer");
   const int nl = (int)model->layers.size();
   const int K = model->layers[nl - 1]->R;
-  if (K < 2) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: the last layer has %d outputs, RobustMax needs >= 2", who, K);
-  if ((long)S * K + K > kEvalMaxSlots) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: S = %d samples of %d classes exceed the tail's LDS", who, S, K);
+  if (!yf && K < 2) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: the last layer has %d outputs, RobustMax needs >= 2", who, K);
+  if (!yf && (long)S * K + K > kEvalMaxSlots) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: S = %d samples of %d classes exceed the tail's LDS", who, S, K);
   const LayerState& L0 = *model->layers[0];
   const long in_len = (long)L0.v.H * L0.v.W * L0.v.C;   // one image of X
   // the per-image results of the whole set: requested once, before batch 0
   const std::string mp = "m" + std::to_string(model->id) + "_";
   double* ld = out_logdens ? out_logdens : (double*)ws_get(ctx, mp + "eval_logdens", (size_t)N_total * sizeof(double));
-  int* ok = (int*)ws_get(ctx, mp + "eval_ok", (size_t)N_total * sizeof(int));
+  int* ok = yf ? nullptr : (int*)ws_get(ctx, mp + "eval_ok", (size_t)N_total * sizeof(int));
+  double* sqerr = yf ? (double*)ws_get(ctx, mp + "eval_sqerr", (size_t)N_total * sizeof(double)) : nullptr;
   double* res = (double*)ws_get(ctx, mp + "eval_res", 4 * sizeof(double));
-  if (!ld || !ok || !res) return DCGP_ERR_ALLOC;
+  if (!ld || !(ok || sqerr) || !res) return DCGP_ERR_ALLOC;
   DCGP_TRY(ensure_events(model));
   StreamGuard guard(ctx);
   std::vector<const double*> zb(nl, nullptr);
@@ -911,7 +985,8 @@ int evaluate_impl(dcgp_model* model, const double* X, const int32_t* y, int N_to
     DCGP_TRY(forward_all(model, X + lo * in_len, n, S, zs ? zb.data() : nullptr, seed + (uint64_t)b, 0, false, false, &rows));
     const auto& o = model->outs[nl - 1];
     if (rows != S * n || o.width != K) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: head rows %d x %d, expected %d x %d", who, rows, o.width, S * n, K);
-    DCGP_TRY(eval_tail(ctx, o.mean, o.var, y + lo, n, S, K, model->eps, lo, ld, out_p_mean, ok));
+    if (yf) DCGP_TRY(gauss_eval_tail(ctx, o.mean, o.var, yf + lo * K, n, S, K, model->d_lik, lo, ld, out_ld_nd, out_p_mean, sqerr));
+    else DCGP_TRY(eval_tail(ctx, o.mean, o.var, y + lo, n, S, K, model->eps, lo, ld, out_p_mean, ok));
     HIP_TRY(ctx, hipEventRecord(model->ev_eval[model->bank], ctx->stream));
     DCGP_TRY(forward_done(model, model->ev_eval[model->bank]));
   }
@@ -920,7 +995,8 @@ int evaluate_impl(dcgp_model* model, const double* X, const int32_t* y, int N_to
   if (groups.size() > 16) return ctx_fail(ctx, DCGP_ERR_ARG, "model: too many factor groups");
   st.ngroups = (int)groups.size();
   for (int q = 0; q < st.ngroups; ++q) { st.info[q] = groups[q].d_info; st.ninfo[q] = (int)groups[q].K.size(); }
-  DCGP_TRY(eval_sum(ctx, ld, ok, N_total, st, res));
+  if (yf) DCGP_TRY(gauss_eval_sum(ctx, ld, sqerr, N_total, st, res));
+  else DCGP_TRY(eval_sum(ctx, ld, ok, N_total, st, res));
   double h[4];
   HIP_TRY(ctx, hipMemcpyAsync(h, res, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -935,6 +1011,20 @@ int evaluate_impl(dcgp_model* model, const double* X, const int32_t* y, int N_to
 }  // namespace
 
 extern "C" {
+
+int dcgp_model_predict_density_f64y(dcgp_model* model, const double* X, const double* y, int N, int S,
+                                    const double* const* z_per_layer, uint64_t seed, double* out_logdens, int* info_host) {
+  if (model && (!out_logdens || !y)) return ctx_fail(model->ctx, DCGP_ERR_ARG, "predict_density_f64y: out_logdens or y is NULL");
+  double sums[2];
+  return evaluate_impl(model, X, nullptr, N, N, S, z_per_layer, seed, nullptr, nullptr, sums, info_host, "predict_density", y, out_logdens);
+}
+
+int dcgp_model_evaluate_f64y(dcgp_model* model, const double* X, const double* y, int N_total, int batch, int S,
+                             const double* const* z_per_layer, uint64_t seed, double* out_logdens, double* out_y_mean,
+                             double* out_host, int* info_host) {
+  if (model && !y) return ctx_fail(model->ctx, DCGP_ERR_ARG, "evaluate_f64y: y is NULL");
+  return evaluate_impl(model, X, nullptr, N_total, batch, S, z_per_layer, seed, out_logdens, out_y_mean, out_host, info_host, "evaluate", y);
+}
 
 int dcgp_model_predict_density(dcgp_model* model, const double* X, const int32_t* y, int N, int S,
                                const double* const* z_per_layer, uint64_t seed, double* out_logdens, int* info_host) {

@@ -7,6 +7,12 @@ struct dcgp_model {
   int S = 1;
   double jitter = 1e-3;
   double eps = 1e-3;   // RobustMax epsilon (conv_gp/models.py:67 keeps gpflow's default)
+  // likelihood (dcgp_model_set_likelihood): 0 RobustMax (labels, int32), 1 Gaussian (targets [N][K] float64).  The Gaussian variance lives
+  // on the device (d_lik[0]; the tails and the optimiser read and write it there), its Adam moments in d_lik[1], d_lik[2] and its gradient in
+  // the last slot of the head's gradient block (LayerState::glik)
+  int lik_kind = 0;
+  double* d_lik = nullptr;
+  bool lik_frozen = false;   // dcgp_model_set_trainable(.., "likelihood_variance", 0)
   std::vector<std::unique_ptr<LayerState>> layers;   // conv layers..., head last (once set)
   bool has_head = false;
   bool keep_outputs = false;
@@ -72,7 +78,7 @@ struct dcgp_model {
       for (auto& e : ev_prep[b]) if (e) hipEventDestroy(e);
     }
     for (auto& o : outs) { hipFree(o.sample); hipFree(o.mean); hipFree(o.var); }
-    hipFree(d_scal); hipFree(d_ve); hipFree(d_kd);
+    hipFree(d_scal); hipFree(d_ve); hipFree(d_kd); hipFree(d_lik);
   }
 };
 
@@ -80,14 +86,14 @@ struct dcgp_model {
 // factorisations / conditional operands in the layers' GpMats.  out_host[0..2] = ELBO, data term, KL.
 int elbo_forward_impl(dcgp_model* model, const double* X, const int32_t* y, int N, double scale,
                       const double* const* z_per_layer_host, uint64_t seed, int dedup_layer0, double* out_host,
-                      int* info_host);
+                      int* info_host, const double* yf = nullptr);
 // the two halves of it: queue the step's launches and the copy of its result into a ring slot / wait for the oldest slot
 int elbo_forward_enqueue_impl(dcgp_model* model, const double* X, const int32_t* y, int N, double scale,
                               const double* const* z_per_layer_host, uint64_t seed, int dedup_layer0, uint64_t* ticket,
-                              bool pipelined = false);
+                              bool pipelined = false, const double* yf = nullptr);   // yf: Gaussian targets [N][K] (y is then nullptr)
 int elbo_forward_collect_impl(dcgp_model* model, uint64_t ticket, double* out_host, int* info_host);
 // grad.hip: reverse pass over the state the forward left behind; fills every layer's gradient buffers
-int model_backward(dcgp_model* model, const double* X, const int32_t* y, int N, double scale, int dedup_layer0);
+int model_backward(dcgp_model* model, const double* X, const int32_t* y, int N, double scale, int dedup_layer0, const double* yf = nullptr);
 // enqueue == false: 1 if a training step's forward should hand the KL adjoint's products to the side stream, else 0;
 // enqueue == true: do it (wait_fork: behind ctx->ev_fork, recorded where the parameter-only chain ended)
 int grad_kl_early(dcgp_model* model, bool enqueue, bool wait_fork);

@@ -110,6 +110,14 @@ _SIGS = {
     "dcgp_model_predict_density": [_vp, _vp, _vp, _i, _i, C.POINTER(_vp), _u64, _vp, _ip],
     "dcgp_model_evaluate": [_vp, _vp, _vp, _i, _i, _i, C.POINTER(_vp), _u64, _vp, _vp, _dp, _ip],
     "dcgp_model_layer_output": [_vp, _i, _vp, _vp, _vp, _ip, _ip],
+    "dcgp_model_set_likelihood": [_vp, _i, _d],
+    "dcgp_elbo_forward_f64y": [_vp, _vp, _vp, _i, _d, C.POINTER(_vp), _u64, _i, _dp, _ip],
+    "dcgp_elbo_forward_enqueue_f64y": [_vp, _vp, _vp, _i, _d, C.POINTER(_vp), _u64, _i, C.POINTER(_u64)],
+    "dcgp_elbo_grad_f64y": [_vp, _vp, _vp, _i, _d, C.POINTER(_vp), _u64, _i, C.POINTER(_d), _ip],
+    "dcgp_model_train_step_adam_f64y": [_vp, _vp, _vp, _i, _d, C.POINTER(_vp), _u64, _i, _d, _d, _d, _d, _i, C.POINTER(_d), _ip],
+    "dcgp_model_predict_mean_var": [_vp, _vp, _i, _i, C.POINTER(_vp), _u64, _vp, _vp, _ip],
+    "dcgp_model_predict_density_f64y": [_vp, _vp, _vp, _i, _i, C.POINTER(_vp), _u64, _vp, _ip],
+    "dcgp_model_evaluate_f64y": [_vp, _vp, _vp, _i, _i, _i, C.POINTER(_vp), _u64, _vp, _vp, _dp, _ip],
     "dcgp_gemm_strided": [_vp, _vp, C.c_long, C.c_long, C.c_long, _vp, C.c_long, C.c_long, C.c_long, _vp, C.c_long, C.c_long,
                           _i, _i, _i, _i, _d, _i, _vp, C.c_long, C.c_long, _vp, C.c_long, C.c_long, _i],
     "dcgp_gemm_strided_ex": [_vp, _vp, C.c_long, C.c_long, C.c_long, _vp, C.c_long, C.c_long, C.c_long, _vp, C.c_long, C.c_long,

@@ -11,6 +11,7 @@ import numpy as np
 from . import device as dev
 from .kernels import JITTER
 from .layers import ConvLayer, SVGP_Layer
+from .likelihoods import Gaussian
 
 
 def batched_noise(zs, N, S, batch_size, dims=None):
@@ -48,9 +49,10 @@ class Parameter:
 class DGP_Base:
     def __init__(self, X, Y, likelihood, layers, minibatch_size=None, num_samples=1, name='DGP', num_data=None):
         self.X = np.ascontiguousarray(X, np.float64)
-        self.Y = np.ascontiguousarray(np.reshape(Y, (-1,)), np.int32)
         self.likelihood = likelihood
         self.layers = list(layers)
+        self.gaussian = isinstance(likelihood, Gaussian)
+        self.Y = self._targets_host(Y) if self.gaussian else np.ascontiguousarray(np.reshape(Y, (-1,)), np.int32)
         self.num_samples = int(num_samples)
         self.minibatch_size = minibatch_size
         self.name = name
@@ -65,6 +67,28 @@ class DGP_Base:
         for l in self.layers[:-1]:
             if not isinstance(l, ConvLayer):
                 raise ValueError("hidden layers must be ConvLayer instances")
+
+    def _targets_host(self, Y, n=None):
+        """Gaussian likelihood: float64 targets N x D, D the head's num_outputs."""
+        D = self.layers[-1].num_outputs
+        Y = np.asarray(Y, np.float64)
+        if Y.ndim == 1 and D == 1:
+            Y = Y[:, None]
+        if Y.ndim != 2 or Y.shape[1] != D:
+            raise ValueError("Gaussian likelihood: targets must be N x %d (the head's num_outputs), got shape %r" % (D, np.shape(Y)))
+        if n is not None and Y.shape[0] != n:
+            raise ValueError("%d targets for %d images" % (Y.shape[0], n))
+        return np.ascontiguousarray(Y)
+
+    def _targets(self, Y, N):
+        """(device targets, Gaussian?) of an explicit minibatch: float64 N x D or int32 labels."""
+        if self.gaussian:
+            if isinstance(Y, dev.DeviceArray):
+                if Y.dtype != np.float64 or int(np.prod(Y.shape)) != N * self.layers[-1].num_outputs:
+                    raise ValueError("Gaussian likelihood: device targets must be float64 N x %d" % self.layers[-1].num_outputs)
+                return Y, True
+            return self._ctx.to_device(self._targets_host(Y, N)), True
+        return self._ctx.as_device(np.reshape(Y, (-1,)) if not isinstance(Y, dev.DeviceArray) else Y, np.int32), False
 
     def _default_scale(self, n_local):
         """num_data / minibatch size.  With an RCCL communicator on the ctx the data term is summed over the ranks inside
@@ -133,6 +157,8 @@ class DGP_Base:
             ctx._check(L.dcgp_model_set_param(self._model, len(self.layers) - 1, b"ard_lengthscales", ls.ctypes.data, ls.size))
         eps = np.array([float(getattr(self.likelihood, "epsilon", 1e-3))])
         ctx._check(L.dcgp_model_set_param(self._model, 0, b"likelihood_epsilon", eps.ctypes.data, 1))
+        if self.gaussian:
+            ctx._check(L.dcgp_model_set_likelihood(self._model, 1, float(self.likelihood.variance)))
 
     def sync_parameters(self):
         """Push the current Python-side parameter values to the device copy."""
@@ -157,12 +183,17 @@ class DGP_Base:
             else:
                 push(li, "Z0", l.Z_prior)
         push(0, "likelihood_epsilon", float(getattr(self.likelihood, "epsilon", 1e-3)))
+        if self.gaussian:
+            push(0, "likelihood_variance", float(self.likelihood.variance))
 
     @property
     def parameters(self):
         """Objects with ``pathname`` + ``value`` in the reference's checkpoint naming
         (DGP/layers/<i>/..., notebooks/Inspect.ipynb cell 6)."""
         out = []
+        if self.gaussian:                            # Gaussian variance under the BroadcastingLikelihood wrapper's doubled path
+            out.append(Parameter("%s/likelihood/likelihood/variance" % self.name, lambda: np.array(self.likelihood.variance),
+                                 lambda v: setattr(self.likelihood, "variance", float(v))))
         if hasattr(self.likelihood, "epsilon"):     # RobustMax epsilon under the BroadcastingLikelihood wrapper's doubled path
             out.append(Parameter("%s/likelihood/likelihood/invlink/epsilon" % self.name, lambda: np.array(self.likelihood.epsilon),
                                  lambda v: setattr(self.likelihood, "epsilon", float(v))))
@@ -210,14 +241,14 @@ class DGP_Base:
             X, Y = self.X[idx], self.Y[idx]
         ctx, L = self._ctx, dev.lib()
         dX = ctx.as_device(np.reshape(X, (np.shape(X)[0], -1)) if not isinstance(X, dev.DeviceArray) else X)
-        dY = ctx.as_device(np.reshape(Y, (-1,)) if not isinstance(Y, dev.DeviceArray) else Y, np.int32)
         N = dX.shape[0]
+        dY, gauss = self._targets(Y, N)
         if scale is None:
             scale = self._default_scale(N)
         arr, keep = self._z_table(zs, N, self.num_samples)
         out = (C.c_double * 3)()
         info = C.c_int(0)
-        rc = L.dcgp_elbo_forward(self._model, dX.ptr, dY.ptr, N, float(scale), arr, int(seed), int(self.dedup_layer0), out, C.byref(info))
+        rc = (L.dcgp_elbo_forward_f64y if gauss else L.dcgp_elbo_forward)(self._model, dX.ptr, dY.ptr, N, float(scale), arr, int(seed), int(self.dedup_layer0), out, C.byref(info))
         ctx._check(rc, info)
         if return_parts:
             return out[0], out[1], out[2]
@@ -231,13 +262,13 @@ class DGP_Base:
         self._build()
         ctx, L = self._ctx, dev.lib()
         dX = ctx.as_device(np.reshape(X, (np.shape(X)[0], -1)) if not isinstance(X, dev.DeviceArray) else X)
-        dY = ctx.as_device(np.reshape(Y, (-1,)) if not isinstance(Y, dev.DeviceArray) else Y, np.int32)
         N = dX.shape[0]
+        dY, gauss = self._targets(Y, N)
         if scale is None:
             scale = self._default_scale(N)
         arr, keep = self._z_table(zs, N, self.num_samples)
         ticket = C.c_uint64(0)
-        ctx._check(L.dcgp_elbo_forward_enqueue(self._model, dX.ptr, dY.ptr, N, float(scale), arr, int(seed), int(self.dedup_layer0),
+        ctx._check((L.dcgp_elbo_forward_enqueue_f64y if gauss else L.dcgp_elbo_forward_enqueue)(self._model, dX.ptr, dY.ptr, N, float(scale), arr, int(seed), int(self.dedup_layer0),
                                                C.byref(ticket)))
         if not hasattr(self, "_inflight"):
             self._inflight = {}
@@ -265,8 +296,8 @@ class DGP_Base:
         self._build()
         ctx, L = self._ctx, dev.lib()
         dX = ctx.as_device(np.reshape(X, (np.shape(X)[0], -1)) if not isinstance(X, dev.DeviceArray) else X)
-        dY = ctx.as_device(np.reshape(Y, (-1,)) if not isinstance(Y, dev.DeviceArray) else Y, np.int32)
         N = dX.shape[0]
+        dY, gauss = self._targets(Y, N)
         if scale is None:
             scale = self._default_scale(N)
         arr, keep = self._z_table(zs, N, self.num_samples)
@@ -275,7 +306,7 @@ class DGP_Base:
         # this call handles one of `shards` batch shards: the replicated KL term is weighted 1 / shards; None = the rank
         # count of the ctx's communicator (1 without one).  Always passed, so that it never sticks from an earlier call.
         ctx._check(L.dcgp_model_set_grad_shards(self._model, int(shards or 0)))
-        ctx._check(L.dcgp_elbo_grad(self._model, dX.ptr, dY.ptr, N, float(scale), arr, int(seed), int(self.dedup_layer0), out,
+        ctx._check((L.dcgp_elbo_grad_f64y if gauss else L.dcgp_elbo_grad)(self._model, dX.ptr, dY.ptr, N, float(scale), arr, int(seed), int(self.dedup_layer0), out,
                                     C.byref(info)), info)
         if not fetch:            # the gradients stay on the device (dcgp_model_get_grad / the optimiser step read them there)
             return out[0], None
@@ -298,6 +329,10 @@ class DGP_Base:
                 ctx._check(L.dcgp_model_get_grad(self._model, li, which.encode(), buf.ctypes.data, buf.size))
                 g[{"lengthscale": "lengthscales", "ard_lengthscales": "lengthscales", "w": "patch_weights"}.get(which, which)] = buf
             grads.append(g)
+        if gauss:                # d ELBO / d likelihood variance, with the head's gradients
+            buf = np.empty(1, np.float64)
+            ctx._check(L.dcgp_model_get_grad(self._model, 0, b"likelihood_variance", buf.ctypes.data, 1))
+            grads[-1]["likelihood_variance"] = buf.reshape(())
         return out[0], grads
 
     def adam_step(self, lr, t=None, beta1=0.9, beta2=0.999, epsilon=1e-8):
@@ -317,15 +352,15 @@ class DGP_Base:
         self._build()
         ctx, L = self._ctx, dev.lib()
         dX = ctx.as_device(np.reshape(X, (np.shape(X)[0], -1)) if not isinstance(X, dev.DeviceArray) else X)
-        dY = ctx.as_device(np.reshape(Y, (-1,)) if not isinstance(Y, dev.DeviceArray) else Y, np.int32)
         N = dX.shape[0]
+        dY, gauss = self._targets(Y, N)
         if scale is None:
             scale = self._default_scale(N)
         arr, keep = self._z_table(zs, N, self.num_samples)
         out = (C.c_double * 3)()
         info = C.c_int(0)
         ctx._check(L.dcgp_model_set_grad_shards(self._model, int(shards or 0)))
-        ctx._check(L.dcgp_model_train_step_adam(self._model, dX.ptr, dY.ptr, N, float(scale), arr, int(seed), int(self.dedup_layer0),
+        ctx._check((L.dcgp_model_train_step_adam_f64y if gauss else L.dcgp_model_train_step_adam)(self._model, dX.ptr, dY.ptr, N, float(scale), arr, int(seed), int(self.dedup_layer0),
                                                 float(lr), float(beta1), float(beta2), float(epsilon), int(t or 0), out, C.byref(info)), info)
         return out[0]
 
@@ -371,7 +406,8 @@ class DGP_Base:
         self.global_batch = int(global_batch) if global_batch else None
 
     def set_trainable(self, layer, which, on):
-        """param.set_trainable(on) for the device optimiser steps: which in Z, q_mu, q_sqrt, w, hyper."""
+        """param.set_trainable(on) for the device optimiser steps: which in Z, q_mu, q_sqrt, w, hyper; "likelihood_variance" (Gaussian
+        likelihood, ``layer`` ignored)."""
         self._build()
         self._ctx._check(dev.lib().dcgp_model_set_trainable(self._model, int(layer), which.encode(), int(bool(on))))
 
@@ -412,6 +448,8 @@ class DGP_Base:
                 kern.bias_variance = float(pull(li, "bias_variance", ()))
             if head and hasattr(l.kern, "patch_weights"):
                 l.kern.patch_weights = pull(li, "w", np.shape(l.kern.patch_weights))
+        if self.gaussian:
+            self.likelihood.variance = float(pull(0, "likelihood_variance", ()))
 
     def propagate(self, X, full_cov=False, S=1, zs=None, seed=0):
         """(Fs, Fmeans, Fvars): per layer S x N x D_l arrays (doubly_stochastic_dgp DGP_Base.propagate); full_cov=True: see
@@ -511,16 +549,33 @@ class DGP_Base:
 
     def predict_y(self, X, S, zs=None, seed=0):
         """(mean, var) of p(y*) per sample: S x N x num_classes (used at conv_gp/utils/log.py:62-66).
-        One device call: forward pass and RobustMax quadrature, only the probabilities come back."""
+        One device call: forward pass and RobustMax quadrature, only the probabilities come back.  Gaussian likelihood:
+        (Fmean, Fvar + variance), each S x N x D (dcgp_model_predict_mean_var)."""
         if np.shape(X)[0] == 0:
             K = self.layers[-1].num_outputs
             return np.zeros((S, 0, K)), np.zeros((S, 0, K))
+        if self.gaussian:
+            return self._predict_gauss(X, S, zs, seed)
         ps, _ = self._predict(X, S, zs, seed, True, False)
         return ps, ps - np.square(ps)
+
+    def _predict_gauss(self, X, S, zs, seed):
+        self._build()
+        ctx, L = self._ctx, dev.lib()
+        X = np.ascontiguousarray(np.reshape(X, (np.shape(X)[0], -1)), np.float64)
+        N, D = X.shape[0], self.layers[-1].num_outputs
+        dX = ctx.to_device(X)
+        arr, keep = self._z_table(zs, N, S)
+        m, v = ctx.empty((S * N, D)), ctx.empty((S * N, D))
+        info = C.c_int(0)
+        ctx._check(L.dcgp_model_predict_mean_var(self._model, dX.ptr, N, int(S), arr, int(seed), m.ptr, v.ptr, C.byref(info)), info)
+        return m.numpy().reshape(S, N, D), v.numpy().reshape(S, N, D)
 
     def predict_proba(self, X, S, zs=None, seed=0):
         """Class probabilities averaged over the S samples, N x num_classes (the quantity AccuracyLogger
         arg-maxes, conv_gp/utils/log.py:62-67); the sample mean is taken on the device."""
+        if self.gaussian:
+            raise ValueError("predict_proba: class probabilities need a classification likelihood, this model is Gaussian")
         if np.shape(X)[0] == 0:
             return np.zeros((0, self.layers[-1].num_outputs))
         return self._predict(X, S, zs, seed, False, True)[1]
@@ -542,9 +597,11 @@ class DGP_Base:
         ctx, L = self._ctx, dev.lib()
         X = np.ascontiguousarray(np.reshape(X, (np.shape(X)[0], -1)), np.float64)
         N, K = X.shape[0], self.layers[-1].num_outputs
-        Y = np.ascontiguousarray(np.reshape(Y, (-1,)), np.int32)
         if X.shape[1] != self.X.shape[1]:
             raise ValueError("images of %d values, the model takes %d" % (X.shape[1], self.X.shape[1]))
+        if self.gaussian:
+            return self._eval_call_gauss(X, self._targets_host(Y, N), S, batch_size, seed, flat_zs, want_p_mean, density_only)
+        Y = np.ascontiguousarray(np.reshape(Y, (-1,)), np.int32)
         if Y.size != N:
             raise ValueError("%d labels for %d images" % (Y.size, N))
         dX, dY = ctx.to_device(X), ctx.to_device(Y, np.int32)     # the whole set crosses the bus once
@@ -568,23 +625,62 @@ class DGP_Base:
         ctx._check(rc, info)
         return ld.numpy(), (pm.numpy() if pm else None), (out[0], out[1])
 
+    def _eval_call_gauss(self, X, Y, S, batch_size, seed, flat_zs, want_y_mean, density_only):
+        ctx, L = self._ctx, dev.lib()
+        N, D = X.shape[0], self.layers[-1].num_outputs
+        dX, dY = ctx.to_device(X), ctx.to_device(Y)
+        arr, keep = None, []
+        if flat_zs is not None:
+            arr = (C.c_void_p * len(self.layers))()
+            for i, z in enumerate(flat_zs):
+                if z is not None:
+                    keep.append(ctx.to_device(z))
+                    arr[i] = keep[-1].ptr
+        info = C.c_int(0)
+        if density_only:
+            ld = ctx.empty((N, D))
+            ctx._check(L.dcgp_model_predict_density_f64y(self._model, dX.ptr, dY.ptr, N, int(S), arr, int(seed), ld.ptr, C.byref(info)), info)
+            return ld.numpy(), None, None
+        ld = ctx.empty((N,))
+        ym = ctx.empty((N, D)) if want_y_mean else None
+        out = (C.c_double * 2)()
+        ctx._check(L.dcgp_model_evaluate_f64y(self._model, dX.ptr, dY.ptr, N, int(batch_size), int(S), arr, int(seed), ld.ptr,
+                                              ym.ptr if ym else None, out, C.byref(info)), info)
+        return ld.numpy(), (ym.numpy() if ym else None), (out[0], out[1])
+
     def predict_density(self, X, Y, S, zs=None, seed=0):
         """Log predictive density of each label, N x 1: logsumexp_s log p(y | f_s) - log S (doubly_stochastic_dgp
-        DGP_Base.predict_density with the RobustMax likelihood).  One device call; ``zs`` per layer [S, N, D]."""
+        DGP_Base.predict_density with the RobustMax likelihood).  Gaussian likelihood: N x D, per output
+        logsumexp_s log N(y; Fmean_s, Fvar_s + variance) - log S.  One device call; ``zs`` per layer [S, N, D]."""
         N = np.shape(X)[0]
         if N == 0:
-            return np.zeros((0, 1))
+            return np.zeros((0, self.layers[-1].num_outputs if self.gaussian else 1))
         ld, _, _ = self._eval_call(X, Y, S, N, seed, batched_noise(zs, N, S, N, self._out_dims()), False, density_only=True)
-        return ld.reshape(N, 1)
+        return ld if self.gaussian else ld.reshape(N, 1)
 
     def evaluate(self, X, Y, S=5, batch_size=32, seed=0, zs=None, per_image=False):
         """A whole test set in one device call (dcgp_model_evaluate): batches of ``batch_size`` images, batch i drawing its noise
         from ``seed + i`` as ``AccuracyLogger`` does, or from ``zs`` (per layer [S, N, D], indexed by image over the whole set).
         Returns {"accuracy", "mean_log_density", "n"}, with ``per_image`` also "log_density" [N] and "p_mean" [N, K] (the
-        sample-mean class probabilities).  Rank-local: nothing is reduced across ranks."""
+        sample-mean class probabilities).  Gaussian likelihood: {"mean_log_density", "rmse", "n"} (the root mean squared error of the
+        sample-mean prediction over all N x D targets), with ``per_image`` also "log_density" [N] (summed over the D outputs) and
+        "y_mean" [N, D].  Rank-local: nothing is reduced across ranks."""
         N = np.shape(X)[0]
         if int(batch_size) <= 0:
             raise ValueError("batch_size must be positive, got %r" % (batch_size,))
+        if self.gaussian:
+            D = self.layers[-1].num_outputs
+            if N == 0:
+                out = {"mean_log_density": float("nan"), "rmse": float("nan"), "n": 0}
+                if per_image:
+                    out["log_density"], out["y_mean"] = np.zeros(0), np.zeros((0, D))
+                return out
+            ld, ym, (sq, total) = self._eval_call(X, Y, S, batch_size, seed, batched_noise(zs, N, S, int(batch_size), self._out_dims()),
+                                                 per_image)
+            out = {"mean_log_density": total / N, "rmse": float(np.sqrt(sq / (N * D))), "n": N}
+            if per_image:
+                out["log_density"], out["y_mean"] = ld, ym
+            return out
         if N == 0:
             out = {"accuracy": 0.0, "mean_log_density": float("nan"), "n": 0}
             if per_image:

@@ -37,3 +37,32 @@ class MultiClass:
         ctx._check(dev.lib().dcgp_robustmax_predict(ctx.handle, dmu.ptr, dvar.ptr, n, K, self.epsilon, out.ptr))
         ps = out.numpy()
         return ps, ps - np.square(ps)
+
+
+class Gaussian:
+    """gpflow 1.x likelihoods.Gaussian(variance) as DS-DGP's BroadcastingLikelihood applies it: one variance shared by every output,
+    kept positive by transforms.positive (softplus + 1e-6) when trained.  Targets are float64 N x D.  On the model path
+    (DGP_Base with this likelihood) every tail runs on the device (csrc/gaussian.hip); these methods are the closed forms of the
+    same quantities on host arrays."""
+
+    def __init__(self, variance=1.0):
+        self.variance = float(variance)
+        if not self.variance > 1e-6:
+            raise ValueError("the Gaussian variance must be > 1e-6, got %r" % (variance,))
+
+    def logp(self, F, Y):
+        F, Y = np.asarray(F, np.float64), np.asarray(Y, np.float64)
+        return -0.5 * np.log(2 * np.pi * self.variance) - 0.5 * np.square(Y - F) / self.variance
+
+    def variational_expectations(self, Fmu, Fvar, Y):
+        Fmu, Fvar, Y = (np.asarray(a, np.float64) for a in (Fmu, Fvar, Y))
+        return -0.5 * np.log(2 * np.pi * self.variance) - 0.5 * (np.square(Y - Fmu) + Fvar) / self.variance
+
+    def predict_mean_and_var(self, Fmu, Fvar):
+        Fmu, Fvar = np.asarray(Fmu, np.float64), np.asarray(Fvar, np.float64)
+        return Fmu.copy(), Fvar + self.variance
+
+    def predict_density(self, Fmu, Fvar, Y):
+        Fmu, Fvar, Y = (np.asarray(a, np.float64) for a in (Fmu, Fvar, Y))
+        v = Fvar + self.variance
+        return -0.5 * np.log(2 * np.pi * v) - 0.5 * np.square(Y - Fmu) / v

@@ -46,9 +46,9 @@ def build_layers_from_spec(spec):
     return layers
 
 
-def build_from_spec(spec, X, Y):
-    """DGP_Base on the HIP path from a model spec (see deepcgp_amd.synthetic)."""
-    return DGP_Base(X, Y, likelihood=MultiClass(10), layers=build_layers_from_spec(spec),
+def build_from_spec(spec, X, Y, likelihood=None):
+    """DGP_Base on the HIP path from a model spec (see deepcgp_amd.synthetic); ``likelihood`` None = MultiClass(10)."""
+    return DGP_Base(X, Y, likelihood=MultiClass(10) if likelihood is None else likelihood, layers=build_layers_from_spec(spec),
                     num_samples=spec["S"], minibatch_size=None, num_data=spec["num_data"], name='DGP')
 
 
@@ -147,6 +147,8 @@ class AccuracyLogger(object):
         self.batch_size, self.num_samples = int(batch_size), int(num_samples)
 
     def __call__(self, model, seed=0):
+        if getattr(model, "gaussian", False):
+            raise ValueError("AccuracyLogger: accuracy needs a classification likelihood, this model is Gaussian")
         correct = 0
         for i, lo in enumerate(range(0, len(self.Y_test), self.batch_size)):
             sl = slice(lo, lo + self.batch_size)
@@ -162,7 +164,9 @@ class TestLogDensityLogger(object):
     __test__ = False   # (not a pytest class despite the name)
 
     def __init__(self, X_test, Y_test, batch_size=32, num_samples=5):
-        self.X_test, self.Y_test = X_test, np.reshape(Y_test, (-1,))
+        # labels are flattened; float targets N x D (a Gaussian likelihood) are kept as they are
+        self.X_test = X_test
+        self.Y_test = Y_test if np.ndim(Y_test) == 2 and np.asarray(Y_test).dtype.kind == "f" else np.reshape(Y_test, (-1,))
         self.batch_size, self.num_samples = int(batch_size), int(num_samples)
 
     def __call__(self, model, seed=0):

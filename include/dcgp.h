@@ -327,6 +327,47 @@ int dcgp_model_predict_density(dcgp_model* model, const double* X, const int32_t
 int dcgp_model_evaluate(dcgp_model* model, const double* X, const int32_t* y, int N_total, int batch, int S,
                         const double* const* z_per_layer, uint64_t seed, double* out_logdens, double* out_p_mean,
                         double* out_host, int* info_host);
+
+/* ---- Gaussian likelihood (gpflow 1.x likelihoods.Gaussian under DS-DGP's BroadcastingLikelihood) ----
+ * The likelihood of the model: kind 0 = RobustMax (the default; int32 labels), 1 = Gaussian with one variance s2 > 1e-6 shared by every
+ * output (float64 targets y [N, K], K = the head's outputs; gpflow's transforms.positive, s2 = softplus(u) + 1e-6, in the optimiser).
+ * Replaces the likelihood argument of DS-DGP DGP_Base.__init__.  Call after dcgp_model_set_head and before the first gradient.
+ * On a Gaussian model the int32 entry points above (dcgp_elbo_forward, _enqueue, dcgp_elbo_grad, dcgp_model_train_step_adam,
+ * dcgp_model_predict_y, dcgp_model_predict_density, dcgp_model_evaluate) return DCGP_ERR_ARG, and so do the _f64y ones below on a
+ * RobustMax model.  s2 is "likelihood_variance" in dcgp_model_set_param / _get_param / _get_grad / _set_trainable (`layer` ignored); its
+ * gradient is the last slot of the head's gradient block (dcgp_model_grad_block), after the ARD lengthscales. */
+int dcgp_model_set_likelihood(dcgp_model* model, int kind, double variance);
+/* dcgp_elbo_forward / _enqueue with Gaussian targets y [N, K] float64 (device): DGP_Base._build_likelihood with
+ * Gaussian.variational_expectations = -0.5 log(2 pi s2) - 0.5 ((y - mu)^2 + var) / s2 summed over the K outputs.  Tickets are
+ * collected with dcgp_elbo_forward_collect. */
+int dcgp_elbo_forward_f64y(dcgp_model* model, const double* X, const double* y, int N, double scale,
+                           const double* const* z_per_layer_host, uint64_t seed, int dedup_layer0, double* out_host,
+                           int* info_host);
+int dcgp_elbo_forward_enqueue_f64y(dcgp_model* model, const double* X, const double* y, int N, double scale,
+                                   const double* const* z_per_layer_host, uint64_t seed, int dedup_layer0, uint64_t* ticket);
+/* dcgp_elbo_grad / dcgp_model_train_step_adam with Gaussian targets (TensorFlow autodiff of the same objective; the Adam step also
+ * moves s2 unless it was set non-trainable). */
+int dcgp_elbo_grad_f64y(dcgp_model* model, const double* X, const double* y, int N, double scale,
+                        const double* const* z_per_layer_host, uint64_t seed, int dedup_layer0, double* out_host,
+                        int* info_host);
+int dcgp_model_train_step_adam_f64y(dcgp_model* model, const double* X, const double* y, int N, double scale,
+                                    const double* const* z_per_layer_host, uint64_t seed, int dedup_layer0, double lr, double beta1,
+                                    double beta2, double eps, int t, double* out_host, int* info_host);
+/* DS-DGP DGP_Base.predict_y with Gaussian.predict_mean_and_var: out_mean = Fmean, out_var = Fvar + s2, each [S*N, K] (device; either
+ * may be NULL, not both).  Only the head's outputs are written. */
+int dcgp_model_predict_mean_var(dcgp_model* model, const double* X, int N, int S,
+                                const double* const* z_per_layer_host, uint64_t seed,
+                                double* out_mean, double* out_var, int* info_host);
+/* DS-DGP DGP_Base.predict_density with Gaussian.predict_density: out_logdens [N, K] (device) =
+ * logsumexp_s log N(y; mu_s, var_s + s2) - log S per image and output. */
+int dcgp_model_predict_density_f64y(dcgp_model* model, const double* X, const double* y, int N, int S,
+                                    const double* const* z_per_layer, uint64_t seed, double* out_logdens, int* info_host);
+/* dcgp_model_evaluate for a Gaussian model: out_logdens [N_total] per image (summed over the K outputs), out_y_mean [N_total][K] the
+ * sample-mean prediction (device, either may be NULL); out_host[2] = {sum of the squared errors of the sample-mean prediction, sum of
+ * the per-image log densities}. */
+int dcgp_model_evaluate_f64y(dcgp_model* model, const double* X, const double* y, int N_total, int batch, int S,
+                             const double* const* z_per_layer, uint64_t seed, double* out_logdens, double* out_y_mean,
+                             double* out_host, int* info_host);
 /* Parameter-only state across steps.  The reference's evaluation loops run hundreds of batches at ONE parameter state (AccuracyLogger /
  * LogLikelihoodLogger, conv_gp/utils/log.py:55-68; conv_gp/utils/tensorboard.py:22-42), and every session.run of them factors every Kuu again.
  * Here a step records the parameter version its chain (operand preparation, factorisations, inverses, G / alpha, KL pieces) ran at; every call that writes
