@@ -1535,7 +1535,9 @@ int model_backward(dcgp_model* m, const double* X, const int32_t* y, int N, doub
   double* gv = (double*)ws_get(ctx, mp + "g_gv_head", (size_t)rows * H.R * sizeof(double));
   NEED(gm); NEED(gv);
   double* gs2 = nullptr;   // Gaussian likelihood: d / d variance, moved into the head's block (glik) once its zero fill is behind us
-  if (yf) {
+  if (yf && m->lik_kind == 2) {
+    DCGP_TRY(bern_grad(ctx, oh.mean, oh.var, yf, rows, H.R, N, weight, gm, gv));
+  } else if (yf) {
     if (!m->d_lik || !H.lik_slots) return ctx_fail(ctx, DCGP_ERR_ARG, "grad: Gaussian targets on a model without the Gaussian likelihood");
     gs2 = (double*)ws_get(ctx, mp + "g_lik", sizeof(double));
     NEED(gs2);

@@ -209,6 +209,19 @@ int gauss_eval_tail(dcgp_ctx* ctx, const double* mu, const double* var, const do
                     double* logdens, double* ld_nd, double* y_mean, double* sqerr);
 int gauss_eval_sum(dcgp_ctx* ctx, const double* logdens, const double* sqerr, long n, const EvalStatus& st, double* res);
 
+// bernoulli.hip: the Bernoulli (probit) likelihood's tails (targets y [n_labels][K] float64, y == 1 positive; row r reads y[r % n_labels]).
+// bern_elbo_tail: elbo_tail's counterpart (same scal / fin / KlTail contract).  bern_grad: gm, gv [rows][K] times weight.  bern_predict:
+// out_mean = p, out_var = p - p^2 (either may be nullptr).  bern_eval_tail: per image the log density summed over K, per (image, k) the
+// log density (ld_nd, may be nullptr) and the sample-mean p (p_mean, may be nullptr), per image the number of correct outputs as a double;
+// gauss_eval_sum adds those up (res[0] = correct entries, res[1] = sum of log densities).
+int bern_elbo_tail(dcgp_ctx* ctx, const double* mu, const double* var, const double* y, int n_rows, int n_labels, int K, double* ve_rows,
+                   double inv_s, double* scal, const ElboFinish& fin, const KlTail* kl = nullptr);
+int bern_grad(dcgp_ctx* ctx, const double* mu, const double* var, const double* y, int rows, int K, int n_labels, double weight, double* gm,
+              double* gv);
+int bern_predict(dcgp_ctx* ctx, const double* mu, const double* var, long n, double* out_mean, double* out_var);
+int bern_eval_tail(dcgp_ctx* ctx, const double* mu, const double* var, const double* y, int n, int S, int K, long lo, double* logdens,
+                   double* ld_nd, double* p_mean, double* correct);
+
 // deterministic single-block sum of n doubles, scaled: out[0] = scale * sum
 int reduce_sum(dcgp_ctx* ctx, const double* in, long n, double scale, double* out);
 constexpr int REDUCE_JOBS_MAX = 12;

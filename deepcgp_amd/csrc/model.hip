@@ -670,16 +670,16 @@ int dcgp_elbo_forward_enqueue_f64y(dcgp_model* model, const double* X, const dou
 int dcgp_model_set_likelihood(dcgp_model* model, int kind, double variance) {
   if (!model) return DCGP_ERR_ARG;
   dcgp_ctx* ctx = model->ctx;
-  if (kind != 0 && kind != 1) return ctx_fail(ctx, DCGP_ERR_ARG, "set_likelihood: kind 0 (RobustMax) or 1 (Gaussian), got %d", kind);
+  if (kind < 0 || kind > 2) return ctx_fail(ctx, DCGP_ERR_ARG, "set_likelihood: kind 0 (RobustMax), 1 (Gaussian) or 2 (Bernoulli), got %d", kind);
   if (kind == 1 && !(variance > 1e-6)) return ctx_fail(ctx, DCGP_ERR_ARG, "set_likelihood: the Gaussian variance must be > 1e-6 (softplus + 1e-6)");
   if (!model->has_head) return ctx_fail(ctx, DCGP_ERR_ARG, "set_likelihood: set the head first");
   LayerState& H = *model->layers.back();
-  if (H.gZ && H.lik_slots != kind) return ctx_fail(ctx, DCGP_ERR_ARG, "set_likelihood: the likelihood is fixed once a gradient was taken");
+  if (H.gZ && model->lik_kind != kind) return ctx_fail(ctx, DCGP_ERR_ARG, "set_likelihood: the likelihood is fixed once a gradient was taken");
   if (model->enq_seq != model->col_seq) return ctx_fail(ctx, DCGP_ERR_ARG, "set_likelihood: enqueued steps are still to be collected");
   ++model->param_version;
   model->lik_kind = kind;
-  H.lik_slots = kind;
-  if (kind == 0) return DCGP_OK;
+  H.lik_slots = kind == 1 ? 1 : 0;   // (only the Gaussian variance takes a slot: a Bernoulli block is a RobustMax one)
+  if (kind != 1) return DCGP_OK;
   if (!model->d_lik) {   // {variance, Adam m, Adam v}
     if (hipMalloc((void**)&model->d_lik, 3 * sizeof(double)) != hipSuccess) return ctx_fail(ctx, DCGP_ERR_ALLOC, "set_likelihood: device allocation failed");
     const double init[3] = {variance, 0.0, 0.0};
@@ -698,9 +698,9 @@ int elbo_forward_enqueue_impl(dcgp_model* model, const double* X, const int32_t*
                               bool pipelined, const double* yf) {
   if (!model || !X || !(y || yf) || N <= 0 || !ticket) return model ? ctx_fail(model->ctx, DCGP_ERR_ARG, "elbo_forward: bad args") : DCGP_ERR_ARG;
   dcgp_ctx* ctx = model->ctx;
-  if ((model->lik_kind == 1) != (yf != nullptr))
-    return ctx_fail(ctx, DCGP_ERR_ARG, model->lik_kind == 1 ? "elbo_forward: a Gaussian-likelihood model takes float64 targets (the _f64y entry points)"
-                                                            : "elbo_forward: a RobustMax model takes int32 labels, not float64 targets");
+  if (model->float_targets() != (yf != nullptr))
+    return ctx_fail(ctx, DCGP_ERR_ARG, model->float_targets() ? "elbo_forward: a Gaussian- or Bernoulli-likelihood model takes float64 targets (the _f64y entry points)"
+                                                              : "elbo_forward: a RobustMax model takes int32 labels, not float64 targets");
   if (model->enq_seq - model->col_seq >= (uint64_t)dcgp_model::RING)
     return ctx_fail(ctx, DCGP_ERR_ARG, "elbo_forward_enqueue: %d steps in flight, collect the oldest first", dcgp_model::RING);
   if (!model->h_ring) {
@@ -745,12 +745,14 @@ int elbo_forward_enqueue_impl(dcgp_model* model, const double* X, const int32_t*
     // 0.1416 -> 0.1462, conv + head +2 us (profiles/r06_tail_ride_and_prep_ab.txt): two levels of agent-scope release/acquire at the end of 200
     // workgroups cost more than the 13 us launch they replace.)
     // expectations, their sum, the KL pieces where the chain left their ingredients, and the ELBO assembly in one launch
-    if (yf) DCGP_TRY(gauss_elbo_tail(ctx, o.mean, o.var, yf, rows, N, H.R, model->d_lik, model->d_ve, inv_s, scal, fin, klt));
+    if (model->lik_kind == 1) DCGP_TRY(gauss_elbo_tail(ctx, o.mean, o.var, yf, rows, N, H.R, model->d_lik, model->d_ve, inv_s, scal, fin, klt));
+    else if (model->lik_kind == 2) DCGP_TRY(bern_elbo_tail(ctx, o.mean, o.var, yf, rows, N, H.R, model->d_ve, inv_s, scal, fin, klt));
     else DCGP_TRY(elbo_tail(ctx, o.mean, o.var, y, rows, N, H.R, model->eps, model->d_ve, inv_s, scal, fin, klt));
   } else {
     // multi-GPU: the data term is summed over the ranks between the reduction and the assembly
     ElboFinish none;
-    if (yf) DCGP_TRY(gauss_elbo_tail(ctx, o.mean, o.var, yf, rows, N, H.R, model->d_lik, model->d_ve, inv_s, scal, none, klt));
+    if (model->lik_kind == 1) DCGP_TRY(gauss_elbo_tail(ctx, o.mean, o.var, yf, rows, N, H.R, model->d_lik, model->d_ve, inv_s, scal, none, klt));
+    else if (model->lik_kind == 2) DCGP_TRY(bern_elbo_tail(ctx, o.mean, o.var, yf, rows, N, H.R, model->d_ve, inv_s, scal, none, klt));
     else DCGP_TRY(elbo_tail(ctx, o.mean, o.var, y, rows, N, H.R, model->eps, model->d_ve, inv_s, scal, none, klt));
     // A step kept in flight: collective and assembly go to the comm stream behind one event, and the main stream is free for the next step's
     // data path at once -- in stream, a 1-double ncclAllReduce (~20 us of latency over xGMI, more when a rank is late) sat in front of the next
@@ -888,7 +890,7 @@ int dcgp_model_predict_y(dcgp_model* model, const double* X, int N, int S, const
   if (!model || !X || N <= 0 || S <= 0 || (!out_p && !out_p_mean))
     return model ? ctx_fail(model->ctx, DCGP_ERR_ARG, "predict_y: bad args") : DCGP_ERR_ARG;
   dcgp_ctx* ctx = model->ctx;
-  if (model->lik_kind != 0) return ctx_fail(ctx, DCGP_ERR_ARG, "predict_y: class probabilities of a Gaussian-likelihood model (dcgp_model_predict_mean_var)");
+  if (model->lik_kind != 0) return ctx_fail(ctx, DCGP_ERR_ARG, "predict_y: a Gaussian- or Bernoulli-likelihood model predicts with dcgp_model_predict_mean_var");
   if (info_host) *info_host = 0;
   int rows = 0;
   StreamGuard guard(ctx);
@@ -918,14 +920,15 @@ int dcgp_model_predict_mean_var(dcgp_model* model, const double* X, int N, int S
   if (!model || !X || N <= 0 || S <= 0 || (!out_mean && !out_var))
     return model ? ctx_fail(model->ctx, DCGP_ERR_ARG, "predict_mean_var: bad args") : DCGP_ERR_ARG;
   dcgp_ctx* ctx = model->ctx;
-  if (model->lik_kind != 1) return ctx_fail(ctx, DCGP_ERR_ARG, "predict_mean_var: not a Gaussian-likelihood model (dcgp_model_predict_y)");
+  if (!model->float_targets()) return ctx_fail(ctx, DCGP_ERR_ARG, "predict_mean_var: not a Gaussian- or Bernoulli-likelihood model (dcgp_model_predict_y)");
   if (info_host) *info_host = 0;
   int rows = 0;
   StreamGuard guard(ctx);
   DCGP_TRY(forward_all(model, X, N, S, z_per_layer_host, seed, 0, false, false, &rows));
   DCGP_TRY(forward_done(model, nullptr));   // this call synchronises the stream before it returns
   auto& o = model->outs.back();
-  DCGP_TRY(gauss_predict(ctx, o.mean, o.var, (long)rows * o.width, model->d_lik, out_mean, out_var));
+  if (model->lik_kind == 2) DCGP_TRY(bern_predict(ctx, o.mean, o.var, (long)rows * o.width, out_mean, out_var));
+  else DCGP_TRY(gauss_predict(ctx, o.mean, o.var, (long)rows * o.width, model->d_lik, out_mean, out_var));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return read_info(model, info_host);
 }
@@ -941,8 +944,9 @@ namespace {
 //   (layer_impl.h: ev_aux).  The chain of a batch (factor_reuse 0, or the first batch) writes the parameter-only state of its bank
 //   on its own stream: done_ev[bank] -- recorded on the main stream behind the tail of the last batch on that bank -- orders it.
 //   Workspaces: batch 0 is the largest, every later request is served by what it grew.
-// yf (Gaussian model, y == nullptr): targets [N_total][K]; out_p_mean is then the sample-mean prediction [N_total][K], out_ld_nd (may be
-// nullptr) the log density per (image, output), and out_host[0] the sum of the squared errors of the sample-mean prediction.
+// yf (Gaussian or Bernoulli model, y == nullptr): targets [N_total][K]; out_p_mean is then the sample-mean prediction (Bernoulli: the
+// sample-mean p) [N_total][K], out_ld_nd (may be nullptr) the log density per (image, output), and out_host[0] the sum of the squared
+// errors of the sample-mean prediction (Bernoulli: the number of correct (image, output) entries; per image in sqerr, summed alike).
 int evaluate_impl(dcgp_model* model, const double* X, const int32_t* y, int N_total, int batch, int S, const double* const* zs,
                   uint64_t seed, double* out_logdens, double* out_p_mean, double* out_host, int* info_host, const char* who,
                   const double* yf = nullptr, double* out_ld_nd = nullptr) {
@@ -951,9 +955,9 @@ int evaluate_impl(dcgp_model* model, const double* X, const int32_t* y, int N_to
   if (info_host) *info_host = 0;
   if (!X || !(y || yf) || N_total <= 0 || batch <= 0 || S <= 0 || !out_host)
     return ctx_fail(ctx, DCGP_ERR_ARG, "%s: bad args (N %d, batch %d, S %d)", who, N_total, batch, S);
-  if ((model->lik_kind == 1) != (yf != nullptr))
-    return ctx_fail(ctx, DCGP_ERR_ARG, model->lik_kind == 1 ? "%s: a Gaussian-likelihood model takes float64 targets (the _f64y entry points)"
-                                                            : "%s: a RobustMax model takes int32 labels, not float64 targets", who);
+  if (model->float_targets() != (yf != nullptr))
+    return ctx_fail(ctx, DCGP_ERR_ARG, model->float_targets() ? "%s: a Gaussian- or Bernoulli-likelihood model takes float64 targets (the _f64y entry points)"
+                                                              : "%s: a RobustMax model takes int32 labels, not float64 targets", who);
   if (!model->has_head) return ctx_fail(ctx, DCGP_ERR_ARG, "model has no head layer");
   const int nl = (int)model->layers.size();
   const int K = model->layers[nl - 1]->R;
@@ -985,7 +989,8 @@ int evaluate_impl(dcgp_model* model, const double* X, const int32_t* y, int N_to
     DCGP_TRY(forward_all(model, X + lo * in_len, n, S, zs ? zb.data() : nullptr, seed + (uint64_t)b, 0, false, false, &rows));
     const auto& o = model->outs[nl - 1];
     if (rows != S * n || o.width != K) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: head rows %d x %d, expected %d x %d", who, rows, o.width, S * n, K);
-    if (yf) DCGP_TRY(gauss_eval_tail(ctx, o.mean, o.var, yf + lo * K, n, S, K, model->d_lik, lo, ld, out_ld_nd, out_p_mean, sqerr));
+    if (model->lik_kind == 1) DCGP_TRY(gauss_eval_tail(ctx, o.mean, o.var, yf + lo * K, n, S, K, model->d_lik, lo, ld, out_ld_nd, out_p_mean, sqerr));
+    else if (model->lik_kind == 2) DCGP_TRY(bern_eval_tail(ctx, o.mean, o.var, yf + lo * K, n, S, K, lo, ld, out_ld_nd, out_p_mean, sqerr));
     else DCGP_TRY(eval_tail(ctx, o.mean, o.var, y + lo, n, S, K, model->eps, lo, ld, out_p_mean, ok));
     HIP_TRY(ctx, hipEventRecord(model->ev_eval[model->bank], ctx->stream));
     DCGP_TRY(forward_done(model, model->ev_eval[model->bank]));

@@ -7,10 +7,11 @@ struct dcgp_model {
   int S = 1;
   double jitter = 1e-3;
   double eps = 1e-3;   // RobustMax epsilon (conv_gp/models.py:67 keeps gpflow's default)
-  // likelihood (dcgp_model_set_likelihood): 0 RobustMax (labels, int32), 1 Gaussian (targets [N][K] float64).  The Gaussian variance lives
-  // on the device (d_lik[0]; the tails and the optimiser read and write it there), its Adam moments in d_lik[1], d_lik[2] and its gradient in
-  // the last slot of the head's gradient block (LayerState::glik)
+  // likelihood (dcgp_model_set_likelihood): 0 RobustMax (labels, int32), 1 Gaussian, 2 Bernoulli (probit) (targets [N][K] float64).  The
+  // Gaussian variance lives on the device (d_lik[0]; the tails and the optimiser read and write it there), its Adam moments in d_lik[1],
+  // d_lik[2] and its gradient in the last slot of the head's gradient block (LayerState::glik).  Bernoulli has no parameter: no d_lik, no slot.
   int lik_kind = 0;
+  bool float_targets() const { return lik_kind != 0; }   // the _f64y entry points
   double* d_lik = nullptr;
   bool lik_frozen = false;   // dcgp_model_set_trainable(.., "likelihood_variance", 0)
   std::vector<std::unique_ptr<LayerState>> layers;   // conv layers..., head last (once set)

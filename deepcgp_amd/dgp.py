@@ -11,7 +11,7 @@ import numpy as np
 from . import device as dev
 from .kernels import JITTER
 from .layers import ConvLayer, SVGP_Layer
-from .likelihoods import Gaussian
+from .likelihoods import Bernoulli, Gaussian
 
 
 def batched_noise(zs, N, S, batch_size, dims=None):
@@ -52,7 +52,9 @@ class DGP_Base:
         self.likelihood = likelihood
         self.layers = list(layers)
         self.gaussian = isinstance(likelihood, Gaussian)
-        self.Y = self._targets_host(Y) if self.gaussian else np.ascontiguousarray(np.reshape(Y, (-1,)), np.int32)
+        self.bernoulli = isinstance(likelihood, Bernoulli)
+        self.float_targets = self.gaussian or self.bernoulli     # float64 N x D targets and the _f64y entry points
+        self.Y = self._targets_host(Y) if self.float_targets else np.ascontiguousarray(np.reshape(Y, (-1,)), np.int32)
         self.num_samples = int(num_samples)
         self.minibatch_size = minibatch_size
         self.name = name
@@ -69,23 +71,28 @@ class DGP_Base:
                 raise ValueError("hidden layers must be ConvLayer instances")
 
     def _targets_host(self, Y, n=None):
-        """Gaussian likelihood: float64 targets N x D, D the head's num_outputs."""
+        """Gaussian or Bernoulli likelihood: float64 targets N x D, D the head's num_outputs (Bernoulli: bool, int or float
+        values in {0, 1})."""
         D = self.layers[-1].num_outputs
-        Y = np.asarray(Y, np.float64)
+        kind = "Gaussian" if self.gaussian else "Bernoulli"
+        Y = np.asarray(Y)
+        if self.bernoulli and Y.size and not np.all((Y == 0) | (Y == 1)):
+            raise ValueError("Bernoulli likelihood: targets must be 0 or 1")
+        Y = Y.astype(np.float64)
         if Y.ndim == 1 and D == 1:
             Y = Y[:, None]
         if Y.ndim != 2 or Y.shape[1] != D:
-            raise ValueError("Gaussian likelihood: targets must be N x %d (the head's num_outputs), got shape %r" % (D, np.shape(Y)))
+            raise ValueError("%s likelihood: targets must be N x %d (the head's num_outputs), got shape %r" % (kind, D, np.shape(Y)))
         if n is not None and Y.shape[0] != n:
             raise ValueError("%d targets for %d images" % (Y.shape[0], n))
         return np.ascontiguousarray(Y)
 
     def _targets(self, Y, N):
-        """(device targets, Gaussian?) of an explicit minibatch: float64 N x D or int32 labels."""
-        if self.gaussian:
+        """(device targets, float64?) of an explicit minibatch: float64 N x D (Gaussian, Bernoulli) or int32 labels."""
+        if self.float_targets:
             if isinstance(Y, dev.DeviceArray):
                 if Y.dtype != np.float64 or int(np.prod(Y.shape)) != N * self.layers[-1].num_outputs:
-                    raise ValueError("Gaussian likelihood: device targets must be float64 N x %d" % self.layers[-1].num_outputs)
+                    raise ValueError("float-target likelihood: device targets must be float64 N x %d" % self.layers[-1].num_outputs)
                 return Y, True
             return self._ctx.to_device(self._targets_host(Y, N)), True
         return self._ctx.as_device(np.reshape(Y, (-1,)) if not isinstance(Y, dev.DeviceArray) else Y, np.int32), False
@@ -159,6 +166,8 @@ class DGP_Base:
         ctx._check(L.dcgp_model_set_param(self._model, 0, b"likelihood_epsilon", eps.ctypes.data, 1))
         if self.gaussian:
             ctx._check(L.dcgp_model_set_likelihood(self._model, 1, float(self.likelihood.variance)))
+        elif self.bernoulli:
+            ctx._check(L.dcgp_model_set_likelihood(self._model, 2, 0.0))
 
     def sync_parameters(self):
         """Push the current Python-side parameter values to the device copy."""
@@ -242,13 +251,13 @@ class DGP_Base:
         ctx, L = self._ctx, dev.lib()
         dX = ctx.as_device(np.reshape(X, (np.shape(X)[0], -1)) if not isinstance(X, dev.DeviceArray) else X)
         N = dX.shape[0]
-        dY, gauss = self._targets(Y, N)
+        dY, f64y = self._targets(Y, N)
         if scale is None:
             scale = self._default_scale(N)
         arr, keep = self._z_table(zs, N, self.num_samples)
         out = (C.c_double * 3)()
         info = C.c_int(0)
-        rc = (L.dcgp_elbo_forward_f64y if gauss else L.dcgp_elbo_forward)(self._model, dX.ptr, dY.ptr, N, float(scale), arr, int(seed), int(self.dedup_layer0), out, C.byref(info))
+        rc = (L.dcgp_elbo_forward_f64y if f64y else L.dcgp_elbo_forward)(self._model, dX.ptr, dY.ptr, N, float(scale), arr, int(seed), int(self.dedup_layer0), out, C.byref(info))
         ctx._check(rc, info)
         if return_parts:
             return out[0], out[1], out[2]
@@ -263,12 +272,12 @@ class DGP_Base:
         ctx, L = self._ctx, dev.lib()
         dX = ctx.as_device(np.reshape(X, (np.shape(X)[0], -1)) if not isinstance(X, dev.DeviceArray) else X)
         N = dX.shape[0]
-        dY, gauss = self._targets(Y, N)
+        dY, f64y = self._targets(Y, N)
         if scale is None:
             scale = self._default_scale(N)
         arr, keep = self._z_table(zs, N, self.num_samples)
         ticket = C.c_uint64(0)
-        ctx._check((L.dcgp_elbo_forward_enqueue_f64y if gauss else L.dcgp_elbo_forward_enqueue)(self._model, dX.ptr, dY.ptr, N, float(scale), arr, int(seed), int(self.dedup_layer0),
+        ctx._check((L.dcgp_elbo_forward_enqueue_f64y if f64y else L.dcgp_elbo_forward_enqueue)(self._model, dX.ptr, dY.ptr, N, float(scale), arr, int(seed), int(self.dedup_layer0),
                                                C.byref(ticket)))
         if not hasattr(self, "_inflight"):
             self._inflight = {}
@@ -297,7 +306,7 @@ class DGP_Base:
         ctx, L = self._ctx, dev.lib()
         dX = ctx.as_device(np.reshape(X, (np.shape(X)[0], -1)) if not isinstance(X, dev.DeviceArray) else X)
         N = dX.shape[0]
-        dY, gauss = self._targets(Y, N)
+        dY, f64y = self._targets(Y, N)
         if scale is None:
             scale = self._default_scale(N)
         arr, keep = self._z_table(zs, N, self.num_samples)
@@ -306,7 +315,7 @@ class DGP_Base:
         # this call handles one of `shards` batch shards: the replicated KL term is weighted 1 / shards; None = the rank
         # count of the ctx's communicator (1 without one).  Always passed, so that it never sticks from an earlier call.
         ctx._check(L.dcgp_model_set_grad_shards(self._model, int(shards or 0)))
-        ctx._check((L.dcgp_elbo_grad_f64y if gauss else L.dcgp_elbo_grad)(self._model, dX.ptr, dY.ptr, N, float(scale), arr, int(seed), int(self.dedup_layer0), out,
+        ctx._check((L.dcgp_elbo_grad_f64y if f64y else L.dcgp_elbo_grad)(self._model, dX.ptr, dY.ptr, N, float(scale), arr, int(seed), int(self.dedup_layer0), out,
                                     C.byref(info)), info)
         if not fetch:            # the gradients stay on the device (dcgp_model_get_grad / the optimiser step read them there)
             return out[0], None
@@ -329,7 +338,7 @@ class DGP_Base:
                 ctx._check(L.dcgp_model_get_grad(self._model, li, which.encode(), buf.ctypes.data, buf.size))
                 g[{"lengthscale": "lengthscales", "ard_lengthscales": "lengthscales", "w": "patch_weights"}.get(which, which)] = buf
             grads.append(g)
-        if gauss:                # d ELBO / d likelihood variance, with the head's gradients
+        if self.gaussian:        # d ELBO / d likelihood variance, with the head's gradients
             buf = np.empty(1, np.float64)
             ctx._check(L.dcgp_model_get_grad(self._model, 0, b"likelihood_variance", buf.ctypes.data, 1))
             grads[-1]["likelihood_variance"] = buf.reshape(())
@@ -353,14 +362,14 @@ class DGP_Base:
         ctx, L = self._ctx, dev.lib()
         dX = ctx.as_device(np.reshape(X, (np.shape(X)[0], -1)) if not isinstance(X, dev.DeviceArray) else X)
         N = dX.shape[0]
-        dY, gauss = self._targets(Y, N)
+        dY, f64y = self._targets(Y, N)
         if scale is None:
             scale = self._default_scale(N)
         arr, keep = self._z_table(zs, N, self.num_samples)
         out = (C.c_double * 3)()
         info = C.c_int(0)
         ctx._check(L.dcgp_model_set_grad_shards(self._model, int(shards or 0)))
-        ctx._check((L.dcgp_model_train_step_adam_f64y if gauss else L.dcgp_model_train_step_adam)(self._model, dX.ptr, dY.ptr, N, float(scale), arr, int(seed), int(self.dedup_layer0),
+        ctx._check((L.dcgp_model_train_step_adam_f64y if f64y else L.dcgp_model_train_step_adam)(self._model, dX.ptr, dY.ptr, N, float(scale), arr, int(seed), int(self.dedup_layer0),
                                                 float(lr), float(beta1), float(beta2), float(epsilon), int(t or 0), out, C.byref(info)), info)
         return out[0]
 
@@ -550,16 +559,17 @@ class DGP_Base:
     def predict_y(self, X, S, zs=None, seed=0):
         """(mean, var) of p(y*) per sample: S x N x num_classes (used at conv_gp/utils/log.py:62-66).
         One device call: forward pass and RobustMax quadrature, only the probabilities come back.  Gaussian likelihood:
-        (Fmean, Fvar + variance), each S x N x D (dcgp_model_predict_mean_var)."""
+        (Fmean, Fvar + variance), each S x N x D (dcgp_model_predict_mean_var); Bernoulli: (p, p - p^2) with
+        p = probit(Fmean / sqrt(1 + Fvar)), each S x N x D."""
         if np.shape(X)[0] == 0:
             K = self.layers[-1].num_outputs
             return np.zeros((S, 0, K)), np.zeros((S, 0, K))
-        if self.gaussian:
-            return self._predict_gauss(X, S, zs, seed)
+        if self.float_targets:
+            return self._predict_mean_var(X, S, zs, seed)
         ps, _ = self._predict(X, S, zs, seed, True, False)
         return ps, ps - np.square(ps)
 
-    def _predict_gauss(self, X, S, zs, seed):
+    def _predict_mean_var(self, X, S, zs, seed):
         self._build()
         ctx, L = self._ctx, dev.lib()
         X = np.ascontiguousarray(np.reshape(X, (np.shape(X)[0], -1)), np.float64)
@@ -573,11 +583,14 @@ class DGP_Base:
 
     def predict_proba(self, X, S, zs=None, seed=0):
         """Class probabilities averaged over the S samples, N x num_classes (the quantity AccuracyLogger
-        arg-maxes, conv_gp/utils/log.py:62-67); the sample mean is taken on the device."""
+        arg-maxes, conv_gp/utils/log.py:62-67); the sample mean is taken on the device.  Bernoulli likelihood: the sample-mean
+        p(y = 1), N x D (the mean over S of ``predict_y``'s p, summed in sample order as ``evaluate`` sums it)."""
         if self.gaussian:
             raise ValueError("predict_proba: class probabilities need a classification likelihood, this model is Gaussian")
         if np.shape(X)[0] == 0:
             return np.zeros((0, self.layers[-1].num_outputs))
+        if self.bernoulli:
+            return self._predict_mean_var(X, S, zs, seed)[0].mean(0)
         return self._predict(X, S, zs, seed, False, True)[1]
 
     def predict_f(self, X, S, zs=None, seed=0):
@@ -599,8 +612,8 @@ class DGP_Base:
         N, K = X.shape[0], self.layers[-1].num_outputs
         if X.shape[1] != self.X.shape[1]:
             raise ValueError("images of %d values, the model takes %d" % (X.shape[1], self.X.shape[1]))
-        if self.gaussian:
-            return self._eval_call_gauss(X, self._targets_host(Y, N), S, batch_size, seed, flat_zs, want_p_mean, density_only)
+        if self.float_targets:
+            return self._eval_call_f64y(X, self._targets_host(Y, N), S, batch_size, seed, flat_zs, want_p_mean, density_only)
         Y = np.ascontiguousarray(np.reshape(Y, (-1,)), np.int32)
         if Y.size != N:
             raise ValueError("%d labels for %d images" % (Y.size, N))
@@ -625,7 +638,7 @@ class DGP_Base:
         ctx._check(rc, info)
         return ld.numpy(), (pm.numpy() if pm else None), (out[0], out[1])
 
-    def _eval_call_gauss(self, X, Y, S, batch_size, seed, flat_zs, want_y_mean, density_only):
+    def _eval_call_f64y(self, X, Y, S, batch_size, seed, flat_zs, want_y_mean, density_only):
         ctx, L = self._ctx, dev.lib()
         N, D = X.shape[0], self.layers[-1].num_outputs
         dX, dY = ctx.to_device(X), ctx.to_device(Y)
@@ -651,12 +664,13 @@ class DGP_Base:
     def predict_density(self, X, Y, S, zs=None, seed=0):
         """Log predictive density of each label, N x 1: logsumexp_s log p(y | f_s) - log S (doubly_stochastic_dgp
         DGP_Base.predict_density with the RobustMax likelihood).  Gaussian likelihood: N x D, per output
-        logsumexp_s log N(y; Fmean_s, Fvar_s + variance) - log S.  One device call; ``zs`` per layer [S, N, D]."""
+        logsumexp_s log N(y; Fmean_s, Fvar_s + variance) - log S; Bernoulli: N x D, per output logsumexp_s log p(y | p_s) - log S with
+        p_s = probit(Fmean_s / sqrt(1 + Fvar_s)).  One device call; ``zs`` per layer [S, N, D]."""
         N = np.shape(X)[0]
         if N == 0:
-            return np.zeros((0, self.layers[-1].num_outputs if self.gaussian else 1))
+            return np.zeros((0, self.layers[-1].num_outputs if self.float_targets else 1))
         ld, _, _ = self._eval_call(X, Y, S, N, seed, batched_noise(zs, N, S, N, self._out_dims()), False, density_only=True)
-        return ld if self.gaussian else ld.reshape(N, 1)
+        return ld if self.float_targets else ld.reshape(N, 1)
 
     def evaluate(self, X, Y, S=5, batch_size=32, seed=0, zs=None, per_image=False):
         """A whole test set in one device call (dcgp_model_evaluate): batches of ``batch_size`` images, batch i drawing its noise
@@ -664,7 +678,9 @@ class DGP_Base:
         Returns {"accuracy", "mean_log_density", "n"}, with ``per_image`` also "log_density" [N] and "p_mean" [N, K] (the
         sample-mean class probabilities).  Gaussian likelihood: {"mean_log_density", "rmse", "n"} (the root mean squared error of the
         sample-mean prediction over all N x D targets), with ``per_image`` also "log_density" [N] (summed over the D outputs) and
-        "y_mean" [N, D].  Rank-local: nothing is reduced across ranks."""
+        "y_mean" [N, D].  Bernoulli likelihood: {"accuracy", "mean_log_density", "n"}, the accuracy over all N x D entries (an entry is
+        correct when its label is 1 exactly where the sample-mean p > 0.5), with ``per_image`` also "log_density" [N] (summed over the
+        D outputs) and "p_mean" [N, D] (the sample-mean p).  Rank-local: nothing is reduced across ranks."""
         N = np.shape(X)[0]
         if int(batch_size) <= 0:
             raise ValueError("batch_size must be positive, got %r" % (batch_size,))
@@ -688,7 +704,8 @@ class DGP_Base:
             return out
         ld, pm, (correct, total) = self._eval_call(X, Y, S, batch_size, seed, batched_noise(zs, N, S, int(batch_size), self._out_dims()),
                                                  per_image)
-        out = {"accuracy": correct / N, "mean_log_density": total / N, "n": N}
+        entries = N * self.layers[-1].num_outputs if self.bernoulli else N
+        out = {"accuracy": correct / entries, "mean_log_density": total / N, "n": N}
         if per_image:
             out["log_density"], out["p_mean"] = ld, pm
         return out

@@ -66,3 +66,51 @@ class Gaussian:
         Fmu, Fvar, Y = (np.asarray(a, np.float64) for a in (Fmu, Fvar, Y))
         v = Fvar + self.variance
         return -0.5 * np.log(2 * np.pi * v) - 0.5 * np.square(Y - Fmu) / v
+
+
+def _probit(x):
+    """gpflow 1.x likelihoods.probit: Phi(x) jittered into [1e-3, 1 - 1e-3], so that every log is finite."""
+    from math import erf
+    x = np.asarray(x, np.float64)
+    return 0.5 * (1.0 + np.vectorize(erf, otypes=[np.float64])(x / np.sqrt(2.0))) * (1 - 2e-3) + 1e-3
+
+
+class Bernoulli:
+    """gpflow 1.x likelihoods.Bernoulli(invlink=probit) as DS-DGP's BroadcastingLikelihood applies it: every output an independent
+    binary label, float64 targets N x D with Y == 1 positive and anything else negative (gpflow's logdensities.bernoulli).  No
+    trainable parameters.  On the model path (DGP_Base with this likelihood) every tail runs on the device (csrc/bernoulli.hip);
+    these methods are the same quantities on host arrays, the variational expectations by gpflow's 20-point Gauss-Hermite rule."""
+    num_gauss_hermite_points = 20
+
+    def __init__(self, invlink="probit"):
+        if invlink != "probit":
+            raise ValueError("Bernoulli: only the probit link is supported, got %r" % (invlink,))
+        self.invlink = invlink
+
+    def conditional_mean(self, F):
+        return _probit(F)
+
+    def conditional_variance(self, F):
+        p = _probit(F)
+        return p - np.square(p)
+
+    def logp(self, F, Y):
+        p, Y = _probit(F), np.asarray(Y, np.float64)
+        return np.where(Y == 1, np.log(p), np.log(1 - p))
+
+    def variational_expectations(self, Fmu, Fvar, Y):
+        """sum_i w_i / sqrt(pi) logp(Fmu + sqrt(2 Fvar) x_i, Y) (gpflow's ndiagquad)."""
+        Fmu, Fvar, Y = (np.asarray(a, np.float64) for a in (Fmu, Fvar, Y))
+        x, w = np.polynomial.hermite.hermgauss(self.num_gauss_hermite_points)
+        F = Fmu[..., None] + np.sqrt(np.maximum(2 * Fvar, 1e-10))[..., None] * x
+        return (self.logp(F, Y[..., None]) * (w / np.sqrt(np.pi))).sum(-1)
+
+    def predict_mean_and_var(self, Fmu, Fvar):
+        Fmu, Fvar = np.asarray(Fmu, np.float64), np.asarray(Fvar, np.float64)
+        p = _probit(Fmu / np.sqrt(1 + Fvar))
+        return p, p - np.square(p)
+
+    def predict_density(self, Fmu, Fvar, Y):
+        p = self.predict_mean_and_var(Fmu, Fvar)[0]
+        Y = np.asarray(Y, np.float64)
+        return np.where(Y == 1, np.log(p), np.log(1 - p))

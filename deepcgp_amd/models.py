@@ -149,12 +149,25 @@ class AccuracyLogger(object):
     def __call__(self, model, seed=0):
         if getattr(model, "gaussian", False):
             raise ValueError("AccuracyLogger: accuracy needs a classification likelihood, this model is Gaussian")
+        if getattr(model, "bernoulli", False):
+            return self._binary(model, seed)
         correct = 0
         for i, lo in enumerate(range(0, len(self.Y_test), self.batch_size)):
             sl = slice(lo, lo + self.batch_size)
             p = model.predict_proba(self.X_test[sl], self.num_samples, seed=seed + i)
             correct += int((p.argmax(axis=1) == self.Y_test[sl]).sum())
         return correct / max(self.Y_test.size, 1)
+
+    def _binary(self, model, seed):
+        """Bernoulli likelihood: every (image, output) entry is a binary label, correct when it is 1 exactly where the sample-mean
+        p(y = 1) is > 0.5 -- ``DGP_Base.evaluate``'s accuracy, with the same batches and seeds."""
+        Y = np.reshape(self.Y_test, (len(self.X_test), -1)) == 1
+        correct = 0
+        for i, lo in enumerate(range(0, len(Y), self.batch_size)):
+            sl = slice(lo, lo + self.batch_size)
+            p = model.predict_proba(self.X_test[sl], self.num_samples, seed=seed + i)
+            correct += int(((p > 0.5) == Y[sl]).sum())
+        return correct / max(Y.size, 1)
 
 
 class TestLogDensityLogger(object):

@@ -328,11 +328,21 @@ int dcgp_model_evaluate(dcgp_model* model, const double* X, const int32_t* y, in
                         const double* const* z_per_layer, uint64_t seed, double* out_logdens, double* out_p_mean,
                         double* out_host, int* info_host);
 
-/* ---- Gaussian likelihood (gpflow 1.x likelihoods.Gaussian under DS-DGP's BroadcastingLikelihood) ----
+/* ---- Gaussian and Bernoulli likelihoods (gpflow 1.x likelihoods.Gaussian / Bernoulli under DS-DGP's BroadcastingLikelihood) ----
  * The likelihood of the model: kind 0 = RobustMax (the default; int32 labels), 1 = Gaussian with one variance s2 > 1e-6 shared by every
- * output (float64 targets y [N, K], K = the head's outputs; gpflow's transforms.positive, s2 = softplus(u) + 1e-6, in the optimiser).
- * Replaces the likelihood argument of DS-DGP DGP_Base.__init__.  Call after dcgp_model_set_head and before the first gradient.
- * On a Gaussian model the int32 entry points above (dcgp_elbo_forward, _enqueue, dcgp_elbo_grad, dcgp_model_train_step_adam,
+ * output (float64 targets y [N, K], K = the head's outputs; gpflow's transforms.positive, s2 = softplus(u) + 1e-6, in the optimiser),
+ * 2 = Bernoulli with gpflow's jittered probit link p(f) = Phi(f) (1 - 2e-3) + 1e-3 (`variance` ignored; float64 targets y [N, K], every
+ * output an independent binary label: y == 1.0 positive, anything else negative, as gpflow's tf.equal(y, 1)).  Other kinds are refused.
+ * Replaces the likelihood argument of DS-DGP DGP_Base.__init__.  Call after dcgp_model_set_head and before the first gradient: once a
+ * gradient was taken the kind is fixed.
+ * Bernoulli has no parameter: its gradient block has the RobustMax layout and length, and it has no "likelihood_variance".  Its
+ * variational expectation per (row, output) is 20-node Gauss-Hermite quadrature, sum_i w_i / sqrt(pi) log p(y | mu + sqrt(2 var) x_i)
+ * (2 var clamped at 1e-10); the gradient is the exact derivative of that sum.  On the _f64y entry points below a Bernoulli model gives:
+ * dcgp_model_predict_mean_var out_mean = p = Phi~(mu / sqrt(1 + var)) (Phi~ the jittered probit), out_var = p - p^2;
+ * dcgp_model_predict_density_f64y out_logdens [N, K] = logsumexp_s log p(y | p_s) - log S; dcgp_model_evaluate_f64y out_y_mean
+ * [N_total][K] = the sample-mean p, out_host[2] = {number of (image, output) entries whose label is 1 exactly where that mean is > 0.5,
+ * sum of the per-image log densities}.  The formulas with s2 below are kind 1's.
+ * On a Gaussian or Bernoulli model the int32 entry points above (dcgp_elbo_forward, _enqueue, dcgp_elbo_grad, dcgp_model_train_step_adam,
  * dcgp_model_predict_y, dcgp_model_predict_density, dcgp_model_evaluate) return DCGP_ERR_ARG, and so do the _f64y ones below on a
  * RobustMax model.  s2 is "likelihood_variance" in dcgp_model_set_param / _get_param / _get_grad / _set_trainable (`layer` ignored); its
  * gradient is the last slot of the head's gradient block (dcgp_model_grad_block), after the ARD lengthscales. */
