@@ -56,8 +56,6 @@ struct DcgpOptions {
   long no_side_stream = 0;       // everything on one stream (counter collection: the profiler serialises dispatches)
   long cu_partition = 0;         // CU-masked main / side streams for steps in flight (ctx create only)
   long grad_nofork = 0;          // reverse pass without the side-stream fork of the M x M adjoint chains
-  long chol_one_launch = 0;      // the persistent one-launch factorisation chain
-  long chol_no_lookahead = 0;    // panel launches without the look-ahead workgroup
   long head_no_overlap = 0;      // head-first model: the factorisation chain in front of the sweep instead of beside it
   long no_factor_reuse = 0;      // evaluation entry points run the parameter-only chain every time, also at unchanged parameters (A/B)
   long prep_on_chain = 0;        // head-first model: the operand preparation on the chain's stream instead of in front of the sweep on the main stream (A/B)
@@ -65,7 +63,6 @@ struct DcgpOptions {
                                  // instead of one launch per stream (A/B)
   long no_early_sweep = 0;       // the first layer's sweep enqueued behind the chain instead of in front of it
   long sync_event = 0;           // wait for the step's event instead of polling its completion word
-  long chain_graph = 0;          // the factorisation chain's panel launches replayed from a captured HIP graph (measured slower: see chol_fused.hip)
   long chain_no_iso = 0;         // chain launches that carry right-hand sides: no XCD isolation of the look-ahead workgroups (A/B)
   long comm_inline = 0;          // multi-rank steps in flight: the data term's all-reduce in the main stream instead of the comm stream (A/B)
   long no_rhs_ride = 0;          // G / alpha by their own launch behind the chain (prep_solve) instead of riding its panel launches
@@ -86,8 +83,6 @@ long* dcgp_option_slot(DcgpOptions* o, const char* name);   // nullptr: no such 
 // debugging aid, process-wide, DCGP_POISON_WS read once: fresh device allocations of the library are filled with NaNs;
 // `name` != nullptr additionally applies DCGP_POISON_ONLY (only workspaces whose name contains that string)
 bool dcgp_poison(const char* name = nullptr);
-
-struct ChainEpoch { unsigned epoch = 0; int T = 0, np = 0, batch = 0; };   // launches so far of the one-launch factorisation chain on a sync area
 
 struct KlTail;   // layer.h
 struct dcgp_ctx {
@@ -126,9 +121,7 @@ struct dcgp_ctx {
   hipEvent_t ev_g[6] = {};
   hipEvent_t ev_aux = nullptr, ev_aux2 = nullptr;  // fork / join of a short side-stream excursion inside a layer
   std::string err;
-  std::map<std::string, hipGraphExec_t> chain_graphs;   // captured panel-launch sequences of the factorisation chain, by argument set (chol_fused.hip)
   std::map<std::string, unsigned> fused_pre_epochs;   // per hand-over area of the layer kernel's prologues ahead (conv_fused.hip): launches so far
-  std::map<std::string, ChainEpoch> chain_epochs;   // per sync workspace of chol_persist_kernel (chol_fused.hip)
   bool chain_alone = true;   // the factorisation chain about to run has the chip to itself (forward_all: synchronous step, chain on the main stream): the
                              // look-ahead workgroups are then confined to one XCD.  Beside a patch sweep or the previous step's layer kernel that
                              // confinement costs more than it saves (head-only model 4250 -> 3190 steps/s without the riding right-hand sides)

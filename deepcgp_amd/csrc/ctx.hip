@@ -24,10 +24,9 @@ const OptSlot kOptSlots[] = {
     {"kl_side", &DcgpOptions::kl_side}, {"kl_no_ride", &DcgpOptions::kl_no_ride}, {"sweep_no_rows", &DcgpOptions::sweep_no_rows}, {"no_fused_bwd", &DcgpOptions::no_fused_bwd}, {"fused_bwd_min_cols", &DcgpOptions::fused_bwd_min_cols},
     {"fused_bwd_frags", &DcgpOptions::fused_bwd_frags}, {"grad_late_kl", &DcgpOptions::grad_late_kl}, {"gemm_tile", &DcgpOptions::gemm_tile}, {"grad_no_keep_k", &DcgpOptions::grad_no_keep_k},
     {"head_unfused", &DcgpOptions::head_unfused}, {"no_side_stream", &DcgpOptions::no_side_stream}, {"cu_partition", &DcgpOptions::cu_partition},
-    {"grad_nofork", &DcgpOptions::grad_nofork}, {"chol_one_launch", &DcgpOptions::chol_one_launch},
-    {"chol_no_lookahead", &DcgpOptions::chol_no_lookahead}, {"head_no_overlap", &DcgpOptions::head_no_overlap},
+    {"grad_nofork", &DcgpOptions::grad_nofork}, {"head_no_overlap", &DcgpOptions::head_no_overlap},
     {"no_early_sweep", &DcgpOptions::no_early_sweep}, {"prep_on_chain", &DcgpOptions::prep_on_chain}, {"prep_one_launch", &DcgpOptions::prep_one_launch}, {"no_factor_reuse", &DcgpOptions::no_factor_reuse}, {"sync_event", &DcgpOptions::sync_event}, {"kuf_upw", &DcgpOptions::kuf_upw},
-    {"chain_graph", &DcgpOptions::chain_graph}, {"no_rhs_ride", &DcgpOptions::no_rhs_ride}, {"comm_inline", &DcgpOptions::comm_inline}, {"chain_no_iso", &DcgpOptions::chain_no_iso}, {"kuf_no_rep", &DcgpOptions::kuf_no_rep}, {"kuf_stream", &DcgpOptions::kuf_stream},
+    {"no_rhs_ride", &DcgpOptions::no_rhs_ride}, {"comm_inline", &DcgpOptions::comm_inline}, {"chain_no_iso", &DcgpOptions::chain_no_iso}, {"kuf_no_rep", &DcgpOptions::kuf_no_rep}, {"kuf_stream", &DcgpOptions::kuf_stream},
     {"kuf_wpg", &DcgpOptions::kuf_wpg}, {"kuf_split", &DcgpOptions::kuf_split}, {"head_tail", &DcgpOptions::head_tail},
     {"sweep_occ", &DcgpOptions::sweep_occ}, {"share_kb", &DcgpOptions::share_kb}, {"head_upw", &DcgpOptions::head_upw}, {"no_syrk", &DcgpOptions::no_syrk}, {"grad_dz_main", &DcgpOptions::grad_dz_main},
     {"fused_persist", &DcgpOptions::fused_persist}, {"fused_stagger", &DcgpOptions::fused_stagger}, {"fused_pre", &DcgpOptions::fused_pre}, {"fused_parts", &DcgpOptions::fused_parts},
@@ -225,7 +224,6 @@ int dcgp_ctx_destroy(dcgp_ctx* ctx) {
   hipSetDevice(ctx->device);
   hipDeviceSynchronize();
   dcgp_comm_destroy(ctx);
-  for (auto& kv : ctx->chain_graphs) hipGraphExecDestroy(kv.second);
   for (auto& kv : ctx->ws) hipFree(kv.second.first);
   for (auto& pe : ctx->pending) {
     hipEventDestroy(pe.start);

@@ -508,8 +508,6 @@ int dcgp_model_destroy(dcgp_model* model) {
       ++it;
     }
   }
-  for (auto it = ctx->chain_epochs.begin(); it != ctx->chain_epochs.end();)   // sync areas of the one-launch chain: gone with their workspaces
-    it = (it->first.find(tag) != std::string::npos) ? ctx->chain_epochs.erase(it) : std::next(it);
   if (ctx->ws_tag.find(tag) != std::string::npos) ctx->ws_tag.clear();   // operator calls behind this model must not name scratch after it
   delete model;
   return DCGP_OK;
