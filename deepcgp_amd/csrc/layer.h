@@ -222,6 +222,13 @@ int bern_predict(dcgp_ctx* ctx, const double* mu, const double* var, long n, dou
 int bern_eval_tail(dcgp_ctx* ctx, const double* mu, const double* var, const double* y, int n, int S, int K, long lo, double* logdens,
                    double* ld_nd, double* p_mean, double* correct);
 
+// patch_map.hip: per-patch evidence maps of a patch head with an RBF base kernel, out [rows][P][R] = (w_p / P) sum_m k(z_m, x_n[p]) beta[m][r]
+// (row n shows X[n % n_mod]); asynchronous on ctx->stream.  ZS: the sweeps' operand of Z (sweep_dev.h) or nullptr (built from Z).  beta [M][R],
+// or nullptr: beta = LinvT alpha from a layer's own factors (alpha [Mp][Rpa] = inv(L) q_mu, q_mu itself when whitened).
+int patch_map(dcgp_ctx* ctx, const double* X, long rows, int n_mod, const ViewGeom& v, const double* Z, const double* ZS, int M, double variance,
+              double lengthscale, const double* w, const double* beta, const double* LinvT, const double* alpha, int Rpa, int R, double* out,
+              const std::string& pfx);
+
 // deterministic single-block sum of n doubles, scaled: out[0] = scale * sum
 int reduce_sum(dcgp_ctx* ctx, const double* in, long n, double scale, double* out);
 constexpr int REDUCE_JOBS_MAX = 12;

@@ -931,6 +931,36 @@ int dcgp_model_predict_mean_var(dcgp_model* model, const double* X, int N, int S
   return read_info(model, info_host);
 }
 
+int dcgp_model_patch_evidence(dcgp_model* model, const double* X, int N, int S, const double* const* z_per_layer_host, uint64_t seed,
+                              double* out_c, double* out_fmean, int* info_host) {
+  if (!model) return DCGP_ERR_ARG;
+  dcgp_ctx* ctx = model->ctx;
+  if (info_host) *info_host = 0;
+  if (N < 0 || S <= 0) return ctx_fail(ctx, DCGP_ERR_ARG, "patch_evidence: bad args (N %d, S %d)", N, S);
+  if (!model->has_head) return ctx_fail(ctx, DCGP_ERR_ARG, "model has no head layer");
+  const int nl = (int)model->layers.size();
+  LayerState& H = *model->layers[nl - 1];
+  if (H.in_scale || (H.v.H == 1 && H.v.W == 1))
+    return ctx_fail(ctx, DCGP_ERR_ARG, "patch_evidence: a dense RBF head has no patches to split its mean over");
+  if (H.base_type != 0) return ctx_fail(ctx, DCGP_ERR_ARG, "patch_evidence: the head's base kernel must be RBF");
+  if (N == 0) return DCGP_OK;
+  if (!X || !out_c) return ctx_fail(ctx, DCGP_ERR_ARG, "patch_evidence: NULL pointer");
+  int rows = 0;
+  StreamGuard guard(ctx);
+  DCGP_TRY(forward_all(model, X, N, S, z_per_layer_host, seed, 0, false, false, &rows));
+  DCGP_TRY(forward_done(model, nullptr));   // this call synchronises the stream before it returns
+  // the head's input: the last hidden layer's sample, or the S copies of X (row n shows image n % N) -- what head_forward swept
+  const double* F = nl > 1 ? model->outs[nl - 2].sample : X;
+  const int n_mod = nl > 1 ? rows : N;
+  // beta = inv(L)^T alpha from the chain's own factors: L^-T q_mu when whitened (alpha is q_mu), Kuu^-1 q_mu otherwise
+  DCGP_TRY(patch_map(ctx, F, rows, n_mod, H.v, H.Z, H.ZS, H.M, H.variance, H.ls, H.w, nullptr, H.g.LinvT, H.g.alpha, H.g.Rp, H.R, out_c,
+                     "m" + std::to_string(model->id) + "_"));
+  if (out_fmean)
+    HIP_TRY(ctx, hipMemcpyAsync(out_fmean, model->outs[nl - 1].mean, (size_t)rows * H.R * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return read_info(model, info_host);
+}
+
 }  // extern "C"
 
 namespace {

@@ -598,6 +598,34 @@ class DGP_Base:
         _, Fmeans, Fvars = self.propagate(X, S=S, zs=zs, seed=seed)
         return Fmeans[-1], Fvars[-1]
 
+    def predict_patch_contributions(self, X, S, zs=None, seed=0):
+        """(C [S, N, P, R], Fmean [S, N, R]): the head's posterior mean of ``predict_f(X, S, zs, seed)`` split over the P patches of
+        the head's input, C[s, n, p, r] = (w_p / P) sum_m k(z_m, h_sn[p]) beta[m, r] with C.sum(2) == Fmean -- per class, where in
+        the image the evidence comes from (``layers[-1].kern.view.as_maps(C)`` makes images of it).  One device call
+        (dcgp_model_patch_evidence): same samples as ``propagate`` for the same (S, zs, seed), any likelihood.  Rank-local."""
+        head = self.layers[-1]
+        if not hasattr(head.kern, "patch_mean"):
+            raise TypeError("predict_patch_contributions needs a patch head (ConvKernel / AdditivePatchKernel); a dense head has no patches")
+        bk = head.kern.base_kernel
+        if not hasattr(bk, "lengthscales") or getattr(bk, "ARD", False):
+            raise NotImplementedError("predict_patch_contributions needs a scalar-lengthscale RBF base kernel")
+        S = int(S)
+        if S < 1:
+            raise ValueError("S must be >= 1")
+        N, P, R = np.shape(X)[0], head.kern.patch_count, head.num_outputs
+        if N == 0:
+            return np.zeros((S, 0, P, R)), np.zeros((S, 0, R))
+        X = np.ascontiguousarray(np.reshape(X, (N, -1)), np.float64)
+        self._build()
+        ctx, L = self._ctx, dev.lib()
+        dX = ctx.to_device(X)
+        arr, keep = self._z_table(zs, N, S)
+        c, fm = ctx.empty((S, N, P, R)), ctx.empty((S, N, R))
+        info = C.c_int(0)
+        rc = L.dcgp_model_patch_evidence(self._model, dX.ptr, N, S, arr, int(seed), c.ptr, fm.ptr, C.byref(info))
+        ctx._check(rc, info)
+        return c.numpy(), fm.numpy()
+
     def predict_all_layers(self, X, S, zs=None, seed=0):
         """(Fs, Fmeans, Fvars) of every layer (doubly_stochastic_dgp DGP_Base.predict_all_layers): what ``propagate`` returns."""
         return self.propagate(X, S=S, zs=zs, seed=seed)

@@ -161,6 +161,31 @@ class AdditivePatchKernel:
                                                  self.base_kernel.variance, self.base_kernel.lengthscales, dw.ptr, out.ptr))
         return out.numpy()
 
+    def patch_mean(self, ML_Z, ND_X, beta):
+        """[N, P, R] per-patch shares of ``Kzx(Z, X).T @ beta``: out[n, p, r] = (w_p / P) sum_m k(z_m, x_n[p]) beta[m, r], so that
+        ``out.sum(1) == Kzx(Z, X).T @ beta`` -- per output, where in the image the evidence comes from (``view.as_maps`` makes images
+        of it).  One launch (dcgp_convkernel_patch_mean), K_uf is never stored.  Scalar-lengthscale RBF base kernel only."""
+        bk = self.base_kernel
+        if not isinstance(bk, RBF) or bk.ARD:
+            raise NotImplementedError("patch_mean needs a scalar-lengthscale RBF base kernel")
+        Z = np.ascontiguousarray(ML_Z, np.float64)
+        beta = np.ascontiguousarray(beta, np.float64)
+        if Z.ndim != 2 or Z.shape[1] != self.patch_length:
+            raise ValueError("Z must be M x %d, got %s" % (self.patch_length, Z.shape))
+        if beta.ndim != 2 or beta.shape[0] != Z.shape[0] or beta.shape[1] < 1:
+            raise ValueError("beta must be M x R with M = %d and R >= 1, got %s" % (Z.shape[0], beta.shape))
+        X = self._reshape_X(ND_X)
+        N, H, W, Cc, f, s = self._geom(X)
+        M, R = beta.shape
+        if N == 0:
+            return np.zeros((0, self.patch_count, R))
+        ctx = dev.get_context()
+        dX, dZ, dw, db = ctx.to_device(X), ctx.to_device(Z), ctx.to_device(self.patch_weights), ctx.to_device(beta)
+        out = ctx.empty((N, self.patch_count, R))
+        ctx._check(dev.lib().dcgp_convkernel_patch_mean(ctx.handle, dX.ptr, N, H, W, Cc, f, s, dZ.ptr, M, bk.variance, bk.lengthscales,
+                                                        dw.ptr, db.ptr, R, out.ptr))
+        return out.numpy()
+
     def Kdiag(self, ND_X):
         ctx = dev.get_context()
         N = np.shape(ND_X)[0]

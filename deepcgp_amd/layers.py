@@ -376,6 +376,28 @@ class SVGP_Layer(Layer):
         ctx._check(rc, info)
         return mean.numpy(), var.numpy()
 
+    def patch_contributions(self, X):
+        """[N, P, R]: the posterior mean of ``conditional_ND(X)`` split over the P patches of each image (the mean function of a
+        head is Zero, so ``patch_contributions(X).sum(1) == conditional_ND(X)[0]``).  beta = L^-T q_mu (white) or Kuu^-1 q_mu from
+        the operator entry points, then ``kern.patch_mean``.  Patch heads only."""
+        if not hasattr(self.kern, "patch_mean"):
+            raise TypeError("patch_contributions needs a patch kernel (ConvKernel / AdditivePatchKernel); a dense head has no patches")
+        M, R = self.num_inducing, self.num_outputs
+        X = np.ascontiguousarray(X, np.float64)
+        if X.shape[0] == 0:
+            return np.zeros((0, self.kern.patch_count, R))
+        ctx = dev.get_context()
+        Lm = _potrf(_Kuu(self.feature, self.kern, jitter=JITTER))
+        dL, dLinv = ctx.to_device(Lm), ctx.empty((M, M))
+        ctx._check(dev.lib().dcgp_trtri_lower(ctx.handle, dL.ptr, M, dLinv.ptr))
+        da = ctx.to_device(self.q_mu)
+        if not self.white:
+            dq, da = da, ctx.empty((M, R))
+            ctx.gemm(dLinv, (M, 1, 0), dq, (R, 1, 0), da, R, M * R, M, R, M)        # inv(L) q_mu
+        dbeta = ctx.empty((M, R))
+        ctx.gemm(dLinv, (1, M, 0), da, (R, 1, 0), dbeta, R, M * R, M, R, M)         # inv(L)^T ...
+        return self.kern.patch_mean(self.feature.Z, X, dbeta.numpy())
+
     def _conditional_full_cov(self, X):
         """conditional_ND(full_cov=True) of B input sets at once: X [B, N, D] -> mean [B, N, R], var [B, N, N, R] (DS-DGP's
         [N, N, R] layout per set).  Patch heads: Kff by the image-pair kernel, one launch for all B; the dense RBF-ARD head: RBF.K.

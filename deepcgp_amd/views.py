@@ -59,6 +59,14 @@ class FullView(View):
                                                   out.ptr, int(pnl)))
         return out.numpy()
 
+    def as_maps(self, a):
+        """[..., patch_count, R] -> [..., out_image_height, out_image_width, R]: per-patch values (``patch_mean``,
+        ``predict_patch_contributions``) as images, patch p = (row p // width, column p % width).  Host only."""
+        a = np.asarray(a)
+        if a.ndim < 2 or a.shape[-2] != self.patch_count:
+            raise ValueError("expected [..., %d, R], got %s" % (self.patch_count, a.shape))
+        return a.reshape(a.shape[:-2] + (self.out_image_height, self.out_image_width, a.shape[-1]))
+
     def extract_patches(self, NHWC_X):
         """N x patch_count x patch_length (conv_gp/views.py:46-54)."""
         return self._extract(NHWC_X, False)

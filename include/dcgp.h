@@ -132,6 +132,14 @@ int dcgp_convkernel_kzx(dcgp_ctx* ctx, const double* X, int N, int H, int W, int
 /* ConvKernel.Kdiag (conv_gp/kernels.py:106-115): out[n] = (1/P^2) sum_{p,p'} w[p] w[p'] k(x[n,p], x[n,p']). */
 int dcgp_convkernel_kdiag(dcgp_ctx* ctx, const double* X, int N, int H, int W, int C, int f, int stride,
                           double variance, double lengthscale, const double* w, double* out_N);
+/* The head's mean split over the patches, out[n,p,r] = (w[p]/P) sum_m k(Z[m], x[n,p]) beta[m,r], so that sum_p out[n,p,:] =
+ * (Kzx^T beta)[n,:]: one launch that never stores K_uf.  Replaces dcgp_kuf_patches_rbf into a [P,M,N] buffer followed by
+ * dcgp_gemm_strided -- the per-patch maps the reference reads off its patch-weight and inducing-patch plots
+ * (conv_gp/utils/tensorboard.py:164-195, Inspect.ipynb).  X [N,H,W,C], Z [M,L], w [P], beta [M,R] -> out [N,P,R] (device).
+ * N == 0: DCGP_OK, nothing written. */
+int dcgp_convkernel_patch_mean(dcgp_ctx* ctx, const double* X, int N, int H, int W, int C, int f, int stride,
+                               const double* Z, int M, double variance, double lengthscale, const double* w,
+                               const double* beta, int R, double* out_NPR);
 /* AdditivePatchKernel.Kdiag (conv_gp/kernels.py:53-61): out[n] = variance * mean_p w[p].        */
 int dcgp_additive_kdiag(dcgp_ctx* ctx, int N, int P, double variance, const double* w, double* out_N);
 
@@ -368,6 +376,14 @@ int dcgp_model_train_step_adam_f64y(dcgp_model* model, const double* X, const do
 int dcgp_model_predict_mean_var(dcgp_model* model, const double* X, int N, int S,
                                 const double* const* z_per_layer_host, uint64_t seed,
                                 double* out_mean, double* out_var, int* info_host);
+/* Per-patch evidence maps of the model's patch head: X goes through the hidden layers exactly as in dcgp_model_propagate for the
+ * same (S, z, seed); out_c [S*N][P][R] (device) = (w_p/P) sum_m k(z_m, h[p]) beta[m,r] on the head's input h, beta = L^-T q_mu
+ * (whitened) or Kuu^-1 q_mu from the chain's own factors; out_fmean [S*N][R] (device, may be NULL) the head's mean, = sum_p out_c.
+ * Any likelihood.  Replaces dcgp_model_propagate + dcgp_model_layer_output + dcgp_kuf_patches_rbf + dcgp_gemm_strided and host
+ * arithmetic for beta (conv_gp/utils/tensorboard.py:164-195).  A dense RBF head has no patches: DCGP_ERR_ARG.  Rank-local.
+ * N == 0: DCGP_OK, nothing written. */
+int dcgp_model_patch_evidence(dcgp_model* model, const double* X, int N, int S, const double* const* z_per_layer, uint64_t seed,
+                              double* out_c, double* out_fmean, int* info_host);
 /* DS-DGP DGP_Base.predict_density with Gaussian.predict_density: out_logdens [N, K] (device) =
  * logsumexp_s log N(y; mu_s, var_s + s2) - log S per image and output. */
 int dcgp_model_predict_density_f64y(dcgp_model* model, const double* X, const double* y, int N, int S,
