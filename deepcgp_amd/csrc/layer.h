@@ -222,6 +222,29 @@ int bern_predict(dcgp_ctx* ctx, const double* mu, const double* var, long n, dou
 int bern_eval_tail(dcgp_ctx* ctx, const double* mu, const double* var, const double* y, int n, int S, int K, long lo, double* logdens,
                    double* ld_nd, double* p_mean, double* correct);
 
+// uncertainty.hip: the uncertainty tails (dcgp_model_evaluate_uncertainty).  unc_tail / bern_unc_tail: eval_tail / bern_eval_tail with the same
+// bits for logdens, p_mean and the correct count, plus per entry (image; Bernoulli: (image, output)) at its index in the whole set the
+// predictive entropy, the expected entropy (may be nullptr), their difference, the confidence and the prediction.  y may be nullptr:
+// then logdens, ok and brier are not touched.  unc_tail keeps kUncExtraSlots wave partials beside eval_tail's LDS: S * K + K + 48 <= kEvalMaxSlots.
+// unc_sum: one launch behind the last batch, res[9] = {correct, sum of the log densities, first non-positive pivot, labels outside
+// [0, K), ECE, MCE, Brier score, mean predictive entropy, mean mutual information} and the reliability table [bins][3] = {count, sum of
+// confidences, correct count}; ok == nullptr (no labels): words 0, 1, 4, 5, 6 are NaN and the table's third column is 0.
+constexpr int kUncExtraSlots = 48;   // three sums x 16 waves
+struct UncOut {
+  double* logdens = nullptr; double* p_mean = nullptr;   // [N_total], [N_total][K] (p_mean may be nullptr)
+  int* ok = nullptr; double* brier = nullptr;            // per entry: 1 / 0 / -1 (label outside [0, K)); the entry's Brier term
+  double* pred_ent = nullptr; double* exp_ent = nullptr; double* mi = nullptr; double* conf = nullptr; int* pred = nullptr;
+};
+struct UncSumArgs {
+  const double* logdens = nullptr; long n_img = 0;
+  const int* ok = nullptr; const double* brier = nullptr; const double* pred_ent = nullptr; const double* mi = nullptr;
+  const double* conf = nullptr; long n_ent = 0;
+  int bins = 0; double* table = nullptr;
+};
+int unc_tail(dcgp_ctx* ctx, const double* mu, const double* var, const int32_t* y, int n, int S, int K, double eps, long lo, const UncOut& o);
+int bern_unc_tail(dcgp_ctx* ctx, const double* mu, const double* var, const double* y, int n, int S, int K, long lo, const UncOut& o);
+int unc_sum(dcgp_ctx* ctx, const UncSumArgs& a, const EvalStatus& st, double* res);
+
 // patch_map.hip: per-patch evidence maps of a patch head with an RBF base kernel, out [rows][P][R] = (w_p / P) sum_m k(z_m, x_n[p]) beta[m][r]
 // (row n shows X[n % n_mod]); asynchronous on ctx->stream.  ZS: the sweeps' operand of Z (sweep_dev.h) or nullptr (built from Z).  beta [M][R],
 // or nullptr: beta = LinvT alpha from a layer's own factors (alpha [Mp][Rpa] = inv(L) q_mu, q_mu itself when whitened).

@@ -1041,6 +1041,92 @@ int evaluate_impl(dcgp_model* model, const double* X, const int32_t* y, int N_to
   out_host[1] = h[1];
   return DCGP_OK;
 }
+
+// evaluate_impl's batches -- the same seeds, noise layout, factor reuse, buffer reuse and single synchronisation -- with the uncertainty
+// tails (uncertainty.hip) in place of eval_tail / bern_eval_tail and unc_sum in place of the sum kernel.  f64y: the Bernoulli entry (targets
+// yf [N_total][K], entries = (image, output) pairs); otherwise RobustMax (labels y [N_total], entries = images).  Labels may be nullptr.
+// u holds the caller's outputs (any may be nullptr: the per-entry values the dataset kernel reads then live in workspaces).
+int uncertainty_impl(dcgp_model* model, const double* X, const int32_t* y, const double* yf, bool f64y, int N_total, int batch, int S,
+                     const double* const* zs, uint64_t seed, int bins, UncOut u, double* out_table, double* out_host, int* info_host,
+                     const char* who) {
+  if (!model) return DCGP_ERR_ARG;
+  dcgp_ctx* ctx = model->ctx;
+  if (info_host) *info_host = 0;
+  if (!X || N_total <= 0 || batch <= 0 || S <= 0 || bins < 1 || !out_host)
+    return ctx_fail(ctx, DCGP_ERR_ARG, "%s: bad args (N %d, batch %d, S %d, bins %d)", who, N_total, batch, S, bins);
+  if (model->lik_kind == 1) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: class probabilities need a classification likelihood, this model is Gaussian", who);
+  if (model->float_targets() != f64y)
+    return ctx_fail(ctx, DCGP_ERR_ARG, f64y ? "%s: a RobustMax model takes int32 labels, not float64 targets"
+                                            : "%s: a Bernoulli-likelihood model takes float64 targets (the _f64y entry point)", who);
+  if (!model->has_head) return ctx_fail(ctx, DCGP_ERR_ARG, "model has no head layer");
+  const int nl = (int)model->layers.size();
+  const int K = model->layers[nl - 1]->R;
+  if (!f64y && K < 2) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: the last layer has %d outputs, RobustMax needs >= 2", who, K);
+  if (!f64y && (long)S * K + K + kUncExtraSlots > kEvalMaxSlots)
+    return ctx_fail(ctx, DCGP_ERR_ARG, "%s: S = %d samples of %d classes exceed the tail's LDS (S * K + K + %d <= %d)", who, S, K, kUncExtraSlots, kEvalMaxSlots);
+  const bool labels = f64y ? yf != nullptr : y != nullptr;
+  const LayerState& L0 = *model->layers[0];
+  const long in_len = (long)L0.v.H * L0.v.W * L0.v.C;   // one image of X
+  const long n_ent = f64y ? (long)N_total * K : N_total;
+  const std::string mp = "m" + std::to_string(model->id) + "_";
+  auto dbl = [&](double* given, const char* name, long n) { return given ? given : (double*)ws_get(ctx, mp + name, (size_t)n * sizeof(double)); };
+  if (labels) {
+    u.logdens = dbl(u.logdens, "unc_logdens", N_total);
+    u.ok = (int*)ws_get(ctx, mp + "unc_ok", (size_t)n_ent * sizeof(int));
+    u.brier = dbl(nullptr, "unc_brier", n_ent);
+    if (!u.logdens || !u.ok || !u.brier) return DCGP_ERR_ALLOC;
+  } else {
+    u.logdens = nullptr;
+  }
+  u.pred_ent = dbl(u.pred_ent, "unc_pred_ent", n_ent);
+  u.mi = dbl(u.mi, "unc_mi", n_ent);
+  u.conf = dbl(u.conf, "unc_conf", n_ent);
+  if (!u.pred) u.pred = (int*)ws_get(ctx, mp + "unc_pred", (size_t)n_ent * sizeof(int));
+  double* table = dbl(out_table, "unc_table", 3L * bins);
+  double* res = (double*)ws_get(ctx, mp + "unc_res", 9 * sizeof(double));
+  if (!u.pred_ent || !u.mi || !u.conf || !u.pred || !table || !res) return DCGP_ERR_ALLOC;
+  DCGP_TRY(ensure_events(model));
+  StreamGuard guard(ctx);
+  std::vector<const double*> zb(nl, nullptr);
+  const int nb = (N_total + batch - 1) / batch;
+  for (int b = 0; b < nb; ++b) {
+    const long lo = (long)b * batch;
+    const int n = (int)(N_total - lo < batch ? N_total - lo : batch);
+    for (int l = 0; l < nl && zs; ++l) {   // noise: evaluate_impl's layout
+      const LayerState& L = *model->layers[l];
+      const long D = L.is_head ? L.R : (long)L.v.P * L.R;
+      zb[l] = zs[l] ? zs[l] + (long)S * lo * D : nullptr;
+    }
+    int rows = 0;
+    DCGP_TRY(forward_all(model, X + lo * in_len, n, S, zs ? zb.data() : nullptr, seed + (uint64_t)b, 0, false, false, &rows));
+    const auto& o = model->outs[nl - 1];
+    if (rows != S * n || o.width != K) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: head rows %d x %d, expected %d x %d", who, rows, o.width, S * n, K);
+    if (f64y) DCGP_TRY(bern_unc_tail(ctx, o.mean, o.var, yf ? yf + lo * K : nullptr, n, S, K, lo, u));
+    else DCGP_TRY(unc_tail(ctx, o.mean, o.var, y ? y + lo : nullptr, n, S, K, model->eps, lo, u));
+    HIP_TRY(ctx, hipEventRecord(model->ev_eval[model->bank], ctx->stream));
+    DCGP_TRY(forward_done(model, model->ev_eval[model->bank]));
+  }
+  EvalStatus st;
+  auto& groups = model->groups[model->bank];
+  if (groups.size() > 16) return ctx_fail(ctx, DCGP_ERR_ARG, "model: too many factor groups");
+  st.ngroups = (int)groups.size();
+  for (int q = 0; q < st.ngroups; ++q) { st.info[q] = groups[q].d_info; st.ninfo[q] = (int)groups[q].K.size(); }
+  UncSumArgs sa;
+  sa.logdens = u.logdens; sa.n_img = N_total; sa.ok = labels ? u.ok : nullptr; sa.brier = u.brier; sa.pred_ent = u.pred_ent; sa.mi = u.mi;
+  sa.conf = u.conf; sa.n_ent = n_ent; sa.bins = bins; sa.table = table;
+  DCGP_TRY(unc_sum(ctx, sa, st, res));
+  double h[9];
+  HIP_TRY(ctx, hipMemcpyAsync(h, res, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  if (h[3] > 0) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: %d labels outside [0, %d)", who, (int)h[3], K);
+  const int bad = (int)h[2];
+  if (info_host) *info_host = bad;
+  if (bad) return ctx_fail(ctx, DCGP_ERR_NOT_PD, "Cholesky: matrix not positive definite at column %d", bad);
+  out_host[0] = h[0];
+  out_host[1] = h[1];
+  for (int q = 2; q < 7; ++q) out_host[q] = h[q + 2];
+  return DCGP_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -1070,6 +1156,29 @@ int dcgp_model_evaluate(dcgp_model* model, const double* X, const int32_t* y, in
                         const double* const* z_per_layer, uint64_t seed, double* out_logdens, double* out_p_mean,
                         double* out_host, int* info_host) {
   return evaluate_impl(model, X, y, N_total, batch, S, z_per_layer, seed, out_logdens, out_p_mean, out_host, info_host, "evaluate");
+}
+
+int dcgp_model_evaluate_uncertainty(dcgp_model* model, const double* X, const int32_t* y, int N_total, int batch, int S,
+                                    const double* const* z_per_layer, uint64_t seed, int bins, double* out_logdens, double* out_p_mean,
+                                    double* out_pred_entropy, double* out_exp_entropy, double* out_mutual_info, double* out_confidence,
+                                    int32_t* out_prediction, double* out_table, double* out_host, int* info_host) {
+  UncOut u;
+  u.logdens = out_logdens; u.p_mean = out_p_mean; u.pred_ent = out_pred_entropy; u.exp_ent = out_exp_entropy; u.mi = out_mutual_info;
+  u.conf = out_confidence; u.pred = out_prediction;
+  return uncertainty_impl(model, X, y, nullptr, false, N_total, batch, S, z_per_layer, seed, bins, u, out_table, out_host, info_host,
+                          "evaluate_uncertainty");
+}
+
+int dcgp_model_evaluate_uncertainty_f64y(dcgp_model* model, const double* X, const double* y, int N_total, int batch, int S,
+                                         const double* const* z_per_layer, uint64_t seed, int bins, double* out_logdens, double* out_p_mean,
+                                         double* out_pred_entropy, double* out_exp_entropy, double* out_mutual_info,
+                                         double* out_confidence, int32_t* out_prediction, double* out_table, double* out_host,
+                                         int* info_host) {
+  UncOut u;
+  u.logdens = out_logdens; u.p_mean = out_p_mean; u.pred_ent = out_pred_entropy; u.exp_ent = out_exp_entropy; u.mi = out_mutual_info;
+  u.conf = out_confidence; u.pred = out_prediction;
+  return uncertainty_impl(model, X, nullptr, y, true, N_total, batch, S, z_per_layer, seed, bins, u, out_table, out_host, info_host,
+                          "evaluate_uncertainty");
 }
 
 int dcgp_model_layer_output(dcgp_model* model, int layer, double* out_sample, double* out_mean, double* out_var,

@@ -118,6 +118,9 @@ _SIGS = {
     "dcgp_model_predict_mean_var": [_vp, _vp, _i, _i, C.POINTER(_vp), _u64, _vp, _vp, _ip],
     "dcgp_model_predict_density_f64y": [_vp, _vp, _vp, _i, _i, C.POINTER(_vp), _u64, _vp, _ip],
     "dcgp_model_evaluate_f64y": [_vp, _vp, _vp, _i, _i, _i, C.POINTER(_vp), _u64, _vp, _vp, _dp, _ip],
+    "dcgp_model_evaluate_uncertainty": [_vp, _vp, _vp, _i, _i, _i, C.POINTER(_vp), _u64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _dp, _ip],
+    "dcgp_model_evaluate_uncertainty_f64y": [_vp, _vp, _vp, _i, _i, _i, C.POINTER(_vp), _u64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _dp,
+                                             _ip],
     "dcgp_convkernel_patch_mean": [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _d, _d, _vp, _vp, _i, _vp],
     "dcgp_model_patch_evidence": [_vp, _vp, _i, _i, C.POINTER(_vp), _u64, _vp, _vp, _ip],
     "dcgp_gemm_strided": [_vp, _vp, C.c_long, C.c_long, C.c_long, _vp, C.c_long, C.c_long, C.c_long, _vp, C.c_long, C.c_long,

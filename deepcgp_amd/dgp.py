@@ -738,6 +738,109 @@ class DGP_Base:
             out["log_density"], out["p_mean"] = ld, pm
         return out
 
+    def _uncertainty_call(self, X, Y, S, batch_size, seed, flat_zs, bins, want_p_mean):
+        """One dcgp_model_evaluate_uncertainty(_f64y) call; Y may be None.  Returns (host arrays by name, the [bins, 3] table, the
+        seven dataset scalars)."""
+        self._build()
+        ctx, L = self._ctx, dev.lib()
+        X = np.ascontiguousarray(np.reshape(X, (np.shape(X)[0], -1)), np.float64)
+        N, K = X.shape[0], self.layers[-1].num_outputs
+        if X.shape[1] != self.X.shape[1]:
+            raise ValueError("images of %d values, the model takes %d" % (X.shape[1], self.X.shape[1]))
+        dY = None
+        if Y is not None and self.bernoulli:
+            dY = ctx.to_device(self._targets_host(Y, N))
+        elif Y is not None:
+            Y = np.ascontiguousarray(np.reshape(Y, (-1,)), np.int32)
+            if Y.size != N:
+                raise ValueError("%d labels for %d images" % (Y.size, N))
+            dY = ctx.to_device(Y, np.int32)
+        dX = ctx.to_device(X)                                       # the whole set crosses the bus once
+        arr, keep = None, []
+        if flat_zs is not None:
+            arr = (C.c_void_p * len(self.layers))()
+            for i, z in enumerate(flat_zs):
+                if z is not None:
+                    keep.append(ctx.to_device(z))
+                    arr[i] = keep[-1].ptr
+        per = (N, K) if self.bernoulli else (N,)
+        bufs = {"log_density": ctx.empty((N,)) if dY is not None else None, "p_mean": ctx.empty((N, K)) if want_p_mean else None}
+        for name in ("predictive_entropy", "expected_entropy", "mutual_information", "confidence"):
+            bufs[name] = ctx.empty(per)
+        bufs["prediction"] = ctx.empty(per, np.int32)
+        table = ctx.empty((int(bins), 3))
+        out, info = (C.c_double * 7)(), C.c_int(0)
+        fn = L.dcgp_model_evaluate_uncertainty_f64y if self.bernoulli else L.dcgp_model_evaluate_uncertainty
+        ptr = lambda a: a.ptr if a is not None else None            # noqa: E731
+        rc = fn(self._model, dX.ptr, ptr(dY), N, int(batch_size), int(S), arr, int(seed), int(bins), ptr(bufs["log_density"]),
+                ptr(bufs["p_mean"]), bufs["predictive_entropy"].ptr, bufs["expected_entropy"].ptr, bufs["mutual_information"].ptr,
+                bufs["confidence"].ptr, bufs["prediction"].ptr, table.ptr, out, C.byref(info))
+        ctx._check(rc, info)
+        return {k: v.numpy() for k, v in bufs.items() if v is not None}, table.numpy(), list(out)
+
+    _UNCERTAINTY_KEYS = ("predictive_entropy", "expected_entropy", "mutual_information", "confidence", "prediction")
+
+    def _uncertainty_empty(self):
+        per = (0, self.layers[-1].num_outputs) if self.bernoulli else (0,)
+        out = {k: np.zeros(per) for k in self._UNCERTAINTY_KEYS[:4]}
+        out["prediction"] = np.zeros(per, np.int32)
+        return out
+
+    def evaluate_uncertainty(self, X, Y, S=5, batch_size=32, seed=0, zs=None, bins=15, per_image=False):
+        """``evaluate`` with the uncertainty of the predictions kept, still one device call (dcgp_model_evaluate_uncertainty): everything
+        ``evaluate`` returns for the same arguments, bit for bit, plus -- in nats, from the S per-sample probabilities p_s and their mean
+        pbar -- "mean_predictive_entropy" (the mean of H(pbar)), "mean_mutual_information" (BALD: H(pbar) - 1/S sum_s H(p_s), the part
+        of the uncertainty that comes from the model), the calibration of the confidence max_k pbar[k] over ``bins`` equal-width bins
+        ("ece", "mce", and "reliability": {"count", "confidence", "accuracy"} per bin, NaN where a bin is empty) and the "brier" score.
+        With ``per_image`` also "predictive_entropy", "expected_entropy", "mutual_information", "confidence" and "prediction" per image.
+        Bernoulli likelihood: every (image, output) entry counts, with the binary entropy, confidence max(pbar, 1 - pbar) and prediction
+        pbar > 0.5; the per-image arrays are N x D.  A Gaussian model has no class probabilities: ValueError.  Rank-local."""
+        if self.gaussian:
+            raise ValueError("evaluate_uncertainty: class probabilities need a classification likelihood, this model is Gaussian")
+        N = np.shape(X)[0]
+        if int(batch_size) <= 0:
+            raise ValueError("batch_size must be positive, got %r" % (batch_size,))
+        bins = int(bins)
+        nan = float("nan")
+        if N == 0:
+            out = self.evaluate(X, Y, S=S, batch_size=batch_size, seed=seed, zs=zs, per_image=per_image)
+            out.update(ece=nan, mce=nan, brier=nan, mean_predictive_entropy=nan, mean_mutual_information=nan,
+                       reliability={"count": np.zeros(max(bins, 0), np.int64), "confidence": np.full(max(bins, 0), nan),
+                                    "accuracy": np.full(max(bins, 0), nan)})
+            if per_image:
+                out.update(self._uncertainty_empty())
+            return out
+        arrs, table, h = self._uncertainty_call(X, Y, S, batch_size, seed, batched_noise(zs, N, S, int(batch_size), self._out_dims()), bins,
+                                                per_image)
+        entries = N * self.layers[-1].num_outputs if self.bernoulli else N
+        out = {"accuracy": h[0] / entries, "mean_log_density": h[1] / N, "n": N, "ece": h[2], "mce": h[3], "brier": h[4],
+               "mean_predictive_entropy": h[5], "mean_mutual_information": h[6]}
+        count = table[:, 0]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            out["reliability"] = {"count": count.astype(np.int64), "confidence": np.where(count > 0, table[:, 1] / count, nan),
+                                  "accuracy": np.where(count > 0, table[:, 2] / count, nan)}
+        if per_image:
+            out.update(arrs)
+        return out
+
+    def predict_uncertainty(self, X, S, zs=None, seed=0, batch_size=None):
+        """The per-image uncertainty of unlabelled images (acquisition functions, out-of-distribution scores), one device call:
+        {"p_mean", "predictive_entropy", "expected_entropy", "mutual_information", "confidence", "prediction"} as
+        ``evaluate_uncertainty(per_image=True)`` returns them.  ``batch_size`` None: one batch of all N images (``predict_proba``'s
+        samples for the same ``seed`` / ``zs``); otherwise batch i draws from ``seed + i``.  Rank-local."""
+        if self.gaussian:
+            raise ValueError("predict_uncertainty: class probabilities need a classification likelihood, this model is Gaussian")
+        N = np.shape(X)[0]
+        if N == 0:
+            out = self._uncertainty_empty()
+            out["p_mean"] = np.zeros((0, self.layers[-1].num_outputs))
+            return out
+        bs = N if batch_size is None else int(batch_size)
+        if bs <= 0:
+            raise ValueError("batch_size must be positive, got %r" % (batch_size,))
+        arrs, _, _ = self._uncertainty_call(X, None, S, bs, seed, batched_noise(zs, N, S, bs, self._out_dims()), 1, True)
+        return arrs
+
     def KL(self):
         return float(sum(l.KL() for l in self.layers))
 

@@ -38,6 +38,18 @@ class MultiClass:
         ps = out.numpy()
         return ps, ps - np.square(ps)
 
+    @staticmethod
+    def predictive_uncertainty(ps):
+        """The closed forms of ``DGP_Base.evaluate_uncertainty`` on host arrays: ``ps`` S x N x K class probabilities per sample
+        (``predict_y``'s mean).  Returns {"p_mean" N x K, "predictive_entropy", "expected_entropy", "mutual_information", "confidence",
+        "prediction"}, each N, in nats: H(pbar), 1/S sum_s H(p_s), their raw difference, max_k pbar and its first index."""
+        ps = np.asarray(ps, np.float64)
+        pbar = ps.sum(0) / ps.shape[0]
+        h = -(pbar * np.log(pbar)).sum(-1)
+        e = -(ps * np.log(ps)).sum(-1).sum(0) / ps.shape[0]
+        return {"p_mean": pbar, "predictive_entropy": h, "expected_entropy": e, "mutual_information": h - e,
+                "confidence": pbar.max(-1), "prediction": pbar.argmax(-1).astype(np.int32)}
+
 
 class Gaussian:
     """gpflow 1.x likelihoods.Gaussian(variance) as DS-DGP's BroadcastingLikelihood applies it: one variance shared by every output,
@@ -114,3 +126,16 @@ class Bernoulli:
         p = self.predict_mean_and_var(Fmu, Fvar)[0]
         Y = np.asarray(Y, np.float64)
         return np.where(Y == 1, np.log(p), np.log(1 - p))
+
+    @staticmethod
+    def predictive_uncertainty(ps):
+        """The closed forms of ``DGP_Base.evaluate_uncertainty`` on host arrays: ``ps`` S x N x D per-sample p(y = 1) (``predict_y``'s
+        mean).  Returns {"p_mean", "predictive_entropy", "expected_entropy", "mutual_information", "confidence", "prediction"}, each
+        N x D, in nats, with the binary entropy h(q) = -q log q - (1 - q) log(1 - q): h(pbar), 1/S sum_s h(p_s), their raw difference,
+        max(pbar, 1 - pbar) and pbar > 0.5."""
+        ps = np.asarray(ps, np.float64)
+        h2 = lambda q: -q * np.log(q) - (1 - q) * np.log(1 - q)      # noqa: E731
+        pbar = ps.sum(0) / ps.shape[0]
+        h, e = h2(pbar), h2(ps).sum(0) / ps.shape[0]
+        return {"p_mean": pbar, "predictive_entropy": h, "expected_entropy": e, "mutual_information": h - e,
+                "confidence": np.maximum(pbar, 1 - pbar), "prediction": (pbar > 0.5).astype(np.int32)}

@@ -170,6 +170,21 @@ class AccuracyLogger(object):
         return correct / max(Y.size, 1)
 
 
+class UncertaintyLogger(object):
+    """Calibration and uncertainty of the test predictions with AccuracyLogger's batching (32 images, five samples, batch i drawing
+    from seed + i): the dataset dict of ``DGP_Base.evaluate_uncertainty`` -- accuracy, mean log density, ECE, MCE, Brier score, mean
+    predictive entropy, mean mutual information and the reliability table -- the whole set in one device call."""
+    title = 'test_uncertainty'
+
+    def __init__(self, X_test, Y_test, S=5, bins=15, batch_size=32):
+        self.X_test = X_test
+        self.Y_test = Y_test if np.ndim(Y_test) == 2 and np.asarray(Y_test).dtype.kind == "f" else np.reshape(Y_test, (-1,))
+        self.num_samples, self.bins, self.batch_size = int(S), int(bins), int(batch_size)
+
+    def __call__(self, model, seed=0):
+        return model.evaluate_uncertainty(self.X_test, self.Y_test, S=self.num_samples, batch_size=self.batch_size, seed=seed, bins=self.bins)
+
+
 class TestLogDensityLogger(object):
     """Mean test log predictive density with AccuracyLogger's batching (32 images, five samples, batch i drawing from seed + i):
     ``DGP_Base.evaluate``, the whole set in one device call."""

@@ -394,6 +394,36 @@ int dcgp_model_predict_density_f64y(dcgp_model* model, const double* X, const do
 int dcgp_model_evaluate_f64y(dcgp_model* model, const double* X, const double* y, int N_total, int batch, int S,
                              const double* const* z_per_layer, uint64_t seed, double* out_logdens, double* out_y_mean,
                              double* out_host, int* info_host);
+/* dcgp_model_evaluate with the uncertainty of every prediction kept: DS-DGP DGP_Base.predict_y hands its caller the S samples of the class
+ * probabilities p[s][k] (the reference's AccuracyLogger, conv_gp/utils/log.py:62-67, averages them and keeps the arg-max); here the device
+ * reduces them per image, in nats, to
+ *   out_pred_entropy  H(pbar) = -sum_k pbar[k] log pbar[k],  pbar = the sample mean (out_p_mean, bit-identical to dcgp_model_evaluate's),
+ *   out_exp_entropy   1/S sum_s H(p[s]),
+ *   out_mutual_info   their difference (BALD; the raw difference, >= 0 up to rounding, not clipped),
+ *   out_confidence    max_k pbar[k],   out_prediction (int32) its first index,
+ * each [N_total], device, any may be NULL; out_logdens [N_total] and out_p_mean [N_total][K] as dcgp_model_evaluate's.  Behind the last batch
+ * one launch bins the confidences into `bins` equal-width bins, b = min(bins - 1, floor(confidence * bins)): out_table [bins][3] =
+ * {count, sum of confidences, number correct} (device, may be NULL), and out_host[7] = {correct count, sum of logdens, ECE = sum_b
+ * count_b / n |accuracy_b - mean confidence_b|, MCE = the largest of those gaps, Brier score 1/n sum_i sum_k (pbar[i][k] - [y_i = k])^2,
+ * mean predictive entropy, mean mutual information}.  Batches, seeds (seed + b), z_per_layer layout, factor reuse and the single stream
+ * synchronisation are dcgp_model_evaluate's; sums run in a fixed order without atomics, so two calls agree bit for bit.  Rank-local.
+ * y may be NULL (unlabelled images: acquisition scores, out-of-distribution checks): out_logdens is not written, the table's third column is
+ * 0 and words 0, 1, 2, 3, 4 of out_host are NaN.  DCGP_ERR_ARG: bins < 1, batch <= 0, K < 2, a label outside [0, K) (checked on the device,
+ * reported after the sync), S * K + K + 48 > 8192 (the tail's LDS), a Gaussian or Bernoulli model. */
+int dcgp_model_evaluate_uncertainty(dcgp_model* model, const double* X, const int32_t* y, int N_total, int batch, int S,
+                                    const double* const* z_per_layer, uint64_t seed, int bins, double* out_logdens, double* out_p_mean,
+                                    double* out_pred_entropy, double* out_exp_entropy, double* out_mutual_info, double* out_confidence,
+                                    int32_t* out_prediction, double* out_table, double* out_host, int* info_host);
+/* The same for a Bernoulli model (dcgp_model_evaluate_f64y; DS-DGP DGP_Base.predict_y with gpflow's Bernoulli.predict_mean_and_var):
+ * targets y [N_total][K] float64 (may be NULL), every (image, output) pair an entry with p = the jittered probit of mu / sqrt(1 + var) and the
+ * binary entropy h(q) = -q log q - (1 - q) log(1 - q) in place of H; confidence = max(pbar, 1 - pbar), prediction = pbar > 0.5, Brier term
+ * (pbar - y)^2.  The per-entry outputs are [N_total][K], n = N_total K entries; out_logdens [N_total] is summed over the K outputs.
+ * DCGP_ERR_ARG on a RobustMax or Gaussian model. */
+int dcgp_model_evaluate_uncertainty_f64y(dcgp_model* model, const double* X, const double* y, int N_total, int batch, int S,
+                                         const double* const* z_per_layer, uint64_t seed, int bins, double* out_logdens, double* out_p_mean,
+                                         double* out_pred_entropy, double* out_exp_entropy, double* out_mutual_info,
+                                         double* out_confidence, int32_t* out_prediction, double* out_table, double* out_host,
+                                         int* info_host);
 /* Parameter-only state across steps.  The reference's evaluation loops run hundreds of batches at ONE parameter state (AccuracyLogger /
  * LogLikelihoodLogger, conv_gp/utils/log.py:55-68; conv_gp/utils/tensorboard.py:22-42), and every session.run of them factors every Kuu again.
  * Here a step records the parameter version its chain (operand preparation, factorisations, inverses, G / alpha, KL pieces) ran at; every call that writes
