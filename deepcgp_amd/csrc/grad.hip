@@ -669,6 +669,9 @@ struct Bk {   // per-backward bookkeeping
   bool kl_early = false;       // the layer being processed had its kl_products beside the forward pass (grad_kl_early)
   bool side_pending = false;   // a layer left the end of its reverse pass on the side stream: model_backward joins once, at the end
   double klw = 1.0;   // weight of the (replicated) KL term on this rank: 1 / number of batch shards
+  // model_backward_data (the input gradient): only the data path runs -- the column-wise adjoint of each conditional, the patch kernel's adjoint with
+  // respect to the patches, dX.  Nothing is written outside the "g_" workspaces: no gradient block, no scalar slot, no chain, no KL, no dZ.
+  bool data_only = false;
   double* ws(const char* name, size_t n_doubles) { return (double*)ws_get(ctx, pfx + "g_" + name, (n_doubles ? n_doubles : 1) * sizeof(double)); }
 };
 
@@ -707,6 +710,7 @@ GenGemm mk(const double* A, long ars, long acs, const double* B, long brs, long 
 
 // scale * sum(part[0..n)) goes to the next slot of the layer: which = 0 variance, 1 lengthscale | acos weight variance, 2 acos bias variance
 int add_scalar(Bk& bk, LayerState& L, int which, const double* part, long n, double scale) {
+  if (bk.data_only) return DCGP_OK;
   int& s = which == 0 ? bk.slot_v : (which == 1 ? bk.slot_l : bk.slot_b);
   if (s >= 16) return ctx_fail(bk.ctx, DCGP_ERR_ARG, "grad: out of scalar slots");
   bk.pending.push_back({part, n, scale, L.gslots + (which == 0 ? VAR_SLOT : (which == 1 ? LS_SLOT : P2_SLOT)) + s});
@@ -804,7 +808,7 @@ int patch_backward(Bk& bk, LayerState& L, const double* E, long ld, long Kc, con
   const double inv_l2 = cz != 0.0 ? cz : 1.0 / (L.ls * L.ls);   // cz: the ArcCosine adjoint passes its weight variance (and its own row vector)
   double* rs = rs_in ? const_cast<double*>(rs_in) : bk.ws("pb_rs", M);
   NEED(rs);
-  if (!rs_in) {
+  if (!rs_in && !bk.data_only) {
     const int chunks = (int)std::min<long>(32, (Kc + 4095) / 4096);
     const long cpc = round_up_l((Kc + chunks - 1) / chunks, 256);
     double* rsp = bk.ws("pb_rsp", (size_t)chunks * M);
@@ -815,7 +819,7 @@ int patch_backward(Bk& bk, LayerState& L, const double* E, long ld, long Kc, con
     LAUNCH_CHECK(ctx);
   }
   const double* Zp = Zuse ? Zuse : L.Z;
-  {   // dZ += (E Xcol - rs o Z) / l^2: one product over the columns (split along k), the correction in its epilogue
+  if (!bk.data_only) {   // dZ += (E Xcol - rs o Z) / l^2: one product over the columns (split along k), the correction in its epilogue
     GenGemm e = mk(E, ld, 1, Xcol, Ld, 1, dz_out ? dz_out : L.gZ, Ld, M, Ld, (int)Kc);
     e.alpha = inv_l2; e.accumulate = 1; e.sub_v = rs; e.sub_x = Zp; e.sx_rs = Ld;
     if (dz_lanes && dz_lanes->forked && !dz_out && !ctx->opt.grad_dz_main) {
@@ -1054,6 +1058,7 @@ int cond_backward_main(Bk& bk, const Lanes& ln, LayerState& L, const double* A1,
       DCGP_TRY(gemm_gen(ctx, mk(g.Linv, 1, Mp, dA1, ld, 1, dKuf, ld, M, (int)Kc, M)));
     }
   }
+  if (bk.data_only) return DCGP_OK;   // dK_uf and gvs are all the data path reads
   // ... then d alpha = A1 gm and dq_mu = d alpha (whitened) or inv(L)^T d alpha.  (d alpha used to open the chain: beside the strip kernel
   // its 288 small workgroups took 108 us instead of 8, in front of W_r.)
   DCGP_TRY(gemm_gen(ctx, mk(A1, ld, 1, gm, R, 1, dalpha, Rp, M, R, (int)Kc)));
@@ -1181,6 +1186,7 @@ int layer_fills(Bk& bk, LayerState& L) {
 int begin_layer(Bk& bk, LayerState& L) {
   bk.slot_v = bk.slot_l = bk.slot_b = 0;
   bk.pending.clear();
+  if (bk.data_only) return DCGP_OK;  // no gradient block is written
   if (bk.prep & 1) return DCGP_OK;   // grad_kl_early ran the fills beside the forward pass
   return layer_fills(bk, L);
 }
@@ -1224,7 +1230,8 @@ int conv_backward(Bk& bk, LayerState& L, const double* Xin, int rows, int n_mod,
   dcgp_ctx* ctx = bk.ctx;
   const int M = L.M, Mp = L.Mp, P = L.v.P, Ld = L.v.L;
   const long Kc = (long)rows * P, ld = col_ld(Kc);
-  const Lanes ln = lanes_of(ctx);
+  Lanes ln = lanes_of(ctx);
+  if (bk.data_only) { ln.forked = false; ln.chain = ln.tail = ln.main; }
   DCGP_TRY(begin_layer(bk, L));
   // forward leftovers (conv_forward / cond_core workspaces)
   auto itB = ctx->ws.find(bk.pfx + "Kuf"), itA = ctx->ws.find(bk.pfx + "A1");
@@ -1242,9 +1249,11 @@ int conv_backward(Bk& bk, LayerState& L, const double* Xin, int rows, int n_mod,
   // main stream: the column-wise adjoint of the conditional, then the patch-kernel adjoint -> dX.  The M x M chain behind the conditional
   // runs beside them on the chain stream, what needs its result on the tail stream (Lanes).
   DCGP_TRY(cond_backward_main(bk, ln, L, A1, ld, Kc, gm, gv, dKuf, gvs, bk.last_layer && ln.forked));
-  DCGP_TRY(im2col(ctx, L, Xin, n_mod, Kc, Xcol));
+  // the input gradient's pass: dX in one launch from E and cs where the shape is covered (input_grad.hip) -- no Xcol, no dXcol, no col2im
+  const bool fuse_dx = bk.data_only && dXin && patch_adjoint_fused_ok(L, rows);
+  if (!fuse_dx) DCGP_TRY(im2col(ctx, L, Xin, n_mod, Kc, Xcol));
   double* dXcol = nullptr;
-  if (dXin) { dXcol = bk.ws("dXcol", (size_t)Kc * Ld); NEED(dXcol); }
+  if (dXin && !fuse_dx) { dXcol = bk.ws("dXcol", (size_t)Kc * Ld); NEED(dXcol); }
   if (L.base_type == 1) {   // ArcCosine(order 0): F1, F2 beside it, the RBF machinery on (F1, rowsum(F2) / Q, colsum(F2) / A, w)
     const unsigned nb = blocks_for(Kc);
     int chunks = (int)std::min<long>(16, std::max<long>(1, 2048 / nb));
@@ -1284,16 +1293,21 @@ int conv_backward(Bk& bk, LayerState& L, const double* Xin, int rows, int n_mod,
     DCGP_TRY(patch_backward(bk, L, E, ld, Kc, cs, Xcol, dXcol, 0));
   }
   if (dXin) {
-    const long n = (long)rows * L.v.H * L.v.W * L.v.C;
-    hipLaunchKernelGGL(col2im_kernel, dim3(blocks_for(n)), dim3(256), 0, ctx->stream, dXcol, rows, L.v.H, L.v.W, L.v.C, L.v.f, L.v.s, L.v.Ho,
-                       L.v.Wo, Ld, dXin);
-    LAUNCH_CHECK(ctx);
+    if (fuse_dx) {
+      DCGP_TRY(patch_adjoint_fused(ctx, L, E, ld, cs, Xin, rows, n_mod, nullptr, dXin));
+    } else {
+      const long n = (long)rows * L.v.H * L.v.W * L.v.C;
+      hipLaunchKernelGGL(col2im_kernel, dim3(blocks_for(n)), dim3(256), 0, ctx->stream, dXcol, rows, L.v.H, L.v.W, L.v.C, L.v.f, L.v.s, L.v.Ho,
+                         L.v.Wo, Ld, dXin);
+      LAUNCH_CHECK(ctx);
+    }
     if (L.identity_mean) {
       hipLaunchKernelGGL(idmean_backward_kernel, dim3(blocks_for(Kc)), dim3(256), 0, ctx->stream, gm, Kc, L.R, P, L.v.Wo, L.v.H, L.v.W, L.v.C,
                          L.v.f, L.v.s, dXin);
       LAUNCH_CHECK(ctx);
     }
   }
+  if (bk.data_only) return DCGP_OK;
   // The main stream's part of this layer ends here (dX is out): it goes straight on to the layer below.
   if (ln.forked) HIP_TRY(ctx, hipEventRecord(ctx->ev_g[3], ctx->stream));
   DCGP_TRY(cond_backward_finish(bk, ln, L, A1, ld, Kc, dKuf, S, false, bk.last_layer && ln.forked));
@@ -1328,6 +1342,19 @@ int dense_head_backward(Bk& bk, LayerState& L, const double* Xin, int rows, int 
   Lanes ln = lanes_of(ctx);
   ln.forked = false; ln.chain = ln.tail = ln.main;   // (a few hundred columns, one patch: everything in line on the main stream)
   DCGP_TRY(cond_backward_main(bk, ln, L, A1, ld, rows, gm, gv, dKzx, gkd, false));
+  if (bk.data_only) {   // x / l -> K_zx -> the conditional: dX = s o (E^T Zs - cs o Xs)
+    hipLaunchKernelGGL(scale_rows_kernel, dim3(blocks_for((long)M * D)), dim3(256), 0, ctx->stream, L.Z, M, (long)M, D, L.in_scale, Zs);
+    LAUNCH_CHECK(ctx);
+    hipLaunchKernelGGL(scale_rows_kernel, dim3(blocks_for((long)rows * D)), dim3(256), 0, ctx->stream, Xin, n_mod, (long)rows, D, L.in_scale, Xs);
+    LAUNCH_CHECK(ctx);
+    DCGP_TRY(e_form(bk, L, dKzx, ld, 1, nullptr, 1.0, Kzx, ld, dKzx, ld, rows, cs, nullptr));
+    DCGP_TRY(patch_backward(bk, L, dKzx, ld, rows, cs, Xs, dXs, 0, Zs, dZs));
+    if (dXin) {
+      hipLaunchKernelGGL(scale_rows_kernel, dim3(blocks_for((long)rows * D)), dim3(256), 0, ctx->stream, dXs, rows, (long)rows, D, L.in_scale, dXin);
+      LAUNCH_CHECK(ctx);
+    }
+    return DCGP_OK;
+  }
   DCGP_TRY(cond_backward_finish(bk, ln, L, A1, ld, rows, dKzx, S, bk.kl_early && !L.white, false));
   if (!bk.kl_early) DCGP_TRY(kl_products(bk, L, L.white ? nullptr : S, false));
   DCGP_TRY(kl_apply(bk, L, false));
@@ -1373,7 +1400,8 @@ int head_backward(Bk& bk, LayerState& L, const double* Xin, int rows, int n_mod,
   // A1 = inv(L) Kzx: left behind by the forward pass's one-launch conditional in a training step (head_forward, keep_k), formed here otherwise
   if (L.a1h_ready) L.a1h_ready = false;
   else DCGP_TRY(gemm_gen(ctx, mk(L.g.Linv, Mp, 1, Kzx, ld, 1, A1, ld, M, rows, M)));
-  const Lanes ln = lanes_of(ctx);
+  Lanes ln = lanes_of(ctx);
+  if (bk.data_only) { ln.forked = false; ln.chain = ln.tail = ln.main; }
   // as in conv_backward: the conditional's column-wise adjoint and the patch-kernel adjoints (K_zx, K_diag) on the main stream, the M x M
   // chain and what needs S beside them
   DCGP_TRY(cond_backward_main(bk, ln, L, A1, ld, rows, gm, gv, dKzx, gkd, bk.last_layer && ln.forked));
@@ -1393,9 +1421,13 @@ int head_backward(Bk& bk, LayerState& L, const double* Xin, int rows, int n_mod,
   DCGP_TRY(im2col(ctx, L, Xin, n_mod, Kc, Xcol));
   // Kzx[m][n] = 1/P sum_p w_p k(Z_m, x_np)
   DCGP_TRY(e_form(bk, L, dKzx, ld, P, L.w, 1.0 / P, Kfull, ldf, E, ldf, Kc, cs, raw));
-  hipLaunchKernelGGL(strided_sum_kernel, dim3(P), dim3(256), 0, ctx->stream, raw, rows, P, 1.0 / P, 1, L.gw);
-  LAUNCH_CHECK(ctx);
-  DCGP_TRY(patch_backward(bk, L, E, ldf, Kc, cs, Xcol, dXin ? dXcol : nullptr, 0, nullptr, nullptr, nullptr, 0.0, &ln));
+  if (!bk.data_only) {
+    hipLaunchKernelGGL(strided_sum_kernel, dim3(P), dim3(256), 0, ctx->stream, raw, rows, P, 1.0 / P, 1, L.gw);
+    LAUNCH_CHECK(ctx);
+  }
+  // (the input gradient's pass, see conv_backward: the K_zx part of dX comes from the fused launch below, ConvKernel's K_diag part rides in as `extra`)
+  const bool fuse_dx = bk.data_only && dXin && patch_adjoint_fused_ok(L, rows);
+  DCGP_TRY(patch_backward(bk, L, E, ldf, Kc, cs, Xcol, dXin && !fuse_dx ? dXcol : nullptr, 0, nullptr, nullptr, nullptr, 0.0, &ln));
   // Kdiag
   if (L.kernel_type == 0) {
     const double inv_l2 = 1.0 / (L.ls * L.ls);
@@ -1413,16 +1445,18 @@ int head_backward(Bk& bk, LayerState& L, const double* Xin, int rows, int n_mod,
     hipLaunchKernelGGL(kdiag_backward_kernel, dim3((P + 3) / 4, rows), dim3(256), 0, ctx->stream, Gm, norms, gkd, L.w, P, L.variance, inv_l2, dwn, pv, pl);
     LAUNCH_CHECK(ctx);
     DCGP_TRY(add_scalars(bk, L, {{0, pv, (long)rows * P, 1.0 / L.variance}, {1, pl, (long)rows * P, inv_l2 / L.ls}}));
-    hipLaunchKernelGGL(strided_sum_kernel, dim3(P), dim3(256), 0, ctx->stream, dwn, rows, P, 1.0, 1, L.gw);
-    LAUNCH_CHECK(ctx);
+    if (!bk.data_only) {
+      hipLaunchKernelGGL(strided_sum_kernel, dim3(P), dim3(256), 0, ctx->stream, dwn, rows, P, 1.0, 1, L.gw);
+      LAUNCH_CHECK(ctx);
+    }
     if (dXin) {
       // d x_p += 2 (E_n X_n - rowsum(E_n) o X_n)_p / l^2   (E symmetric), per image
       GenGemm ge = mk(Gm, P, 1, Xcol, Ld, 1, dXcol, Ld, P, Ld, P);
       ge.batch = rows; ge.a_bs = (long)P * P; ge.b_bs = (long)P * Ld; ge.c_bs = (long)P * Ld;
-      ge.alpha = 2.0 * inv_l2; ge.accumulate = 1; ge.sub_v = pv; ge.sv_bs = P; ge.sub_x = Xcol; ge.sx_rs = Ld; ge.sx_bs = (long)P * Ld;
+      ge.alpha = 2.0 * inv_l2; ge.accumulate = fuse_dx ? 0 : 1; ge.sub_v = pv; ge.sv_bs = P; ge.sub_x = Xcol; ge.sx_rs = Ld; ge.sx_bs = (long)P * Ld;
       DCGP_TRY(gemm_gen(ctx, ge));
     }
-  } else {
+  } else if (!bk.data_only) {   // (no x in it: nothing for the data path)
     // AdditivePatchKernel.Kdiag = mean_p w_p variance (conv_gp/kernels.py:53-61)
     double* tmp = bk.ws("kd_tmp", 2);
     NEED(tmp);
@@ -1433,12 +1467,15 @@ int head_backward(Bk& bk, LayerState& L, const double* Xin, int rows, int n_mod,
     LAUNCH_CHECK(ctx);
     ++bk.slot_v;
   }
-  if (dXin) {
+  if (dXin && fuse_dx) {
+    DCGP_TRY(patch_adjoint_fused(ctx, L, E, ldf, cs, Xin, rows, n_mod, L.kernel_type == 0 ? dXcol : nullptr, dXin));
+  } else if (dXin) {
     const long n = (long)rows * L.v.H * L.v.W * L.v.C;
     hipLaunchKernelGGL(col2im_kernel, dim3(blocks_for(n)), dim3(256), 0, ctx->stream, dXcol, rows, L.v.H, L.v.W, L.v.C, L.v.f, L.v.s, L.v.Ho,
                        L.v.Wo, Ld, dXin);
     LAUNCH_CHECK(ctx);
   }
+  if (bk.data_only) return DCGP_OK;
   // the main stream's part of the head ends here (dX is out): it goes on to the layer below (see conv_backward)
   if (ln.forked) HIP_TRY(ctx, hipEventRecord(ctx->ev_g[3], ctx->stream));
   DCGP_TRY(cond_backward_finish(bk, ln, L, A1, ld, rows, dKzx, S, bk.kl_early && !L.white, bk.last_layer && ln.forked));
@@ -1624,9 +1661,99 @@ int model_backward(dcgp_model* m, const double* X, const int32_t* y, int N, doub
   return DCGP_OK;
 }
 
-extern "C" {
 
-}  // extern "C"
+// ---- the input gradient's reverse pass (input_grad.hip) --------------------------------------------------------------------------------------
+// out[i] = sum_s in[s * n + i]: layer 0 saw the batch tiled S times, the S replicas' dX add up (in the order s = 0, 1, ...)
+namespace {
+__global__ void reduce_replicas1_kernel(const double* __restrict__ a, int S, long n, double* __restrict__ out) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  double s = 0.0;
+  for (int r = 0; r < S; ++r) s += a[(long)r * n + i];
+  out[i] = s;
+}
+}  // namespace
+
+// RobustMax seeds of the "elbo" objective: gm, gv [rows][K] = weight * d E_q[log p(y | f)] / d(mean, var) of the head's rows
+int grad_seed_robustmax(dcgp_model* m, const int32_t* y, int N, double weight, double* gm, double* gv) {
+  dcgp_ctx* ctx = m->ctx;
+  const LayerState& H = *m->layers.back();
+  const auto& oh = m->outs.back();
+  if (H.R > RM_KMAX) return ctx_fail(ctx, DCGP_ERR_ARG, "grad: at most %d classes", RM_KMAX);
+  const double* gh = gauss_hermite_table(ctx);
+  if (!gh) return DCGP_ERR_ALLOC;
+  hipLaunchKernelGGL(robustmax_grad_kernel, dim3((oh.rows + RM_ROWS - 1) / RM_ROWS), dim3(256), 0, ctx->stream, oh.mean, oh.var, y, oh.rows, N, H.R,
+                     m->eps, gh, weight, gm, gv);
+  LAUNCH_CHECK(ctx);
+  return DCGP_OK;
+}
+
+// model_backward's data path alone: from the head's (gm, gv) [rows][R] down to and INCLUDING layer 0, whose dX -- summed over the S replicas of a
+// tiled batch -- goes to out_dX [N][H W C].  Reads what a forward pass with keep_outputs / keep_state left; writes workspaces only (Bk::data_only).
+int model_backward_data(dcgp_model* m, const double* X, int N, int S, int dedup_layer0, double* gm, double* gv, double* out_dX) {
+  dcgp_ctx* ctx = m->ctx;
+  const int nl = (int)m->layers.size();
+  if (!m->keep_outputs) return ctx_fail(ctx, DCGP_ERR_ARG, "input_grad: the forward pass must keep the layer outputs");
+  for (auto& l : m->layers) {
+    if (l->base_type != 0 && l->is_head) return ctx_fail(ctx, DCGP_ERR_ARG, "input_grad: the head kernels are RBF-based");
+  }
+  Bk bk;
+  bk.m = m; bk.ctx = ctx; bk.data_only = true;
+  const std::string mp = "m" + std::to_string(m->id) + "_";
+  bool dedup_done = false;
+  for (int li = nl - 1; li >= 0; --li) {
+    LayerState& L = *m->layers[li];
+    bk.pfx = mp + std::to_string(li) + "_";
+    bk.last_layer = li == 0;
+    const double* Xin = li == 0 ? X : m->outs[li - 1].sample;
+    int rows_l = m->outs[li].rows;
+    if (li == 0 && dedup_layer0 && !L.is_head && rows_l == S * N && S > 1) {   // (see model_backward)
+      if (!dedup_done) {
+        const long n = (long)N * L.v.P * L.R;
+        double* gm0 = (double*)ws_get(ctx, bk.pfx + "g_gm_dedup", (size_t)n * sizeof(double));
+        double* gv0 = (double*)ws_get(ctx, bk.pfx + "g_gv_dedup", (size_t)n * sizeof(double));
+        NEED(gm0); NEED(gv0);
+        hipLaunchKernelGGL(reduce_replicas_kernel, dim3(blocks_for(n)), dim3(256), 0, ctx->stream, gm, gv, S, n, gm0, gv0);
+        LAUNCH_CHECK(ctx);
+        gm = gm0; gv = gv0;
+      }
+      rows_l = N;
+    }
+    const int n_mod = li == 0 ? N : rows_l;
+    const long img = (long)L.v.H * L.v.W * L.v.C;
+    double* dXin = out_dX;
+    if (li > 0 || rows_l != N) {
+      dXin = (double*)ws_get(ctx, bk.pfx + "g_dXin", (size_t)rows_l * img * sizeof(double));
+      NEED(dXin);
+    }
+    if (L.is_head) DCGP_TRY(head_backward(bk, L, Xin, rows_l, n_mod, gm, gv, dXin));
+    else DCGP_TRY(conv_backward(bk, L, Xin, rows_l, n_mod, gm, gv, dXin));
+    if (li == 0) {
+      if (rows_l != N) {
+        if (rows_l % N) return ctx_fail(ctx, DCGP_ERR_ARG, "input_grad: %d rows at layer 0 for %d images", rows_l, N);
+        hipLaunchKernelGGL(reduce_replicas1_kernel, dim3(blocks_for(N * img)), dim3(256), 0, ctx->stream, dXin, rows_l / N, N * img, out_dX);
+        LAUNCH_CHECK(ctx);
+      }
+      break;
+    }
+    auto& o = m->outs[li - 1];
+    const long n = (long)o.rows * o.width;
+    gm = (double*)ws_get(ctx, mp + std::to_string(li - 1) + "_g_gm", (size_t)n * sizeof(double));
+    gv = (double*)ws_get(ctx, mp + std::to_string(li - 1) + "_g_gv", (size_t)n * sizeof(double));
+    NEED(gm); NEED(gv);
+    LayerState& Lb = *m->layers[li - 1];
+    if (li - 1 == 0 && dedup_layer0 && !Lb.is_head && o.rows == S * N && S > 1) {
+      const long n0 = (long)N * o.width;
+      hipLaunchKernelGGL(sample_backward_dedup_kernel, dim3(blocks_for(n0)), dim3(256), 0, ctx->stream, dXin, o.sample, o.mean, o.var, m->jitter, S, n0,
+                         gm, gv);
+      dedup_done = true;
+    } else {
+      hipLaunchKernelGGL(sample_backward_kernel, dim3(blocks_for(n)), dim3(256), 0, ctx->stream, dXin, o.sample, o.mean, o.var, m->jitter, n, gm, gv);
+    }
+    LAUNCH_CHECK(ctx);
+  }
+  return DCGP_OK;
+}
 
 // Adam step enqueued behind the reverse pass (dcgp_model_train_step_adam): lr is the bias-corrected rate
 struct AdamReq { double lr_t, beta1, beta2, eps; };

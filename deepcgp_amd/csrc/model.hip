@@ -185,7 +185,7 @@ int forward_all(dcgp_model* m, const double* X, int N, int S, const double* cons
   DCGP_TRY(ensure_events(m));
   // The chain of the previous step stands if no parameter was written since and this step may use it (model_state.h: factor_reuse): same bank, no
   // preparation, no factorisation, no G / alpha, no KL launches -- the step is its data path.
-  const bool reuse = !pipelined && !m->grad_follows && !m->keep_state && m->chain_version == m->param_version && m->chain_with_kl == need_kl &&
+  const bool reuse = !pipelined && !m->grad_follows && (!m->keep_state || m->data_grad) && m->chain_version == m->param_version && m->chain_with_kl == need_kl &&
                      m->factor_reuse >= (need_kl ? 2 : 1) && !ctx->opt.no_factor_reuse;
   if (!reuse) m->chain_version = 0;   // (stays 0 if this step fails on the way)
   const int bank = reuse ? m->bank : m->bank ^ 1;
@@ -426,7 +426,7 @@ int forward_all(dcgp_model* m, const double* X, int N, int S, const double* cons
     hipStreamSynchronize(chain_s);
     return rc;
   }
-  if (!reuse && !pipelined && !m->grad_follows && !m->keep_state) { m->chain_version = m->param_version; m->chain_with_kl = need_kl; }
+  if (!reuse && !pipelined && !m->grad_follows && (!m->keep_state || m->data_grad)) { m->chain_version = m->param_version; m->chain_with_kl = need_kl; }
   // A training step: the parameter-only part of the reverse pass (grad.hip, grad_kl_early) runs beside the forward pass on the auxiliary
   // stream.  Its start is marked behind the FIRST layer (below): that layer's launch fills the chip at the full batch, and forty short
   // launches squeezed in between its rounds cost it more than they gained.  They are enqueued by dcgp_elbo_grad behind the whole forward
@@ -690,6 +690,13 @@ int dcgp_model_set_likelihood(dcgp_model* model, int kind, double variance) {
 }
 
 }  // extern "C"
+
+int forward_data_impl(dcgp_model* model, const double* X, int N, int S, const double* const* z_per_layer_host, uint64_t seed,
+                      int dedup_layer0, int* rows_last) {
+  StreamGuard guard(model->ctx);
+  DCGP_TRY(forward_all(model, X, N, S, z_per_layer_host, seed, dedup_layer0, false, false, rows_last));
+  return forward_done(model, nullptr);   // the caller synchronises the stream before it returns
+}
 
 int elbo_forward_enqueue_impl(dcgp_model* model, const double* X, const int32_t* y, int N, double scale,
                               const double* const* z_per_layer_host, uint64_t seed, int dedup_layer0, uint64_t* ticket,

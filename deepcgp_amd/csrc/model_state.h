@@ -18,6 +18,8 @@ struct dcgp_model {
   bool has_head = false;
   bool keep_outputs = false;
   bool keep_state = false;   // the forward leaves K_uf / A1 of every conv layer in HBM (set around the forward of dcgp_elbo_grad)
+  bool data_grad = false;    // set around the forward of dcgp_model_input_grad: keep_state without a training step -- the parameter-only chain is
+                             // an evaluation's (it may stand, and it is recorded, as for propagate / predict_y)
   bool grad_follows = false; // set around the forward of dcgp_elbo_grad: forward_all hands the parameter-only part of the reverse pass to the side stream
   int gkl_state = 0;         // forward_all of such a step: 0 nothing to hand over, 1 the side stream itself holds the parameter-only chain, 2 it waits for ctx->ev_fork
   int gkl_prep_wait = 0;     // forward_all: grad_kl_early must also wait for ev_prep[bank][0 .. gkl_prep_wait) (chain on a side stream, mark on the main stream)
@@ -98,3 +100,17 @@ int model_backward(dcgp_model* model, const double* X, const int32_t* y, int N, 
 // enqueue == false: 1 if a training step's forward should hand the KL adjoint's products to the side stream, else 0;
 // enqueue == true: do it (wait_fork: behind ctx->ev_fork, recorded where the parameter-only chain ended)
 int grad_kl_early(dcgp_model* model, bool enqueue, bool wait_fork);
+
+// model.hip: the data path of an evaluation forward (propagate's: no KL, factor reuse as for propagate) on `S` samples, asynchronous on ctx->stream;
+// with keep_outputs / keep_state / data_grad set it leaves what model_backward_data reads.  *rows_last: rows of the head's mean / var.
+int forward_data_impl(dcgp_model* model, const double* X, int N, int S, const double* const* z_per_layer_host, uint64_t seed,
+                      int dedup_layer0, int* rows_last);
+// grad.hip: the reverse pass's data path only (no gradient block is touched), from the head's seeds gm, gv [rows][R] to out_dX [N][H W C] (device);
+// grad_seed_robustmax: the RobustMax seeds of the variational expectation, times weight
+int model_backward_data(dcgp_model* model, const double* X, int N, int S, int dedup_layer0, double* gm, double* gv, double* out_dX);
+int grad_seed_robustmax(dcgp_model* model, const int32_t* y, int N, double weight, double* gm, double* gv);
+// input_grad.hip: dX of a scalar-lengthscale RBF patch layer from E / cs in one launch (the product on the matrix pipe, the fold in LDS);
+// extra [rows P][L] or nullptr is added to the patch gradients before the fold.  _ok: the shape is covered (otherwise the product + col2im pair)
+bool patch_adjoint_fused_ok(const LayerState& L, long rows);
+int patch_adjoint_fused(dcgp_ctx* ctx, const LayerState& L, const double* E, long ld, const double* cs, const double* Xin, int rows, int n_mod,
+                        const double* extra, double* dXin);

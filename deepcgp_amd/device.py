@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("DCGP_LIB", os.path.join(_HERE, "libdcgp.so"))   # DCG
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "dcgp.h")
 
 DCGP_OK, ERR_ARG, ERR_HIP, ERR_NOT_PD, ERR_RCCL, ERR_ALLOC = 0, -1, -2, -3, -4, -5
+OBJECTIVE_DENSITY, OBJECTIVE_ELBO, INPUT_GRAD_DEDUP = 0, 1, 0x100   # dcgp_model_input_grad's `objective` (include/dcgp.h)
 
 
 class LibraryMissing(RuntimeError):
@@ -108,6 +109,8 @@ _SIGS = {
     "dcgp_model_natgrad_step": [_vp, _d, _ip],
     "dcgp_model_predict_y": [_vp, _vp, _i, _i, C.POINTER(_vp), _u64, _vp, _vp, _ip],
     "dcgp_model_predict_density": [_vp, _vp, _vp, _i, _i, C.POINTER(_vp), _u64, _vp, _ip],
+    "dcgp_model_input_grad": [_vp, _vp, _vp, _i, _i, C.POINTER(_vp), _u64, _i, _vp, _vp, _ip],
+    "dcgp_model_input_grad_f64y": [_vp, _vp, _vp, _i, _i, C.POINTER(_vp), _u64, _i, _vp, _vp, _ip],
     "dcgp_model_evaluate": [_vp, _vp, _vp, _i, _i, _i, C.POINTER(_vp), _u64, _vp, _vp, _dp, _ip],
     "dcgp_model_layer_output": [_vp, _i, _vp, _vp, _vp, _ip, _ip],
     "dcgp_model_set_likelihood": [_vp, _i, _d],

@@ -344,6 +344,69 @@ class DGP_Base:
             grads[-1]["likelihood_variance"] = buf.reshape(())
         return out[0], grads
 
+    OBJECTIVES = {"density": 0, "elbo": 1}
+
+    def _input_grad_args(self, S, objective):
+        """Argument checks of ``input_gradient`` that need no device: (S, objective code)."""
+        if objective not in self.OBJECTIVES:
+            raise ValueError("objective must be 'density' or 'elbo', got %r" % (objective,))
+        if objective == "density" and self.float_targets:
+            raise NotImplementedError("input_gradient: the 'density' objective exists for the RobustMax likelihood only; a %s model takes "
+                                      "objective='elbo'" % ("Gaussian" if self.gaussian else "Bernoulli"))
+        S = self.num_samples if S is None else int(S)
+        if S < 1:
+            raise ValueError("S must be >= 1")
+        return S, self.OBJECTIVES[objective]
+
+    def input_gradient(self, X, Y, S=None, objective="density", zs=None, seed=0):
+        """(J [N], dX [N, D_in]): a per-image objective and its gradient with respect to the input pixels, one device call
+        (dcgp_model_input_grad).  ``objective="density"``: J_n = log 1/S sum_s p(y_n | f_sn), the value ``predict_density`` returns for
+        the same (S, zs, seed) (RobustMax models); ``"elbo"``: J_n = 1/S sum_s E_q[log p(y_n | f_sn)], the image's unscaled share of the
+        ELBO's data term (every likelihood).  ``S=None`` takes ``num_samples``; ``zs`` per layer [S, N, D].  X and Y may be host arrays
+        or DeviceArrays.  Training state (parameters, gradients on the device, Adam moments, factor reuse) is left untouched."""
+        S, code = self._input_grad_args(S, objective)
+        N = np.shape(X)[0] if not isinstance(X, dev.DeviceArray) else X.shape[0]
+        if N == 0:
+            return np.zeros(0), np.zeros((0, self.X.shape[1]))
+        if not isinstance(X, dev.DeviceArray):
+            X = np.reshape(X, (N, -1))
+            if X.shape[1] != self.X.shape[1]:
+                raise ValueError("images of %d values, the model takes %d" % (X.shape[1], self.X.shape[1]))
+        if not self.float_targets and not isinstance(Y, dev.DeviceArray):
+            Yh = np.reshape(Y, (-1,))
+            K = self.layers[-1].num_outputs
+            if Yh.size != N:
+                raise ValueError("%d labels for %d images" % (Yh.size, N))
+            if Yh.size and (Yh.min() < 0 or Yh.max() >= K):
+                raise ValueError("labels outside [0, %d)" % K)
+        self._build()
+        ctx, L = self._ctx, dev.lib()
+        dX = ctx.as_device(X)
+        dY, f64y = self._targets(Y, N)
+        arr, keep = self._z_table(zs, N, S)
+        J, g = ctx.empty((N,)), ctx.empty((N, self.X.shape[1]))
+        info = C.c_int(0)
+        code |= dev.INPUT_GRAD_DEDUP if self.dedup_layer0 else 0
+        ctx._check((L.dcgp_model_input_grad_f64y if f64y else L.dcgp_model_input_grad)(self._model, dX.ptr, dY.ptr, N, S, arr, int(seed), code, J.ptr, g.ptr,
+                                                                                     C.byref(info)), info)
+        return J.numpy(), g.numpy()
+
+    def saliency(self, X, Y=None, S=None, objective="density", zs=None, seed=0):
+        """Saliency maps [N, H, W, C]: ``input_gradient``'s dX in the first layer's image shape.  ``Y=None`` takes the model's own
+        prediction (``predict_proba(X, S, zs, seed).argmax(1)``, the same noise) as the label."""
+        S = self.num_samples if S is None else int(S)
+        if Y is None:
+            if self.float_targets:
+                raise ValueError("saliency: a Gaussian or Bernoulli model needs targets Y")
+            Y = self.predict_proba(X, S, zs=zs, seed=seed).argmax(axis=1)
+        _, g = self.input_gradient(X, Y, S=S, objective=objective, zs=zs, seed=seed)
+        l0 = self.layers[0]
+        v = l0.view if hasattr(l0, "view") else getattr(l0.kern, "view", None)
+        if v is None:      # dense head on flat features: no image shape
+            return g
+        C_in = l0.feature_maps_in if hasattr(l0, "feature_maps_in") else v.feature_maps
+        return g.reshape(g.shape[0], v.input_size[0], v.input_size[1], C_in)
+
     def adam_step(self, lr, t=None, beta1=0.9, beta2=0.999, epsilon=1e-8):
         """One Adam step (tf.train.AdamOptimizer defaults, gpflow.train.AdamOptimizer at
         conv_gp/experiment.py:104-107) on the gradients the last ``compute_gradients`` left on the device,

@@ -170,6 +170,58 @@ class AccuracyLogger(object):
         return correct / max(Y.size, 1)
 
 
+def adversarial_examples(model, X, Y, epsilon, steps=1, step_size=None, clip=None, objective="density", S=None, seed=0, zs=None):
+    """Adversarial images in the L-infinity ball of radius ``epsilon`` around X, same shape as X.  ``steps=1`` is the fast gradient sign
+    method, X - epsilon sign(dJ/dX): it lowers the objective (the log density of the true label) to first order; ``steps > 1`` is its
+    iterated form with steps of ``step_size`` (default epsilon / steps), each followed by the projection onto the ball and onto
+    ``clip=(lo, hi)`` if given.  A host loop over ``model.input_gradient`` with the same noise (``seed`` / ``zs``) at every step."""
+    epsilon, steps = float(epsilon), int(steps)
+    if not epsilon >= 0.0:
+        raise ValueError("epsilon must be >= 0, got %r" % (epsilon,))
+    if steps < 1:
+        raise ValueError("steps must be >= 1, got %r" % (steps,))
+    step = epsilon / steps if step_size is None else float(step_size)
+    if not step >= 0.0:
+        raise ValueError("step_size must be >= 0, got %r" % (step_size,))
+    if clip is not None:
+        lo, hi = float(clip[0]), float(clip[1])
+        if not lo <= hi:
+            raise ValueError("clip must be (lo, hi) with lo <= hi, got %r" % (clip,))
+    X0 = np.asarray(X, np.float64)
+    flat = X0.reshape(X0.shape[0], -1)
+    adv = flat.copy()
+    for _ in range(steps):
+        _, g = model.input_gradient(adv, Y, S=S, objective=objective, zs=zs, seed=seed)
+        adv = adv - step * np.sign(g)
+        adv = np.minimum(np.maximum(adv, flat - epsilon), flat + epsilon)
+        if clip is not None:
+            adv = np.clip(adv, lo, hi)
+    return adv.reshape(X0.shape)
+
+
+class AdversarialAccuracyLogger(object):
+    """Test accuracy on adversarial images, with AccuracyLogger's batching (32 images, five samples, batch i drawing from seed + i):
+    each batch is attacked with ``adversarial_examples`` (FGSM for ``steps=1``) under the noise it is then classified with."""
+    title = 'adversarial_accuracy'
+
+    def __init__(self, X_test, Y_test, epsilon, steps=1, step_size=None, clip=None, objective="density", batch_size=32, num_samples=5):
+        self.X_test, self.Y_test = X_test, np.reshape(Y_test, (-1,))
+        self.epsilon, self.steps, self.step_size, self.clip, self.objective = float(epsilon), int(steps), step_size, clip, objective
+        self.batch_size, self.num_samples = int(batch_size), int(num_samples)
+
+    def __call__(self, model, seed=0):
+        if getattr(model, "float_targets", False):
+            raise ValueError("AdversarialAccuracyLogger: needs a multi-class (RobustMax) model")
+        correct = 0
+        for i, lo in enumerate(range(0, len(self.Y_test), self.batch_size)):
+            sl = slice(lo, lo + self.batch_size)
+            adv = adversarial_examples(model, self.X_test[sl], self.Y_test[sl], self.epsilon, steps=self.steps, step_size=self.step_size,
+                                       clip=self.clip, objective=self.objective, S=self.num_samples, seed=seed + i)
+            p = model.predict_proba(adv, self.num_samples, seed=seed + i)
+            correct += int((p.argmax(axis=1) == self.Y_test[sl]).sum())
+        return correct / max(self.Y_test.size, 1)
+
+
 class UncertaintyLogger(object):
     """Calibration and uncertainty of the test predictions with AccuracyLogger's batching (32 images, five samples, batch i drawing
     from seed + i): the dataset dict of ``DGP_Base.evaluate_uncertainty`` -- accuracy, mean log density, ECE, MCE, Brier score, mean

@@ -323,6 +323,24 @@ int dcgp_model_predict_y(dcgp_model* model, const double* X, int N, int S,
  * The class probabilities are dcgp_model_predict_y's; y [N] int32 in [0, K) (device), else DCGP_ERR_ARG.                              */
 int dcgp_model_predict_density(dcgp_model* model, const double* X, const int32_t* y, int N, int S,
                                const double* const* z_per_layer, uint64_t seed, double* out_logdens, int* info_host);
+/* Input gradients (saliency maps, adversarial examples; the reference's users get them from tf.gradients on predict_density / the ELBO).
+ * Per image n of the batch an objective J_n, with the noise fixed by z_per_layer or seed exactly as in dcgp_model_predict_density:
+ *   DCGP_OBJECTIVE_DENSITY  J_n = log(1/S sum_s p(y_n | f_sn)), dcgp_model_predict_density's value (RobustMax models only; a Gaussian or
+ *                           Bernoulli model gets DCGP_ERR_ARG, never the other objective),
+ *   DCGP_OBJECTIVE_ELBO     J_n = 1/S sum_s E_q[log p(y_n | f_sn)], the image's share of the ELBO's data term, unscaled, without the KL.
+ * out_value [N] = J (device, may be NULL), out_dX [N][H*W*C] = dJ_n / dX_n (device; the layers treat images independently, so it is
+ * also d(sum_n J_n) / dX).  `objective` may be OR-ed with DCGP_INPUT_GRAD_DEDUP: layer 0's conditional runs on the N distinct images
+ * instead of the batch tiled S times (dcgp_elbo_grad's dedup_layer0; the same result up to summation order).
+ * One call: a forward pass that keeps the layer outputs, the objective's adjoint at the head, and the data path only of the reverse
+ * pass down to layer 0 -- no parameter gradient is formed.  Parameters, the gradient blocks (dcgp_model_get_grad), Adam moments, the step
+ * count and the parameter version (dcgp_model_set_factor_reuse keeps its chain, and this call uses it) are left as they were; no atomics,
+ * so two calls give the same bits.  y [N] int32 in [0, K) (device), else DCGP_ERR_ARG; DCGP_ERR_NOT_PD with *info_host as elsewhere. */
+#define DCGP_OBJECTIVE_DENSITY 0
+#define DCGP_OBJECTIVE_ELBO 1
+#define DCGP_INPUT_GRAD_DEDUP 0x100
+int dcgp_model_input_grad(dcgp_model* model, const double* X, const int32_t* y, int N, int S,
+                          const double* const* z_per_layer, uint64_t seed, int objective,
+                          double* out_value, double* out_dX, int* info_host);
 /* A whole test set in batches of `batch` images, enqueued back to back, ONE stream synchronisation per call -- the loops of the reference's
  * AccuracyLogger (conv_gp/utils/log.py:50-67) and of a test log density over DS-DGP DGP_Base.predict_density, one device call.
  * Batch b = images [b*batch, min((b+1)*batch, N_total)), noise from seed + b (AccuracyLogger's convention), or from
@@ -388,6 +406,11 @@ int dcgp_model_patch_evidence(dcgp_model* model, const double* X, int N, int S, 
  * logsumexp_s log N(y; mu_s, var_s + s2) - log S per image and output. */
 int dcgp_model_predict_density_f64y(dcgp_model* model, const double* X, const double* y, int N, int S,
                                     const double* const* z_per_layer, uint64_t seed, double* out_logdens, int* info_host);
+/* dcgp_model_input_grad with float64 targets y [N, K] (device) for a Gaussian or Bernoulli model: DCGP_OBJECTIVE_ELBO only, J_n summed
+ * over the K outputs. */
+int dcgp_model_input_grad_f64y(dcgp_model* model, const double* X, const double* y, int N, int S,
+                               const double* const* z_per_layer, uint64_t seed, int objective,
+                               double* out_value, double* out_dX, int* info_host);
 /* dcgp_model_evaluate for a Gaussian model: out_logdens [N_total] per image (summed over the K outputs), out_y_mean [N_total][K] the
  * sample-mean prediction (device, either may be NULL); out_host[2] = {sum of the squared errors of the sample-mean prediction, sum of
  * the per-image log densities}. */
