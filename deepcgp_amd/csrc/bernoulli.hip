@@ -74,7 +74,7 @@ __global__ __launch_bounds__(256) void bern_tail_kernel(BernTailArgs a, KlTail k
     if (tid < o) red[tid] += red[tid + o];
     __syncthreads();
   }
-  if (tid == 0) elbo_assemble(t, red[0] * t.inv_s);
+  if (tid == 0) elbo_assemble(t.scal, t.fin, red[0] * t.inv_s);
 }
 
 // Reverse tail: d (weight * ve) / d mu and / d v per element of [rows][K], one thread each.  With f_i = mu + s x_i:

@@ -171,7 +171,7 @@ __global__ __launch_bounds__(256) void elbo_tail_kernel(TailArgs t, KlTail kl) {
     if (tid < o) red[tid] += red[tid + o];
     __syncthreads();
   }
-  if (tid == 0) elbo_assemble(t, red[0] * t.inv_s);
+  if (tid == 0) elbo_assemble(t.scal, t.fin, red[0] * t.inv_s);
 }
 
 __global__ __launch_bounds__(1024) void reduce_sum_kernel(const double* __restrict__ in, long n, double scale,

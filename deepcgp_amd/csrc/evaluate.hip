@@ -76,7 +76,7 @@ __global__ __launch_bounds__(kEvalThreads) void eval_tail_kernel(EvalTailArgs a)
 // order from run to run), res[2] = first non-positive pivot of the factorisations the batches used (0: none), res[3] = labels
 // outside [0, K).
 __global__ __launch_bounds__(1024) void eval_sum_kernel(const double* __restrict__ logdens, const int* __restrict__ ok, long n,
-                                                        EvalStatus st, double* __restrict__ res) {
+                                                        FactorStatus st, double* __restrict__ res) {
   __shared__ double red[3][1024];
   const int tid = threadIdx.x;
   double s = 0.0, c = 0.0, bad = 0.0;
@@ -94,10 +94,7 @@ __global__ __launch_bounds__(1024) void eval_sum_kernel(const double* __restrict
     __syncthreads();
   }
   if (tid != 0) return;
-  int pivot = 0;
-  for (int q = 0; q < st.ngroups; ++q)
-    for (int j = 0; j < st.ninfo[q]; ++j)
-      if (st.info[q][j] && !pivot) pivot = st.info[q][j];
+  const int pivot = first_bad_pivot(st);
   res[0] = red[0][0];
   res[1] = red[1][0];
   res[2] = (double)pivot;
@@ -121,7 +118,7 @@ int eval_tail(dcgp_ctx* ctx, const double* mu, const double* var, const int32_t*
   return DCGP_OK;
 }
 
-int eval_sum(dcgp_ctx* ctx, const double* logdens, const int* ok, long n, const EvalStatus& st, double* res) {
+int eval_sum(dcgp_ctx* ctx, const double* logdens, const int* ok, long n, const FactorStatus& st, double* res) {
   hipLaunchKernelGGL(eval_sum_kernel, dim3(1), dim3(1024), 0, ctx->stream, logdens, ok, n, st, res);
   LAUNCH_CHECK(ctx);
   return DCGP_OK;

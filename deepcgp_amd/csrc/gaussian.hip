@@ -7,7 +7,7 @@
 // Every kernel reads s2 from its device word (the optimiser moves it there), so steps enqueued back to back see the value the
 // previous step left.  Sums run in a fixed order (a tree per workgroup, then the last workgroup to arrive over the partials in
 // index order): results are bitwise reproducible, no float atomics.  The RobustMax tails (cond.hip, grad.hip, evaluate.hip) are
-// untouched; model.hip / grad.hip pick these by dcgp_model::lik_kind.
+// untouched; likelihood.hip picks these by the model's Likelihood.
 #include "layer_impl.h"
 #include "tail_dev.h"
 
@@ -56,7 +56,7 @@ __global__ __launch_bounds__(256) void gauss_tail_kernel(GaussTailArgs a, KlTail
     if (tid < o) red[tid] += red[tid + o];
     __syncthreads();
   }
-  if (tid == 0) elbo_assemble(t, red[0] * t.inv_s);
+  if (tid == 0) elbo_assemble(t.scal, t.fin, red[0] * t.inv_s);
 }
 
 // Reverse tail: d (w sum ve) / d(mu, var) per element and d / d s2 of the whole sum.  One thread per element of [rows][K]; each
@@ -148,7 +148,7 @@ __global__ __launch_bounds__(256) void gauss_eval_tail_kernel(const double* __re
 // One workgroup behind the last batch: res[0] = sum of the squared errors, res[1] = sum of the log densities (strided per thread, then
 // a tree), res[2] = first non-positive pivot of the factorisations the batches used.
 __global__ __launch_bounds__(1024) void gauss_eval_sum_kernel(const double* __restrict__ logdens, const double* __restrict__ sqerr, long n,
-                                                              EvalStatus st, double* __restrict__ res) {
+                                                              FactorStatus st, double* __restrict__ res) {
   __shared__ double red[2][1024];
   const int tid = threadIdx.x;
   double s = 0.0, e = 0.0;
@@ -160,10 +160,7 @@ __global__ __launch_bounds__(1024) void gauss_eval_sum_kernel(const double* __re
     __syncthreads();
   }
   if (tid != 0) return;
-  int pivot = 0;
-  for (int q = 0; q < st.ngroups; ++q)
-    for (int j = 0; j < st.ninfo[q]; ++j)
-      if (st.info[q][j] && !pivot) pivot = st.info[q][j];
+  const int pivot = first_bad_pivot(st);
   res[0] = red[0][0];
   res[1] = red[1][0];
   res[2] = (double)pivot;
@@ -222,7 +219,7 @@ int gauss_eval_tail(dcgp_ctx* ctx, const double* mu, const double* var, const do
   return DCGP_OK;
 }
 
-int gauss_eval_sum(dcgp_ctx* ctx, const double* logdens, const double* sqerr, long n, const EvalStatus& st, double* res) {
+int gauss_eval_sum(dcgp_ctx* ctx, const double* logdens, const double* sqerr, long n, const FactorStatus& st, double* res) {
   hipLaunchKernelGGL(gauss_eval_sum_kernel, dim3(1), dim3(1024), 0, ctx->stream, logdens, sqerr, n, st, res);
   LAUNCH_CHECK(ctx);
   return DCGP_OK;

@@ -1548,51 +1548,51 @@ int grad_kl_early(dcgp_model* m, bool enqueue, bool wait_fork) {
   return rc;
 }
 
-int model_backward(dcgp_model* m, const double* X, const int32_t* y, int N, double scale, int dedup_layer0, const double* yf) {
-  dcgp_ctx* ctx = m->ctx;
-  const int nl = (int)m->layers.size(), S = m->S;
-  if (!m->keep_outputs) return ctx_fail(ctx, DCGP_ERR_ARG, "grad: the forward pass must keep the layer outputs");
-  for (auto& l : m->layers) {
-    if (l->base_type != 0 && l->is_head) return ctx_fail(ctx, DCGP_ERR_ARG, "grad: the head kernels are RBF-based");
-  }
+// out[i] = sum_s in[s * n + i]: layer 0 saw the batch tiled S times, the S replicas' dX add up (in the order s = 0, 1, ...)
+namespace {
+__global__ void reduce_replicas1_kernel(const double* __restrict__ a, int S, long n, double* __restrict__ out) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  double s = 0.0;
+  for (int r = 0; r < S; ++r) s += a[(long)r * n + i];
+  out[i] = s;
+}
+}  // namespace
+
+// RobustMax seeds of the variational expectation: gm, gv [rows][K] = weight * d E_q[log p(y | f)] / d(mean, var), row r with label y[r % n_labels]
+int robustmax_grad(dcgp_ctx* ctx, const double* mu, const double* var, const int32_t* y, int rows, int n_labels, int K, double eps, double weight,
+                   double* gm, double* gv) {
+  if (K > RM_KMAX) return ctx_fail(ctx, DCGP_ERR_ARG, "grad: at most %d classes", RM_KMAX);
   const double* gh = gauss_hermite_table(ctx);
   if (!gh) return DCGP_ERR_ALLOC;
-  bool prepped = false;
-  for (int f : m->prep_early) prepped = prepped || f != 0;
-  if (prepped) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_kl2, 0));   // fills and parameter-only operands from the side stream (grad_kl_early)
-  Bk bk;
-  bk.m = m; bk.ctx = ctx;
-  bk.klw = kl_weight(m);
-  const std::string mp = "m" + std::to_string(m->id) + "_";
-  LayerState& H = *m->layers[nl - 1];
-  auto& oh = m->outs[nl - 1];
-  const int rows = oh.rows;
-  const double weight = scale * ((rows == S * N) ? 1.0 / S : 1.0);
-  double* gm = (double*)ws_get(ctx, mp + "g_gm_head", (size_t)rows * H.R * sizeof(double));
-  double* gv = (double*)ws_get(ctx, mp + "g_gv_head", (size_t)rows * H.R * sizeof(double));
-  NEED(gm); NEED(gv);
-  double* gs2 = nullptr;   // Gaussian likelihood: d / d variance, moved into the head's block (glik) once its zero fill is behind us
-  if (yf && m->lik_kind == 2) {
-    DCGP_TRY(bern_grad(ctx, oh.mean, oh.var, yf, rows, H.R, N, weight, gm, gv));
-  } else if (yf) {
-    if (!m->d_lik || !H.lik_slots) return ctx_fail(ctx, DCGP_ERR_ARG, "grad: Gaussian targets on a model without the Gaussian likelihood");
-    gs2 = (double*)ws_get(ctx, mp + "g_lik", sizeof(double));
-    NEED(gs2);
-    DCGP_TRY(gauss_grad(ctx, oh.mean, oh.var, yf, rows, H.R, N, m->d_lik, weight, gm, gv, gs2));
-  } else {
-    if (H.R > RM_KMAX) return ctx_fail(ctx, DCGP_ERR_ARG, "grad: at most %d classes", RM_KMAX);
-    hipLaunchKernelGGL(robustmax_grad_kernel, dim3((rows + RM_ROWS - 1) / RM_ROWS), dim3(256), 0, ctx->stream, oh.mean, oh.var, y, rows, N, H.R,
-                       m->eps, gh, weight, gm, gv);
-    LAUNCH_CHECK(ctx);
+  hipLaunchKernelGGL(robustmax_grad_kernel, dim3((rows + RM_ROWS - 1) / RM_ROWS), dim3(256), 0, ctx->stream, mu, var, y, rows, n_labels, K, eps, gh, weight,
+                     gm, gv);
+  LAUNCH_CHECK(ctx);
+  return DCGP_OK;
+}
+
+// The reverse walk over the layers, from the head's (gm, gv) [rows][R] down to layer 0, on what a forward pass with keep_outputs / keep_state left.
+// bk.data_only (the input gradient): the data path alone, down to and INCLUDING layer 0's dX, which -- summed over the S replicas of a tiled batch --
+// goes to out_dX [N][H W C]; nothing but workspaces is written.  Otherwise (a training step, out_dX == nullptr): every layer's gradient block, layer
+// 0 produces no dX, and what grad_kl_early enqueued beside the forward pass is consumed per layer.
+static int backward_walk(Bk& bk, const double* X, int N, int S, int dedup_layer0, double* gm, double* gv, double* out_dX, const char* who) {
+  dcgp_model* m = bk.m;
+  dcgp_ctx* ctx = bk.ctx;
+  const int nl = (int)m->layers.size();
+  if (!m->keep_outputs) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: the forward pass must keep the layer outputs", who);
+  for (auto& l : m->layers) {
+    if (l->base_type != 0 && l->is_head) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: the head kernels are RBF-based", who);
   }
+  const std::string mp = "m" + std::to_string(m->id) + "_";
   bool dedup_done = false;   // layer 0's (dmean, dvar) already summed over the S replicas
   for (int li = nl - 1; li >= 0; --li) {
     LayerState& L = *m->layers[li];
     bk.pfx = mp + std::to_string(li) + "_";
     bk.last_layer = li == 0;
-    bk.kl_early = li < 8 && m->kl_early[li];
-    bk.prep = li < 8 ? m->prep_early[li] : 0;
-    if (li < 8) { m->kl_early[li] = false; m->prep_early[li] = 0; }
+    if (!bk.data_only && li < 8) {
+      bk.kl_early = m->kl_early[li]; bk.prep = m->prep_early[li];
+      m->kl_early[li] = false; m->prep_early[li] = 0;
+    }
     const double* Xin = li == 0 ? X : m->outs[li - 1].sample;
     int rows_l = m->outs[li].rows;                  // rows entering == rows leaving ...
     // ... except for a de-duplicated first conv layer: propagate() tiles the batch S times, so layer 0 saw S identical
@@ -1611,31 +1611,63 @@ int model_backward(dcgp_model* m, const double* X, const int32_t* y, int N, doub
       rows_l = N;
     }
     const int n_mod = li == 0 ? N : rows_l;
-    double* dXin = nullptr;
-    if (li > 0) {
-      dXin = (double*)ws_get(ctx, bk.pfx + "g_dXin", (size_t)rows_l * L.v.H * L.v.W * L.v.C * sizeof(double));
+    const long img = (long)L.v.H * L.v.W * L.v.C;
+    double* dXin = li == 0 ? out_dX : nullptr;   // (layer 0 of a training step: no dX)
+    if (li > 0 || (out_dX && rows_l != N)) {
+      dXin = (double*)ws_get(ctx, bk.pfx + "g_dXin", (size_t)rows_l * img * sizeof(double));
       NEED(dXin);
     }
     if (L.is_head) DCGP_TRY(head_backward(bk, L, Xin, rows_l, n_mod, gm, gv, dXin));
     else DCGP_TRY(conv_backward(bk, L, Xin, rows_l, n_mod, gm, gv, dXin));
-    if (li > 0) {
-      auto& o = m->outs[li - 1];
-      const long n = (long)o.rows * o.width;
-      gm = (double*)ws_get(ctx, mp + std::to_string(li - 1) + "_g_gm", (size_t)n * sizeof(double));
-      gv = (double*)ws_get(ctx, mp + std::to_string(li - 1) + "_g_gv", (size_t)n * sizeof(double));
-      NEED(gm); NEED(gv);
-      LayerState& Lb = *m->layers[li - 1];
-      if (li - 1 == 0 && dedup_layer0 && !Lb.is_head && o.rows == S * N && S > 1) {   // S gradients per element of the shared conditional: summed here
-        const long n0 = (long)N * o.width;
-        hipLaunchKernelGGL(sample_backward_dedup_kernel, dim3(blocks_for(n0)), dim3(256), 0, ctx->stream, dXin, o.sample, o.mean, o.var, m->jitter, S, n0,
-                           gm, gv);
-        dedup_done = true;
-      } else {
-        hipLaunchKernelGGL(sample_backward_kernel, dim3(blocks_for(n)), dim3(256), 0, ctx->stream, dXin, o.sample, o.mean, o.var, m->jitter, n, gm, gv);
+    if (li == 0) {
+      if (out_dX && rows_l != N) {   // the final replica sum
+        if (rows_l % N) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: %d rows at layer 0 for %d images", who, rows_l, N);
+        hipLaunchKernelGGL(reduce_replicas1_kernel, dim3(blocks_for(N * img)), dim3(256), 0, ctx->stream, dXin, rows_l / N, N * img, out_dX);
+        LAUNCH_CHECK(ctx);
       }
-      LAUNCH_CHECK(ctx);
+      break;
     }
+    auto& o = m->outs[li - 1];
+    const long n = (long)o.rows * o.width;
+    gm = (double*)ws_get(ctx, mp + std::to_string(li - 1) + "_g_gm", (size_t)n * sizeof(double));
+    gv = (double*)ws_get(ctx, mp + std::to_string(li - 1) + "_g_gv", (size_t)n * sizeof(double));
+    NEED(gm); NEED(gv);
+    LayerState& Lb = *m->layers[li - 1];
+    if (li - 1 == 0 && dedup_layer0 && !Lb.is_head && o.rows == S * N && S > 1) {   // S gradients per element of the shared conditional: summed here
+      const long n0 = (long)N * o.width;
+      hipLaunchKernelGGL(sample_backward_dedup_kernel, dim3(blocks_for(n0)), dim3(256), 0, ctx->stream, dXin, o.sample, o.mean, o.var, m->jitter, S, n0,
+                         gm, gv);
+      dedup_done = true;
+    } else {
+      hipLaunchKernelGGL(sample_backward_kernel, dim3(blocks_for(n)), dim3(256), 0, ctx->stream, dXin, o.sample, o.mean, o.var, m->jitter, n, gm, gv);
+    }
+    LAUNCH_CHECK(ctx);
   }
+  return DCGP_OK;
+}
+
+int model_backward(dcgp_model* m, const Targets& targets, const double* X, int N, double scale, int dedup_layer0) {
+  dcgp_ctx* ctx = m->ctx;
+  const int nl = (int)m->layers.size(), S = m->S;
+  bool prepped = false;
+  for (int f : m->prep_early) prepped = prepped || f != 0;
+  if (prepped) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_kl2, 0));   // fills and parameter-only operands from the side stream (grad_kl_early)
+  Bk bk;
+  bk.m = m; bk.ctx = ctx;
+  bk.klw = kl_weight(m);
+  const std::string mp = "m" + std::to_string(m->id) + "_";
+  LayerState& H = *m->layers[nl - 1];
+  auto& oh = m->outs[nl - 1];
+  const int rows = oh.rows;
+  const double weight = scale * ((rows == S * N) ? 1.0 / S : 1.0);
+  const Likelihood lik = m->lik();
+  double* gm = (double*)ws_get(ctx, mp + "g_gm_head", (size_t)rows * H.R * sizeof(double));
+  double* gv = (double*)ws_get(ctx, mp + "g_gv_head", (size_t)rows * H.R * sizeof(double));
+  NEED(gm); NEED(gv);
+  double* gs2 = nullptr;   // Gaussian likelihood: d / d variance, moved into the head's block (glik) once its zero fill is behind us
+  if (lik.n_params()) { gs2 = (double*)ws_get(ctx, mp + "g_lik", sizeof(double)); NEED(gs2); }
+  DCGP_TRY(lik_grad_seeds(ctx, lik, oh.mean, oh.var, targets, rows, N, H.R, weight, gm, gv, gs2));
+  DCGP_TRY(backward_walk(bk, X, N, S, dedup_layer0, gm, gv, nullptr, "grad"));
   if (bk.side_pending) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_kl, 0));   // the one join of the step: every layer's side-stream tail
   if (gs2) HIP_TRY(ctx, hipMemcpyAsync(H.glik, gs2, sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));   // (behind every fill of the block)
   m->grad_scattered = false;
@@ -1661,98 +1693,11 @@ int model_backward(dcgp_model* m, const double* X, const int32_t* y, int N, doub
   return DCGP_OK;
 }
 
-
-// ---- the input gradient's reverse pass (input_grad.hip) --------------------------------------------------------------------------------------
-// out[i] = sum_s in[s * n + i]: layer 0 saw the batch tiled S times, the S replicas' dX add up (in the order s = 0, 1, ...)
-namespace {
-__global__ void reduce_replicas1_kernel(const double* __restrict__ a, int S, long n, double* __restrict__ out) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  double s = 0.0;
-  for (int r = 0; r < S; ++r) s += a[(long)r * n + i];
-  out[i] = s;
-}
-}  // namespace
-
-// RobustMax seeds of the "elbo" objective: gm, gv [rows][K] = weight * d E_q[log p(y | f)] / d(mean, var) of the head's rows
-int grad_seed_robustmax(dcgp_model* m, const int32_t* y, int N, double weight, double* gm, double* gv) {
-  dcgp_ctx* ctx = m->ctx;
-  const LayerState& H = *m->layers.back();
-  const auto& oh = m->outs.back();
-  if (H.R > RM_KMAX) return ctx_fail(ctx, DCGP_ERR_ARG, "grad: at most %d classes", RM_KMAX);
-  const double* gh = gauss_hermite_table(ctx);
-  if (!gh) return DCGP_ERR_ALLOC;
-  hipLaunchKernelGGL(robustmax_grad_kernel, dim3((oh.rows + RM_ROWS - 1) / RM_ROWS), dim3(256), 0, ctx->stream, oh.mean, oh.var, y, oh.rows, N, H.R,
-                     m->eps, gh, weight, gm, gv);
-  LAUNCH_CHECK(ctx);
-  return DCGP_OK;
-}
-
-// model_backward's data path alone: from the head's (gm, gv) [rows][R] down to and INCLUDING layer 0, whose dX -- summed over the S replicas of a
-// tiled batch -- goes to out_dX [N][H W C].  Reads what a forward pass with keep_outputs / keep_state left; writes workspaces only (Bk::data_only).
+// the input gradient's reverse pass (input_grad.hip): the walk's data path alone, no gradient block is touched
 int model_backward_data(dcgp_model* m, const double* X, int N, int S, int dedup_layer0, double* gm, double* gv, double* out_dX) {
-  dcgp_ctx* ctx = m->ctx;
-  const int nl = (int)m->layers.size();
-  if (!m->keep_outputs) return ctx_fail(ctx, DCGP_ERR_ARG, "input_grad: the forward pass must keep the layer outputs");
-  for (auto& l : m->layers) {
-    if (l->base_type != 0 && l->is_head) return ctx_fail(ctx, DCGP_ERR_ARG, "input_grad: the head kernels are RBF-based");
-  }
   Bk bk;
-  bk.m = m; bk.ctx = ctx; bk.data_only = true;
-  const std::string mp = "m" + std::to_string(m->id) + "_";
-  bool dedup_done = false;
-  for (int li = nl - 1; li >= 0; --li) {
-    LayerState& L = *m->layers[li];
-    bk.pfx = mp + std::to_string(li) + "_";
-    bk.last_layer = li == 0;
-    const double* Xin = li == 0 ? X : m->outs[li - 1].sample;
-    int rows_l = m->outs[li].rows;
-    if (li == 0 && dedup_layer0 && !L.is_head && rows_l == S * N && S > 1) {   // (see model_backward)
-      if (!dedup_done) {
-        const long n = (long)N * L.v.P * L.R;
-        double* gm0 = (double*)ws_get(ctx, bk.pfx + "g_gm_dedup", (size_t)n * sizeof(double));
-        double* gv0 = (double*)ws_get(ctx, bk.pfx + "g_gv_dedup", (size_t)n * sizeof(double));
-        NEED(gm0); NEED(gv0);
-        hipLaunchKernelGGL(reduce_replicas_kernel, dim3(blocks_for(n)), dim3(256), 0, ctx->stream, gm, gv, S, n, gm0, gv0);
-        LAUNCH_CHECK(ctx);
-        gm = gm0; gv = gv0;
-      }
-      rows_l = N;
-    }
-    const int n_mod = li == 0 ? N : rows_l;
-    const long img = (long)L.v.H * L.v.W * L.v.C;
-    double* dXin = out_dX;
-    if (li > 0 || rows_l != N) {
-      dXin = (double*)ws_get(ctx, bk.pfx + "g_dXin", (size_t)rows_l * img * sizeof(double));
-      NEED(dXin);
-    }
-    if (L.is_head) DCGP_TRY(head_backward(bk, L, Xin, rows_l, n_mod, gm, gv, dXin));
-    else DCGP_TRY(conv_backward(bk, L, Xin, rows_l, n_mod, gm, gv, dXin));
-    if (li == 0) {
-      if (rows_l != N) {
-        if (rows_l % N) return ctx_fail(ctx, DCGP_ERR_ARG, "input_grad: %d rows at layer 0 for %d images", rows_l, N);
-        hipLaunchKernelGGL(reduce_replicas1_kernel, dim3(blocks_for(N * img)), dim3(256), 0, ctx->stream, dXin, rows_l / N, N * img, out_dX);
-        LAUNCH_CHECK(ctx);
-      }
-      break;
-    }
-    auto& o = m->outs[li - 1];
-    const long n = (long)o.rows * o.width;
-    gm = (double*)ws_get(ctx, mp + std::to_string(li - 1) + "_g_gm", (size_t)n * sizeof(double));
-    gv = (double*)ws_get(ctx, mp + std::to_string(li - 1) + "_g_gv", (size_t)n * sizeof(double));
-    NEED(gm); NEED(gv);
-    LayerState& Lb = *m->layers[li - 1];
-    if (li - 1 == 0 && dedup_layer0 && !Lb.is_head && o.rows == S * N && S > 1) {
-      const long n0 = (long)N * o.width;
-      hipLaunchKernelGGL(sample_backward_dedup_kernel, dim3(blocks_for(n0)), dim3(256), 0, ctx->stream, dXin, o.sample, o.mean, o.var, m->jitter, S, n0,
-                         gm, gv);
-      dedup_done = true;
-    } else {
-      hipLaunchKernelGGL(sample_backward_kernel, dim3(blocks_for(n)), dim3(256), 0, ctx->stream, dXin, o.sample, o.mean, o.var, m->jitter, n, gm, gv);
-    }
-    LAUNCH_CHECK(ctx);
-  }
-  return DCGP_OK;
+  bk.m = m; bk.ctx = m->ctx; bk.data_only = true;
+  return backward_walk(bk, X, N, S, dedup_layer0, gm, gv, out_dX, "input_grad");
 }
 
 // Adam step enqueued behind the reverse pass (dcgp_model_train_step_adam): lr is the bias-corrected rate
@@ -1778,7 +1723,7 @@ static int elbo_grad_run(dcgp_model* model, const double* X, const int32_t* y, i
                                              : elbo_forward_enqueue_impl(model, X, y, N, scale, z_per_layer_host, seed, dedup_layer0, &ticket, false, yf);
   const bool enqueued = rc == DCGP_OK;
   if (rc == DCGP_OK && model->gkl_state) rc = grad_kl_early(model, true, model->gkl_state == 2);
-  if (rc == DCGP_OK) rc = model_backward(model, X, y, N, scale, dedup_layer0, yf);
+  if (rc == DCGP_OK) rc = model_backward(model, Targets::of(y, yf, model->layers.back()->R), X, N, scale, dedup_layer0);
   // (the update reads the step's factorisation status word on the device: a failed step leaves the parameters as they were)
   if (rc == DCGP_OK && adam)
     rc = opt_enqueue(model, "train_step_adam", false, adam->lr_t, adam->beta1, adam->beta2, adam->eps, model->d_scal + 64 * model->bank + 43, 0);

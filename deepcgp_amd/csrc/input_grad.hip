@@ -127,12 +127,9 @@ __global__ void sample_mean_rows_kernel(const double* __restrict__ ve, int S, in
 }
 
 // res[0] = first non-positive pivot of the factorisations the forward used (0: none), res[1] = labels outside [0, K)
-__global__ void ig_status_kernel(EvalStatus st, const int* __restrict__ bad, double* __restrict__ res) {
+__global__ void ig_status_kernel(FactorStatus st, const int* __restrict__ bad, double* __restrict__ res) {
   if (blockIdx.x || threadIdx.x) return;
-  int pivot = 0;
-  for (int q = 0; q < st.ngroups; ++q)
-    for (int j = 0; j < st.ninfo[q]; ++j)
-      if (st.info[q][j] && !pivot) pivot = st.info[q][j];
+  const int pivot = first_bad_pivot(st);
   res[0] = (double)pivot;
   res[1] = bad ? (double)bad[0] : 0.0;
 }
@@ -302,15 +299,14 @@ int input_grad_run(dcgp_model* model, const double* X, const int32_t* y, const d
   if (!X || !(y || yf) || N <= 0 || S <= 0 || !out_dX) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: bad args (N %d, S %d)", who, N, S);
   if ((objective & ~(0xff | DCGP_INPUT_GRAD_DEDUP)) || (obj != DCGP_OBJECTIVE_DENSITY && obj != DCGP_OBJECTIVE_ELBO))
     return ctx_fail(ctx, DCGP_ERR_ARG, "%s: objective %d (0 density, 1 elbo)", who, objective);
-  if (model->float_targets() != (yf != nullptr))
-    return ctx_fail(ctx, DCGP_ERR_ARG, model->float_targets() ? "%s: a Gaussian- or Bernoulli-likelihood model takes float64 targets (the _f64y entry point)"
-                                                              : "%s: a RobustMax model takes int32 labels, not float64 targets", who);
-  if (yf && obj == DCGP_OBJECTIVE_DENSITY)
-    return ctx_fail(ctx, DCGP_ERR_ARG, "%s: the density objective exists for the RobustMax likelihood only; a Gaussian or Bernoulli model takes the elbo objective", who);
   if (!model->has_head) return ctx_fail(ctx, DCGP_ERR_ARG, "model has no head layer");
-  if (model->enq_seq != model->col_seq) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: enqueued steps are still to be collected", who);
   const int nl = (int)model->layers.size();
   const int K = model->layers[nl - 1]->R;
+  const Likelihood lik = model->lik();
+  DCGP_TRY(lik_check_targets(ctx, lik, Targets::of(y, yf, K), who));
+  if (yf && obj == DCGP_OBJECTIVE_DENSITY)
+    return ctx_fail(ctx, DCGP_ERR_ARG, "%s: the density objective exists for the RobustMax likelihood only; a Gaussian or Bernoulli model takes the elbo objective", who);
+  if (model->enq_seq != model->col_seq) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: enqueued steps are still to be collected", who);
   if (!yf && (K < 2 || K > DR_KMAX)) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: RobustMax over %d outputs (2 to %d)", who, K, DR_KMAX);
   const std::string mp = "m" + std::to_string(model->id) + "_";
   double* res = (double*)ws_get(ctx, mp + "ig_res", 2 * sizeof(double));
@@ -351,29 +347,17 @@ int input_grad_run(dcgp_model* model, const double* X, const int32_t* y, const d
       double* ve = (double*)ws_get(ctx, mp + "ig_ve", (size_t)rows * sizeof(double));
       double* scal = (double*)ws_get(ctx, mp + "ig_scal", 64 * sizeof(double));
       if (!ve || !scal) return DCGP_ERR_ALLOC;
-      ElboFinish none;
       const double w = 1.0 / Sh;
-      if (model->lik_kind == 1) {
-        double* gs2 = (double*)ws_get(ctx, mp + "ig_gs2", sizeof(double));
-        if (!gs2 || !model->d_lik) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: the Gaussian likelihood has no variance on the device", who);
-        DCGP_TRY(gauss_elbo_tail(ctx, o.mean, o.var, yf, rows, N, K, model->d_lik, ve, w, scal, none));
-        DCGP_TRY(gauss_grad(ctx, o.mean, o.var, yf, rows, K, N, model->d_lik, w, gm, gv, gs2));
-      } else if (model->lik_kind == 2) {
-        DCGP_TRY(bern_elbo_tail(ctx, o.mean, o.var, yf, rows, N, K, ve, w, scal, none));
-        DCGP_TRY(bern_grad(ctx, o.mean, o.var, yf, rows, K, N, w, gm, gv));
-      } else {
-        DCGP_TRY(elbo_tail(ctx, o.mean, o.var, ys, rows, N, K, model->eps, ve, w, scal, none));
-        DCGP_TRY(grad_seed_robustmax(model, ys, N, w, gm, gv));
-      }
+      const Targets t = Targets::of(ys, yf, K);   // (labels: the clamped copy)
+      double* gs2 = lik.n_params() ? (double*)ws_get(ctx, mp + "ig_gs2", sizeof(double)) : nullptr;   // (the variance's gradient: not reported)
+      DCGP_TRY(lik_elbo_tail(ctx, lik, o.mean, o.var, t, rows, N, K, ve, w, scal, ElboFinish()));
+      DCGP_TRY(lik_grad_seeds(ctx, lik, o.mean, o.var, t, rows, N, K, w, gm, gv, gs2));
       hipLaunchKernelGGL(sample_mean_rows_kernel, dim3(blocks_for(N)), dim3(256), 0, ctx->stream, ve, Sh, N, J);
       LAUNCH_CHECK(ctx);
     }
     DCGP_TRY(model_backward_data(model, X, N, S, dedup, gm, gv, out_dX));
-    EvalStatus st;
-    auto& groups = model->groups[model->bank];
-    if (groups.size() > 16) return ctx_fail(ctx, DCGP_ERR_ARG, "model: too many factor groups");
-    st.ngroups = (int)groups.size();
-    for (int q = 0; q < st.ngroups; ++q) { st.info[q] = groups[q].d_info; st.ninfo[q] = (int)groups[q].K.size(); }
+    FactorStatus st;
+    DCGP_TRY(fill_status(model, &st));
     hipLaunchKernelGGL(ig_status_kernel, dim3(1), dim3(64), 0, ctx->stream, st, y ? bad : nullptr, res);
     LAUNCH_CHECK(ctx);
     return DCGP_OK;

@@ -152,14 +152,18 @@ int conv_fused(dcgp_ctx* ctx, const ConvFusedArgs& a);
 int kl_layer(dcgp_ctx* ctx, const GpMats& g, const double* Lp, const double* LpinvT, int white, const char* ws_prefix,
              double* kl4);
 
+// the status words of a model's factorisations: one device scan finds the first non-positive pivot (first_bad_pivot, tail_dev.h)
+struct FactorStatus {
+  const int* info[16];   // per factor group: potrf status words (0 or the 1-based failing column)
+  int ninfo[16];
+  int ngroups = 0;
+};
 // the ELBO assembly the tail kernel performs after the data term (nl == 0: data term only -> scal[0])
 struct ElboFinish {
   int nl = 0;
   int M[8], R[8], white[8];
   double scale = 1.0;
-  const int* info[16];   // per factor group: potrf status words (0 or the 1-based failing column)
-  int ninfo[16];
-  int ngroups = 0;
+  FactorStatus st;
   double* host_out = nullptr;   // pinned host slot (device-visible address): the four result words are also written there,
                                 // so no copy command follows the launch
   double host_seq = 0.0;        // written to host_out[4] behind them (system-scope release): the word the host polls for (ticket + 1)
@@ -189,10 +193,9 @@ const double* gauss_hermite_table(dcgp_ctx* ctx);   // [40]: 20 nodes then 20 we
 // ok = 1 / 0 (arg-max == label) or -1 (label outside [0, K)).  eval_sum: one launch behind the last batch, res[4] = {correct count,
 // sum of the log densities, first non-positive pivot of the status words in st, labels outside [0, K)}.
 constexpr int kEvalMaxSlots = 8192;   // S * K + K doubles of LDS per workgroup (64 KB)
-struct EvalStatus { const int* info[16]; int ninfo[16]; int ngroups = 0; };
 int eval_tail(dcgp_ctx* ctx, const double* mu, const double* var, const int32_t* y, int n, int S, int K, double eps, long lo,
               double* logdens, double* p_mean, int* ok);
-int eval_sum(dcgp_ctx* ctx, const double* logdens, const int* ok, long n, const EvalStatus& st, double* res);
+int eval_sum(dcgp_ctx* ctx, const double* logdens, const int* ok, long n, const FactorStatus& st, double* res);
 
 // gaussian.hip: the Gaussian likelihood's tails (targets y [n_labels][K] float64, row r reads y[r % n_labels]; s2 the variance's device word).
 // gauss_elbo_tail: elbo_tail's counterpart (same scal / fin / KlTail contract).  gauss_grad: gm, gv [rows][K] and gs2[0] = d / d s2, all
@@ -207,7 +210,7 @@ int gauss_grad(dcgp_ctx* ctx, const double* mu, const double* var, const double*
 int gauss_predict(dcgp_ctx* ctx, const double* mu, const double* var, long n, const double* s2, double* out_mean, double* out_var);
 int gauss_eval_tail(dcgp_ctx* ctx, const double* mu, const double* var, const double* y, int n, int S, int K, const double* s2, long lo,
                     double* logdens, double* ld_nd, double* y_mean, double* sqerr);
-int gauss_eval_sum(dcgp_ctx* ctx, const double* logdens, const double* sqerr, long n, const EvalStatus& st, double* res);
+int gauss_eval_sum(dcgp_ctx* ctx, const double* logdens, const double* sqerr, long n, const FactorStatus& st, double* res);
 
 // bernoulli.hip: the Bernoulli (probit) likelihood's tails (targets y [n_labels][K] float64, y == 1 positive; row r reads y[r % n_labels]).
 // bern_elbo_tail: elbo_tail's counterpart (same scal / fin / KlTail contract).  bern_grad: gm, gv [rows][K] times weight.  bern_predict:
@@ -243,7 +246,42 @@ struct UncSumArgs {
 };
 int unc_tail(dcgp_ctx* ctx, const double* mu, const double* var, const int32_t* y, int n, int S, int K, double eps, long lo, const UncOut& o);
 int bern_unc_tail(dcgp_ctx* ctx, const double* mu, const double* var, const double* y, int n, int S, int K, long lo, const UncOut& o);
-int unc_sum(dcgp_ctx* ctx, const UncSumArgs& a, const EvalStatus& st, double* res);
+int unc_sum(dcgp_ctx* ctx, const UncSumArgs& a, const FactorStatus& st, double* res);
+
+// likelihood.hip: which likelihood a model has is decided there and nowhere else.  Likelihood: the kind with its two parameters; Targets: int32
+// labels [N] or float64 targets [N][K] of a whole set (either pointer may be nullptr where labels are optional: f64 still says which entry
+// point they came through).  Each lik_* function dispatches once on the kind to the launchers above and to robustmax_grad (grad.hip: the RobustMax
+// seeds gm, gv [rows][K] = weight * d E_q[log p(y | f)] / d(mean, var)); lik_eval_tail / lik_unc_tail take the whole set's targets and batch `lo`.
+struct Likelihood {
+  int kind = 0;                  // 0 RobustMax (labels), 1 Gaussian, 2 Bernoulli (probit) (targets)
+  double eps = 1e-3;             // RobustMax epsilon
+  const double* s2 = nullptr;    // the Gaussian variance's device word
+  bool float_targets() const { return kind != 0; }    // the _f64y entry points
+  int n_params() const { return kind == 1 ? 1 : 0; }   // trainable words (the Gaussian variance): lik_grad_seeds wants a gs2 for each
+};
+struct Targets {
+  const int32_t* labels = nullptr; const double* values = nullptr; int K = 1; bool f64 = false;
+  static Targets of(const int32_t* y, const double* yf, int K) { return Targets{y, yf, K, yf != nullptr}; }
+  Targets from(long lo) const { return Targets{labels ? labels + lo : nullptr, values ? values + lo * K : nullptr, K, f64}; }   // the targets from image lo on
+};
+struct EvalOut {   // per image of the whole set (p_mean, ld_nd per (image, output); either may be nullptr)
+  double* logdens = nullptr; double* ld_nd = nullptr; double* p_mean = nullptr;
+  int* ok = nullptr;          // RobustMax: eval_tail's ok
+  double* score = nullptr;    // Gaussian: squared error, Bernoulli: correct outputs
+};
+int robustmax_grad(dcgp_ctx* ctx, const double* mu, const double* var, const int32_t* y, int rows, int n_labels, int K, double eps, double weight,
+                   double* gm, double* gv);
+int lik_check_targets(dcgp_ctx* ctx, const Likelihood& lik, const Targets& t, const char* who);   // targets of the wrong type for this likelihood
+int lik_elbo_tail(dcgp_ctx* ctx, const Likelihood& lik, const double* mu, const double* var, const Targets& t, int n_rows, int n_labels, int K,
+                  double* ve_rows, double inv_s, double* scal, const ElboFinish& fin, const KlTail* kl = nullptr);
+int lik_grad_seeds(dcgp_ctx* ctx, const Likelihood& lik, const double* mu, const double* var, const Targets& t, int rows, int n_labels, int K,
+                   double weight, double* gm, double* gv, double* gs2);   // gs2[0] = d / d s2 (n_params() > 0, else unused)
+int lik_predict(dcgp_ctx* ctx, const Likelihood& lik, const double* mu, const double* var, long n, double* out_mean, double* out_var);
+int lik_eval_tail(dcgp_ctx* ctx, const Likelihood& lik, const double* mu, const double* var, const Targets& all, int n, int S, int K, long lo,
+                  const EvalOut& o);
+int lik_eval_sum(dcgp_ctx* ctx, const Likelihood& lik, const EvalOut& o, long n, const FactorStatus& st, double* res);
+int lik_unc_tail(dcgp_ctx* ctx, const Likelihood& lik, const double* mu, const double* var, const Targets& all, int n, int S, int K, long lo,
+                 const UncOut& o);
 
 // patch_map.hip: per-patch evidence maps of a patch head with an RBF base kernel, out [rows][P][R] = (w_p / P) sum_m k(z_m, x_n[p]) beta[m][r]
 // (row n shows X[n % n_mod]); asynchronous on ctx->stream.  ZS: the sweeps' operand of Z (sweep_dev.h) or nullptr (built from Z).  beta [M][R],

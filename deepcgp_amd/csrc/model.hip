@@ -9,14 +9,13 @@
 //   3. main, per conv layer: patch sweep -> stage-1 GEMM -> stage-3 GEMM -> mean -> finalize (+ sample)
 //   4. main: head Kzx sweep (Kdiag beside it on the side stream), fused head conditional, RobustMax expectations
 //   5. (multi-GPU) all-reduce of the data term, ELBO assembly, one 32-byte read-back, one host sync.
+#include <chrono>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
 
 #include "model_state.h"
 #include "tail_dev.h"
-#include <chrono>
-
 
 namespace {
 
@@ -74,7 +73,7 @@ int ensure(dcgp_ctx* ctx, double** p, size_t* cap, size_t n) {
   return DCGP_OK;
 }
 
-int ensure_out(dcgp_model* m, int li, int rows, int width, bool need_mv) {
+int ensure_out(dcgp_model* m, int li, int rows, int width) {
   auto& o = m->outs[li];
   size_t n = (size_t)rows * width;
   if (o.cap < n) {
@@ -90,43 +89,13 @@ int ensure_out(dcgp_model* m, int li, int rows, int width, bool need_mv) {
     }
     o.cap = n;
   }
-  (void)need_mv;
   o.rows = rows; o.width = width;
   return DCGP_OK;
 }
 
-struct CombineArgs {
-  int nl;
-  int M[8], R[8], white[8];
-  double scale;
-  const int* info[16];   // per factor group: potrf status words (0 or the 1-based failing column)
-  int ninfo[16];
-  int ngroups;
-  double* host_out;   // pinned host slot (device-visible address) or nullptr
-  double host_seq;    // completion word behind the four result words (see elbo_forward_collect_impl)
-};
-__global__ void combine_kernel(const double* __restrict__ scal_in, double* __restrict__ out, CombineArgs c) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  double kl = 0.0;
-  for (int l = 0; l < c.nl; ++l) {
-    const double* k4 = scal_in + 4 + 4 * l;
-    double two = k4[0] - (double)c.M[l] * c.R[l] - k4[1] + k4[3];
-    if (!c.white[l]) two += (double)c.R[l] * k4[2];
-    kl += 0.5 * two;
-  }
-  double data = scal_in[0];
-  out[0] = data * c.scale - kl;
-  out[1] = data;
-  out[2] = kl;
-  int bad = 0;   // first non-positive pivot of any factorisation: rides back with the result (one D2H, one sync)
-  for (int g = 0; g < c.ngroups; ++g)
-    for (int i = 0; i < c.ninfo[g]; ++i)
-      if (c.info[g][i] && !bad) bad = c.info[g][i];
-  out[3] = (double)bad;
-  if (c.host_out) {
-    for (int i = 0; i < 4; ++i) __hip_atomic_store(c.host_out + i, out[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(c.host_out + 4, c.host_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
+// multi-rank step: the assembly behind the all-reduce of the data term scal[0] -- the tail kernels' own (tail_dev.h), on one thread
+__global__ void combine_kernel(double* __restrict__ scal, ElboFinish fin) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) elbo_assemble(scal, fin, scal[0]);
 }
 
 int read_info(dcgp_model* m, int* info_host) {
@@ -142,6 +111,11 @@ int read_info(dcgp_model* m, int* info_host) {
   if (info_host) *info_host = bad;
   if (bad) return ctx_fail(ctx, DCGP_ERR_NOT_PD, "Cholesky: matrix not positive definite at column %d", bad);
   return DCGP_OK;
+}
+// the end of an inference entry point: everything it enqueued behind forward_data_impl is done, then the factorisations' status
+int finish_inference(dcgp_model* m, int* info_host) {
+  HIP_TRY(m->ctx, hipStreamSynchronize(m->ctx->stream));
+  return read_info(m, info_host);
 }
 
 // Restores ctx->stream when a forward step returns, whichever way
@@ -159,14 +133,14 @@ struct StreamGuard {
 // pipelined (dcgp_elbo_forward_enqueue): main = 30 CUs of every XCD, side = the other 2, so that the chain of step i + 1 runs
 // under the data path of step i without competing for its CUs; otherwise both streams see the whole chip.
 // what the assembly at the end of a step needs: layer shapes, the status words of the factor groups, the pinned result slot
-void fill_finish(dcgp_model* model, std::vector<FactorGroup>& groups, double scale, int slot, ElboFinish* fin) {
+int fill_finish(dcgp_model* model, double scale, int slot, ElboFinish* fin) {
   const int nl = (int)model->layers.size();
   fin->nl = nl; fin->scale = scale;
   for (int l = 0; l < nl; ++l) { fin->M[l] = model->layers[l]->M; fin->R[l] = model->layers[l]->R; fin->white[l] = model->layers[l]->white; }
-  fin->ngroups = (int)groups.size();
-  for (int g = 0; g < fin->ngroups && g < 16; ++g) { fin->info[g] = groups[g].d_info; fin->ninfo[g] = (int)groups[g].K.size(); }
+  DCGP_TRY(fill_status(model, &fin->st));
   fin->host_out = model->h_ring_dev + 8 * slot;   // the last kernel of the step writes the result words into the pinned slot itself
   fin->host_seq = (double)(model->enq_seq + 1);   // ... and this step's ticket + 1 behind them
+  return DCGP_OK;
 }
 
 int forward_all(dcgp_model* m, const double* X, int N, int S, const double* const* zs, uint64_t seed, int dedup,
@@ -236,7 +210,7 @@ int forward_all(dcgp_model* m, const double* X, int N, int S, const double* cons
       const int width = L.v.P * L.R;
       const bool expand = dedup && li == 0;          // N distinct images -> S*N sampled rows
       const int out_rows = expand ? S * N : rows;
-      DCGP_TRY(ensure_out(m, li, out_rows, width, true));
+      DCGP_TRY(ensure_out(m, li, out_rows, width));
       auto& o = m->outs[li];
       // device RNG: with a shard declared (dcgp_model_set_shard) every element draws at its counter in the un-sharded batch, one
       // stream per layer -- the step's value is then independent of the number of ranks; otherwise one stream per (layer, rank)
@@ -248,7 +222,7 @@ int forward_all(dcgp_model* m, const double* X, int N, int S, const double* cons
                             fdone, pdone, phase, m->keep_state, &rm));
       *out_rows_p = out_rows;
     } else {
-      DCGP_TRY(ensure_out(m, li, rows, L.R, true));
+      DCGP_TRY(ensure_out(m, li, rows, L.R));
       auto& o = m->outs[li];
       DCGP_TRY(ensure(ctx, &m->d_kd, &m->kd_cap, (size_t)rows));
       DCGP_TRY(head_forward(ctx, L, F, rows, n_mod, m->d_kd, o.mean, o.var, pfx, fdone, pdone, 3,
@@ -691,6 +665,15 @@ int dcgp_model_set_likelihood(dcgp_model* model, int kind, double variance) {
 
 }  // extern "C"
 
+// the status words of the factorisations the model's current bank holds (with factor reuse: the chain of an earlier call)
+int fill_status(dcgp_model* model, FactorStatus* st) {
+  auto& groups = model->groups[model->bank];
+  if (groups.size() > 16) return ctx_fail(model->ctx, DCGP_ERR_ARG, "model: too many factor groups");
+  st->ngroups = (int)groups.size();
+  for (int q = 0; q < st->ngroups; ++q) { st->info[q] = groups[q].d_info; st->ninfo[q] = (int)groups[q].K.size(); }
+  return DCGP_OK;
+}
+
 int forward_data_impl(dcgp_model* model, const double* X, int N, int S, const double* const* z_per_layer_host, uint64_t seed,
                       int dedup_layer0, int* rows_last) {
   StreamGuard guard(model->ctx);
@@ -703,9 +686,10 @@ int elbo_forward_enqueue_impl(dcgp_model* model, const double* X, const int32_t*
                               bool pipelined, const double* yf) {
   if (!model || !X || !(y || yf) || N <= 0 || !ticket) return model ? ctx_fail(model->ctx, DCGP_ERR_ARG, "elbo_forward: bad args") : DCGP_ERR_ARG;
   dcgp_ctx* ctx = model->ctx;
-  if (model->float_targets() != (yf != nullptr))
-    return ctx_fail(ctx, DCGP_ERR_ARG, model->float_targets() ? "elbo_forward: a Gaussian- or Bernoulli-likelihood model takes float64 targets (the _f64y entry points)"
-                                                              : "elbo_forward: a RobustMax model takes int32 labels, not float64 targets");
+  if (!model->has_head) return ctx_fail(ctx, DCGP_ERR_ARG, "model has no head layer");
+  const Likelihood lik = model->lik();
+  const Targets targets = Targets::of(y, yf, model->layers.back()->R);
+  DCGP_TRY(lik_check_targets(ctx, lik, targets, "elbo_forward"));
   if (model->enq_seq - model->col_seq >= (uint64_t)dcgp_model::RING)
     return ctx_fail(ctx, DCGP_ERR_ARG, "elbo_forward_enqueue: %d steps in flight, collect the oldest first", dcgp_model::RING);
   if (!model->h_ring) {
@@ -725,13 +709,11 @@ int elbo_forward_enqueue_impl(dcgp_model* model, const double* X, const int32_t*
   DCGP_TRY(forward_all(model, X, N, S, z_per_layer_host, seed, dedup_layer0, true, pipelined, &rows));
   auto& o = model->outs[nl - 1];
   double* scal = model->d_scal + 64 * model->bank;
-  auto& groups_now = model->groups[model->bank];
   DCGP_TRY(ensure(ctx, &model->d_ve, &model->ve_cap, (size_t)rows));
   // rows == S*N normally; a head-only model under dedup has rows == N with S identical copies
   const double inv_s = (rows == S * N) ? 1.0 / S : 1.0;
-  if (groups_now.size() > 16) return ctx_fail(ctx, DCGP_ERR_ARG, "model: too many factor groups");
   ElboFinish fin;
-  fill_finish(model, groups_now, scale, slot, &fin);
+  DCGP_TRY(fill_finish(model, scale, slot, &fin));
   const KlTail* klt = (model->kl_in_tail[model->bank] && !model->kl_rode[model->bank]) ? &model->kl_tail[model->bank] : nullptr;
   // From here on a kernel that writes this slot's completion word (ticket + 1) may be in flight.  If anything below fails the ticket is
   // NOT handed out and the next enqueue reuses slot and ticket: the word is cleared, behind a device sync, so that the stale kernel's
@@ -750,15 +732,10 @@ int elbo_forward_enqueue_impl(dcgp_model* model, const double* X, const int32_t*
     // 0.1416 -> 0.1462, conv + head +2 us (profiles/r06_tail_ride_and_prep_ab.txt): two levels of agent-scope release/acquire at the end of 200
     // workgroups cost more than the 13 us launch they replace.)
     // expectations, their sum, the KL pieces where the chain left their ingredients, and the ELBO assembly in one launch
-    if (model->lik_kind == 1) DCGP_TRY(gauss_elbo_tail(ctx, o.mean, o.var, yf, rows, N, H.R, model->d_lik, model->d_ve, inv_s, scal, fin, klt));
-    else if (model->lik_kind == 2) DCGP_TRY(bern_elbo_tail(ctx, o.mean, o.var, yf, rows, N, H.R, model->d_ve, inv_s, scal, fin, klt));
-    else DCGP_TRY(elbo_tail(ctx, o.mean, o.var, y, rows, N, H.R, model->eps, model->d_ve, inv_s, scal, fin, klt));
+    DCGP_TRY(lik_elbo_tail(ctx, lik, o.mean, o.var, targets, rows, N, H.R, model->d_ve, inv_s, scal, fin, klt));
   } else {
     // multi-GPU: the data term is summed over the ranks between the reduction and the assembly
-    ElboFinish none;
-    if (model->lik_kind == 1) DCGP_TRY(gauss_elbo_tail(ctx, o.mean, o.var, yf, rows, N, H.R, model->d_lik, model->d_ve, inv_s, scal, none, klt));
-    else if (model->lik_kind == 2) DCGP_TRY(bern_elbo_tail(ctx, o.mean, o.var, yf, rows, N, H.R, model->d_ve, inv_s, scal, none, klt));
-    else DCGP_TRY(elbo_tail(ctx, o.mean, o.var, y, rows, N, H.R, model->eps, model->d_ve, inv_s, scal, none, klt));
+    DCGP_TRY(lik_elbo_tail(ctx, lik, o.mean, o.var, targets, rows, N, H.R, model->d_ve, inv_s, scal, ElboFinish(), klt));
     // A step kept in flight: collective and assembly go to the comm stream behind one event, and the main stream is free for the next step's
     // data path at once -- in stream, a 1-double ncclAllReduce (~20 us of latency over xGMI, more when a rank is late) sat in front of the next
     // step's layer kernel.  What it reads (scal of this bank, the chain's status words) stays untouched until the bank's next writer, which
@@ -776,13 +753,7 @@ int elbo_forward_enqueue_impl(dcgp_model* model, const double* X, const int32_t*
       if (ctx->comm_gate) DCGP_TRY(comm_gate_wait(ctx));
     }
     DCGP_TRY(allreduce_sum_f64_async(ctx, scal, 1));
-    CombineArgs c;
-    c.nl = nl; c.scale = scale;
-    for (int l = 0; l < nl; ++l) { c.M[l] = fin.M[l]; c.R[l] = fin.R[l]; c.white[l] = fin.white[l]; }
-    c.ngroups = fin.ngroups;
-    for (int g = 0; g < c.ngroups; ++g) { c.info[g] = fin.info[g]; c.ninfo[g] = fin.ninfo[g]; }
-    c.host_out = fin.host_out; c.host_seq = fin.host_seq;
-    hipLaunchKernelGGL(combine_kernel, dim3(1), dim3(64), 0, ctx->stream, scal, scal + 40, c);
+    hipLaunchKernelGGL(combine_kernel, dim3(1), dim3(64), 0, ctx->stream, scal, fin);
     LAUNCH_CHECK(ctx);
   }
   HIP_TRY(ctx, hipEventRecord(model->ring_ev[slot], ctx->stream));
@@ -867,16 +838,13 @@ int dcgp_model_propagate(dcgp_model* model, const double* X, int N, int S, const
   dcgp_ctx* ctx = model->ctx;
   if (info_host) *info_host = 0;
   int rows = 0;
-  StreamGuard guard(ctx);
-  DCGP_TRY(forward_all(model, X, N, S, z_per_layer_host, seed, 0, false, false, &rows));
-  DCGP_TRY(forward_done(model, nullptr));   // this call synchronises the stream before it returns
+  DCGP_TRY(forward_data_impl(model, X, N, S, z_per_layer_host, seed, 0, &rows));
   const int nl = (int)model->layers.size();
   auto& o = model->outs[nl - 1];
   size_t n = (size_t)rows * o.width;
   if (out_fmean) HIP_TRY(ctx, hipMemcpyAsync(out_fmean, o.mean, n * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
   if (out_fvar) HIP_TRY(ctx, hipMemcpyAsync(out_fvar, o.var, n * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return read_info(model, info_host);
+  return finish_inference(model, info_host);
 }
 
 namespace {
@@ -898,9 +866,7 @@ int dcgp_model_predict_y(dcgp_model* model, const double* X, int N, int S, const
   if (model->lik_kind != 0) return ctx_fail(ctx, DCGP_ERR_ARG, "predict_y: a Gaussian- or Bernoulli-likelihood model predicts with dcgp_model_predict_mean_var");
   if (info_host) *info_host = 0;
   int rows = 0;
-  StreamGuard guard(ctx);
-  DCGP_TRY(forward_all(model, X, N, S, z_per_layer_host, seed, 0, false, false, &rows));
-  DCGP_TRY(forward_done(model, nullptr));   // this call synchronises the stream before it returns
+  DCGP_TRY(forward_data_impl(model, X, N, S, z_per_layer_host, seed, 0, &rows));
   const int nl = (int)model->layers.size();
   auto& o = model->outs[nl - 1];
   const int K = o.width;
@@ -916,8 +882,7 @@ int dcgp_model_predict_y(dcgp_model* model, const double* X, int N, int S, const
     hipLaunchKernelGGL(sample_mean_kernel, dim3((unsigned)((NK + 255) / 256)), dim3(256), 0, ctx->stream, p, S, NK, out_p_mean);
     LAUNCH_CHECK(ctx);
   }
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return read_info(model, info_host);
+  return finish_inference(model, info_host);
 }
 
 int dcgp_model_predict_mean_var(dcgp_model* model, const double* X, int N, int S, const double* const* z_per_layer_host,
@@ -925,17 +890,13 @@ int dcgp_model_predict_mean_var(dcgp_model* model, const double* X, int N, int S
   if (!model || !X || N <= 0 || S <= 0 || (!out_mean && !out_var))
     return model ? ctx_fail(model->ctx, DCGP_ERR_ARG, "predict_mean_var: bad args") : DCGP_ERR_ARG;
   dcgp_ctx* ctx = model->ctx;
-  if (!model->float_targets()) return ctx_fail(ctx, DCGP_ERR_ARG, "predict_mean_var: not a Gaussian- or Bernoulli-likelihood model (dcgp_model_predict_y)");
+  if (!model->lik().float_targets()) return ctx_fail(ctx, DCGP_ERR_ARG, "predict_mean_var: not a Gaussian- or Bernoulli-likelihood model (dcgp_model_predict_y)");
   if (info_host) *info_host = 0;
   int rows = 0;
-  StreamGuard guard(ctx);
-  DCGP_TRY(forward_all(model, X, N, S, z_per_layer_host, seed, 0, false, false, &rows));
-  DCGP_TRY(forward_done(model, nullptr));   // this call synchronises the stream before it returns
+  DCGP_TRY(forward_data_impl(model, X, N, S, z_per_layer_host, seed, 0, &rows));
   auto& o = model->outs.back();
-  if (model->lik_kind == 2) DCGP_TRY(bern_predict(ctx, o.mean, o.var, (long)rows * o.width, out_mean, out_var));
-  else DCGP_TRY(gauss_predict(ctx, o.mean, o.var, (long)rows * o.width, model->d_lik, out_mean, out_var));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return read_info(model, info_host);
+  DCGP_TRY(lik_predict(ctx, model->lik(), o.mean, o.var, (long)rows * o.width, out_mean, out_var));
+  return finish_inference(model, info_host);
 }
 
 int dcgp_model_patch_evidence(dcgp_model* model, const double* X, int N, int S, const double* const* z_per_layer_host, uint64_t seed,
@@ -953,9 +914,7 @@ int dcgp_model_patch_evidence(dcgp_model* model, const double* X, int N, int S, 
   if (N == 0) return DCGP_OK;
   if (!X || !out_c) return ctx_fail(ctx, DCGP_ERR_ARG, "patch_evidence: NULL pointer");
   int rows = 0;
-  StreamGuard guard(ctx);
-  DCGP_TRY(forward_all(model, X, N, S, z_per_layer_host, seed, 0, false, false, &rows));
-  DCGP_TRY(forward_done(model, nullptr));   // this call synchronises the stream before it returns
+  DCGP_TRY(forward_data_impl(model, X, N, S, z_per_layer_host, seed, 0, &rows));
   // the head's input: the last hidden layer's sample, or the S copies of X (row n shows image n % N) -- what head_forward swept
   const double* F = nl > 1 ? model->outs[nl - 2].sample : X;
   const int n_mod = nl > 1 ? rows : N;
@@ -964,49 +923,30 @@ int dcgp_model_patch_evidence(dcgp_model* model, const double* X, int N, int S, 
                      "m" + std::to_string(model->id) + "_"));
   if (out_fmean)
     HIP_TRY(ctx, hipMemcpyAsync(out_fmean, model->outs[nl - 1].mean, (size_t)rows * H.R * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return read_info(model, info_host);
+  return finish_inference(model, info_host);
 }
 
 }  // extern "C"
 
 namespace {
 // A test set in batches of `batch` images, enqueued back to back on the main stream: per batch forward_all (the parameter-only chain
-// only where factor_reuse does not let it stand) and ONE eval_tail launch; behind the last batch one eval_sum launch and one 32-byte
+// only where factor_reuse does not let it stand) and ONE tail launch; behind the last batch one sum launch and one
 // read-back -- the call's only stream synchronisation.
 //   Buffer reuse between batches: the head's mean / var (model->outs), the sweeps' scratch and d_kd are written by batch b + 1 on the
 //   main stream, behind batch b's tail; the Kdiag excursion to the auxiliary stream forks from the main stream at that point
 //   (layer_impl.h: ev_aux).  The chain of a batch (factor_reuse 0, or the first batch) writes the parameter-only state of its bank
 //   on its own stream: done_ev[bank] -- recorded on the main stream behind the tail of the last batch on that bank -- orders it.
 //   Workspaces: batch 0 is the largest, every later request is served by what it grew.
-// yf (Gaussian or Bernoulli model, y == nullptr): targets [N_total][K]; out_p_mean is then the sample-mean prediction (Bernoulli: the
-// sample-mean p) [N_total][K], out_ld_nd (may be nullptr) the log density per (image, output), and out_host[0] the sum of the squared
-// errors of the sample-mean prediction (Bernoulli: the number of correct (image, output) entries; per image in sqerr, summed alike).
-int evaluate_impl(dcgp_model* model, const double* X, const int32_t* y, int N_total, int batch, int S, const double* const* zs,
-                  uint64_t seed, double* out_logdens, double* out_p_mean, double* out_host, int* info_host, const char* who,
-                  const double* yf = nullptr, double* out_ld_nd = nullptr) {
-  if (!model) return DCGP_ERR_ARG;
+// tail(lo, n, o): the tail launch of the batch of n images from image lo on, on the head's rows o; sum(st): the launch behind the last batch, which
+// leaves `nres` words in res -- [2] the first non-positive pivot of st, [3] the labels outside [0, K) -- read back into h.
+template <class Tail, class Sum>
+int eval_batches(dcgp_model* model, const double* X, int N_total, int batch, int S, const double* const* zs, uint64_t seed, const char* who,
+                 Tail tail, Sum sum, const double* res, double* h, int nres, int* info_host) {
   dcgp_ctx* ctx = model->ctx;
-  if (info_host) *info_host = 0;
-  if (!X || !(y || yf) || N_total <= 0 || batch <= 0 || S <= 0 || !out_host)
-    return ctx_fail(ctx, DCGP_ERR_ARG, "%s: bad args (N %d, batch %d, S %d)", who, N_total, batch, S);
-  if (model->float_targets() != (yf != nullptr))
-    return ctx_fail(ctx, DCGP_ERR_ARG, model->float_targets() ? "%s: a Gaussian- or Bernoulli-likelihood model takes float64 targets (the _f64y entry points)"
-                                                              : "%s: a RobustMax model takes int32 labels, not float64 targets", who);
-  if (!model->has_head) return ctx_fail(ctx, DCGP_ERR_ARG, "model has no head layer");
   const int nl = (int)model->layers.size();
   const int K = model->layers[nl - 1]->R;
-  if (!yf && K < 2) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: the last layer has %d outputs, RobustMax needs >= 2", who, K);
-  if (!yf && (long)S * K + K > kEvalMaxSlots) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: S = %d samples of %d classes exceed the tail's LDS", who, S, K);
   const LayerState& L0 = *model->layers[0];
   const long in_len = (long)L0.v.H * L0.v.W * L0.v.C;   // one image of X
-  // the per-image results of the whole set: requested once, before batch 0
-  const std::string mp = "m" + std::to_string(model->id) + "_";
-  double* ld = out_logdens ? out_logdens : (double*)ws_get(ctx, mp + "eval_logdens", (size_t)N_total * sizeof(double));
-  int* ok = yf ? nullptr : (int*)ws_get(ctx, mp + "eval_ok", (size_t)N_total * sizeof(int));
-  double* sqerr = yf ? (double*)ws_get(ctx, mp + "eval_sqerr", (size_t)N_total * sizeof(double)) : nullptr;
-  double* res = (double*)ws_get(ctx, mp + "eval_res", 4 * sizeof(double));
-  if (!ld || !(ok || sqerr) || !res) return DCGP_ERR_ALLOC;
   DCGP_TRY(ensure_events(model));
   StreamGuard guard(ctx);
   std::vector<const double*> zb(nl, nullptr);
@@ -1024,35 +964,63 @@ int evaluate_impl(dcgp_model* model, const double* X, const int32_t* y, int N_to
     DCGP_TRY(forward_all(model, X + lo * in_len, n, S, zs ? zb.data() : nullptr, seed + (uint64_t)b, 0, false, false, &rows));
     const auto& o = model->outs[nl - 1];
     if (rows != S * n || o.width != K) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: head rows %d x %d, expected %d x %d", who, rows, o.width, S * n, K);
-    if (model->lik_kind == 1) DCGP_TRY(gauss_eval_tail(ctx, o.mean, o.var, yf + lo * K, n, S, K, model->d_lik, lo, ld, out_ld_nd, out_p_mean, sqerr));
-    else if (model->lik_kind == 2) DCGP_TRY(bern_eval_tail(ctx, o.mean, o.var, yf + lo * K, n, S, K, lo, ld, out_ld_nd, out_p_mean, sqerr));
-    else DCGP_TRY(eval_tail(ctx, o.mean, o.var, y + lo, n, S, K, model->eps, lo, ld, out_p_mean, ok));
+    DCGP_TRY(tail(lo, n, o));
     HIP_TRY(ctx, hipEventRecord(model->ev_eval[model->bank], ctx->stream));
     DCGP_TRY(forward_done(model, model->ev_eval[model->bank]));
   }
-  EvalStatus st;   // the status words of the factorisations the batches used (with factor reuse: the chain of an earlier call)
-  auto& groups = model->groups[model->bank];
-  if (groups.size() > 16) return ctx_fail(ctx, DCGP_ERR_ARG, "model: too many factor groups");
-  st.ngroups = (int)groups.size();
-  for (int q = 0; q < st.ngroups; ++q) { st.info[q] = groups[q].d_info; st.ninfo[q] = (int)groups[q].K.size(); }
-  if (yf) DCGP_TRY(gauss_eval_sum(ctx, ld, sqerr, N_total, st, res));
-  else DCGP_TRY(eval_sum(ctx, ld, ok, N_total, st, res));
-  double h[4];
-  HIP_TRY(ctx, hipMemcpyAsync(h, res, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+  FactorStatus st;   // the status words of the factorisations the batches used
+  DCGP_TRY(fill_status(model, &st));
+  DCGP_TRY(sum(st));
+  HIP_TRY(ctx, hipMemcpyAsync(h, res, nres * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   if (h[3] > 0) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: %d labels outside [0, %d)", who, (int)h[3], K);
   const int bad = (int)h[2];
   if (info_host) *info_host = bad;
   if (bad) return ctx_fail(ctx, DCGP_ERR_NOT_PD, "Cholesky: matrix not positive definite at column %d", bad);
+  return DCGP_OK;
+}
+
+// The evaluation tails (lik_eval_tail) and sum over eval_batches.
+// yf (Gaussian or Bernoulli model, y == nullptr): targets [N_total][K]; out_p_mean is then the sample-mean prediction (Bernoulli: the
+// sample-mean p) [N_total][K], out_ld_nd (may be nullptr) the log density per (image, output), and out_host[0] the sum of the squared
+// errors of the sample-mean prediction (Bernoulli: the number of correct (image, output) entries; per image in sqerr, summed alike).
+int evaluate_impl(dcgp_model* model, const double* X, const int32_t* y, int N_total, int batch, int S, const double* const* zs,
+                  uint64_t seed, double* out_logdens, double* out_p_mean, double* out_host, int* info_host, const char* who,
+                  const double* yf = nullptr, double* out_ld_nd = nullptr) {
+  if (!model) return DCGP_ERR_ARG;
+  dcgp_ctx* ctx = model->ctx;
+  if (info_host) *info_host = 0;
+  if (!X || !(y || yf) || N_total <= 0 || batch <= 0 || S <= 0 || !out_host)
+    return ctx_fail(ctx, DCGP_ERR_ARG, "%s: bad args (N %d, batch %d, S %d)", who, N_total, batch, S);
+  if (!model->has_head) return ctx_fail(ctx, DCGP_ERR_ARG, "model has no head layer");
+  const int K = model->layers.back()->R;
+  const Likelihood lik = model->lik();
+  const Targets targets = Targets::of(y, yf, K);
+  DCGP_TRY(lik_check_targets(ctx, lik, targets, who));
+  if (!yf && K < 2) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: the last layer has %d outputs, RobustMax needs >= 2", who, K);
+  if (!yf && (long)S * K + K > kEvalMaxSlots) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: S = %d samples of %d classes exceed the tail's LDS", who, S, K);
+  // the per-image results of the whole set: requested once, before batch 0
+  const std::string mp = "m" + std::to_string(model->id) + "_";
+  EvalOut eo;
+  eo.logdens = out_logdens ? out_logdens : (double*)ws_get(ctx, mp + "eval_logdens", (size_t)N_total * sizeof(double));
+  eo.ld_nd = out_ld_nd; eo.p_mean = out_p_mean;
+  eo.ok = yf ? nullptr : (int*)ws_get(ctx, mp + "eval_ok", (size_t)N_total * sizeof(int));
+  eo.score = yf ? (double*)ws_get(ctx, mp + "eval_sqerr", (size_t)N_total * sizeof(double)) : nullptr;
+  double* res = (double*)ws_get(ctx, mp + "eval_res", 4 * sizeof(double));
+  if (!eo.logdens || !(eo.ok || eo.score) || !res) return DCGP_ERR_ALLOC;
+  double h[4];
+  DCGP_TRY(eval_batches(
+      model, X, N_total, batch, S, zs, seed, who,
+      [&](long lo, int n, const dcgp_model::Out& o) { return lik_eval_tail(ctx, lik, o.mean, o.var, targets, n, S, K, lo, eo); },
+      [&](const FactorStatus& st) { return lik_eval_sum(ctx, lik, eo, N_total, st, res); }, res, h, 4, info_host));
   out_host[0] = h[0];
   out_host[1] = h[1];
   return DCGP_OK;
 }
 
-// evaluate_impl's batches -- the same seeds, noise layout, factor reuse, buffer reuse and single synchronisation -- with the uncertainty
-// tails (uncertainty.hip) in place of eval_tail / bern_eval_tail and unc_sum in place of the sum kernel.  f64y: the Bernoulli entry (targets
-// yf [N_total][K], entries = (image, output) pairs); otherwise RobustMax (labels y [N_total], entries = images).  Labels may be nullptr.
-// u holds the caller's outputs (any may be nullptr: the per-entry values the dataset kernel reads then live in workspaces).
+// eval_batches with the uncertainty tails (uncertainty.hip) in place of the evaluation tails and unc_sum in place of the sum kernel.  f64y: the
+// Bernoulli entry (targets yf [N_total][K], entries = (image, output) pairs); otherwise RobustMax (labels y [N_total], entries = images).  Labels may
+// be nullptr.  u holds the caller's outputs (any may be nullptr: the per-entry values the dataset kernel reads then live in workspaces).
 int uncertainty_impl(dcgp_model* model, const double* X, const int32_t* y, const double* yf, bool f64y, int N_total, int batch, int S,
                      const double* const* zs, uint64_t seed, int bins, UncOut u, double* out_table, double* out_host, int* info_host,
                      const char* who) {
@@ -1062,18 +1030,15 @@ int uncertainty_impl(dcgp_model* model, const double* X, const int32_t* y, const
   if (!X || N_total <= 0 || batch <= 0 || S <= 0 || bins < 1 || !out_host)
     return ctx_fail(ctx, DCGP_ERR_ARG, "%s: bad args (N %d, batch %d, S %d, bins %d)", who, N_total, batch, S, bins);
   if (model->lik_kind == 1) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: class probabilities need a classification likelihood, this model is Gaussian", who);
-  if (model->float_targets() != f64y)
-    return ctx_fail(ctx, DCGP_ERR_ARG, f64y ? "%s: a RobustMax model takes int32 labels, not float64 targets"
-                                            : "%s: a Bernoulli-likelihood model takes float64 targets (the _f64y entry point)", who);
   if (!model->has_head) return ctx_fail(ctx, DCGP_ERR_ARG, "model has no head layer");
-  const int nl = (int)model->layers.size();
-  const int K = model->layers[nl - 1]->R;
+  const int K = model->layers.back()->R;
+  const Likelihood lik = model->lik();
+  const Targets targets{y, yf, K, f64y};
+  DCGP_TRY(lik_check_targets(ctx, lik, targets, who));
   if (!f64y && K < 2) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: the last layer has %d outputs, RobustMax needs >= 2", who, K);
   if (!f64y && (long)S * K + K + kUncExtraSlots > kEvalMaxSlots)
     return ctx_fail(ctx, DCGP_ERR_ARG, "%s: S = %d samples of %d classes exceed the tail's LDS (S * K + K + %d <= %d)", who, S, K, kUncExtraSlots, kEvalMaxSlots);
   const bool labels = f64y ? yf != nullptr : y != nullptr;
-  const LayerState& L0 = *model->layers[0];
-  const long in_len = (long)L0.v.H * L0.v.W * L0.v.C;   // one image of X
   const long n_ent = f64y ? (long)N_total * K : N_total;
   const std::string mp = "m" + std::to_string(model->id) + "_";
   auto dbl = [&](double* given, const char* name, long n) { return given ? given : (double*)ws_get(ctx, mp + name, (size_t)n * sizeof(double)); };
@@ -1092,43 +1057,14 @@ int uncertainty_impl(dcgp_model* model, const double* X, const int32_t* y, const
   double* table = dbl(out_table, "unc_table", 3L * bins);
   double* res = (double*)ws_get(ctx, mp + "unc_res", 9 * sizeof(double));
   if (!u.pred_ent || !u.mi || !u.conf || !u.pred || !table || !res) return DCGP_ERR_ALLOC;
-  DCGP_TRY(ensure_events(model));
-  StreamGuard guard(ctx);
-  std::vector<const double*> zb(nl, nullptr);
-  const int nb = (N_total + batch - 1) / batch;
-  for (int b = 0; b < nb; ++b) {
-    const long lo = (long)b * batch;
-    const int n = (int)(N_total - lo < batch ? N_total - lo : batch);
-    for (int l = 0; l < nl && zs; ++l) {   // noise: evaluate_impl's layout
-      const LayerState& L = *model->layers[l];
-      const long D = L.is_head ? L.R : (long)L.v.P * L.R;
-      zb[l] = zs[l] ? zs[l] + (long)S * lo * D : nullptr;
-    }
-    int rows = 0;
-    DCGP_TRY(forward_all(model, X + lo * in_len, n, S, zs ? zb.data() : nullptr, seed + (uint64_t)b, 0, false, false, &rows));
-    const auto& o = model->outs[nl - 1];
-    if (rows != S * n || o.width != K) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: head rows %d x %d, expected %d x %d", who, rows, o.width, S * n, K);
-    if (f64y) DCGP_TRY(bern_unc_tail(ctx, o.mean, o.var, yf ? yf + lo * K : nullptr, n, S, K, lo, u));
-    else DCGP_TRY(unc_tail(ctx, o.mean, o.var, y ? y + lo : nullptr, n, S, K, model->eps, lo, u));
-    HIP_TRY(ctx, hipEventRecord(model->ev_eval[model->bank], ctx->stream));
-    DCGP_TRY(forward_done(model, model->ev_eval[model->bank]));
-  }
-  EvalStatus st;
-  auto& groups = model->groups[model->bank];
-  if (groups.size() > 16) return ctx_fail(ctx, DCGP_ERR_ARG, "model: too many factor groups");
-  st.ngroups = (int)groups.size();
-  for (int q = 0; q < st.ngroups; ++q) { st.info[q] = groups[q].d_info; st.ninfo[q] = (int)groups[q].K.size(); }
   UncSumArgs sa;
   sa.logdens = u.logdens; sa.n_img = N_total; sa.ok = labels ? u.ok : nullptr; sa.brier = u.brier; sa.pred_ent = u.pred_ent; sa.mi = u.mi;
   sa.conf = u.conf; sa.n_ent = n_ent; sa.bins = bins; sa.table = table;
-  DCGP_TRY(unc_sum(ctx, sa, st, res));
   double h[9];
-  HIP_TRY(ctx, hipMemcpyAsync(h, res, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  if (h[3] > 0) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: %d labels outside [0, %d)", who, (int)h[3], K);
-  const int bad = (int)h[2];
-  if (info_host) *info_host = bad;
-  if (bad) return ctx_fail(ctx, DCGP_ERR_NOT_PD, "Cholesky: matrix not positive definite at column %d", bad);
+  DCGP_TRY(eval_batches(
+      model, X, N_total, batch, S, zs, seed, who,
+      [&](long lo, int n, const dcgp_model::Out& o) { return lik_unc_tail(ctx, lik, o.mean, o.var, targets, n, S, K, lo, u); },
+      [&](const FactorStatus& st) { return unc_sum(ctx, sa, st, res); }, res, h, 9, info_host));
   out_host[0] = h[0];
   out_host[1] = h[1];
   for (int q = 2; q < 7; ++q) out_host[q] = h[q + 2];

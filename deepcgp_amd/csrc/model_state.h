@@ -11,7 +11,7 @@ struct dcgp_model {
   // Gaussian variance lives on the device (d_lik[0]; the tails and the optimiser read and write it there), its Adam moments in d_lik[1],
   // d_lik[2] and its gradient in the last slot of the head's gradient block (LayerState::glik).  Bernoulli has no parameter: no d_lik, no slot.
   int lik_kind = 0;
-  bool float_targets() const { return lik_kind != 0; }   // the _f64y entry points
+  Likelihood lik() const { return Likelihood{lik_kind, eps, d_lik}; }   // what likelihood.hip's functions take
   double* d_lik = nullptr;
   bool lik_frozen = false;   // dcgp_model_set_trainable(.., "likelihood_variance", 0)
   std::vector<std::unique_ptr<LayerState>> layers;   // conv layers..., head last (once set)
@@ -95,8 +95,9 @@ int elbo_forward_enqueue_impl(dcgp_model* model, const double* X, const int32_t*
                               const double* const* z_per_layer_host, uint64_t seed, int dedup_layer0, uint64_t* ticket,
                               bool pipelined = false, const double* yf = nullptr);   // yf: Gaussian targets [N][K] (y is then nullptr)
 int elbo_forward_collect_impl(dcgp_model* model, uint64_t ticket, double* out_host, int* info_host);
-// grad.hip: reverse pass over the state the forward left behind; fills every layer's gradient buffers
-int model_backward(dcgp_model* model, const double* X, const int32_t* y, int N, double scale, int dedup_layer0, const double* yf = nullptr);
+// grad.hip: reverse pass over the state the forward left behind; fills every layer's gradient buffers (the likelihood's seeds, the reverse walk over
+// the layers, the join of its side streams, the likelihood's own gradient and the collectives)
+int model_backward(dcgp_model* model, const Targets& targets, const double* X, int N, double scale, int dedup_layer0);
 // enqueue == false: 1 if a training step's forward should hand the KL adjoint's products to the side stream, else 0;
 // enqueue == true: do it (wait_fork: behind ctx->ev_fork, recorded where the parameter-only chain ended)
 int grad_kl_early(dcgp_model* model, bool enqueue, bool wait_fork);
@@ -105,10 +106,11 @@ int grad_kl_early(dcgp_model* model, bool enqueue, bool wait_fork);
 // with keep_outputs / keep_state / data_grad set it leaves what model_backward_data reads.  *rows_last: rows of the head's mean / var.
 int forward_data_impl(dcgp_model* model, const double* X, int N, int S, const double* const* z_per_layer_host, uint64_t seed,
                       int dedup_layer0, int* rows_last);
-// grad.hip: the reverse pass's data path only (no gradient block is touched), from the head's seeds gm, gv [rows][R] to out_dX [N][H W C] (device);
-// grad_seed_robustmax: the RobustMax seeds of the variational expectation, times weight
+// model.hip: the status words of the factorisations of the model's current bank, for the kernel that closes a call (first_bad_pivot, tail_dev.h)
+int fill_status(dcgp_model* model, FactorStatus* st);
+// grad.hip: the same reverse walk's data path only (Bk::data_only: no gradient block is touched), from the head's seeds gm, gv [rows][R] to out_dX
+// [N][H W C] (device)
 int model_backward_data(dcgp_model* model, const double* X, int N, int S, int dedup_layer0, double* gm, double* gv, double* out_dX);
-int grad_seed_robustmax(dcgp_model* model, const int32_t* y, int N, double weight, double* gm, double* gv);
 // input_grad.hip: dX of a scalar-lengthscale RBF patch layer from E / cs in one launch (the product on the matrix pipe, the fold in LDS);
 // extra [rows P][L] or nullptr is added to the patch gradients before the fold.  _ok: the shape is covered (otherwise the product + col2im pair)
 bool patch_adjoint_fused_ok(const LayerState& L, long rows);

@@ -63,10 +63,17 @@ __device__ __forceinline__ void kl_pieces_block(const KlTailLayer& L, double* __
   if (tid < 4) kl4[tid] = red[tid * 256];
 }
 
+// first non-positive pivot of any factorisation behind `st` (0: none): rides back with a call's result words (no further copy, one sync)
+__device__ __forceinline__ int first_bad_pivot(const FactorStatus& st) {
+  int bad = 0;
+  for (int q = 0; q < st.ngroups; ++q)
+    for (int i = 0; i < st.ninfo[q]; ++i)
+      if (st.info[q][i] && !bad) bad = st.info[q][i];
+  return bad;
+}
+
 // one thread: scal[0] = data term; with fin.nl > 0 the four result words (device and pinned host slot)
-__device__ __forceinline__ void elbo_assemble(const TailArgs& t, double data) {
-  double* scal = t.scal;
-  const ElboFinish& fin = t.fin;
+__device__ __forceinline__ void elbo_assemble(double* scal, const ElboFinish& fin, double data) {
   scal[0] = data;
   if (fin.nl <= 0) return;
   double kl = 0.0;
@@ -76,11 +83,7 @@ __device__ __forceinline__ void elbo_assemble(const TailArgs& t, double data) {
     if (!fin.white[l]) two += (double)fin.R[l] * k4[2];
     kl += 0.5 * two;
   }
-  int bad = 0;   // first non-positive pivot of any factorisation: rides back with the result (no further copy, one sync)
-  for (int q = 0; q < fin.ngroups; ++q)
-    for (int i = 0; i < fin.ninfo[q]; ++i)
-      if (fin.info[q][i] && !bad) bad = fin.info[q][i];
-  const double res[4] = {data * fin.scale - kl, data, kl, (double)bad};
+  const double res[4] = {data * fin.scale - kl, data, kl, (double)first_bad_pivot(fin.st)};
   for (int i = 0; i < 4; ++i) scal[40 + i] = res[i];
   if (fin.host_out) {   // straight into the caller's pinned slot: a 32-byte copy command cost 4 us and a gap behind this kernel
     for (int i = 0; i < 4; ++i) __hip_atomic_store(fin.host_out + i, res[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);

@@ -174,7 +174,7 @@ __global__ __launch_bounds__(256) void bern_unc_tail_kernel(BernUncArgs a) {
 // index order, then a xor-shuffle tree.  Thread 0 then reads the table back for ECE and MCE.
 // res[9] = {correct, sum of log densities, first non-positive pivot, labels outside [0, K), ECE, MCE, Brier score, mean predictive
 // entropy, mean mutual information}; without labels (ok == nullptr) words 0, 1, 4, 5, 6 are NaN.
-__global__ __launch_bounds__(1024) void unc_sum_kernel(UncSumArgs a, EvalStatus st, double* __restrict__ res) {
+__global__ __launch_bounds__(1024) void unc_sum_kernel(UncSumArgs a, FactorStatus st, double* __restrict__ res) {
   __shared__ double red[6][1024];
   const int tid = threadIdx.x;
   double s = 0.0, c = 0.0, bad = 0.0, br = 0.0, pe = 0.0, mi = 0.0;
@@ -213,10 +213,7 @@ __global__ __launch_bounds__(1024) void unc_sum_kernel(UncSumArgs a, EvalStatus 
   }
   __syncthreads();   // (the table's words are this workgroup's own stores)
   if (tid != 0) return;
-  int pivot = 0;
-  for (int q = 0; q < st.ngroups; ++q)
-    for (int j = 0; j < st.ninfo[q]; ++j)
-      if (st.info[q][j] && !pivot) pivot = st.info[q][j];
+  const int pivot = first_bad_pivot(st);
   const double n = (double)a.n_ent, nan = __builtin_nan("");
   double ece = 0.0, mce = 0.0;
   for (int b = 0; b < a.bins; ++b) {
@@ -268,7 +265,7 @@ int bern_unc_tail(dcgp_ctx* ctx, const double* mu, const double* var, const doub
   return DCGP_OK;
 }
 
-int unc_sum(dcgp_ctx* ctx, const UncSumArgs& a, const EvalStatus& st, double* res) {
+int unc_sum(dcgp_ctx* ctx, const UncSumArgs& a, const FactorStatus& st, double* res) {
   hipLaunchKernelGGL(unc_sum_kernel, dim3(1), dim3(1024), 0, ctx->stream, a, st, res);
   LAUNCH_CHECK(ctx);
   return DCGP_OK;
