@@ -1,0 +1,152 @@
+"""Test helper: model specs at M > 256 whose EVERY gradient group is live, and the measures the large-M gradient tests share.
+
+``syn.make_config`` is right for timing and for the forward, but its deep specs are degenerate for gradients: the inducing patches of a deeper
+layer are cut from images pushed through the identity convolution, which SUMS the input channels (10 equal maps: values 10 x the image, 30 x at
+the CIFAR head), while the data that reaches that layer is mean + noise of order one.  With one lengthscale of 5 everywhere K_uf underflows and
+nothing flows back (|dZ|max 1e-30 for both conv layers of cfg3 / cfg4).  ``live_spec`` keeps ``make_spec``'s geometry, seeds and inducing
+patches and edits the dicts:
+
+* per-layer lengthscale  c * rms_i |Z_i|  (the root-mean-square norm of that layer's own inducing patches: c * sqrt(patch length) for
+  patches of unit-variance pixels, 10 x / 30 x that where the identity convolution has scaled them);
+* q_mu scaled by ``a``; conv q_sqrt = 0.3 * chol(K_uu) at the NEW lengthscale (identity when whitened), the head's chol(K_uu);
+* head patch weights 0.5 + U(0, 1).
+
+Used by tests/test_host_grad_large_m.py (liveness of the torch reference, no GPU) and tests/test_gpu_grad_large_m.py."""
+import numpy as np
+
+from deepcgp_amd import synthetic as syn
+
+LIVE_MAX = 1e-3          # every group: |want|max >= LIVE_MAX
+LIVE_MEDIAN = 1e-6       # Z, q_mu, patch_weights: median |want| >= LIVE_MEDIAN * |want|max
+ENTRY_FLOOR = 1e-6       # entry-wise measure: over the entries with |want| >= ENTRY_FLOOR * |want|max
+LEFT_OUT_CAP = 0.5       # ... which may leave out at most this share of Z, q_mu, patch_weights and tril(q_sqrt)
+MEDIAN_GROUPS = ("Z", "q_mu", "patch_weights")
+CAPPED_GROUPS = MEDIAN_GROUPS + ("q_sqrt",)
+
+# name -> geometry, M, images, and the two constants of live_spec.  S = 2 and seed 7 everywhere.
+CASES = {
+    "ch_M1024": dict(hwc=(28, 28, 1), convs=[(5, 2, 10)], head=(5, 1), M=1024, N=4, c=0.7, a=0.1),
+    "ch_M1000": dict(hwc=(28, 28, 1), convs=[(5, 2, 10)], head=(5, 1), M=1000, N=3, c=0.7, a=0.1),
+    "h_M1024": dict(hwc=(28, 28, 1), convs=[], head=(5, 1), M=1024, N=4, c=0.5, a=0.3),
+    "cifar3_M384": dict(hwc=(32, 32, 3), convs=[(4, 2, 10), (5, 1, 10)], head=(5, 1), M=384, N=2, c=1.0, a=0.1),
+    "mnist3_M320": dict(hwc=(28, 28, 1), convs=[(4, 2, 10), (5, 1, 10)], head=(5, 1), M=320, N=3, c=1.0, a=0.1),
+    "ch_white_M384": dict(hwc=(28, 28, 1), convs=[(5, 2, 10)], head=(5, 1), M=384, N=4, c=1.0, a=0.1, white=True),
+    "ch_M384": dict(hwc=(28, 28, 1), convs=[(5, 2, 10)], head=(5, 1), M=384, N=4, c=1.0, a=0.1),
+}
+
+
+def live_spec(hwc, convs, head, M, c, a, S=2, seed=7, white=False, num_data=60000, conv_q_sqrt_scale=0.3):
+    spec = syn.make_spec(hwc, convs, head, M, S=S, num_data=num_data, seed=seed, white=white, conv_q_sqrt_scale=conv_q_sqrt_scale)
+    rng = np.random.default_rng(seed)
+    layers = spec["convs"] + [spec["head"]]
+    for li, l in enumerate(layers):
+        Z = np.asarray(l["Z"], np.float64)
+        l["ls"] = float(c * np.sqrt(np.mean(np.sum(Z * Z, 1))))
+        l["q_mu"] = a * np.asarray(l["q_mu"], np.float64)
+        if not white:
+            Lu = np.linalg.cholesky(syn._rbf(Z, Z, l["variance"], l["ls"]) + syn.JITTER * np.eye(M))
+            l["q_sqrt"] = np.tile(Lu[None], [l["R"], 1, 1]) * (1.0 if l is spec["head"] else conv_q_sqrt_scale)
+    spec["head"]["w"] = 0.5 + rng.random(spec["head"]["w"].shape)
+    return spec
+
+
+def make_case(name):
+    """(spec, X, Y, zs) of CASES[name]."""
+    k = dict(CASES[name])
+    N = k.pop("N")
+    spec = live_spec(**k)
+    X, Y = syn.make_batch(k["hwc"], N, seed=7)
+    return spec, X, Y, syn.make_noise(spec, N, seed=7)
+
+
+def torch_reference(spec, X, Y, zs):
+    """(ELBO, [per-layer {group: gradient}]) by torch autograd of tests/test_oracle_autograd.py's forward, float64 on the CPU; q_sqrt's
+    gradient is cut to the lower triangle (the parameter)."""
+    import torch
+    from test_oracle_autograd import _torch_elbo
+    e_t, leaves = _torch_elbo(spec, X, Y, zs)
+    flat = [(li, k, t) for li, p in enumerate(leaves) for k, t in p.items()]
+    tg = torch.autograd.grad(e_t, [t for _, _, t in flat])
+    want = [{} for _ in leaves]
+    for (li, k, _), g in zip(flat, tg):
+        want[li][k] = np.tril(g.numpy()) if k == "q_sqrt" else g.numpy().copy()
+    return e_t.item(), want
+
+
+SPEC_KEY = {"Z": "Z", "q_mu": "q_mu", "q_sqrt": "q_sqrt", "variance": "variance", "lengthscales": "ls", "patch_weights": "w"}
+POSITIVE = ("variance", "lengthscales")      # softplus + 1e-6 in gpflow's unconstrained space
+
+
+def softplus_inv(x):
+    return np.log(np.expm1(x - 1e-6))
+
+
+def adam_numpy_step(spec, grads, state, lr, t, b1=0.9, b2=0.999, eps=1e-8):
+    """tf.train.AdamOptimizer's update (ascent on the ELBO) of every value of `spec` in place, from `grads` as torch_reference returns them;
+    `state` {(layer, group): [m, v]} is filled on the first call.  The scheme of test_adam_steps_match_numpy_on_oracle_gradients."""
+    lr_t = lr * np.sqrt(1 - b2 ** t) / (1 - b1 ** t)
+    for li, l in enumerate(spec["convs"] + [spec["head"]]):
+        for name, g in grads[li].items():
+            x = np.array(l[SPEC_KEY[name]], np.float64)
+            g = -np.asarray(g, np.float64)
+            u = softplus_inv(x) if name in POSITIVE else x
+            if name in POSITIVE:
+                g = g * (1.0 - np.exp(-(x - 1e-6)))
+            m, v = state.setdefault((li, name), [np.zeros_like(x), np.zeros_like(x)])
+            m[...] = b1 * m + (1 - b1) * g
+            v[...] = b2 * v + (1 - b2) * g * g
+            u = u - lr_t * m / (np.sqrt(v) + eps)
+            new = np.log1p(np.exp(u)) + 1e-6 if name in POSITIVE else u
+            l[SPEC_KEY[name]] = float(new) if np.ndim(new) == 0 else new
+
+
+def model_values(model):
+    """[per-layer {group: value}] of a device model's Python-side parameters (after pull_parameters), under the gradient's names."""
+    out = []
+    for li, l in enumerate(model.layers):
+        head = li == len(model.layers) - 1
+        kern = l.kern.base_kernel if head else l.base_kernel
+        d = dict(Z=np.array(l.feature.Z), q_mu=np.array(l.q_mu), q_sqrt=np.array(l.q_sqrt), variance=float(kern.variance),
+                 lengthscales=float(kern.lengthscales))
+        if head:
+            d["patch_weights"] = np.array(l.kern.patch_weights)
+        out.append(d)
+    return out
+
+
+def _entries(name, g):
+    """The entries of a group that are parameters: the lower triangle of every q_sqrt[r], everything otherwise."""
+    g = np.asarray(g, np.float64)
+    if name == "q_sqrt":
+        return g[:, np.tril(np.ones(g.shape[1:], bool))]
+    return g.reshape(-1)
+
+
+def liveness(want):
+    """[(layer, group, |want|max, median |want| / |want|max, share of entries below ENTRY_FLOOR * |want|max)] of a reference gradient."""
+    rows = []
+    for li, groups in enumerate(want):
+        for name, g in groups.items():
+            v = np.abs(_entries(name, g))
+            top = float(v.max())
+            rows.append((li, name, top, float(np.median(v)) / top if top > 0 else 0.0, float(np.mean(v < ENTRY_FLOOR * top))))
+    return rows
+
+
+def assert_live(case, want):
+    """The liveness condition of a case, on the reference alone."""
+    for li, name, top, med, left_out in liveness(want):
+        assert top >= LIVE_MAX, (case, li, name, "max", top)
+        if name in MEDIAN_GROUPS:
+            assert med >= LIVE_MEDIAN, (case, li, name, "median / max", med)
+        if name in CAPPED_GROUPS:
+            assert left_out <= LEFT_OUT_CAP, (case, li, name, "share below the entry floor", left_out)
+
+
+def errors(name, got, want):
+    """(group-wise |got - want|max / |want|max, entry-wise max |got - want| / |want| over the entries at or above the floor)."""
+    g, w = _entries(name, got), _entries(name, want)
+    top = np.abs(w).max()
+    keep = np.abs(w) >= ENTRY_FLOOR * top
+    d = np.abs(g - w)
+    return float(d.max() / top), float((d[keep] / np.abs(w[keep])).max())

@@ -914,7 +914,10 @@ def test_kept_patch_responses_match_recomputed(ctx, hwc, convs, M, N):
 
 def test_gradients_finite_and_repeatable_at_cfg3_size(ctx):
     """BASELINE configs[2] at full size: three layers, 640 rows, a head of 25 patches of 250 elements -- far-apart patch pairs whose
-    kernel values are denormals (a NaN lengthscale gradient once: 0 x log 0 in the kernel adjoint).  Finite, and the same bits twice."""
+    kernel values are denormals (a NaN lengthscale gradient once: 0 x log 0 in the kernel adjoint).  Finite, and the same bits twice.
+    NOT gradient-parity coverage: this spec is degenerate for that (K_uf of the second layer underflows, torch autograd gives |dZ|max of
+    1e-30 for both conv layers, so a gradient of zeros would pass any relative bar).  Parity of the deep data path and of M > 256 is
+    tests/test_gpu_grad_large_m.py, on specs whose every group is live."""
     cfg = syn.CONFIGS["cfg3_mnist_3layer_M256"]
     spec = syn.make_spec(cfg["hwc"], cfg["convs"], cfg["head"], cfg["M"], S=10, num_data=cfg["num_data"], seed=1)
     X, Y = syn.make_batch(cfg["hwc"], cfg["batch"], seed=1)
