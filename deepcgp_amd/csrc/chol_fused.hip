@@ -664,14 +664,14 @@ __global__ void chol_finish_kernel(double* const* __restrict__ Ap, const double*
 }  // namespace
 
 // Cholesky factor in place (strict upper triangle zeroed) and, when d_Linv != nullptr, inv(L) (+ its transpose).
-bool chain_can_ride(const dcgp_ctx* ctx, int Mp) {
-  return ctx->chain_ride_ok && Mp <= kChainRhsMaxMp && !ctx->opt.no_rhs_ride;
+bool chain_can_ride(const dcgp_ctx* ctx, int Mp, ChainMode mode) {
+  return mode.may_ride && Mp <= kChainRhsMaxMp && !ctx->opt.no_rhs_ride;
 }
 
 int factor_inverse_batched(dcgp_ctx* ctx, double* const* d_A, double* const* d_Linv, double* const* d_LinvT, int batch,
-                           int Mp, int ld, int* d_info, bool defer_finish, const ChainRhs* d_rhs, int max_R) {
+                           int Mp, int ld, int* d_info, bool defer_finish, const ChainRhs* d_rhs, int max_R, ChainMode mode) {
   if (batch <= 0) return DCGP_OK;
-  if (d_rhs && (!d_Linv || !chain_can_ride(ctx, Mp))) return ctx_fail(ctx, DCGP_ERR_ARG, "factorisation chain: right-hand sides cannot ride this route");
+  if (d_rhs && (!d_Linv || !chain_can_ride(ctx, Mp, mode))) return ctx_fail(ctx, DCGP_ERR_ARG, "factorisation chain: right-hand sides cannot ride this route");
   ScopedTimer t(ctx, "factor_chain");
   const size_t mm = (size_t)Mp * ld;
   double* Lout = (double*)ws_get(ctx, "chol_Lout" + ctx->ws_tag, (size_t)batch * mm * sizeof(double));
@@ -717,7 +717,7 @@ int factor_inverse_batched(dcgp_ctx* ctx, double* const* d_A, double* const* d_L
     }
     // gx == 0: last panel of a plain potrf -- only L_jj is left; one workgroup factors and publishes it
     a.gx_trace = gx > 0 ? gx : 1;
-    if (Xla && !ctx->opt.chain_no_iso && ctx->chain_alone) {   // the look-ahead workgroups alone on one XCD (RlArgs::iso_per)
+    if (Xla && !ctx->opt.chain_no_iso && mode.alone) {   // the look-ahead workgroups alone on one XCD (RlArgs::iso_per)
       a.batch = batch;
       a.iso_per = (gx > 0 ? gx : 1) - (a.la_idx >= 0 ? 1 : 0);
       const int items = batch * a.iso_per, slots = (items + 6) / 7;

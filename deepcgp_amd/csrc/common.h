@@ -59,10 +59,7 @@ struct DcgpOptions {
   long head_no_overlap = 0;      // head-first model: the factorisation chain in front of the sweep instead of beside it
   long no_factor_reuse = 0;      // evaluation entry points run the parameter-only chain every time, also at unchanged parameters (A/B)
   long prep_on_chain = 0;        // head-first model: the operand preparation on the chain's stream instead of in front of the sweep on the main stream (A/B)
-  long prep_one_launch = 0;      // head-first model, synchronous step: the operand preparation as ONE launch on the main stream with an event to the chain's stream
-                                 // instead of one launch per stream (A/B)
   long no_early_sweep = 0;       // the first layer's sweep enqueued behind the chain instead of in front of it
-  long sync_event = 0;           // wait for the step's event instead of polling its completion word
   long chain_no_iso = 0;         // chain launches that carry right-hand sides: no XCD isolation of the look-ahead workgroups (A/B)
   long comm_inline = 0;          // multi-rank steps in flight: the data term's all-reduce in the main stream instead of the comm stream (A/B)
   long no_rhs_ride = 0;          // G / alpha by their own launch behind the chain (prep_solve) instead of riding its panel launches
@@ -84,14 +81,8 @@ long* dcgp_option_slot(DcgpOptions* o, const char* name);   // nullptr: no such 
 // `name` != nullptr additionally applies DCGP_POISON_ONLY (only workspaces whose name contains that string)
 bool dcgp_poison(const char* name = nullptr);
 
-struct KlTail;   // layer.h
 struct dcgp_ctx {
   int device = 0;
-  // KL pieces riding the head's one-launch conditional (model.hip sets kl_ride in front of the head layer of an ELBO step; head_cond.hip carries them as
-  // extra workgroups of its launch, clears kl_ride and sets kl_rode; a head on another route leaves them to the tail launch)
-  const KlTail* kl_ride = nullptr;
-  double* kl_ride_scal = nullptr;
-  bool kl_rode = false;
   int n_cus = 256;   // compute units of the device (set at dcgp_ctx_create)
   hipStream_t stream = nullptr;    // the stream launches go to (temporarily swapped to stream2 for the side branch)
   hipStream_t stream2 = nullptr;   // side stream: factorisation chain + KL terms
@@ -108,8 +99,7 @@ struct dcgp_ctx {
   hipStream_t last_main = nullptr;             // main stream of the most recent forward step ...
   hipEvent_t ev_last = nullptr;                // ... and the event marking the end of that step on it (not owned; a step on the other main stream waits for it)
   bool ev_last_valid = false;
-  hipEvent_t ev_fork = nullptr, ev_factor = nullptr, ev_kl = nullptr;
-  hipEvent_t ev_prep[8] = {};   // per layer: G / alpha of layer l are ready (side stream)
+  hipEvent_t ev_fork = nullptr, ev_kl = nullptr;
   DcgpOptions opt;                 // A/B switches: environment at dcgp_ctx_create, then dcgp_ctx_set_option only
   bool no_side = false;            // opt.no_side_stream: everything on the main stream (A/B switch; counter-collection runs, where
                                    // the profiler serialises dispatches and cross-stream waits can deadlock it)
@@ -122,11 +112,6 @@ struct dcgp_ctx {
   hipEvent_t ev_aux = nullptr, ev_aux2 = nullptr;  // fork / join of a short side-stream excursion inside a layer
   std::string err;
   std::map<std::string, unsigned> fused_pre_epochs;   // per hand-over area of the layer kernel's prologues ahead (conv_fused.hip): launches so far
-  bool chain_alone = true;   // the factorisation chain about to run has the chip to itself (forward_all: synchronous step, chain on the main stream): the
-                             // look-ahead workgroups are then confined to one XCD.  Beside a patch sweep or the previous step's layer kernel that
-                             // confinement costs more than it saves (head-only model 4250 -> 3190 steps/s without the riding right-hand sides)
-  bool chain_ride_ok = true; // right-hand sides may ride the chain about to run: not beside a patch sweep (a head-first model: 4250 -> 4200 steps/s).
-                             // A property of the model, not of the step's mode: synchronous and in-flight steps take the same route (bit-identical)
   std::string ws_tag;   // suffix of the chain's / KL terms' scratch names: steps in flight on the two banks must not share them
   // named, grow-only device workspaces owned by the ctx
   std::map<std::string, std::pair<void*, size_t>> ws;
@@ -429,14 +414,22 @@ int trtri_batched(dcgp_ctx* ctx, double* const* d_L, double* const* d_Linv, doub
 struct ChainRhs { const double* Lq; const double* qmu; double* G; double* alpha; double* sums; double* Yw; int R, Rp; };
 inline int chain_rhs_slots(int Mp) { const int np = (Mp + 31) / 32; return np * (np + 1) / 2; }
 constexpr int kChainRhsMaxMp = 256;   // beyond: the substitution's workgroups outgrow a panel launch (the generic GEMM route takes those layers)
+// How a factorisation chain shares the chip with what runs beside it (a step's plan decides: model.hip, plan_step; an operator called on its own: the defaults).
+struct ChainMode {
+  bool alone = true;      // the chain has the chip to itself (synchronous step, chain on the main stream): the look-ahead workgroups are then confined to one XCD.
+                          // Beside a patch sweep or the previous step's layer kernel that confinement costs more than it saves (head-only model 4250 -> 3190
+                          // steps/s without the riding right-hand sides)
+  bool may_ride = true;   // right-hand sides may ride the chain: not beside a patch sweep (a head-first model: 4250 -> 4200 steps/s).  A property of the
+                          // model, not of the step's mode: synchronous and in-flight steps take the same route (bit-identical)
+};
 // left-looking fused Cholesky (+ inverse of the factor when d_Linv != nullptr): one launch per 32-wide panel.
 // d_rhs != nullptr (device array, one entry per matrix; max_R = the largest R among them): right-hand sides ride the chain.
 int factor_inverse_batched(dcgp_ctx* ctx, double* const* d_A, double* const* d_Linv, double* const* d_LinvT, int batch,
-                           int Mp, int ld, int* d_info, bool defer_finish = false, const ChainRhs* d_rhs = nullptr, int max_R = 0);
+                           int Mp, int ld, int* d_info, bool defer_finish = false, const ChainRhs* d_rhs = nullptr, int max_R = 0, ChainMode mode = ChainMode());
 int comm_gate_wait(dcgp_ctx* ctx);   // comm.hip (debugging aid)
 int reduce_scatter_sum_f64_async(dcgp_ctx* ctx, double* block_dev, size_t shard);   // comm.hip (in place, this rank's shard)
 int all_gather_f64_async(dcgp_ctx* ctx, double* block_dev, size_t shard);
 int factor_finish_batched(dcgp_ctx* ctx, double* const* d_A, int batch, int Mp, int ld);
-bool chain_can_ride(const dcgp_ctx* ctx, int Mp);   // right-hand sides may ride the chain of a matrix of this size under the ctx's options
+bool chain_can_ride(const dcgp_ctx* ctx, int Mp, ChainMode mode);   // right-hand sides may ride the chain of a matrix of this size under the ctx's options
 int pad_copy(dcgp_ctx* ctx, const double* src, int rows, int cols, int lds, double* dst, int ldd, int rows_p,
              int cols_p, int mode, int batch, long src_batch, long dst_batch);   // mode 0 full, 1 lower-tri, 2: +I on pad diag

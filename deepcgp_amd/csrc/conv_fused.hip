@@ -1061,7 +1061,9 @@ int conv_fused(dcgp_ctx* ctx, const ConvFusedArgs& a_in) {
     a.persist = (int)(per_cu * n_cus);
     a.n_strips = (int)strips;
     if (want != 2) {   // (2: the fixed deal blockIdx, blockIdx + grid, ... -- A/B)
-      const std::string nm = "fused_dyn" + ctx->ws_tag;   // steps in flight on the two banks run this kernel side by side: a counter pair each
+      // ONE counter pair (and one hand-over area, below) per ctx: ws_tag is empty by the time a layer runs, so the names carry no bank.  Safe because a
+      // ctx's layer launches are serialised on one main stream (a step on the other main stream starts behind the previous one's end, model.hip)
+      const std::string nm = "fused_dyn" + ctx->ws_tag;
       const bool fresh = ctx->ws.find(nm) == ctx->ws.end();
       a.dyn = static_cast<int*>(ws_get(ctx, nm, 2 * sizeof(int)));
       if (!a.dyn) return DCGP_ERR_ALLOC;

@@ -25,7 +25,7 @@ const OptSlot kOptSlots[] = {
     {"fused_bwd_frags", &DcgpOptions::fused_bwd_frags}, {"grad_late_kl", &DcgpOptions::grad_late_kl}, {"gemm_tile", &DcgpOptions::gemm_tile}, {"grad_no_keep_k", &DcgpOptions::grad_no_keep_k},
     {"head_unfused", &DcgpOptions::head_unfused}, {"no_side_stream", &DcgpOptions::no_side_stream}, {"cu_partition", &DcgpOptions::cu_partition},
     {"grad_nofork", &DcgpOptions::grad_nofork}, {"head_no_overlap", &DcgpOptions::head_no_overlap},
-    {"no_early_sweep", &DcgpOptions::no_early_sweep}, {"prep_on_chain", &DcgpOptions::prep_on_chain}, {"prep_one_launch", &DcgpOptions::prep_one_launch}, {"no_factor_reuse", &DcgpOptions::no_factor_reuse}, {"sync_event", &DcgpOptions::sync_event}, {"kuf_upw", &DcgpOptions::kuf_upw},
+    {"no_early_sweep", &DcgpOptions::no_early_sweep}, {"prep_on_chain", &DcgpOptions::prep_on_chain}, {"no_factor_reuse", &DcgpOptions::no_factor_reuse}, {"kuf_upw", &DcgpOptions::kuf_upw},
     {"no_rhs_ride", &DcgpOptions::no_rhs_ride}, {"comm_inline", &DcgpOptions::comm_inline}, {"chain_no_iso", &DcgpOptions::chain_no_iso}, {"kuf_no_rep", &DcgpOptions::kuf_no_rep}, {"kuf_stream", &DcgpOptions::kuf_stream},
     {"kuf_wpg", &DcgpOptions::kuf_wpg}, {"kuf_split", &DcgpOptions::kuf_split}, {"head_tail", &DcgpOptions::head_tail},
     {"sweep_occ", &DcgpOptions::sweep_occ}, {"share_kb", &DcgpOptions::share_kb}, {"head_upw", &DcgpOptions::head_upw}, {"no_syrk", &DcgpOptions::no_syrk}, {"grad_dz_main", &DcgpOptions::grad_dz_main},
@@ -174,7 +174,6 @@ int dcgp_ctx_create(int device, dcgp_ctx** out) {
       side_stream_create(&c->stream2) != hipSuccess || side_stream_create(&c->stream2b) != hipSuccess ||
       hipStreamCreateWithFlags(&c->stream_aux, hipStreamNonBlocking) != hipSuccess ||
       hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_factor, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&c->ev_aux, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&c->ev_kl2, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&c->ev_kl3, hipEventDisableTiming) != hipSuccess ||
@@ -186,11 +185,6 @@ int dcgp_ctx_create(int device, dcgp_ctx** out) {
     delete c;
     return DCGP_ERR_HIP;
   }
-  for (auto& e : c->ev_prep)
-    if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) {
-      delete c;
-      return DCGP_ERR_HIP;
-    }
   {
     // CU-mask bit i lands on XCD i % 8, CU i / 8 (tools/cu_mask_census.hip): bits [0, 240) = 30 CUs of every XCD, [240, 256) = the
     // other two.  OPT-IN (DCGP_CU_PARTITION=1), measured and NOT faster: workgroups are dealt to the four shader engines of an XCD
@@ -235,14 +229,11 @@ int dcgp_ctx_destroy(dcgp_ctx* ctx) {
   if (ctx->comm_gate) hipHostFree(ctx->comm_gate);
   if (ctx->stream_comm) { hipStreamDestroy(ctx->stream_comm); for (auto e : ctx->ev_comm) if (e) hipEventDestroy(e); }
   hipEventDestroy(ctx->ev_fork);
-  hipEventDestroy(ctx->ev_factor);
   hipEventDestroy(ctx->ev_aux);
   hipEventDestroy(ctx->ev_kl2);
   hipEventDestroy(ctx->ev_kl3);
   for (hipEvent_t e : ctx->ev_g) hipEventDestroy(e);
   hipEventDestroy(ctx->ev_aux2);
-  for (auto& e : ctx->ev_prep)
-    if (e) hipEventDestroy(e);
   hipEventDestroy(ctx->ev_kl);
   if (ctx->stream_m) hipStreamDestroy(ctx->stream_m);
   if (ctx->stream2_m) hipStreamDestroy(ctx->stream2_m);

@@ -314,7 +314,7 @@ static bool prep_solve_ok(const GpMats& g) { return g.Mp <= PS_MP && g.Mp % HC_B
 
 // mean / var [Kc][R] of the conditional at Kc columns whose Kzx is B [Mp][ldb]; G / alpha from cond_prep
 int head_cond_fused(dcgp_ctx* ctx, const GpMats& g, const double* B, long ldb, int Kc, bool have_qsqrt, const double* kd,
-                    double* out_mean, double* out_var, int kd_n, double kd_scale, double* A1_out, long lda1) {
+                    double* out_mean, double* out_var, int kd_n, double kd_scale, double* A1_out, long lda1, KlOffer* kl) {
   if (Kc <= 0) return DCGP_OK;
   if (!head_cond_fused_ok(g) || (long)g.Mp * ldb * 8 >= (1L << 31))
     return ctx_fail(ctx, DCGP_ERR_ARG, "head_cond_fused: M = %d not supported", g.Mp);
@@ -330,11 +330,11 @@ int head_cond_fused(dcgp_ctx* ctx, const GpMats& g, const double* B, long ldb, i
   // (worth it from ~1000 diagonal entries per layer on: M = 256, R = 10 -- head-only model 0.2186 -> 0.2160 ms per step; at M = 32 the extra row of
   // workgroups costs the launch more than the tail saves: 0.1408 -> 0.1418)
   long kl_work = 0;
-  if (ctx->kl_ride)
-    for (int l = 0; l < ctx->kl_ride->nl; ++l) kl_work = std::max<long>(kl_work, (long)ctx->kl_ride->l[l].M * ctx->kl_ride->l[l].R);
-  if (ctx->kl_ride && ctx->kl_ride->nl <= strips && kl_work >= 1024 && !ctx->opt.kl_no_ride) {
-    a.kl = *ctx->kl_ride; a.kl_scal = ctx->kl_ride_scal;
-    ctx->kl_ride = nullptr; ctx->kl_rode = true;
+  if (kl)
+    for (int l = 0; l < kl->tail->nl; ++l) kl_work = std::max<long>(kl_work, (long)kl->tail->l[l].M * kl->tail->l[l].R);
+  if (kl && kl->tail->nl <= strips && kl_work >= 1024 && !ctx->opt.kl_no_ride) {
+    a.kl = *kl->tail; a.kl_scal = kl->scal;
+    kl->carried = true;
   }
   const size_t lds = (size_t)(g.Mp * HC_BN + 4 * 16 * 16) * sizeof(double);   // (>= the 8 KB of a KL workgroup: Mp >= 16)
   static bool attr_set[64] = {};   // per device (72 KB at Mp = 512)

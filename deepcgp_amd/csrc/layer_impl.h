@@ -237,10 +237,10 @@ struct FactorGroup {
   // only the KL terms (and the reverse pass) read it, so the copy need not sit in front of the first layer
   bool deferred = false;
   bool rode = false;   // the most recent run() carried the right-hand sides (the ctx's options may rule it out from one step to the next)
-  int run(dcgp_ctx* ctx, bool defer_finish = false) {
+  int run(dcgp_ctx* ctx, bool defer_finish = false, ChainMode mode = ChainMode()) {
     DCGP_TRY(upload(ctx));
-    rode = ride && chain_can_ride(ctx, Mp);
-    DCGP_TRY(factor_inverse_batched(ctx, dK, dLinv, dLinvT, (int)K.size(), Mp, Mp, d_info, defer_finish, rode ? d_rhs : nullptr, max_R));
+    rode = ride && chain_can_ride(ctx, Mp, mode);
+    DCGP_TRY(factor_inverse_batched(ctx, dK, dLinv, dLinvT, (int)K.size(), Mp, Mp, d_info, defer_finish, rode ? d_rhs : nullptr, max_R, mode));
     deferred = defer_finish;
     return DCGP_OK;
   }
@@ -251,11 +251,34 @@ struct FactorGroup {
   }
 };
 
+// What a conv layer on `rows` images hands the one-launch layer kernel of its own: geometry, operands and the column count -- every field the route
+// decision reads (conv_fused.hip, plan_fused).  Filled here and nowhere else, for a step's plan (model.hip, plan_step) and for the dispatch below, so that
+// the two cannot be asked different questions.
+static inline ConvFusedArgs conv_fused_shape(const LayerState& L, long rows) {
+  ConvFusedArgs fa;
+  fa.H = L.v.H; fa.W = L.v.W; fa.C = L.v.C; fa.f = L.v.f; fa.s = L.v.s; fa.Wo = L.v.Wo; fa.P = L.v.P; fa.L = L.v.L; fa.Lp = L.Lp;
+  fa.HWC = L.v.H * L.v.W * L.v.C;
+  fa.ZT = L.ZT; fa.zn = L.zn; fa.M = L.M; fa.Mp = L.Mp; fa.bk = L.base();
+  fa.ZS = L.ZS; fa.Lz = L.Lz; fa.csq = sqrt(1.4426950408889634074) / L.ls;
+  fa.LinvT = L.g.LinvT; fa.G = L.has_qsqrt ? L.g.G : nullptr; fa.alpha = L.g.alpha; fa.R = L.R; fa.Rp = L.g.Rp;
+  fa.Kc = (int)std::min<long>(rows * L.v.P, 0x7fffffffL); fa.knn = L.variance; fa.idm = L.identity_mean;
+  return fa;
+}
+// Whether a model's first layer on `rows` images is ONE launch behind the factorisation (nothing of it can run beside the chain) or opens with a sweep
+// of its own that needs Z only.  A conv layer: the one-launch layer kernel covers it.  The head: a chain of one or two panels is shorter than the
+// hand-off between streams (option head_no_overlap: A/B switch and how bench.py times the sweep alone on the chip).
+static inline bool first_layer_one_launch(const dcgp_ctx* ctx, const LayerState& L, long rows) {
+  return L.is_head ? !(L.Mp >= 96 && !ctx->opt.head_no_overlap) : conv_fused_ok(ctx, conv_fused_shape(L, rows));
+}
+
 // ConvLayer.conditional_ND (+ sampling) on `rows` input images taken as X[(n % n_mod)]
+// planned_one_launch: -1, or the route a step's plan placed its streams and events for (0 sweep + GEMM, 1 the one-launch kernel): a different answer here
+// is refused, not run
 static inline int conv_forward(dcgp_ctx* ctx, LayerState& L, const double* X, int rows, int n_mod, int rep, long rep_stride,
                  const double* z, uint64_t seed, uint32_t stream_id, double jitter, double* out_sample, double* out_mean,
                  double* out_var, const std::string& pfx, hipEvent_t factor_done = nullptr,
-                               hipEvent_t prep_done = nullptr, int phase = 3, bool keep_state = true, const RngMap* rmap = nullptr) {
+                               hipEvent_t prep_done = nullptr, int phase = 3, bool keep_state = true, const RngMap* rmap = nullptr,
+                               int planned_one_launch = -1) {
   // phase bit 0: the K_uf sweep (needs only Z); bit 1: conditional + finalize (needs the factorisation).  The model
   // path enqueues bit 0 of its first layer BEFORE the long side-stream sequence so that the sweep is not held up
   // by the host still enqueueing the factorisation chain.
@@ -267,18 +290,16 @@ static inline int conv_forward(dcgp_ctx* ctx, LayerState& L, const double* X, in
   {
     // one launch for the whole layer where the shape allows (conv_fused.hip): the strip of K_uf / A1 a workgroup owns
     // stays in LDS from the patch gather to the sample
-    ConvFusedArgs fa;
+    ConvFusedArgs fa = conv_fused_shape(L, rows);
     fa.X = X; fa.n_mod = n_mod;
-    fa.H = L.v.H; fa.W = L.v.W; fa.C = L.v.C; fa.f = L.v.f; fa.s = L.v.s; fa.Wo = L.v.Wo; fa.P = P; fa.L = L.v.L; fa.Lp = L.Lp;
-    fa.HWC = L.v.H * L.v.W * L.v.C;
-    fa.ZT = L.ZT; fa.zn = L.zn; fa.M = L.M; fa.Mp = Mp; fa.bk = L.base();
-    fa.ZS = L.ZS; fa.Lz = L.Lz; fa.csq = sqrt(1.4426950408889634074) / L.ls;
-    fa.LinvT = L.g.LinvT; fa.G = L.has_qsqrt ? L.g.G : nullptr; fa.alpha = L.g.alpha; fa.R = L.R; fa.Rp = L.g.Rp;
-    fa.Kc = (int)Kc; fa.knn = L.variance;
     fa.rep = rep; fa.rep_stride = rep_stride; fa.z = z; fa.seed = seed; fa.stream_id = stream_id; fa.jitter = jitter;
-    fa.out_sample = out_sample; fa.out_mean = out_mean; fa.out_var = out_var; fa.idm = L.identity_mean;
+    fa.out_sample = out_sample; fa.out_mean = out_mean; fa.out_var = out_var;
     if (rmap) fa.rmap = *rmap;
-    if (conv_fused_ok(ctx, fa)) {
+    const bool one_launch = conv_fused_ok(ctx, fa);
+    if (planned_one_launch >= 0 && one_launch != (planned_one_launch != 0))
+      return ctx_fail(ctx, DCGP_ERR_ARG, "conv layer: the step was planned for the %s route, the layer takes the other (M = %d, %ld patch columns)",
+                      planned_one_launch ? "one-launch" : "sweep + GEMM", L.M, Kc);
+    if (one_launch) {
       if (!(phase & 2)) return DCGP_OK;   // nothing to run ahead of the factorisation: the sweep is part of the one launch
       if (keep_state) {
         fa.Kuf_out = (double*)ws_get(ctx, pfx + "Kuf", (size_t)Mp * ldb * sizeof(double));
@@ -360,8 +381,9 @@ static inline int conv_forward(dcgp_ctx* ctx, LayerState& L, const double* X, in
 // SVGP head: Kzx / Kdiag from the conv kernel, then the shared conditional
 static inline int head_forward(dcgp_ctx* ctx, LayerState& L, const double* X, int rows, int n_mod, double* kd, double* out_mean,
                  double* out_var, const std::string& pfx, hipEvent_t factor_done = nullptr,
-                               hipEvent_t prep_done = nullptr, int phase = 3, int sweep_mode = 0, bool* early_done = nullptr,
-                               bool keep_k = false) {
+                               hipEvent_t prep_done = nullptr, int sweep_mode = 0, bool* early_done = nullptr,
+                               bool keep_k = false, KlOffer* kl = nullptr) {
+  // kl: the KL pieces of an ELBO step, for the one-launch conditional to carry (layer.h: KlOffer)
   // keep_k (a training step): the unit sweep also leaves every patch response in the "<pfx>g_Kfull" workspace [Mp][col_ld(rows P)] and sets
   // L.kfull_ready (the reverse pass would otherwise evaluate them all again)
   // sweep_mode (the unit-sweep route only): 1 = the sweep launch alone (it needs Z only: the model enqueues it in front of the long
@@ -378,7 +400,7 @@ static inline int head_forward(dcgp_ctx* ctx, LayerState& L, const double* X, in
   }
   double* B = (double*)ws_get(ctx, pfx + "Kzx", (size_t)Mp * ldb * sizeof(double));
   if (!B) return DCGP_ERR_ALLOC;
-  if ((phase & 1) && sweep_mode != 2 && Mp > L.M) HIP_TRY(ctx, hipMemsetAsync(B + (size_t)L.M * ldb, 0, (size_t)(Mp - L.M) * ldb * sizeof(double), ctx->stream));
+  if (sweep_mode != 2 && Mp > L.M) HIP_TRY(ctx, hipMemsetAsync(B + (size_t)L.M * ldb, 0, (size_t)(Mp - L.M) * ldb * sizeof(double), ctx->stream));
   PatchRbfArgs a;
   a.X = X; a.N = rows; a.n_mod = n_mod;
   a.H = L.v.H; a.W = L.v.W; a.C = L.v.C; a.f = L.v.f; a.s = L.v.s; a.Ho = L.v.Ho; a.Wo = L.v.Wo; a.P = L.v.P; a.L = L.v.L;
@@ -387,9 +409,8 @@ static inline int head_forward(dcgp_ctx* ctx, LayerState& L, const double* X, in
   a.out = B; a.sM = ldb; a.sN = 1; a.sP = 0;
   a.w = L.w; a.scale = 1.0 / (double)L.v.P; a.reduce = 1;
   a.in_scale = L.in_scale;
-  a.share_cu = phase == 1;
   const bool unfused = ctx->opt.head_unfused != 0;   // A/B switch
-  if (phase == 3 && L.kernel_type == 0 && a.bk.type == 0 && !L.in_scale) {
+  if (L.kernel_type == 0 && a.bk.type == 0 && !L.in_scale) {
     // ConvKernel head: Kzx and Kdiag as wave-sized units of one launch (head_units.hip), any M
     HeadUnitsArgs h;
     h.X = X; h.n_mod = n_mod; h.N = rows;
@@ -427,7 +448,7 @@ static inline int head_forward(dcgp_ctx* ctx, LayerState& L, const double* X, in
       else if (factor_done) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, factor_done, 0));
       if (head_cond_fused_ok(L.g) && !unfused) {
         L.a1h_ready = a1_out != nullptr;
-        return head_cond_fused(ctx, L.g, B, ldb, rows, L.has_qsqrt, h.kd, out_mean, out_var, h.n_kd, kd_scale, a1_out, ldb);
+        return head_cond_fused(ctx, L.g, B, ldb, rows, L.has_qsqrt, h.kd, out_mean, out_var, h.n_kd, kd_scale, a1_out, ldb, kl);
       }
       DCGP_TRY(kdiag_reduce(ctx, h.kd, h.n_kd, rows, kd_scale, kd));
       CondScratch sc;
@@ -440,7 +461,7 @@ static inline int head_forward(dcgp_ctx* ctx, LayerState& L, const double* X, in
     }
   }
   if (sweep_mode == 1) return DCGP_OK;   // not the unit-sweep route: nothing is launched ahead
-  if (phase == 3 && L.kernel_type == 0 && a.bk.type == 0 && head_cond_fused_ok(L.g) && !unfused) {
+  if (L.kernel_type == 0 && a.bk.type == 0 && head_cond_fused_ok(L.g) && !unfused) {
     // ConvKernel head, M <= 256: Kzx and Kdiag in one launch, then the whole conditional in one launch that adds up the Kdiag
     // tile-pair sums itself -- two launches on one stream for the layer
     const double* kdp = nullptr; int kd_n = 1; double kd_scale = 1.0;
@@ -448,43 +469,39 @@ static inline int head_forward(dcgp_ctx* ctx, LayerState& L, const double* X, in
     if (prep_done) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, prep_done, 0));
     else if (factor_done) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, factor_done, 0));
     L.a1h_ready = a1_out != nullptr;
-    return head_cond_fused(ctx, L.g, B, ldb, rows, L.has_qsqrt, kdp, out_mean, out_var, kd_n, kd_scale, a1_out, ldb);
+    return head_cond_fused(ctx, L.g, B, ldb, rows, L.has_qsqrt, kdp, out_mean, out_var, kd_n, kd_scale, a1_out, ldb, kl);
   }
-  bool kd_on_side = false;
-  if (phase & 1) {
-    // Kdiag (all patch pairs of an image) is needed by finalize only: it runs on the side stream beside the
-    // Kzx sweep and the conditional GEMMs instead of in front of them.
-    hipStream_t main_s = ctx->stream;
-    kd_on_side = !ctx->no_side;
-    if (kd_on_side) {
-      HIP_TRY(ctx, hipEventRecord(ctx->ev_aux, main_s));   // X is ready at this point of the main stream
-      HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream_aux, ctx->ev_aux, 0));
-      ctx->stream = ctx->stream_aux;
-    }
-    int rc;
-    if (L.kernel_type == 0) {
-      rc = head_kdiag(ctx, X, rows, n_mod, L.v.H, L.v.W, L.v.C, L.v.f, L.v.s, L.base(), L.w, kd);
-    } else {
-      rc = additive_kdiag_async(ctx, rows, L.v.P, L.variance, L.w, kd);
-    }
-    if (kd_on_side) {
-      if (rc == DCGP_OK && hipEventRecord(ctx->ev_aux2, ctx->stream_aux) != hipSuccess) rc = DCGP_ERR_HIP;
-      ctx->stream = main_s;
-    }
-    DCGP_TRY(rc);
-    DCGP_TRY(patch_rbf(ctx, a, "head_kzx"));
+  // Kdiag (all patch pairs of an image) is needed by finalize only: it runs on the side stream beside the
+  // Kzx sweep and the conditional GEMMs instead of in front of them.
+  hipStream_t main_s = ctx->stream;
+  const bool kd_on_side = !ctx->no_side;
+  if (kd_on_side) {
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_aux, main_s));   // X is ready at this point of the main stream
+    HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream_aux, ctx->ev_aux, 0));
+    ctx->stream = ctx->stream_aux;
   }
-  if (!(phase & 2)) return DCGP_OK;
+  int rc;
+  if (L.kernel_type == 0) {
+    rc = head_kdiag(ctx, X, rows, n_mod, L.v.H, L.v.W, L.v.C, L.v.f, L.v.s, L.base(), L.w, kd);
+  } else {
+    rc = additive_kdiag_async(ctx, rows, L.v.P, L.variance, L.w, kd);
+  }
+  if (kd_on_side) {
+    if (rc == DCGP_OK && hipEventRecord(ctx->ev_aux2, ctx->stream_aux) != hipSuccess) rc = DCGP_ERR_HIP;
+    ctx->stream = main_s;
+  }
+  DCGP_TRY(rc);
+  DCGP_TRY(patch_rbf(ctx, a, "head_kzx"));
   if (factor_done) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, factor_done, 0));
   if (head_cond_fused_ok(L.g) && !unfused) {
     // few columns (one per image): both triangular products, the mean and mean / var in one launch (head_cond.hip)
     if (prep_done) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, prep_done, 0));
     if (!ctx->no_side) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_aux2, 0));
-    return head_cond_fused(ctx, L.g, B, ldb, rows, L.has_qsqrt, kd, out_mean, out_var);
+    return head_cond_fused(ctx, L.g, B, ldb, rows, L.has_qsqrt, kd, out_mean, out_var, 1, 1.0, nullptr, 0, kl);
   }
   CondScratch sc;
   DCGP_TRY(cond_core(ctx, L.g, B, ldb, rows, L.white, L.has_qsqrt, pfx.c_str(), &sc, prep_done, true));
-  // join: with phase == 2 the excursion was started by the earlier phase-1 call on the same stream pair
+  // join the Kdiag excursion
   if (!ctx->no_side) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_aux2, 0));
   FinalizeArgs fa;
   fa.s1p = sc.s1p; fa.nrb1 = sc.nrb1; fa.s2p = sc.s2p; fa.nrb3 = sc.nrb3; fa.mu = sc.mu; fa.ldk = ldb;

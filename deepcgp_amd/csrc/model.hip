@@ -125,13 +125,6 @@ struct StreamGuard {
   ~StreamGuard() { ctx->stream = saved; ctx->ws_tag.clear(); }
 };
 
-// layers 0..n-1 forward; leaves ctx->stream on the main stream the step runs on (the caller holds a StreamGuard).
-//   side stream: everything that depends on the parameters only, into the bank of this step's parity -- Kuu / prior Kuu /
-//                Z^T / padded q_sqrt, q_mu of every layer (one launch), ONE batched Cholesky + inverse chain for all M x M
-//                matrices, G / alpha of every layer (one launch), the KL terms;
-//   main stream: the data path (sweeps, conditionals, sampling), gated per layer by the side stream's events.
-// pipelined (dcgp_elbo_forward_enqueue): main = 30 CUs of every XCD, side = the other 2, so that the chain of step i + 1 runs
-// under the data path of step i without competing for its CUs; otherwise both streams see the whole chip.
 // what the assembly at the end of a step needs: layer shapes, the status words of the factor groups, the pinned result slot
 int fill_finish(dcgp_model* model, double scale, int slot, ElboFinish* fin) {
   const int nl = (int)model->layers.size();
@@ -143,6 +136,285 @@ int fill_finish(dcgp_model* model, double scale, int slot, ElboFinish* fin) {
   return DCGP_OK;
 }
 
+// ---- A forward step (forward_all): its schedule is decided once, in plan_step, and three functions enqueue from that plan ----
+//   chain stream: everything that depends on the parameters only, into the bank of this step's parity -- Kuu / prior Kuu /
+//                 Z^T / padded q_sqrt, q_mu of every layer, ONE batched Cholesky + inverse chain for all M x M
+//                 matrices, G / alpha of every layer (one launch), the KL terms;
+//   main stream:  the data path (sweeps, conditionals, sampling), gated per layer by the chain's events.
+// pipelined (dcgp_elbo_forward_enqueue): main = 30 CUs of every XCD, side = the other 2, so that the chain of step i + 1 runs
+// under the data path of step i without competing for its CUs; otherwise both streams see the whole chip.
+
+// Where the operand preparation (prep.hip) goes.
+// OnChain: one launch on the chain's stream, ev_sweep behind it for a first layer that sweeps beside the chain.  Steps kept in flight stay here: the preparation
+// runs under the previous step's data path -- on the main stream it waited for that step (head-only model 4830 -> 4590 steps/s in flight).
+// Split*: a synchronous step whose first layer's sweep is a launch of its own: that sweep is the step's critical path.  The preparation in TWO launches, each on
+// the stream of its reader -- what a sweep reads (Z^T, |z|^2, the scaled Z) on the MAIN stream with the sweep directly behind it, the Gram matrices and
+// the padded q_sqrt / q_mu on the chain's -- and no event between the streams at the head of the step: the record was a packet between the preparation
+// and the sweep (7.6 us from one to the other), the wait held the chain back.  With the preparation on the chain's stream the sweep started 20.8 us
+// into the step (8 us of preparation + the event), now at ~9.  (Option prep_on_chain: back to OnChain, A/B.)
+// Which stream's part the host enqueues first is which part gets the chip first.  SplitChainFirst: a conv layer on the sweep + GEMM route (M > 256): the CHAIN is the
+// longest path (the first product waits for inv(L) long after the sweep is done) -- enqueued behind the sweep its preparation ran 71 us beside it
+// instead of ~15 and the first product of cfg4 started 53 us later (profiles/the first cut of this split)
+// SplitSweepFirst: a model that opens with the head: the sweep is the step's longest path (170 us against the chain's ~150 beside it) -- its part and the sweep, then the
+// chain's part BEHIND the sweep: at the head of a synchronous step the device waits for the host, ~4 us a launch
+enum class PrepPlace { OnChain, SplitChainFirst, SplitSweepFirst };
+// Where a training step marks the start of the parameter-only part of its reverse pass (grad.hip, grad_kl_early; ctx->ev_fork).  That part runs beside the
+// forward pass on the auxiliary stream; dcgp_elbo_grad enqueues it behind the whole forward pass (in front of the layers the host kept the first layer
+// waiting for 170 us, in front of the tail launch the end of the forward pass for 60).
+// BehindFirstLayer: that layer's launch fills the chip at the full batch, and forty short launches squeezed in between its rounds cost it more than they
+// gained.  BehindChain: a first layer of a few thousand patch columns -- the de-duplicated batch -- leaves half the chip idle: there the mark is behind the chain.
+enum class ForkMark { BehindFirstLayer, BehindChain };
+
+struct StepPlan {
+  // The chain of the previous step stands if no parameter was written since and this step may use it (model_state.h: factor_reuse): same bank, no
+  // preparation, no factorisation, no G / alpha, no KL launches -- the step is its data path.
+  bool reuse = false;
+  int bank = 0, rows0 = 0;   // rows0: rows entering layer 0; it reads image (row % N): tile(X,[S,1,1]) is never formed
+  // Where the parameter-only chain runs.  A synchronous step has nothing else to do until the factorisation is there: the chain
+  // sits on the main stream itself (no cross-stream hand-off in front of the first layer, ~15 us each) and only the KL terms
+  // fork to the side stream.  A step enqueued beside others: the side stream of its bank, so that it overtakes the step in flight.
+  // A first layer that opens with a sweep of its own (the sweep + GEMM route; a model that opens with the head -- the reference's "1-layer") needs Z
+  // only for it: the sweep runs on the main stream beside the chain on the side stream, and the step is the longer of the two instead of their sum.
+  hipStream_t main_s = nullptr, chain_s = nullptr, kl_s = nullptr;
+  bool first_one_launch = true;   // layer 0's route (layer_impl.h: first_layer_one_launch -- the dispatch's own question; conv_forward refuses another answer)
+  PrepPlace prep = PrepPlace::OnChain;
+  // Layer 0's sweep needs nothing but the preparation: it goes to the main stream in front of the chain's ~12 launches -- enqueued behind
+  // them it started when the host was done with those, 60 us after prepare_all had finished (cfg2 head-only: 0.287 -> 0.24 ms).  (Option no_early_sweep: A/B.)
+  bool early_sweep = false;
+  bool defer = false;   // with a single factor group its "chol_Lout" scratch stays untouched until the deferred copy runs on the KL stream
+  ChainMode chain;
+  ForkMark mark = ForkMark::BehindFirstLayer;
+  bool chain_beside() const { return chain_s != main_s; }   // events only where another stream waits for them: each record is a packet in front of the next launch
+};
+// what the caller of a step hands over
+struct StepIn { const double* X; int N, S; const double* const* zs; uint64_t seed; int dedup; bool need_kl; };
+std::string model_pfx(const dcgp_model* m) { return "m" + std::to_string(m->id) + "_"; }
+
+// No HIP call, nothing written to the model or the ctx.
+StepPlan plan_step(const dcgp_model* m, int N, int S, int dedup, bool need_kl, bool pipelined) {
+  const dcgp_ctx* ctx = m->ctx;
+  const LayerState& L0 = *m->layers[0];
+  StepPlan p;
+  p.reuse = !pipelined && !m->grad_follows && (!m->keep_state || m->data_grad) && m->chain_version == m->param_version && m->chain_with_kl == need_kl &&
+            m->factor_reuse >= (need_kl ? 2 : 1) && !ctx->opt.no_factor_reuse;
+  p.bank = p.reuse ? m->bank : m->bank ^ 1;
+  const bool part = pipelined && ctx->stream_m && !ctx->no_side;   // (no_side: A/B switch, everything on one stream)
+  p.main_s = part ? ctx->stream_m : ctx->stream;
+  p.kl_s = ctx->no_side ? p.main_s : (part ? ctx->stream2_m : (pipelined ? (p.bank ? ctx->stream2b : ctx->stream2) : ctx->stream2));
+  p.rows0 = dedup ? N : S * N;
+  p.first_one_launch = first_layer_one_launch(ctx, L0, p.rows0);
+  p.chain_s = p.reuse ? p.main_s : ((pipelined || !p.first_one_launch) ? p.kl_s : p.main_s);
+  p.early_sweep = p.chain_beside() && !p.first_one_launch && !ctx->opt.no_early_sweep;
+  if (p.early_sweep && !pipelined && !ctx->opt.prep_on_chain) p.prep = L0.is_head ? PrepPlace::SplitSweepFirst : PrepPlace::SplitChainFirst;
+  bool one_group = true;   // build_groups: one factor group per distinct Mp
+  for (auto& l : m->layers) one_group = one_group && l->Mp == L0.Mp;
+  p.defer = one_group && need_kl && !m->keep_state;
+  p.chain = ChainMode{!p.chain_beside() && !pipelined, p.first_one_launch};
+  p.mark = (long)p.rows0 * L0.v.P >= 8192 ? ForkMark::BehindFirstLayer : ForkMark::BehindChain;
+  return p;
+}
+
+// The parameter-only part of a step runs on the chain's / KL stream and names its scratch per model and bank: the chains / KL terms of two steps in flight
+// may overlap, and with the deferred copy the tail launch reads the prior factor's diagonal out of this scratch at the END of the step -- another model's
+// chain on the same ctx must not have overwritten it by then.  Both end here, whichever way that part returns: ctx->stream is the step's main stream and the
+// tag is gone before a layer runs.  If the part failed, what it had enqueued on the two streams is waited for before the error goes up.
+struct ChainScope {
+  dcgp_ctx* ctx; const StepPlan& p; bool ok = false;
+  ChainScope(dcgp_model* m, const StepPlan& plan) : ctx(m->ctx), p(plan) { ctx->stream = p.chain_s; ctx->ws_tag = "~m" + std::to_string(m->id) + "b" + std::to_string(p.bank); }
+  ~ChainScope() {
+    ctx->stream = p.main_s; ctx->ws_tag.clear();
+    if (!ok) { hipStreamSynchronize(p.kl_s); hipStreamSynchronize(p.chain_s); }
+  }
+};
+
+// one layer of the data path on ctx->stream.  phase 1: only what needs Z alone (the layer's sweep, where it is a launch of its own), 2: the rest, 3: both.
+// head_swept: whether the head's phase 1 launched anything (written by phase 1, read by phase 2).  kl: the KL pieces offered to the head (layer.h: KlOffer)
+int run_layer(dcgp_model* m, const StepPlan& p, const StepIn& in, int li, const double* F, int rows, int n_mod, int phase, bool* head_swept, KlOffer* kl,
+              int* out_rows_p) {
+  dcgp_ctx* ctx = m->ctx;
+  LayerState& L = *m->layers[li];
+  const std::string pfx = model_pfx(m) + std::to_string(li) + "_";
+  const double* z = in.zs ? in.zs[li] : nullptr;
+  hipEvent_t fdone = (li == 0 && p.chain_beside()) ? m->ev_factor[p.bank] : nullptr;   // later layers are stream-ordered behind layer 0
+  hipEvent_t pdone = p.chain_beside() ? m->ev_prep[p.bank][li] : nullptr;
+  if (!L.is_head) {
+    const int width = L.v.P * L.R;
+    const bool expand = in.dedup && li == 0;          // N distinct images -> S*N sampled rows
+    const int out_rows = expand ? in.S * in.N : rows;
+    DCGP_TRY(ensure_out(m, li, out_rows, width));
+    auto& o = m->outs[li];
+    // device RNG: with a shard declared (dcgp_model_set_shard) every element draws at its counter in the un-sharded batch, one
+    // stream per layer -- the step's value is then independent of the number of ranks; otherwise one stream per (layer, rank)
+    RngMap rm;
+    const bool sharded = m->shard_global > 0;
+    if (sharded && (m->shard_global != in.N || m->shard_lo != 0)) { rm.W = width; rm.Nl = in.N; rm.Ng = m->shard_global; rm.lo = m->shard_lo; }
+    DCGP_TRY(conv_forward(ctx, L, F, rows, n_mod, expand ? in.S : 1, (long)in.N * width, z, in.seed, (uint32_t)(li + 1 + (sharded ? 0 : 64 * ctx->rank)),
+                          m->jitter, o.sample, m->keep_outputs ? o.mean : nullptr, m->keep_outputs ? o.var : nullptr, pfx,
+                          fdone, pdone, phase, m->keep_state, &rm, li == 0 ? (int)p.first_one_launch : -1));
+    *out_rows_p = out_rows;
+    return DCGP_OK;
+  }
+  DCGP_TRY(ensure_out(m, li, rows, L.R));
+  auto& o = m->outs[li];
+  DCGP_TRY(ensure(ctx, &m->d_kd, &m->kd_cap, (size_t)rows));
+  DCGP_TRY(head_forward(ctx, L, F, rows, n_mod, m->d_kd, o.mean, o.var, pfx, fdone, pdone,
+                        phase == 1 ? 1 : (phase == 2 && *head_swept ? 2 : 0), phase == 1 ? head_swept : nullptr,
+                        m->keep_state && m->grad_follows, kl));
+  *out_rows_p = rows;
+  if (phase != 1 && m->keep_outputs) {
+    // the head's sample is not needed by the ELBO; produce it only on request
+    size_t n = (size_t)rows * L.R;
+    if (z) {
+      DCGP_TRY(reparam_async(ctx, o.mean, o.var, z, n, m->jitter, o.sample));
+    } else {
+      HIP_TRY(ctx, hipMemcpyAsync(o.sample, o.mean, n * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    }
+  }
+  return DCGP_OK;
+}
+
+// The parameter-only chain on p.chain_s (inside a ChainScope): preparation, layer 0's early sweep where the plan has one, the factor groups, G / alpha of
+// every layer.  *early0: layer 0's phase 1 is enqueued (the data path runs its phase 2).
+int enqueue_chain(dcgp_model* m, const StepPlan& p, const StepIn& in, bool* early0, bool* head_swept) {
+  dcgp_ctx* ctx = m->ctx;
+  const int nl = (int)m->layers.size(), bank = p.bank;
+  const bool beside = p.chain_beside();
+  if (beside && m->done_valid[bank]) HIP_TRY(ctx, hipStreamWaitEvent(p.chain_s, m->done_ev[bank], 0));     // the bank's previous reader
+  else if (beside && ctx->ev_last_valid) HIP_TRY(ctx, hipStreamWaitEvent(p.chain_s, ctx->ev_last, 0));    // first use: behind whatever ran last
+  PrepArgs pa;
+  pa.nl = nl;
+  for (int li = 0; li < nl; ++li) pa.l[li] = m->layers[li]->prep_args(m->jitter);
+  if (p.prep == PrepPlace::OnChain) {
+    DCGP_TRY(prepare_all(ctx, pa));
+    if (beside && !p.first_one_launch) HIP_TRY(ctx, hipEventRecord(m->ev_sweep[bank], p.chain_s));   // Z^T, |z|^2: what a sweep needs
+  } else {
+    if (p.prep == PrepPlace::SplitChainFirst) DCGP_TRY(prepare_all(ctx, pa, ~kPrepSweepTasks));
+    ctx->stream = p.main_s;
+    DCGP_TRY(prepare_all(ctx, pa, kPrepSweepTasks));
+    ctx->stream = p.chain_s;
+  }
+  if (p.early_sweep) {
+    ctx->stream = p.main_s;
+    if (p.prep == PrepPlace::OnChain) HIP_TRY(ctx, hipStreamWaitEvent(p.main_s, m->ev_sweep[bank], 0));
+    int out_rows = 0;
+    DCGP_TRY(run_layer(m, p, in, 0, in.X, p.rows0, in.N, 1, head_swept, nullptr, &out_rows));
+    *early0 = true;
+    ctx->stream = p.chain_s;
+  }
+  if (p.prep == PrepPlace::SplitSweepFirst) DCGP_TRY(prepare_all(ctx, pa, ~kPrepSweepTasks));
+  for (auto& gr : m->groups[bank]) DCGP_TRY(gr.run(ctx, p.defer, p.chain));
+  if (beside) HIP_TRY(ctx, hipEventRecord(m->ev_factor[bank], p.chain_s));
+  // G_r = inv(L) Lq_r and alpha = inv(L) q_mu of every layer: gate the second conditional GEMM
+  bool made[8] = {}, rode[8] = {};
+  for (int li = 0; li < nl; ++li) {   // layers whose right-hand sides rode the chain (build_groups): nothing left to do
+    LayerState& L = *m->layers[li];
+    bool live_sums = false, prior_sums = false;
+    for (auto& gr : m->groups[bank]) {
+      if (!gr.rode) continue;
+      for (size_t i = 0; i < gr.K.size(); ++i) {
+        if (gr.K[i] == L.g.K && (gr.rhs[i].Lq || gr.rhs[i].qmu)) { rode[li] = true; live_sums = gr.rhs[i].Lq != nullptr; }
+        if (L.g.Kp && gr.K[i] == L.g.Kp && gr.rhs[i].Lq) prior_sums = true;
+      }
+    }
+    if (!(made[li] = rode[li])) continue;
+    L.g.klp_valid = live_sums; L.g.klpp_valid = prior_sums;
+    L.g.kl_ns = chain_rhs_slots(L.Mp); L.g.kl_nsa = (L.Mp + 31) / 32;
+  }
+  GpMats* gs[8]; int wh[8]; bool hq[8];   // every other layer the one-launch route covers (unwhitened, M <= 256, <= 16 outputs): head_cond.hip
+  for (int li = 0; li < nl; ++li) { gs[li] = &m->layers[li]->g; wh[li] = m->layers[li]->white; hq[li] = m->layers[li]->has_qsqrt; }
+  DCGP_TRY(prep_solve_all(ctx, gs, wh, hq, nl, made, rode));
+  for (int li = 0; li < nl; ++li) {
+    if (!made[li]) DCGP_TRY(cond_prep(ctx, m->layers[li]->g, m->layers[li]->white, m->layers[li]->has_qsqrt));   // generic GEMMs
+    if (beside) HIP_TRY(ctx, hipEventRecord(m->ev_prep[bank][li], p.chain_s));   // per layer: layer 0 does not wait for the others
+  }
+  return DCGP_OK;
+}
+
+// Where the KL pieces go (behind enqueue_chain, inside its ChainScope).  They need nothing but parameter-only state.  Where the chain left the sums of
+// squares they are made of (every layer unwhitened, M <= 256, with q_sqrt), one extra workgroup per layer of the tail launch -- or of the head's one-launch
+// conditional (enqueue_layers) -- adds them up with the factors' log-determinants: no KL launches, no stream of their own, no fork in front of the first
+// layer and no join (tail_dev.h); m->kl_in_tail / m->kl_tail of the bank say so to the tail.  Otherwise (and with option kl_side) their own launches, on
+// the KL stream: *join = the main stream must wait for ev_kl of the bank.
+int place_kl(dcgp_model* m, const StepPlan& p, bool need_kl, double* scal, bool* join) {
+  dcgp_ctx* ctx = m->ctx;
+  const int nl = (int)m->layers.size(), bank = p.bank;
+  bool in_tail = need_kl && !ctx->opt.kl_side;
+  for (int li = 0; li < nl && in_tail; ++li) {   // (the sums are valid where this step's chain or prep_solve left them with G / alpha)
+    const LayerState& L = *m->layers[li];
+    in_tail = !L.white && L.has_qsqrt && L.g.klp_valid && (!L.g.Kp || L.g.klpp_valid);
+  }
+  m->kl_in_tail[bank] = in_tail;
+  if (in_tail) {
+    KlTail& kt = m->kl_tail[bank];
+    kt.nl = nl;
+    const auto it = p.defer ? ctx->ws.find("chol_Lout" + ctx->ws_tag) : ctx->ws.end();   // deferred copy: the factors are still in the chain's scratch,
+    const double* lout = it != ctx->ws.end() ? (const double*)it->second.first : nullptr;      // [matrix of the group][Mp][Mp]
+    for (int li = 0; li < nl; ++li) {
+      const LayerState& L = *m->layers[li];
+      KlTailLayer& q = kt.l[li];
+      const double* prior = L.g.Kp ? L.g.Kp : L.g.K;
+      q.Lfac = prior; q.ldf = L.Mp;
+      if (p.defer) {
+        const auto& gr = m->groups[bank][0];
+        long idx = -1;
+        for (size_t i = 0; i < gr.K.size(); ++i) if (gr.K[i] == prior) idx = (long)i;
+        if (!lout || idx < 0) return ctx_fail(ctx, DCGP_ERR_ARG, "model: factor scratch of layer %d not found", li);
+        q.Lfac = lout + idx * (long)L.Mp * L.Mp;
+      }
+      q.Lq = L.g.Lq; q.sums = L.g.Kp ? L.g.klpp : L.g.klp; q.M = L.M; q.Mp = L.Mp; q.R = L.R;
+      q.ns = L.g.kl_ns; q.nsa = L.g.kl_nsa;
+    }
+  }
+  if (!need_kl || in_tail) return DCGP_OK;
+  if (p.kl_s != p.chain_s) {   // fork: the KL terms need the factors only, the main stream goes on with the layers
+    if (!p.chain_beside()) HIP_TRY(ctx, hipEventRecord(m->ev_prep[bank][nl - 1], p.chain_s));   // (a chain beside the main stream has recorded it)
+    HIP_TRY(ctx, hipStreamWaitEvent(p.kl_s, m->ev_prep[bank][nl - 1], 0));
+    ctx->stream = p.kl_s;
+  }
+  for (auto& gr : m->groups[bank]) DCGP_TRY(gr.finish(ctx));   // the factor back over K (deferred copy): the KL terms read its diagonal
+  for (int li = 0; li < nl; ++li) {
+    LayerState& L = *m->layers[li];
+    const double* Lp = L.g.Kp ? L.g.Kp : L.g.K;
+    const double* LpinvT = L.g.Kp ? L.g.LpinvT : L.g.LinvT;
+    DCGP_TRY(kl_layer(ctx, L.g, Lp, LpinvT, L.white, (model_pfx(m) + std::to_string(li)).c_str(), scal + 4 + 4 * li));
+  }
+  *join = p.kl_s != p.main_s;
+  if (*join) HIP_TRY(ctx, hipEventRecord(m->ev_kl[bank], ctx->stream));
+  return DCGP_OK;
+}
+
+// The data path over the layers on p.main_s, with the join of the KL stream.
+int enqueue_layers(dcgp_model* m, const StepPlan& p, const StepIn& in, bool early0, bool head_swept, bool kl_join, double* scal, int* rows_last) {
+  dcgp_ctx* ctx = m->ctx;
+  const int nl = (int)m->layers.size(), bank = p.bank;
+  // sweeps read Z^T / |z|^2 of this bank (a one-launch first layer waits for its G / alpha, recorded behind them on the same stream)
+  if (p.chain_beside() && !p.first_one_launch && p.prep == PrepPlace::OnChain) HIP_TRY(ctx, hipStreamWaitEvent(p.main_s, m->ev_sweep[bank], 0));
+  const double* F = in.X;
+  int rows = p.rows0, n_mod = in.N;
+  // Join the side stream where the wait is already satisfied when the main stream gets to it: in front of the last layer when
+  // other layers precede it (the KL terms finish beside the first of them), behind it otherwise.  In front of the tail kernel
+  // the wait packet sat between two short launches at the very end of the step (6 us).
+  const bool join_early = nl > 1;
+  // the KL pieces ride the head's one-launch conditional where there is one (head_cond.hip); m->kl_rode[bank] says whether they did
+  KlOffer offer{&m->kl_tail[bank], scal};
+  for (int li = 0; li < nl; ++li) {
+    const bool last = li == nl - 1;
+    int out_rows = 0;
+    if (last && join_early && kl_join) HIP_TRY(ctx, hipStreamWaitEvent(p.main_s, m->ev_kl[bank], 0));
+    DCGP_TRY(run_layer(m, p, in, li, F, rows, n_mod, (li == 0 && early0) ? 2 : 3, &head_swept,
+                       (last && in.need_kl && m->kl_in_tail[bank]) ? &offer : nullptr, &out_rows));
+    if (li == 0 && m->gkl_state && p.mark == ForkMark::BehindFirstLayer)
+      HIP_TRY(ctx, hipEventRecord(ctx->ev_fork, p.main_s));   // (the chain's results are ordered in front of this layer)
+    if (!m->layers[li]->is_head) F = m->outs[li].sample;
+    rows = n_mod = out_rows;
+  }
+  m->kl_rode[bank] = offer.carried;
+  if (!join_early && kl_join) HIP_TRY(ctx, hipStreamWaitEvent(p.main_s, m->ev_kl[bank], 0));   // join the side stream
+  *rows_last = rows;
+  return DCGP_OK;
+}
+
+// layers 0..n-1 forward; leaves ctx->stream on the main stream the step runs on (the caller holds a StreamGuard).
 int forward_all(dcgp_model* m, const double* X, int N, int S, const double* const* zs, uint64_t seed, int dedup,
                 bool need_kl, bool pipelined, int* rows_last) {
   dcgp_ctx* ctx = m->ctx;
@@ -157,287 +429,36 @@ int forward_all(dcgp_model* m, const double* X, int N, int S, const double* cons
     return ctx_fail(ctx, DCGP_ERR_ARG, "forward: %d images from image %d on overrun the declared global batch of %d (dcgp_model_set_shard)", N,
                     m->shard_lo, m->shard_global);
   DCGP_TRY(ensure_events(m));
-  // The chain of the previous step stands if no parameter was written since and this step may use it (model_state.h: factor_reuse): same bank, no
-  // preparation, no factorisation, no G / alpha, no KL launches -- the step is its data path.
-  const bool reuse = !pipelined && !m->grad_follows && (!m->keep_state || m->data_grad) && m->chain_version == m->param_version && m->chain_with_kl == need_kl &&
-                     m->factor_reuse >= (need_kl ? 2 : 1) && !ctx->opt.no_factor_reuse;
-  if (!reuse) m->chain_version = 0;   // (stays 0 if this step fails on the way)
-  const int bank = reuse ? m->bank : m->bank ^ 1;
-  m->bank = bank;
-  for (auto& l : m->layers) DCGP_TRY(l->use_bank(bank));
-  DCGP_TRY(build_groups(m, bank));
+  const StepPlan p = plan_step(m, N, S, dedup, need_kl, pipelined);
+  const StepIn in{X, N, S, zs, seed, dedup, need_kl};
+  if (!p.reuse) m->chain_version = 0;   // (stays 0 if this step fails on the way)
+  m->bank = p.bank;
+  for (auto& l : m->layers) DCGP_TRY(l->use_bank(p.bank));
+  DCGP_TRY(build_groups(m, p.bank));
   if (!m->d_scal && hipMalloc((void**)&m->d_scal, 128 * sizeof(double)) != hipSuccess)
     return ctx_fail(ctx, DCGP_ERR_ALLOC, "model: allocation failed");
-  double* scal = m->d_scal + 64 * bank;
+  double* scal = m->d_scal + 64 * p.bank;
   m->outs.resize(nl);
-  const std::string mp = "m" + std::to_string(m->id) + "_";
-  const int rows0 = dedup ? N : S * N;   // rows entering layer 0; it reads image (row % N): tile(X,[S,1,1]) is never formed
-
-  const bool no_side = ctx->no_side;   // A/B switch: everything on one stream
-  const bool part = pipelined && ctx->stream_m && !no_side;
-  const hipStream_t main_s = part ? ctx->stream_m : ctx->stream;
-  // Where the parameter-only chain runs.  A synchronous step has nothing else to do until the factorisation is there: the chain
-  // sits on the main stream itself (no cross-stream hand-off in front of the first layer, ~15 us each) and only the KL terms
-  // fork to the side stream.  A step enqueued beside others: the side stream of its bank, so that it overtakes the step in flight.
-  const hipStream_t kl_s = no_side ? main_s : (part ? ctx->stream2_m : (pipelined ? (bank ? ctx->stream2b : ctx->stream2) : ctx->stream2));
-  // (A first layer on the sweep + GEMM route keeps the side stream: its sweep needs Z only and runs beside the chain.)
-  // (A model that opens with the head -- the reference's "1-layer" -- has a first kernel that needs Z only: its sweep runs on the main
-  // stream beside the chain on the side stream, and the step is the longer of the two instead of their sum.)
-  // (a chain of one or two panels is shorter than the hand-off between streams; option head_no_overlap: A/B switch
-  // and how bench.py times the sweep alone on the chip)
-  bool first_fused = !(m->layers[0]->is_head && m->layers[0]->Mp >= 96 && !ctx->opt.head_no_overlap);
-  if (!m->layers[0]->is_head) {
-    const LayerState& L0 = *m->layers[0];
-    ConvFusedArgs fa;
-    fa.Mp = L0.Mp; fa.M = L0.M; fa.R = L0.R; fa.Rp = L0.g.Rp; fa.P = L0.v.P; fa.HWC = L0.v.H * L0.v.W * L0.v.C; fa.Lp = L0.Lp; fa.Lz = L0.Lz;
-    first_fused = conv_fused_ok(ctx, fa);
-  }
-  const hipStream_t chain_s = reuse ? main_s : ((pipelined || !first_fused) ? kl_s : main_s);
   // a step on the other main stream than the previous one starts behind it
-  if (ctx->ev_last_valid && ctx->last_main != main_s) HIP_TRY(ctx, hipStreamWaitEvent(main_s, ctx->ev_last, 0));
-  ctx->last_main = main_s;
+  if (ctx->ev_last_valid && ctx->last_main != p.main_s) HIP_TRY(ctx, hipStreamWaitEvent(p.main_s, ctx->ev_last, 0));
+  ctx->last_main = p.main_s;
 
-  // one layer of the data path on ctx->stream.  phase 1: only what needs Z alone (the layer's sweep, where it is a launch of its own),
-  // 2: the rest, 3: both
-  bool early_head = false;
-  auto layer_step = [&](int li, const double* F, int rows, int n_mod, int* out_rows_p, int phase) -> int {
-    LayerState& L = *m->layers[li];
-    const std::string pfx = mp + std::to_string(li) + "_";
-    const double* z = zs ? zs[li] : nullptr;
-    hipEvent_t fdone = (li == 0 && chain_s != main_s) ? m->ev_factor[bank] : nullptr;   // later layers are stream-ordered behind layer 0
-    hipEvent_t pdone = chain_s != main_s ? m->ev_prep[bank][li] : nullptr;
-    if (!L.is_head) {
-      const int width = L.v.P * L.R;
-      const bool expand = dedup && li == 0;          // N distinct images -> S*N sampled rows
-      const int out_rows = expand ? S * N : rows;
-      DCGP_TRY(ensure_out(m, li, out_rows, width));
-      auto& o = m->outs[li];
-      // device RNG: with a shard declared (dcgp_model_set_shard) every element draws at its counter in the un-sharded batch, one
-      // stream per layer -- the step's value is then independent of the number of ranks; otherwise one stream per (layer, rank)
-      RngMap rm;
-      const bool sharded = m->shard_global > 0;
-      if (sharded && (m->shard_global != N || m->shard_lo != 0)) { rm.W = width; rm.Nl = N; rm.Ng = m->shard_global; rm.lo = m->shard_lo; }
-      DCGP_TRY(conv_forward(ctx, L, F, rows, n_mod, expand ? S : 1, (long)N * width, z, seed, (uint32_t)(li + 1 + (sharded ? 0 : 64 * ctx->rank)),
-                            m->jitter, o.sample, m->keep_outputs ? o.mean : nullptr, m->keep_outputs ? o.var : nullptr, pfx,
-                            fdone, pdone, phase, m->keep_state, &rm));
-      *out_rows_p = out_rows;
-    } else {
-      DCGP_TRY(ensure_out(m, li, rows, L.R));
-      auto& o = m->outs[li];
-      DCGP_TRY(ensure(ctx, &m->d_kd, &m->kd_cap, (size_t)rows));
-      DCGP_TRY(head_forward(ctx, L, F, rows, n_mod, m->d_kd, o.mean, o.var, pfx, fdone, pdone, 3,
-                            phase == 1 ? 1 : (phase == 2 && early_head ? 2 : 0), phase == 1 ? &early_head : nullptr,
-                            m->keep_state && m->grad_follows));
-      if (phase == 1) { *out_rows_p = rows; return DCGP_OK; }
-      if (m->keep_outputs) {
-        // the head's sample is not needed by the ELBO; produce it only on request
-        size_t n = (size_t)rows * L.R;
-        if (z) {
-          DCGP_TRY(reparam_async(ctx, o.mean, o.var, z, n, m->jitter, o.sample));
-        } else {
-          HIP_TRY(ctx, hipMemcpyAsync(o.sample, o.mean, n * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-        }
-      }
-      *out_rows_p = rows;
-    }
-    return DCGP_OK;
-  };
-  int rc = DCGP_OK;
-  const bool xs = chain_s != main_s;
-  // (steps kept in flight: the preparation stays on the chain's stream, where it runs under the previous step's data path -- on the main stream it
-  // waited for that step: head-only model 4830 -> 4590 steps/s in flight)
-  const bool prep_on_main = xs && !first_fused && !pipelined && !ctx->opt.no_early_sweep && !ctx->opt.prep_on_chain;
-  const bool prep_split = prep_on_main && !ctx->opt.prep_one_launch;
-  const bool chain_first = prep_split && !m->layers[0]->is_head;
-  bool early0 = false, side_kl = false;
-  if (reuse) ++m->chain_skips;
-  if (!reuse) {
-  // ---- the parameter-only chain ----
-  ctx->stream = chain_s;
-  // its scratch per model and bank: the chains / KL terms of two steps in flight may overlap, and with the deferred copy the tail
-  // launch reads the prior factor's diagonal out of this scratch at the END of the step -- another model's chain on the same
-  // ctx must not have overwritten it by then
-  ctx->ws_tag = "~m" + std::to_string(m->id) + "b" + std::to_string(bank);
-  if (chain_s != main_s) {
-    if (m->done_valid[bank]) HIP_TRY(ctx, hipStreamWaitEvent(chain_s, m->done_ev[bank], 0));   // the bank's previous reader
-    else if (ctx->ev_last_valid) HIP_TRY(ctx, hipStreamWaitEvent(chain_s, ctx->ev_last, 0));    // first use: behind whatever ran last
+  bool early0 = false, head_swept = false, kl_join = false;
+  if (p.reuse) ++m->chain_skips;   // (never pipelined: p.main_s is ctx->stream as the caller left it)
+  else {
+    ChainScope scope(m, p);
+    DCGP_TRY(enqueue_chain(m, p, in, &early0, &head_swept));
+    DCGP_TRY(place_kl(m, p, need_kl, scal, &kl_join));
+    scope.ok = true;
   }
-  // (events only where another stream waits for them: each record is a packet in front of the next launch)
-  // A first layer whose sweep is a launch of its own (the head-first model) is the step's critical path: the operand preparation sits on the MAIN
-  // stream, the sweep directly behind it, and it is the CHAIN that pays the hand-off between streams -- it ends well before the sweep does.  With the
-  // preparation on the chain's stream the sweep started 20.8 us into the step (8 us of preparation + the event), now at ~9.
-  {
-    PrepArgs pa;
-    pa.nl = nl;
-    for (int li = 0; li < nl; ++li) pa.l[li] = m->layers[li]->prep_args(m->jitter);
-    // Round 6, second step: the preparation in TWO launches, each on the stream of its reader -- what a sweep reads (Z^T, |z|^2, the scaled Z) on the
-    // main stream, the Gram matrices and the padded q_sqrt / q_mu on the chain's -- and no event between the streams at the head of the step: the
-    // record was a packet between the preparation and the sweep (7.6 us from one to the other), the wait held the chain back (option prep_one_launch: A/B)
-    if (prep_split) {
-      // Which stream's part the host enqueues first is which part gets the chip first.  A model that opens with the head: the sweep is the step's longest
-      // path (170 us against the chain's ~150 beside it) -- its part and the sweep, then the chain's.  A conv layer on the sweep + GEMM route (M > 256): the
-      // CHAIN is (the first product waits for inv(L) long after the sweep is done) -- enqueued behind the sweep its preparation ran 71 us beside it instead
-      // of ~15 and the first product of cfg4 started 53 us later (profiles/the first cut of this split)
-      if (chain_first) rc = prepare_all(ctx, pa, ~kPrepSweepTasks);
-      ctx->stream = main_s;
-      if (rc == DCGP_OK) rc = prepare_all(ctx, pa, kPrepSweepTasks);
-      ctx->stream = chain_s;   // (head first: the chain's part is enqueued BEHIND the sweep, below: at the head of a synchronous step the device waits for the host, ~4 us a launch)
-    } else {
-      if (prep_on_main) ctx->stream = main_s;
-      rc = prepare_all(ctx, pa);
-    }
-  }
-  if (rc == DCGP_OK && xs && !first_fused && !prep_split && hipEventRecord(m->ev_sweep[bank], ctx->stream) != hipSuccess) rc = DCGP_ERR_HIP;   // Z^T, |z|^2: what a sweep needs
-  if (rc == DCGP_OK && prep_on_main && !prep_split && hipStreamWaitEvent(chain_s, m->ev_sweep[bank], 0) != hipSuccess) rc = DCGP_ERR_HIP;
-  // The first layer's sweep needs nothing else: it goes to the main stream NOW, in front of the chain's ~12 launches -- enqueued behind
-  // them it started when the host was done with those, 60 us after prepare_all had finished (cfg2 head-only: 0.287 -> 0.24 ms).
-  if (rc == DCGP_OK && xs && !first_fused && !ctx->opt.no_early_sweep) {
-    ctx->stream = main_s;
-    if (!prep_on_main && hipStreamWaitEvent(main_s, m->ev_sweep[bank], 0) != hipSuccess) rc = DCGP_ERR_HIP;
-    int out_rows = 0;
-    if (rc == DCGP_OK) rc = layer_step(0, X, rows0, N, &out_rows, 1);
-    early0 = rc == DCGP_OK;
-    ctx->stream = chain_s;
-  }
-  if (rc == DCGP_OK && prep_split && !chain_first) {
-    PrepArgs pa;
-    pa.nl = nl;
-    for (int li = 0; li < nl; ++li) pa.l[li] = m->layers[li]->prep_args(m->jitter);
-    rc = prepare_all(ctx, pa, ~kPrepSweepTasks);
-  }
-  // with a single factor group its "chol_Lout" scratch stays untouched until the deferred copy runs on the KL stream
-  const bool defer = m->groups[bank].size() == 1 && need_kl && !m->keep_state;
-  ctx->chain_alone = chain_s == main_s && !pipelined;
-  ctx->chain_ride_ok = first_fused;
-  for (auto& gr : m->groups[bank])
-    if (rc == DCGP_OK) rc = gr.run(ctx, defer);
-  ctx->chain_alone = ctx->chain_ride_ok = true;
-  if (rc == DCGP_OK && xs && hipEventRecord(m->ev_factor[bank], ctx->stream) != hipSuccess) rc = DCGP_ERR_HIP;
-  // G_r = inv(L) Lq_r and alpha = inv(L) q_mu of every layer (cond_prep): gate the second conditional GEMM
-  bool prep_done[8] = {}, rode[8] = {};
-  int kl_ns[8] = {}, kl_nsa[8] = {};
-  for (int li = 0; li < nl && rc == DCGP_OK; ++li) {   // layers whose right-hand sides rode the chain (build_groups): nothing left to do
-    LayerState& L = *m->layers[li];
-    bool live_sums = false, prior_sums = false;
-    for (auto& gr : m->groups[bank]) {
-      if (!gr.rode) continue;
-      for (size_t i = 0; i < gr.K.size(); ++i) {
-        if (gr.K[i] == L.g.K && (gr.rhs[i].Lq || gr.rhs[i].qmu)) { rode[li] = true; live_sums = gr.rhs[i].Lq != nullptr; }
-        if (L.g.Kp && gr.K[i] == L.g.Kp && gr.rhs[i].Lq) prior_sums = true;
-      }
-    }
-    if (!rode[li]) continue;
-    prep_done[li] = true;
-    L.g.klp_valid = live_sums; L.g.klpp_valid = prior_sums;
-    kl_ns[li] = chain_rhs_slots(L.Mp); kl_nsa[li] = (L.Mp + 31) / 32;
-    L.g.kl_ns = kl_ns[li]; L.g.kl_nsa = kl_nsa[li];
-  }
-  if (rc == DCGP_OK) {   // every other layer the one-launch route covers (unwhitened, M <= 256, <= 16 outputs): head_cond.hip
-    GpMats* gs[8]; int wh[8]; bool hq[8];
-    for (int li = 0; li < nl; ++li) { gs[li] = &m->layers[li]->g; wh[li] = m->layers[li]->white; hq[li] = m->layers[li]->has_qsqrt; }
-    rc = prep_solve_all(ctx, gs, wh, hq, nl, prep_done, rode);
-  }
-  // The KL pieces need nothing but parameter-only state.  Where prep_solve left the sums of squares they are made of (every
-  // layer unwhitened, M <= 256, with q_sqrt), one extra workgroup per layer of the tail launch adds them up with the factors'
-  // log-determinants: no KL launches, no stream of their own, no fork in front of the first layer and no join (tail_dev.h).
-  bool kl_tail = need_kl && rc == DCGP_OK && nl <= 8 && !ctx->opt.kl_side;
-  for (int li = 0; li < nl && kl_tail; ++li) {
-    const LayerState& L = *m->layers[li];
-    kl_tail = !L.white && prep_done[li] && L.has_qsqrt && L.g.klp_valid && (!L.g.Kp || L.g.klpp_valid);
-  }
-  m->kl_in_tail[bank] = kl_tail;
-  if (kl_tail) {
-    KlTail& kt = m->kl_tail[bank];
-    kt.nl = nl;
-    const double* lout = nullptr;   // deferred copy: the factors are still in the chain's scratch, [matrix of the group][Mp][Mp]
-    if (defer) {
-      auto it = ctx->ws.find("chol_Lout" + ctx->ws_tag);
-      if (it != ctx->ws.end()) lout = (const double*)it->second.first;
-    }
-    for (int li = 0; li < nl; ++li) {
-      const LayerState& L = *m->layers[li];
-      KlTailLayer& q = kt.l[li];
-      const double* prior = L.g.Kp ? L.g.Kp : L.g.K;
-      q.Lfac = prior; q.ldf = L.Mp;
-      if (defer) {
-        const auto& gr = m->groups[bank][0];
-        long idx = -1;
-        for (size_t i = 0; i < gr.K.size(); ++i) if (gr.K[i] == prior) idx = (long)i;
-        if (!lout || idx < 0) { rc = ctx_fail(ctx, DCGP_ERR_ARG, "model: factor scratch of layer %d not found", li); break; }
-        q.Lfac = lout + idx * (long)L.Mp * L.Mp;
-      }
-      q.Lq = L.g.Lq; q.sums = L.g.Kp ? L.g.klpp : L.g.klp; q.M = L.M; q.Mp = L.Mp; q.R = L.R;
-      q.ns = kl_ns[li]; q.nsa = kl_nsa[li];
-    }
-  }
-  side_kl = need_kl && !kl_tail;
-  for (int li = 0; li < nl && rc == DCGP_OK; ++li) {
-    if (!prep_done[li]) rc = cond_prep(ctx, m->layers[li]->g, m->layers[li]->white, m->layers[li]->has_qsqrt);   // generic GEMMs
-    if (rc == DCGP_OK && (xs || (li == nl - 1 && side_kl && kl_s != chain_s)) && hipEventRecord(m->ev_prep[bank][li], ctx->stream) != hipSuccess)
-      rc = DCGP_ERR_HIP;   // per layer: layer 0 does not wait for the others (same stream: only the fork of the KL terms needs one)
-  }
-  if (rc == DCGP_OK && side_kl) {
-    if (kl_s != chain_s) {   // fork: the KL terms need the factors only, the main stream goes on with the layers
-      if (hipStreamWaitEvent(kl_s, m->ev_prep[bank][nl - 1], 0) != hipSuccess) rc = DCGP_ERR_HIP;
-      ctx->stream = kl_s;
-    }
-    for (auto& gr : m->groups[bank])
-      if (rc == DCGP_OK) rc = gr.finish(ctx);   // the factor back over K (deferred copy): the KL terms read its diagonal
-    for (int li = 0; li < nl && rc == DCGP_OK; ++li) {
-      LayerState& L = *m->layers[li];
-      const double* Lp = L.g.Kp ? L.g.Kp : L.g.K;
-      const double* LpinvT = L.g.Kp ? L.g.LpinvT : L.g.LinvT;
-      rc = kl_layer(ctx, L.g, Lp, LpinvT, L.white, (mp + std::to_string(li)).c_str(), scal + 4 + 4 * li);
-    }
-  }
-  }   // !reuse
-  const bool kl_join = side_kl && kl_s != main_s;
-  if (rc == DCGP_OK && kl_join && hipEventRecord(m->ev_kl[bank], ctx->stream) != hipSuccess) rc = DCGP_ERR_HIP;
-  ctx->stream = main_s;
-  ctx->ws_tag.clear();
-  if (rc != DCGP_OK) {
-    hipStreamSynchronize(kl_s);
-    hipStreamSynchronize(chain_s);
-    return rc;
-  }
-  if (!reuse && !pipelined && !m->grad_follows && (!m->keep_state || m->data_grad)) { m->chain_version = m->param_version; m->chain_with_kl = need_kl; }
-  // A training step: the parameter-only part of the reverse pass (grad.hip, grad_kl_early) runs beside the forward pass on the auxiliary
-  // stream.  Its start is marked behind the FIRST layer (below): that layer's launch fills the chip at the full batch, and forty short
-  // launches squeezed in between its rounds cost it more than they gained.  They are enqueued by dcgp_elbo_grad behind the whole forward
-  // pass (in front of the layers below the host kept the first layer waiting for 170 us, in front of the tail launch the end of the
-  // forward pass for 60).
+  if (!p.reuse && !pipelined && !m->grad_follows && (!m->keep_state || m->data_grad)) { m->chain_version = m->param_version; m->chain_with_kl = need_kl; }
+  // a training step: see ForkMark.  1 = the side stream itself holds the parameter-only chain (not here), 2 = it waits for ctx->ev_fork
   m->gkl_state = (m->grad_follows && !pipelined && grad_kl_early(m, false, false) == 1) ? 2 : 0;
-  // (a first layer of a few thousand patch columns -- the de-duplicated batch -- leaves half the chip idle: there the mark is here, behind the chain)
-  const bool mark_behind_first = (long)rows0 * m->layers[0]->v.P >= 8192;
-  if (m->gkl_state && !mark_behind_first) HIP_TRY(ctx, hipEventRecord(ctx->ev_fork, chain_s));
+  if (m->gkl_state && p.mark == ForkMark::BehindChain) HIP_TRY(ctx, hipEventRecord(ctx->ev_fork, p.chain_s));
   // with the chain on a side stream a mark on the MAIN stream orders layer 0's operands only: grad_kl_early also waits for the G / alpha
   // of the other layers (cond_prep of whitened / M > 256 layers runs behind ev_prep[0] on that stream)
-  m->gkl_prep_wait = (m->gkl_state && mark_behind_first && chain_s != main_s) ? nl : 0;
-
-  // sweeps read Z^T / |z|^2 of this bank (a one-launch first layer waits for its G / alpha, recorded behind them on the same stream)
-  if (chain_s != main_s && !first_fused && !prep_on_main) HIP_TRY(ctx, hipStreamWaitEvent(main_s, m->ev_sweep[bank], 0));
-  const double* F = X;
-  int rows = rows0, n_mod = N;
-  // Join the side stream where the wait is already satisfied when the main stream gets to it: in front of the last layer when
-  // other layers precede it (the KL terms finish beside the first of them), behind it otherwise.  In front of the tail kernel
-  // the wait packet sat between two short launches at the very end of the step (6 us).
-  const bool join_early = nl > 1;
-  for (int li = 0; li < nl; ++li) {
-    int out_rows = 0;
-    if (li == nl - 1 && join_early && kl_join) HIP_TRY(ctx, hipStreamWaitEvent(main_s, m->ev_kl[bank], 0));
-    // the KL pieces ride the head's one-launch conditional where there is one (head_cond.hip); m->kl_rode[bank] says whether they did
-    if (li == nl - 1 && need_kl && m->kl_in_tail[bank]) { ctx->kl_ride = &m->kl_tail[bank]; ctx->kl_ride_scal = scal; ctx->kl_rode = false; }
-    const int rc_l = layer_step(li, F, rows, n_mod, &out_rows, (li == 0 && early0) ? 2 : 3);
-    if (li == nl - 1) { m->kl_rode[bank] = need_kl && m->kl_in_tail[bank] && ctx->kl_rode; ctx->kl_ride = nullptr; ctx->kl_rode = false; }
-    DCGP_TRY(rc_l);
-    if (li == 0 && m->gkl_state && mark_behind_first) HIP_TRY(ctx, hipEventRecord(ctx->ev_fork, main_s));   // (the chain's results are ordered in front of this layer)
-    if (!m->layers[li]->is_head) F = m->outs[li].sample;
-    rows = out_rows;
-    n_mod = rows;
-  }
-  if (!join_early && kl_join) HIP_TRY(ctx, hipStreamWaitEvent(main_s, m->ev_kl[bank], 0));   // join the side stream
-  *rows_last = rows;
-  return DCGP_OK;
+  m->gkl_prep_wait = (m->gkl_state && p.mark == ForkMark::BehindFirstLayer && p.chain_beside()) ? nl : 0;
+  return enqueue_layers(m, p, in, early0, head_swept, kl_join, scal, rows_last);
 }
 
 // The end of a step's data path on its main stream: `ev` (already recorded there, behind the step's last command) frees the
@@ -779,35 +800,28 @@ int elbo_forward_collect_impl(dcgp_model* model, uint64_t ticket, double* out_ho
   // that word instead of waiting for the event behind the kernel -- the event's signal is another packet for the command processor and a
   // wake-up through the runtime, several microseconds on a step of 150-800.  The event is still consulted now and then: a failed launch
   // or a lost device must end the wait.
-  {
-    const volatile double* hv = model->h_ring + 8 * slot;
-    const double want = (double)(ticket + 1);
-    const bool use_event = ctx->opt.sync_event != 0;   // A/B switch: the event wait this replaced
-    if (use_event) {
-      HIP_TRY(ctx, hipEventSynchronize(model->ring_ev[slot]));
-    } else {
-      // bounded spin: a step of this path is 0.15-0.8 ms; one that has not answered after ~65 000 polls (a millisecond or two: the
-      // large configurations, a rank waiting for a slower peer's all-reduce) hands the core back and blocks on the event instead --
-      // eight ranks of a node must not hold eight cores against RCCL's proxy threads
-      for (unsigned spins = 1; hv[4] != want; ++spins) {
+  const volatile double* hv = model->h_ring + 8 * slot;
+  const double want = (double)(ticket + 1);
+  // bounded spin: a step of this path is 0.15-0.8 ms; one that has not answered after ~65 000 polls (a millisecond or two: the
+  // large configurations, a rank waiting for a slower peer's all-reduce) hands the core back and blocks on the event instead --
+  // eight ranks of a node must not hold eight cores against RCCL's proxy threads
+  for (unsigned spins = 1; hv[4] != want; ++spins) {
 #if defined(__x86_64__) || defined(__i386__)
-        __builtin_ia32_pause();
+    __builtin_ia32_pause();
 #elif defined(__aarch64__)
-        asm volatile("yield");
+    asm volatile("yield");
 #endif
-        if ((spins & 0xfff) == 0) {
-          const hipError_t q = hipEventQuery(model->ring_ev[slot]);
-          if (q == hipSuccess) break;                       // complete: coherent host memory already holds the words
-          if (q != hipErrorNotReady) { HIP_TRY(ctx, q); }
-          if (spins >= (1u << 16)) {
-            HIP_TRY(ctx, hipEventSynchronize(model->ring_ev[slot]));
-            break;
-          }
-        }
+    if ((spins & 0xfff) == 0) {
+      const hipError_t q = hipEventQuery(model->ring_ev[slot]);
+      if (q == hipSuccess) break;                       // complete: coherent host memory already holds the words
+      if (q != hipErrorNotReady) { HIP_TRY(ctx, q); }
+      if (spins >= (1u << 16)) {
+        HIP_TRY(ctx, hipEventSynchronize(model->ring_ev[slot]));
+        break;
       }
-      __atomic_thread_fence(__ATOMIC_ACQUIRE);
     }
   }
+  __atomic_thread_fence(__ATOMIC_ACQUIRE);
   ++model->col_seq;
   const double* h = model->h_ring + 8 * slot;
   out_host[0] = h[0]; out_host[1] = h[1]; out_host[2] = h[2];
