@@ -1,4 +1,5 @@
-"""Test helper: model specs at M > 256 whose EVERY gradient group is live, and the measures the large-M gradient tests share.
+"""Test helper: model specs whose EVERY gradient group is live (CASES: M > 256, CASES_M256: M <= 256 and the model variants), and the measures
+the entry-wise gradient tests share.
 
 ``syn.make_config`` is right for timing and for the forward, but its deep specs are degenerate for gradients: the inducing patches of a deeper
 layer are cut from images pushed through the identity convolution, which SUMS the input channels (10 equal maps: values 10 x the image, 30 x at
@@ -11,7 +12,8 @@ patches and edits the dicts:
 * q_mu scaled by ``a``; conv q_sqrt = 0.3 * chol(K_uu) at the NEW lengthscale (identity when whitened), the head's chol(K_uu);
 * head patch weights 0.5 + U(0, 1).
 
-Used by tests/test_host_grad_large_m.py (liveness of the torch reference, no GPU) and tests/test_gpu_grad_large_m.py."""
+Used by tests/test_host_grad_large_m.py and tests/test_host_grad_m256.py (liveness of the torch reference, no GPU) and by
+tests/test_gpu_grad_large_m.py and tests/test_gpu_grad_m256.py."""
 import numpy as np
 
 from deepcgp_amd import synthetic as syn
@@ -34,25 +36,58 @@ CASES = {
     "ch_M384": dict(hwc=(28, 28, 1), convs=[(5, 2, 10)], head=(5, 1), M=384, N=4, c=1.0, a=0.1),
 }
 
+# The M <= 256 route (tests/test_host_grad_m256.py, tests/test_gpu_grad_m256.py).  Kept apart: the large-M host test asserts M > 256 on every
+# entry of CASES.  S = 2 unless a case says otherwise: the two ch cases run S = 4, 15 x 4 x 144 = 8640 columns in the conv layer, past the 4096
+# of the strip kernel and the 8192 of syrk_kscale_kernel.  The last three are the model variants (`head_kernel`, `additive`, `conv2d_mean`).
+_MNIST, _MNIST3, _SMALL3 = dict(hwc=(28, 28, 1), head=(5, 1)), [(4, 2, 10), (5, 1, 10)], [(3, 1, 3), (4, 2, 2)]
+CASES_M256 = {
+    "ch_M256": dict(_MNIST, convs=[(5, 2, 10)], M=256, N=15, c=1.0, a=0.1, S=4),
+    "ch_M200": dict(_MNIST, convs=[(5, 2, 10)], M=200, N=15, c=1.0, a=0.1, S=4),
+    "ch_white_M256": dict(_MNIST, convs=[(5, 2, 10)], M=256, N=15, c=1.0, a=0.1, white=True),
+    "h_M256": dict(_MNIST, convs=[], M=256, N=8, c=0.5, a=0.3),
+    "mnist3_M256": dict(_MNIST, convs=_MNIST3, M=256, N=3, c=1.0, a=0.1),
+    "mnist3_M72": dict(_MNIST, convs=_MNIST3, M=72, N=3, c=1.0, a=0.1),
+    "small3_M20": dict(hwc=(14, 14, 1), convs=_SMALL3, head=(3, 1), M=20, N=3, c=1.0, a=0.1),
+    "small3_white_M20": dict(hwc=(14, 14, 1), convs=_SMALL3, head=(3, 1), M=20, N=3, c=1.0, a=0.1, white=True),
+    "odd_M33": dict(hwc=(13, 13, 2), convs=[(4, 3, 13)], head=(2, 1), M=33, N=5, c=1.0, a=0.1),
+    "additive_M24": dict(hwc=(12, 12, 1), convs=[(3, 1, 3)], head=(3, 1), M=24, N=3, c=1.0, a=0.1, additive=True),
+    "dense_ard_M24": dict(hwc=(12, 12, 1), convs=[(3, 1, 3)], head=(3, 1), M=24, N=3, c=1.0, a=0.1, head_kernel="rbf"),
+    "conv2d_mean_M24": dict(hwc=(12, 12, 1), convs=[(3, 1, 3)], head=(3, 1), M=24, N=3, c=1.0, a=0.1, conv2d_mean=True),
+}
 
-def live_spec(hwc, convs, head, M, c, a, S=2, seed=7, white=False, num_data=60000, conv_q_sqrt_scale=0.3):
-    spec = syn.make_spec(hwc, convs, head, M, S=S, num_data=num_data, seed=seed, white=white, conv_q_sqrt_scale=conv_q_sqrt_scale)
+
+def live_spec(hwc, convs, head, M, c, a, S=2, seed=7, white=False, num_data=60000, conv_q_sqrt_scale=0.3, head_kernel="conv", additive=False,
+              conv2d_mean=False):
+    """``head_kernel="rbf"``: the dense RBF(ARD) head, its lengthscales make_spec's 0.8 - 1.2 spread around c * rms_i |Z_i|; ``additive``: the
+    AdditivePatchKernel head; ``conv2d_mean``: Conv2dMean on every conv layer (odd filters)."""
+    spec = syn.make_spec(hwc, convs, head, M, S=S, num_data=num_data, seed=seed, white=white, conv_q_sqrt_scale=conv_q_sqrt_scale,
+                         head_kernel=head_kernel)
     rng = np.random.default_rng(seed)
     layers = spec["convs"] + [spec["head"]]
     for li, l in enumerate(layers):
         Z = np.asarray(l["Z"], np.float64)
+        ls_old = l["ls"]
         l["ls"] = float(c * np.sqrt(np.mean(np.sum(Z * Z, 1))))
         l["q_mu"] = a * np.asarray(l["q_mu"], np.float64)
+        if "ls_ard" in l:
+            l["ls_ard"] = np.asarray(l["ls_ard"], np.float64) * (l["ls"] / ls_old)
         if not white:
-            Lu = np.linalg.cholesky(syn._rbf(Z, Z, l["variance"], l["ls"]) + syn.JITTER * np.eye(M))
+            Ku = syn._rbf(Z / l["ls_ard"], Z / l["ls_ard"], l["variance"], 1.0) if "ls_ard" in l else syn._rbf(Z, Z, l["variance"], l["ls"])
+            Lu = np.linalg.cholesky(Ku + syn.JITTER * np.eye(M))
             l["q_sqrt"] = np.tile(Lu[None], [l["R"], 1, 1]) * (1.0 if l is spec["head"] else conv_q_sqrt_scale)
-    spec["head"]["w"] = 0.5 + rng.random(spec["head"]["w"].shape)
+    if head_kernel != "rbf":
+        spec["head"]["w"] = 0.5 + rng.random(spec["head"]["w"].shape)
+    if additive:
+        spec["head"]["kernel"] = "add"
+    if conv2d_mean:
+        for l in spec["convs"]:
+            l["mean_function"] = "conv2d"
     return spec
 
 
 def make_case(name):
-    """(spec, X, Y, zs) of CASES[name]."""
-    k = dict(CASES[name])
+    """(spec, X, Y, zs) of CASES[name] or CASES_M256[name]."""
+    k = dict(CASES[name] if name in CASES else CASES_M256[name])
     N = k.pop("N")
     spec = live_spec(**k)
     X, Y = syn.make_batch(k["hwc"], N, seed=7)
