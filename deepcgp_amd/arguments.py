@@ -21,7 +21,7 @@ FLAGS = (
     ("--feature-maps", str, "10", "outputs of each conv layer, comma separated ('' with a head-only model)"),
     ("--filter-sizes", str, "5,5", "patch size of each layer incl. the head"),
     ("--strides", str, "2,1", "patch stride of each layer incl. the head"),
-    ("--base-kernel", str, "rbf", "base kernel of the conv layers: rbf | acos"),
+    ("--base-kernel", str, "rbf", "base kernel of the conv layers: rbf | acos | matern32 | matern52"),
     ("--white", None, False, "whitened variational parameters"),
     ("--last-kernel", str, "conv", "head kernel: conv | add | rbf"),
     ("--gamma", float, 0.001, "NatGrad step size"),

@@ -299,12 +299,22 @@ const double* exp2_table(struct dcgp_ctx* ctx);   // device: 2^(j / 256), j < 25
 //   type 1  gpflow ArcCosine(0):  variance * (pi - theta) / pi,  theta = acos(1e-15 + (1 - 2e-15) cos),
 //           cos = (w x.z + b) / sqrt((w |x|^2 + b)(w |z|^2 + b)), argument clamped to <= 1    p1 = w (weight variance), p2 = b (bias variance)
 //   (conv_gp/models.py:113-121: --base-kernel rbf | acos; Kdiag = variance for both)
+//   type 2  gpflow Matern32:      variance * (1 + a) exp(-a),            a = sqrt(3 rho)      p1 = 1 / l^2
+//   type 3  gpflow Matern52:      variance * (1 + a + a^2 / 3) exp(-a),  a = sqrt(5 rho)
+//           rho = max(|x|^2 + |z|^2 - 2 x.z, 0) / l^2 + 1e-12 (gpflow's scaled_euclid_dist; the max: rounding can take the raw
+//           difference of norms and product below zero).  Kdiag = variance (Stationary.Kdiag)
 struct BaseKernel {
   int type = 0;
   double variance = 1.0, p1 = 1.0, p2 = 0.0;
-  template <int T>   // the hot sweeps are instantiated per type: the acos code must not cost the RBF path registers
+  template <int T>   // the hot sweeps are instantiated per type: the acos / Matern code must not cost the RBF path registers
   __device__ __forceinline__ double eval_as(double dot, double n1, double n2) const {
     if (T == 0) return variance * exp_sweep(-0.5 * (n1 + n2 - 2.0 * dot) * p1);
+    if (T == 2 || T == 3) {
+      // sqrt: v_rsq_f64 and two refinement steps, exp_sweep: range reduction and 14 fused multiply-adds -- ~45 VALU instructions a value
+      const double a = sqrt((T == 2 ? 3.0 : 5.0) * fma(fmax(n1 + n2 - 2.0 * dot, 0.0), p1, 1e-12));
+      const double poly = T == 2 ? 1.0 + a : fma(a, fma(a, 1.0 / 3.0, 1.0), 1.0);
+      return variance * poly * exp_sweep(-a);
+    }
     const double c = (p1 * dot + p2) / sqrt((p1 * n1 + p2) * (p1 * n2 + p2));
     // fmin: on a diagonal entry cos can round a few ulp above 1 (dot and norms are accumulated in different orders)
     // and overshoot the reference's 1e-15 guard -- acos() would return NaN there, as the reference formula does
@@ -321,7 +331,7 @@ struct BaseKernel {
     for (int i = 0; i < N; ++i) io[i] = eval_as<T>(io[i], n1[i], n2[i]);
   }
   __device__ __forceinline__ double eval(double dot, double n1, double n2) const {
-    return type == 0 ? eval_as<0>(dot, n1, n2) : eval_as<1>(dot, n1, n2);
+    return type == 0 ? eval_as<0>(dot, n1, n2) : type == 1 ? eval_as<1>(dot, n1, n2) : type == 2 ? eval_as<2>(dot, n1, n2) : eval_as<3>(dot, n1, n2);
   }
 };
 

@@ -68,10 +68,11 @@ __device__ __forceinline__ int frag_of(int w, int W, int c) { return (c >> 1) * 
 // 64-column strip: the fp64 MFMA pipe reaches 92 % of its rate from two waves per SIMD and 98 % from four.
 // MAXF: row fragments per wave at most.  ABL: timing experiments only (wrong results): 1 = second product without its
 // A-operand loads, 2 = without the LDS reads of the B operand, 4 = two more A tiles in flight.
-// BTP: 0 RBF, 1 ArcCosine, 2 RBF on 5 x 5 x 10 patches (the in-kernel sweep walks patch rows; an instance of its own so that the others do not carry its registers)
+// BTP: 0 RBF, 1 ArcCosine, 2 RBF on 5 x 5 x 10 patches (the in-kernel sweep walks patch rows; an instance of its own so that the others do not carry its registers),
+// 3 Matern32, 4 Matern52 (ArcCosine's route: raw dot products, the norms applied after the sweep)
 template <int FN, int NS, int MAXF, int NT, int BTP, int ABL = 0>
 __global__ __launch_bounds__(NT) void conv_fused_kernel(ConvFusedArgs a_in) {
-  constexpr int BT = BTP == 1 ? 1 : 0;
+  constexpr int BT = BTP == 1 ? 1 : (BTP == 3 ? 2 : (BTP == 4 ? 3 : 0));   // BaseKernel type
   // The arguments are read through the kernarg pointer, which every strip of a persistent workgroup sees as a new value: as a by-value
   // struct the loop-invariant loads of all ~70 words are hoisted out of the strip loop, live across it, and spill (240 VGPRs at 16 waves)
   typedef const __attribute__((address_space(4))) ConvFusedArgs KArgs;
@@ -230,7 +231,7 @@ __global__ __launch_bounds__(NT) void conv_fused_kernel(ConvFusedArgs a_in) {
     const int oh = fdiv(p, a.Wo, a.inv_Wo), ow = p - oh * a.Wo;
     return (n - n_first) * a.HWC + (oh * a.s * a.W + ow * a.s) * a.C;
   };
-  // acos: |z_m|^2 of this lane's accumulator rows: fetched here, needed after the sweep (RBF: the norms ride in the product)
+  // acos, Matern: |z_m|^2 of this lane's accumulator rows: fetched here, needed after the sweep (RBF: the norms ride in the product)
   double znv[BT == 0 ? 1 : MAXF][4];
   if (BT != 0) {
 #pragma unroll
@@ -818,6 +819,8 @@ int launch_fused(dcgp_ctx* ctx, const ConvFusedArgs& a, size_t lds) {
   if (!attr_done[dv]) {   // more than 64 KB of dynamic LDS needs the opt-in
     hipFuncSetAttribute((const void*)conv_fused_kernel<FN, NS, MAXF, NT, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     hipFuncSetAttribute((const void*)conv_fused_kernel<FN, NS, MAXF, NT, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipFuncSetAttribute((const void*)conv_fused_kernel<FN, NS, MAXF, NT, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipFuncSetAttribute((const void*)conv_fused_kernel<FN, NS, MAXF, NT, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr_done[dv] = true;
   }
   const bool rows50 = a.bk.type == 0 && a.f * a.C == 50 && (a.f & 1) && a.L == a.f * a.f * a.C && a.Lz == ((a.L + 2 + 3) & ~3) && !a.no_rows;
@@ -834,7 +837,10 @@ int launch_fused(dcgp_ctx* ctx, const ConvFusedArgs& a, size_t lds) {
     }
   }
   if (a.bk.type == 0) hipLaunchKernelGGL((conv_fused_kernel<FN, NS, MAXF, NT, 0>), dim3(grid), dim3(NT), lds, ctx->stream, a);
-  else hipLaunchKernelGGL((conv_fused_kernel<FN, NS, MAXF, NT, 1>), dim3(grid), dim3(NT), lds, ctx->stream, a);
+  else if (a.bk.type == 1) hipLaunchKernelGGL((conv_fused_kernel<FN, NS, MAXF, NT, 1>), dim3(grid), dim3(NT), lds, ctx->stream, a);
+  else if (a.bk.type == 2) hipLaunchKernelGGL((conv_fused_kernel<FN, NS, MAXF, NT, 3>), dim3(grid), dim3(NT), lds, ctx->stream, a);
+  else if (a.bk.type == 3) hipLaunchKernelGGL((conv_fused_kernel<FN, NS, MAXF, NT, 4>), dim3(grid), dim3(NT), lds, ctx->stream, a);
+  else return ctx_fail(ctx, DCGP_ERR_ARG, "conv_fused: unknown base kernel type %d", a.bk.type);
   LAUNCH_CHECK(ctx);
   return DCGP_OK;
 }

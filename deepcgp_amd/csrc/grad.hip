@@ -197,9 +197,20 @@ __global__ void kl_diag_kernel(double* __restrict__ gq, const double* __restrict
   gq[((long)r * M + i) * M + i] += kw / Lq[((long)r * Mp + i) * Mp + i];
 }
 
+// Matern32 (BT == 2) / Matern52 (BT == 3) at rho = r^2 + 1e-12: the value k and g = -2 dk/drho = 3 variance exp(-a) | (5 / 3) variance (1 + a) exp(-a),
+// a = sqrt(3 rho) | sqrt(5 rho).  Finite at r = 0.
+template <int BT>
+__device__ __forceinline__ void matern_k_g(double rho, double variance, double* k, double* g) {
+  const double a = sqrt((BT == 2 ? 3.0 : 5.0) * rho), e = variance * exp(-a);
+  if (BT == 2) { *k = (1.0 + a) * e; *g = 3.0 * e; }
+  else { *k = fma(a, fma(a, 1.0 / 3.0, 1.0), 1.0) * e; *g = (5.0 / 3.0) * (1.0 + a) * e; }
+}
 // ---- RBF Gram backward ------------------------------------------------------------------------------------------
 // One block per row i.  S = d ELBO / dK (not symmetrised).  Writes Es[i][j] = (S_ij + S_ji) k_ij (or nothing if Es is
 // null), rs[i] = sum_j Es[i][j], and the per-row partial sums pv[i] = sum_j S_ij k_ij / variance, pl[i] = sum_j S_ij k_ij d_ij^2 / l^3.
+// BT: 0 RBF; 2 / 3 Matern32 / Matern52, which are functions of rho = d^2 / l^2 + 1e-12 like the RBF (dk/drho = -k / 2 there): their g = -2 dk/drho takes
+// the place of k in E, so that dZ and the lengthscale sum keep their form; the variance sum stays sum(S o K) / variance
+template <int BT>
 __global__ __launch_bounds__(256) void kuu_backward_kernel(const double* __restrict__ Z, const double* __restrict__ ZT, int ldzt, int M, int L,
                                                            const double* __restrict__ S, long lds,
                                                            double variance, double inv_l2, double inv_l3, double* __restrict__ Es, long lde,
@@ -220,12 +231,18 @@ __global__ __launch_bounds__(256) void kuu_backward_kernel(const double* __restr
         d2 += d * d;
       }
     }
-    const double k = variance * exp(-0.5 * d2 * inv_l2);
-    const double e = S[i * lds + j] * k;
-    sv += e;
+    double k, g;
+    if constexpr (BT == 0) {
+      k = variance * exp(-0.5 * d2 * inv_l2);
+      g = k;
+    } else {
+      matern_k_g<BT>(fma(d2, inv_l2, 1e-12), variance, &k, &g);
+    }
+    const double e = S[i * lds + j] * g;
+    sv += BT == 0 ? e : S[i * lds + j] * k;
     sl += e * d2;
     if (Es) {
-      const double es = e + S[j * lds + i] * k;
+      const double es = e + S[j * lds + i] * g;
       Es[i * lde + j] = es;
       srow += es;
     }
@@ -491,6 +508,39 @@ __global__ __launch_bounds__(256) void acos_e_form_kernel(const double* __restri
 __global__ void acos_divide_kernel(double* __restrict__ v, const double* __restrict__ n, int M, double w, double b) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < M) v[i] /= (w * n[i] + b);
+}
+// Matern K_uf adjoint, one thread per column c and row chunk (blockIdx.y).  In: E[m][c] = z_m . x_c (a product of Z and Xcol).  Out: E = dK o g with
+// g = -2 dk/drho at rho = max(|z|^2 + |x|^2 - 2 z.x, 0) / l^2 + 1e-12, the forward pass's own argument; csp[chunk][c] = sum_m E, block partials
+// pv = sum dK o K (K as the forward pass stored it) and pl = sum E d^2: what e_form_kernel leaves for the RBF
+template <int BT>
+__global__ __launch_bounds__(256) void matern_e_form_kernel(const double* __restrict__ dK, double* __restrict__ E, long ld, const double* __restrict__ K,
+                                                            int M, int rows_per_chunk, long Kc, double variance, double inv_l2,
+                                                            const double* __restrict__ zn, const double* __restrict__ xn, double* __restrict__ csp,
+                                                            double* __restrict__ pv, double* __restrict__ pl) {
+  __shared__ double red[256];
+  const long c = (long)blockIdx.x * 256 + threadIdx.x;
+  const int m0 = blockIdx.y * rows_per_chunk, m1 = min(M, m0 + rows_per_chunk);
+  double sv = 0.0, sl = 0.0, sc = 0.0;
+  if (c < Kc) {
+    const double a2 = xn[c];
+    for (int m = m0; m < m1; ++m) {
+      const double dk = dK[m * ld + c];
+      const double d2 = fmax(zn[m] + a2 - 2.0 * E[m * ld + c], 0.0);
+      double k, g;
+      matern_k_g<BT>(fma(d2, inv_l2, 1e-12), variance, &k, &g);
+      const double e = dk * g;
+      E[m * ld + c] = e;
+      sv += dk * K[m * ld + c];
+      sl += e * d2;
+      sc += e;
+    }
+    csp[(long)blockIdx.y * Kc + c] = sc;
+  }
+  const double a = block_sum_256(sv, red), b = block_sum_256(sl, red);
+  if (threadIdx.x == 0) {
+    const long o = (long)blockIdx.y * gridDim.x + blockIdx.x;
+    pv[o] = a; pl[o] = b;
+  }
 }
 // Gram adjoint, one block per row i (both arguments are Z; the diagonal is skipped): Es[i][j] = (F_ij + F_ji) / sqrt(Q_i Q_j),
 // rs[i] = sum_j (F_ij + F_ji) c_ij / Q_i, partials pv (variance), pw, pb
@@ -780,7 +830,8 @@ int kuu_backward(Bk& bk, LayerState& L, const double* Zsrc, const double* S, lon
     LAUNCH_CHECK(ctx);
     cz = L.acos_w;
   } else {
-    hipLaunchKernelGGL(kuu_backward_kernel, dim3(M), dim3(256), 0, ctx->stream, Zsrc, Zsrc == L.Z ? L.ZT : nullptr, L.Mp, M, Ld, S, lds, L.variance,
+    auto kern = L.base_type == 0 ? kuu_backward_kernel<0> : (L.base_type == 2 ? kuu_backward_kernel<2> : kuu_backward_kernel<3>);
+    hipLaunchKernelGGL(kern, dim3(M), dim3(256), 0, ctx->stream, Zsrc, Zsrc == L.Z ? L.ZT : nullptr, L.Mp, M, Ld, S, lds, L.variance,
                        inv_l2, inv_l3, Es, (long)M, rs, pv, pl);
     LAUNCH_CHECK(ctx);
   }
@@ -1288,6 +1339,28 @@ int conv_backward(Bk& bk, LayerState& L, const double* Xin, int rows, int n_mod,
       LAUNCH_CHECK(ctx);
     }
     DCGP_TRY(patch_backward(bk, L, E, ld, Kc, cs, Xcol, dXcol, 0, nullptr, nullptr, rs2, L.acos_w));
+  } else if (L.base_type == 2 || L.base_type == 3) {   // Matern32 / Matern52: E = dK o (-2 dk/drho), then the RBF machinery as it is
+    const unsigned nb = blocks_for(Kc);
+    int chunks = (int)std::min<long>(16, std::max<long>(1, 2048 / nb));
+    chunks = std::min(chunks, (M + 15) / 16);
+    const int rpc = (M + chunks - 1) / chunks;
+    chunks = (M + rpc - 1) / rpc;
+    double* xn = bk.ws("mat_xn", Kc);
+    double* csp = bk.ws("ef_csp", (size_t)chunks * Kc);
+    double* pv = bk.ws("ef_pv", (size_t)nb * chunks);
+    double* pl = bk.ws("ef_pl", (size_t)nb * chunks);
+    NEED(xn); NEED(csp); NEED(pv); NEED(pl);
+    hipLaunchKernelGGL(rownorm_kernel, dim3(blocks_for(Kc)), dim3(256), 0, ctx->stream, Xcol, Kc, Ld, xn);
+    LAUNCH_CHECK(ctx);
+    DCGP_TRY(gemm_gen(ctx, mk(L.Z, Ld, 1, Xcol, 1, Ld, E, ld, M, (int)Kc, Ld)));   // z_m . x_c
+    const double inv_l2 = 1.0 / (L.ls * L.ls);
+    hipLaunchKernelGGL(L.base_type == 2 ? matern_e_form_kernel<2> : matern_e_form_kernel<3>, dim3(nb, chunks), dim3(256), 0, ctx->stream, dKuf, E, ld, Kuf,
+                       M, rpc, Kc, L.variance, inv_l2, L.zn, xn, csp, pv, pl);
+    LAUNCH_CHECK(ctx);
+    hipLaunchKernelGGL(sum_chunks_kernel, dim3(blocks_for(Kc)), dim3(256), 0, ctx->stream, csp, chunks, Kc, cs);
+    LAUNCH_CHECK(ctx);
+    DCGP_TRY(add_scalars(bk, L, {{0, pv, (long)nb * chunks, 1.0 / L.variance}, {1, pl, (long)nb * chunks, inv_l2 / L.ls}}));
+    DCGP_TRY(patch_backward(bk, L, E, ld, Kc, cs, Xcol, dXcol, 0));
   } else {
     DCGP_TRY(e_form(bk, L, dKuf, ld, 1, nullptr, 1.0, Kuf, ld, E, ld, Kc, cs, nullptr));
     DCGP_TRY(patch_backward(bk, L, E, ld, Kc, cs, Xcol, dXcol, 0));

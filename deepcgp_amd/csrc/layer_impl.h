@@ -22,12 +22,13 @@ struct LayerState {
   int M = 0, Mp = 0, R = 0, Lp = 0;
   int white = 0, identity_mean = 0, kernel_type = 0;
   double variance = 1.0, ls = 1.0;
-  int base_type = 0;             // 0: RBF(variance, ls); 1: ArcCosine order 0 (variance, weight variance = acos_w, bias variance = acos_b)
+  int base_type = 0;             // 0: RBF(variance, ls); 1: ArcCosine order 0 (variance, weight variance = acos_w, bias variance = acos_b);
+                                 // 2 / 3: Matern32 / Matern52 (variance, ls)
   double acos_w = 1.0, acos_b = 1.0;
   BaseKernel base() const {
     BaseKernel b;
     b.type = base_type; b.variance = variance;
-    if (base_type == 0) { b.p1 = 1.0 / (ls * ls); b.p2 = 0.0; } else { b.p1 = acos_w; b.p2 = acos_b; }
+    if (base_type != 1) { b.p1 = 1.0 / (ls * ls); b.p2 = 0.0; } else { b.p1 = acos_w; b.p2 = acos_b; }
     return b;
   }
   bool has_qsqrt = true;

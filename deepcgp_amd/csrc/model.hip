@@ -618,14 +618,15 @@ int dcgp_model_set_param(dcgp_model* model, int layer, const char* which, const 
     DCGP_TRY(L.upload(L.ard, value_host, count));
     return L.upload(L.in_scale, inv.data(), count);
   }
-  if (!strcmp(which, "base_kernel")) {   // {type, variance, p1, p2}: 0 = RBF (p1 = lengthscale), 1 = ArcCosine order 0 (p1 = weight, p2 = bias variance)
+  if (!strcmp(which, "base_kernel")) {   // {type, variance, p1, p2}: 0 = RBF (p1 = lengthscale), 1 = ArcCosine order 0 (p1 = weight, p2 = bias variance),
+                                         // 2 = Matern32, 3 = Matern52 (p1 = lengthscale)
     DCGP_TRY(expect(4));
     const int type = (int)value_host[0];
-    if ((type != 0 && type != 1) || !(value_host[1] > 0) || !(value_host[2] > 0) || (type == 1 && !(value_host[3] >= 0)))
+    if (type < 0 || type > 3 || (double)type != value_host[0] || !(value_host[1] > 0) || !(value_host[2] > 0) || (type == 1 && !(value_host[3] >= 0)))
       return ctx_fail(ctx, DCGP_ERR_ARG, "set_param(base_kernel): bad kernel description");
-    if (type == 1 && L.is_head) return ctx_fail(ctx, DCGP_ERR_ARG, "set_param(base_kernel): the head kernels are RBF-based (conv_gp/models.py:160-187)");
+    if (type != 0 && L.is_head) return ctx_fail(ctx, DCGP_ERR_ARG, "set_param(base_kernel): the head kernels are RBF-based (conv_gp/models.py:160-187)");
     L.base_type = type; L.variance = value_host[1];
-    if (type == 0) L.ls = value_host[2]; else { L.acos_w = value_host[2]; L.acos_b = value_host[3]; }
+    if (type != 1) L.ls = value_host[2]; else { L.acos_w = value_host[2]; L.acos_b = value_host[3]; }
     return DCGP_OK;
   }
   return ctx_fail(ctx, DCGP_ERR_ARG, "set_param: unknown parameter '%s'", which);

@@ -132,6 +132,11 @@ static BaseKernel acos_bk(double variance, double weight_variance, double bias_v
   b.type = 1; b.variance = variance; b.p1 = weight_variance; b.p2 = bias_variance;
   return b;
 }
+static BaseKernel matern_bk(int nu2, double variance, double lengthscale) {
+  BaseKernel b;
+  b.type = nu2 == 3 ? 2 : 3; b.variance = variance; b.p1 = 1.0 / (lengthscale * lengthscale); b.p2 = 0.0;
+  return b;
+}
 static int kuu_impl(dcgp_ctx* ctx, const double* Z, int M, int L, BaseKernel bk, double jitter, double* out_MM) {
   DCGP_TRY(rbf_gram_padded(ctx, Z, M, L, bk, jitter, out_MM, M, M));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -166,6 +171,21 @@ int dcgp_kuf_patches_acos(dcgp_ctx* ctx, const double* X, int N, int H, int W, i
                 weight_variance > 0 && bias_variance >= 0 && (layout == 0 || layout == 1),
             "kuf_patches_acos: bad args");
   return kuf_impl(ctx, X, N, H, W, C, f, stride, Z, M, acos_bk(variance, weight_variance, bias_variance), out, layout);
+}
+
+// gpflow.kernels.Matern32 (nu2 = 3) / Matern52 (nu2 = 5), ARD = False
+int dcgp_kuu_matern(dcgp_ctx* ctx, const double* Z, int M, int L, int nu2, double variance, double lengthscale, double jitter,
+                    double* out_MM) {
+  ARG_CHECK(ctx && Z && out_MM && M > 0 && L > 0 && (nu2 == 3 || nu2 == 5) && variance > 0 && lengthscale > 0, "kuu_matern: bad args");
+  return kuu_impl(ctx, Z, M, L, matern_bk(nu2, variance, lengthscale), jitter, out_MM);
+}
+
+int dcgp_kuf_patches_matern(dcgp_ctx* ctx, const double* X, int N, int H, int W, int C, int f, int stride, const double* Z,
+                            int M, int nu2, double variance, double lengthscale, double* out, int layout) {
+  ARG_CHECK(ctx && X && Z && out && N > 0 && M > 0 && f > 0 && stride > 0 && f <= H && f <= W && C > 0 && (nu2 == 3 || nu2 == 5) &&
+                variance > 0 && lengthscale > 0 && (layout == 0 || layout == 1),
+            "kuf_patches_matern: bad args");
+  return kuf_impl(ctx, X, N, H, W, C, f, stride, Z, M, matern_bk(nu2, variance, lengthscale), out, layout);
 }
 
 static int kuf_impl(dcgp_ctx* ctx, const double* X, int N, int H, int W, int C, int f, int stride, const double* Z, int M,

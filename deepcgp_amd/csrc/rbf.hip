@@ -583,7 +583,10 @@ int patch_rbf(dcgp_ctx* ctx, const PatchRbfArgs& a, const char* timer_name) {
   dim3 grid(a.reduce ? 1 : p_tiles, (a.Mp + PR_BM - 1) / PR_BM, a.N);
   ScopedTimer t(ctx, timer_name);
   if (a.bk.type == 0) hipLaunchKernelGGL(patch_rbf_kernel<0>, grid, dim3(256), lds, ctx->stream, a);
-  else hipLaunchKernelGGL(patch_rbf_kernel<1>, grid, dim3(256), lds, ctx->stream, a);
+  else if (a.bk.type == 1) hipLaunchKernelGGL(patch_rbf_kernel<1>, grid, dim3(256), lds, ctx->stream, a);
+  else if (a.bk.type == 2) hipLaunchKernelGGL(patch_rbf_kernel<2>, grid, dim3(256), lds, ctx->stream, a);
+  else if (a.bk.type == 3) hipLaunchKernelGGL(patch_rbf_kernel<3>, grid, dim3(256), lds, ctx->stream, a);
+  else return ctx_fail(ctx, DCGP_ERR_ARG, "patch_rbf: unknown base kernel type %d", a.bk.type);
   LAUNCH_CHECK(ctx);
   return DCGP_OK;
 }
@@ -607,6 +610,7 @@ int head_kdiag(dcgp_ctx* ctx, const double* X, int N, int n_mod, int H, int W, i
   KdiagArgs k;
   size_t lds = 0;
   DCGP_TRY(kdiag_args(ctx, X, N, n_mod, H, W, C, f, s, bk, w, &k, &lds));
+  if (bk.type != 0 && bk.type != 1) return ctx_fail(ctx, DCGP_ERR_ARG, "head_kdiag: the head kernels are RBF-based");
   ScopedTimer t(ctx, "head_kdiag");
   if (bk.type == 0) hipLaunchKernelGGL(head_kdiag_kernel<0>, dim3(k.n_pairs, N), dim3(256), lds, ctx->stream, k);
   else hipLaunchKernelGGL(head_kdiag_kernel<1>, dim3(k.n_pairs, N), dim3(256), lds, ctx->stream, k);

@@ -120,6 +120,62 @@ class ArcCosine:
                                                    self.weight_variances, self.bias_variance, out.ptr, layout))
 
 
+class _Matern:
+    """gpflow Stationary kernel with ARD=False in the Matern family: k is a function of
+    r = sqrt(|x - z|^2 / lengthscales^2 + 1e-12) (gpflow's scaled_euclid_dist); Kdiag = variance.  A base kernel of the conv layers
+    (``--base-kernel matern32 | matern52``); the heads stay RBF-based."""
+
+    nu2 = None      # 2 nu: 3 or 5
+    _type = None    # dcgp_model_set_param's base-kernel type
+
+    def __init__(self, input_dim, variance=1.0, lengthscales=1.0, ARD=False):
+        if ARD:
+            raise NotImplementedError("%s: only ARD=False (one lengthscale) is on the accelerated path" % type(self).__name__)
+        if np.ndim(lengthscales) != 0:
+            raise ValueError("lengthscales must be a scalar")
+        self.input_dim = int(input_dim)
+        self.variance = float(variance)
+        self.lengthscales = float(lengthscales)
+        self.ARD = False
+        if not (self.variance > 0 and self.lengthscales > 0):
+            raise ValueError("variance and lengthscales must be positive")
+
+    def K(self, X, X2=None):
+        if X2 is not None:
+            raise NotImplementedError("cross-covariances are evaluated by the fused patch kernels")
+        return self._gram(X, 0.0)
+
+    def _gram(self, Z, jitter):
+        ctx = dev.get_context()
+        Z = np.ascontiguousarray(Z, np.float64)
+        M, L = Z.shape
+        if L != self.input_dim:
+            raise ValueError("expected inputs of length %d, got %d" % (self.input_dim, L))
+        dZ, out = ctx.to_device(Z), ctx.empty((M, M))
+        ctx._check(dev.lib().dcgp_kuu_matern(ctx.handle, dZ.ptr, M, L, self.nu2, self.variance, self.lengthscales, float(jitter), out.ptr))
+        return out.numpy()
+
+    def Kdiag(self, X):
+        return np.full(np.shape(X)[0], self.variance)
+
+    def _describe(self):
+        return [float(self._type), self.variance, self.lengthscales, 0.0]
+
+    def _kuf(self, ctx, dX, N, H, W, C, f, s, dZ, M, out, layout):
+        ctx._check(dev.lib().dcgp_kuf_patches_matern(ctx.handle, dX.ptr, N, H, W, C, f, s, dZ.ptr, M, self.nu2, self.variance,
+                                                     self.lengthscales, out.ptr, layout))
+
+
+class Matern32(_Matern):
+    """gpflow.kernels.Matern32(input_dim, variance, lengthscales): k = variance (1 + a) exp(-a), a = sqrt(3) r."""
+    nu2, _type = 3, 2
+
+
+class Matern52(_Matern):
+    """gpflow.kernels.Matern52(input_dim, variance, lengthscales): k = variance (1 + a + a^2 / 3) exp(-a), a = sqrt(5) r."""
+    nu2, _type = 5, 3
+
+
 class AdditivePatchKernel:
     """K(x, x') = mean_i w_i k(x[i], x'[i]) (conv_gp/kernels.py:15-77).  Kzx / Kdiag / Kzz serve the training path; the full
     ``K`` (prediction with full covariances) runs on the image-pair kernel of csrc/head_full.hip."""
@@ -127,6 +183,8 @@ class AdditivePatchKernel:
     kernel_type = 1
 
     def __init__(self, base_kernel, view, patch_weights=None):
+        if isinstance(base_kernel, _Matern):
+            raise NotImplementedError("the head kernels are RBF-based: Matern base kernels belong to the conv layers")
         self.base_kernel = base_kernel
         self.view = view
         self.patch_length = view.patch_length

@@ -6,7 +6,7 @@ import numpy as np
 
 from . import device as dev
 from .conditionals import conditional
-from .kernels import JITTER, Kuu as _Kuu, Kuf as _Kuf
+from .kernels import JITTER, RBF, Kuu as _Kuu, Kuf as _Kuf
 from .views import FullView
 
 
@@ -261,7 +261,7 @@ class ConvLayer(Layer):
         D = self.num_outputs
         if N == 0:
             return np.zeros((0, D)), np.zeros((0, D)), np.zeros((0, D))
-        if not hasattr(self.base_kernel, "lengthscales"):
+        if not isinstance(self.base_kernel, RBF):
             return self._forward_composed(ND_X, z)
         dX, dZ = ctx.to_device(ND_X), ctx.to_device(self.feature.Z)
         dmu, dsq = ctx.to_device(self.q_mu), ctx.to_device(self.q_sqrt)
@@ -285,7 +285,7 @@ class ConvLayer(Layer):
     def _forward_composed(self, ND_X, z):
         """conditional_ND as the reference composes it (conv_gp/layers.py:108-135) from the operator-level calls --
         Kuu, fused patches + Kuf, Kdiag, conditional -- for base kernels the one-call layer operator has no
-        signature for (ArcCosine); the model path (dcgp_elbo_forward) handles them natively."""
+        signature for (ArcCosine, Matern32, Matern52); the model path (dcgp_elbo_forward) handles them natively."""
         N = ND_X.shape[0]
         v = self.view
         X4 = ND_X.reshape(N, v.input_size[0], v.input_size[1], self.feature_maps_in)

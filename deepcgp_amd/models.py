@@ -3,7 +3,7 @@ from the neutral model spec used by the benchmarks and parity tests (deepcgp_amd
 import numpy as np
 
 from .dgp import DGP_Base
-from .kernels import RBF, ArcCosine, ConvKernel, AdditivePatchKernel, PatchInducingFeatures, InducingPoints
+from .kernels import RBF, ArcCosine, Matern32, Matern52, ConvKernel, AdditivePatchKernel, PatchInducingFeatures, InducingPoints
 from .layers import ConvLayer, SVGP_Layer
 from .likelihoods import MultiClass
 from .mean_functions import Conv2dMean, IdentityConv2dMean  # noqa: F401  (the names conv_gp/models.py:11 imports)
@@ -17,11 +17,18 @@ def parse_ints(int_string):
     return [int(i) for i in int_string.split(',')]
 
 
+# --base-kernel values (conv layers); "acos" takes gpflow's default parameters, the others (variance, lengthscales)
+BASE_KERNELS = {"rbf": RBF, "acos": ArcCosine, "matern32": Matern32, "matern52": Matern52}
+
+
 def build_layers_from_spec(spec):
     layers = []
     for c in spec["convs"]:
         view = FullView((c["H"], c["W"]), c["f"], c["C"], c["s"])
-        base = ArcCosine(view.patch_length, order=0) if c.get("base", "rbf") == "acos" else RBF(view.patch_length, c["variance"], c["ls"])
+        kind = c.get("base", "rbf")
+        if kind not in BASE_KERNELS:
+            raise ValueError("Not a valid base-kernel value")
+        base = ArcCosine(view.patch_length, order=0) if kind == "acos" else BASE_KERNELS[kind](view.patch_length, c["variance"], c["ls"])
         mf = c.get("mean_function")
         if mf == "conv2d":      # --identity-mean: Conv2dMean(filter_size, NHWC[3], feature_map, stride=stride), conv_gp/models.py:95-97
             mf = Conv2dMean(c["f"], c["C"], c["R"], stride=c["s"])
@@ -368,7 +375,7 @@ class ModelBuilder(object):
         stored = {}
         if getattr(fl, "load_model", None) is not None:
             self.global_step, stored = read_checkpoint(self.model_path, n_layers)
-        if fl.base_kernel not in ("rbf", "acos"):
+        if fl.base_kernel not in BASE_KERNELS:
             raise ValueError("Not a valid base-kernel value")
         if fl.last_kernel not in ("conv", "add", "rbf"):
             raise ValueError("Invalid last layer kernel")

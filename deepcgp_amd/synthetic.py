@@ -89,6 +89,13 @@ def _acos0(A, B, variance, wv, bv):
     return variance * (np.pi - theta) / np.pi
 
 
+def _matern(A, B, variance, ls, nu2):
+    """gpflow Matern32 (nu2 = 3) / Matern52 (nu2 = 5) Gram matrix (host helper for synthetic q_sqrt initialisation only)."""
+    d2 = np.maximum(np.sum(A * A, 1)[:, None] + np.sum(B * B, 1)[None, :] - 2.0 * (A @ B.T), 0.0) / ls ** 2
+    a = np.sqrt(nu2 * (d2 + 1e-12))
+    return variance * ((1.0 + a) if nu2 == 3 else (1.0 + a + a * a / 3.0)) * np.exp(-a)
+
+
 def make_spec(hwc, convs, head, M, S=10, num_data=60000, seed=0, white=False, q_mu_random=True,
               conv_q_sqrt_scale=1e-5, head_q_sqrt_scale=1.0, head_outputs=10, variance=5.0, ls=5.0, base_kernel="rbf", head_kernel="conv"):
     """Build a model spec (see module docstring) with seeded synthetic parameters."""
@@ -101,6 +108,8 @@ def make_spec(hwc, convs, head, M, S=10, num_data=60000, seed=0, white=False, q_
         Z = _cut_patches(rng, init_imgs, M, f)
         if base_kernel == "acos":   # conv layers only (conv_gp/models.py:113-121); gpflow defaults 1, 1, 1
             Kuu = _acos0(Z, Z, 1.0, 1.0, 1.0) + JITTER * np.eye(M)
+        elif base_kernel in ("matern32", "matern52"):
+            Kuu = _matern(Z, Z, variance, ls, 3 if base_kernel == "matern32" else 5) + JITTER * np.eye(M)
         else:
             Kuu = _rbf(Z, Z, variance, ls) + JITTER * np.eye(M)
         Lu = np.linalg.cholesky(Kuu)

@@ -93,6 +93,15 @@ int dcgp_kuu_acos(dcgp_ctx* ctx, const double* Z, int M, int L, double variance,
 int dcgp_kuf_patches_acos(dcgp_ctx* ctx, const double* X, int N, int H, int W, int C, int f, int stride,
                           const double* Z, int M, double variance, double weight_variance,
                           double bias_variance, double* out, int layout);
+/* The same two matrices for gpflow.kernels.Matern32 (nu2 = 3) and gpflow.kernels.Matern52 (nu2 = 5), ARD = False:
+ * k = variance (1 + a) exp(-a), a = sqrt(3) r, and k = variance (1 + a + a^2 / 3) exp(-a), a = sqrt(5) r, with
+ * r = sqrt(max(|x - z|^2, 0) / lengthscale^2 + 1e-12) (gpflow's scaled_euclid_dist); Kdiag = variance.  The conv layers'
+ * base kernel under --base-kernel matern32 | matern52.                                                        */
+int dcgp_kuu_matern(dcgp_ctx* ctx, const double* Z, int M, int L, int nu2, double variance, double lengthscale,
+                    double jitter, double* out_MM);
+int dcgp_kuf_patches_matern(dcgp_ctx* ctx, const double* X, int N, int H, int W, int C, int f, int stride,
+                            const double* Z, int M, int nu2, double variance, double lengthscale,
+                            double* out, int layout);
 
 /* ---- dense M x M factorisations ------------------------------------------------------------ */
 /* tf.cholesky (conv_gp/conditionals.py:29, layers.py:151,156): in place, lower factor, strict
@@ -208,7 +217,8 @@ int dcgp_model_set_head(dcgp_model* model, int H, int W, int C, int f, int strid
 int dcgp_model_set_keep_outputs(dcgp_model* model, int on);
 /* Push a changed parameter: which = "Z", "Z0", "q_mu", "q_sqrt", "w", "variance", "lengthscale", or
  * "base_kernel" = {type, variance, p1, p2}: type 0 RBF (p1 = lengthscale), type 1 ArcCosine order 0 (p1 = weight
- * variance, p2 = bias variance; conv layers only, conv_gp/models.py:113-121), or "ard_lengthscales" = one lengthscale
+ * variance, p2 = bias variance; conv layers only, conv_gp/models.py:113-121), type 2 Matern32 and type 3 Matern52
+ * (p1 = lengthscale; conv layers only), or "ard_lengthscales" = one lengthscale
  * per input dimension for a single-patch head (H = W = f = 1, C = D): gpflow RBF(D, ARD=True) on the flattened
  * features, the dense head of --last-kernel rbf (conv_gp/models.py:160-168).  "likelihood_epsilon" (one value in
  * (0, 1), `layer` ignored) is the RobustMax epsilon of the ELBO / predict_y entry points (default 1e-3).  */
