@@ -569,6 +569,17 @@ int dcgp_model_chain_skips(dcgp_model* model, uint64_t* out) {
   *out = model->chain_skips;
   return DCGP_OK;
 }
+int dcgp_model_factor_groups(dcgp_model* model, int cap, int* count_out, int* Mp_out, int* matrices_out, int* riding_out) {
+  if (!model || !count_out || cap < 0 || (cap > 0 && (!Mp_out || !matrices_out || !riding_out))) return DCGP_ERR_ARG;
+  const auto& groups = model->groups[model->bank];
+  *count_out = (int)groups.size();
+  for (int q = 0; q < cap && q < (int)groups.size(); ++q) {
+    int riding = 0;
+    for (const auto& r : groups[q].rhs) riding += (groups[q].rode && (r.Lq || r.qmu)) ? 1 : 0;
+    Mp_out[q] = groups[q].Mp; matrices_out[q] = (int)groups[q].K.size(); riding_out[q] = riding;
+  }
+  return DCGP_OK;
+}
 
 int dcgp_model_set_param(dcgp_model* model, int layer, const char* which, const double* value_host, size_t count) {
   if (model) ++model->param_version;   // (whatever becomes of the call: the parameter-only state of earlier steps is not reused)

@@ -108,6 +108,7 @@ _SIGS = {
     "dcgp_model_set_trainable": [_vp, _i, C.c_char_p, _i],
     "dcgp_model_set_factor_reuse": [_vp, _i],
     "dcgp_model_chain_skips": [_vp, C.POINTER(_u64)],
+    "dcgp_model_factor_groups": [_vp, _i, _ip, _ip, _ip, _ip],
     "dcgp_model_natgrad_step": [_vp, _d, _ip],
     "dcgp_model_predict_y": [_vp, _vp, _i, _i, C.POINTER(_vp), _u64, _vp, _vp, _ip],
     "dcgp_model_predict_density": [_vp, _vp, _vp, _i, _i, C.POINTER(_vp), _u64, _vp, _ip],

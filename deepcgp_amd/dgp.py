@@ -459,6 +459,15 @@ class DGP_Base:
         self._ctx._check(dev.lib().dcgp_model_chain_skips(self._model, C.byref(out)))
         return int(out.value)
 
+    def factor_groups(self):
+        """[(Mp, matrices, riding)] of the factor groups the most recent step ran (dcgp_model_factor_groups): one batched factorisation chain per
+        distinct padded size Mp, the matrices it factors and how many of them carried G / alpha on the chain.  Empty before the first step."""
+        self._build()
+        cap = 16
+        n, Mp, mats, ride = C.c_int(0), (C.c_int * cap)(), (C.c_int * cap)(), (C.c_int * cap)()
+        self._ctx._check(dev.lib().dcgp_model_factor_groups(self._model, cap, C.byref(n), Mp, mats, ride))
+        return [(Mp[q], mats[q], ride[q]) for q in range(min(n.value, cap))]
+
     def debug_sharded_adam(self, ranks, lr, t=None, beta1=0.9, beta2=0.999, epsilon=1e-8):
         """Debugging aid: ``adam_step`` taken the way ``ranks`` ranks take it in exchange mode 1, played on this one GPU (bit-identical).  Needs the
         complete gradient of a ``compute_gradients`` call."""

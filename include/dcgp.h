@@ -466,6 +466,11 @@ int dcgp_model_evaluate_uncertainty_f64y(dcgp_model* model, const double* X, con
  * Results are bit-identical to a step that runs the chain.  dcgp_model_chain_skips: steps that reused it so far. */
 int dcgp_model_set_factor_reuse(dcgp_model* model, int mode);
 int dcgp_model_chain_skips(dcgp_model* model, uint64_t* out);
+/* The factor groups of the model's most recent step (one batched factorisation chain per distinct padded size Mp = round_up(M, 16)): *count_out groups,
+ * none before the first step; for the first min(*count_out, cap) of them the padded size, the number of matrices the chain factors (every layer's Kuu(Z) and,
+ * for conv layers, the prior's Kuu(Z0)) and how many of those carried their right-hand sides G / alpha on the chain in that step.  Host arrays of `cap`
+ * entries; reads host state only. */
+int dcgp_model_factor_groups(dcgp_model* model, int cap, int* count_out, int* Mp_out, int* matrices_out, int* riding_out);
 /* Output of layer `layer` from the most recent forward: sample/mean/var [rows, D_l] device->device copy. */
 int dcgp_model_layer_output(dcgp_model* model, int layer, double* out_sample, double* out_mean,
                             double* out_var, int* rows, int* width);

@@ -12,8 +12,10 @@ patches and edits the dicts:
 * q_mu scaled by ``a``; conv q_sqrt = 0.3 * chol(K_uu) at the NEW lengthscale (identity when whitened), the head's chol(K_uu);
 * head patch weights 0.5 + U(0, 1).
 
-Used by tests/test_host_grad_large_m.py and tests/test_host_grad_m256.py (liveness of the torch reference, no GPU) and by
-tests/test_gpu_grad_large_m.py and tests/test_gpu_grad_m256.py."""
+``mixed_live_spec`` builds the heterogeneous stacks of CASES_MIXED from it: one M and one white flag per layer.
+
+Used by tests/test_host_grad_large_m.py, tests/test_host_grad_m256.py and tests/test_host_mixed_layers.py (liveness of the torch reference,
+no GPU) and by tests/test_gpu_grad_large_m.py, tests/test_gpu_grad_m256.py and tests/test_gpu_mixed_layers.py."""
 import numpy as np
 
 from deepcgp_amd import synthetic as syn
@@ -85,8 +87,86 @@ def live_spec(hwc, convs, head, M, c, a, S=2, seed=7, white=False, num_data=6000
     return spec
 
 
+def mixed_live_spec(hwc, convs, head, Ms, c, a, whites=None, **kw):
+    """A live spec whose layers differ in M (``Ms``: one count per layer, the head last, as the reference's ``-M 384,64``) and in whitening
+    (``whites``: one flag per layer, default all False): ``live_spec`` once per layer with that layer's M and white, layer i kept from call i.
+    A layer's inducing patches are cut from images that depend on the geometry and the seed alone, and its lengthscale edit and q_sqrt on its
+    own Z: nothing in layer i of call i depends on the M another layer would have had.  ``kw`` goes to ``live_spec`` (S, seed, ...)."""
+    nl = len(convs) + 1
+    whites = [False] * nl if whites is None else list(whites)
+    assert len(Ms) == nl and len(whites) == nl, (Ms, whites, nl)
+    each = [live_spec(hwc, convs, head, M, c, a, white=w, **kw) for M, w in zip(Ms, whites)]
+    return {"S": each[0]["S"], "num_data": each[0]["num_data"], "convs": [each[i]["convs"][i] for i in range(nl - 1)], "head": each[-1]["head"]}
+
+
+# Heterogeneous stacks (tests/test_host_mixed_layers.py, tests/test_gpu_mixed_layers.py): one M per layer, Mp = round_up(M, 16) in brackets, one
+# white flag per layer where given.  S = 2, seed 7, N = 3.  The library keeps one factor group per distinct Mp (csrc/model.hip, build_groups).
+_CH = dict(hwc=(28, 28, 1), convs=[(5, 2, 10)], head=(5, 1))
+_SMALL = dict(hwc=(14, 14, 1), convs=_SMALL3, head=(3, 1))
+CASES_MIXED = {
+    # two groups (32: layers 0 and 2 with layer 0's prior, 48: layer 1 and its prior); no deferred factor copy, the in-tail KL reads K / Kp
+    "small3_20_40_24": dict(_SMALL, Ms=(20, 40, 24), N=3, c=1.0, a=0.1),                                         # Mp 32, 48, 32
+    # group 32 holds a riding matrix pair (layer 1) and a whitened head that does not ride; a whitened layer moves the KL out of the tail launch
+    "small3_mixwhite": dict(_SMALL, Ms=(40, 20, 24), N=3, c=1.0, a=0.1, whites=(True, False, True)),             # Mp 48, 32, 32
+    # one group, the deferred copy on, three different true M inside it
+    "small3_sameMp": dict(_SMALL, Ms=(20, 24, 30), N=3, c=1.0, a=0.1),                                           # Mp 32, 32, 32
+    # the conv layer on the M > 256 route, the head on the M <= 256 route, and the reverse
+    "ch_264_72": dict(_CH, Ms=(264, 72), N=3, c=1.0, a=0.1),                                                     # Mp 272, 80
+    "ch_72_264": dict(_CH, Ms=(72, 264), N=3, c=1.0, a=0.1),                                                     # Mp 80, 272
+    # 33 feature maps, Rp = 48: the widest conv layer of the suite (13 elsewhere), beside a head with Rp = 16 in the same group.  Its right-hand sides
+    # cannot ride (Rp > 32) -- and nor do the head's here: a conv layer with Rp != 16 is not one launch (conv_fused.hip, plan_fused), and a chain beside
+    # a first layer's sweep carries no right-hand sides at all (plan_step: may_ride).  Mixed riding in one group is small3_mixwhite's
+    "wide_R33": dict(hwc=(12, 12, 1), convs=[(3, 1, 33)], head=(3, 1), Ms=(24, 24), N=3, c=1.0, a=0.1),          # Mp 32, 32
+}
+
+
+# What each CASES_MIXED entry is claimed to reach.  Per layer (the head last): Mp, whether the layer takes the M > 256 route, white, Rp =
+# round_up(R, 16).  `groups`: the factor groups in the order build_groups makes them, (Mp, matrices, riding): an unwhitened conv layer brings
+# Kuu(Z) and the prior's Kuu(Z0), a whitened conv layer and the head one matrix each; `riding` = how many of them carry G / alpha (the prior:
+# the KL's sums) on the chain in an ELBO step -- the layer unwhitened, Mp <= 256 and Rp <= 32, and only where the chain may carry any: a first layer
+# that is one launch behind the chain (a conv layer with Mp <= 256 and R <= 16), not one that opens with a sweep beside it.  None: not claimed.
+EXPECT_MIXED = {
+    "small3_20_40_24": dict(Mp=(32, 48, 32), large=(False, False, False), white=(False, False, False), Rp=(16, 16, 16),
+                            groups=[(32, 3, 3), (48, 2, 2)]),
+    "small3_mixwhite": dict(Mp=(48, 32, 32), large=(False, False, False), white=(True, False, True), Rp=(16, 16, 16),
+                            groups=[(48, 1, 0), (32, 3, 2)]),
+    "small3_sameMp": dict(Mp=(32, 32, 32), large=(False, False, False), white=(False, False, False), Rp=(16, 16, 16), groups=[(32, 5, 5)]),
+    "ch_264_72": dict(Mp=(272, 80), large=(True, False), white=(False, False), Rp=(16, 16), groups=[(272, 2, None), (80, 1, None)]),
+    "ch_72_264": dict(Mp=(80, 272), large=(False, True), white=(False, False), Rp=(16, 16), groups=[(80, 2, None), (272, 1, 0)]),
+    "wide_R33": dict(Mp=(32, 32), large=(False, False), white=(False, False), Rp=(48, 16), groups=[(32, 3, 0)]),
+}
+
+
+def round_up(n, k):
+    return (n + k - 1) // k * k
+
+
+def host_groups(spec):
+    """[(Mp, matrices, riding)] of a spec as build_groups makes them: layers in order, a group per distinct Mp in order of first appearance;
+    riding as EXPECT_MIXED defines it (never None; conv-first specs)."""
+    groups = []
+    layers = spec["convs"] + [spec["head"]]
+    may_ride = bool(spec["convs"]) and round_up(layers[0]["M"], 16) <= 256 and layers[0]["R"] <= 16       # the first layer is one launch
+    for li, l in enumerate(layers):
+        n = 2 if (li < len(layers) - 1 and not l["white"]) else 1
+        Mp = round_up(l["M"], 16)
+        ride = n if (may_ride and not l["white"] and Mp <= 256 and round_up(l["R"], 16) <= 32) else 0
+        at = [i for i, g in enumerate(groups) if g[0] == Mp]
+        if at:
+            groups[at[0]] = (Mp, groups[at[0]][1] + n, groups[at[0]][2] + ride)
+        else:
+            groups.append((Mp, n, ride))
+    return groups
+
+
 def make_case(name):
-    """(spec, X, Y, zs) of CASES[name] or CASES_M256[name]."""
+    """(spec, X, Y, zs) of CASES[name], CASES_M256[name] or CASES_MIXED[name]."""
+    if name in CASES_MIXED:
+        k = dict(CASES_MIXED[name])
+        N = k.pop("N")
+        spec = mixed_live_spec(**k)
+        X, Y = syn.make_batch(k["hwc"], N, seed=7)
+        return spec, X, Y, syn.make_noise(spec, N, seed=7)
     k = dict(CASES[name] if name in CASES else CASES_M256[name])
     N = k.pop("N")
     spec = live_spec(**k)

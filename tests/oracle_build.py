@@ -36,6 +36,24 @@ def oracle_model(spec, X, Y):
     return DGP_Base(X, Y, MultiClass(10), oracle_layers(spec), num_samples=spec["S"], num_data=spec["num_data"])
 
 
+def spec_from_model(model):
+    """The neutral spec of a device model's Python-side parameter values (RBF base kernels, ConvKernel head, no mean function): what
+    ``oracle_model`` needs to build the oracle from the same parameters, e.g. for a model ModelBuilder made from flags."""
+    def geom(v):
+        return dict(H=v.input_size[0], W=v.input_size[1], C=v.feature_maps, f=v.filter_size, s=v.stride)
+    convs = []
+    for l in model.layers[:-1]:
+        assert l.mean_function is None, "spec_from_model: conv layers without a mean function only"
+        convs.append(dict(geom(l.view), M=l.num_inducing, R=l.gp_count, Z=np.array(l.feature.Z), Z0=np.array(l.Z_prior),
+                          variance=float(l.base_kernel.variance), ls=float(l.base_kernel.lengthscales), q_mu=np.array(l.q_mu),
+                          q_sqrt=np.array(l.q_sqrt), white=bool(l.white)))
+    h = model.layers[-1]
+    head = dict(geom(h.kern.view), M=h.num_inducing, R=h.num_outputs, Z=np.array(h.feature.Z), variance=float(h.kern.base_kernel.variance),
+                ls=float(h.kern.base_kernel.lengthscales), w=np.array(h.kern.patch_weights), q_mu=np.array(h.q_mu), q_sqrt=np.array(h.q_sqrt),
+                white=bool(h.white))
+    return {"S": model.num_samples, "num_data": model.num_data, "convs": convs, "head": head}
+
+
 def oracle_param_handles(model):
     """[(layer index, gradient name, getter, setter)] of every trainable value of an oracle model with RBF base
     kernels -- the names oracle.grad.elbo_and_grad and dcgp_model_get_grad use."""

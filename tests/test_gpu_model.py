@@ -678,6 +678,16 @@ def test_model_builder_from_flags(ctx):
     assert np.max(np.abs(conv.q_sqrt)) < 1e-3 and head.q_sqrt.shape == (10, 7, 7)
     e = model.compute_log_likelihood(X[:8].reshape(8, -1), Y[:8], seed=1)
     assert np.isfinite(e)
+    # ... and at explicit noise it is the ELBO of the oracle built from the same parameters (M = 6 and 7 share Mp = 16: one factor group;
+    # two groups from flags: tests/test_gpu_mixed_layers.py)
+    from oracle_build import spec_from_model
+    built = spec_from_model(model)
+    Xb, Yb = X[:8].reshape(8, -1), Y[:8].reshape(-1)
+    zs = syn.make_noise(built, 8, seed=1)
+    e_z = model.compute_log_likelihood(Xb, Yb, zs=zs)
+    e_o = oracle_model(built, Xb, Yb).compute_log_likelihood(Xb, Yb, zs=zs)
+    assert abs(e_z - e_o) <= 1e-9 * abs(e_o), (e_z, e_o)
+    assert [g[:2] for g in model.factor_groups()] == [(16, 3)]
     assert abs(head.KL()) < 1e-8 and np.isfinite(conv.KL()) and conv.KL() > 0
     # checkpoint round trip in the reference's format (experiment.py:56-64 writes it, models.py:200-240 reads it):
     # perturb the parameters, save, rebuild from the file -> same parameters, same ELBO
