@@ -24,6 +24,7 @@ FLAGS = (
     ("--base-kernel", str, "rbf", "base kernel of the conv layers: rbf | acos | matern32 | matern52"),
     ("--white", None, False, "whitened variational parameters"),
     ("--last-kernel", str, "conv", "head kernel: conv | add | rbf"),
+    ("--likelihood", str, "robustmax", "multi-class likelihood: robustmax | softmax"),
     ("--gamma", float, 0.001, "NatGrad step size"),
     ("--identity-mean", None, False, "Conv2dMean identity mean function on the conv layers"),
     ("--load-model", str, None, "checkpoint (.npy, reference key set) to start from"),

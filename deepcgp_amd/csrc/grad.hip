@@ -1638,6 +1638,7 @@ int robustmax_grad(dcgp_ctx* ctx, const double* mu, const double* var, const int
   if (K > RM_KMAX) return ctx_fail(ctx, DCGP_ERR_ARG, "grad: at most %d classes", RM_KMAX);
   const double* gh = gauss_hermite_table(ctx);
   if (!gh) return DCGP_ERR_ALLOC;
+  ScopedTimer tm(ctx, "robustmax_grad");
   hipLaunchKernelGGL(robustmax_grad_kernel, dim3((rows + RM_ROWS - 1) / RM_ROWS), dim3(256), 0, ctx->stream, mu, var, y, rows, n_labels, K, eps, gh, weight,
                      gm, gv);
   LAUNCH_CHECK(ctx);

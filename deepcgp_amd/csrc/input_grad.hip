@@ -4,7 +4,7 @@
 //   the objective's tail adjoint -- (gm, gv) = dJ / d(mean, var) of the head's rows [S N][K], row s N + n --
 //   and the DATA PATH of the reverse pass down to and including layer 0 (model_backward_data, grad.hip).
 // Objectives, per image n (the layers treat images independently, so row n of the result is dJ_n / dX_n):
-//   density  J_n = log(1/S sum_s p(y_n | mean_sn, var_sn))      -- dcgp_model_predict_density's value; RobustMax
+//   density  J_n = log(1/S sum_s p(y_n | mean_sn, var_sn))      -- dcgp_model_predict_density's value; RobustMax, Softmax (softmax.hip)
 //   elbo     J_n = 1/S sum_s E_q[log p(y_n | f_sn)]             -- the image's share of the ELBO's data term, unscaled; every likelihood
 // RobustMax: p = (1 - eps) P + eps / (K - 1) (1 - P) and E_q[log p] = log(1 - eps) P + log(eps / (K - 1)) (1 - P) are both affine in the
 // Gauss-Hermite probability P that the label's output is the largest, so both tails are dP / d(mean, var) (robustmax_grad_kernel's terms, grad.hip)
@@ -42,7 +42,7 @@ __global__ __launch_bounds__(256) void labels_clamp_kernel(const int32_t* __rest
 // same clips), thread (row slot, k) adds the 20 nodes in a fixed order and stores the UNSCALED derivative; p_s = (1 - eps) P_s + eps / (K - 1) (1 - P_s)
 // stays in LDS.  Then pbar_n = 1/S sum_s p_s (s = 0, 1, ...), J[n] = log pbar_n, and the workgroup rescales the rows it wrote by
 // (1 - eps - eps / (K - 1)) / (S pbar_n).
-constexpr int DR_ROWS = 12, DR_KMAX = 16;
+constexpr int DR_ROWS = 12, DR_KMAX = kRmDensityMaxK;
 __global__ __launch_bounds__(256) void rm_density_grad_kernel(const double* __restrict__ mu, const double* __restrict__ var, const int32_t* __restrict__ y,
                                                               int n_img, int S, int K, double eps, const double* __restrict__ gh,
                                                               double* __restrict__ J, double* __restrict__ gm, double* __restrict__ gv) {
@@ -288,6 +288,18 @@ int patch_adjoint_fused(dcgp_ctx* ctx, const LayerState& L, const double* E, lon
   }
 }
 
+int rm_density_grad(dcgp_ctx* ctx, const double* mu, const double* var, const int32_t* y, int n_img, int S, int K, double eps, double* J, double* gm,
+                    double* gv) {
+  const double* gh = gauss_hermite_table(ctx);
+  if (!gh) return DCGP_ERR_ALLOC;
+  if (S > 256) return   // (static LDS of the kernel + S doubles within 64 KiB)
+    ctx_fail(ctx, DCGP_ERR_ARG, "input_grad: S = %d samples exceed the tail's LDS", S);
+  hipLaunchKernelGGL(rm_density_grad_kernel, dim3((unsigned)n_img), dim3(256), (size_t)S * sizeof(double), ctx->stream, mu, var, y, n_img, S, K, eps, gh, J,
+                     gm, gv);
+  LAUNCH_CHECK(ctx);
+  return DCGP_OK;
+}
+
 namespace {
 
 int input_grad_run(dcgp_model* model, const double* X, const int32_t* y, const double* yf, int N, int S, const double* const* zs, uint64_t seed,
@@ -305,9 +317,9 @@ int input_grad_run(dcgp_model* model, const double* X, const int32_t* y, const d
   const Likelihood lik = model->lik();
   DCGP_TRY(lik_check_targets(ctx, lik, Targets::of(y, yf, K), who));
   if (yf && obj == DCGP_OBJECTIVE_DENSITY)
-    return ctx_fail(ctx, DCGP_ERR_ARG, "%s: the density objective exists for the RobustMax likelihood only; a Gaussian or Bernoulli model takes the elbo objective", who);
+    return ctx_fail(ctx, DCGP_ERR_ARG, "%s: the density objective exists for the RobustMax and Softmax likelihoods only; a Gaussian or Bernoulli model takes the elbo objective", who);
   if (model->enq_seq != model->col_seq) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: enqueued steps are still to be collected", who);
-  if (!yf && (K < 2 || K > DR_KMAX)) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: RobustMax over %d outputs (2 to %d)", who, K, DR_KMAX);
+  if (!yf && (K < 2 || K > lik_density_max_k(lik))) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: %d classes (2 to %d)", who, K, lik_density_max_k(lik));
   const std::string mp = "m" + std::to_string(model->id) + "_";
   double* res = (double*)ws_get(ctx, mp + "ig_res", 2 * sizeof(double));
   int* bad = (int*)ws_get(ctx, mp + "ig_bad", sizeof(int));
@@ -335,13 +347,7 @@ int input_grad_run(dcgp_model* model, const double* X, const int32_t* y, const d
       LAUNCH_CHECK(ctx);
     }
     if (obj == DCGP_OBJECTIVE_DENSITY) {
-      const double* gh = gauss_hermite_table(ctx);
-      if (!gh) return DCGP_ERR_ALLOC;
-      if (Sh > 256) return   // (static LDS of the kernel + S doubles within 64 KiB)
-        ctx_fail(ctx, DCGP_ERR_ARG, "%s: S = %d samples exceed the tail's LDS", who, Sh);
-      hipLaunchKernelGGL(rm_density_grad_kernel, dim3((unsigned)N), dim3(256), (size_t)Sh * sizeof(double), ctx->stream, o.mean, o.var, ys, N, Sh, K,
-                         model->eps, gh, J, gm, gv);
-      LAUNCH_CHECK(ctx);
+      DCGP_TRY(lik_density_grad(ctx, lik, o.mean, o.var, ys, N, Sh, K, J, gm, gv));
     } else {
       // the variational expectations of the rows (the ELBO step's tail launch without its assembly), their mean per image, and the step's own seeds
       double* ve = (double*)ws_get(ctx, mp + "ig_ve", (size_t)rows * sizeof(double));

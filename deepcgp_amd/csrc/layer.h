@@ -229,6 +229,24 @@ int bern_predict(dcgp_ctx* ctx, const double* mu, const double* var, long n, dou
 int bern_eval_tail(dcgp_ctx* ctx, const double* mu, const double* var, const double* y, int n, int S, int K, long lo, double* logdens,
                    double* ld_nd, double* p_mean, double* correct);
 
+// softmax.hip: the Softmax likelihood's tails (int32 labels y; nodes [Q][K] on the device, the same table for every row; 2 <= K, 1 <= Q,
+// Q * K <= 4096, else DCGP_ERR_ARG).  softmax_elbo_tail: elbo_tail's counterpart (same scal / fin / KlTail contract); a label outside [0, K) leaves
+// NaN.  softmax_grad: gm, gv [rows][K] times weight.  softmax_predict: out_mean = p, out_var = p - p^2 (either may be nullptr).  softmax_eval_tail /
+// softmax_unc_tail: eval_tail / unc_tail with the probabilities of the softmax rule (eval_sum / unc_sum add them up).  softmax_density_grad: the
+// density objective's tail of dcgp_model_input_grad.  Every one of them gives the same bits for the probabilities of the same row.
+int softmax_elbo_tail(dcgp_ctx* ctx, const double* mu, const double* var, const int32_t* y, int n_rows, int n_labels, int K, const double* nodes, int Q,
+                      double* ve_rows, double inv_s, double* scal, const ElboFinish& fin, const KlTail* kl = nullptr);
+int softmax_grad(dcgp_ctx* ctx, const double* mu, const double* var, const int32_t* y, int rows, int n_labels, int K, const double* nodes, int Q,
+                 double weight, double* gm, double* gv);
+int softmax_predict(dcgp_ctx* ctx, const double* mu, const double* var, int rows, int K, const double* nodes, int Q, double* out_mean, double* out_var);
+int softmax_eval_tail(dcgp_ctx* ctx, const double* mu, const double* var, const int32_t* y, int n, int S, int K, const double* nodes, int Q, long lo,
+                      double* logdens, double* p_mean, int* ok);
+struct UncOut;
+int softmax_unc_tail(dcgp_ctx* ctx, const double* mu, const double* var, const int32_t* y, int n, int S, int K, const double* nodes, int Q, long lo,
+                     const UncOut& o);
+int softmax_density_grad(dcgp_ctx* ctx, const double* mu, const double* var, const int32_t* y, int n_img, int S, int K, const double* nodes, int Q,
+                         double* J, double* gm, double* gv);
+
 // uncertainty.hip: the uncertainty tails (dcgp_model_evaluate_uncertainty).  unc_tail / bern_unc_tail: eval_tail / bern_eval_tail with the same
 // bits for logdens, p_mean and the correct count, plus per entry (image; Bernoulli: (image, output)) at its index in the whole set the
 // predictive entropy, the expected entropy (may be nullptr), their difference, the confidence and the prediction.  y may be nullptr:
@@ -252,15 +270,16 @@ int unc_tail(dcgp_ctx* ctx, const double* mu, const double* var, const int32_t* 
 int bern_unc_tail(dcgp_ctx* ctx, const double* mu, const double* var, const double* y, int n, int S, int K, long lo, const UncOut& o);
 int unc_sum(dcgp_ctx* ctx, const UncSumArgs& a, const FactorStatus& st, double* res);
 
-// likelihood.hip: which likelihood a model has is decided there and nowhere else.  Likelihood: the kind with its two parameters; Targets: int32
+// likelihood.hip: which likelihood a model has is decided there and nowhere else.  Likelihood: the kind with its parameters; Targets: int32
 // labels [N] or float64 targets [N][K] of a whole set (either pointer may be nullptr where labels are optional: f64 still says which entry
 // point they came through).  Each lik_* function dispatches once on the kind to the launchers above and to robustmax_grad (grad.hip: the RobustMax
 // seeds gm, gv [rows][K] = weight * d E_q[log p(y | f)] / d(mean, var)); lik_eval_tail / lik_unc_tail take the whole set's targets and batch `lo`.
 struct Likelihood {
-  int kind = 0;                  // 0 RobustMax (labels), 1 Gaussian, 2 Bernoulli (probit) (targets)
+  int kind = 0;                  // 0 RobustMax, 3 Softmax (labels), 1 Gaussian, 2 Bernoulli (probit) (targets)
   double eps = 1e-3;             // RobustMax epsilon
   const double* s2 = nullptr;    // the Gaussian variance's device word
-  bool float_targets() const { return kind != 0; }    // the _f64y entry points
+  const double* nodes = nullptr; int Q = 0;   // Softmax: the node table [Q][K] on the device (nullptr: none set yet)
+  bool float_targets() const { return kind == 1 || kind == 2; }    // the _f64y entry points
   int n_params() const { return kind == 1 ? 1 : 0; }   // trainable words (the Gaussian variance): lik_grad_seeds wants a gs2 for each
 };
 struct Targets {
@@ -281,6 +300,16 @@ int lik_elbo_tail(dcgp_ctx* ctx, const Likelihood& lik, const double* mu, const 
 int lik_grad_seeds(dcgp_ctx* ctx, const Likelihood& lik, const double* mu, const double* var, const Targets& t, int rows, int n_labels, int K,
                    double weight, double* gm, double* gv, double* gs2);   // gs2[0] = d / d s2 (n_params() > 0, else unused)
 int lik_predict(dcgp_ctx* ctx, const Likelihood& lik, const double* mu, const double* var, long n, double* out_mean, double* out_var);
+// the label likelihoods: lik_class_probs -- out_p [rows][K] class probabilities per row (dcgp_model_predict_y); lik_density_max_k -- the classes the
+// density objective of dcgp_model_input_grad takes; lik_density_grad -- its tail (rm_density_grad, input_grad.hip / softmax_density_grad): J [n_img] and
+// (gm, gv) = d J / d(mean, var) of the rows [S n_img][K], row s n_img + n, labels y already inside [0, K)
+int lik_class_probs(dcgp_ctx* ctx, const Likelihood& lik, const double* mu, const double* var, int rows, int K, double* out_p);
+int lik_density_max_k(const Likelihood& lik);
+int lik_density_grad(dcgp_ctx* ctx, const Likelihood& lik, const double* mu, const double* var, const int32_t* y, int n_img, int S, int K, double* J,
+                     double* gm, double* gv);
+constexpr int kRmDensityMaxK = 16;   // classes of rm_density_grad_kernel's LDS tiles
+int rm_density_grad(dcgp_ctx* ctx, const double* mu, const double* var, const int32_t* y, int n_img, int S, int K, double eps, double* J, double* gm,
+                    double* gv);
 int lik_eval_tail(dcgp_ctx* ctx, const Likelihood& lik, const double* mu, const double* var, const Targets& all, int n, int S, int K, long lo,
                   const EvalOut& o);
 int lik_eval_sum(dcgp_ctx* ctx, const Likelihood& lik, const EvalOut& o, long n, const FactorStatus& st, double* res);

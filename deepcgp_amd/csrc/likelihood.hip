@@ -1,12 +1,14 @@
 // likelihood.hip -- the one place that knows which likelihood a model has (host code only: no kernels).  Every function takes the
 // Likelihood and the Targets (layer.h) and dispatches once on the kind to the launchers of cond.hip / evaluate.hip / uncertainty.hip /
-// grad.hip (RobustMax), gaussian.hip and bernoulli.hip; what differs between their argument lists ends here.
+// grad.hip / input_grad.hip (RobustMax), gaussian.hip, bernoulli.hip and softmax.hip; what differs between their argument lists ends here.
 #include "layer_impl.h"
 
 int lik_check_targets(dcgp_ctx* ctx, const Likelihood& lik, const Targets& t, const char* who) {
-  if (lik.float_targets() == t.f64) return DCGP_OK;
-  return ctx_fail(ctx, DCGP_ERR_ARG, t.f64 ? "%s: a RobustMax model takes int32 labels, not float64 targets"
-                                           : "%s: a Gaussian- or Bernoulli-likelihood model takes float64 targets (the _f64y entry points)", who);
+  if (lik.float_targets() != t.f64)
+    return ctx_fail(ctx, DCGP_ERR_ARG, t.f64 ? "%s: a RobustMax or Softmax model takes int32 labels, not float64 targets"
+                                             : "%s: a Gaussian- or Bernoulli-likelihood model takes float64 targets (the _f64y entry points)", who);
+  if (lik.kind == 3 && !lik.nodes) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: the Softmax likelihood has no node table yet (dcgp_model_set_likelihood_nodes)", who);
+  return DCGP_OK;
 }
 
 int lik_elbo_tail(dcgp_ctx* ctx, const Likelihood& lik, const double* mu, const double* var, const Targets& t, int n_rows, int n_labels, int K,
@@ -14,6 +16,7 @@ int lik_elbo_tail(dcgp_ctx* ctx, const Likelihood& lik, const double* mu, const 
   switch (lik.kind) {
     case 1: return gauss_elbo_tail(ctx, mu, var, t.values, n_rows, n_labels, K, lik.s2, ve_rows, inv_s, scal, fin, kl);
     case 2: return bern_elbo_tail(ctx, mu, var, t.values, n_rows, n_labels, K, ve_rows, inv_s, scal, fin, kl);
+    case 3: return softmax_elbo_tail(ctx, mu, var, t.labels, n_rows, n_labels, K, lik.nodes, lik.Q, ve_rows, inv_s, scal, fin, kl);
     default: return elbo_tail(ctx, mu, var, t.labels, n_rows, n_labels, K, lik.eps, ve_rows, inv_s, scal, fin, kl);
   }
 }
@@ -25,6 +28,7 @@ int lik_grad_seeds(dcgp_ctx* ctx, const Likelihood& lik, const double* mu, const
       if (!lik.s2 || !gs2) return ctx_fail(ctx, DCGP_ERR_ARG, "grad: the Gaussian likelihood has no variance on the device");
       return gauss_grad(ctx, mu, var, t.values, rows, K, n_labels, lik.s2, weight, gm, gv, gs2);
     case 2: return bern_grad(ctx, mu, var, t.values, rows, K, n_labels, weight, gm, gv);
+    case 3: return softmax_grad(ctx, mu, var, t.labels, rows, n_labels, K, lik.nodes, lik.Q, weight, gm, gv);
     default: return robustmax_grad(ctx, mu, var, t.labels, rows, n_labels, K, lik.eps, weight, gm, gv);
   }
 }
@@ -37,19 +41,33 @@ int lik_predict(dcgp_ctx* ctx, const Likelihood& lik, const double* mu, const do
   }
 }
 
+int lik_class_probs(dcgp_ctx* ctx, const Likelihood& lik, const double* mu, const double* var, int rows, int K, double* out_p) {
+  switch (lik.kind) {
+    case 1:
+    case 2: return ctx_fail(ctx, DCGP_ERR_ARG, "predict_y: a Gaussian- or Bernoulli-likelihood model predicts with dcgp_model_predict_mean_var");
+    case 3:
+      if (!lik.nodes) return ctx_fail(ctx, DCGP_ERR_ARG, "predict_y: the Softmax likelihood has no node table yet (dcgp_model_set_likelihood_nodes)");
+      return softmax_predict(ctx, mu, var, rows, K, lik.nodes, lik.Q, out_p, nullptr);
+    default:
+      if (K < 2) return ctx_fail(ctx, DCGP_ERR_ARG, "predict_y: the last layer has %d outputs, RobustMax needs >= 2", K);
+      return varexp_rows(ctx, mu, var, nullptr, rows, 1, K, lik.eps, out_p, 1);
+  }
+}
+
 int lik_eval_tail(dcgp_ctx* ctx, const Likelihood& lik, const double* mu, const double* var, const Targets& all, int n, int S, int K, long lo,
                   const EvalOut& o) {
   const Targets t = all.from(lo);
   switch (lik.kind) {
     case 1: return gauss_eval_tail(ctx, mu, var, t.values, n, S, K, lik.s2, lo, o.logdens, o.ld_nd, o.p_mean, o.score);
     case 2: return bern_eval_tail(ctx, mu, var, t.values, n, S, K, lo, o.logdens, o.ld_nd, o.p_mean, o.score);
+    case 3: return softmax_eval_tail(ctx, mu, var, t.labels, n, S, K, lik.nodes, lik.Q, lo, o.logdens, o.p_mean, o.ok);
     default: return eval_tail(ctx, mu, var, t.labels, n, S, K, lik.eps, lo, o.logdens, o.p_mean, o.ok);
   }
 }
 
 int lik_eval_sum(dcgp_ctx* ctx, const Likelihood& lik, const EvalOut& o, long n, const FactorStatus& st, double* res) {
   if (lik.float_targets()) return gauss_eval_sum(ctx, o.logdens, o.score, n, st, res);   // (Bernoulli: the same sum over its correct counts)
-  return eval_sum(ctx, o.logdens, o.ok, n, st, res);
+  return eval_sum(ctx, o.logdens, o.ok, n, st, res);                                      // (Softmax: eval_tail's outputs, the same sum)
 }
 
 int lik_unc_tail(dcgp_ctx* ctx, const Likelihood& lik, const double* mu, const double* var, const Targets& all, int n, int S, int K, long lo,
@@ -58,6 +76,19 @@ int lik_unc_tail(dcgp_ctx* ctx, const Likelihood& lik, const double* mu, const d
   switch (lik.kind) {
     case 1: return ctx_fail(ctx, DCGP_ERR_ARG, "evaluate_uncertainty: class probabilities need a classification likelihood, this model is Gaussian");
     case 2: return bern_unc_tail(ctx, mu, var, t.values, n, S, K, lo, o);
+    case 3: return softmax_unc_tail(ctx, mu, var, t.labels, n, S, K, lik.nodes, lik.Q, lo, o);
     default: return unc_tail(ctx, mu, var, t.labels, n, S, K, lik.eps, lo, o);
+  }
+}
+
+int lik_density_max_k(const Likelihood& lik) { return lik.kind == 3 ? 4096 : kRmDensityMaxK; }
+
+int lik_density_grad(dcgp_ctx* ctx, const Likelihood& lik, const double* mu, const double* var, const int32_t* y, int n_img, int S, int K, double* J,
+                     double* gm, double* gv) {
+  switch (lik.kind) {
+    case 1:
+    case 2: return ctx_fail(ctx, DCGP_ERR_ARG, "input_grad: the density objective exists for the RobustMax and Softmax likelihoods only");
+    case 3: return softmax_density_grad(ctx, mu, var, y, n_img, S, K, lik.nodes, lik.Q, J, gm, gv);
+    default: return rm_density_grad(ctx, mu, var, y, n_img, S, K, lik.eps, J, gm, gv);
   }
 }

@@ -675,12 +675,17 @@ int dcgp_elbo_forward_enqueue_f64y(dcgp_model* model, const double* X, const dou
 int dcgp_model_set_likelihood(dcgp_model* model, int kind, double variance) {
   if (!model) return DCGP_ERR_ARG;
   dcgp_ctx* ctx = model->ctx;
-  if (kind < 0 || kind > 2) return ctx_fail(ctx, DCGP_ERR_ARG, "set_likelihood: kind 0 (RobustMax), 1 (Gaussian) or 2 (Bernoulli), got %d", kind);
+  if (kind < 0 || kind > 3) return ctx_fail(ctx, DCGP_ERR_ARG, "set_likelihood: kind 0 (RobustMax), 1 (Gaussian), 2 (Bernoulli) or 3 (Softmax), got %d", kind);
   if (kind == 1 && !(variance > 1e-6)) return ctx_fail(ctx, DCGP_ERR_ARG, "set_likelihood: the Gaussian variance must be > 1e-6 (softplus + 1e-6)");
   if (!model->has_head) return ctx_fail(ctx, DCGP_ERR_ARG, "set_likelihood: set the head first");
   LayerState& H = *model->layers.back();
   if (H.gZ && model->lik_kind != kind) return ctx_fail(ctx, DCGP_ERR_ARG, "set_likelihood: the likelihood is fixed once a gradient was taken");
   if (model->enq_seq != model->col_seq) return ctx_fail(ctx, DCGP_ERR_ARG, "set_likelihood: enqueued steps are still to be collected");
+  // Softmax is chosen in place of the default RobustMax: a model already switched to float64 targets keeps them
+  if (kind == 3 && model->lik().float_targets())
+    return ctx_fail(ctx, DCGP_ERR_ARG, "set_likelihood: kind 3 (Softmax) takes int32 labels, this model was set to a float64-target likelihood (kind %d)", model->lik_kind);
+  if (kind == 3 && H.R < 2) return ctx_fail(ctx, DCGP_ERR_ARG, "set_likelihood: the Softmax likelihood needs K >= 2 classes, the head has %d outputs", H.R);
+  if (kind != 3) model->lik_Q = 0;   // (a node table belongs to the Softmax likelihood it was set on)
   ++model->param_version;
   model->lik_kind = kind;
   H.lik_slots = kind == 1 ? 1 : 0;   // (only the Gaussian variance takes a slot: a Bernoulli block is a RobustMax one)
@@ -889,20 +894,21 @@ int dcgp_model_predict_y(dcgp_model* model, const double* X, int N, int S, const
   if (!model || !X || N <= 0 || S <= 0 || (!out_p && !out_p_mean))
     return model ? ctx_fail(model->ctx, DCGP_ERR_ARG, "predict_y: bad args") : DCGP_ERR_ARG;
   dcgp_ctx* ctx = model->ctx;
-  if (model->lik_kind != 0) return ctx_fail(ctx, DCGP_ERR_ARG, "predict_y: a Gaussian- or Bernoulli-likelihood model predicts with dcgp_model_predict_mean_var");
+  const Likelihood lik = model->lik();
+  if (lik.float_targets()) return ctx_fail(ctx, DCGP_ERR_ARG, "predict_y: a Gaussian- or Bernoulli-likelihood model predicts with dcgp_model_predict_mean_var");
+  if (model->has_head) DCGP_TRY(lik_check_targets(ctx, lik, Targets{nullptr, nullptr, model->layers.back()->R, false}, "predict_y"));
   if (info_host) *info_host = 0;
   int rows = 0;
   DCGP_TRY(forward_data_impl(model, X, N, S, z_per_layer_host, seed, 0, &rows));
   const int nl = (int)model->layers.size();
   auto& o = model->outs[nl - 1];
   const int K = o.width;
-  if (K < 2) return ctx_fail(ctx, DCGP_ERR_ARG, "predict_y: the last layer has %d outputs, RobustMax needs >= 2", K);
   double* p = out_p;
   if (!p) {
     p = (double*)ws_get(ctx, "predict_p", (size_t)rows * K * sizeof(double));
     if (!p) return DCGP_ERR_ALLOC;
   }
-  DCGP_TRY(varexp_rows(ctx, o.mean, o.var, nullptr, rows, 1, K, model->eps, p, 1));
+  DCGP_TRY(lik_class_probs(ctx, lik, o.mean, o.var, rows, K, p));
   if (out_p_mean) {
     long NK = (long)N * K;
     hipLaunchKernelGGL(sample_mean_kernel, dim3((unsigned)((NK + 255) / 256)), dim3(256), 0, ctx->stream, p, S, NK, out_p_mean);
@@ -1023,7 +1029,7 @@ int evaluate_impl(dcgp_model* model, const double* X, const int32_t* y, int N_to
   const Likelihood lik = model->lik();
   const Targets targets = Targets::of(y, yf, K);
   DCGP_TRY(lik_check_targets(ctx, lik, targets, who));
-  if (!yf && K < 2) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: the last layer has %d outputs, RobustMax needs >= 2", who, K);
+  if (!yf && K < 2) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: the last layer has %d outputs, a multi-class likelihood needs >= 2", who, K);
   if (!yf && (long)S * K + K > kEvalMaxSlots) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: S = %d samples of %d classes exceed the tail's LDS", who, S, K);
   // the per-image results of the whole set: requested once, before batch 0
   const std::string mp = "m" + std::to_string(model->id) + "_";
@@ -1061,7 +1067,7 @@ int uncertainty_impl(dcgp_model* model, const double* X, const int32_t* y, const
   const Likelihood lik = model->lik();
   const Targets targets{y, yf, K, f64y};
   DCGP_TRY(lik_check_targets(ctx, lik, targets, who));
-  if (!f64y && K < 2) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: the last layer has %d outputs, RobustMax needs >= 2", who, K);
+  if (!f64y && K < 2) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: the last layer has %d outputs, a multi-class likelihood needs >= 2", who, K);
   if (!f64y && (long)S * K + K + kUncExtraSlots > kEvalMaxSlots)
     return ctx_fail(ctx, DCGP_ERR_ARG, "%s: S = %d samples of %d classes exceed the tail's LDS (S * K + K + %d <= %d)", who, S, K, kUncExtraSlots, kEvalMaxSlots);
   const bool labels = f64y ? yf != nullptr : y != nullptr;

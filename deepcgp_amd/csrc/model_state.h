@@ -10,9 +10,12 @@ struct dcgp_model {
   // likelihood (dcgp_model_set_likelihood): 0 RobustMax (labels, int32), 1 Gaussian, 2 Bernoulli (probit) (targets [N][K] float64).  The
   // Gaussian variance lives on the device (d_lik[0]; the tails and the optimiser read and write it there), its Adam moments in d_lik[1],
   // d_lik[2] and its gradient in the last slot of the head's gradient block (LayerState::glik).  Bernoulli has no parameter: no d_lik, no slot.
+  // 3 Softmax (labels, int32): no parameter either; its node table [lik_Q][K] lives in d_nodes (dcgp_model_set_likelihood_nodes) and is no
+  // part of the parameter state -- replacing it starts no new parameter version.
   int lik_kind = 0;
-  Likelihood lik() const { return Likelihood{lik_kind, eps, d_lik}; }   // what likelihood.hip's functions take
+  Likelihood lik() const { return Likelihood{lik_kind, eps, d_lik, lik_Q > 0 ? d_nodes : nullptr, lik_Q}; }   // what likelihood.hip's functions take
   double* d_lik = nullptr;
+  double* d_nodes = nullptr; size_t nodes_cap = 0; int lik_Q = 0;
   bool lik_frozen = false;   // dcgp_model_set_trainable(.., "likelihood_variance", 0)
   std::vector<std::unique_ptr<LayerState>> layers;   // conv layers..., head last (once set)
   bool has_head = false;
@@ -81,7 +84,7 @@ struct dcgp_model {
       for (auto& e : ev_prep[b]) if (e) hipEventDestroy(e);
     }
     for (auto& o : outs) { hipFree(o.sample); hipFree(o.mean); hipFree(o.var); }
-    hipFree(d_scal); hipFree(d_ve); hipFree(d_kd); hipFree(d_lik);
+    hipFree(d_scal); hipFree(d_ve); hipFree(d_kd); hipFree(d_lik); hipFree(d_nodes);
   }
 };
 

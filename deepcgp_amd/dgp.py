@@ -11,7 +11,7 @@ import numpy as np
 from . import device as dev
 from .kernels import JITTER
 from .layers import ConvLayer, SVGP_Layer
-from .likelihoods import Bernoulli, Gaussian
+from .likelihoods import Bernoulli, Gaussian, Softmax
 
 
 def batched_noise(zs, N, S, batch_size, dims=None):
@@ -53,6 +53,7 @@ class DGP_Base:
         self.layers = list(layers)
         self.gaussian = isinstance(likelihood, Gaussian)
         self.bernoulli = isinstance(likelihood, Bernoulli)
+        self.softmax = isinstance(likelihood, Softmax)           # int32 labels like MultiClass; its node table is pushed at build time
         self.float_targets = self.gaussian or self.bernoulli     # float64 N x D targets and the _f64y entry points
         self.Y = self._targets_host(Y) if self.float_targets else np.ascontiguousarray(np.reshape(Y, (-1,)), np.int32)
         self.num_samples = int(num_samples)
@@ -168,6 +169,20 @@ class DGP_Base:
             ctx._check(L.dcgp_model_set_likelihood(self._model, 1, float(self.likelihood.variance)))
         elif self.bernoulli:
             ctx._check(L.dcgp_model_set_likelihood(self._model, 2, 0.0))
+        elif self.softmax:
+            if self.likelihood.num_classes != h_.num_outputs:
+                raise ValueError("Softmax(%d) on a head with %d outputs" % (self.likelihood.num_classes, h_.num_outputs))
+            ctx._check(L.dcgp_model_set_likelihood(self._model, 3, 0.0))
+            self.push_likelihood_nodes()
+            self.likelihood._attach(self)
+
+    def push_likelihood_nodes(self):
+        """Softmax likelihood: copy ``likelihood.nodes`` [Q, K] to the built device model (dcgp_model_set_likelihood_nodes).  The table is no
+        parameter: factor reuse keeps its chain.  Not allowed while enqueued steps are outstanding."""
+        if not self.softmax or self._model is None:
+            return
+        nodes = np.ascontiguousarray(self.likelihood.nodes, np.float64)
+        self._ctx._check(dev.lib().dcgp_model_set_likelihood_nodes(self._model, nodes.ctypes.data, nodes.shape[0]))
 
     def sync_parameters(self):
         """Push the current Python-side parameter values to the device copy."""
@@ -351,7 +366,7 @@ class DGP_Base:
         if objective not in self.OBJECTIVES:
             raise ValueError("objective must be 'density' or 'elbo', got %r" % (objective,))
         if objective == "density" and self.float_targets:
-            raise NotImplementedError("input_gradient: the 'density' objective exists for the RobustMax likelihood only; a %s model takes "
+            raise NotImplementedError("input_gradient: the 'density' objective exists for the RobustMax and Softmax likelihoods only; a %s model takes "
                                       "objective='elbo'" % ("Gaussian" if self.gaussian else "Bernoulli"))
         S = self.num_samples if S is None else int(S)
         if S < 1:

@@ -1,5 +1,5 @@
-"""MultiClass likelihood with the RobustMax inverse link -- the gpflow.likelihoods.MultiClass(10) the
-reference builds at /root/reference/conv_gp/models.py:67 (20 Gauss-Hermite points, epsilon 1e-3)."""
+"""Likelihoods of the model path: MultiClass with the RobustMax inverse link -- the gpflow.likelihoods.MultiClass(10) the
+reference builds at /root/reference/conv_gp/models.py:67 (20 Gauss-Hermite points, epsilon 1e-3) -- Gaussian, Bernoulli and Softmax."""
 import numpy as np
 
 from . import device as dev
@@ -139,3 +139,126 @@ class Bernoulli:
         h, e = h2(pbar), h2(ps).sum(0) / ps.shape[0]
         return {"p_mean": pbar, "predictive_entropy": h, "expected_entropy": e, "mutual_information": h - e,
                 "confidence": np.maximum(pbar, 1 - pbar), "prediction": (pbar > 0.5).astype(np.int32)}
+
+
+def softmax_nodes(num_classes, num_points, rng):
+    """[Q, K] nodes of the Softmax rule: Q // 2 rows of standard-normal draws followed by their negations (antithetic pairs: the odd
+    moments of the rule are exact), an odd Q with one more unpaired row at the end."""
+    Q, K = int(num_points), int(num_classes)
+    half = rng.standard_normal((Q // 2, K))
+    rows = [half, -half]
+    if Q % 2:
+        rows.append(rng.standard_normal((1, K)))
+    return np.ascontiguousarray(np.concatenate(rows, 0), np.float64)
+
+
+class Softmax:
+    """gpflow 1.x likelihoods.SoftMax(num_classes) -- p(y | f) = softmax(f)[y], a MonteCarloLikelihood -- with gpflow's fresh draw per call
+    replaced by a FIXED table of nodes ``nodes`` [Q, K] of standard-normal draws, the same for every row (a Q-node rule, used the way the
+    Gauss-Hermite nodes are used for RobustMax and Bernoulli): with s = sqrt(max(Fvar, 1e-10)) and f_q = Fmu + s * nodes[q],
+      variational expectation  1/Q sum_q (f_q[y] - logsumexp f_q),   predictive mean  p = 1/Q sum_q softmax(f_q), variance p - p^2,
+      predictive density log p[y].
+    The objective is deterministic (same bits on two calls, whatever the rank count); ``resample()`` between steps gives gpflow's fresh
+    noise.  Labels are integers in [0, num_classes).  No trainable parameters; the table is not saved in checkpoints.  On the model path
+    (DGP_Base with this likelihood) every tail runs on the device (csrc/softmax.hip); ``variational_expectations`` on arrays goes through
+    the device too (dcgp_softmax_varexp), the other methods are NumPy on the same table."""
+
+    def __init__(self, num_classes=10, num_monte_carlo_points=100, seed=0, nodes=None):
+        self.num_classes = int(num_classes)
+        if self.num_classes < 2:
+            raise ValueError("Softmax needs num_classes >= 2, got %r" % (num_classes,))
+        self._models = []
+        if nodes is not None:
+            nodes = np.ascontiguousarray(nodes, np.float64)
+            if nodes.ndim != 2 or nodes.shape[1] != self.num_classes or nodes.shape[0] < 1:
+                raise ValueError("nodes must be Q x %d with Q >= 1, got shape %r" % (self.num_classes, nodes.shape))
+            self.nodes = nodes
+        else:
+            if int(num_monte_carlo_points) < 1:
+                raise ValueError("num_monte_carlo_points must be >= 1, got %r" % (num_monte_carlo_points,))
+            self.nodes = softmax_nodes(self.num_classes, num_monte_carlo_points, np.random.RandomState(seed))
+        if self.nodes.size > 4096:
+            raise ValueError("Softmax: Q * K = %d * %d > 4096 (the device tails keep the table in 32 KB of LDS)" % self.nodes.shape)
+
+    @property
+    def num_monte_carlo_points(self):
+        return self.nodes.shape[0]
+
+    def _attach(self, model):
+        import weakref
+        self._models = [r for r in self._models if r() is not None and r() is not model] + [weakref.ref(model)]
+
+    def resample(self, rng=None):
+        """Redraw the table (same Q, antithetic pairs again) from ``rng`` -- a RandomState, a seed, or None for a fresh RandomState -- and
+        push it to every built model this likelihood is attached to."""
+        if not isinstance(rng, np.random.RandomState):
+            rng = np.random.RandomState(rng)
+        self.nodes = softmax_nodes(self.num_classes, self.nodes.shape[0], rng)
+        for r in self._models:
+            m = r()
+            if m is not None:
+                m.push_likelihood_nodes()
+        return self.nodes
+
+    # ---- host closed forms on the table ------------------------------------------------------------
+    @staticmethod
+    def _log_softmax(F):
+        F = np.asarray(F, np.float64)
+        mx = F.max(-1, keepdims=True)
+        return F - (mx + np.log(np.exp(F - mx).sum(-1, keepdims=True)))
+
+    def _labels(self, Y, shape):
+        Y = np.asarray(Y)
+        if Y.ndim == len(shape) + 1 and Y.shape[-1] == 1:
+            Y = Y[..., 0]
+        Y = np.broadcast_to(Y, shape).astype(np.int64)
+        if Y.size and (Y.min() < 0 or Y.max() >= self.num_classes):
+            raise ValueError("labels must be integers in [0, %d)" % self.num_classes)
+        return Y
+
+    def _F(self, Fmu, Fvar):
+        """[..., Q, K]: f_q = Fmu + sqrt(max(Fvar, 1e-10)) * nodes[q]"""
+        Fmu, Fvar = np.asarray(Fmu, np.float64), np.asarray(Fvar, np.float64)
+        if Fmu.shape[-1] != self.num_classes:
+            raise ValueError("expected %d latent functions, got %d" % (self.num_classes, Fmu.shape[-1]))
+        return Fmu[..., None, :] + np.sqrt(np.maximum(Fvar, 1e-10))[..., None, :] * self.nodes
+
+    def logp(self, F, Y):
+        """log softmax(F)[Y]: F [..., K], Y [...] integer labels."""
+        ls = self._log_softmax(F)
+        Y = self._labels(Y, ls.shape[:-1])
+        return np.take_along_axis(ls, Y[..., None], -1)[..., 0]
+
+    def conditional_mean(self, F):
+        return np.exp(self._log_softmax(F))
+
+    def conditional_variance(self, F):
+        p = self.conditional_mean(F)
+        return p - np.square(p)
+
+    def predict_mean_and_var(self, Fmu, Fvar):
+        p = np.exp(self._log_softmax(self._F(Fmu, Fvar))).sum(-2) / self.nodes.shape[0]
+        return p, p - np.square(p)
+
+    def predict_density(self, Fmu, Fvar, Y):
+        p = self.predict_mean_and_var(Fmu, Fvar)[0]
+        Y = self._labels(Y, p.shape[:-1])
+        return np.log(np.take_along_axis(p, Y[..., None], -1)[..., 0])
+
+    def variational_expectations(self, Fmu, Fvar, Y):
+        ctx = dev.get_context()
+        Fmu = np.ascontiguousarray(Fmu, np.float64)
+        n, K = Fmu.shape
+        if K != self.num_classes:
+            raise ValueError("expected %d latent functions, got %d" % (self.num_classes, K))
+        Y = np.ascontiguousarray(np.reshape(Y, -1), np.int32)
+        if Y.shape[0] != n or Y.min(initial=0) < 0 or Y.max(initial=0) >= K:
+            raise ValueError("labels must be %d integers in [0, %d)" % (n, K))
+        if n == 0:
+            return np.zeros((0,))
+        dmu, dvar, dy, dn = ctx.to_device(Fmu), ctx.to_device(Fvar), ctx.to_device(Y, np.int32), ctx.to_device(self.nodes)
+        out = ctx.empty((n,))
+        ctx._check(dev.lib().dcgp_softmax_varexp(ctx.handle, dmu.ptr, dvar.ptr, dy.ptr, n, K, dn.ptr, self.nodes.shape[0], out.ptr))
+        return out.numpy()
+
+    predictive_uncertainty = staticmethod(MultiClass.predictive_uncertainty)

@@ -5,7 +5,7 @@ import numpy as np
 from .dgp import DGP_Base
 from .kernels import RBF, ArcCosine, Matern32, Matern52, ConvKernel, AdditivePatchKernel, PatchInducingFeatures, InducingPoints
 from .layers import ConvLayer, SVGP_Layer
-from .likelihoods import MultiClass
+from .likelihoods import MultiClass, Softmax
 from .mean_functions import Conv2dMean, IdentityConv2dMean  # noqa: F401  (the names conv_gp/models.py:11 imports)
 from .views import FullView
 
@@ -16,6 +16,9 @@ def parse_ints(int_string):
         return []
     return [int(i) for i in int_string.split(',')]
 
+
+# --likelihood values (the ten-class likelihood ModelBuilder puts on the head)
+LIKELIHOODS = {"robustmax": MultiClass, "softmax": Softmax}
 
 # --base-kernel values (conv layers); "acos" takes gpflow's default parameters, the others (variance, lengthscales)
 BASE_KERNELS = {"rbf": RBF, "acos": ArcCosine, "matern32": Matern32, "matern52": Matern52}
@@ -218,7 +221,7 @@ class AdversarialAccuracyLogger(object):
 
     def __call__(self, model, seed=0):
         if getattr(model, "float_targets", False):
-            raise ValueError("AdversarialAccuracyLogger: needs a multi-class (RobustMax) model")
+            raise ValueError("AdversarialAccuracyLogger: needs a multi-class (RobustMax or Softmax) model")
         correct = 0
         for i, lo in enumerate(range(0, len(self.Y_test), self.batch_size)):
             sl = slice(lo, lo + self.batch_size)
@@ -421,12 +424,20 @@ class ModelBuilder(object):
         return spec
 
     # ---- spec -> model -----------------------------------------------------------------------------
+    def likelihood(self):
+        """The ten-class likelihood --likelihood names: MultiClass(10) (RobustMax, the reference's) or Softmax(10)."""
+        kind = getattr(self.flags, "likelihood", "robustmax")
+        if kind not in LIKELIHOODS:
+            raise ValueError("Not a valid likelihood value: %r (choices: %s)" % (kind, ", ".join(sorted(LIKELIHOODS))))
+        return LIKELIHOODS[kind](10)
+
     def build(self):
+        likelihood = self.likelihood()
         spec = self.spec()
         layers = build_layers_from_spec(spec)
         for layer, c in zip(layers, spec["convs"]):
             if c["q_sqrt_scale"] is not None:
                 layer.q_sqrt = layer.q_sqrt * c["q_sqrt_scale"]
         X = self.X_train.reshape(-1, int(np.prod(self.X_train.shape[1:])))
-        return DGP_Base(X, self.Y_train, likelihood=MultiClass(10), num_samples=self.flags.num_samples,
+        return DGP_Base(X, self.Y_train, likelihood=likelihood, num_samples=self.flags.num_samples,
                         layers=layers, minibatch_size=self.flags.batch_size, name='DGP')

@@ -193,6 +193,15 @@ int dcgp_robustmax_varexp(dcgp_ctx* ctx, const double* mu, const double* var, co
 /* MultiClass.predict_mean_and_var: per-class probabilities [n,K].                                */
 int dcgp_robustmax_predict(dcgp_ctx* ctx, const double* mu, const double* var, int n, int K, double eps,
                            double* out_p);
+/* gpflow likelihoods.SoftMax(K) variational_expectations / predict_mean_and_var (MonteCarloLikelihood) with the per-call draw replaced by
+ * a fixed table of nodes [Q, K] (standard-normal draws, the same for every row; device): with s = sqrt(max(var, 1e-10)), f_q = mu + s * e_q,
+ * out_n [n] = 1/Q sum_q (f_q[y] - logsumexp_k f_q[k]) and out_p [n, K] = 1/Q sum_q softmax(f_q), summed in a fixed order (two calls give the
+ * same bits).  mu, var [n, K]; y [n] int32.  DCGP_ERR_ARG unless 2 <= K, 1 <= Q, Q * K <= 4096 (the table's 32 KB of LDS) and every
+ * label is in [0, K).                                                                            */
+int dcgp_softmax_varexp(dcgp_ctx* ctx, const double* mu, const double* var, const int32_t* y, int n,
+                        int K, const double* nodes, int Q, double* out_n);
+int dcgp_softmax_predict(dcgp_ctx* ctx, const double* mu, const double* var, int n, int K,
+                         const double* nodes, int Q, double* out_p);
 /* doubly_stochastic_dgp.utils.reparameterize: out = mean + z*sqrt(var + jitter), n elements.     */
 int dcgp_reparam(dcgp_ctx* ctx, const double* mean, const double* var, const double* z, size_t n,
                  double jitter, double* out);
@@ -322,20 +331,20 @@ int dcgp_model_get_param(dcgp_model* model, int layer, const char* which, double
 int dcgp_model_propagate(dcgp_model* model, const double* X, int N, int S,
                          const double* const* z_per_layer_host, uint64_t seed,
                          double* out_fmean, double* out_fvar, int* info_host);
-/* DGP_Base.predict_y(X, S) with the RobustMax likelihood, device end to end (doubly_stochastic_dgp
+/* DGP_Base.predict_y(X, S) with the RobustMax or Softmax likelihood, device end to end (doubly_stochastic_dgp
  * predict_y -> likelihood.predict_mean_and_var; caller at conv_gp/utils/log.py:62-66): out_p [S*N, K]
  * class probabilities per sample (the predictive variance is p - p^2), out_p_mean [N, K] their mean over
  * the S samples (what AccuracyLogger arg-maxes).  Either output may be NULL, not both.  Device buffers. */
 int dcgp_model_predict_y(dcgp_model* model, const double* X, int N, int S,
                          const double* const* z_per_layer_host, uint64_t seed,
                          double* out_p, double* out_p_mean, int* info_host);
-/* DS-DGP DGP_Base.predict_density(X, Y, S): per image logsumexp_s log p(y | f_s) - log S, RobustMax likelihood. out_logdens [N], device.
+/* DS-DGP DGP_Base.predict_density(X, Y, S): per image logsumexp_s log p(y | f_s) - log S, RobustMax or Softmax likelihood. out_logdens [N], device.
  * The class probabilities are dcgp_model_predict_y's; y [N] int32 in [0, K) (device), else DCGP_ERR_ARG.                              */
 int dcgp_model_predict_density(dcgp_model* model, const double* X, const int32_t* y, int N, int S,
                                const double* const* z_per_layer, uint64_t seed, double* out_logdens, int* info_host);
 /* Input gradients (saliency maps, adversarial examples; the reference's users get them from tf.gradients on predict_density / the ELBO).
  * Per image n of the batch an objective J_n, with the noise fixed by z_per_layer or seed exactly as in dcgp_model_predict_density:
- *   DCGP_OBJECTIVE_DENSITY  J_n = log(1/S sum_s p(y_n | f_sn)), dcgp_model_predict_density's value (RobustMax models only; a Gaussian or
+ *   DCGP_OBJECTIVE_DENSITY  J_n = log(1/S sum_s p(y_n | f_sn)), dcgp_model_predict_density's value (RobustMax and Softmax models; a Gaussian or
  *                           Bernoulli model gets DCGP_ERR_ARG, never the other objective),
  *   DCGP_OBJECTIVE_ELBO     J_n = 1/S sum_s E_q[log p(y_n | f_sn)], the image's share of the ELBO's data term, unscaled, without the KL.
  * out_value [N] = J (device, may be NULL), out_dX [N][H*W*C] = dJ_n / dX_n (device; the layers treat images independently, so it is
@@ -368,7 +377,8 @@ int dcgp_model_evaluate(dcgp_model* model, const double* X, const int32_t* y, in
  * The likelihood of the model: kind 0 = RobustMax (the default; int32 labels), 1 = Gaussian with one variance s2 > 1e-6 shared by every
  * output (float64 targets y [N, K], K = the head's outputs; gpflow's transforms.positive, s2 = softplus(u) + 1e-6, in the optimiser),
  * 2 = Bernoulli with gpflow's jittered probit link p(f) = Phi(f) (1 - 2e-3) + 1e-3 (`variance` ignored; float64 targets y [N, K], every
- * output an independent binary label: y == 1.0 positive, anything else negative, as gpflow's tf.equal(y, 1)).  Other kinds are refused.
+ * output an independent binary label: y == 1.0 positive, anything else negative, as gpflow's tf.equal(y, 1)), 3 = Softmax (`variance`
+ * ignored; int32 labels, see dcgp_model_set_likelihood_nodes below).  Other kinds are refused.
  * Replaces the likelihood argument of DS-DGP DGP_Base.__init__.  Call after dcgp_model_set_head and before the first gradient: once a
  * gradient was taken the kind is fixed.
  * Bernoulli has no parameter: its gradient block has the RobustMax layout and length, and it has no "likelihood_variance".  Its
@@ -383,6 +393,21 @@ int dcgp_model_evaluate(dcgp_model* model, const double* X, const int32_t* y, in
  * RobustMax model.  s2 is "likelihood_variance" in dcgp_model_set_param / _get_param / _get_grad / _set_trainable (`layer` ignored); its
  * gradient is the last slot of the head's gradient block (dcgp_model_grad_block), after the ARD lengthscales. */
 int dcgp_model_set_likelihood(dcgp_model* model, int kind, double variance);
+/* The Softmax likelihood, dcgp_model_set_likelihood(model, 3, 0.0) (gpflow 1.x likelihoods.SoftMax as a MonteCarloLikelihood, its per-call
+ * draw replaced by a fixed table): per head row, with the node table e [Q, K], s = sqrt(max(var, 1e-10)) and f_q = mu + s * e_q,
+ *   variational expectation 1/Q sum_q (f_q[y] - logsumexp_k f_q[k]),  class probabilities p = 1/Q sum_q softmax(f_q),
+ * the gradient the exact derivative of that sum (d / d var = 0 where the clamp holds), the log density per image log(1/S sum_s p_s[y]).
+ * It takes int32 labels in [0, K) through the int32 entry points: dcgp_elbo_forward, _enqueue, dcgp_elbo_grad, dcgp_model_train_step_adam,
+ * the SGD and natural-gradient steps, dcgp_model_predict_y, dcgp_model_predict_density, dcgp_model_evaluate,
+ * dcgp_model_evaluate_uncertainty and dcgp_model_input_grad with both objectives; the _f64y entry points return DCGP_ERR_ARG on it.  It has
+ * no trainable parameter: the gradient blocks have the RobustMax layout and length.  Kind 3 is chosen in place of the default RobustMax
+ * (K >= 2): a model already set to a float64-target likelihood (kind 1 or 2) refuses it with DCGP_ERR_ARG.
+ * dcgp_model_set_likelihood_nodes copies the host table nodes_host [Q, K] (row q = node q; K = the head's outputs) to the device.
+ * 1 <= Q and Q * K <= 4096 (32 KB of LDS), else DCGP_ERR_ARG; Q may differ from call to call.  Allowed whenever no enqueued step is
+ * outstanding (else DCGP_ERR_ARG).  The table is no parameter: the call starts no new parameter version, so dcgp_model_set_factor_reuse
+ * keeps its chain.  A kind-3 model without a table refuses every step with DCGP_ERR_ARG; on a model of another kind the call is
+ * DCGP_ERR_ARG.  Every sum runs in a fixed order (no atomics): two calls give the same bits, whatever the number of ranks. */
+int dcgp_model_set_likelihood_nodes(dcgp_model* model, const double* nodes_host, int Q);
 /* dcgp_elbo_forward / _enqueue with Gaussian targets y [N, K] float64 (device): DGP_Base._build_likelihood with
  * Gaussian.variational_expectations = -0.5 log(2 pi s2) - 0.5 ((y - mu)^2 + var) / s2 summed over the K outputs.  Tickets are
  * collected with dcgp_elbo_forward_collect. */
