@@ -330,6 +330,11 @@ struct BaseKernel {
 #pragma unroll
     for (int i = 0; i < N; ++i) io[i] = eval_as<T>(io[i], n1[i], n2[i]);
   }
+  // A Gram matrix's own diagonal, k(z, z).  ArcCosine: cos == 1 identically in z, w and b, so the entry is the constant variance (1 - acos(1 - 1e-15) / pi);
+  // evaluated from (dot, n1, n2) one ulp of the cosine would move it by ~1e-9 variance, which inv(K_uu) amplifies a hundredfold and more
+  __device__ __forceinline__ double eval_diag(double dot, double n1, double n2) const {
+    return type == 1 ? variance * (1.0 - acos(1.0 - 1e-15) * 0.31830988618379067154) : eval(dot, n1, n2);
+  }
   __device__ __forceinline__ double eval(double dot, double n1, double n2) const {
     return type == 0 ? eval_as<0>(dot, n1, n2) : type == 1 ? eval_as<1>(dot, n1, n2) : type == 2 ? eval_as<2>(dot, n1, n2) : eval_as<3>(dot, n1, n2);
   }

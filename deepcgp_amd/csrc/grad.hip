@@ -559,7 +559,7 @@ __global__ __launch_bounds__(256) void acos_kuu_backward_kernel(const double* __
     const double c = (w * s + b) / rt;
     const double cp = fmin(1e-15 + (1.0 - 2e-15) * c, 1.0);
     const double theta = acos(cp);
-    const double k = variance * (1.0 - theta * 0.31830988618379067154);
+    const double k = variance * (1.0 - (j == i ? acos(1.0 - 1e-15) : theta) * 0.31830988618379067154);   // the diagonal: BaseKernel::eval_diag
     const double Sij = S[i * lds + j];
     sv += Sij * k;
     double es = 0.0;
@@ -629,6 +629,7 @@ struct OptGroup {
   int transform, hyp_layer;                           // hyp_layer >= 0: p is that layer's {variance, p1, p2} triple
   // sharded step (OptArgs::sharded): the group's offset in its layer's gradient block, the layer, and whether it only passes through
   long off; int layer, frozen;
+  int hold;                                           // hyp_layer >= 0: bit i set = element i of the triple is held (set_trainable on one ArcCosine parameter)
 };
 constexpr int OPT_GROUPS_MAX = 48;
 struct OptArgs {
@@ -656,7 +657,7 @@ __global__ __launch_bounds__(256) void opt_step_kernel(OptArgs a) {
   if (a.sharded && (G.off + i < a.sh_lo[G.layer] || G.off + i >= a.sh_hi[G.layer])) return;
   const double x = G.hyp_layer >= 0 ? a.hyp_in[G.hyp_layer][i] : G.p[i];
   double out;
-  if (G.frozen) {
+  if (G.frozen || (G.hyp_layer >= 0 && ((G.hold >> (int)i) & 1))) {
     out = x;
   } else if (a.sgd) {   // plain gradient ascent on the ELBO in the unconstrained space
     const double gr = G.g[i];
@@ -1991,7 +1992,9 @@ static int opt_enqueue(dcgp_model* model, const char* who, bool sgd, double lr, 
     DCGP_TRY(add(L.q_mu, L.gq_mu, L.aq_mu, (long)L.M * L.R, 0, -1, nullptr, (L.frozen & 2u) != 0));
     if (L.has_qsqrt) DCGP_TRY(add(L.q_sqrt, L.gq_sqrt, L.aq_sqrt, (long)L.R * L.M * L.M, 0, -1, nullptr, (L.frozen & 4u) != 0));   // upper triangle: zero gradient, zero step
     if (L.is_head && L.w) DCGP_TRY(add(L.w, L.gw, L.aw, (long)L.v.P, 0, -1, nullptr, (L.frozen & 8u) != 0));
+    const int ng_hyp = a.ng;
     DCGP_TRY(add(L.hyp, L.gscal, L.ahyp, 3, 1, li, nullptr, (L.frozen & 16u) != 0));
+    if (a.ng > ng_hyp) a.grp[ng_hyp].hold = (int)((L.frozen >> 5) & 3u) << 1;   // bits 32 / 64: elements 1 / 2 of the triple stay where they are
     if (L.ard) DCGP_TRY(add(L.ard, L.gard, L.aard, (long)L.v.L, 1, -1, L.in_scale, (L.frozen & 16u) != 0));   // dense head: per-dimension lengthscales and the staging scale 1 / l
     if (L.glik) {   // Gaussian likelihood variance: the last slot of the head's block, moments beside it on the device
       if (!model->d_lik) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: the head's block has a likelihood slot but the model no Gaussian likelihood", who);
@@ -2084,6 +2087,8 @@ int dcgp_model_set_trainable(dcgp_model* model, int layer, const char* which, in
   else if (!strcmp(which, "q_sqrt")) bit = 4u;
   else if (!strcmp(which, "w")) bit = 8u;
   else if (!strcmp(which, "variance") || !strcmp(which, "lengthscale") || !strcmp(which, "hyper")) bit = 16u;
+  else if (L.base_type == 1 && !strcmp(which, "weight_variances")) bit = 32u;   // one ArcCosine parameter alone (the other and the variance go on moving)
+  else if (L.base_type == 1 && !strcmp(which, "bias_variance")) bit = 64u;
   else return ctx_fail(model->ctx, DCGP_ERR_ARG, "set_trainable: unknown parameter '%s'", which);
   if (on) L.frozen &= ~bit; else L.frozen |= bit;
   return DCGP_OK;

@@ -62,8 +62,7 @@ __device__ void gram_tile(const PrepLayerArgs& p, const double* __restrict__ Z, 
   if (i < p.Mp && j < p.Mp) {
     double v = 0.0;
     if (i < p.M && j < p.M) {
-      v = p.bk.eval(dot, ni, nj);
-      if (i == j) v += p.jitter;
+      v = i == j ? p.bk.eval_diag(dot, ni, nj) + p.jitter : p.bk.eval(dot, ni, nj);
     } else if (i == j) {
       v = 1.0;   // identity on the padding keeps the padded matrix factorisable
     }

@@ -53,8 +53,7 @@ __global__ __launch_bounds__(256) void rbf_gram_kernel(const double* __restrict_
     if (i >= Mp || j >= ld) continue;
     double v = 0.0;
     if (i < M && j < M) {
-      v = bk.eval(dot[q], ni[q], nj);
-      if (i == j) v += jitter;
+      v = i == j ? bk.eval_diag(dot[q], ni[q], nj) + jitter : bk.eval(dot[q], ni[q], nj);
     } else if (i == j) {
       v = 1.0;   // identity on the padding so that factorisations of the padded matrix stay valid
     }

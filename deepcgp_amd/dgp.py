@@ -502,8 +502,9 @@ class DGP_Base:
         self.global_batch = int(global_batch) if global_batch else None
 
     def set_trainable(self, layer, which, on):
-        """param.set_trainable(on) for the device optimiser steps: which in Z, q_mu, q_sqrt, w, hyper; "likelihood_variance" (Gaussian
-        likelihood, ``layer`` ignored)."""
+        """param.set_trainable(on) for the device optimiser steps: which in Z, q_mu, q_sqrt, w, hyper (every kernel parameter of the layer);
+        weight_variances, bias_variance (that one parameter of an ArcCosine conv layer); "likelihood_variance" (Gaussian likelihood,
+        ``layer`` ignored)."""
         self._build()
         self._ctx._check(dev.lib().dcgp_model_set_trainable(self._model, int(layer), which.encode(), int(bool(on))))
 

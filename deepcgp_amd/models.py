@@ -20,7 +20,7 @@ def parse_ints(int_string):
 # --likelihood values (the ten-class likelihood ModelBuilder puts on the head)
 LIKELIHOODS = {"robustmax": MultiClass, "softmax": Softmax}
 
-# --base-kernel values (conv layers); "acos" takes gpflow's default parameters, the others (variance, lengthscales)
+# --base-kernel values (conv layers); "acos" takes gpflow's default parameters (a spec may carry its own three), the others (variance, lengthscales)
 BASE_KERNELS = {"rbf": RBF, "acos": ArcCosine, "matern32": Matern32, "matern52": Matern52}
 
 
@@ -31,7 +31,11 @@ def build_layers_from_spec(spec):
         kind = c.get("base", "rbf")
         if kind not in BASE_KERNELS:
             raise ValueError("Not a valid base-kernel value")
-        base = ArcCosine(view.patch_length, order=0) if kind == "acos" else BASE_KERNELS[kind](view.patch_length, c["variance"], c["ls"])
+        if kind == "acos":      # optional key acos = (variance, weight_variances, bias_variance); absent: gpflow's defaults
+            av, aw, ab = c.get("acos", (1.0, 1.0, 1.0))
+            base = ArcCosine(view.patch_length, order=0, variance=av, weight_variances=aw, bias_variance=ab)
+        else:
+            base = BASE_KERNELS[kind](view.patch_length, c["variance"], c["ls"])
         mf = c.get("mean_function")
         if mf == "conv2d":      # --identity-mean: Conv2dMean(filter_size, NHWC[3], feature_map, stride=stride), conv_gp/models.py:95-97
             mf = Conv2dMean(c["f"], c["C"], c["R"], stride=c["s"])

@@ -82,6 +82,7 @@ class ArcCosine:
     def K(self, X, X2=None):
         X = np.asarray(X, FLOAT)
         den = np.sqrt(self._weighted_product(X))
+        same = X2 is None
         if X2 is None:
             X2, den2 = X, den
         else:
@@ -90,6 +91,11 @@ class ArcCosine:
         cos_theta = self._weighted_product(X, X2) / den[:, None] / den2[None, :]
         jitter = 1e-15
         theta = np.arccos(jitter + (1.0 - 2.0 * jitter) * cos_theta)
+        if same:
+            # k(x, x): cos == 1 identically in x and in both variances, so theta = acos(1 - 1e-15) there.  Evaluated from the rounded
+            # quotient above, one ulp of cos moves the entry by ~1e-9 variance, which inv(K_uu) amplifies: the floors of
+            # tests/test_host_acos.py fall from 1e-7 / 6e-4 to 6e-9 / 2e-7 with the constant written out
+            theta[np.diag_indices_from(theta)] = np.arccos(1.0 - jitter)
         return self.variance * (1.0 / np.pi) * (np.pi - theta)
 
     def Kdiag(self, X):

@@ -8,8 +8,9 @@ file differentiates the oracle's forward pass (`oracle/layers.py`, `oracle/condi
 differences of `DGP_Base.compute_log_likelihood` (tests/test_oracle_cpu.py).  PARITY UNPINNED in the same
 sense as the rest of the oracle.
 
-Scope: RBF base kernels with one lengthscale -- or ArcCosine(order 0) on the conv layers, pinned at kernel level only
-(finite differences of the ELBO cannot see past the rounding noise of acos(1 - 1e-15) on the K_uu diagonal) --, `ConvLayer`s (mean function None or the fixed `Conv2dMean`) followed by an
+Scope: RBF base kernels with one lengthscale -- or ArcCosine(order 0) on the conv layers, pinned at kernel level
+(tests/test_oracle_cpu.py) and, at non-unit parameters on live specs, entry by entry against torch autograd of a forward whose K_uu
+diagonal is the closed form variance (1 - acos(1 - 1e-15) / pi) (tests/acos_ref.py, tests/test_host_acos.py) --, `ConvLayer`s (mean function None or the fixed `Conv2dMean`) followed by an
 `SVGP_Layer` whose kernel is `ConvKernel`, `AdditivePatchKernel` or the dense `RBF(ARD=True)` of `--last-kernel rbf`;
 whitened or not.  Gradients are taken
 with respect to the constrained values (variance, lengthscales, Z, q_mu, q_sqrt (lower triangle),
@@ -129,6 +130,7 @@ def _acos_backward(kern, Zm, Xc, dK, skip_diag=False):
         F = dK * var / np.pi * (1.0 - 2e-15) / np.sin(theta)           # dLoss/dc
     if skip_diag:
         F[np.diag_indices(min(F.shape))] = 0.0
+        K[np.diag_indices(min(K.shape))] = var * (np.pi - np.arccos(1.0 - 1e-15)) / np.pi      # ArcCosine.K(Z)'s diagonal (gpflow_ref.py)
     F1 = F / rt
     F2 = F * c
     dZ = w * (F1 @ Xc - (F2.sum(1) / Q)[:, None] * Zm)

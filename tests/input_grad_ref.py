@@ -68,11 +68,13 @@ def head_marginals(spec, X, zs):
         cols = pt.reshape(S * N * P, -1)
         Z = _t(c["Z"])
         if c.get("base", "rbf") == "acos":
-            # (K_uu's diagonal is acos at 1 - 1e-15, where one ulp of the cosine moves K by 1e-9: it is DEFINED by its float64 evaluation,
-            # gpflow's expression order in NumPy; parameter-only, nothing differentiates through it)
+            # (K_uu's diagonal is acos at 1 - 1e-15, where one ulp of the cosine moves K by 1e-9: it is the constant 1 - acos(1 - 1e-15) / pi,
+            # written out as the oracle and the device write it; parameter-only, nothing differentiates through it)
             Zn = np.asarray(c["Z"], np.float64)
             den = np.sqrt(np.sum(1.0 * np.square(Zn), axis=1) + 1.0)
-            Kuu = _t(1.0 * (1.0 / np.pi) * (np.pi - np.arccos(1e-15 + (1.0 - 2e-15) * (((1.0 * Zn) @ Zn.T + 1.0) / den[:, None] / den[None, :]))))
+            theta = np.arccos(1e-15 + (1.0 - 2e-15) * (((1.0 * Zn) @ Zn.T + 1.0) / den[:, None] / den[None, :]))
+            theta[np.diag_indices_from(theta)] = np.arccos(1.0 - 1e-15)
+            Kuu = _t(1.0 * (1.0 / np.pi) * (np.pi - theta))
             Kuf, kff = _acos0(Z, cols), torch.ones(cols.shape[0], dtype=T)
         else:
             Kuu, Kuf = _rbf(Z, Z, c["variance"], c["ls"]), _rbf(Z, cols, c["variance"], c["ls"])

@@ -188,8 +188,9 @@ def torch_reference(spec, X, Y, zs):
     return e_t.item(), want
 
 
-SPEC_KEY = {"Z": "Z", "q_mu": "q_mu", "q_sqrt": "q_sqrt", "variance": "variance", "lengthscales": "ls", "patch_weights": "w"}
-POSITIVE = ("variance", "lengthscales")      # softplus + 1e-6 in gpflow's unconstrained space
+SPEC_KEY = {"Z": "Z", "q_mu": "q_mu", "q_sqrt": "q_sqrt", "variance": "variance", "lengthscales": "ls", "patch_weights": "w",
+            "weight_variances": "weight_variances", "bias_variance": "bias_variance"}      # (the last two: tests/acos_ref.py's flattened specs)
+POSITIVE = ("variance", "lengthscales", "weight_variances", "bias_variance")      # softplus + 1e-6 in gpflow's unconstrained space
 
 
 def softplus_inv(x):
@@ -221,8 +222,11 @@ def model_values(model):
     for li, l in enumerate(model.layers):
         head = li == len(model.layers) - 1
         kern = l.kern.base_kernel if head else l.base_kernel
-        d = dict(Z=np.array(l.feature.Z), q_mu=np.array(l.q_mu), q_sqrt=np.array(l.q_sqrt), variance=float(kern.variance),
-                 lengthscales=float(kern.lengthscales))
+        d = dict(Z=np.array(l.feature.Z), q_mu=np.array(l.q_mu), q_sqrt=np.array(l.q_sqrt), variance=float(kern.variance))
+        if hasattr(kern, "lengthscales"):
+            d["lengthscales"] = float(kern.lengthscales)
+        else:                                             # ArcCosine(order 0)
+            d["weight_variances"], d["bias_variance"] = float(kern.weight_variances), float(kern.bias_variance)
         if head:
             d["patch_weights"] = np.array(l.kern.patch_weights)
         out.append(d)

@@ -12,7 +12,11 @@ def oracle_layers(spec):
     layers = []
     for c in spec["convs"]:
         view = FullView((c["H"], c["W"]), c["f"], c["C"], c["s"])
-        rbf = ArcCosine(view.patch_length, order=0) if c.get("base", "rbf") == "acos" else RBF(view.patch_length, c["variance"], c["ls"])
+        if c.get("base", "rbf") == "acos":      # optional key acos = (variance, weight_variances, bias_variance); absent: gpflow's defaults
+            av, aw, ab = c.get("acos", (1.0, 1.0, 1.0))
+            rbf = ArcCosine(view.patch_length, order=0, variance=av, weight_variances=aw, bias_variance=ab)
+        else:
+            rbf = RBF(view.patch_length, c["variance"], c["ls"])
         mean = None
         if c.get("mean_function") == "conv2d":   # Conv2dMean, conv_gp/models.py:97-100
             from oracle.mean_functions import Conv2dMean

@@ -29,10 +29,9 @@ below the entry floor).  S = 2 except the two ch cases, S = 4 (15 x 4 x 144 = 86
     conv2d_mean_M24   24   3   1.0  0.1   1.2e+01 (L1 variance)      2.2e-02 (L1 q_mu)    0.002 (L1)
 
 The last three are the model variants the textbook forward supports (12 x 12 x 1 images, conv (3, 1, 3), head (3, 1)): the additive head,
-the dense RBF(ARD) head, Conv2dMean.  The arc-cosine base kernel is left out: the textbook forward holds its weight_variances and
-bias_variance as constants (no leaf, so no reference for two of the device's groups), and autograd differentiates acos at the coincident
-points of K_uu (slope 2e7 at 1 - 1e-15), which oracle/grad.py skips on purpose -- the forward is value-only for that kernel
-(test_arccosine_forward_matches_torch).  Its gradient stays with test_gradients_match_oracle.
+the dense RBF(ARD) head, Conv2dMean.  The arc-cosine base kernel has this module's scheme in tests/test_gpu_acos.py, at non-unit variance,
+weight_variances and bias_variance: its reference (tests/acos_ref.py) has leaves for all three and writes K_uu's diagonal as the closed
+form of the variance alone, so autograd never differentiates acos at the coincident points (slope 2e7 at 1 - 1e-15).
 
 Rounding floor of the comparison: oracle/grad.py against torch autograd, two independent float64 implementations, on every case on the CPU.
 Largest error over the groups of a case, group-wise (|a - b|max / |want|max) / entry-wise (|a - b| / |want| over the entries with
