@@ -42,6 +42,9 @@ struct DcgpOptions {
                                  // (-1: chosen by a simulated deal; 0: never; k > 0: up to k per spare workgroup)
   long fused_parts = -1;         // layer kernel on few strips (< 1.5 rounds of the CUs): every strip's prologue by one item, its outputs by q parts that fetch A1
                                  // (-1, 0: never -- measured slower at every shard, conv_fused.hip: plan_parts; q > 0: this many parts; -2: q by the simulated deal)
+  long fused_rep_share = -1;     // persistent layer kernel on a tiled batch: the strips that show the same images at the same patches share one prologue, handed over by
+                                 // the first of them (-1: where the simulated deal has it ahead; 0: never -- the launch of fused_pre alone)
+  long fused_wgs = 0;            // persistent layer kernel: this many workgroups instead of one per slot of the chip (0: all; tests: several rounds on a small layer)
   long fused_stagger = -1;       // persistent layer kernel: microseconds the second workgroup of a CU holds back (-1: default; 0: none)
   long kl_side = 0;              // KL terms by their own launches on the side stream instead of inside the tail launch
   long sweep_no_rows = 0;        // long-patch sweeps (5 x 5 x 10 patches) on the generic streamed loop instead of the patch-row form (A/B)
@@ -125,6 +128,7 @@ struct dcgp_ctx {
   // pinned host scratch for small result read-backs
   double* h_scratch = nullptr;   // 64 doubles
   int* h_info = nullptr;         // 16 ints
+  int fused_plan[4] = {0, 0, 0, 0};   // debugging aid (dcgp_debug_fused_plan): the most recent layer-kernel launch -- persistent workgroups, items, hand-over slots, shared D
   long long* fused_trace = nullptr;   // debugging aid (dcgp_debug_set_fused_trace): phase stamps of the one-launch layer kernel
   std::string sweep_trace_family;     // ... of the launches of this timer family only ("kuf", "kuf_long", "head_sweep")
   long long* sweep_trace = nullptr; long sweep_trace_wgs = 0;   // debugging aid (dcgp_debug_set_sweep_trace): stamps of every workgroup of the patch sweeps

@@ -116,7 +116,7 @@ __global__ __launch_bounds__(NT) void conv_fused_kernel(ConvFusedArgs a_in) {
     __syncthreads();
   }
   // (a workgroup that starts when every item has been dealt -- more workgroups than CUs it may run on -- has nothing to do but sign off)
-  const int first_limit = a.pre_n > 0 ? a.n_strips + a.pre_n * a.pre_sq : 0x7fffffff;
+  const int first_limit = a.pre_n > 0 ? a.n_items : 0x7fffffff;
   for (int it = 0; strip_next < first_limit; ++it) {
   // every strip sees the kernarg pointer and the thread index as new values: nothing of a strip's set-up (argument words, per-lane offsets of every
   // phase) is then loop-invariant, hoisted and kept live across the whole body -- as plain invariants they cost 240 spilled VGPRs at 16 waves
@@ -154,9 +154,16 @@ __global__ __launch_bounds__(NT) void conv_fused_kernel(ConvFusedArgs a_in) {
   // of the strips [pre_first, pre_first + pre_n) and leave A1 (the LDS image of the strip) and the partial sums of A1^2 in a.pre_buf: they fill the
   // first round's spare workgroups; then the remaining strips whole; then the pre_n strips again, which fetch their A1 and go straight to phase 3.
   // Same arithmetic in the same order as a whole strip: bit-identical.
+  // Replicas share a prologue (a.pre_D > 0: the rows are a batch of n_mod images tiled, n_mod * P columns = pre_D whole strips, so that strip i shows the images
+  // of strip i % pre_D at the same patches: K_uf, A1 and the partial sums of A1^2 are the same numbers).  One item per strip, strip i the i-th the counter deals:
+  // the strips below pre_D run whole AND leave their A1 in slot i of a.pre_buf on the way (mode 3), the other strips below pre_whole (the rest of the first
+  // round) run whole, every later strip fetches slot i % pre_D.  A slot's writer is an earlier item than any of its readers and waits for nobody.
   bool pre_fail = false;
-  int mode = 0, pre_slot = 0;   // 0: a whole strip; 1: phases 0 - 2 only, A1 left in a.pre_buf; 2: A1 fetched from a.pre_buf, phases 3 - 4
-  if (a.pre_n > 0) {
+  int mode = 0, pre_slot = 0;   // 0: a whole strip; 1: phases 0 - 2 only, A1 left in a.pre_buf; 2: A1 fetched from a.pre_buf, phases 3 - 4; 3: whole, A1 left as well
+  if (a.pre_D > 0) {
+    if (strip_next < a.pre_D) { mode = 3; pre_slot = strip_next; }
+    else if (strip_next >= a.pre_whole) { mode = 2; pre_slot = strip_next % a.pre_D; }
+  } else if (a.pre_n > 0) {
     if (strip_next >= a.n_strips) {   // (pre_sq > 1: part sq of the strip's SQ, the split of a shared last round applied to a strip whose A1 is fetched)
       mode = 2;
       const int t = strip_next - a.n_strips;
@@ -528,7 +535,7 @@ __global__ __launch_bounds__(NT) void conv_fused_kernel(ConvFusedArgs a_in) {
   __syncthreads();   // A1 published
   CF_TR(5)
   if (a.A1_out && sq == 0) store_strip(a.A1_out);
-  if (mode == 1) {
+  if (mode & 1) {
     // the strip as it lies in LDS and the [TW][BN] partial sums behind it, by coherent (sc1) stores another XCD's loads see (chol_fused.hip: ldg / stg);
     // acknowledged before the barrier in front of the flag
     double* __restrict__ dst = a.pre_buf + (long)pre_slot * a.pre_stride;
@@ -786,7 +793,7 @@ __global__ __launch_bounds__(NT) void conv_fused_kernel(ConvFusedArgs a_in) {
   if (tid == 0) ticket[0] = a.dyn ? (a.pre_n > 0 ? 0 : (int)gridDim.x) + atomicAdd(a.dyn, 1) : strip_next + (int)gridDim.x;
   __syncthreads();   // (and the partial sums are read: the next strip's images may land on them)
   strip_next = __builtin_amdgcn_readfirstlane(ticket[0]);
-  if (strip_next >= a.n_strips + a.pre_n * a.pre_sq) break;
+  if (strip_next >= a.n_items) break;
   }
   if (threadIdx.x == 0) {
     if (cu_word >= 0) atomicSub(ap->cu_slots + cu_word, 1);
@@ -879,14 +886,16 @@ double last_round(const dcgp_ctx* ctx, const FusedShape& sh, long strips, int R,
 // The items are dealt in list order to whichever workgroup is free; this returns the makespan of that deal in units of one output of the second product
 // (sweep + first product 1.75, epilogue 0.3, hand-over 0.2 on either side: the phase times of profiles/r06_fused_phase_trace.txt at M = 256), for n_pre
 // prologues ahead, a hand-over waiting for its prologue where the deal has it so.
-double deal_makespan(long strips, int slots, long n_pre, int R) {
+// share_D > 0: replicas share a prologue (plan_rep_share) -- strip i < share_D whole and leaving its A1 on the way (ready once its prologue and the hand-over are
+// through), the rest of the first round whole, every later strip fetching the A1 of strip i % share_D.
+double deal_makespan(long strips, int slots, long n_pre, int R, long share_D = 0) {
   const double pro = 1.75, epi = 0.3, io = 0.2;
   const double F = pro + R + epi, P = pro + io, C = io + R + epi;
-  if (n_pre <= 0) return (double)((strips + slots - 1) / slots) * F;
+  if (n_pre <= 0 && share_D <= 0) return (double)((strips + slots - 1) / slots) * F;
   const long rem = strips % slots;
   std::priority_queue<double, std::vector<double>, std::greater<double>> free_at;
   for (int i = 0; i < slots; ++i) free_at.push(0.0);
-  std::vector<double> ready((size_t)n_pre, 0.0);
+  std::vector<double> ready((size_t)std::max<long>(n_pre, 0), 0.0);
   double end = 0.0;
   auto give = [&](double cost, double not_before) {
     double t = free_at.top();
@@ -897,6 +906,16 @@ double deal_makespan(long strips, int slots, long n_pre, int R) {
     if (t > end) end = t;
     return t;
   };
+  if (share_D > 0) {
+    const long whole = std::max<long>(share_D, std::min<long>(slots, strips));
+    ready.assign((size_t)share_D, 0.0);
+    for (long i = 0; i < strips; ++i) {
+      if (i < share_D) ready[(size_t)i] = give(F + io, 0.0) - (R + epi);
+      else if (i < whole) give(F, 0.0);
+      else give(C, ready[(size_t)(i % share_D)]);
+    }
+    return end;
+  }
   for (long i = 0; i < rem; ++i) give(F, 0.0);
   for (long i = 0; i < n_pre; ++i) ready[(size_t)i] = give(P, 0.0);
   for (long i = 0; i < strips - rem - n_pre; ++i) give(F, 0.0);
@@ -972,6 +991,33 @@ long plan_prologues(const dcgp_ctx* ctx, long strips, int slots, int R) {
   memo[key] = best_n;
   return best_n;
 }
+// Replicas share a prologue: the number of distinct strips D of a tiled batch whose prologues the launch hands over (0: today's plan).  propagate() tiles the
+// minibatch S times in front of the first layer, so row n shows image n % n_mod: where n_mod * P columns are a whole number D of strips, strip i reads the images
+// of strip i % D at the same patch positions and its K_uf, A1 and sum A1^2 are the same numbers, bit for bit.  Nothing is shared across a strip that straddles
+// two replicas (a period that is no whole number of strips), with `rep` in force (the outputs are already laid out per replica) or in the launch that keeps
+// K_uf / A1 for the reverse pass (not persistent).  n_pre: what plan_prologues chose for the same launch -- the shared plan must beat that deal and the plain
+// launch by plan_prologues' own margin.
+long plan_rep_share(const dcgp_ctx* ctx, const ConvFusedArgs& a, long strips, int slots, int BN, long n_pre) {
+  if (ctx->opt.fused_rep_share == 0 || ctx->opt.fused_pre >= 0) return 0;   // (fused_pre 0: no hand-over of any kind; k > 0: that plan, forced)
+  if (a.n_mod <= 0 || a.rep != 1 || a.P <= 0 || a.Kc % a.P || a.Kuf_out || a.A1_out) return 0;
+  const long rows = a.Kc / a.P, period = (long)a.n_mod * a.P;
+  if (rows % a.n_mod || rows / a.n_mod < 2 || period % BN) return 0;
+  const long D = period / BN;
+  if (D >= strips || D > 4L * slots) return 0;   // (the hand-over area: a strip's LDS image per slot)
+  static std::mutex mu;
+  static std::map<std::array<long, 5>, long> memo;
+  const std::array<long, 5> key = {strips, (long)slots, (long)a.R, D, n_pre};
+  std::lock_guard<std::mutex> lock(mu);
+  auto it = memo.find(key);
+  if (it != memo.end()) return it->second;
+  const double plain = deal_makespan(strips, slots, 0, a.R);
+  const double today = n_pre > 0 ? std::min(plain, deal_makespan(strips, slots, n_pre, a.R)) : plain;
+  const double shared = deal_makespan(strips, slots, 0, a.R, D);
+  const long chosen = shared < today * 0.98 - 1e-9 ? D : 0;
+  if (memo.size() > 256) memo.clear();
+  memo[key] = chosen;
+  return chosen;
+}
 
 // the first instantiated shape (widest strip, most waves) that covers Mp and whose LDS footprint fits
 bool plan_fused(const dcgp_ctx* ctx, const ConvFusedArgs& a, FusedPlan* p) {
@@ -1028,6 +1074,14 @@ extern "C" int dcgp_debug_set_fused_trace(dcgp_ctx* ctx, long long* buf_dev) {
   return DCGP_OK;
 }
 
+// debugging aid (tests): how the most recent layer-kernel launch of the ctx was dealt -- out4 = {persistent workgroups (0: one workgroup per strip), items the
+// counter deals, hand-over slots, distinct strips D whose prologues the replicas share (0: not shared)}
+extern "C" int dcgp_debug_fused_plan(dcgp_ctx* ctx, int* out4) {
+  if (!ctx || !out4) return DCGP_ERR_ARG;
+  for (int i = 0; i < 4; ++i) out4[i] = ctx->fused_plan[i];
+  return DCGP_OK;
+}
+
 bool conv_fused_ok(const dcgp_ctx* ctx, const ConvFusedArgs& a) {
   const bool off = ctx->opt.no_fused_layer != 0;   // A/B switch (tests flip it through dcgp_ctx_set_option): the unfused sweep + GEMM route
   FusedPlan p;
@@ -1045,7 +1099,8 @@ int conv_fused(dcgp_ctx* ctx, const ConvFusedArgs& a_in) {
   a.no_rows = ctx->opt.sweep_no_rows ? 1 : 0;
   a.inv_HWC = 1.0f / (float)a.HWC; a.inv_nmod = 1.0f / (float)a.n_mod; a.inv_P = 1.0f / (float)a.P; a.inv_Wo = 1.0f / (float)a.Wo; a.inv_R = 1.0f / (float)a.R;
   const long strips = ((long)a.Kc + kShapes[p.shape].FN * 16 - 1) / (kShapes[p.shape].FN * 16);
-  const int n_cus = ctx->n_cus > 0 ? ctx->n_cus : 256;
+  const int all_cus = ctx->n_cus > 0 ? ctx->n_cus : 256;
+  const int n_cus = ctx->opt.fused_wgs > 0 && ctx->opt.fused_wgs < all_cus ? (int)ctx->opt.fused_wgs : all_cus;   // (fused_wgs: a small layer in several rounds, tests)
   // workgroups a CU holds: LDS (160 KB) and wave slots (the kernels are held to 128 registers: 16 waves of 64 per CU)
   const long per_cu = std::min<long>(160 * 1024 / (long)p.lds, 1024 / kShapes[p.shape].NT);
   // chosen (-1): where a workgroup owns its CU and no strip of the last round is shared.  What it buys is the deal, not the persistence: strips handed out
@@ -1066,6 +1121,7 @@ int conv_fused(dcgp_ctx* ctx, const ConvFusedArgs& a_in) {
   if (persist) {
     a.persist = (int)(per_cu * n_cus);
     a.n_strips = (int)strips;
+    a.n_items = (int)strips;
     if (want != 2) {   // (2: the fixed deal blockIdx, blockIdx + grid, ... -- A/B)
       // ONE counter pair (and one hand-over area, below) per ctx: ws_tag is empty by the time a layer runs, so the names carry no bank.  Safe because a
       // ctx's layer launches are serialised on one main stream (a step on the other main stream starts behind the previous one's end, model.hip)
@@ -1077,11 +1133,20 @@ int conv_fused(dcgp_ctx* ctx, const ConvFusedArgs& a_in) {
     }
     if (per_cu == 1 && a.dyn && a.G) {
       const int TW = kShapes[p.shape].NT / 64 / kShapes[p.shape].NS, BN = kShapes[p.shape].FN * 16;
-      const long n_pre = parts_sq > 1 ? strips : plan_prologues(ctx, strips, a.persist, a.R);
+      long n_pre = parts_sq > 1 ? strips : plan_prologues(ctx, strips, a.persist, a.R);
+      const long share_D = parts_sq > 1 ? 0 : plan_rep_share(ctx, a, strips, a.persist, BN, n_pre);
+      if (share_D > 0) n_pre = share_D;   // one slot per distinct strip
       if (n_pre > 0) {
         a.pre_n = (int)n_pre;
         a.pre_first = parts_sq > 1 ? 0 : (int)(strips % a.persist);
         a.pre_sq = parts_sq > 1 ? parts_sq : 1;
+        if (share_D > 0) {
+          a.pre_D = (int)share_D;
+          a.pre_whole = (int)std::max<long>(share_D, std::min<long>(a.persist, strips));
+          a.pre_first = 0;
+        } else {
+          a.n_items = (int)(strips + n_pre * a.pre_sq);
+        }
         a.pre_stride = (long)a.Mp * BN + (long)TW * BN;
         const std::string nb = "fused_pre_buf" + ctx->ws_tag, nf = "fused_pre_flag" + ctx->ws_tag;
         const size_t fbytes = (size_t)n_pre * sizeof(unsigned);
@@ -1109,6 +1174,7 @@ int conv_fused(dcgp_ctx* ctx, const ConvFusedArgs& a_in) {
     a.split_q = p.split_q;
     a.split_first = (int)(strips - strips % n_cus);
   }
+  ctx->fused_plan[0] = a.persist; ctx->fused_plan[1] = a.persist ? a.n_items : 0; ctx->fused_plan[2] = a.pre_n; ctx->fused_plan[3] = a.pre_D;
   ScopedTimer t(ctx, "conv_fused");
 #ifdef DCGP_EXPERIMENTS
   const int abl = (int)ctx->opt.fused_abl;   // timing build only (make EXPERIMENTS=1): wrong results

@@ -136,6 +136,11 @@ struct ConvFusedArgs {
   int no_rows = 0;                                         // set by the launcher (ctx option sweep_no_rows): 5 x 5 x 10 patches on the generic in-kernel sweep (A/B)
   int pre_n = 0, pre_first = 0, pre_sq = 1; long pre_stride = 0;
   double* pre_buf = nullptr; unsigned* pre_flag = nullptr; unsigned pre_epoch = 0;
+  // set by the launcher: items the counter deals in a persistent launch (n_strips + pre_n * pre_sq; n_strips where replicas share a prologue)
+  int n_items = 0;
+  // set by the launcher: replicas share a prologue (conv_fused.hip) -- the rows are n_mod images tiled and n_mod * P columns are pre_D whole strips: strip i < pre_D
+  // runs whole and leaves A1 in slot i (pre_n = pre_D slots), strips in [pre_D, pre_whole) run whole, strip i >= pre_whole fetches slot i % pre_D
+  int pre_D = 0, pre_whole = 0;
 };
 // the reverse pass of the same strip (conv_bwd_fused.hip): dK_uf = inv(L)^T [sum_r (S_r A1) o (2 gv_r) + alpha gm^T - 2 A1 o gvs]
 struct ConvBwdArgs {

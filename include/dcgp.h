@@ -548,6 +548,9 @@ int dcgp_debug_comm_gate(dcgp_ctx* ctx, int closed, int* main_idle_out);
 /* Device buffer of 8 x 16 x 16 int64 into which the one-launch conv layer kernel (csrc/conv_fused.hip) stamps the shader
  * clock at its phase boundaries (8 sampled workgroups x 4 strips of a persistent one x 16 waves x 16 stamps = 8192 words); NULL switches it off (tools/fused_trace.py). */
 int dcgp_debug_set_fused_trace(dcgp_ctx* ctx, long long* buf_dev);
+/* How the most recent launch of that kernel was dealt: out4 = {persistent workgroups (0: one workgroup per strip), items the device counter deals,
+ * hand-over slots, distinct strips whose prologue the replicas of a tiled batch share (0: not shared)}. */
+int dcgp_debug_fused_plan(dcgp_ctx* ctx, int* out4);
 /* The same for the patch sweeps (csrc/head_units.hip; tools/sweep_trace.py): [n_workgroups][waves per workgroup][8] int64 -- wall clock at entry,
  * shader clock at entry / image staged / set-up done / first unit done / last unit done, wall clock at exit, units run.            */
 /* The ceilings bench.py prices kernels against, measured on this device (csrc/peaks.hip): the sustained fp64 MFMA rate (TFLOP/s, 4 waves
