@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/dcgp.h"
+#include "fused_plan.h"
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 
@@ -41,7 +42,7 @@ struct DcgpOptions {
   long fused_pre = -1;           // persistent layer kernel: prologues (sweep + first product) of later strips run by the spare workgroups of a partial first round
                                  // (-1: chosen by a simulated deal; 0: never; k > 0: up to k per spare workgroup)
   long fused_parts = -1;         // layer kernel on few strips (< 1.5 rounds of the CUs): every strip's prologue by one item, its outputs by q parts that fetch A1
-                                 // (-1, 0: never -- measured slower at every shard, conv_fused.hip: plan_parts; q > 0: this many parts; -2: q by the simulated deal)
+                                 // (-1, 0: never -- measured slower at every shard, fused_plan.h; q > 0: this many parts; -2: q by the simulated deal)
   long fused_rep_share = -1;     // persistent layer kernel on a tiled batch: the strips that show the same images at the same patches share one prologue, handed over by
                                  // the first of them (-1: where the simulated deal has it ahead; 0: never -- the launch of fused_pre alone)
   long fused_wgs = 0;            // persistent layer kernel: this many workgroups instead of one per slot of the chip (0: all; tests: several rounds on a small layer)
@@ -114,7 +115,7 @@ struct dcgp_ctx {
   hipEvent_t ev_g[6] = {};
   hipEvent_t ev_aux = nullptr, ev_aux2 = nullptr;  // fork / join of a short side-stream excursion inside a layer
   std::string err;
-  std::map<std::string, unsigned> fused_pre_epochs;   // per hand-over area of the layer kernel's prologues ahead (conv_fused.hip): launches so far
+  unsigned fused_pre_epoch = 0;   // the hand-over area of the layer kernel (conv_fused.hip): launches that used it so far
   std::string ws_tag;   // suffix of the chain's / KL terms' scratch names: steps in flight on the two banks must not share them
   // named, grow-only device workspaces owned by the ctx
   std::map<std::string, std::pair<void*, size_t>> ws;
@@ -128,7 +129,7 @@ struct dcgp_ctx {
   // pinned host scratch for small result read-backs
   double* h_scratch = nullptr;   // 64 doubles
   int* h_info = nullptr;         // 16 ints
-  int fused_plan[4] = {0, 0, 0, 0};   // debugging aid (dcgp_debug_fused_plan): the most recent layer-kernel launch -- persistent workgroups, items, hand-over slots, shared D
+  fused_plan::Plan last_fused_plan;   // debugging aid (dcgp_debug_fused_plan): how the most recent layer-kernel launch was dealt
   long long* fused_trace = nullptr;   // debugging aid (dcgp_debug_set_fused_trace): phase stamps of the one-launch layer kernel
   std::string sweep_trace_family;     // ... of the launches of this timer family only ("kuf", "kuf_long", "head_sweep")
   long long* sweep_trace = nullptr; long sweep_trace_wgs = 0;   // debugging aid (dcgp_debug_set_sweep_trace): stamps of every workgroup of the patch sweeps

@@ -18,12 +18,10 @@
 // inside any k loop (5 barriers per workgroup in all), HBM traffic = the images in and the samples out.
 // Row fragments are dealt to the waves boustrophedon (w, 2W-1-w, 2W+w, ...) so that every wave carries the same number
 // of live k-tiles of the triangular products.
-#include <array>
-#include <map>
-#include <mutex>
-#include <queue>
-#include <vector>
+#include <cstring>
+#include <tuple>
 
+#include "fused_plan.h"
 #include "layer.h"
 #include "rng.h"
 
@@ -806,268 +804,67 @@ __global__ __launch_bounds__(NT) void conv_fused_kernel(ConvFusedArgs a_in) {
   }
 }
 
-// the instantiated shapes: <FN, NS, MAXF, NT>
-//   0: <4,2,2,1024>  Mp <= 256, 64-column strips, 16 waves in two teams       1: <4,1,2,512>  the same on 8 waves
-//   2: <2,1,2,512>   Mp <= 256, 32-column strips (large images)               3: <1,1,2,512>  16-column strips
-//   4: <2,1,2,768>   Mp <= 384 (12 waves)     5: <2,1,2,1024>  Mp <= 512      6: <1,1,4,1024>  Mp <= 1024
-struct FusedShape { int FN, NS, MAXF, NT, max_nf; };
-constexpr FusedShape kShapes[] = {{4, 2, 2, 1024, 16}, {4, 1, 2, 512, 16}, {2, 1, 2, 512, 16}, {1, 1, 2, 512, 16},
-                                  {2, 1, 2, 768, 24},  {2, 1, 2, 1024, 32}, {1, 1, 4, 1024, 64},
-                                  {2, 2, 2, 1024, 16}};   // 7: a 32-column strip on 16 waves, two teams splitting the outputs (few columns: a rank's shard)
-constexpr int kNumShapes = sizeof(kShapes) / sizeof(kShapes[0]);
+using fused_plan::kShapes;
+using fused_plan::Plan;
+using fused_plan::Query;
 
-template <int FN, int NS, int MAXF, int NT>
-int launch_fused(dcgp_ctx* ctx, const ConvFusedArgs& a, size_t lds) {
-  const int BN = FN * 16;
-  const long strips = ((long)a.Kc + BN - 1) / BN;
-  const unsigned grid = (unsigned)(a.persist ? a.persist : (a.split_q > 1 ? a.split_first + (strips - a.split_first) * a.split_q : strips));
+// one launch of instance BTP (the base kernel's, or the patch-row form of the RBF sweep) of shape I of the table (fused_plan.h)
+template <int I, int BTP>
+int launch_instance(dcgp_ctx* ctx, const ConvFusedArgs& a, const Plan& p) {
+  constexpr int FN = kShapes[I].FN, NS = kShapes[I].NS, MAXF = kShapes[I].MAXF, NT = kShapes[I].NT;
   static bool attr_done[64] = {};   // per device: a second ctx on another device of this process needs the opt-in too
   const int dv = ctx->device >= 0 && ctx->device < 64 ? ctx->device : 0;
   if (!attr_done[dv]) {   // more than 64 KB of dynamic LDS needs the opt-in
-    hipFuncSetAttribute((const void*)conv_fused_kernel<FN, NS, MAXF, NT, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipFuncSetAttribute((const void*)conv_fused_kernel<FN, NS, MAXF, NT, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipFuncSetAttribute((const void*)conv_fused_kernel<FN, NS, MAXF, NT, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipFuncSetAttribute((const void*)conv_fused_kernel<FN, NS, MAXF, NT, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipFuncSetAttribute((const void*)conv_fused_kernel<FN, NS, MAXF, NT, BTP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr_done[dv] = true;
   }
-  const bool rows50 = a.bk.type == 0 && a.f * a.C == 50 && (a.f & 1) && a.L == a.f * a.f * a.C && a.Lz == ((a.L + 2 + 3) & ~3) && !a.no_rows;
-  if constexpr (FN == 4 && NS == 2) {   // (the patch-row instance only where such layers run: the 64-column strip on 16 waves)
-    if (rows50) {
-      static bool attr2[64] = {};
-      if (!attr2[dv]) {
-        hipFuncSetAttribute((const void*)conv_fused_kernel<FN, NS, MAXF, NT, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr2[dv] = true;
-      }
-      hipLaunchKernelGGL((conv_fused_kernel<FN, NS, MAXF, NT, 2>), dim3(grid), dim3(NT), lds, ctx->stream, a);
-      LAUNCH_CHECK(ctx);
-      return DCGP_OK;
-    }
-  }
-  if (a.bk.type == 0) hipLaunchKernelGGL((conv_fused_kernel<FN, NS, MAXF, NT, 0>), dim3(grid), dim3(NT), lds, ctx->stream, a);
-  else if (a.bk.type == 1) hipLaunchKernelGGL((conv_fused_kernel<FN, NS, MAXF, NT, 1>), dim3(grid), dim3(NT), lds, ctx->stream, a);
-  else if (a.bk.type == 2) hipLaunchKernelGGL((conv_fused_kernel<FN, NS, MAXF, NT, 3>), dim3(grid), dim3(NT), lds, ctx->stream, a);
-  else if (a.bk.type == 3) hipLaunchKernelGGL((conv_fused_kernel<FN, NS, MAXF, NT, 4>), dim3(grid), dim3(NT), lds, ctx->stream, a);
-  else return ctx_fail(ctx, DCGP_ERR_ARG, "conv_fused: unknown base kernel type %d", a.bk.type);
+  hipLaunchKernelGGL((conv_fused_kernel<FN, NS, MAXF, NT, BTP>), dim3((unsigned)p.grid), dim3(NT), (size_t)p.lds, ctx->stream, a);
   LAUNCH_CHECK(ctx);
   return DCGP_OK;
 }
-
-struct FusedPlan { int shape; size_t lds; int lds_main, lds_img; int split_q; };
-
-// The partial last round.  A 1024-thread strip owns its CU, so `strips` workgroups take ceil(strips / CUs) strip times and the last round
-// leaves CUs idle.  Where they are enough, its strips are shared by Q workgroups each: every one of them runs the sweep and the first product
-// (~0.11 of a strip, `kFront`) and the outputs r = q, q + Q, ... of the R-batched product, whose teams take them in turn -- a part costs
-// kFront + (1 - kFront) * (outputs of its busiest team) / (outputs of a whole strip's busiest team).  Returns the last round's cost in strip
-// times (1 unshared) and the Q to use.  Measured on shards of the headline batch (tools/shape_try.py): 90 strips of 64 columns 198 -> 118 us
-// with Q = 2, 360 strips of 32 columns on 16 waves 215 -> 174 us; the full batch (720 strips, 208 in the last round) has no CUs to share with.
-double last_round(const dcgp_ctx* ctx, const FusedShape& sh, long strips, int R, bool has_g, int* q_out) {
-  *q_out = 1;
-  const long want = ctx->opt.fused_split;
-  const int slots = ctx->n_cus > 0 ? ctx->n_cus : 256;
-  const long rem = strips % slots;
-  if (rem == 0) return 0.0;
-  if (want == 0 || want == 1 || sh.NT != 1024 || !has_g || R < 2) return 1.0;
-  constexpr double kFront = 0.11;
-  const int whole = (R + sh.NS - 1) / sh.NS;
-  const long qmax = slots / rem < R ? slots / rem : R;
-  double best = 0.9;   // a split must save a tenth of a strip time to be worth its extra sweeps
-  for (int q = 2; q <= qmax; ++q) {
-    const int part = ((R + q - 1) / q + sh.NS - 1) / sh.NS;
-    const double cost = kFront + (1.0 - kFront) * part / whole;
-    if ((want > 1 && q <= want) || (want < 0 && cost < best - 1e-9)) { best = cost; *q_out = q; }
+template <int I>
+int launch_fused(dcgp_ctx* ctx, const ConvFusedArgs& a, const Plan& p) {
+  switch (p.patch_rows ? -1 : a.bk.type) {
+    case 0: return launch_instance<I, 0>(ctx, a, p);
+    case 1: return launch_instance<I, 1>(ctx, a, p);
+    case 2: return launch_instance<I, 3>(ctx, a, p);
+    case 3: return launch_instance<I, 4>(ctx, a, p);
+    case -1:   // (the patch-row instance only where such layers run, the 64-column strip on 16 waves: the plan asks for it nowhere else)
+      if constexpr (I == 0) return launch_instance<I, 2>(ctx, a, p);
+      [[fallthrough]];
+    default: return ctx_fail(ctx, DCGP_ERR_ARG, "conv_fused: unknown base kernel type %d", a.bk.type);
   }
-  return *q_out > 1 ? best : 1.0;
 }
 
-// Prologues ahead.  A persistent launch of `slots` workgroups (one per CU) over `strips` strips runs ceil(strips / slots) strip times, and a partial
-// round leaves slots - rem workgroups idle for a whole one (720 strips on 256 CUs: 3 rounds for 2.81 of work).  Sharing a strip's OUTPUTS between workgroups re-pays
-// its sweep and first product (4h.6: no split wins).  Sharing its PROLOGUE does not: the partial round goes first, its spare workgroups run phases 0 - 2 of
-// later strips (a sixth of a strip each) and leave A1 in memory (132 KB per strip, L2 / Infinity-Cache traffic); those strips then start at the second product.
-// The items are dealt in list order to whichever workgroup is free; this returns the makespan of that deal in units of one output of the second product
-// (sweep + first product 1.75, epilogue 0.3, hand-over 0.2 on either side: the phase times of profiles/r06_fused_phase_trace.txt at M = 256), for n_pre
-// prologues ahead, a hand-over waiting for its prologue where the deal has it so.
-// share_D > 0: replicas share a prologue (plan_rep_share) -- strip i < share_D whole and leaving its A1 on the way (ready once its prologue and the hand-over are
-// through), the rest of the first round whole, every later strip fetching the A1 of strip i % share_D.
-double deal_makespan(long strips, int slots, long n_pre, int R, long share_D = 0) {
-  const double pro = 1.75, epi = 0.3, io = 0.2;
-  const double F = pro + R + epi, P = pro + io, C = io + R + epi;
-  if (n_pre <= 0 && share_D <= 0) return (double)((strips + slots - 1) / slots) * F;
-  const long rem = strips % slots;
-  std::priority_queue<double, std::vector<double>, std::greater<double>> free_at;
-  for (int i = 0; i < slots; ++i) free_at.push(0.0);
-  std::vector<double> ready((size_t)std::max<long>(n_pre, 0), 0.0);
-  double end = 0.0;
-  auto give = [&](double cost, double not_before) {
-    double t = free_at.top();
-    free_at.pop();
-    if (t < not_before) t = not_before;
-    t += cost;
-    free_at.push(t);
-    if (t > end) end = t;
-    return t;
-  };
-  if (share_D > 0) {
-    const long whole = std::max<long>(share_D, std::min<long>(slots, strips));
-    ready.assign((size_t)share_D, 0.0);
-    for (long i = 0; i < strips; ++i) {
-      if (i < share_D) ready[(size_t)i] = give(F + io, 0.0) - (R + epi);
-      else if (i < whole) give(F, 0.0);
-      else give(C, ready[(size_t)(i % share_D)]);
-    }
-    return end;
-  }
-  for (long i = 0; i < rem; ++i) give(F, 0.0);
-  for (long i = 0; i < n_pre; ++i) ready[(size_t)i] = give(P, 0.0);
-  for (long i = 0; i < strips - rem - n_pre; ++i) give(F, 0.0);
-  for (long i = 0; i < n_pre; ++i) give(C, ready[(size_t)i]);
-  return end;
-}
-// Few strips (a rank's shard of a strongly-scaled batch: strips < 1.5 rounds of the CUs), every one handed over: `strips` prologue items first, then every
-// strip's outputs as SQ parts (part q: r = q, q + SQ, ...; a team of a part runs its outputs in turn) -- what sharing a strip between workgroups always wanted,
-// without re-paying sweep and first product per part.  Makespan of the counter's deal in the units of deal_makespan.
-double deal_makespan_parts(long strips, int slots, int SQ, int R, int NS) {
-  const double pro = 1.75, epi = 0.3, io = 0.2, P = pro + io;
-  std::priority_queue<double, std::vector<double>, std::greater<double>> free_at;
-  for (int i = 0; i < slots; ++i) free_at.push(0.0);
-  std::vector<double> ready((size_t)strips, 0.0);
-  double end = 0.0;
-  auto give = [&](double cost, double not_before) {
-    double t = free_at.top();
-    free_at.pop();
-    if (t < not_before) t = not_before;
-    t += cost;
-    free_at.push(t);
-    if (t > end) end = t;
-    return t;
-  };
-  for (long i = 0; i < strips; ++i) ready[(size_t)i] = give(P, 0.0);
-  for (long i = 0; i < strips; ++i)
-    for (int q = 0; q < SQ; ++q) {
-      const int nr = q < R ? (R - 1 - q) / SQ + 1 : 0;
-      const double work = NS == 2 ? 2.0 * ((nr + 1) / 2) : (double)nr;   // (two teams: an output costs its team two units)
-      give(io + work + epi, ready[(size_t)i]);
-    }
-  return end;
-}
-// SQ for such a launch (0: not worth it / not wanted), given what the launch would cost without (`legacy_units`).
-// MEASURED (tools/parts_try.py, the 4 / 8 / 16-image shards of the headline batch): correct and bit-identical, and SLOWER than the launches it would replace at
-// every shard and every SQ -- 4 images 109 us (180 strips of 32 columns, one round) against 120-148 us as parts, 8 images 169 against 185-259, 16 images 303-308
-// against 302-421.  A part pays its ticket, the flag, the fetch of the strip, the mean product, two barriers of partial sums and the epilogue (~10 us) for 8-15 us of
-// second product; the simulated deal prices that at 0.5 of an output.  So the deal below never chooses parts by itself any more (fused_parts = -1 is "off"); the
-// form stays reachable through fused_parts = q for tests/test_gpu_ops.py and for a part that is made cheaper one day.
-int plan_parts(const dcgp_ctx* ctx, long strips, int slots, int R, int NS, double legacy_units) {
-  const long want = ctx->opt.fused_parts;   // -1 / 0: off, q > 0: this SQ; -2: chosen by the simulated deal (A/B)
-  if (want == 0 || want == -1 || R < 2 || strips <= 0 || 2 * strips > 3L * slots) return 0;
-  if (want > 0) return (int)std::min<long>(want, R);
-  double best = legacy_units * 0.9;   // a tenth better, or the plain launch stays
-  int best_q = 0;
-  for (int q = 2; q <= R; ++q) {
-    const double t = deal_makespan_parts(strips, slots, q, R, NS);
-    if (t < best - 1e-9) { best = t; best_q = q; }
-  }
-  return best_q;
-}
-// the number of prologues ahead for a persistent launch (0: none)
-long plan_prologues(const dcgp_ctx* ctx, long strips, int slots, int R) {
-  const long want = ctx->opt.fused_pre;
-  const long rem = strips % slots, q = strips / slots;
-  if (want == 0 || rem == 0 || q < 1 || q > 16 || R < 2) return 0;
-  static std::mutex mu;
-  static std::map<std::array<long, 4>, long> memo;
-  const std::array<long, 4> key = {strips, (long)slots, (long)R, want};
-  std::lock_guard<std::mutex> lock(mu);
-  auto it = memo.find(key);
-  if (it != memo.end()) return it->second;
-  const long per = want > 0 ? want : (long)((1.75 + R + 0.3) / 1.95);   // prologues a spare workgroup runs in one strip time
-  const long most = std::min<long>((slots - rem) * per, strips - rem);
-  const long step = std::max<long>(slots / 8, 1);
-  long best_n = 0;
-  double best = deal_makespan(strips, slots, 0, R) * (want > 0 ? 2.0 : 0.98);   // chosen: a deal must save 2 %; forced: the best non-zero count
-  for (long n = step; n <= most; n += step) {
-    const double t = deal_makespan(strips, slots, n, R);
-    if (t < best - 1e-9) { best = t; best_n = n; }
-  }
-  if (memo.size() > 256) memo.clear();
-  memo[key] = best_n;
-  return best_n;
-}
-// Replicas share a prologue: the number of distinct strips D of a tiled batch whose prologues the launch hands over (0: today's plan).  propagate() tiles the
-// minibatch S times in front of the first layer, so row n shows image n % n_mod: where n_mod * P columns are a whole number D of strips, strip i reads the images
-// of strip i % D at the same patch positions and its K_uf, A1 and sum A1^2 are the same numbers, bit for bit.  Nothing is shared across a strip that straddles
-// two replicas (a period that is no whole number of strips), with `rep` in force (the outputs are already laid out per replica) or in the launch that keeps
-// K_uf / A1 for the reverse pass (not persistent).  n_pre: what plan_prologues chose for the same launch -- the shared plan must beat that deal and the plain
-// launch by plan_prologues' own margin.
-long plan_rep_share(const dcgp_ctx* ctx, const ConvFusedArgs& a, long strips, int slots, int BN, long n_pre) {
-  if (ctx->opt.fused_rep_share == 0 || ctx->opt.fused_pre >= 0) return 0;   // (fused_pre 0: no hand-over of any kind; k > 0: that plan, forced)
-  if (a.n_mod <= 0 || a.rep != 1 || a.P <= 0 || a.Kc % a.P || a.Kuf_out || a.A1_out) return 0;
-  const long rows = a.Kc / a.P, period = (long)a.n_mod * a.P;
-  if (rows % a.n_mod || rows / a.n_mod < 2 || period % BN) return 0;
-  const long D = period / BN;
-  if (D >= strips || D > 4L * slots) return 0;   // (the hand-over area: a strip's LDS image per slot)
-  static std::mutex mu;
-  static std::map<std::array<long, 5>, long> memo;
-  const std::array<long, 5> key = {strips, (long)slots, (long)a.R, D, n_pre};
-  std::lock_guard<std::mutex> lock(mu);
-  auto it = memo.find(key);
-  if (it != memo.end()) return it->second;
-  const double plain = deal_makespan(strips, slots, 0, a.R);
-  const double today = n_pre > 0 ? std::min(plain, deal_makespan(strips, slots, n_pre, a.R)) : plain;
-  const double shared = deal_makespan(strips, slots, 0, a.R, D);
-  const long chosen = shared < today * 0.98 - 1e-9 ? D : 0;
-  if (memo.size() > 256) memo.clear();
-  memo[key] = chosen;
-  return chosen;
+// the question a layer launch asks the plan: filled here and nowhere else, for conv_fused_ok() and for conv_fused()
+Query fused_query(const dcgp_ctx* ctx, const ConvFusedArgs& a) {
+  const DcgpOptions& o = ctx->opt;
+  Query q;
+  q.Mp = a.Mp; q.M = a.M; q.R = a.R; q.Rp = a.Rp; q.Kc = a.Kc; q.P = a.P; q.HWC = a.HWC; q.L = a.L; q.Lp = a.Lp; q.Lz = a.Lz; q.f = a.f; q.C = a.C;
+  q.n_mod = a.n_mod; q.rep = a.rep; q.base = a.bk.type;
+  q.has_G = a.G != nullptr; q.keeps_state = a.Kuf_out || a.A1_out; q.has_trace = ctx->fused_trace != nullptr; q.n_cus = ctx->n_cus;
+  q.fused_shape = o.fused_shape; q.fused_large = o.fused_large; q.fused_split = o.fused_split; q.fused_persist = o.fused_persist; q.fused_pre = o.fused_pre;
+  q.fused_parts = o.fused_parts; q.fused_rep_share = o.fused_rep_share; q.fused_wgs = o.fused_wgs; q.fused_stagger = o.fused_stagger;
+  q.sweep_no_rows = o.sweep_no_rows;
+  return q;
 }
 
-// the first instantiated shape (widest strip, most waves) that covers Mp and whose LDS footprint fits
-bool plan_fused(const dcgp_ctx* ctx, const ConvFusedArgs& a, FusedPlan* p) {
-  const int force = (int)ctx->opt.fused_shape;   // A/B experiments (-1: none)
-  const int nf = a.Mp / 16;
-  if (a.Rp != 16 || a.R > 16 || a.Mp > 1024 || a.Mp % 16) return false;
-  if (a.Kc >= (1 << 23) || a.HWC >= (1 << 23)) return false;   // the kernel's index arithmetic (fdiv) is exact below 2^23: larger layers take the sweep + GEMM route
-  // M > 256: the 32- / 16-column strips LDS leaves room for re-fetch the A operands 2 - 4 x as often per MFMA and measure
-  // 2 % (M = 384) to 16 % (M = 1024) behind the sweep + 128 x 128-tile GEMM route (87 % of the MFMA peak there); opt-in
-  if (nf > 16 && force < 0 && !ctx->opt.fused_large) return false;
-  // Among the shapes that fit, the one whose busiest CU carries the fewest columns: workgroups go round the 256 CUs, a CU works
-  // through ceil(strips / 256) strips of BN columns at a rate that does not depend on BN (narrow strips share the CU), so few
-  // columns -- a shard of a strongly-scaled batch -- are better cut into narrower strips (4 images x 10 samples x 144 patches:
-  // 90 strips of 64 keep 90 CUs busy for a full strip time, 180 strips of 32 keep 180 busy for half of it).  The wider strip
-  // wins ties: fewer A-operand fetches per MFMA (measured 3 % / 6 % behind at 32 / 16 columns on the full batch).
-  double best = 0.0;
-  bool found = false;
-  for (int i = 0; i < kNumShapes; ++i) {
-    const FusedShape& sh = kShapes[i];
-    if (force >= 0 && i != force) continue;
-    if (nf > sh.max_nf) continue;
-    if (sh.max_nf > 16 && nf <= 16 && force < 0) continue;   // the many-wave shapes are for the large matrices
-    if (i == 1 && force < 0) continue;                        // (the 8-wave form of shape 0: A/B experiments only)
-    const int BN = sh.FN * 16, W = sh.NT / 64, TW = W / sh.NS, KG = W / sh.FN;
-    const int nimg = (BN - 1) / a.P + 2;           // images a strip can touch
-    const long fin = (long)(TW * a.R + KG * 16) * BN;
-    const long main_d = (long)a.Mp * BN > fin ? (long)a.Mp * BN : fin;
-    long img_d = ((long)nimg * a.HWC + 1) & ~1L;
-    if (img_d < (long)TW * BN) img_d = (long)TW * BN;
-    const long bytes = (main_d + img_d + BN + 2) * 8 + (long)(a.Lz > a.Lp ? a.Lz : a.Lp) * 4;
-    if (bytes > 160 * 1024) continue;
-    const long strips = a.Kc > 0 ? ((long)a.Kc + BN - 1) / BN : 1;
-    // shape 7 (32 columns on 16 waves, the outputs split over two teams): a strip's latency is what a launch of one round costs, and
-    // the second team shortens it (a 4-image shard of the headline batch: 0.297 -> 0.290 ms per step); over several rounds the eight-wave
-    // form's two strips per CU do better (8 images: 0.398 against 0.384)
-    if (i == 7 && force < 0 && strips > 512) continue;
-    int q = 1;
-    const int slots = ctx->n_cus > 0 ? ctx->n_cus : 256;
-    const double rounds = sh.NT == 1024 ? (double)(strips / slots) + last_round(ctx, sh, strips, a.R, a.G != nullptr, &q) : (double)((strips + 255) / 256);
-    const double cost = rounds * BN * (i == 7 ? 0.97 : (sh.FN == 4 ? 1.0 : (sh.FN == 2 ? 1.03 : 1.12)));
-    if (found && cost >= best) continue;
-    found = true; best = cost;
-    p->shape = i; p->lds = (size_t)bytes; p->lds_main = (int)main_d; p->lds_img = (int)img_d; p->split_q = q;
-  }
-  return found;
+// A workspace of the ctx that the kernel leaves zeroed behind every launch: cleared on the stream when it is new, has grown, or `clear` says so
+template <class T>
+int ws_zeroed(dcgp_ctx* ctx, const char* name, size_t bytes, T** out, bool clear = false, bool* cleared = nullptr) {
+  const auto it = ctx->ws.find(name);
+  clear = clear || it == ctx->ws.end() || it->second.second < bytes;
+  *out = static_cast<T*>(ws_get(ctx, name, bytes));
+  if (!*out) return DCGP_ERR_ALLOC;
+  if (clear) HIP_TRY(ctx, hipMemsetAsync(*out, 0, ctx->ws[name].second, ctx->stream));
+  if (cleared) *cleared = clear;
+  return DCGP_OK;
 }
 
 }  // namespace
 
-// debugging aid (tools/fused_trace.py): device buffer of 8 x 16 x 16 int64 that the fused layer kernel stamps its phases into
+// debugging aid (tools/fused_trace.py): device buffer of 8 x 4 x 16 x 16 int64 ([sampled workgroup][strip of a persistent one][wave][stamp]) that the fused
+// layer kernel stamps its phases into
 extern "C" int dcgp_debug_set_fused_trace(dcgp_ctx* ctx, long long* buf_dev) {
   if (!ctx) return DCGP_ERR_ARG;
   ctx->fused_trace = buf_dev;   // per ctx: goes away with it (nullptr switches the stamps off)
@@ -1078,103 +875,60 @@ extern "C" int dcgp_debug_set_fused_trace(dcgp_ctx* ctx, long long* buf_dev) {
 // counter deals, hand-over slots, distinct strips D whose prologues the replicas share (0: not shared)}
 extern "C" int dcgp_debug_fused_plan(dcgp_ctx* ctx, int* out4) {
   if (!ctx || !out4) return DCGP_ERR_ARG;
-  for (int i = 0; i < 4; ++i) out4[i] = ctx->fused_plan[i];
+  const Plan& p = ctx->last_fused_plan;
+  out4[0] = p.persist; out4[1] = p.n_items; out4[2] = p.pre_n; out4[3] = p.pre_D;
+  return DCGP_OK;
+}
+
+// debugging aid (tests, no device needed): the plan of a layer launch from a flat query; field orders in include/dcgp.h
+extern "C" int dcgp_debug_plan_layer_launch(const long long* query, int n_query, long long* plan, int n_plan) {
+  if (!query || !plan || n_query != Query::kFields || n_plan != Plan::kFields) return DCGP_ERR_ARG;
+  Query q;
+  auto fields = Query::fields(q);
+  static_assert(std::tuple_size<decltype(fields)>::value == Query::kFields, "the flat query covers every field");
+  std::apply([&](auto&... f) { ((f = (long)*query++), ...); }, fields);
+  const Plan p = fused_plan::plan_layer_launch(q);
+  long long units[3];
+  const double u[3] = {p.units_plain, p.units_ahead, p.units_shared};
+  memcpy(units, u, sizeof units);
+  const long long flat[Plan::kFields] = {p.ok, p.shape, p.lds, p.lds_main, p.lds_img, p.grid, p.persist, p.n_strips, p.n_items, p.deal, p.split_first, p.split_q,
+                                         p.pre_n, p.pre_first, p.pre_sq, p.pre_D, p.pre_whole, p.pre_stride, p.stagger, p.cu_slots, p.patch_rows,
+                                         units[0], units[1], units[2]};
+  memcpy(plan, flat, sizeof flat);
   return DCGP_OK;
 }
 
 bool conv_fused_ok(const dcgp_ctx* ctx, const ConvFusedArgs& a) {
-  const bool off = ctx->opt.no_fused_layer != 0;   // A/B switch (tests flip it through dcgp_ctx_set_option): the unfused sweep + GEMM route
-  FusedPlan p;
-  return !off && plan_fused(ctx, a, &p);
+  // no_fused_layer: A/B switch (tests flip it through dcgp_ctx_set_option): the unfused sweep + GEMM route
+  return !ctx->opt.no_fused_layer && fused_plan::plan_layer_launch(fused_query(ctx, a)).ok;
 }
 
 int conv_fused(dcgp_ctx* ctx, const ConvFusedArgs& a_in) {
   if (a_in.Kc <= 0) return DCGP_OK;
-  FusedPlan p;
-  if (!plan_fused(ctx, a_in, &p)) return ctx_fail(ctx, DCGP_ERR_ARG, "conv_fused: layer shape not supported (M = %d, R = %d)", a_in.M, a_in.R);
-  if ((long)a_in.R * a_in.Mp * a_in.Mp * 8 >= (1L << 31)) return ctx_fail(ctx, DCGP_ERR_ARG, "conv_fused: G exceeds 2 GiB");
+  const Plan p = fused_plan::plan_layer_launch(fused_query(ctx, a_in));
+  if (!p.ok) return ctx_fail(ctx, DCGP_ERR_ARG, "conv_fused: layer shape not supported (M = %d, R = %d)", a_in.M, a_in.R);
+  // The workspaces the plan asks for.  ONE counter pair, one hand-over area and one set of arrival counters per ctx: the code relies on a ctx's layer
+  // launches being serialised on one main stream (a step on the other main stream starts behind the previous one's end, model.hip)
   ConvFusedArgs a = a_in;
+  if (p.deal == fused_plan::kCounter) DCGP_TRY(ws_zeroed(ctx, "fused_dyn", 2 * sizeof(int), &a.dyn));
+  if (p.pre_n > 0) {
+    a.pre_buf = static_cast<double*>(ws_get(ctx, "fused_pre_buf", (size_t)p.pre_n * p.pre_stride * sizeof(double)));
+    if (!a.pre_buf) return DCGP_ERR_ALLOC;
+    bool cleared = false;   // flags compare equal to the launch's epoch: a fresh (or wrapped) area starts from zero
+    DCGP_TRY(ws_zeroed(ctx, "fused_pre_flag", (size_t)p.pre_n * sizeof(unsigned), &a.pre_flag, ctx->fused_pre_epoch == 0xffffffffu, &cleared));
+    if (cleared) ctx->fused_pre_epoch = 0;
+    a.pre_epoch = ++ctx->fused_pre_epoch;
+  }
+  if (p.cu_slots) DCGP_TRY(ws_zeroed(ctx, "fused_cu_slots", 1024 * sizeof(int), &a.cu_slots));
+  // the plan into the argument block
   a.lds_main = p.lds_main; a.lds_img = p.lds_img;
+  a.split_first = p.split_first; a.split_q = p.split_q;
+  a.persist = p.persist; a.n_strips = p.n_strips; a.n_items = p.n_items; a.stagger = p.stagger;
+  a.pre_n = p.pre_n; a.pre_first = p.pre_first; a.pre_sq = p.pre_sq; a.pre_stride = p.pre_stride; a.pre_D = p.pre_D; a.pre_whole = p.pre_whole;
   a.trace = ctx->fused_trace;
   a.no_rows = ctx->opt.sweep_no_rows ? 1 : 0;
   a.inv_HWC = 1.0f / (float)a.HWC; a.inv_nmod = 1.0f / (float)a.n_mod; a.inv_P = 1.0f / (float)a.P; a.inv_Wo = 1.0f / (float)a.Wo; a.inv_R = 1.0f / (float)a.R;
-  const long strips = ((long)a.Kc + kShapes[p.shape].FN * 16 - 1) / (kShapes[p.shape].FN * 16);
-  const int all_cus = ctx->n_cus > 0 ? ctx->n_cus : 256;
-  const int n_cus = ctx->opt.fused_wgs > 0 && ctx->opt.fused_wgs < all_cus ? (int)ctx->opt.fused_wgs : all_cus;   // (fused_wgs: a small layer in several rounds, tests)
-  // workgroups a CU holds: LDS (160 KB) and wave slots (the kernels are held to 128 registers: 16 waves of 64 per CU)
-  const long per_cu = std::min<long>(160 * 1024 / (long)p.lds, 1024 / kShapes[p.shape].NT);
-  // chosen (-1): where a workgroup owns its CU and no strip of the last round is shared.  What it buys is the deal, not the persistence: strips handed out
-  // by a device counter to whichever workgroup is free 572 us at cfg2, dealt by a fixed stride 576 -- as many as one workgroup per strip takes
-  // (profiles/r06_fused_ab.txt)
-  const long want = ctx->opt.fused_persist;
-  bool persist = per_cu >= 1 && strips > per_cu * n_cus && (want > 0 || (want < 0 && per_cu == 1 && p.split_q == 1 && !a.Kuf_out && !a.A1_out));
-  // few strips: all of them handed over, their outputs dealt as parts (deal_makespan_parts)
-  int parts_sq = 0;
-  if (!persist && per_cu == 1 && a.G && !a.Kuf_out && !a.A1_out && want != 0 && want != 2) {
-    const FusedShape& sh = kShapes[p.shape];
-    int q_legacy = 1;
-    const double last = last_round(ctx, sh, strips, a.R, true, &q_legacy);
-    const double legacy = ((double)(strips / n_cus) + (strips % n_cus ? last : 0.0)) * (1.75 + a.R + 0.3);
-    parts_sq = plan_parts(ctx, strips, n_cus, a.R, sh.NS, legacy);
-    if (parts_sq > 1) persist = true;
-  }
-  if (persist) {
-    a.persist = (int)(per_cu * n_cus);
-    a.n_strips = (int)strips;
-    a.n_items = (int)strips;
-    if (want != 2) {   // (2: the fixed deal blockIdx, blockIdx + grid, ... -- A/B)
-      // ONE counter pair (and one hand-over area, below) per ctx: ws_tag is empty by the time a layer runs, so the names carry no bank.  Safe because a
-      // ctx's layer launches are serialised on one main stream (a step on the other main stream starts behind the previous one's end, model.hip)
-      const std::string nm = "fused_dyn" + ctx->ws_tag;
-      const bool fresh = ctx->ws.find(nm) == ctx->ws.end();
-      a.dyn = static_cast<int*>(ws_get(ctx, nm, 2 * sizeof(int)));
-      if (!a.dyn) return DCGP_ERR_ALLOC;
-      if (fresh) HIP_TRY(ctx, hipMemsetAsync(a.dyn, 0, 2 * sizeof(int), ctx->stream));
-    }
-    if (per_cu == 1 && a.dyn && a.G) {
-      const int TW = kShapes[p.shape].NT / 64 / kShapes[p.shape].NS, BN = kShapes[p.shape].FN * 16;
-      long n_pre = parts_sq > 1 ? strips : plan_prologues(ctx, strips, a.persist, a.R);
-      const long share_D = parts_sq > 1 ? 0 : plan_rep_share(ctx, a, strips, a.persist, BN, n_pre);
-      if (share_D > 0) n_pre = share_D;   // one slot per distinct strip
-      if (n_pre > 0) {
-        a.pre_n = (int)n_pre;
-        a.pre_first = parts_sq > 1 ? 0 : (int)(strips % a.persist);
-        a.pre_sq = parts_sq > 1 ? parts_sq : 1;
-        if (share_D > 0) {
-          a.pre_D = (int)share_D;
-          a.pre_whole = (int)std::max<long>(share_D, std::min<long>(a.persist, strips));
-          a.pre_first = 0;
-        } else {
-          a.n_items = (int)(strips + n_pre * a.pre_sq);
-        }
-        a.pre_stride = (long)a.Mp * BN + (long)TW * BN;
-        const std::string nb = "fused_pre_buf" + ctx->ws_tag, nf = "fused_pre_flag" + ctx->ws_tag;
-        const size_t fbytes = (size_t)n_pre * sizeof(unsigned);
-        const bool fresh = ctx->ws.find(nf) == ctx->ws.end() || ctx->ws[nf].second < fbytes;
-        a.pre_buf = static_cast<double*>(ws_get(ctx, nb, (size_t)n_pre * a.pre_stride * sizeof(double)));
-        a.pre_flag = static_cast<unsigned*>(ws_get(ctx, nf, fbytes));
-        if (!a.pre_buf || !a.pre_flag) return DCGP_ERR_ALLOC;
-        unsigned& epoch = ctx->fused_pre_epochs[nf];
-        if (fresh || epoch == 0xffffffffu) {   // flags compare equal to the launch's epoch: a fresh (or wrapped) area starts from zero
-          HIP_TRY(ctx, hipMemsetAsync(a.pre_flag, 0, ctx->ws[nf].second, ctx->stream));
-          epoch = 0;
-        }
-        a.pre_epoch = ++epoch;
-      }
-    }
-    if (per_cu > 1) {
-      const long us = ctx->opt.fused_stagger >= 0 ? ctx->opt.fused_stagger : 40;
-      a.stagger = (int)(us * 100);
-      bool fresh = ctx->ws.find("fused_cu_slots") == ctx->ws.end();
-      a.cu_slots = static_cast<int*>(ws_get(ctx, "fused_cu_slots", 1024 * sizeof(int)));
-      if (!a.cu_slots) return DCGP_ERR_ALLOC;
-      if (fresh) HIP_TRY(ctx, hipMemsetAsync(a.cu_slots, 0, 1024 * sizeof(int), ctx->stream));
-    }
-  } else if (p.split_q > 1 && !a.trace) {
-    a.split_q = p.split_q;
-    a.split_first = (int)(strips - strips % n_cus);
-  }
-  ctx->fused_plan[0] = a.persist; ctx->fused_plan[1] = a.persist ? a.n_items : 0; ctx->fused_plan[2] = a.pre_n; ctx->fused_plan[3] = a.pre_D;
+  ctx->last_fused_plan = p;
   ScopedTimer t(ctx, "conv_fused");
 #ifdef DCGP_EXPERIMENTS
   const int abl = (int)ctx->opt.fused_abl;   // timing build only (make EXPERIMENTS=1): wrong results
@@ -1183,7 +937,7 @@ int conv_fused(dcgp_ctx* ctx, const ConvFusedArgs& a_in) {
 #define CF_ABL(X)                                                                                                                       \
   case X:                                                                                                                               \
     hipFuncSetAttribute((const void*)conv_fused_kernel<4, 2, 2, 1024, 0, X>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-    hipLaunchKernelGGL((conv_fused_kernel<4, 2, 2, 1024, 0, X>), dim3(grid), dim3(1024), p.lds, ctx->stream, a);                        \
+    hipLaunchKernelGGL((conv_fused_kernel<4, 2, 2, 1024, 0, X>), dim3(grid), dim3(1024), (size_t)p.lds, ctx->stream, a);               \
     break;
     switch (abl) { CF_ABL(1) CF_ABL(2) CF_ABL(3) CF_ABL(4) default: return ctx_fail(ctx, DCGP_ERR_ARG, "conv_fused: unknown DCGP_FUSED_ABL value %d", abl); }
 #undef CF_ABL
@@ -1191,14 +945,15 @@ int conv_fused(dcgp_ctx* ctx, const ConvFusedArgs& a_in) {
     return DCGP_OK;
   }
 #endif
+  static_assert(fused_plan::kNumShapes == 8, "one case per row of the shape table");
   switch (p.shape) {
-    case 0: return launch_fused<4, 2, 2, 1024>(ctx, a, p.lds);
-    case 1: return launch_fused<4, 1, 2, 512>(ctx, a, p.lds);
-    case 2: return launch_fused<2, 1, 2, 512>(ctx, a, p.lds);
-    case 3: return launch_fused<1, 1, 2, 512>(ctx, a, p.lds);
-    case 4: return launch_fused<2, 1, 2, 768>(ctx, a, p.lds);
-    case 5: return launch_fused<2, 1, 2, 1024>(ctx, a, p.lds);
-    case 6: return launch_fused<1, 1, 4, 1024>(ctx, a, p.lds);
-    default: return launch_fused<2, 2, 2, 1024>(ctx, a, p.lds);
+    case 0: return launch_fused<0>(ctx, a, p);
+    case 1: return launch_fused<1>(ctx, a, p);
+    case 2: return launch_fused<2>(ctx, a, p);
+    case 3: return launch_fused<3>(ctx, a, p);
+    case 4: return launch_fused<4>(ctx, a, p);
+    case 5: return launch_fused<5>(ctx, a, p);
+    case 6: return launch_fused<6>(ctx, a, p);
+    default: return launch_fused<7>(ctx, a, p);
   }
 }

@@ -312,6 +312,7 @@ int dcgp_ctx_set_option(dcgp_ctx* ctx, const char* name, long value) {
 }
 int dcgp_ctx_get_option(dcgp_ctx* ctx, const char* name, long* value_out) {
   if (!ctx || !name || !value_out) return DCGP_ERR_ARG;
+  if (strcmp(name, "n_cus") == 0) { *value_out = ctx->n_cus; return DCGP_OK; }   // (read-only: the device's compute units, as the launch plans count them)
   long* slot = dcgp_option_slot(&ctx->opt, name);
   if (!slot) return ctx_fail(ctx, DCGP_ERR_ARG, "unknown option '%s'", name);
   *value_out = *slot;

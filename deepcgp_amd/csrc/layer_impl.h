@@ -253,7 +253,7 @@ struct FactorGroup {
 };
 
 // What a conv layer on `rows` images hands the one-launch layer kernel of its own: geometry, operands and the column count -- every field the route
-// decision reads (conv_fused.hip, plan_fused).  Filled here and nowhere else, for a step's plan (model.hip, plan_step) and for the dispatch below, so that
+// decision reads (conv_fused.hip: fused_query; fused_plan.h: plan_layer_launch).  Filled here and nowhere else, for a step's plan (model.hip, plan_step) and for the dispatch below, so that
 // the two cannot be asked different questions.
 static inline ConvFusedArgs conv_fused_shape(const LayerState& L, long rows) {
   ConvFusedArgs fa;

@@ -139,6 +139,7 @@ _SIGS = {
     "dcgp_kmeans": [_vp, _vp, C.c_long, _i, _i, _vp, _i, _d, _vp, _ip],
     "dcgp_debug_set_fused_trace": [_vp, _vp],
     "dcgp_debug_fused_plan": [_vp, _vp],
+    "dcgp_debug_plan_layer_launch": [_vp, _i, _vp, _i],
     "dcgp_debug_comm_gate": [_vp, _i, _ip],
     "dcgp_debug_mfma_f64_rate": [_vp, _dp],
     "dcgp_debug_store_rate": [_vp, _i, _i, _i, _dp],

@@ -55,7 +55,8 @@ int dcgp_sync(dcgp_ctx* ctx);
 int dcgp_workspace_query(dcgp_ctx* ctx, size_t* bytes_out, int* count_out);
 /* A/B and debugging switches (csrc/common.h: DcgpOptions).  A ctx reads the environment variable DCGP_<NAME> once, in
  * dcgp_ctx_create, as the switch's initial value; afterwards only these calls change it -- no getenv on the step path.  Names are
- * lower case ("no_fused_layer", "kl_side", ...); an unknown name is DCGP_ERR_ARG.                                                 */
+ * lower case ("no_fused_layer", "kl_side", ...); an unknown name is DCGP_ERR_ARG.  dcgp_ctx_get_option also answers "n_cus": the
+ * compute units of the ctx's device, which is no switch and cannot be set.                                                          */
 int dcgp_ctx_set_option(dcgp_ctx* ctx, const char* name, long value);
 int dcgp_ctx_get_option(dcgp_ctx* ctx, const char* name, long* value_out);
 
@@ -545,12 +546,23 @@ int dcgp_allreduce_sum_f64(dcgp_ctx* ctx, double* buf_dev, int n);
  * prove it: closed != 0 -- every such all-reduce enqueued from now on first waits (at most ~4 s) for the gate; 0 -- opens and removes it.
  * main_idle_out (may be NULL): bit 0 -- the ctx's main stream has drained (hipStreamQuery), bit 1 -- the comm stream has. */
 int dcgp_debug_comm_gate(dcgp_ctx* ctx, int closed, int* main_idle_out);
-/* Device buffer of 8 x 16 x 16 int64 into which the one-launch conv layer kernel (csrc/conv_fused.hip) stamps the shader
+/* Device buffer of 8 x 4 x 16 x 16 int64 into which the one-launch conv layer kernel (csrc/conv_fused.hip) stamps the shader
  * clock at its phase boundaries (8 sampled workgroups x 4 strips of a persistent one x 16 waves x 16 stamps = 8192 words); NULL switches it off (tools/fused_trace.py). */
 int dcgp_debug_set_fused_trace(dcgp_ctx* ctx, long long* buf_dev);
 /* How the most recent launch of that kernel was dealt: out4 = {persistent workgroups (0: one workgroup per strip), items the device counter deals,
  * hand-over slots, distinct strips whose prologue the replicas of a tiled batch share (0: not shared)}. */
 int dcgp_debug_fused_plan(dcgp_ctx* ctx, int* out4);
+/* The whole plan of such a launch (csrc/fused_plan.h, plan_layer_launch) for a layer described by integers alone: needs no ctx and no device.
+ * query[29] = {Mp, M, R, Rp, Kc, P, HWC, L, Lp, Lz, f, C, n_mod, rep, base-kernel type, has_G (the layer has a q_sqrt term), keeps_state (K_uf / A1 are
+ *   kept for the reverse pass), has_trace (dcgp_debug_set_fused_trace is on), n_cus (compute units of the device), then the ctx options fused_shape,
+ *   fused_large, fused_split, fused_persist, fused_pre, fused_parts, fused_rep_share, fused_wgs, fused_stagger, sweep_no_rows}.
+ * plan[24] = {ok (0: the kernel does not cover the layer; the rest is then not set), shape, LDS bytes, lds_main, lds_img, grid, persist (workgroups of a
+ *   persistent launch, 0: none), n_strips, n_items (both 0 unless persistent), deal (0: one workgroup per strip, 1: device counter, 2: fixed stride),
+ *   split_first, split_q, pre_n, pre_first, pre_sq, pre_D, pre_whole, pre_stride, stagger, cu_slots (the per-CU arrival counters are needed),
+ *   patch_rows (the patch-row instance of the sweep), then the makespans of the simulated deals that were compared, in outputs of the second product,
+ *   each an IEEE double BIT-CAST into its 64-bit slot (0.0: not simulated): one item per strip, prologues ahead, replicas sharing a prologue}.
+ * dcgp_debug_fused_plan's four values are persist, n_items, pre_n and pre_D of the plan of the launch.  DCGP_ERR_ARG unless n_query == 29, n_plan == 24. */
+int dcgp_debug_plan_layer_launch(const long long* query, int n_query, long long* plan, int n_plan);
 /* The same for the patch sweeps (csrc/head_units.hip; tools/sweep_trace.py): [n_workgroups][waves per workgroup][8] int64 -- wall clock at entry,
  * shader clock at entry / image staged / set-up done / first unit done / last unit done, wall clock at exit, units run.            */
 /* The ceilings bench.py prices kernels against, measured on this device (csrc/peaks.hip): the sustained fp64 MFMA rate (TFLOP/s, 4 waves

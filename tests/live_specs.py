@@ -114,7 +114,7 @@ CASES_MIXED = {
     "ch_264_72": dict(_CH, Ms=(264, 72), N=3, c=1.0, a=0.1),                                                     # Mp 272, 80
     "ch_72_264": dict(_CH, Ms=(72, 264), N=3, c=1.0, a=0.1),                                                     # Mp 80, 272
     # 33 feature maps, Rp = 48: the widest conv layer of the suite (13 elsewhere), beside a head with Rp = 16 in the same group.  Its right-hand sides
-    # cannot ride (Rp > 32) -- and nor do the head's here: a conv layer with Rp != 16 is not one launch (conv_fused.hip, plan_fused), and a chain beside
+    # cannot ride (Rp > 32) -- and nor do the head's here: a conv layer with Rp != 16 is not one launch (fused_plan.h, plan_layer_launch), and a chain beside
     # a first layer's sweep carries no right-hand sides at all (plan_step: may_ride).  Mixed riding in one group is small3_mixwhite's
     "wide_R33": dict(hwc=(12, 12, 1), convs=[(3, 1, 33)], head=(3, 1), Ms=(24, 24), N=3, c=1.0, a=0.1),          # Mp 32, 32
 }

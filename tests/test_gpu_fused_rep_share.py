@@ -1,5 +1,5 @@
-"""The layer kernel on a tiled batch: the strips that show the same images at the same patches share one prologue (csrc/conv_fused.hip:
-plan_rep_share; ctx option fused_rep_share, -1 chosen / 0 off).
+"""The layer kernel on a tiled batch: the strips that show the same images at the same patches share one prologue (csrc/fused_plan.h:
+plan_layer_launch; ctx option fused_rep_share, -1 chosen / 0 off).
 
 DGP_Base.propagate tiles the minibatch S times in front of the first layer, so strip i of layer 0 and strip i + k D (D = N P / strip width, where that
 is a whole number) compute the same K_uf, A1 and sum A1^2.  The shared launch runs D of them whole, has those leave their A1 in memory on the way, and
@@ -8,12 +8,14 @@ fused_rep_share = 0 against the default with assert_array_equal, three shared la
 
 Small layers are put through several rounds by fused_wgs (that many persistent workgroups instead of one per CU) and fused_shape (6: 16-column strips,
 0: 64-column strips, both one workgroup per CU, as the hand-over needs).  dcgp_debug_fused_plan says which plan the last launch took, so a case that is
-meant to share (or to fall back) cannot pass by doing the other."""
-import ctypes as C
+meant to share (or to fall back) cannot pass by doing the other; and every launch took the plan that the planner (csrc/fused_plan.h, asked through
+dcgp_debug_plan_layer_launch) gives for a query built here from the spec, the ctx's options and its device."""
 import os
 
 import numpy as np
 import pytest
+
+import fused_plan_cases as fc
 
 pytestmark = pytest.mark.gpu
 
@@ -23,11 +25,12 @@ CONV = (5, 2)
 
 def _plan(ctx):
     """(workgroups, items, hand-over slots, distinct strips D of the shared plan or 0) of the most recent layer-kernel launch"""
-    from deepcgp_amd import device as dev
-    out = (C.c_int * 4)()
-    rc = dev.lib().dcgp_debug_fused_plan(ctx.handle, out)
-    assert rc == 0
-    return tuple(out)
+    return fc.last_launch(ctx)
+
+
+def _planned(ctx, M, R, N, S, base="rbf"):
+    """the same four values of the plan for layer 0 on N images tiled S times, under the ctx's options of the moment"""
+    return fc.debug_plan_of(fc.plan(fc.ctx_query(ctx, HWC, CONV[0], CONV[1], M, R, N * S, N, base=base)))
 
 
 _models = {}
@@ -66,10 +69,12 @@ def _check(ctx, M, R, N, S, shape, wgs, want_D, noise="z", base="rbf", idm=False
         with ctx.options(fused_rep_share=0):
             ref = _layer0(model, X, S, zs, 11)
             plan0 = _plan(ctx)
+            assert plan0 == _planned(ctx, M, R, N, S, base)
         assert plan0[0] == wgs and plan0[3] == 0, plan0
         for _ in range(3):
             got = _layer0(model, X, S, zs, 11)
             plan = _plan(ctx)
+            assert plan == _planned(ctx, M, R, N, S, base)
             assert plan[0] == wgs and plan[3] == want_D, (plan, want_D)
             if want_D:
                 assert plan[1] == strips and plan[2] == want_D, plan     # one item per strip, one slot per distinct strip
@@ -144,7 +149,7 @@ def test_consumers_draw_their_own_noise(ctx):
     X, _ = syn.make_batch(HWC, 4, seed=104)
     with ctx.options(fused_shape=6, fused_persist=1, fused_wgs=4):
         smp, mean, var = _layer0(model, X, 3, None, 5)
-        assert _plan(ctx)[3] == 4
+        assert _plan(ctx)[3] == 4 and _plan(ctx) == _planned(ctx, 32, 3, 4, 3)
     np.testing.assert_array_equal(mean[0], mean[1])
     np.testing.assert_array_equal(var[0], var[2])
     assert np.abs(smp[0] - smp[1]).min() > 0 and np.abs(smp[0] - smp[2]).min() > 0

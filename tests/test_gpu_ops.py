@@ -401,10 +401,16 @@ def test_fused_strip_shared_by_workgroups(ctx, shape, split, M, N, R):
     Z *= 1.5
     layer = ConvLayer(RBF(v.patch_length, 5.0, 5.0), None, PatchInducingFeatures(Z), v, gp_count=R, q_mu=q_mu, q_sqrt=q_sqrt)
     z = rng.standard_normal((N, layer.num_outputs))
+    import fused_plan_cases as fc
     with ctx.options(fused_shape=shape, fused_split=0, fused_parts=0):
         smp_w, mean_w, var_w = layer._forward(X, z)
+        whole = fc.plan(fc.ctx_query(ctx, (H, W, C), f, s, M, R, N, N, keeps_state=1))      # (the operator keeps K_uf and A1)
+        assert fc.last_launch(ctx) == fc.debug_plan_of(whole) and whole["split_q"] == 1
     with ctx.options(fused_shape=shape, fused_split=split, fused_parts=0):
         smp, mean, var = layer._forward(X, z)
+        shared = fc.plan(fc.ctx_query(ctx, (H, W, C), f, s, M, R, N, N, keeps_state=1))
+        assert fc.last_launch(ctx) == fc.debug_plan_of(shared)
+        assert shared["persist"] == 0 and 1 < shared["split_q"] <= min(split, R) and shared["grid"] > whole["grid"]
     np.testing.assert_array_equal(mean, mean_w)
     np.testing.assert_array_equal(var, var_w)
     np.testing.assert_array_equal(smp, smp_w)

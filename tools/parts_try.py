@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """usage (GPU box): python tools/parts_try.py   -- the layer kernel on a rank's shard of the headline batch (4 / 8 / 16 images): strips handed over and their outputs
-dealt as parts (csrc/conv_fused.hip: plan_parts; ctx option fused_parts) against the whole-strip / shared-last-round launches, per strip shape: ms per synchronous
+dealt as parts (csrc/fused_plan.h: ahead_units; ctx option fused_parts) against the whole-strip / shared-last-round launches, per strip shape: ms per synchronous
 step, the layer kernel's own launch (HIP events) and the ELBO (identical for every row of a batch)."""
 import sys, time
 import numpy as np
