@@ -1739,7 +1739,7 @@ int model_backward(dcgp_model* m, const Targets& targets, const double* X, int N
   double* gm = (double*)ws_get(ctx, mp + "g_gm_head", (size_t)rows * H.R * sizeof(double));
   double* gv = (double*)ws_get(ctx, mp + "g_gv_head", (size_t)rows * H.R * sizeof(double));
   NEED(gm); NEED(gv);
-  double* gs2 = nullptr;   // Gaussian likelihood: d / d variance, moved into the head's block (glik) once its zero fill is behind us
+  double* gs2 = nullptr;   // Gaussian likelihood: d / d variance (StudentT: d / d scale), moved into the head's block (glik) once its zero fill is behind us
   if (lik.n_params()) { gs2 = (double*)ws_get(ctx, mp + "g_lik", sizeof(double)); NEED(gs2); }
   DCGP_TRY(lik_grad_seeds(ctx, lik, oh.mean, oh.var, targets, rows, N, H.R, weight, gm, gv, gs2));
   DCGP_TRY(backward_walk(bk, X, N, S, dedup_layer0, gm, gv, nullptr, "grad"));
@@ -1889,6 +1889,14 @@ int dcgp_model_get_grad(dcgp_model* model, int layer, const char* which, double*
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return DCGP_OK;
   }
+  if (!strcmp(which, "likelihood_scale")) {   // model-wide, `layer` is ignored: the last slot of the head's gradient block
+    const LayerState* H = model->has_head ? model->layers.back().get() : nullptr;
+    if (model->lik_kind != 4 || !H || !H->glik) return ctx_fail(ctx, DCGP_ERR_ARG, "get_grad(likelihood_scale): no StudentT-likelihood gradient (dcgp_elbo_grad_f64y first)");
+    if (count != 1) return ctx_fail(ctx, DCGP_ERR_ARG, "get_grad(likelihood_scale): expected 1 value");
+    HIP_TRY(ctx, hipMemcpyAsync(out_host, H->glik, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return DCGP_OK;
+  }
   if (layer < 0 || layer >= (int)model->layers.size()) return ctx_fail(ctx, DCGP_ERR_ARG, "get_grad: no layer %d", layer);
   LayerState& L = *model->layers[layer];
   if (!L.gZ) return ctx_fail(ctx, DCGP_ERR_ARG, "get_grad: call dcgp_elbo_grad first");
@@ -1996,7 +2004,7 @@ static int opt_enqueue(dcgp_model* model, const char* who, bool sgd, double lr, 
     DCGP_TRY(add(L.hyp, L.gscal, L.ahyp, 3, 1, li, nullptr, (L.frozen & 16u) != 0));
     if (a.ng > ng_hyp) a.grp[ng_hyp].hold = (int)((L.frozen >> 5) & 3u) << 1;   // bits 32 / 64: elements 1 / 2 of the triple stay where they are
     if (L.ard) DCGP_TRY(add(L.ard, L.gard, L.aard, (long)L.v.L, 1, -1, L.in_scale, (L.frozen & 16u) != 0));   // dense head: per-dimension lengthscales and the staging scale 1 / l
-    if (L.glik) {   // Gaussian likelihood variance: the last slot of the head's block, moments beside it on the device
+    if (L.glik) {   // Gaussian likelihood variance / StudentT scale: the last slot of the head's block, moments beside it on the device
       if (!model->d_lik) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: the head's block has a likelihood slot but the model no Gaussian likelihood", who);
       double* lik_mv[2] = {model->d_lik + 1, model->d_lik + 2};
       DCGP_TRY(add(model->d_lik, L.glik, lik_mv, 1, 1, -1, nullptr, model->lik_frozen));
@@ -2079,6 +2087,11 @@ int dcgp_model_set_trainable(dcgp_model* model, int layer, const char* which, in
     model->lik_frozen = !on;
     return DCGP_OK;
   }
+  if (!strcmp(which, "likelihood_scale")) {   // model-wide, `layer` is ignored
+    if (model->lik_kind != 4) return ctx_fail(model->ctx, DCGP_ERR_ARG, "set_trainable(likelihood_scale): not a StudentT-likelihood model");
+    model->lik_frozen = !on;
+    return DCGP_OK;
+  }
   if (layer < 0 || layer >= (int)model->layers.size()) return ctx_fail(model->ctx, DCGP_ERR_ARG, "set_trainable: no layer %d", layer);
   LayerState& L = *model->layers[layer];
   unsigned bit = 0;
@@ -2100,6 +2113,13 @@ int dcgp_model_get_param(dcgp_model* model, int layer, const char* which, double
   if (!strcmp(which, "likelihood_variance")) {   // model-wide, `layer` is ignored
     if (model->lik_kind != 1) return ctx_fail(ctx, DCGP_ERR_ARG, "get_param(likelihood_variance): not a Gaussian-likelihood model");
     if (count != 1) return ctx_fail(ctx, DCGP_ERR_ARG, "get_param(likelihood_variance): expected 1 value");
+    HIP_TRY(ctx, hipMemcpyAsync(out_host, model->d_lik, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return DCGP_OK;
+  }
+  if (!strcmp(which, "likelihood_scale")) {   // model-wide, `layer` is ignored
+    if (model->lik_kind != 4) return ctx_fail(ctx, DCGP_ERR_ARG, "get_param(likelihood_scale): not a StudentT-likelihood model");
+    if (count != 1) return ctx_fail(ctx, DCGP_ERR_ARG, "get_param(likelihood_scale): expected 1 value");
     HIP_TRY(ctx, hipMemcpyAsync(out_host, model->d_lik, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return DCGP_OK;

@@ -234,6 +234,30 @@ int bern_predict(dcgp_ctx* ctx, const double* mu, const double* var, long n, dou
 int bern_eval_tail(dcgp_ctx* ctx, const double* mu, const double* var, const double* y, int n, int S, int K, long lo, double* logdens,
                    double* ld_nd, double* p_mean, double* correct);
 
+// quadrature.hip: the tails of the likelihoods that are a per-element log density under the 20-node Gauss-Hermite rule -- kind 4 StudentT(scale,
+// deg_free nu; c_nu = student_t_const(nu)), kind 5 Poisson(exp link, binsize) -- targets y [n_labels][K] float64, row r reads y[r % n_labels].  The
+// StudentT scale is read from its device word `scale` where that is set (a model's), else from scale_val (the stand-alone entry points).
+// quad_elbo_tail: elbo_tail's counterpart (same scal / fin / KlTail contract; 1 <= K <= 1024, else DCGP_ERR_ARG).  quad_grad: gm, gv [rows][K] and, kind 4,
+// gpar[0] = d / d scale, all times weight.  quad_predict: (E_y, V_y) per element (either may be nullptr).  quad_elementwise: per element of [n]
+// what = 0 the variational expectation, 1 (E_y, V_y), 2 the log density of one sample.  quad_eval_tail: per image the log density summed over K,
+// per (image, k) the log density (ld_nd, may be nullptr) and the sample-mean E_y (y_mean, may be nullptr), per image the squared error of
+// that mean; gauss_eval_sum adds those up.
+struct QuadLik {
+  int kind = 0;                       // 4 StudentT, 5 Poisson
+  const double* scale = nullptr;      // StudentT: the scale's device word, or nullptr: scale_val
+  double scale_val = 1.0, nu = 3.0, c_nu = 0.0, binsize = 1.0;
+};
+double student_t_const(double nu);    // lgamma((nu + 1) / 2) - lgamma(nu / 2) - log(nu pi) / 2
+int quad_elbo_tail(dcgp_ctx* ctx, const QuadLik& q, const double* mu, const double* var, const double* y, int n_rows, int n_labels, int K,
+                   double* ve_rows, double inv_s, double* scal, const ElboFinish& fin, const KlTail* kl = nullptr);
+int quad_grad(dcgp_ctx* ctx, const QuadLik& q, const double* mu, const double* var, const double* y, int rows, int K, int n_labels, double weight,
+              double* gm, double* gv, double* gpar);
+int quad_predict(dcgp_ctx* ctx, const QuadLik& q, const double* mu, const double* var, long n, double* out_mean, double* out_var);
+int quad_elementwise(dcgp_ctx* ctx, const QuadLik& q, int what, const double* mu, const double* var, const double* y, long n, double* out_a,
+                     double* out_b);
+int quad_eval_tail(dcgp_ctx* ctx, const QuadLik& q, const double* mu, const double* var, const double* y, int n, int S, int K, long lo,
+                   double* logdens, double* ld_nd, double* y_mean, double* sqerr);
+
 // softmax.hip: the Softmax likelihood's tails (int32 labels y; nodes [Q][K] on the device, the same table for every row; 2 <= K, 1 <= Q,
 // Q * K <= 4096, else DCGP_ERR_ARG).  softmax_elbo_tail: elbo_tail's counterpart (same scal / fin / KlTail contract); a label outside [0, K) leaves
 // NaN.  softmax_grad: gm, gv [rows][K] times weight.  softmax_predict: out_mean = p, out_var = p - p^2 (either may be nullptr).  softmax_eval_tail /
@@ -280,12 +304,15 @@ int unc_sum(dcgp_ctx* ctx, const UncSumArgs& a, const FactorStatus& st, double* 
 // point they came through).  Each lik_* function dispatches once on the kind to the launchers above and to robustmax_grad (grad.hip: the RobustMax
 // seeds gm, gv [rows][K] = weight * d E_q[log p(y | f)] / d(mean, var)); lik_eval_tail / lik_unc_tail take the whole set's targets and batch `lo`.
 struct Likelihood {
-  int kind = 0;                  // 0 RobustMax, 3 Softmax (labels), 1 Gaussian, 2 Bernoulli (probit) (targets)
+  int kind = 0;                  // 0 RobustMax, 3 Softmax (labels), 1 Gaussian, 2 Bernoulli (probit), 4 StudentT, 5 Poisson (exp link) (targets)
   double eps = 1e-3;             // RobustMax epsilon
-  const double* s2 = nullptr;    // the Gaussian variance's device word
+  const double* s2 = nullptr;    // the Gaussian variance's device word; StudentT: the scale's
   const double* nodes = nullptr; int Q = 0;   // Softmax: the node table [Q][K] on the device (nullptr: none set yet)
-  bool float_targets() const { return kind == 1 || kind == 2; }    // the _f64y entry points
-  int n_params() const { return kind == 1 ? 1 : 0; }   // trainable words (the Gaussian variance): lik_grad_seeds wants a gs2 for each
+  double nu = 3.0, c_nu = 0.0;   // StudentT: degrees of freedom (fixed) and student_t_const(nu)
+  double binsize = 1.0;          // Poisson
+  bool float_targets() const { return kind == 1 || kind == 2 || kind == 4 || kind == 5; }    // the _f64y entry points
+  int n_params() const { return kind == 1 || kind == 4 ? 1 : 0; }   // trainable words (the Gaussian variance, the StudentT scale): lik_grad_seeds wants a gs2 for each
+  QuadLik quad() const { QuadLik q; q.kind = kind; q.scale = s2; q.nu = nu; q.c_nu = c_nu; q.binsize = binsize; return q; }   // kinds 4, 5
 };
 struct Targets {
   const int32_t* labels = nullptr; const double* values = nullptr; int K = 1; bool f64 = false;
@@ -295,7 +322,7 @@ struct Targets {
 struct EvalOut {   // per image of the whole set (p_mean, ld_nd per (image, output); either may be nullptr)
   double* logdens = nullptr; double* ld_nd = nullptr; double* p_mean = nullptr;
   int* ok = nullptr;          // RobustMax: eval_tail's ok
-  double* score = nullptr;    // Gaussian: squared error, Bernoulli: correct outputs
+  double* score = nullptr;    // Gaussian, StudentT, Poisson: squared error, Bernoulli: correct outputs
 };
 int robustmax_grad(dcgp_ctx* ctx, const double* mu, const double* var, const int32_t* y, int rows, int n_labels, int K, double eps, double weight,
                    double* gm, double* gv);
@@ -303,7 +330,7 @@ int lik_check_targets(dcgp_ctx* ctx, const Likelihood& lik, const Targets& t, co
 int lik_elbo_tail(dcgp_ctx* ctx, const Likelihood& lik, const double* mu, const double* var, const Targets& t, int n_rows, int n_labels, int K,
                   double* ve_rows, double inv_s, double* scal, const ElboFinish& fin, const KlTail* kl = nullptr);
 int lik_grad_seeds(dcgp_ctx* ctx, const Likelihood& lik, const double* mu, const double* var, const Targets& t, int rows, int n_labels, int K,
-                   double weight, double* gm, double* gv, double* gs2);   // gs2[0] = d / d s2 (n_params() > 0, else unused)
+                   double weight, double* gm, double* gv, double* gs2);   // gs2[0] = d / d s2 (StudentT: d / d scale) (n_params() > 0, else unused)
 int lik_predict(dcgp_ctx* ctx, const Likelihood& lik, const double* mu, const double* var, long n, double* out_mean, double* out_var);
 // the label likelihoods: lik_class_probs -- out_p [rows][K] class probabilities per row (dcgp_model_predict_y); lik_density_max_k -- the classes the
 // density objective of dcgp_model_input_grad takes; lik_density_grad -- its tail (rm_density_grad, input_grad.hip / softmax_density_grad): J [n_img] and

@@ -1,9 +1,12 @@
 // likelihood.hip -- the one place that knows which likelihood a model has (host code only: no kernels).  Every function takes the
 // Likelihood and the Targets (layer.h) and dispatches once on the kind to the launchers of cond.hip / evaluate.hip / uncertainty.hip /
-// grad.hip / input_grad.hip (RobustMax), gaussian.hip, bernoulli.hip and softmax.hip; what differs between their argument lists ends here.
+// grad.hip / input_grad.hip (RobustMax), gaussian.hip, bernoulli.hip, softmax.hip and quadrature.hip (StudentT, Poisson); what differs between
+// their argument lists ends here.
 #include "layer_impl.h"
 
 int lik_check_targets(dcgp_ctx* ctx, const Likelihood& lik, const Targets& t, const char* who) {
+  if (lik.float_targets() != t.f64 && (lik.kind == 4 || lik.kind == 5))
+    return ctx_fail(ctx, DCGP_ERR_ARG, "%s: a StudentT- or Poisson-likelihood model takes float64 targets (the _f64y entry points)", who);
   if (lik.float_targets() != t.f64)
     return ctx_fail(ctx, DCGP_ERR_ARG, t.f64 ? "%s: a RobustMax or Softmax model takes int32 labels, not float64 targets"
                                              : "%s: a Gaussian- or Bernoulli-likelihood model takes float64 targets (the _f64y entry points)", who);
@@ -17,6 +20,8 @@ int lik_elbo_tail(dcgp_ctx* ctx, const Likelihood& lik, const double* mu, const 
     case 1: return gauss_elbo_tail(ctx, mu, var, t.values, n_rows, n_labels, K, lik.s2, ve_rows, inv_s, scal, fin, kl);
     case 2: return bern_elbo_tail(ctx, mu, var, t.values, n_rows, n_labels, K, ve_rows, inv_s, scal, fin, kl);
     case 3: return softmax_elbo_tail(ctx, mu, var, t.labels, n_rows, n_labels, K, lik.nodes, lik.Q, ve_rows, inv_s, scal, fin, kl);
+    case 4:
+    case 5: return quad_elbo_tail(ctx, lik.quad(), mu, var, t.values, n_rows, n_labels, K, ve_rows, inv_s, scal, fin, kl);
     default: return elbo_tail(ctx, mu, var, t.labels, n_rows, n_labels, K, lik.eps, ve_rows, inv_s, scal, fin, kl);
   }
 }
@@ -29,6 +34,10 @@ int lik_grad_seeds(dcgp_ctx* ctx, const Likelihood& lik, const double* mu, const
       return gauss_grad(ctx, mu, var, t.values, rows, K, n_labels, lik.s2, weight, gm, gv, gs2);
     case 2: return bern_grad(ctx, mu, var, t.values, rows, K, n_labels, weight, gm, gv);
     case 3: return softmax_grad(ctx, mu, var, t.labels, rows, n_labels, K, lik.nodes, lik.Q, weight, gm, gv);
+    case 4:
+      if (!lik.s2 || !gs2) return ctx_fail(ctx, DCGP_ERR_ARG, "grad: the StudentT likelihood has no scale on the device");
+      return quad_grad(ctx, lik.quad(), mu, var, t.values, rows, K, n_labels, weight, gm, gv, gs2);
+    case 5: return quad_grad(ctx, lik.quad(), mu, var, t.values, rows, K, n_labels, weight, gm, gv, nullptr);
     default: return robustmax_grad(ctx, mu, var, t.labels, rows, n_labels, K, lik.eps, weight, gm, gv);
   }
 }
@@ -37,6 +46,8 @@ int lik_predict(dcgp_ctx* ctx, const Likelihood& lik, const double* mu, const do
   switch (lik.kind) {
     case 1: return gauss_predict(ctx, mu, var, n, lik.s2, out_mean, out_var);
     case 2: return bern_predict(ctx, mu, var, n, out_mean, out_var);
+    case 4:
+    case 5: return quad_predict(ctx, lik.quad(), mu, var, n, out_mean, out_var);
     default: return ctx_fail(ctx, DCGP_ERR_ARG, "predict_mean_var: not a Gaussian- or Bernoulli-likelihood model (dcgp_model_predict_y)");
   }
 }
@@ -45,6 +56,8 @@ int lik_class_probs(dcgp_ctx* ctx, const Likelihood& lik, const double* mu, cons
   switch (lik.kind) {
     case 1:
     case 2: return ctx_fail(ctx, DCGP_ERR_ARG, "predict_y: a Gaussian- or Bernoulli-likelihood model predicts with dcgp_model_predict_mean_var");
+    case 4:
+    case 5: return ctx_fail(ctx, DCGP_ERR_ARG, "predict_y: a StudentT- or Poisson-likelihood model predicts with dcgp_model_predict_mean_var");
     case 3:
       if (!lik.nodes) return ctx_fail(ctx, DCGP_ERR_ARG, "predict_y: the Softmax likelihood has no node table yet (dcgp_model_set_likelihood_nodes)");
       return softmax_predict(ctx, mu, var, rows, K, lik.nodes, lik.Q, out_p, nullptr);
@@ -60,13 +73,15 @@ int lik_eval_tail(dcgp_ctx* ctx, const Likelihood& lik, const double* mu, const 
   switch (lik.kind) {
     case 1: return gauss_eval_tail(ctx, mu, var, t.values, n, S, K, lik.s2, lo, o.logdens, o.ld_nd, o.p_mean, o.score);
     case 2: return bern_eval_tail(ctx, mu, var, t.values, n, S, K, lo, o.logdens, o.ld_nd, o.p_mean, o.score);
+    case 4:
+    case 5: return quad_eval_tail(ctx, lik.quad(), mu, var, t.values, n, S, K, lo, o.logdens, o.ld_nd, o.p_mean, o.score);
     case 3: return softmax_eval_tail(ctx, mu, var, t.labels, n, S, K, lik.nodes, lik.Q, lo, o.logdens, o.p_mean, o.ok);
     default: return eval_tail(ctx, mu, var, t.labels, n, S, K, lik.eps, lo, o.logdens, o.p_mean, o.ok);
   }
 }
 
 int lik_eval_sum(dcgp_ctx* ctx, const Likelihood& lik, const EvalOut& o, long n, const FactorStatus& st, double* res) {
-  if (lik.float_targets()) return gauss_eval_sum(ctx, o.logdens, o.score, n, st, res);   // (Bernoulli: the same sum over its correct counts)
+  if (lik.float_targets()) return gauss_eval_sum(ctx, o.logdens, o.score, n, st, res);   // (Bernoulli: the same sum over its correct counts; StudentT, Poisson: squared errors)
   return eval_sum(ctx, o.logdens, o.ok, n, st, res);                                      // (Softmax: eval_tail's outputs, the same sum)
 }
 
@@ -76,6 +91,8 @@ int lik_unc_tail(dcgp_ctx* ctx, const Likelihood& lik, const double* mu, const d
   switch (lik.kind) {
     case 1: return ctx_fail(ctx, DCGP_ERR_ARG, "evaluate_uncertainty: class probabilities need a classification likelihood, this model is Gaussian");
     case 2: return bern_unc_tail(ctx, mu, var, t.values, n, S, K, lo, o);
+    case 4: return ctx_fail(ctx, DCGP_ERR_ARG, "evaluate_uncertainty: class probabilities need a classification likelihood, this model is StudentT");
+    case 5: return ctx_fail(ctx, DCGP_ERR_ARG, "evaluate_uncertainty: class probabilities need a classification likelihood, this model is Poisson");
     case 3: return softmax_unc_tail(ctx, mu, var, t.labels, n, S, K, lik.nodes, lik.Q, lo, o);
     default: return unc_tail(ctx, mu, var, t.labels, n, S, K, lik.eps, lo, o);
   }
@@ -87,7 +104,9 @@ int lik_density_grad(dcgp_ctx* ctx, const Likelihood& lik, const double* mu, con
                      double* gm, double* gv) {
   switch (lik.kind) {
     case 1:
-    case 2: return ctx_fail(ctx, DCGP_ERR_ARG, "input_grad: the density objective exists for the RobustMax and Softmax likelihoods only");
+    case 2:
+    case 4:
+    case 5: return ctx_fail(ctx, DCGP_ERR_ARG, "input_grad: the density objective exists for the RobustMax and Softmax likelihoods only");
     case 3: return softmax_density_grad(ctx, mu, var, y, n_img, S, K, lik.nodes, lik.Q, J, gm, gv);
     default: return rm_density_grad(ctx, mu, var, y, n_img, S, K, lik.eps, J, gm, gv);
   }

@@ -597,6 +597,13 @@ int dcgp_model_set_param(dcgp_model* model, int layer, const char* which, const 
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return DCGP_OK;
   }
+  if (!strcmp(which, "likelihood_scale")) {   // model-wide, `layer` is ignored
+    if (model->lik_kind != 4) return ctx_fail(ctx, DCGP_ERR_ARG, "set_param(likelihood_scale): not a StudentT-likelihood model");
+    if (count != 1 || !(value_host[0] > 1e-6)) return ctx_fail(ctx, DCGP_ERR_ARG, "set_param(likelihood_scale): one value > 1e-6");
+    HIP_TRY(ctx, hipMemcpyAsync(model->d_lik, value_host, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return DCGP_OK;
+  }
   if (layer < 0 || layer >= (int)model->layers.size()) return ctx_fail(ctx, DCGP_ERR_ARG, "set_param: no layer %d", layer);
   LayerState& L = *model->layers[layer];
   auto expect = [&](size_t n) { return count == n ? DCGP_OK : ctx_fail(ctx, DCGP_ERR_ARG, "set_param(%s): expected %zu values, got %zu", which, n, count); };
@@ -697,6 +704,38 @@ int dcgp_model_set_likelihood(dcgp_model* model, int kind, double variance) {
   } else {
     HIP_TRY(ctx, hipMemcpyAsync(model->d_lik, &variance, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   }
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return DCGP_OK;
+}
+
+int dcgp_model_set_likelihood_params(dcgp_model* model, int kind, const double* params_host, int n) {
+  if (!model) return DCGP_ERR_ARG;
+  dcgp_ctx* ctx = model->ctx;
+  if (kind != 4 && kind != 5) return ctx_fail(ctx, DCGP_ERR_ARG, "set_likelihood_params: kind 4 (StudentT) or 5 (Poisson), got %d (dcgp_model_set_likelihood sets the others)", kind);
+  if (!params_host || n != (kind == 4 ? 2 : 1))
+    return ctx_fail(ctx, DCGP_ERR_ARG, "set_likelihood_params: kind %d takes %s", kind, kind == 4 ? "2 values {scale, deg_free}" : "1 value {binsize}");
+  const double p0 = params_host[0], p1 = kind == 4 ? params_host[1] : 0.0;
+  if (kind == 4 && (!(p0 > 1e-6) || !std::isfinite(p0) || !(p1 > 2.0) || !std::isfinite(p1)))
+    return ctx_fail(ctx, DCGP_ERR_ARG, "set_likelihood_params: StudentT needs scale > 1e-6 (softplus + 1e-6) and deg_free > 2, got %g, %g", p0, p1);
+  if (kind == 5 && (!(p0 > 0) || !std::isfinite(p0))) return ctx_fail(ctx, DCGP_ERR_ARG, "set_likelihood_params: Poisson needs binsize > 0, got %g", p0);
+  if (!model->has_head) return ctx_fail(ctx, DCGP_ERR_ARG, "set_likelihood_params: set the head first");
+  LayerState& H = *model->layers.back();
+  if (H.gZ && model->lik_kind != kind) return ctx_fail(ctx, DCGP_ERR_ARG, "set_likelihood_params: the likelihood is fixed once a gradient was taken");
+  if (model->enq_seq != model->col_seq) return ctx_fail(ctx, DCGP_ERR_ARG, "set_likelihood_params: enqueued steps are still to be collected");
+  // a model that has taken steps with int32 labels keeps them (as Softmax is refused on a float64-target model)
+  if (!model->lik().float_targets() && model->enq_seq > 0)
+    return ctx_fail(ctx, DCGP_ERR_ARG, "set_likelihood_params: kind %d takes float64 targets, this model has taken steps with int32 labels (kind %d)", kind, model->lik_kind);
+  const bool fresh = model->lik_kind != kind;
+  ++model->param_version;
+  model->lik_Q = 0;   // (a node table belongs to the Softmax likelihood it was set on)
+  model->lik_kind = kind;
+  H.lik_slots = kind == 4 ? 1 : 0;   // (the StudentT scale takes the Gaussian variance's slot: a Poisson block is a RobustMax one)
+  if (kind == 5) { model->lik_binsize = p0; return DCGP_OK; }
+  model->lik_nu = p1; model->lik_cnu = student_t_const(p1);
+  if (!model->d_lik && hipMalloc((void**)&model->d_lik, 3 * sizeof(double)) != hipSuccess)   // {scale, Adam m, Adam v}
+    return ctx_fail(ctx, DCGP_ERR_ALLOC, "set_likelihood_params: device allocation failed");
+  const double init[3] = {p0, 0.0, 0.0};
+  HIP_TRY(ctx, hipMemcpyAsync(model->d_lik, init, fresh ? sizeof init : sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return DCGP_OK;
 }
@@ -1062,6 +1101,8 @@ int uncertainty_impl(dcgp_model* model, const double* X, const int32_t* y, const
   if (!X || N_total <= 0 || batch <= 0 || S <= 0 || bins < 1 || !out_host)
     return ctx_fail(ctx, DCGP_ERR_ARG, "%s: bad args (N %d, batch %d, S %d, bins %d)", who, N_total, batch, S, bins);
   if (model->lik_kind == 1) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: class probabilities need a classification likelihood, this model is Gaussian", who);
+  if (model->lik_kind == 4 || model->lik_kind == 5)
+    return ctx_fail(ctx, DCGP_ERR_ARG, "%s: class probabilities need a classification likelihood, this model is %s", who, model->lik_kind == 4 ? "StudentT" : "Poisson");
   if (!model->has_head) return ctx_fail(ctx, DCGP_ERR_ARG, "model has no head layer");
   const int K = model->layers.back()->R;
   const Likelihood lik = model->lik();

@@ -12,11 +12,15 @@ struct dcgp_model {
   // d_lik[2] and its gradient in the last slot of the head's gradient block (LayerState::glik).  Bernoulli has no parameter: no d_lik, no slot.
   // 3 Softmax (labels, int32): no parameter either; its node table [lik_Q][K] lives in d_nodes (dcgp_model_set_likelihood_nodes) and is no
   // part of the parameter state -- replacing it starts no new parameter version.
+  // 4 StudentT, 5 Poisson with the exp link (targets [N][K] float64; dcgp_model_set_likelihood_params): the StudentT scale lives where the Gaussian
+  // variance does (d_lik[0], moments beside it, gradient in glik), its degrees of freedom are fixed (lik_nu, lik_cnu = student_t_const(lik_nu));
+  // Poisson has its bin size (lik_binsize) and no trainable parameter.
   int lik_kind = 0;
-  Likelihood lik() const { return Likelihood{lik_kind, eps, d_lik, lik_Q > 0 ? d_nodes : nullptr, lik_Q}; }   // what likelihood.hip's functions take
+  double lik_nu = 3.0, lik_cnu = 0.0, lik_binsize = 1.0;
+  Likelihood lik() const { return Likelihood{lik_kind, eps, d_lik, lik_Q > 0 ? d_nodes : nullptr, lik_Q, lik_nu, lik_cnu, lik_binsize}; }   // what likelihood.hip's functions take
   double* d_lik = nullptr;
   double* d_nodes = nullptr; size_t nodes_cap = 0; int lik_Q = 0;
-  bool lik_frozen = false;   // dcgp_model_set_trainable(.., "likelihood_variance", 0)
+  bool lik_frozen = false;   // dcgp_model_set_trainable(.., "likelihood_variance" / "likelihood_scale", 0)
   std::vector<std::unique_ptr<LayerState>> layers;   // conv layers..., head last (once set)
   bool has_head = false;
   bool keep_outputs = false;

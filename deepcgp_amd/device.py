@@ -84,6 +84,10 @@ _SIGS = {
     "dcgp_robustmax_predict": [_vp, _vp, _vp, _i, _i, _d, _vp],
     "dcgp_softmax_varexp": [_vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp],
     "dcgp_softmax_predict": [_vp, _vp, _vp, _i, _i, _vp, _i, _vp],
+    "dcgp_quad_varexp": [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp],
+    "dcgp_quad_predict": [_vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp],
+    "dcgp_quad_logdensity": [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp],
+    "dcgp_quad_grad_seeds": [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _d, _vp, _vp, _vp],
     "dcgp_reparam": [_vp, _vp, _vp, _vp, _sz, _d, _vp],
     "dcgp_model_create": [_vp, _i, _d, C.POINTER(_vp)],
     "dcgp_model_destroy": [_vp],
@@ -120,6 +124,7 @@ _SIGS = {
     "dcgp_model_layer_output": [_vp, _i, _vp, _vp, _vp, _ip, _ip],
     "dcgp_model_set_likelihood": [_vp, _i, _d],
     "dcgp_model_set_likelihood_nodes": [_vp, _vp, _i],
+    "dcgp_model_set_likelihood_params": [_vp, _i, _vp, _i],
     "dcgp_elbo_forward_f64y": [_vp, _vp, _vp, _i, _d, C.POINTER(_vp), _u64, _i, _dp, _ip],
     "dcgp_elbo_forward_enqueue_f64y": [_vp, _vp, _vp, _i, _d, C.POINTER(_vp), _u64, _i, C.POINTER(_u64)],
     "dcgp_elbo_grad_f64y": [_vp, _vp, _vp, _i, _d, C.POINTER(_vp), _u64, _i, C.POINTER(_d), _ip],

@@ -11,7 +11,7 @@ import numpy as np
 from . import device as dev
 from .kernels import JITTER
 from .layers import ConvLayer, SVGP_Layer
-from .likelihoods import Bernoulli, Gaussian, Softmax
+from .likelihoods import Bernoulli, Gaussian, Poisson, Softmax, StudentT
 
 
 def batched_noise(zs, N, S, batch_size, dims=None):
@@ -54,7 +54,9 @@ class DGP_Base:
         self.gaussian = isinstance(likelihood, Gaussian)
         self.bernoulli = isinstance(likelihood, Bernoulli)
         self.softmax = isinstance(likelihood, Softmax)           # int32 labels like MultiClass; its node table is pushed at build time
-        self.float_targets = self.gaussian or self.bernoulli     # float64 N x D targets and the _f64y entry points
+        self.student_t = isinstance(likelihood, StudentT)       # robust regression: the trainable scale where the Gaussian variance lives
+        self.poisson = isinstance(likelihood, Poisson)          # count targets
+        self.float_targets = self.gaussian or self.bernoulli or self.student_t or self.poisson     # float64 N x D targets and the _f64y entry points
         self.Y = self._targets_host(Y) if self.float_targets else np.ascontiguousarray(np.reshape(Y, (-1,)), np.int32)
         self.num_samples = int(num_samples)
         self.minibatch_size = minibatch_size
@@ -72,13 +74,21 @@ class DGP_Base:
                 raise ValueError("hidden layers must be ConvLayer instances")
 
     def _targets_host(self, Y, n=None):
-        """Gaussian or Bernoulli likelihood: float64 targets N x D, D the head's num_outputs (Bernoulli: bool, int or float
-        values in {0, 1})."""
+        """Gaussian, Bernoulli, StudentT or Poisson likelihood: float64 targets N x D, D the head's num_outputs (Bernoulli: bool, int or
+        float values in {0, 1}; Poisson: finite non-negative integer values)."""
         D = self.layers[-1].num_outputs
-        kind = "Gaussian" if self.gaussian else "Bernoulli"
+        kind = self._lik_name()
         Y = np.asarray(Y)
         if self.bernoulli and Y.size and not np.all((Y == 0) | (Y == 1)):
             raise ValueError("Bernoulli likelihood: targets must be 0 or 1")
+        if self.poisson and Y.size:
+            Yf = Y.astype(np.float64)
+            if not np.all(np.isfinite(Yf)):
+                raise ValueError("Poisson likelihood: targets must be finite")
+            if not np.all(Yf >= 0):
+                raise ValueError("Poisson likelihood: targets must be >= 0")
+            if not np.all(Yf == np.floor(Yf)):
+                raise ValueError("Poisson likelihood: targets must be integer-valued counts")
         Y = Y.astype(np.float64)
         if Y.ndim == 1 and D == 1:
             Y = Y[:, None]
@@ -87,6 +97,13 @@ class DGP_Base:
         if n is not None and Y.shape[0] != n:
             raise ValueError("%d targets for %d images" % (Y.shape[0], n))
         return np.ascontiguousarray(Y)
+
+    def _lik_name(self):
+        for flag, name in (("gaussian", "Gaussian"), ("bernoulli", "Bernoulli"), ("student_t", "StudentT"), ("poisson", "Poisson"),
+                           ("softmax", "Softmax")):
+            if getattr(self, flag):
+                return name
+        return "RobustMax"
 
     def _targets(self, Y, N):
         """(device targets, float64?) of an explicit minibatch: float64 N x D (Gaussian, Bernoulli) or int32 labels."""
@@ -175,6 +192,9 @@ class DGP_Base:
             ctx._check(L.dcgp_model_set_likelihood(self._model, 3, 0.0))
             self.push_likelihood_nodes()
             self.likelihood._attach(self)
+        elif self.student_t or self.poisson:
+            par = np.ascontiguousarray(self.likelihood._params(), np.float64)
+            ctx._check(L.dcgp_model_set_likelihood_params(self._model, self.likelihood.kind, par.ctypes.data, par.size))
 
     def push_likelihood_nodes(self):
         """Softmax likelihood: copy ``likelihood.nodes`` [Q, K] to the built device model (dcgp_model_set_likelihood_nodes).  The table is no
@@ -209,6 +229,8 @@ class DGP_Base:
         push(0, "likelihood_epsilon", float(getattr(self.likelihood, "epsilon", 1e-3)))
         if self.gaussian:
             push(0, "likelihood_variance", float(self.likelihood.variance))
+        if self.student_t:
+            push(0, "likelihood_scale", float(self.likelihood.scale))
 
     @property
     def parameters(self):
@@ -218,6 +240,9 @@ class DGP_Base:
         if self.gaussian:                            # Gaussian variance under the BroadcastingLikelihood wrapper's doubled path
             out.append(Parameter("%s/likelihood/likelihood/variance" % self.name, lambda: np.array(self.likelihood.variance),
                                  lambda v: setattr(self.likelihood, "variance", float(v))))
+        if self.student_t:                           # StudentT scale, beside the Gaussian's path (deg_free is no parameter)
+            out.append(Parameter("%s/likelihood/likelihood/scale" % self.name, lambda: np.array(self.likelihood.scale),
+                                 lambda v: setattr(self.likelihood, "scale", float(v))))
         if hasattr(self.likelihood, "epsilon"):     # RobustMax epsilon under the BroadcastingLikelihood wrapper's doubled path
             out.append(Parameter("%s/likelihood/likelihood/invlink/epsilon" % self.name, lambda: np.array(self.likelihood.epsilon),
                                  lambda v: setattr(self.likelihood, "epsilon", float(v))))
@@ -357,6 +382,10 @@ class DGP_Base:
             buf = np.empty(1, np.float64)
             ctx._check(L.dcgp_model_get_grad(self._model, 0, b"likelihood_variance", buf.ctypes.data, 1))
             grads[-1]["likelihood_variance"] = buf.reshape(())
+        if self.student_t:       # d ELBO / d likelihood scale, in the same slot
+            buf = np.empty(1, np.float64)
+            ctx._check(L.dcgp_model_get_grad(self._model, 0, b"likelihood_scale", buf.ctypes.data, 1))
+            grads[-1]["likelihood_scale"] = buf.reshape(())
         return out[0], grads
 
     OBJECTIVES = {"density": 0, "elbo": 1}
@@ -367,7 +396,7 @@ class DGP_Base:
             raise ValueError("objective must be 'density' or 'elbo', got %r" % (objective,))
         if objective == "density" and self.float_targets:
             raise NotImplementedError("input_gradient: the 'density' objective exists for the RobustMax and Softmax likelihoods only; a %s model takes "
-                                      "objective='elbo'" % ("Gaussian" if self.gaussian else "Bernoulli"))
+                                      "objective='elbo'" % self._lik_name())
         S = self.num_samples if S is None else int(S)
         if S < 1:
             raise ValueError("S must be >= 1")
@@ -412,7 +441,8 @@ class DGP_Base:
         S = self.num_samples if S is None else int(S)
         if Y is None:
             if self.float_targets:
-                raise ValueError("saliency: a Gaussian or Bernoulli model needs targets Y")
+                raise ValueError("saliency: a Gaussian or Bernoulli model needs targets Y" if self.gaussian or self.bernoulli else
+                                 "saliency: a %s model needs targets Y" % self._lik_name())
             Y = self.predict_proba(X, S, zs=zs, seed=seed).argmax(axis=1)
         _, g = self.input_gradient(X, Y, S=S, objective=objective, zs=zs, seed=seed)
         l0 = self.layers[0]
@@ -504,7 +534,7 @@ class DGP_Base:
     def set_trainable(self, layer, which, on):
         """param.set_trainable(on) for the device optimiser steps: which in Z, q_mu, q_sqrt, w, hyper (every kernel parameter of the layer);
         weight_variances, bias_variance (that one parameter of an ArcCosine conv layer); "likelihood_variance" (Gaussian likelihood,
-        ``layer`` ignored)."""
+        ``layer`` ignored); "likelihood_scale" (StudentT likelihood, ``layer`` ignored)."""
         self._build()
         self._ctx._check(dev.lib().dcgp_model_set_trainable(self._model, int(layer), which.encode(), int(bool(on))))
 
@@ -547,6 +577,8 @@ class DGP_Base:
                 l.kern.patch_weights = pull(li, "w", np.shape(l.kern.patch_weights))
         if self.gaussian:
             self.likelihood.variance = float(pull(0, "likelihood_variance", ()))
+        if self.student_t:
+            self.likelihood.scale = float(pull(0, "likelihood_scale", ()))
 
     def propagate(self, X, full_cov=False, S=1, zs=None, seed=0):
         """(Fs, Fmeans, Fvars): per layer S x N x D_l arrays (doubly_stochastic_dgp DGP_Base.propagate); full_cov=True: see
@@ -648,7 +680,8 @@ class DGP_Base:
         """(mean, var) of p(y*) per sample: S x N x num_classes (used at conv_gp/utils/log.py:62-66).
         One device call: forward pass and RobustMax quadrature, only the probabilities come back.  Gaussian likelihood:
         (Fmean, Fvar + variance), each S x N x D (dcgp_model_predict_mean_var); Bernoulli: (p, p - p^2) with
-        p = probit(Fmean / sqrt(1 + Fvar)), each S x N x D."""
+        p = probit(Fmean / sqrt(1 + Fvar)), each S x N x D; StudentT, Poisson: (E_y, V_y) of the 20-node rule, each S x N x D
+        (StudentT: Fmean and Fvar + scale^2 nu / (nu - 2))."""
         if np.shape(X)[0] == 0:
             K = self.layers[-1].num_outputs
             return np.zeros((S, 0, K)), np.zeros((S, 0, K))
@@ -673,8 +706,8 @@ class DGP_Base:
         """Class probabilities averaged over the S samples, N x num_classes (the quantity AccuracyLogger
         arg-maxes, conv_gp/utils/log.py:62-67); the sample mean is taken on the device.  Bernoulli likelihood: the sample-mean
         p(y = 1), N x D (the mean over S of ``predict_y``'s p, summed in sample order as ``evaluate`` sums it)."""
-        if self.gaussian:
-            raise ValueError("predict_proba: class probabilities need a classification likelihood, this model is Gaussian")
+        if self.gaussian or self.student_t or self.poisson:
+            raise ValueError("predict_proba: class probabilities need a classification likelihood, this model is %s" % self._lik_name())
         if np.shape(X)[0] == 0:
             return np.zeros((0, self.layers[-1].num_outputs))
         if self.bernoulli:
@@ -781,7 +814,8 @@ class DGP_Base:
         """Log predictive density of each label, N x 1: logsumexp_s log p(y | f_s) - log S (doubly_stochastic_dgp
         DGP_Base.predict_density with the RobustMax likelihood).  Gaussian likelihood: N x D, per output
         logsumexp_s log N(y; Fmean_s, Fvar_s + variance) - log S; Bernoulli: N x D, per output logsumexp_s log p(y | p_s) - log S with
-        p_s = probit(Fmean_s / sqrt(1 + Fvar_s)).  One device call; ``zs`` per layer [S, N, D]."""
+        p_s = probit(Fmean_s / sqrt(1 + Fvar_s)); StudentT, Poisson: N x D, per output logsumexp_s ld_s - log S with ld_s the 20-node
+        log density of sample s.  One device call; ``zs`` per layer [S, N, D]."""
         N = np.shape(X)[0]
         if N == 0:
             return np.zeros((0, self.layers[-1].num_outputs if self.float_targets else 1))
@@ -796,11 +830,12 @@ class DGP_Base:
         sample-mean prediction over all N x D targets), with ``per_image`` also "log_density" [N] (summed over the D outputs) and
         "y_mean" [N, D].  Bernoulli likelihood: {"accuracy", "mean_log_density", "n"}, the accuracy over all N x D entries (an entry is
         correct when its label is 1 exactly where the sample-mean p > 0.5), with ``per_image`` also "log_density" [N] (summed over the
-        D outputs) and "p_mean" [N, D] (the sample-mean p).  Rank-local: nothing is reduced across ranks."""
+        D outputs) and "p_mean" [N, D] (the sample-mean p).  StudentT, Poisson: what a Gaussian model returns, "y_mean" the sample-mean
+        E_y.  Rank-local: nothing is reduced across ranks."""
         N = np.shape(X)[0]
         if int(batch_size) <= 0:
             raise ValueError("batch_size must be positive, got %r" % (batch_size,))
-        if self.gaussian:
+        if self.gaussian or self.student_t or self.poisson:
             D = self.layers[-1].num_outputs
             if N == 0:
                 out = {"mean_log_density": float("nan"), "rmse": float("nan"), "n": 0}
@@ -883,8 +918,8 @@ class DGP_Base:
         With ``per_image`` also "predictive_entropy", "expected_entropy", "mutual_information", "confidence" and "prediction" per image.
         Bernoulli likelihood: every (image, output) entry counts, with the binary entropy, confidence max(pbar, 1 - pbar) and prediction
         pbar > 0.5; the per-image arrays are N x D.  A Gaussian model has no class probabilities: ValueError.  Rank-local."""
-        if self.gaussian:
-            raise ValueError("evaluate_uncertainty: class probabilities need a classification likelihood, this model is Gaussian")
+        if self.gaussian or self.student_t or self.poisson:
+            raise ValueError("evaluate_uncertainty: class probabilities need a classification likelihood, this model is %s" % self._lik_name())
         N = np.shape(X)[0]
         if int(batch_size) <= 0:
             raise ValueError("batch_size must be positive, got %r" % (batch_size,))
@@ -916,8 +951,8 @@ class DGP_Base:
         {"p_mean", "predictive_entropy", "expected_entropy", "mutual_information", "confidence", "prediction"} as
         ``evaluate_uncertainty(per_image=True)`` returns them.  ``batch_size`` None: one batch of all N images (``predict_proba``'s
         samples for the same ``seed`` / ``zs``); otherwise batch i draws from ``seed + i``.  Rank-local."""
-        if self.gaussian:
-            raise ValueError("predict_uncertainty: class probabilities need a classification likelihood, this model is Gaussian")
+        if self.gaussian or self.student_t or self.poisson:
+            raise ValueError("predict_uncertainty: class probabilities need a classification likelihood, this model is %s" % self._lik_name())
         N = np.shape(X)[0]
         if N == 0:
             out = self._uncertainty_empty()

@@ -1,5 +1,6 @@
 """Likelihoods of the model path: MultiClass with the RobustMax inverse link -- the gpflow.likelihoods.MultiClass(10) the
-reference builds at /root/reference/conv_gp/models.py:67 (20 Gauss-Hermite points, epsilon 1e-3) -- Gaussian, Bernoulli and Softmax."""
+reference builds at /root/reference/conv_gp/models.py:67 (20 Gauss-Hermite points, epsilon 1e-3) -- Gaussian, Bernoulli, Softmax, StudentT
+and Poisson."""
 import numpy as np
 
 from . import device as dev
@@ -139,6 +140,114 @@ class Bernoulli:
         h, e = h2(pbar), h2(ps).sum(0) / ps.shape[0]
         return {"p_mean": pbar, "predictive_entropy": h, "expected_entropy": e, "mutual_information": h - e,
                 "confidence": np.maximum(pbar, 1 - pbar), "prediction": (pbar > 0.5).astype(np.int32)}
+
+
+class _Quadrature:
+    """What StudentT and Poisson share: the 20-node Gauss-Hermite rule of gpflow's ndiagquad applied to a per-element log density.  With
+    x_i, w_i the nodes and weights, c_i = w_i / sqrt(pi), s = sqrt(max(2 Fvar, 1e-10)) and f_i = Fmu + s x_i:
+      variational expectation  sum_i c_i logp(f_i, Y),
+      predictive mean E_y = sum_i c_i conditional_mean(f_i), variance sum_i c_i (conditional_variance(f_i) + conditional_mean(f_i)^2) - E_y^2,
+      predictive density logsumexp_i (logp(f_i, Y) + log c_i).
+    On the model path (DGP_Base with such a likelihood) every tail runs on the device (csrc/quadrature.hip);
+    ``variational_expectations`` on arrays goes through the device too (dcgp_quad_varexp), the other methods are NumPy."""
+    num_gauss_hermite_points = 20
+    kind = None
+
+    def _params(self):
+        raise NotImplementedError
+
+    def _nodes(self, Fmu, Fvar):
+        Fmu, Fvar = np.asarray(Fmu, np.float64), np.asarray(Fvar, np.float64)
+        x, w = np.polynomial.hermite.hermgauss(self.num_gauss_hermite_points)
+        return Fmu[..., None] + np.sqrt(np.maximum(2 * Fvar, 1e-10))[..., None] * x, w / np.sqrt(np.pi)
+
+    def predict_mean_and_var(self, Fmu, Fvar):
+        F, c = self._nodes(Fmu, Fvar)
+        cm = self.conditional_mean(F)
+        e = (cm * c).sum(-1)
+        return e, ((self.conditional_variance(F) + np.square(cm)) * c).sum(-1) - np.square(e)
+
+    def predict_density(self, Fmu, Fvar, Y):
+        F, c = self._nodes(Fmu, Fvar)
+        t = self.logp(F, np.asarray(Y, np.float64)[..., None]) + np.log(c)
+        mx = t.max(-1)
+        return mx + np.log(np.exp(t - mx[..., None]).sum(-1))
+
+    def variational_expectations(self, Fmu, Fvar, Y):
+        ctx = dev.get_context()
+        Fmu, Fvar, Y = (np.ascontiguousarray(a, np.float64) for a in (Fmu, Fvar, Y))
+        if Fmu.ndim != 2 or Fvar.shape != Fmu.shape or Y.shape != Fmu.shape:
+            raise ValueError("Fmu, Fvar and Y must be N x D arrays of one shape, got %r, %r, %r" % (Fmu.shape, Fvar.shape, Y.shape))
+        n, K = Fmu.shape
+        if Fmu.size == 0:
+            return np.zeros((n, K))
+        par = np.ascontiguousarray(self._params(), np.float64)
+        dmu, dvar, dy = ctx.to_device(Fmu), ctx.to_device(Fvar), ctx.to_device(Y)
+        out = ctx.empty((n, K))
+        ctx._check(dev.lib().dcgp_quad_varexp(ctx.handle, self.kind, par.ctypes.data, dmu.ptr, dvar.ptr, dy.ptr, n, K, out.ptr))
+        return out.numpy()
+
+
+def _lgamma(x):
+    from math import lgamma
+    return np.vectorize(lgamma, otypes=[np.float64])(np.asarray(x, np.float64))
+
+
+class StudentT(_Quadrature):
+    """gpflow 1.x likelihoods.StudentT(scale, deg_free) as DS-DGP's BroadcastingLikelihood applies it: robust regression, float64 targets
+    N x D, logp(f, y) = c_nu - log scale - (nu + 1) / 2 log1p(((y - f) / scale)^2 / nu) with c_nu = lgamma((nu + 1) / 2) - lgamma(nu / 2) -
+    log(nu pi) / 2.  ``scale`` is trainable, kept positive by transforms.positive (softplus + 1e-6); ``deg_free`` (> 2, so that the
+    predictive variance exists) is fixed at construction, as in gpflow."""
+    kind = 4
+
+    def __init__(self, scale=1.0, deg_free=3.0):
+        self.scale, self.deg_free = float(scale), float(deg_free)
+        if not (self.scale > 1e-6 and np.isfinite(self.scale)):
+            raise ValueError("the StudentT scale must be > 1e-6, got %r" % (scale,))
+        if not (self.deg_free > 2.0 and np.isfinite(self.deg_free)):
+            raise ValueError("the StudentT deg_free must be > 2, got %r" % (deg_free,))
+
+    def _params(self):
+        return [self.scale, self.deg_free]
+
+    def logp(self, F, Y):
+        from math import lgamma, log, pi
+        F, Y = np.asarray(F, np.float64), np.asarray(Y, np.float64)
+        nu = self.deg_free
+        c = lgamma(0.5 * (nu + 1)) - lgamma(0.5 * nu) - 0.5 * log(nu * pi)
+        return c - np.log(self.scale) - 0.5 * (nu + 1) * np.log1p(np.square((Y - F) / self.scale) / nu)
+
+    def conditional_mean(self, F):
+        return np.array(F, np.float64)
+
+    def conditional_variance(self, F):
+        return np.full(np.shape(F), self.scale ** 2 * self.deg_free / (self.deg_free - 2.0))
+
+
+class Poisson(_Quadrature):
+    """gpflow 1.x likelihoods.Poisson(invlink=exp, binsize) as DS-DGP's BroadcastingLikelihood applies it: count targets (non-negative
+    integer values, float64 N x D), logp(f, y) = y (f + log b) - b e^f - lgamma(y + 1).  The variational expectation is gpflow's closed form
+    for the exp link, y Fmu - b exp(Fmu + Fvar / 2) - lgamma(y + 1) + y log b.  No trainable parameters."""
+    kind = 5
+
+    def __init__(self, invlink="exp", binsize=1.0):
+        if invlink != "exp":
+            raise ValueError("Poisson: only the exp link is supported, got %r" % (invlink,))
+        self.invlink, self.binsize = invlink, float(binsize)
+        if not (self.binsize > 0 and np.isfinite(self.binsize)):
+            raise ValueError("the Poisson binsize must be > 0, got %r" % (binsize,))
+
+    def _params(self):
+        return [self.binsize]
+
+    def logp(self, F, Y):
+        F, Y = np.asarray(F, np.float64), np.asarray(Y, np.float64)
+        return Y * (F + np.log(self.binsize)) - self.binsize * np.exp(F) - _lgamma(Y + 1.0)
+
+    def conditional_mean(self, F):
+        return self.binsize * np.exp(np.asarray(F, np.float64))
+
+    conditional_variance = conditional_mean
 
 
 def softmax_nodes(num_classes, num_points, rng):

@@ -163,6 +163,8 @@ class AccuracyLogger(object):
     def __call__(self, model, seed=0):
         if getattr(model, "gaussian", False):
             raise ValueError("AccuracyLogger: accuracy needs a classification likelihood, this model is Gaussian")
+        if getattr(model, "student_t", False) or getattr(model, "poisson", False):
+            raise ValueError("AccuracyLogger: accuracy needs a classification likelihood, this model is %s" % model._lik_name())
         if getattr(model, "bernoulli", False):
             return self._binary(model, seed)
         correct = 0

@@ -203,6 +203,27 @@ int dcgp_softmax_varexp(dcgp_ctx* ctx, const double* mu, const double* var, cons
                         int K, const double* nodes, int Q, double* out_n);
 int dcgp_softmax_predict(dcgp_ctx* ctx, const double* mu, const double* var, int n, int K,
                          const double* nodes, int Q, double* out_p);
+/* gpflow likelihoods.StudentT(scale, deg_free) (kind 4, params_host = {scale > 1e-6, deg_free > 2}) and likelihoods.Poisson(invlink=exp,
+ * binsize) (kind 5, params_host = {binsize > 0}) on arrays mu, var, y, out [n, K] (device; y float64), per element with the 20 Gauss-Hermite
+ * nodes x_i, c_i = w_i / sqrt(pi), f_i = mu + sqrt(max(2 var, 1e-10)) x_i:
+ *   dcgp_quad_varexp      Likelihood.variational_expectations: sum_i c_i logp(f_i, y); Poisson: gpflow's closed form
+ *                         y mu - b exp(mu + var / 2) - lgamma(y + 1) + y log b,
+ *   dcgp_quad_predict     Likelihood.predict_mean_and_var: E_y = sum_i c_i cm(f_i), V_y = sum_i c_i (cv(f_i) + cm(f_i)^2) - E_y^2 (StudentT: the
+ *                         closed forms mu and var + scale^2 nu / (nu - 2); Poisson: cm = cv = b e^f); either output may be NULL,
+ *   dcgp_quad_logdensity  Likelihood.predict_density: logsumexp_i (logp(f_i, y) + log c_i),
+ * with logp = c_nu - log scale - (nu + 1) / 2 log1p(((y - f) / scale)^2 / nu) or y (f + log b) - b e^f - lgamma(y + 1).  Another kind, a
+ * bad parameter or n, K <= 0: DCGP_ERR_ARG.                                                       */
+int dcgp_quad_varexp(dcgp_ctx* ctx, int kind, const double* params_host, const double* mu, const double* var, const double* y,
+                     int n, int K, double* out);
+int dcgp_quad_predict(dcgp_ctx* ctx, int kind, const double* params_host, const double* mu, const double* var, int n, int K,
+                      double* out_mean, double* out_var);
+int dcgp_quad_logdensity(dcgp_ctx* ctx, int kind, const double* params_host, const double* mu, const double* var, const double* y,
+                         int n, int K, double* out);
+/* The reverse tail of dcgp_quad_varexp on the same arrays (what TensorFlow autodiff of Likelihood.variational_expectations gives):
+ * out_gm, out_gv [n, K] = weight * d varexp / d(mu, var) per element (d / d var = 0 where 2 var <= 1e-10) and, kind 4, out_gparam [1] (device) =
+ * weight * the sum over the elements of d varexp / d scale, summed in a fixed order; kind 5 leaves out_gparam alone (it may be NULL). */
+int dcgp_quad_grad_seeds(dcgp_ctx* ctx, int kind, const double* params_host, const double* mu, const double* var, const double* y,
+                         int n, int K, double weight, double* out_gm, double* out_gv, double* out_gparam);
 /* doubly_stochastic_dgp.utils.reparameterize: out = mean + z*sqrt(var + jitter), n elements.     */
 int dcgp_reparam(dcgp_ctx* ctx, const double* mean, const double* var, const double* z, size_t n,
                  double jitter, double* out);
@@ -409,6 +430,21 @@ int dcgp_model_set_likelihood(dcgp_model* model, int kind, double variance);
  * keeps its chain.  A kind-3 model without a table refuses every step with DCGP_ERR_ARG; on a model of another kind the call is
  * DCGP_ERR_ARG.  Every sum runs in a fixed order (no atomics): two calls give the same bits, whatever the number of ranks. */
 int dcgp_model_set_likelihood_nodes(dcgp_model* model, const double* nodes_host, int Q);
+/* The StudentT and Poisson likelihoods of a model (gpflow 1.x likelihoods.StudentT(scale, deg_free) / likelihoods.Poisson(invlink=exp, binsize)
+ * under DS-DGP's BroadcastingLikelihood; replaces the likelihood argument of DS-DGP DGP_Base.__init__ for them): kind 4 with params_host =
+ * {scale, deg_free} (n = 2; scale > 1e-6, deg_free > 2), kind 5 with params_host = {binsize} (n = 1; binsize > 0).  Float64 targets y [N, K]
+ * (Poisson: non-negative integer values) through the _f64y entry points, every output an independent target; the formulas are those of
+ * dcgp_quad_varexp / _predict / _logdensity above, the gradient the exact derivative of what the forward computes (d / d var = 0 where the
+ * clamp holds), dcgp_model_predict_mean_var gives (E_y, V_y), dcgp_model_predict_density_f64y logsumexp_s ld_s - log S per (image, output),
+ * dcgp_model_evaluate_f64y what it gives a Gaussian model (the squared error of the sample-mean E_y).  The StudentT scale is trainable: it
+ * lives where the Gaussian variance does (the same positive transform softplus + 1e-6, its gradient in the last slot of the head's gradient
+ * block) and is "likelihood_scale" in dcgp_model_set_param / _get_param / _get_grad / _set_trainable (`layer` ignored; a value must be
+ * > 1e-6; DCGP_ERR_ARG on a model of another kind); deg_free is fixed.  Poisson has no trainable parameter: its gradient blocks have the
+ * RobustMax layout.  dcgp_model_predict_y, dcgp_model_evaluate_uncertainty(_f64y), the density objective of dcgp_model_input_grad and the int32
+ * entry points return DCGP_ERR_ARG on these models.  DCGP_ERR_ARG too for a bad value, a wrong n, any other kind (dcgp_model_set_likelihood
+ * sets those, and itself refuses kinds 4 and 5), a model that has taken steps with int32 labels, enqueued steps outstanding, or another
+ * kind than the model's once a gradient was taken. */
+int dcgp_model_set_likelihood_params(dcgp_model* model, int kind, const double* params_host, int n);
 /* dcgp_elbo_forward / _enqueue with Gaussian targets y [N, K] float64 (device): DGP_Base._build_likelihood with
  * Gaussian.variational_expectations = -0.5 log(2 pi s2) - 0.5 ((y - mu)^2 + var) / s2 summed over the K outputs.  Tickets are
  * collected with dcgp_elbo_forward_collect. */
