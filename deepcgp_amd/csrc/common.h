@@ -45,6 +45,7 @@ struct DcgpOptions {
                                  // (-1, 0: never -- measured slower at every shard, fused_plan.h; q > 0: this many parts; -2: q by the simulated deal)
   long fused_rep_share = -1;     // persistent layer kernel on a tiled batch: the strips that show the same images at the same patches share one prologue, handed over by
                                  // the first of them (-1: where the simulated deal has it ahead; 0: never -- the launch of fused_pre alone)
+  long head_ride = -1;           // the head's Kzx sweep as items of the layer kernel's persistent launch (-1: where fused_plan.h: plan_head_ride admits it; 0: never)
   long fused_wgs = 0;            // persistent layer kernel: this many workgroups instead of one per slot of the chip (0: all; tests: several rounds on a small layer)
   long fused_stagger = -1;       // persistent layer kernel: microseconds the second workgroup of a CU holds back (-1: default; 0: none)
   long kl_side = 0;              // KL terms by their own launches on the side stream instead of inside the tail launch
@@ -115,6 +116,8 @@ struct dcgp_ctx {
   hipEvent_t ev_g[6] = {};
   hipEvent_t ev_aux = nullptr, ev_aux2 = nullptr;  // fork / join of a short side-stream excursion inside a layer
   std::string err;
+  int last_head_rows = 0; long head_ride_launches = 0;   // debugging aid (dcgp_debug_head_ride)
+  unsigned fused_head_epoch = 0;  // ... and the strips' done-flags of a launch that carries head rows
   unsigned fused_pre_epoch = 0;   // the hand-over area of the layer kernel (conv_fused.hip): launches that used it so far
   std::string ws_tag;   // suffix of the chain's / KL terms' scratch names: steps in flight on the two banks must not share them
   // named, grow-only device workspaces owned by the ctx
@@ -412,6 +415,7 @@ struct HeadUnitsArgs {
 };
 void head_units_plan(HeadUnitsArgs* a);
 bool head_units_ok(const HeadUnitsArgs& a);
+size_t head_units_lds(const HeadUnitsArgs& a);   // dynamic LDS of a workgroup, bytes (behind head_units_plan)
 int head_units(dcgp_ctx* ctx, const HeadUnitsArgs& a);
 int sweep_operand(dcgp_ctx* ctx, const double* Z, const double* in_scale, int M, int Mp, int L, double variance, double lengthscale, double* ZS);
 int kdiag_reduce(dcgp_ctx* ctx, const double* partial, int n_parts, int N, double scale, double* out_N);   // out[n] = scale * sum_i partial[n * n_parts + i]

@@ -22,6 +22,7 @@
 #include <tuple>
 
 #include "fused_plan.h"
+#include "head_units_dev.h"
 #include "layer.h"
 #include "rng.h"
 
@@ -68,7 +69,9 @@ __device__ __forceinline__ int frag_of(int w, int W, int c) { return (c >> 1) * 
 // A-operand loads, 2 = without the LDS reads of the B operand, 4 = two more A tiles in flight.
 // BTP: 0 RBF, 1 ArcCosine, 2 RBF on 5 x 5 x 10 patches (the in-kernel sweep walks patch rows; an instance of its own so that the others do not carry its registers),
 // 3 Matern32, 4 Matern52 (ArcCosine's route: raw dot products, the norms applied after the sweep)
-template <int FN, int NS, int MAXF, int NT, int BTP, int ABL = 0>
+// HEAD: the launch also carries the rows of the head's patch sweep (a.head_n items behind the last strip item: below).  An instance of its own, launched only where
+// fused_plan::plan_head_ride says so: every other launch runs the code it ran before.
+template <int FN, int NS, int MAXF, int NT, int BTP, int ABL = 0, int HEAD = 0>
 __global__ __launch_bounds__(NT) void conv_fused_kernel(ConvFusedArgs a_in) {
   constexpr int BT = BTP == 1 ? 1 : (BTP == 3 ? 2 : (BTP == 4 ? 3 : 0));   // BaseKernel type
   // The arguments are read through the kernarg pointer, which every strip of a persistent workgroup sees as a new value: as a by-value
@@ -103,7 +106,7 @@ __global__ __launch_bounds__(NT) void conv_fused_kernel(ConvFusedArgs a_in) {
     }
   }
   int strip_next = blockIdx.x;
-  if (a.pre_n > 0) {
+  if (HEAD || a.pre_n > 0) {   // (head rows: a row's strips must be held by running workgroups, like a prologue's)
     // Prologues ahead: EVERY item, a workgroup's first included, comes off the counter -- an item is then held by a workgroup that is running.  (Dealt by
     // blockIdx, a prologue item could belong to a workgroup that is not resident yet -- the chip shared with another kernel, a CU-masked stream -- while a
     // running one already waits for its A1.)
@@ -114,13 +117,47 @@ __global__ __launch_bounds__(NT) void conv_fused_kernel(ConvFusedArgs a_in) {
     __syncthreads();
   }
   // (a workgroup that starts when every item has been dealt -- more workgroups than CUs it may run on -- has nothing to do but sign off)
-  const int first_limit = a.pre_n > 0 ? a.n_items : 0x7fffffff;
+  const int first_limit = HEAD ? a.n_items + a.head_n : (a.pre_n > 0 ? a.n_items : 0x7fffffff);
   for (int it = 0; strip_next < first_limit; ++it) {
   // every strip sees the kernarg pointer and the thread index as new values: nothing of a strip's set-up (argument words, per-lane offsets of every
   // phase) is then loop-invariant, hoisted and kept live across the whole body -- as plain invariants they cost 240 spilled VGPRs at 16 waves
   int tid = threadIdx.x;
   asm volatile("" : "+s"(ap), "+v"(tid));
   KArgs& a = *ap;
+  if constexpr (HEAD) {
+    // ---- a head row (item a.n_items + row): the head's Kzx units of that row, one Z fragment per wave, by the device code of head_units_kernel itself
+    // (head_units_dev.h: a.head is that launch's argument block with one workgroup per row) -- the values go where the head's conditional reads them.
+    // The row's input is this layer's sample of the strips that cover its columns: each sets its flag word to the launch's epoch behind its coherent
+    // stores.  Head rows are dealt behind every strip item, so a strip a row waits for is an earlier item, held by a workgroup that is running and that
+    // waits for nothing a head row produces (the invariant of the A1 hand-over; the same bounded spin, and a row that gave up leaves NaNs).
+    if (strip_next >= a.n_items) {
+      int* tk = reinterpret_cast<int*>(smem + a.lds_main + a.lds_img + BN);
+      const int row = strip_next - a.n_items;
+      if (tid == 0) {
+        const int s_hi = (row * a.P + a.P - 1) / BN;
+        int ok = 1;
+        for (int st = (row * a.P) / BN; st <= s_hi && ok; ++st) {
+          ok = 0;
+          for (int spin = 0; spin < (1 << 24) && !ok; ++spin) {
+            ok = __hip_atomic_load(a.head_flag + st, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == a.head_epoch ? 1 : 0;
+            if (!ok) __builtin_amdgcn_s_sleep(2);
+          }
+        }
+        tk[1] = ok;
+      }
+      __syncthreads();
+      if (tk[1]) {
+        head_units_dev::head_units_body<0, 50, 0, NT, true>(ap->head, row);
+      } else {
+        for (int m = tid; m < a.head.kzx_rows; m += NT) a.head.kzx[(long)m * a.head.ldk + row] = __builtin_nan("");
+      }
+      if (tid == 0) tk[0] = atomicAdd(a.dyn, 1);
+      __syncthreads();   // (and every wave is done with the row's image)
+      strip_next = __builtin_amdgcn_readfirstlane(tk[0]);
+      if (strip_next >= first_limit) break;
+      continue;
+    }
+  }
   const int Mp = a.Mp, nf = Mp >> 4, R = a.R;
   const int lane = tid & 63, lrow = lane >> 4, lcol = lane & 15;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -778,7 +815,9 @@ __global__ __launch_bounds__(NT) void conv_fused_kernel(ConvFusedArgs a_in) {
       if (a.out_var) a.out_var[o] = v;
       if (a.out_sample) {
         const double zz = a.z ? a.z[o] : philox_normal(a.seed, a.stream_id, rng_index(rmap, o));
-        a.out_sample[o] = m + zz * sqrt(v + a.jitter);
+        const double smp = m + zz * sqrt(v + a.jitter);
+        if constexpr (HEAD) __hip_atomic_store(a.out_sample + o, smp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (a head row reads it on another XCD)
+        else a.out_sample[o] = smp;
       }
     }
   }
@@ -788,10 +827,14 @@ __global__ __launch_bounds__(NT) void conv_fused_kernel(ConvFusedArgs a_in) {
   if (!a.persist) break;
   // the next strip: dealt by arrival (a.dyn: one counter per launch) -- two workgroups share a CU and the one launched first wins every arbitration
   // between them, so a fixed deal leaves the other with a strip and a half to run alone at the end (profiles/r06_fused_persistent_static_trace.txt)
-  if (tid == 0) ticket[0] = a.dyn ? (a.pre_n > 0 ? 0 : (int)gridDim.x) + atomicAdd(a.dyn, 1) : strip_next + (int)gridDim.x;
+  if (tid == 0) ticket[0] = a.dyn ? ((HEAD || a.pre_n > 0) ? 0 : (int)gridDim.x) + atomicAdd(a.dyn, 1) : strip_next + (int)gridDim.x;
+  if constexpr (HEAD) __builtin_amdgcn_s_waitcnt(0);   // the strip's samples are acknowledged before the barrier in front of its flag (as the A1 hand-over's)
   __syncthreads();   // (and the partial sums are read: the next strip's images may land on them)
+  if constexpr (HEAD) {
+    if (mode != 1 && tid == 0) __hip_atomic_store(a.head_flag + sidx, a.head_epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
   strip_next = __builtin_amdgcn_readfirstlane(ticket[0]);
-  if (strip_next >= a.n_items) break;
+  if (strip_next >= (HEAD ? first_limit : a.n_items)) break;
   }
   if (threadIdx.x == 0) {
     if (cu_word >= 0) atomicSub(ap->cu_slots + cu_word, 1);
@@ -809,21 +852,27 @@ using fused_plan::Plan;
 using fused_plan::Query;
 
 // one launch of instance BTP (the base kernel's, or the patch-row form of the RBF sweep) of shape I of the table (fused_plan.h)
-template <int I, int BTP>
+template <int I, int BTP, int HEAD = 0>
 int launch_instance(dcgp_ctx* ctx, const ConvFusedArgs& a, const Plan& p) {
   constexpr int FN = kShapes[I].FN, NS = kShapes[I].NS, MAXF = kShapes[I].MAXF, NT = kShapes[I].NT;
-  static bool attr_done[64] = {};   // per device: a second ctx on another device of this process needs the opt-in too
+  static bool attr_done[64] = {};   // (per instance)   // per device: a second ctx on another device of this process needs the opt-in too
   const int dv = ctx->device >= 0 && ctx->device < 64 ? ctx->device : 0;
   if (!attr_done[dv]) {   // more than 64 KB of dynamic LDS needs the opt-in
-    hipFuncSetAttribute((const void*)conv_fused_kernel<FN, NS, MAXF, NT, BTP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipFuncSetAttribute((const void*)conv_fused_kernel<FN, NS, MAXF, NT, BTP, 0, HEAD>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr_done[dv] = true;
   }
-  hipLaunchKernelGGL((conv_fused_kernel<FN, NS, MAXF, NT, BTP>), dim3((unsigned)p.grid), dim3(NT), (size_t)p.lds, ctx->stream, a);
+  hipLaunchKernelGGL((conv_fused_kernel<FN, NS, MAXF, NT, BTP, 0, HEAD>), dim3((unsigned)p.grid), dim3(NT), (size_t)p.lds, ctx->stream, a);
   LAUNCH_CHECK(ctx);
   return DCGP_OK;
 }
 template <int I>
 int launch_fused(dcgp_ctx* ctx, const ConvFusedArgs& a, const Plan& p) {
+  if (a.head_n > 0) {   // head rows ride: the 64-column strip on 16 waves, RBF (plan_head_ride admits nothing else)
+    if constexpr (I == 0) {
+      if (!p.patch_rows && a.bk.type == 0) return launch_instance<0, 0, 1>(ctx, a, p);
+    }
+    return ctx_fail(ctx, DCGP_ERR_ARG, "conv_fused: head rows on a launch that cannot carry them (shape %d)", I);
+  }
   switch (p.patch_rows ? -1 : a.bk.type) {
     case 0: return launch_instance<I, 0>(ctx, a, p);
     case 1: return launch_instance<I, 1>(ctx, a, p);
@@ -880,6 +929,35 @@ extern "C" int dcgp_debug_fused_plan(dcgp_ctx* ctx, int* out4) {
   return DCGP_OK;
 }
 
+// debugging aid (tests): {head rows the most recent layer-kernel launch of the ctx carried, launches of the ctx that carried any}
+extern "C" int dcgp_debug_head_ride(dcgp_ctx* ctx, long long* out2) {
+  if (!ctx || !out2) return DCGP_ERR_ARG;
+  out2[0] = ctx->last_head_rows; out2[1] = ctx->head_ride_launches;
+  return DCGP_OK;
+}
+
+// debugging aid (tests, no device needed): fused_plan::plan_head_ride for the launch plan_layer_launch gives the flat query, and where head row `row` sits in
+// the deal: out[8] = {ok, why (fused_plan::RideWhy), head rows, item of row 0, item of `row`, first and last strip of `row`, the latest item that writes
+// samples of `row`}
+extern "C" int dcgp_debug_plan_head_ride(const long long* query, int n_query, const long long* ride, int n_ride, long long row, long long* out, int n_out) {
+  if (!query || !ride || !out || n_query != Query::kFields || n_ride != fused_plan::RideQuery::kFields || n_out != 8) return DCGP_ERR_ARG;
+  Query q;
+  std::apply([&](auto&... f) { ((f = (long)*query++), ...); }, Query::fields(q));
+  fused_plan::RideQuery r;
+  r.next_is_head = ride[0]; r.head_form = ride[1]; r.head_HWC = ride[2]; r.head_lds = ride[3]; r.head_nfm = ride[4]; r.in_flight = ride[5]; r.chain_beside = ride[6];
+  r.head_ride = ride[7];
+  const Plan p = fused_plan::plan_layer_launch(q);
+  const fused_plan::Ride rd = fused_plan::plan_head_ride(q, p, r);
+  long lo = 0, hi = -1, last = -1;
+  if (rd.ok && row >= 0 && row < rd.n_rows) {
+    fused_plan::ride_row_strips(row, q.P, kShapes[p.shape].FN * 16, &lo, &hi);
+    for (long st = lo; st <= hi; ++st) last = std::max(last, fused_plan::ride_sample_item(p, st));
+  }
+  const long long flat[8] = {rd.ok, rd.why, rd.n_rows, rd.first_item, rd.ok ? rd.first_item + row : -1, lo, hi, last};
+  memcpy(out, flat, sizeof flat);
+  return DCGP_OK;
+}
+
 // debugging aid (tests, no device needed): the plan of a layer launch from a flat query; field orders in include/dcgp.h
 extern "C" int dcgp_debug_plan_layer_launch(const long long* query, int n_query, long long* plan, int n_plan) {
   if (!query || !plan || n_query != Query::kFields || n_plan != Plan::kFields) return DCGP_ERR_ARG;
@@ -903,6 +981,17 @@ bool conv_fused_ok(const dcgp_ctx* ctx, const ConvFusedArgs& a) {
   return !ctx->opt.no_fused_layer && fused_plan::plan_layer_launch(fused_query(ctx, a)).ok;
 }
 
+int conv_fused_rides_head(const dcgp_ctx* ctx, const ConvFusedArgs& a, bool keeps_state, bool head_form, long head_HWC, long head_lds, long head_nfm, bool in_flight,
+                           bool chain_beside) {
+  if (ctx->opt.no_fused_layer) return 0;
+  Query q = fused_query(ctx, a);
+  q.keeps_state = keeps_state;
+  fused_plan::RideQuery r;
+  r.next_is_head = 1; r.head_form = head_form; r.head_HWC = head_HWC; r.head_lds = head_lds; r.head_nfm = head_nfm; r.in_flight = in_flight;
+  r.chain_beside = chain_beside; r.head_ride = ctx->opt.head_ride;
+  return fused_plan::plan_head_ride(q, fused_plan::plan_layer_launch(q), r).n_rows;
+}
+
 int conv_fused(dcgp_ctx* ctx, const ConvFusedArgs& a_in) {
   if (a_in.Kc <= 0) return DCGP_OK;
   const Plan p = fused_plan::plan_layer_launch(fused_query(ctx, a_in));
@@ -920,6 +1009,26 @@ int conv_fused(dcgp_ctx* ctx, const ConvFusedArgs& a_in) {
     a.pre_epoch = ++ctx->fused_pre_epoch;
   }
   if (p.cu_slots) DCGP_TRY(ws_zeroed(ctx, "fused_cu_slots", 1024 * sizeof(int), &a.cu_slots));
+  ctx->last_head_rows = 0;
+  if (a.head_n > 0) {
+    // Head rows ride (decided by the step's plan through fused_plan::plan_head_ride; asked again here about the launch itself: a launch that cannot carry
+    // them is refused, not run without them).  `head` becomes a launch plan of one workgroup per row that runs the row's Kzx units, one per wave.
+    fused_plan::RideQuery rq;
+    rq.next_is_head = 1; rq.head_form = 1; rq.head_HWC = a.head.HWC; rq.head_lds = (long)head_units_lds(a.head); rq.head_nfm = a.head.nfm;
+    rq.head_ride = ctx->opt.head_ride;
+    const fused_plan::Ride ride = fused_plan::plan_head_ride(fused_query(ctx, a_in), p, rq);
+    if (!ride.ok || ride.n_rows != a.head_n || a.head.X != a.out_sample || a.head.N != a_in.Kc / a_in.P || a.head.n_mod < a.head.N || a.head.n0 != 0 || !a.head.kzx ||
+        a.head.kuf || a.head.kfull || a.head.trace)
+      return ctx_fail(ctx, DCGP_ERR_ARG, "conv_fused: the launch cannot carry the head's rows (reason %d)", ride.why);
+    a.head.kd = nullptr; a.head.want_kd = 0;
+    a.head.nseg = 1; a.head.seg[0] = HuSeg{}; a.head.n_wgs = a.head_n; a.head.upw = 1;
+    bool cleared = false;
+    DCGP_TRY(ws_zeroed(ctx, "fused_head_flag", (size_t)p.n_strips * sizeof(unsigned), &a.head_flag, ctx->fused_head_epoch == 0xffffffffu, &cleared));
+    if (cleared) ctx->fused_head_epoch = 0;
+    a.head_epoch = ++ctx->fused_head_epoch;
+    ctx->last_head_rows = a.head_n;
+    ++ctx->head_ride_launches;
+  }
   // the plan into the argument block
   a.lds_main = p.lds_main; a.lds_img = p.lds_img;
   a.split_first = p.split_first; a.split_q = p.split_q;

@@ -97,6 +97,11 @@ class DealSim {
     else run(kCostHandOver + outputs + kCostEpilogue, ready_[(size_t)slot]);
   }
   double makespan() const { return end_; }
+  std::vector<double> free_times() const {   // when each workgroup is done with its last item
+    std::vector<double> out;
+    for (auto q = free_at_; !q.empty(); q.pop()) out.push_back(q.top());
+    return out;
+  }
 
  private:
   double run(double cost, double not_before) {
@@ -326,6 +331,88 @@ inline Plan plan_layer_launch(const Query& q) {
   if (it != memo.end()) return it->second;
   if (memo.size() > 256) memo.clear();
   return memo[q] = plan_uncached(q);
+}
+
+// ---- Head rows riding the launch (conv_fused.hip: HEAD) --------------------------------------------------------------------------------------------------
+// A persistent launch of 720 strips on 256 workgroups ends with 48 workgroups idle for a strip's time (the partial round that prologues ahead and shared
+// prologues cannot fill: no strip work is left).  Where the next layer is the head, the rows of its patch sweep are dealt by the same counter behind the
+// last strip item: row n waits for the strips that cover its columns [n P, n P + P) and runs the head's Kzx units of that row.  Whether a launch carries
+// them is decided here and nowhere else (model.hip: plan_step); everywhere else the step is the one it was.
+// HOW MANY rows ride: as many as the simulated deal's workgroups have room for before the launch's last strip ends (a row costs kCostHeadRow outputs of the second
+// product).  Every row of the headline step in the launch (320 rows on 256 workgroups) measured 535 -> 574 us for the layer
+// kernel: the 48 spare workgroups absorb ~240 rows, and the 80 left are a round of their own on 208 workgroups that end together -- 38 us for a sweep launch
+// that had shrunk by 43.  The rows beyond the count stay in the head's sweep launch, whose one thin round costs about the same with or without them.
+struct RideQuery {
+  long next_is_head = 0;    // the layer's sample is the head's input, row for row
+  long head_form = 0;       // the head's sweep is the reducing patch-row form of head_units_kernel (<0, 50, 0, *>: RBF ConvKernel head on 5 x 5 x 10 patches, nothing kept)
+  long head_HWC = 0;        // doubles of a head row
+  long head_lds = 0;        // LDS bytes of that sweep's workgroup
+  long head_nfm = 0;        // its Z fragments (Mp / 16): one per wave
+  long in_flight = 0;       // the step is enqueued beside others
+  long chain_beside = 0;    // the parameter-only chain is not on the step's main stream (the head's prepared operands are not ordered in front of the launch)
+  long head_ride = -1;      // the ctx option (0: never; k > 0: k rows, or all of them if there are fewer -- tests, A/B)
+  static constexpr int kFields = 8;
+};
+enum RideWhy { kRides = 0, kRideOff, kRideNotHead, kRideForm, kRideLaunch, kRideState, kRideTrace, kRideInFlight, kRideGeometry, kRideNoRoom };
+struct Ride {
+  int ok = 0, why = kRideOff;
+  int n_rows = 0;       // head items = rows 0 .. n_rows - 1 of the head, dealt behind the plan's n_items (which stay what they were)
+  int first_item = 0;   // item of row 0
+};
+// a head row of 16 Kzx units, in outputs of the second product (15.4 us each): a round of rows measured 38 us (2.5), and a row also waits for its strips' flags.
+// Counts tried at the headline: 144 rows (three per spare workgroup) 1420 steps/s, 192 (four: 2.4 a row) 1410, 224 1405, 240 1389, all 320 1387, none 1385
+constexpr double kCostHeadRow = 3.0;
+// rows that fit in front of the end of the launch's last strip, over the workgroups of the simulated deal (the deal of plan p, item by item)
+inline long ride_room(const Query& q, const Plan& p) {
+  const long S = p.persist, strips = p.n_strips, R = q.R;
+  DealSim d(S, R, p.pre_n);
+  if (p.pre_D > 0) {
+    for (long i = 0; i < strips; ++i) {
+      if (i < p.pre_D) d.give(kLeaving, i);
+      else if (i < p.pre_whole) d.give(kWhole);
+      else d.give(kConsumer, i % p.pre_D, (double)R);
+    }
+  } else if (p.pre_n > 0) {
+    for (long i = 0; i < p.pre_first; ++i) d.give(kWhole);
+    for (long i = 0; i < p.pre_n; ++i) d.give(kPrologueOnly, i);
+    for (long i = 0; i < strips - p.pre_first - p.pre_n; ++i) d.give(kWhole);
+    for (long i = 0; i < p.pre_n; ++i) d.give(kConsumer, i, (double)R);
+  } else {
+    for (long i = 0; i < strips; ++i) d.give(kWhole);
+  }
+  long room = 0;
+  for (double t : d.free_times()) room += (long)((d.makespan() - t + kEps) / kCostHeadRow);
+  return room;
+}
+inline Ride plan_head_ride(const Query& q, const Plan& p, const RideQuery& r) {
+  Ride out;
+  auto no = [&](int why) { out.ok = 0; out.why = why; return out; };
+  if (r.head_ride == 0) return no(kRideOff);
+  if (!r.next_is_head) return no(kRideNotHead);
+  if (!r.head_form) return no(kRideForm);
+  // persistent on the counter deal, one workgroup per CU, the RBF instance of the 64-column strip on 16 waves, no strip shared between workgroups
+  if (!p.ok || p.shape != 0 || p.persist <= 0 || p.deal != kCounter || p.grid != p.persist || p.cu_slots || p.patch_rows || q.base != 0 || q.rep != 1 ||
+      p.pre_sq != 1 || p.split_q != 1)
+    return no(kRideLaunch);
+  if (q.keeps_state) return no(kRideState);
+  if (q.has_trace) return no(kRideTrace);
+  if (r.in_flight || r.chain_beside) return no(kRideInFlight);
+  if (q.P <= 0 || q.Kc <= 0 || q.Kc % q.P || q.P * q.R != r.head_HWC || r.head_nfm < 1 || r.head_nfm > kShapes[0].NT / 64 || r.head_lds > (long)p.lds_main * 8)
+    return no(kRideGeometry);
+  const long rows = q.Kc / q.P;
+  const long n = r.head_ride > 0 ? std::min(r.head_ride, rows) : std::min(ride_room(q, p), rows);
+  if (n <= 0) return no(kRideNoRoom);
+  out.ok = 1; out.why = kRides;
+  out.n_rows = (int)n;
+  out.first_item = p.n_items;
+  return out;
+}
+// the strips whose samples are head row `row`
+inline void ride_row_strips(long row, long P, long BN, long* lo, long* hi) { *lo = row * P / BN; *hi = (row * P + P - 1) / BN; }
+// the item that writes a strip's samples (and sets its flag): the strip's own, or the consumer of a prologue that ran ahead
+inline long ride_sample_item(const Plan& p, long strip) {
+  if (p.pre_n > 0 && p.pre_D == 0 && strip >= p.pre_first && strip < p.pre_first + p.pre_n) return p.n_strips + (strip - p.pre_first) * p.pre_sq;
+  return strip;
 }
 
 }  // namespace fused_plan

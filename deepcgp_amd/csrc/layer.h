@@ -141,6 +141,11 @@ struct ConvFusedArgs {
   // set by the launcher: replicas share a prologue (conv_fused.hip) -- the rows are n_mod images tiled and n_mod * P columns are pre_D whole strips: strip i < pre_D
   // runs whole and leaves A1 in slot i (pre_n = pre_D slots), strips in [pre_D, pre_whole) run whole, strip i >= pre_whole fetches slot i % pre_D
   int pre_D = 0, pre_whole = 0;
+  // head rows riding the launch (fused_plan.h: plan_head_ride; conv_fused.hip: HEAD).  The caller sets head_n = the rows that ride (0 .. head_n - 1) and `head` = the head's sweep
+  // arguments (out_sample is its X, row for row); the launcher makes `head` a plan of one workgroup per row that runs the Kzx units only, and sets the flags.
+  int head_n = 0;
+  unsigned* head_flag = nullptr; unsigned head_epoch = 0;   // [n_strips]: a strip's samples are written once its word is the launch's epoch
+  HeadUnitsArgs head;
 };
 // the reverse pass of the same strip (conv_bwd_fused.hip): dK_uf = inv(L)^T [sum_r (S_r A1) o (2 gv_r) + alpha gm^T - 2 A1 o gvs]
 struct ConvBwdArgs {
@@ -156,6 +161,10 @@ bool conv_bwd_fused_ok(const dcgp_ctx* ctx, const ConvBwdArgs& a);
 int conv_bwd_fused(dcgp_ctx* ctx, const ConvBwdArgs& a);
 bool conv_fused_ok(const dcgp_ctx* ctx, const ConvFusedArgs& a);
 int conv_fused(dcgp_ctx* ctx, const ConvFusedArgs& a);
+// how many rows of the head's sweep described by head_* that launch carries (a: with n_mod and rep set; keeps_state: it leaves K_uf / A1 for a reverse
+// pass); 0: none (fused_plan.h: plan_head_ride -- the one place that decides)
+int conv_fused_rides_head(const dcgp_ctx* ctx, const ConvFusedArgs& a, bool keeps_state, bool head_form, long head_HWC, long head_lds, long head_nfm, bool in_flight,
+                           bool chain_beside);
 
 // KL pieces of one layer -> kl4[0..3] = {mahalanobis, logdet_q, logdet_p, trace} (device)
 int kl_layer(dcgp_ctx* ctx, const GpMats& g, const double* Lp, const double* LpinvT, int white, const char* ws_prefix,

@@ -272,14 +272,41 @@ static inline bool first_layer_one_launch(const dcgp_ctx* ctx, const LayerState&
   return L.is_head ? !(L.Mp >= 96 && !ctx->opt.head_no_overlap) : conv_fused_ok(ctx, conv_fused_shape(L, rows));
 }
 
+// The unit sweep of a ConvKernel head (head_units.hip) on `rows` rows of X, its Kzx into B [Mp][ldb]: geometry and operands, not yet planned.  Filled here and
+// nowhere else: by head_forward for its launch, and by a step whose layer kernel carries the head's rows (model.hip) for that kernel.
+static inline HeadUnitsArgs head_sweep_shape(const dcgp_ctx* ctx, const LayerState& L, const double* X, int rows, int n_mod, double* B, long ldb) {
+  HeadUnitsArgs h;
+  h.X = X; h.n_mod = n_mod; h.N = rows;
+  h.H = L.v.H; h.W = L.v.W; h.C = L.v.C; h.f = L.v.f; h.s = L.v.s; h.Wo = L.v.Wo; h.P = L.v.P; h.L = L.v.L; h.Lq = L.Lz;
+  h.ZS = L.ZS; h.M = L.M; h.Mp = L.Mp;
+  h.csq = sqrt(1.4426950408889634074) / L.ls; h.log2var = log2(L.variance);
+  h.w = L.w; h.kzx = B; h.ldk = ldb; h.kzx_scale = 1.0 / (double)L.v.P;
+  h.want_kd = 1;
+  h.tail_mode = (int)ctx->opt.head_tail;
+  h.occ_force = (int)ctx->opt.sweep_occ;
+  h.share_kb = (int)ctx->opt.share_kb;
+  h.upw_force = (int)ctx->opt.head_upw;
+  return h;
+}
+// whether the head takes that sweep at all (head_forward's first route) ...
+static inline bool head_takes_unit_sweep(const LayerState& L) { return L.is_head && L.kernel_type == 0 && L.base().type == 0 && !L.in_scale; }
+// ... and in the form whose rows the layer kernel can carry: the reducing patch-row form on 5 x 5 x 10 patches (head_units.hip: <0, 50, 0, *>), nothing kept
+// for a reverse pass.  `h`: planned (head_units_plan).
+static inline bool head_sweep_rides_form(const dcgp_ctx* ctx, const LayerState& L, const HeadUnitsArgs& h) {
+  return head_takes_unit_sweep(L) && !h.kuf && !h.kfull && h.f * h.C == 50 && (h.f & 1) && h.L == h.f * h.f * h.C && !ctx->opt.sweep_no_rows &&
+         h.Lq == round_up(h.L + 2, 4) && h.Mp % 16 == 0 && head_units_ok(h);
+}
+
 // ConvLayer.conditional_ND (+ sampling) on `rows` input images taken as X[(n % n_mod)]
+// ride_head, ride_rows: the planned sweep of the head that follows, whose Kzx rows 0 .. ride_rows - 1 this layer's launch carries (fused_plan.h: plan_head_ride;
+// nullptr: none)
 // planned_one_launch: -1, or the route a step's plan placed its streams and events for (0 sweep + GEMM, 1 the one-launch kernel): a different answer here
 // is refused, not run
 static inline int conv_forward(dcgp_ctx* ctx, LayerState& L, const double* X, int rows, int n_mod, int rep, long rep_stride,
                  const double* z, uint64_t seed, uint32_t stream_id, double jitter, double* out_sample, double* out_mean,
                  double* out_var, const std::string& pfx, hipEvent_t factor_done = nullptr,
                                hipEvent_t prep_done = nullptr, int phase = 3, bool keep_state = true, const RngMap* rmap = nullptr,
-                               int planned_one_launch = -1) {
+                               int planned_one_launch = -1, const HeadUnitsArgs* ride_head = nullptr, int ride_rows = 0) {
   // phase bit 0: the K_uf sweep (needs only Z); bit 1: conditional + finalize (needs the factorisation).  The model
   // path enqueues bit 0 of its first layer BEFORE the long side-stream sequence so that the sweep is not held up
   // by the host still enqueueing the factorisation chain.
@@ -311,8 +338,10 @@ static inline int conv_forward(dcgp_ctx* ctx, LayerState& L, const double* X, in
       // G / alpha are recorded behind the factorisation on the chain's stream: one wait covers both
       if (prep_done) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, prep_done, 0));
       else if (factor_done) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, factor_done, 0));
+      if (ride_head) { fa.head = *ride_head; fa.head_n = ride_rows; }
       return conv_fused(ctx, fa);
     }
+    if (ride_head) return ctx_fail(ctx, DCGP_ERR_ARG, "conv layer: the step was planned to carry the head's rows in a launch the layer does not take");
   }
   // The sweep + GEMM route materialises K_uf [Mp][columns] and fetches whole k-tiles of it through 32-bit-offset buffer
   // descriptors: an operand slab must stay under 2 GiB.  A forward-only pass takes a larger batch in chunks of whole images
@@ -383,7 +412,10 @@ static inline int conv_forward(dcgp_ctx* ctx, LayerState& L, const double* X, in
 static inline int head_forward(dcgp_ctx* ctx, LayerState& L, const double* X, int rows, int n_mod, double* kd, double* out_mean,
                  double* out_var, const std::string& pfx, hipEvent_t factor_done = nullptr,
                                hipEvent_t prep_done = nullptr, int sweep_mode = 0, bool* early_done = nullptr,
-                               bool keep_k = false, KlOffer* kl = nullptr) {
+                               bool keep_k = false, KlOffer* kl = nullptr, int kzx_done = 0) {
+  // kzx_done: the layer kernel in front has run the Kzx units of the rows below it (conv_forward: ride_head) -- the sweep launch is the Kzx units of the other
+  // rows and the same Kdiag chunks (the plan is made with every Kzx unit and those rows are then taken out: a unit's value, a chunk's sum do not depend on
+  // where in the launch they run)
   // kl: the KL pieces of an ELBO step, for the one-launch conditional to carry (layer.h: KlOffer)
   // keep_k (a training step): the unit sweep also leaves every patch response in the "<pfx>g_Kfull" workspace [Mp][col_ld(rows P)] and sets
   // L.kfull_ready (the reverse pass would otherwise evaluate them all again)
@@ -413,18 +445,8 @@ static inline int head_forward(dcgp_ctx* ctx, LayerState& L, const double* X, in
   const bool unfused = ctx->opt.head_unfused != 0;   // A/B switch
   if (L.kernel_type == 0 && a.bk.type == 0 && !L.in_scale) {
     // ConvKernel head: Kzx and Kdiag as wave-sized units of one launch (head_units.hip), any M
-    HeadUnitsArgs h;
-    h.X = X; h.n_mod = n_mod; h.N = rows;
-    h.H = L.v.H; h.W = L.v.W; h.C = L.v.C; h.f = L.v.f; h.s = L.v.s; h.Wo = L.v.Wo; h.P = L.v.P; h.L = L.v.L; h.Lq = L.Lz;
-    h.ZS = L.ZS; h.M = L.M; h.Mp = Mp;
-    h.csq = sqrt(1.4426950408889634074) / L.ls; h.log2var = log2(L.variance);
-    h.w = L.w; h.kzx = B; h.ldk = ldb; h.kzx_scale = 1.0 / (double)L.v.P;
+    HeadUnitsArgs h = head_sweep_shape(ctx, L, X, rows, n_mod, B, ldb);
     h.share_cu = factor_done != nullptr;   // first layer of the model with the chain on another stream: the chain runs beside this launch
-    h.want_kd = 1;
-    h.tail_mode = (int)ctx->opt.head_tail;
-    h.occ_force = (int)ctx->opt.sweep_occ;
-    h.share_kb = (int)ctx->opt.share_kb;
-    h.upw_force = (int)ctx->opt.head_upw;
     // (long patches only: a value of a 5 x 5 x 1 patch costs 7 MFMAs to evaluate again -- less than the sweep loses by storing it; head-only MNIST
     // model 0.64 -> 0.67 ms with the values kept, conv + head at L = 250 1.50 -> 1.43)
     if (keep_k && !ctx->opt.grad_no_keep_k && L.v.L >= 64) {
@@ -439,6 +461,19 @@ static inline int head_forward(dcgp_ctx* ctx, LayerState& L, const double* X, in
       if (sweep_mode != 2) L.kfull_ready = h.kfull != nullptr;
       h.kd = (double*)ws_get(ctx, "kdiag_partial", (size_t)rows * h.n_kd * sizeof(double));   // [rows][n_kd] partial sums (head_units_plan)
       if (!h.kd) return DCGP_ERR_ALLOC;
+      if (kzx_done) {
+        if (sweep_mode != 0 || h.kfull || h.nseg < 2 || h.seg[0].kind != 0)
+          return ctx_fail(ctx, DCGP_ERR_ARG, "head: its Kzx rows were run by the layer kernel, but the sweep is not the one that was planned");
+        if (kzx_done > rows) return ctx_fail(ctx, DCGP_ERR_ARG, "head: more Kzx rows done than the head has");
+        const int gone = h.seg[0].wpi * kzx_done;   // their workgroups
+        for (int q = 1; q < h.nseg; ++q) h.seg[q].wg0 -= gone;
+        h.n_wgs -= gone;
+        if (kzx_done < rows) h.seg[0].img0 = kzx_done;
+        else {
+          for (int q = 1; q < h.nseg; ++q) h.seg[q - 1] = h.seg[q];
+          --h.nseg;
+        }
+      }
       if (sweep_mode != 2) DCGP_TRY(head_units(ctx, h));
       if (sweep_mode == 1) {
         if (early_done) *early_done = true;
@@ -461,6 +496,7 @@ static inline int head_forward(dcgp_ctx* ctx, LayerState& L, const double* X, in
       return finalize_layer(ctx, fa);
     }
   }
+  if (kzx_done) return ctx_fail(ctx, DCGP_ERR_ARG, "head: its Kzx rows were run by the layer kernel, but the head does not take the unit sweep");
   if (sweep_mode == 1) return DCGP_OK;   // not the unit-sweep route: nothing is launched ahead
   if (L.kernel_type == 0 && a.bk.type == 0 && head_cond_fused_ok(L.g) && !unfused) {
     // ConvKernel head, M <= 256: Kzx and Kdiag in one launch, then the whole conditional in one launch that adds up the Kdiag

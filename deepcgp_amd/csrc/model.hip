@@ -184,6 +184,9 @@ struct StepPlan {
   bool defer = false;   // with a single factor group its "chol_Lout" scratch stays untouched until the deferred copy runs on the KL stream
   ChainMode chain;
   ForkMark mark = ForkMark::BehindFirstLayer;
+  // The conv layer whose persistent launch also runs the Kzx units of the head's rows 0 .. ride_rows - 1, in the workgroup time its partial last round
+  // leaves (-1: none; fused_plan.h: plan_head_ride decides).  The head's sweep launch is then the other rows' Kzx units and the Kdiag chunks.
+  int ride_layer = -1, ride_rows = 0;
   bool chain_beside() const { return chain_s != main_s; }   // events only where another stream waits for them: each record is a packet in front of the next launch
 };
 // what the caller of a step hands over
@@ -211,6 +214,22 @@ StepPlan plan_step(const dcgp_model* m, int N, int S, int dedup, bool need_kl, b
   p.defer = one_group && need_kl && !m->keep_state;
   p.chain = ChainMode{!p.chain_beside() && !pipelined, p.first_one_launch};
   p.mark = (long)p.rows0 * L0.v.P >= 8192 ? ForkMark::BehindFirstLayer : ForkMark::BehindChain;
+  const int nl = (int)m->layers.size();
+  if (nl >= 2 && m->layers[nl - 1]->is_head && !m->layers[nl - 2]->is_head) {
+    const int li = nl - 2;
+    const LayerState& Lc = *m->layers[li];
+    const LayerState& Lh = *m->layers[nl - 1];
+    const bool expand = dedup && li == 0;
+    const int rows_in = li == 0 ? p.rows0 : S * N, rows_out = S * N;
+    ConvFusedArgs fa = conv_fused_shape(Lc, rows_in);
+    fa.n_mod = li == 0 ? N : rows_in; fa.rep = expand ? S : 1;
+    HeadUnitsArgs h = head_sweep_shape(ctx, Lh, nullptr, rows_out, rows_out, nullptr, col_ld(rows_out));
+    head_units_plan(&h);
+    const bool form = head_sweep_rides_form(ctx, Lh, h) && !(m->keep_state && m->grad_follows);
+    if (li > 0 || p.first_one_launch)
+      p.ride_rows = conv_fused_rides_head(ctx, fa, m->keep_state, form, h.HWC, (long)head_units_lds(h), h.nfm, pipelined, p.chain_beside() && !p.reuse);
+    if (p.ride_rows > 0) p.ride_layer = li;
+  }
   return p;
 }
 
@@ -248,9 +267,19 @@ int run_layer(dcgp_model* m, const StepPlan& p, const StepIn& in, int li, const 
     RngMap rm;
     const bool sharded = m->shard_global > 0;
     if (sharded && (m->shard_global != in.N || m->shard_lo != 0)) { rm.W = width; rm.Nl = in.N; rm.Ng = m->shard_global; rm.lo = m->shard_lo; }
+    HeadUnitsArgs ride;
+    if (li == p.ride_layer && (phase & 2)) {   // the head's Kzx rows ride this launch: the sweep head_forward would plan, on this layer's sample
+      LayerState& Lh = *m->layers[li + 1];
+      const long ldh = col_ld(out_rows);
+      double* B = (double*)ws_get(ctx, model_pfx(m) + std::to_string(li + 1) + "_" + "Kzx", (size_t)Lh.Mp * ldh * sizeof(double));
+      if (!B) return DCGP_ERR_ALLOC;
+      ride = head_sweep_shape(ctx, Lh, o.sample, out_rows, out_rows, B, ldh);
+      head_units_plan(&ride);
+    }
     DCGP_TRY(conv_forward(ctx, L, F, rows, n_mod, expand ? in.S : 1, (long)in.N * width, z, in.seed, (uint32_t)(li + 1 + (sharded ? 0 : 64 * ctx->rank)),
                           m->jitter, o.sample, m->keep_outputs ? o.mean : nullptr, m->keep_outputs ? o.var : nullptr, pfx,
-                          fdone, pdone, phase, m->keep_state, &rm, li == 0 ? (int)p.first_one_launch : -1));
+                          fdone, pdone, phase, m->keep_state, &rm, li == 0 ? (int)p.first_one_launch : -1,
+                          (li == p.ride_layer && (phase & 2)) ? &ride : nullptr, p.ride_rows));
     *out_rows_p = out_rows;
     return DCGP_OK;
   }
@@ -259,7 +288,7 @@ int run_layer(dcgp_model* m, const StepPlan& p, const StepIn& in, int li, const 
   DCGP_TRY(ensure(ctx, &m->d_kd, &m->kd_cap, (size_t)rows));
   DCGP_TRY(head_forward(ctx, L, F, rows, n_mod, m->d_kd, o.mean, o.var, pfx, fdone, pdone,
                         phase == 1 ? 1 : (phase == 2 && *head_swept ? 2 : 0), phase == 1 ? head_swept : nullptr,
-                        m->keep_state && m->grad_follows, kl));
+                        m->keep_state && m->grad_follows, kl, (p.ride_layer == li - 1 && p.ride_layer >= 0) ? p.ride_rows : 0));
   *out_rows_p = rows;
   if (phase != 1 && m->keep_outputs) {
     // the head's sample is not needed by the ELBO; produce it only on request

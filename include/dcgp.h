@@ -599,6 +599,18 @@ int dcgp_debug_fused_plan(dcgp_ctx* ctx, int* out4);
  *   each an IEEE double BIT-CAST into its 64-bit slot (0.0: not simulated): one item per strip, prologues ahead, replicas sharing a prologue}.
  * dcgp_debug_fused_plan's four values are persist, n_items, pre_n and pre_D of the plan of the launch.  DCGP_ERR_ARG unless n_query == 29, n_plan == 24. */
 int dcgp_debug_plan_layer_launch(const long long* query, int n_query, long long* plan, int n_plan);
+/* Head rows riding the layer kernel's persistent launch (csrc/fused_plan.h, plan_head_ride; ctx option head_ride, 0: never).
+ * dcgp_debug_head_ride: out2 = {head rows the ctx's most recent layer-kernel launch carried (0: none), launches of the ctx that carried any}.
+ * dcgp_debug_plan_head_ride (no ctx, no device): the decision for the launch that `query` (as above) is planned as and
+ *   ride[8] = {next_is_head, head_form (the head's sweep is the reducing patch-row form), doubles of a head row, LDS bytes of the sweep's workgroup, its Z
+ *   fragments, in_flight, chain_beside, the ctx option head_ride (-1: as many rows as the simulated deal's workgroups have room for before the last strip ends;
+ *   k > 0: k rows, or all)};
+ *   out[8] = {ok, why (0 rides, 1 option off, 2 the next layer is not the head, 3 another form of the sweep, 4 the launch cannot carry rows, 5 state is kept
+ *   for a reverse pass, 6 trace on, 7 steps in flight / chain beside the main stream, 8 geometry, 9 no workgroup has room for a row), head rows that ride (the first so many),
+ *   item of row 0, item of `row`, first and last
+ *   strip whose samples are `row`, the latest item that writes any of them (-1 where it does not ride or `row` is out of range)}. */
+int dcgp_debug_head_ride(dcgp_ctx* ctx, long long* out2);
+int dcgp_debug_plan_head_ride(const long long* query, int n_query, const long long* ride, int n_ride, long long row, long long* out, int n_out);
 /* The same for the patch sweeps (csrc/head_units.hip; tools/sweep_trace.py): [n_workgroups][waves per workgroup][8] int64 -- wall clock at entry,
  * shader clock at entry / image staged / set-up done / first unit done / last unit done, wall clock at exit, units run.            */
 /* The ceilings bench.py prices kernels against, measured on this device (csrc/peaks.hip): the sustained fp64 MFMA rate (TFLOP/s, 4 waves
