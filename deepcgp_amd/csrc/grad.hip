@@ -1836,13 +1836,6 @@ int dcgp_elbo_grad(dcgp_model* model, const double* X, const int32_t* y, int N, 
   return elbo_grad_run(model, X, y, N, scale, z_per_layer_host, seed, dedup_layer0, out_host, info_host, nullptr);
 }
 
-// One training step in one call: value, gradient and the Adam update (dcgp_model_adam_step's arguments; t == 0: the model's own step
-// count), enqueued back to back with one wait at the end -- what session.run(minimise_op) is to the reference (conv_gp/experiment.py:84-108).
-// A step whose factorisation fails returns DCGP_ERR_NOT_PD and leaves parameters, moments and step count untouched.
-static int train_step_adam_run(dcgp_model* model, const double* X, const int32_t* y, int N, double scale, const double* const* z_per_layer_host,
-                               uint64_t seed, int dedup_layer0, double lr, double beta1, double beta2, double eps, int t, double* out_host,
-                               int* info_host, const double* yf);
-
 int dcgp_elbo_grad_f64y(dcgp_model* model, const double* X, const double* y, int N, double scale, const double* const* z_per_layer_host,
                         uint64_t seed, int dedup_layer0, double* out_host, int* info_host) {
   if (!model || !X || !y || N <= 0 || !out_host) return model ? ctx_fail(model->ctx, DCGP_ERR_ARG, "elbo_grad_f64y: bad args") : DCGP_ERR_ARG;
@@ -1863,9 +1856,15 @@ int dcgp_model_train_step_adam(dcgp_model* model, const double* X, const int32_t
   return train_step_adam_run(model, X, y, N, scale, z_per_layer_host, seed, dedup_layer0, lr, beta1, beta2, eps, t, out_host, info_host, nullptr);
 }
 
-static int train_step_adam_run(dcgp_model* model, const double* X, const int32_t* y, int N, double scale, const double* const* z_per_layer_host,
-                               uint64_t seed, int dedup_layer0, double lr, double beta1, double beta2, double eps, int t, double* out_host,
-                               int* info_host, const double* yf) {
+}  // extern "C"
+
+// One training step in one call: value, gradient and the Adam update (dcgp_model_adam_step's arguments; t == 0: the model's own step
+// count), enqueued back to back with one wait at the end -- what session.run(minimise_op) is to the reference (conv_gp/experiment.py:84-108).
+// A step whose factorisation fails returns DCGP_ERR_NOT_PD and leaves parameters, moments and step count untouched.
+// (also the step of dcgp_model_train_run_adam, train_run.hip)
+int train_step_adam_run(dcgp_model* model, const double* X, const int32_t* y, int N, double scale, const double* const* z_per_layer_host,
+                        uint64_t seed, int dedup_layer0, double lr, double beta1, double beta2, double eps, int t, double* out_host,
+                        int* info_host, const double* yf) {
   if (t < 0 || !(lr > 0) || !(beta1 >= 0 && beta1 < 1) || !(beta2 >= 0 && beta2 < 1) || !(eps > 0))
     return ctx_fail(model->ctx, DCGP_ERR_ARG, "train_step_adam: bad optimiser arguments");
   const int t_use = t == 0 ? model->adam_t + 1 : t;
@@ -1877,6 +1876,8 @@ static int train_step_adam_run(dcgp_model* model, const double* X, const int32_t
   model->adam_t = t_use;
   return DCGP_OK;
 }
+
+extern "C" {
 
 int dcgp_model_get_grad(dcgp_model* model, int layer, const char* which, double* out_host, size_t count) {
   if (!model || !which || !out_host) return DCGP_ERR_ARG;

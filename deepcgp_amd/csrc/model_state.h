@@ -75,8 +75,18 @@ struct dcgp_model {
   double* h_ring_dev = nullptr;        // the same slots as the device addresses them (written by the last kernel of a step)
   hipEvent_t ring_ev[RING] = {};
   uint64_t enq_seq = 0, col_seq = 0;   // tickets handed out / collected
+  // the training set of dcgp_model_train_run_adam (train_run.hip): uploaded once by dcgp_model_set_dataset, rows gathered per step on the device
+  double* ds_X = nullptr;              // [ds_n][ds_len], ds_len = H W C of layer 0
+  void* ds_Y = nullptr;                // int32 [ds_n] (ds_D == 0) or float64 [ds_n][ds_D]
+  long ds_n = 0, ds_len = 0;
+  int ds_D = 0;
+  // ... and the run's own buffers (grow-only): the index table of a run, the batch of the step in flight
+  int32_t* run_idx = nullptr; size_t run_idx_cap = 0;
+  double* run_X = nullptr; size_t run_X_cap = 0;
+  void* run_Y = nullptr; size_t run_Y_cap = 0;   // (bytes)
 
   ~dcgp_model() {
+    hipFree(ds_X); hipFree(ds_Y); hipFree(run_idx); hipFree(run_X); hipFree(run_Y);
     if (h_ring) hipHostFree(h_ring);
     for (auto& e : ring_ev) if (e) hipEventDestroy(e);
     for (auto& gs : groups) for (auto& gr : gs) gr.release();
@@ -108,6 +118,10 @@ int model_backward(dcgp_model* model, const Targets& targets, const double* X, i
 // enqueue == false: 1 if a training step's forward should hand the KL adjoint's products to the side stream, else 0;
 // enqueue == true: do it (wait_fork: behind ctx->ev_fork, recorded where the parameter-only chain ended)
 int grad_kl_early(dcgp_model* model, bool enqueue, bool wait_fork);
+// grad.hip: one training step (dcgp_model_train_step_adam / _f64y behind their argument checks; y or yf, the other nullptr)
+int train_step_adam_run(dcgp_model* model, const double* X, const int32_t* y, int N, double scale, const double* const* z_per_layer_host,
+                        uint64_t seed, int dedup_layer0, double lr, double beta1, double beta2, double eps, int t, double* out_host,
+                        int* info_host, const double* yf);
 
 // model.hip: the data path of an evaluation forward (propagate's: no KL, factor reuse as for propagate) on `S` samples, asynchronous on ctx->stream;
 // with keep_outputs / keep_state / data_grad set it leaves what model_backward_data reads.  *rows_last: rows of the head's mean / var.

@@ -27,9 +27,10 @@ class DcgpError(RuntimeError):
         self.code = code
 
 
-class NotPositiveDefinite(DcgpError):
+class NotPositiveDefinite(DcgpError, np.linalg.LinAlgError):
     """Cholesky hit a non-positive pivot -- the counterpart of the tf.errors.InvalidArgumentError the
-    reference catches at conv_gp/experiment.py:45.  ``column`` is the 1-based failing column."""
+    reference catches at conv_gp/experiment.py:45.  ``column`` is the 1-based failing column.  Also a
+    ``numpy.linalg.LinAlgError``, what ``numpy.linalg.cholesky`` raises for the same matrix."""
 
     def __init__(self, code, msg, column):
         super().__init__(code, msg)
@@ -103,6 +104,8 @@ _SIGS = {
     "dcgp_model_get_grad": [_vp, _i, C.c_char_p, _vp, C.c_size_t],
     "dcgp_model_adam_step": [_vp, _d, _d, _d, _d, _i],
     "dcgp_model_train_step_adam": [_vp, _vp, _vp, _i, _d, C.POINTER(_vp), _u64, _i, _d, _d, _d, _d, _i, C.POINTER(_d), _ip],
+    "dcgp_model_set_dataset": [_vp, _vp, _vp, C.c_long, _i],
+    "dcgp_model_train_run_adam": [_vp, _vp, _i, _i, _d, _vp, _u64, _i, _d, _d, _d, _vp, _ip, _ip],
     "dcgp_model_get_param": [_vp, _i, C.c_char_p, _vp, C.c_size_t],
     "dcgp_model_set_grad_shards": [_vp, _i],
     "dcgp_model_set_shard": [_vp, _i, _i],

@@ -67,6 +67,7 @@ class DGP_Base:
         self._ctx = None
         self._model = None
         self._batch_rng = np.random.RandomState(0)    # Minibatch(seed=0)
+        self._dataset = None          # (rows, attached without arguments?) of the set attach_dataset put on the device
         if not self.layers or not isinstance(self.layers[-1], SVGP_Layer):
             raise ValueError("the last layer must be an SVGP_Layer")
         for l in self.layers[:-1]:
@@ -480,6 +481,92 @@ class DGP_Base:
         ctx._check((L.dcgp_model_train_step_adam_f64y if f64y else L.dcgp_model_train_step_adam)(self._model, dX.ptr, dY.ptr, N, float(scale), arr, int(seed), int(self.dedup_layer0),
                                                 float(lr), float(beta1), float(beta2), float(epsilon), int(t or 0), out, C.byref(info)), info)
         return out[0]
+
+    # ---- a training run on the device -------------------------------------------------------------
+    def _row_length(self):
+        """Values per image, H * W * C of the first layer (the geometry ``_build`` hands the device model)."""
+        l = self.layers[0]
+        if len(self.layers) > 1:
+            return int(l.view.input_size[0] * l.view.input_size[1] * l.feature_maps_in)
+        if hasattr(l.kern, "base_kernel"):
+            v = l.kern.view
+            return int(v.input_size[0] * v.input_size[1] * v.feature_maps)
+        return int(l.kern.input_dim)
+
+    def attach_dataset(self, X=None, Y=None):
+        """Upload a training set once (dcgp_model_set_dataset); ``train_run`` then draws its batches from it on the device.  Defaults to the
+        model's own ``X``, ``Y``.  Replaces an earlier set.  Targets are validated as for an explicit minibatch (``_targets_host``)."""
+        self._build()
+        default = X is None and Y is None
+        X = self.X if X is None else X
+        Y = self.Y if Y is None else Y
+        X = np.ascontiguousarray(np.reshape(X, (np.shape(X)[0], -1)), np.float64)
+        n = X.shape[0]
+        if n < 1:
+            raise ValueError("attach_dataset: the set is empty")
+        if X.shape[1] != self._row_length():
+            raise ValueError("attach_dataset: images of %d values, the model's first layer takes %d" % (X.shape[1], self._row_length()))
+        if self.float_targets:
+            Y = self._targets_host(Y, n)
+        else:
+            Y = np.ascontiguousarray(np.reshape(Y, (-1,)), np.int32)
+            if Y.shape[0] != n:
+                raise ValueError("%d targets for %d images" % (Y.shape[0], n))
+        self._dataset = None
+        self._ctx._check(dev.lib().dcgp_model_set_dataset(self._model, X.ctypes.data, Y.ctypes.data, n, int(self.float_targets)))
+        self._dataset = (n, default)
+
+    def detach_dataset(self):
+        """Release the set ``attach_dataset`` uploaded."""
+        if self._model is not None and self._dataset is not None:
+            self._ctx._check(dev.lib().dcgp_model_set_dataset(self._model, None, None, 0, 0))
+        self._dataset = None
+
+    def train_run(self, idx, lr, seed=0, scale=None, beta1=0.9, beta2=0.999, epsilon=1e-8):
+        """``steps`` training steps in one device call (dcgp_model_train_run_adam) -- ``Loop(self.loop, stop=test_every)`` of
+        conv_gp/experiment.py:38-49.  ``idx`` [steps, batch]: the rows of the attached set each step trains on; ``lr``: a scalar or one rate
+        per step; step i draws its noise from ``seed + i``; ``scale`` defaults to num_data / batch.  Returns the steps' ELBOs; they, the
+        parameters and the optimiser state are those of ``steps`` calls ``train_step(X[idx[i]], Y[idx[i]], lr[i], seed=seed + i)`` bit for
+        bit.  Raises what ``train_step`` raises, with the failing step in the message and in the exception's ``.step`` and the ELBOs of the
+        completed steps in its ``.history``; bad arguments raise ``ValueError`` before anything is launched."""
+        self._build()
+        ctx, L = self._ctx, dev.lib()
+        if self._dataset is None:
+            raise ValueError("train_run: no dataset attached (attach_dataset)")
+        if getattr(ctx, "nranks", 1) > 1:
+            raise NotImplementedError("train_run drives one GPU; shard the minibatch per rank and call train_step yourself")
+        n = self._dataset[0]
+        idx = np.asarray(idx)
+        if idx.ndim != 2 or idx.size == 0 or idx.dtype.kind not in "iu":
+            raise ValueError("train_run: idx must be an integer array [steps, batch], got %s %r" % (idx.dtype, idx.shape))
+        steps, batch = idx.shape
+        if idx.min() < 0 or idx.max() >= n:
+            raise ValueError("train_run: indices must lie in [0, %d), got [%d, %d]" % (n, idx.min(), idx.max()))
+        idx = np.ascontiguousarray(idx, np.int32)
+        lr = np.asarray(lr, np.float64)
+        if lr.ndim == 0:
+            lr = np.full(steps, float(lr))
+        if lr.shape != (steps,):
+            raise ValueError("train_run: %d steps but a learning-rate table of shape %r" % (steps, lr.shape))
+        if not np.all(lr > 0):
+            raise ValueError("train_run: every learning rate must be > 0")
+        lr = np.ascontiguousarray(lr)
+        if scale is None:
+            scale = float(self.num_data) / float(batch)
+        elbo = np.zeros(steps, np.float64)
+        done, info = C.c_int(0), C.c_int(0)
+        ctx._check(L.dcgp_model_set_grad_shards(self._model, 0))
+        rc = L.dcgp_model_train_run_adam(self._model, idx.ctypes.data, steps, batch, float(scale), lr.ctypes.data, int(seed), int(self.dedup_layer0),
+                                         float(beta1), float(beta2), float(epsilon), elbo.ctypes.data, C.byref(done), C.byref(info))
+        if rc != dev.DCGP_OK:
+            try:
+                ctx._check(rc, info)
+            except dev.DcgpError as e:
+                e.args = ("%s (train_run: step %d of %d)" % (e.args[0] if e.args else "", done.value, steps),) + tuple(e.args[1:])
+                e.step = done.value
+                e.history = elbo[:done.value].copy()
+                raise
+        return elbo
 
     def set_grad_exchange(self, mode):
         """Multi-rank ``train_step``: 0 = all-reduce of the gradient blocks, every rank updates everything; 1 = reduce-scatter, Adam on this
@@ -971,3 +1058,4 @@ class DGP_Base:
         if self._model is not None:
             dev.lib().dcgp_model_destroy(self._model)
             self._model = None
+            self._dataset = None      # (the resident training set went with the device model)

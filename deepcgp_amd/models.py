@@ -87,11 +87,51 @@ def natgrad_gamma(global_step, gamma0=0.001, steps_back=0, gamma_step=1e-3, back
     return min((t * gamma_step + gamma0) * back_step ** steps_back, gamma_max)
 
 
+def index_table(rng, n, batch, steps):
+    """[steps, batch] int32: the minibatches of ``steps`` successive steps, one ``rng.choice(n, batch, replace=False)`` per step in step order
+    -- the draws the per-step loop makes."""
+    out = np.empty((int(steps), int(batch)), np.int32)
+    for i in range(int(steps)):
+        out[i] = rng.choice(n, size=batch, replace=False)
+    return out
+
+
+def lr_table(lr, global_step, steps, lr_decay_steps):
+    """``learning_rate`` of steps global_step .. global_step + steps - 1."""
+    return np.array([learning_rate(lr, global_step + i, lr_decay_steps) for i in range(int(steps))], np.float64)
+
+
+def _train_adam(model, steps, lr, lr_decay_steps, global_step, seed, callback, rng, n, bs):
+    """The Adam branch of ``train``: the whole span through ``DGP_Base.train_run`` on the model's own X / Y, attached for the call (a set the
+    model already holds resident, ``attach_dataset()`` without arguments, is used as it is).  With a callback one step per run: it may
+    inspect the model at that step."""
+    if steps < 1:
+        return []
+    idx = index_table(rng, n, bs, steps)
+    lrs = lr_table(lr, global_step, steps, lr_decay_steps)
+    own = model._dataset is not None and model._dataset[1] and model._dataset[0] == n
+    if not own:
+        model.attach_dataset()
+    try:
+        if callback is None:
+            return [float(e) for e in model.train_run(idx, lrs, seed=seed + global_step)]
+        history = []
+        for i in range(steps):
+            elbo = float(model.train_run(idx[i:i + 1], lrs[i:i + 1], seed=seed + global_step + i)[0])
+            history.append(elbo)
+            callback(global_step + i + 1, elbo)
+        return history
+    finally:
+        if not own:
+            model.detach_dataset()
+
+
 def train(model, steps, lr=0.01, lr_decay_steps=50000, global_step=0, seed=0, callback=None, optimizer="Adam", gamma=0.001,
           max_retries=5, dedup_layer0=True):
     """The reference's optimisation loop (conv_gp/experiment.py:84-108 + gpflow.actions.Loop at :44).  Every step draws a
     minibatch and evaluates the ELBO and its gradient on the device (``compute_gradients``), then
-      "Adam":    one device Adam step on every parameter (value, gradient and update in ONE call, ``train_step``);
+      "Adam":    one device Adam step on every parameter; the whole span is ONE call (``train_run``: the training set resident on the
+                 device, the minibatches gathered there), one call per step when a ``callback`` wants to see every step;
       "SGD":     one plain gradient step;
       "NatGrad": a natural-gradient step on every layer's (q_mu, q_sqrt) (``DGP_Base.natgrad_step``, step size from
                  ``natgrad_gamma``), then -- as the reference's loop does, with the variational parameters switched to
@@ -116,15 +156,11 @@ def train(model, steps, lr=0.01, lr_decay_steps=50000, global_step=0, seed=0, ca
     for li in range(nl):
         for which in ("q_mu", "q_sqrt"):
             model.set_trainable(li, which, optimizer != "NatGrad")
-    for i in range(int(steps)):
+    if optimizer == "Adam":          # value, gradient and update of a whole span in one device call (dcgp_model_train_run_adam)
+        history = _train_adam(model, int(steps), lr, lr_decay_steps, global_step, seed, callback, rng, n, bs)
+    for i in range(0 if optimizer == "Adam" else int(steps)):
         idx = rng.choice(n, size=bs, replace=False)
         step = global_step + i
-        if optimizer == "Adam":      # value, gradient and update in one device call (dcgp_model_train_step_adam)
-            elbo = model.train_step(model.X[idx], model.Y[idx], learning_rate(lr, step, lr_decay_steps), seed=seed + step)
-            history.append(elbo)
-            if callback is not None:
-                callback(step + 1, elbo)
-            continue
         elbo, _ = model.compute_gradients(model.X[idx], model.Y[idx], seed=seed + step, fetch=False)
         if optimizer == "NatGrad":
             # a step that leaves the positive-definite cone is retried with gamma scaled by 0.2, at most max_retries

@@ -321,6 +321,25 @@ int dcgp_model_adam_step(dcgp_model* model, double lr, double beta1, double beta
 int dcgp_model_train_step_adam(dcgp_model* model, const double* X, const int32_t* y, int N, double scale,
                                const double* const* z_per_layer_host, uint64_t seed, int dedup_layer0, double lr, double beta1,
                                double beta2, double eps, int t, double* out_host, int* info_host);
+/* The training set of a run, resident on the device: X_host [n][H*W*C] float64, Y_host int32 [n] (y_is_f64 == 0) or float64 [n][D] for the
+ * float-target likelihoods (y_is_f64 != 0; D the head's outputs) -- what the reference hands its model once as Minibatch tensors and then draws
+ * from inside session.run (conv_gp/experiment.py:38-49,84-108).  Uploads once, replaces an earlier set, n == 0 releases it.  The model needs its
+ * head (and its likelihood) first: the row length and the kind of target are the model's. */
+int dcgp_model_set_dataset(dcgp_model* model, const double* X_host, const void* Y_host, long n, int y_is_f64);
+/* `steps` training steps in one call -- gpflow.actions.Loop(self.loop, stop=test_every) over the Adam action of conv_gp/experiment.py:38-49,84-108.
+ * Step i is exactly dcgp_model_train_step_adam (its _f64y twin for float targets) on rows idx_host[i][0 .. batch) of the attached set with
+ * z_per_layer_host = NULL, seed seed0 + i, learning rate lr_host[i] and t = 0: elbo_host[i], every parameter, both moment buffers, the likelihood
+ * parameter and the step count after the run are those of `steps` such calls bit for bit (set_trainable flags and dedup_layer0 apply as there).
+ * The rows are gathered on the device (csrc/train_run.hip); the index table crosses the bus once per run, no image does.
+ * Checked on the host before anything is enqueued (DCGP_ERR_ARG): a set is attached, 0 <= idx < n for every entry, steps >= 1, batch >= 1, every
+ * lr > 0, no enqueued forward step outstanding, the ctx holds one rank.
+ * Failure is the per-step loop's: when step j fails (DCGP_ERR_NOT_PD, *info_host = the column) the run returns that code with *steps_done = j and
+ * elbo_host[0 .. j) filled; parameters, moments and step count are what step j - 1 left (a failed step's update reads the step's status word on the
+ * device and changes nothing, and no later step has been enqueued).
+ * The host waits once per step: the kernels take the base kernels' hyper-parameters by value from host-side state that the step's update writes. */
+int dcgp_model_train_run_adam(dcgp_model* model, const int32_t* idx_host /* [steps][batch] */, int steps, int batch, double scale,
+                              const double* lr_host /* [steps] */, uint64_t seed0, int dedup_layer0, double beta1, double beta2, double eps,
+                              double* elbo_host /* [steps] */, int* steps_done, int* info_host);
 /* Multi-rank training step (one process per GPU, dcgp_comm_init_rank): how a step's gradient is exchanged inside dcgp_model_train_step_adam.
  * 0 (default): ncclAllReduce of every layer's gradient block, every rank then updates every parameter.  1: ncclReduceScatter of the block
  * (each rank receives the sum of its shard only -- dcgp_shard_range), Adam on that shard of the layer's parameter block, ncclAllGather
