@@ -21,6 +21,7 @@ FLAGS = (
     ("--feature-maps", str, "10", "outputs of each conv layer, comma separated ('' with a head-only model)"),
     ("--filter-sizes", str, "5,5", "patch size of each layer incl. the head"),
     ("--strides", str, "2,1", "patch stride of each layer incl. the head"),
+    ("--paddings", str, "", "zero padding (pixels per side) of each layer's input incl. the head, comma separated; '' = no padding anywhere"),
     ("--base-kernel", str, "rbf", "base kernel of the conv layers: rbf | acos | matern32 | matern52"),
     ("--white", None, False, "whitened variational parameters"),
     ("--last-kernel", str, "conv", "head kernel: conv | add | rbf"),
@@ -41,6 +42,25 @@ def default_parser():
         else:
             parser.add_argument(flag, type=kind, default=default, required=flag in REQUIRED, help=doc)
     return parser
+
+
+def parse_paddings(flags, n_layers):
+    """The ``--paddings`` list of a model of ``n_layers`` GP layers (head included): ``n_layers`` ints >= 0, all zero when the flag is
+    absent or ''.  A wrong length, a negative or non-integer entry, or padding on a dense (``--last-kernel rbf``) head raise ValueError."""
+    text = getattr(flags, "paddings", "") or ""
+    if text.strip() == "":
+        return [0] * n_layers
+    try:
+        pads = [int(t) for t in text.split(",")]
+    except ValueError:
+        raise ValueError("--paddings: expected comma-separated integers, got %r" % (text,))
+    if len(pads) != n_layers:
+        raise ValueError("--paddings: %d entries for %d GP layers (one per layer, head included, like --strides)" % (len(pads), n_layers))
+    if any(p < 0 for p in pads):
+        raise ValueError("--paddings: entries must be >= 0, got %r" % (text,))
+    if pads[-1] > 0 and getattr(flags, "last_kernel", "conv") == "rbf":
+        raise ValueError("--paddings: the dense head of --last-kernel rbf takes no padding (last entry %d)" % pads[-1])
+    return pads
 
 
 def train_steps(flags):

@@ -1668,7 +1668,9 @@ static int backward_walk(Bk& bk, const double* X, int N, int S, int dedup_layer0
       bk.kl_early = m->kl_early[li]; bk.prep = m->prep_early[li];
       m->kl_early[li] = false; m->prep_early[li] = 0;
     }
-    const double* Xin = li == 0 ? X : m->outs[li - 1].sample;
+    const int pad = li < 8 ? m->pad[li] : 0;   // a padded layer read the padded copy its forward left (model.hip: pad_input); its dX has that size
+    const double* Xin = pad > 0 ? m->pad_in[li] : (li == 0 ? X : m->outs[li - 1].sample);
+    if (!Xin) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: layer %d has no padded input from the forward pass", who, li);
     int rows_l = m->outs[li].rows;                  // rows entering == rows leaving ...
     // ... except for a de-duplicated first conv layer: propagate() tiles the batch S times, so layer 0 saw S identical
     // copies; the forward evaluated its conditional on the N distinct images and drew S samples from it.  The S
@@ -1688,15 +1690,17 @@ static int backward_walk(Bk& bk, const double* X, int N, int S, int dedup_layer0
     const int n_mod = li == 0 ? N : rows_l;
     const long img = (long)L.v.H * L.v.W * L.v.C;
     double* dXin = li == 0 ? out_dX : nullptr;   // (layer 0 of a training step: no dX)
-    if (li > 0 || (out_dX && rows_l != N)) {
+    if (li > 0 || (out_dX && (rows_l != N || pad > 0))) {
       dXin = (double*)ws_get(ctx, bk.pfx + "g_dXin", (size_t)rows_l * img * sizeof(double));
       NEED(dXin);
     }
     if (L.is_head) DCGP_TRY(head_backward(bk, L, Xin, rows_l, n_mod, gm, gv, dXin));
     else DCGP_TRY(conv_backward(bk, L, Xin, rows_l, n_mod, gm, gv, dXin));
     if (li == 0) {
-      if (out_dX && rows_l != N) {   // the final replica sum
-        if (rows_l % N) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: %d rows at layer 0 for %d images", who, rows_l, N);
+      if (out_dX && rows_l % N) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: %d rows at layer 0 for %d images", who, rows_l, N);
+      if (out_dX && pad > 0) {       // crop to the caller's geometry, the replica sum in the same pass
+        DCGP_TRY(crop_images(ctx, ctx->stream, dXin, rows_l / N, N, L.v.H - 2 * pad, L.v.W - 2 * pad, L.v.C, pad, out_dX));
+      } else if (out_dX && rows_l != N) {   // the final replica sum
         hipLaunchKernelGGL(reduce_replicas1_kernel, dim3(blocks_for(N * img)), dim3(256), 0, ctx->stream, dXin, rows_l / N, N * img, out_dX);
         LAUNCH_CHECK(ctx);
       }
@@ -1708,6 +1712,12 @@ static int backward_walk(Bk& bk, const double* X, int N, int S, int dedup_layer0
     gv = (double*)ws_get(ctx, mp + std::to_string(li - 1) + "_g_gv", (size_t)n * sizeof(double));
     NEED(gm); NEED(gv);
     LayerState& Lb = *m->layers[li - 1];
+    if (pad > 0) {   // the sample's gradient is the interior of the padded input's
+      double* dcrop = (double*)ws_get(ctx, bk.pfx + "g_dXcrop", (size_t)n * sizeof(double));
+      NEED(dcrop);
+      DCGP_TRY(crop_images(ctx, ctx->stream, dXin, 1, o.rows, L.v.H - 2 * pad, L.v.W - 2 * pad, L.v.C, pad, dcrop));
+      dXin = dcrop;
+    }
     if (li - 1 == 0 && dedup_layer0 && !Lb.is_head && o.rows == S * N && S > 1) {   // S gradients per element of the shared conditional: summed here
       const long n0 = (long)N * o.width;
       hipLaunchKernelGGL(sample_backward_dedup_kernel, dim3(blocks_for(n0)), dim3(256), 0, ctx->stream, dXin, o.sample, o.mean, o.var, m->jitter, S, n0,

@@ -215,7 +215,8 @@ StepPlan plan_step(const dcgp_model* m, int N, int S, int dedup, bool need_kl, b
   p.chain = ChainMode{!p.chain_beside() && !pipelined, p.first_one_launch};
   p.mark = (long)p.rows0 * L0.v.P >= 8192 ? ForkMark::BehindFirstLayer : ForkMark::BehindChain;
   const int nl = (int)m->layers.size();
-  if (nl >= 2 && m->layers[nl - 1]->is_head && !m->layers[nl - 2]->is_head) {
+  // (a padded head sweeps the padded copy of the sample: the ride reads the sample itself)
+  if (nl >= 2 && m->layers[nl - 1]->is_head && !m->layers[nl - 2]->is_head && m->pad[nl - 1] == 0) {
     const int li = nl - 2;
     const LayerState& Lc = *m->layers[li];
     const LayerState& Lh = *m->layers[nl - 1];
@@ -245,6 +246,46 @@ struct ChainScope {
     if (!ok) { hipStreamSynchronize(p.kl_s); hipStreamSynchronize(p.chain_s); }
   }
 };
+
+// Zero padding (dcgp_model_set_input_padding): the checks of a model's first forward, before anything is enqueued.  The layers were added with
+// their padded H, W; what is checked is that the padded input of layer l is its predecessor's output plus the border.
+int check_padding(dcgp_model* m) {
+  if (!m->any_pad || m->pad_ok) return DCGP_OK;
+  dcgp_ctx* ctx = m->ctx;
+  const int nl = (int)m->layers.size();
+  for (int li = 0; li < nl && li < 8; ++li) {
+    const int p = m->pad[li];
+    if (p == 0) continue;
+    const LayerState& L = *m->layers[li];
+    if (p < 0) return ctx_fail(ctx, DCGP_ERR_ARG, "padding: layer %d has a negative padding (%d)", li, p);
+    if (L.is_head && L.in_scale)   // (per-dimension lengthscales on the flattened input: --last-kernel rbf)
+      return ctx_fail(ctx, DCGP_ERR_ARG, "padding: layer %d is a dense head, only conv layers and patch heads take padding", li);
+    if (L.v.H - 2 * p < 1 || L.v.W - 2 * p < 1)
+      return ctx_fail(ctx, DCGP_ERR_ARG, "padding: layer %d was added as %d x %d, smaller than its border of %d (add the layer with the padded size)", li,
+                      L.v.H, L.v.W, p);
+    if (li == 0) continue;
+    const LayerState& B = *m->layers[li - 1];
+    if (B.is_head || B.v.Ho + 2 * p != L.v.H || B.v.Wo + 2 * p != L.v.W || B.R != L.v.C)
+      return ctx_fail(ctx, DCGP_ERR_ARG, "padding: layer %d takes %d x %d x %d, layer %d produces %d x %d x %d and the padding is %d", li, L.v.H, L.v.W, L.v.C,
+                      li - 1, B.v.Ho, B.v.Wo, B.R, p);
+  }
+  m->pad_ok = true;
+  return DCGP_OK;
+}
+
+// the padded copy of layer li's input (rows images of the predecessor's geometry) on `stream`: a workspace of the model, layer 0's per bank
+int pad_input(dcgp_model* m, hipStream_t stream, int li, int bank, const double* src, long rows, const double** out) {
+  dcgp_ctx* ctx = m->ctx;
+  const LayerState& L = *m->layers[li];
+  const int p = m->pad[li];
+  const std::string name = "m" + std::to_string(m->id) + "_" + std::to_string(li) + "_Xpad" + (li == 0 ? "_b" + std::to_string(bank) : std::string());
+  double* dst = (double*)ws_get(ctx, name, (size_t)rows * L.v.H * L.v.W * L.v.C * sizeof(double));
+  if (!dst) return DCGP_ERR_ALLOC;
+  DCGP_TRY(pad_images(ctx, stream, src, rows, L.v.H - 2 * p, L.v.W - 2 * p, L.v.C, p, dst));
+  m->pad_in[li] = dst;
+  *out = dst;
+  return DCGP_OK;
+}
 
 // one layer of the data path on ctx->stream.  phase 1: only what needs Z alone (the layer's sweep, where it is a launch of its own), 2: the rest, 3: both.
 // head_swept: whether the head's phase 1 launched anything (written by phase 1, read by phase 2).  kl: the KL pieces offered to the head (layer.h: KlOffer)
@@ -430,6 +471,7 @@ int enqueue_layers(dcgp_model* m, const StepPlan& p, const StepIn& in, bool earl
     const bool last = li == nl - 1;
     int out_rows = 0;
     if (last && join_early && kl_join) HIP_TRY(ctx, hipStreamWaitEvent(p.main_s, m->ev_kl[bank], 0));
+    if (li > 0 && m->pad[li] > 0) DCGP_TRY(pad_input(m, p.main_s, li, bank, F, rows, &F));   // (layer 0's: forward_all)
     DCGP_TRY(run_layer(m, p, in, li, F, rows, n_mod, (li == 0 && early0) ? 2 : 3, &head_swept,
                        (last && in.need_kl && m->kl_in_tail[bank]) ? &offer : nullptr, &out_rows));
     if (li == 0 && m->gkl_state && p.mark == ForkMark::BehindFirstLayer)
@@ -457,9 +499,10 @@ int forward_all(dcgp_model* m, const double* X, int N, int S, const double* cons
   if (need_kl && m->shard_global > 0 && (long)m->shard_lo + N > m->shard_global)
     return ctx_fail(ctx, DCGP_ERR_ARG, "forward: %d images from image %d on overrun the declared global batch of %d (dcgp_model_set_shard)", N,
                     m->shard_lo, m->shard_global);
+  DCGP_TRY(check_padding(m));
   DCGP_TRY(ensure_events(m));
   const StepPlan p = plan_step(m, N, S, dedup, need_kl, pipelined);
-  const StepIn in{X, N, S, zs, seed, dedup, need_kl};
+  StepIn in{X, N, S, zs, seed, dedup, need_kl};
   if (!p.reuse) m->chain_version = 0;   // (stays 0 if this step fails on the way)
   m->bank = p.bank;
   for (auto& l : m->layers) DCGP_TRY(l->use_bank(p.bank));
@@ -471,6 +514,9 @@ int forward_all(dcgp_model* m, const double* X, int N, int S, const double* cons
   // a step on the other main stream than the previous one starts behind it
   if (ctx->ev_last_valid && ctx->last_main != p.main_s) HIP_TRY(ctx, hipStreamWaitEvent(p.main_s, ctx->ev_last, 0));
   ctx->last_main = p.main_s;
+  // a padded first layer: X is padded once, here -- the early sweep, the de-duplicated first layer and the replicas of a tiled batch then read an
+  // ordinary image.  Per bank: two steps may be in flight.
+  if (m->pad[0] > 0) DCGP_TRY(pad_input(m, p.main_s, 0, p.bank, X, N, &in.X));
 
   bool early0 = false, head_swept = false, kl_join = false;
   if (p.reuse) ++m->chain_skips;   // (never pipelined: p.main_s is ctx->stream as the caller left it)
@@ -542,6 +588,25 @@ int dcgp_model_set_shard(dcgp_model* model, int first_image, int global_batch) {
   if (global_batch < 0 || first_image < 0 || (global_batch > 0 && first_image >= global_batch))
     return ctx_fail(model->ctx, DCGP_ERR_ARG, "set_shard: first image %d of a global batch of %d", first_image, global_batch);
   model->shard_lo = first_image; model->shard_global = global_batch;
+  return DCGP_OK;
+}
+
+int dcgp_model_set_input_padding(dcgp_model* model, int layer, int pad) {
+  if (!model) return DCGP_ERR_ARG;
+  dcgp_ctx* ctx = model->ctx;
+  if (layer < 0 || layer >= (int)model->layers.size() || layer >= 8) return ctx_fail(ctx, DCGP_ERR_ARG, "set_input_padding: no layer %d", layer);
+  if (pad < 0) return ctx_fail(ctx, DCGP_ERR_ARG, "set_input_padding: layer %d: the padding must be >= 0, got %d", layer, pad);
+  const ViewGeom& v = model->layers[layer]->v;
+  if (v.H - 2 * pad < 1 || v.W - 2 * pad < 1)
+    return ctx_fail(ctx, DCGP_ERR_ARG, "set_input_padding: layer %d was added as %d x %d, smaller than its border of %d (add the layer with the padded size)",
+                    layer, v.H, v.W, pad);
+  if (model->enq_seq != model->col_seq) return ctx_fail(ctx, DCGP_ERR_ARG, "set_input_padding: enqueued steps are still to be collected");
+  if (layer == 0 && model->ds_X && pad != model->pad[0])
+    return ctx_fail(ctx, DCGP_ERR_ARG, "set_input_padding: a dataset is attached (its image length follows layer 0's padding); detach it first");
+  model->pad[layer] = pad;
+  model->any_pad = false;
+  for (int p : model->pad) model->any_pad = model->any_pad || p != 0;
+  model->pad_ok = false;   // checked against the neighbouring layers at the next forward
   return DCGP_OK;
 }
 
@@ -1016,7 +1081,7 @@ int dcgp_model_patch_evidence(dcgp_model* model, const double* X, int N, int S, 
   int rows = 0;
   DCGP_TRY(forward_data_impl(model, X, N, S, z_per_layer_host, seed, 0, &rows));
   // the head's input: the last hidden layer's sample, or the S copies of X (row n shows image n % N) -- what head_forward swept
-  const double* F = nl > 1 ? model->outs[nl - 2].sample : X;
+  const double* F = model->pad[nl - 1] > 0 ? model->pad_in[nl - 1] : (nl > 1 ? model->outs[nl - 2].sample : X);
   const int n_mod = nl > 1 ? rows : N;
   // beta = inv(L)^T alpha from the chain's own factors: L^-T q_mu when whitened (alpha is q_mu), Kuu^-1 q_mu otherwise
   DCGP_TRY(patch_map(ctx, F, rows, n_mod, H.v, H.Z, H.ZS, H.M, H.variance, H.ls, H.w, nullptr, H.g.LinvT, H.g.alpha, H.g.Rp, H.R, out_c,
@@ -1045,8 +1110,7 @@ int eval_batches(dcgp_model* model, const double* X, int N_total, int batch, int
   dcgp_ctx* ctx = model->ctx;
   const int nl = (int)model->layers.size();
   const int K = model->layers[nl - 1]->R;
-  const LayerState& L0 = *model->layers[0];
-  const long in_len = (long)L0.v.H * L0.v.W * L0.v.C;   // one image of X
+  const long in_len = model->image_len();   // one image of X (unpadded: a padded first layer pads its batch on the device)
   DCGP_TRY(ensure_events(model));
   StreamGuard guard(ctx);
   std::vector<const double*> zb(nl, nullptr);

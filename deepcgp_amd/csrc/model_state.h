@@ -84,6 +84,14 @@ struct dcgp_model {
   int32_t* run_idx = nullptr; size_t run_idx_cap = 0;
   double* run_X = nullptr; size_t run_X_cap = 0;
   void* run_Y = nullptr; size_t run_Y_cap = 0;   // (bytes)
+  // zero padding of a layer's input (dcgp_model_set_input_padding; pad.hip): layer l was added with the PADDED H, W and reads a padded copy of
+  // its predecessor's sample (of X for layer 0).  pad_in[l]: that copy as the most recent forward left it (a workspace; layer 0's per bank) --
+  // the reverse pass reads it, nothing overwrites it before the model's next forward.  pad_ok: the geometry was checked since the last change.
+  int pad[8] = {};
+  bool any_pad = false, pad_ok = false;
+  const double* pad_in[8] = {};
+  // one image of the caller's X: layer 0's geometry without its padding
+  long image_len() const { const auto& v = layers[0]->v; return (long)(v.H - 2 * pad[0]) * (v.W - 2 * pad[0]) * v.C; }
 
   ~dcgp_model() {
     hipFree(ds_X); hipFree(ds_Y); hipFree(run_idx); hipFree(run_X); hipFree(run_Y);
@@ -132,6 +140,10 @@ int fill_status(dcgp_model* model, FactorStatus* st);
 // grad.hip: the same reverse walk's data path only (Bk::data_only: no gradient block is touched), from the head's seeds gm, gv [rows][R] to out_dX
 // [N][H W C] (device)
 int model_backward_data(dcgp_model* model, const double* X, int N, int S, int dedup_layer0, double* gm, double* gv, double* out_dX);
+// pad.hip: dst [rows][H + 2p][W + 2p][C] <- src [rows][H][W][C] with a zero border / its adjoint, dst [rows][H][W][C] <- the interior of
+// src [reps][rows][H + 2p][W + 2p][C] summed over the replicas
+int pad_images(dcgp_ctx* ctx, hipStream_t stream, const double* src, long rows, int H, int W, int C, int p, double* dst);
+int crop_images(dcgp_ctx* ctx, hipStream_t stream, const double* src, int reps, long rows, int H, int W, int C, int p, double* dst);
 // input_grad.hip: dX of a scalar-lengthscale RBF patch layer from E / cs in one launch (the product on the matrix pipe, the fold in LDS);
 // extra [rows P][L] or nullptr is added to the patch gradients before the fold.  _ok: the shape is covered (otherwise the product + col2im pair)
 bool patch_adjoint_fused_ok(const LayerState& L, long rows);

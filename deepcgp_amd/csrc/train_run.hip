@@ -68,8 +68,7 @@ int dcgp_model_set_dataset(dcgp_model* model, const double* X_host, const void* 
   if (!model->has_head || model->layers.empty()) return ctx_fail(ctx, DCGP_ERR_ARG, "set_dataset: the model has no head layer yet");
   if ((y_is_f64 != 0) != float_targets(model))
     return ctx_fail(ctx, DCGP_ERR_ARG, "set_dataset: this model's likelihood takes %s targets", float_targets(model) ? "float64 [n][D]" : "int32 labels");
-  const LayerState& L0 = *model->layers[0];
-  const long len = (long)L0.v.H * L0.v.W * L0.v.C;
+  const long len = model->image_len();   // the caller's images: a padded first layer pads them on the device
   const int D = y_is_f64 ? model->layers.back()->R : 0;
   const size_t xb = (size_t)n * len * sizeof(double), yb = y_is_f64 ? (size_t)n * D * sizeof(double) : (size_t)n * sizeof(int32_t);
   if (hipMalloc((void**)&model->ds_X, xb) != hipSuccess || hipMalloc(&model->ds_Y, yb) != hipSuccess) {

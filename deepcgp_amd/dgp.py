@@ -158,8 +158,9 @@ class DGP_Base:
                 raise ValueError("layer %d: the model path takes mean_function None / Zero() / Conv2dMean with its initial filter; "
                                  "got %r" % (li, l.mean_function))
             keep = [np.ascontiguousarray(a, np.float64) for a in (l.feature.Z, l.Z_prior, l.q_mu, l.q_sqrt)]
+            Hp, Wp = getattr(v, "padded_size", v.input_size[:2])      # the device layer is a VALID layer on the padded image
             ctx._check(L.dcgp_model_add_conv_layer(
-                self._model, v.input_size[0], v.input_size[1], l.feature_maps_in, v.filter_size, v.stride,
+                self._model, Hp, Wp, l.feature_maps_in, v.filter_size, v.stride,
                 l.num_inducing, l.gp_count, int(l.white), int(l.identity_mean), l.base_kernel.variance,
                 getattr(l.base_kernel, "lengthscales", 1.0), *[a.ctypes.data for a in keep]))
             desc = np.ascontiguousarray(l.base_kernel._describe(), np.float64)
@@ -169,7 +170,8 @@ class DGP_Base:
         h_ = self.layers[-1]
         if hasattr(h_.kern, "base_kernel"):      # ConvKernel / AdditivePatchKernel head (--last-kernel conv | add)
             v = h_.kern.view
-            geom = (v.input_size[0], v.input_size[1], v.feature_maps, v.filter_size, v.stride)
+            Hp, Wp = getattr(v, "padded_size", v.input_size[:2])
+            geom = (Hp, Wp, v.feature_maps, v.filter_size, v.stride)
             ktype, base, weights = int(h_.kern.kernel_type), h_.kern.base_kernel, h_.kern.patch_weights
         else:                                    # dense RBF head on the flattened features (--last-kernel rbf): one patch = the input
             geom = (1, 1, h_.kern.input_dim, 1, 1)
@@ -181,6 +183,10 @@ class DGP_Base:
         if getattr(base, "ARD", False):
             ls = np.ascontiguousarray(base.lengthscales, np.float64)
             ctx._check(L.dcgp_model_set_param(self._model, len(self.layers) - 1, b"ard_lengthscales", ls.ctypes.data, ls.size))
+        for li, l in enumerate(self.layers):      # zero padding: the layer's input is its predecessor's output (X for layer 0) plus the border
+            v = l.view if li < len(self.layers) - 1 else getattr(l.kern, "view", None)
+            if getattr(v, "padding", 0):
+                ctx._check(L.dcgp_model_set_input_padding(self._model, li, int(v.padding)))
         eps = np.array([float(getattr(self.likelihood, "epsilon", 1e-3))])
         ctx._check(L.dcgp_model_set_param(self._model, 0, b"likelihood_epsilon", eps.ctypes.data, 1))
         if self.gaussian:
@@ -484,7 +490,7 @@ class DGP_Base:
 
     # ---- a training run on the device -------------------------------------------------------------
     def _row_length(self):
-        """Values per image, H * W * C of the first layer (the geometry ``_build`` hands the device model)."""
+        """Values per image, H * W * C of the first layer's UNPADDED input (a padded first layer adds its border on the device)."""
         l = self.layers[0]
         if len(self.layers) > 1:
             return int(l.view.input_size[0] * l.view.input_size[1] * l.feature_maps_in)

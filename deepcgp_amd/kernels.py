@@ -201,13 +201,17 @@ class AdditivePatchKernel:
             size = size + [self.view.feature_maps]
         return ND_X.reshape([ND_X.shape[0]] + size)
 
+    def _padded_X(self, ND_X):
+        """The images as the sliding window sees them: reshaped and, on a padded view, with the zero border."""
+        return self.view.pad(self._reshape_X(ND_X))
+
     def _geom(self, X):
         N, H, W, Cc = X.shape
         return N, H, W, Cc, self.view.filter_size, self.view.stride
 
     def Kzx(self, ML_Z, ND_X):
         ctx = dev.get_context()
-        X = self._reshape_X(ND_X)
+        X = self._padded_X(ND_X)
         Z = np.ascontiguousarray(ML_Z, np.float64)
         N, H, W, Cc, f, s = self._geom(X)
         M = Z.shape[0]
@@ -232,7 +236,7 @@ class AdditivePatchKernel:
             raise ValueError("Z must be M x %d, got %s" % (self.patch_length, Z.shape))
         if beta.ndim != 2 or beta.shape[0] != Z.shape[0] or beta.shape[1] < 1:
             raise ValueError("beta must be M x R with M = %d and R >= 1, got %s" % (Z.shape[0], beta.shape))
-        X = self._reshape_X(ND_X)
+        X = self._padded_X(ND_X)
         N, H, W, Cc, f, s = self._geom(X)
         M, R = beta.shape
         if N == 0:
@@ -269,10 +273,12 @@ class AdditivePatchKernel:
         bk = self.base_kernel
         if not isinstance(bk, RBF) or bk.ARD:
             raise NotImplementedError("the full K of a patch kernel needs a scalar-lengthscale RBF base kernel")
-        X = np.ascontiguousarray(X, np.float64)
+        p = getattr(self.view, "padding", 0)
+        border = ((0, 0), (0, 0), (p, p), (p, p), (0, 0))      # a padded view: the zero border around every image of both sets
+        X = np.ascontiguousarray(np.pad(X, border) if p else X, np.float64)
         B, N, H, W, Cc = X.shape
         if X2 is not None:
-            X2 = np.ascontiguousarray(X2, np.float64)
+            X2 = np.ascontiguousarray(np.pad(X2, border) if p else X2, np.float64)
             if X2.shape[0] != B or X2.shape[2:] != X.shape[2:]:
                 raise ValueError("X2 of shape %s does not match X of shape %s" % (X2.shape, X.shape))
         N2 = N if X2 is None else X2.shape[1]
@@ -299,7 +305,7 @@ class ConvKernel(AdditivePatchKernel):
 
     def Kdiag(self, ND_X):
         ctx = dev.get_context()
-        X = self._reshape_X(ND_X)
+        X = self._padded_X(ND_X)
         N, H, W, Cc, f, s = self._geom(X)
         if N == 0:
             return np.zeros((0,))

@@ -89,7 +89,7 @@ class MultiOutputConvKernel:
         M = Z.shape[0]
         if isinstance(PNL_patches, tuple):
             X, view = PNL_patches
-            X = np.ascontiguousarray(X, np.float64)
+            X = np.ascontiguousarray(view.pad(X) if hasattr(view, "pad") else X, np.float64)
             N, H, W, Cc = X.shape
             f, s = view.filter_size, view.stride
         else:
@@ -240,9 +240,9 @@ class ConvLayer(Layer):
         mean = mean.reshape(N, self.num_outputs)
         if self.identity_mean:
             f, st = v.filter_size, v.stride
-            Ho, Wo = (v.input_size[0] - f) // st + 1, (v.input_size[1] - f) // st + 1
+            Ho, Wo = v.out_image_height, v.out_image_width
             c0 = f // 2
-            centre = X4[:, c0:c0 + (Ho - 1) * st + 1:st, c0:c0 + (Wo - 1) * st + 1:st, 0]
+            centre = v.pad(X4)[:, c0:c0 + (Ho - 1) * st + 1:st, c0:c0 + (Wo - 1) * st + 1:st, 0]
             mean = mean.copy()
             mean.reshape(N, v.patch_count, self.gp_count)[:, :, 0] += centre.reshape(N, v.patch_count)
         extra = self._generic_mean_value(X4)
@@ -263,14 +263,15 @@ class ConvLayer(Layer):
             return np.zeros((0, D)), np.zeros((0, D)), np.zeros((0, D))
         if not isinstance(self.base_kernel, RBF):
             return self._forward_composed(ND_X, z)
-        dX, dZ = ctx.to_device(ND_X), ctx.to_device(self.feature.Z)
+        Hp, Wp = v.padded_size
+        dX, dZ = ctx.to_device(v.pad(ND_X.reshape(N, H, W, self.feature_maps_in))), ctx.to_device(self.feature.Z)
         dmu, dsq = ctx.to_device(self.q_mu), ctx.to_device(self.q_sqrt)
         dz = ctx.to_device(np.reshape(z, (N, D))) if z is not None else None
         ds = ctx.empty((N, D)) if z is not None else None
         dm, dv = ctx.empty((N, D)), ctx.empty((N, D))
         info = C.c_int(0)
         rc = dev.lib().dcgp_conv_layer_forward(
-            ctx.handle, dX.ptr, N, H, W, self.feature_maps_in, v.filter_size, v.stride, dZ.ptr,
+            ctx.handle, dX.ptr, N, Hp, Wp, self.feature_maps_in, v.filter_size, v.stride, dZ.ptr,
             self.num_inducing, self.gp_count, self.base_kernel.variance, self.base_kernel.lengthscales,
             dmu.ptr, dsq.ptr, int(self.white), int(self.identity_mean), dz.ptr if dz else None, JITTER,
             ds.ptr if ds else None, dm.ptr, dv.ptr, C.byref(info))
@@ -297,9 +298,9 @@ class ConvLayer(Layer):
         var = np.transpose(var, (2, 1, 0)).reshape(N, self.num_outputs)
         if self.identity_mean:
             f, st = v.filter_size, v.stride
-            Ho, Wo = (v.input_size[0] - f) // st + 1, (v.input_size[1] - f) // st + 1
+            Ho, Wo = v.out_image_height, v.out_image_width
             c0 = f // 2
-            centre = X4[:, c0:c0 + (Ho - 1) * st + 1:st, c0:c0 + (Wo - 1) * st + 1:st, 0]
+            centre = v.pad(X4)[:, c0:c0 + (Ho - 1) * st + 1:st, c0:c0 + (Wo - 1) * st + 1:st, 0]
             mean = mean.copy()
             mean.reshape(N, v.patch_count, self.gp_count)[:, :, 0] += centre.reshape(N, v.patch_count)
         extra = self._generic_mean_value(X4)

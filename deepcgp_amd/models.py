@@ -8,6 +8,7 @@ from .layers import ConvLayer, SVGP_Layer
 from .likelihoods import MultiClass, Softmax
 from .mean_functions import Conv2dMean, IdentityConv2dMean  # noqa: F401  (the names conv_gp/models.py:11 imports)
 from .views import FullView
+from .arguments import parse_paddings
 
 
 def parse_ints(int_string):
@@ -25,9 +26,12 @@ BASE_KERNELS = {"rbf": RBF, "acos": ArcCosine, "matern32": Matern32, "matern52":
 
 
 def build_layers_from_spec(spec):
+    """Layers of a neutral model spec.  An entry's optional ``pad`` is the zero padding of its input; its ``H``, ``W`` stay unpadded."""
+    if spec["head"].get("kernel", "conv") == "rbf" and spec["head"].get("pad", 0):
+        raise ValueError("--paddings: the dense head of --last-kernel rbf takes no padding (pad %d)" % spec["head"]["pad"])
     layers = []
     for c in spec["convs"]:
-        view = FullView((c["H"], c["W"]), c["f"], c["C"], c["s"])
+        view = FullView((c["H"], c["W"]), c["f"], c["C"], c["s"], padding=c.get("pad", 0))
         kind = c.get("base", "rbf")
         if kind not in BASE_KERNELS:
             raise ValueError("Not a valid base-kernel value")
@@ -47,7 +51,7 @@ def build_layers_from_spec(spec):
         layer._build_prior_cholesky()
         layers.append(layer)
     h = spec["head"]
-    view = FullView((h["H"], h["W"], h["C"]), h["f"], h["C"], h["s"])
+    view = FullView((h["H"], h["W"], h["C"]), h["f"], h["C"], h["s"], padding=h.get("pad", 0))
     if h.get("kernel", "conv") == "rbf":   # dense RBF-ARD head (--last-kernel rbf)
         layers.append(SVGP_Layer(kern=RBF(h["Z"].shape[1], h["variance"], h["ls_ard"], ARD=True), num_outputs=h["R"],
                                  feature=InducingPoints(h["Z"]), mean_function=None, white=h["white"], q_mu=h["q_mu"],
@@ -327,6 +331,11 @@ class LogLikelihoodLogger(object):
         return total / (batches * self.batch_size)
 
 
+def zero_pad(NHWC_X, p):
+    """[n, H, W, C] -> [n, H + 2p, W + 2p, C] with a zero border (the array itself when p == 0)."""
+    return NHWC_X if not p else np.pad(NHWC_X, ((0, 0), (p, p), (p, p), (0, 0)))
+
+
 def identity_conv(NHWC_X, filter_size, feature_maps_in, feature_maps_out, stride, count=1000):
     """Propagate random images through IdentityConv2dMean to initialise the next layer
     (conv_gp/models.py:29-33, conv_gp/mean_functions.py:6-26)."""
@@ -403,7 +412,8 @@ class ModelBuilder(object):
     # ---- flags -> stages ---------------------------------------------------------------------------
     def stages(self):
         """[(M, filter, stride, feature maps)] per conv layer and (M, filter, stride) of the head.  The comma lists follow
-        conv_gp/arguments.py:27-31: one M / filter size / stride per GP layer (head included), one feature-map count per conv layer."""
+        conv_gp/arguments.py:27-31: one M / filter size / stride per GP layer (head included), one feature-map count per conv layer.
+        ``paddings()`` is the same list for --paddings."""
         fl = self.flags
         M, fmaps = parse_ints(fl.M), parse_ints(fl.feature_maps)
         filt, strd = parse_ints(fl.filter_sizes), parse_ints(fl.strides)
@@ -412,11 +422,16 @@ class ModelBuilder(object):
         convs = [(M[i], filt[i], strd[i], fmaps[i]) for i in range(len(fmaps))]
         return convs, (M[-1], filt[-1], strd[-1])
 
+    def paddings(self):
+        """--paddings: one zero-padding width per GP layer (head included); all zeros without the flag."""
+        return parse_paddings(self.flags, len(parse_ints(self.flags.M)))
+
     # ---- stages -> spec ----------------------------------------------------------------------------
     def spec(self):
         fl = self.flags
         convs, (head_M, head_f, head_s) = self.stages()
         n_layers = len(convs) + 1
+        pads = self.paddings()
         stored = {}
         if getattr(fl, "load_model", None) is not None:
             self.global_step, stored = read_checkpoint(self.model_path, n_layers)
@@ -429,10 +444,11 @@ class ModelBuilder(object):
         images = self.X_train                              # what the next layer is initialised on
         for li, (M, f, s, R) in enumerate(convs):
             have = stored.get(li, {})
-            _, H, W, C = images.shape
+            _, H, W, C = images.shape                          # (H, W stay the unpadded size; "pad" carries the border)
+            images = zero_pad(images, pads[li])                # inducing patches and the next layer's images: from what the window sees
             Z = have["Z"] if "Z" in have else PatchInducingFeatures.from_images(images, M, f).Z
             spec["convs"].append(dict(
-                H=H, W=W, C=C, f=f, s=s, M=M, R=R, Z=Z, Z0=Z, white=white, base=fl.base_kernel,
+                H=H, W=W, C=C, f=f, s=s, M=M, R=R, Z=Z, Z0=Z, white=white, base=fl.base_kernel, pad=pads[li],
                 variance=float(have.get("variance", 5.0)), ls=float(have.get("ls", 5.0)),     # models.py:114-117
                 q_mu=have.get("q_mu"), q_sqrt=have.get("q_sqrt"),
                 q_sqrt_scale=None if "q_sqrt" in have else 1e-5,                               # start with low variance (models.py:136-138)
@@ -440,12 +456,13 @@ class ModelBuilder(object):
             images = identity_conv(images, f, C, R, s)                                          # models.py:29-33,104
         have = stored.get(n_layers - 1, {})
         _, H, W, C = images.shape
+        images = zero_pad(images, pads[-1])
         if "Z" in have and fl.last_kernel != "rbf":
             stored_f = int(round(np.sqrt(have["Z"].shape[1] / C)))
             if stored_f != head_f:        # a head trained with another filter size starts afresh (models.py:152-158)
                 print("filter_size {} != {} for last layer. Resetting parameters.".format(head_f, stored_f))
                 have = {k: v for k, v in have.items() if k not in ("Z", "q_mu", "q_sqrt")}
-        head = dict(H=H, W=W, C=C, f=head_f, s=head_s, M=head_M, R=10, white=white, kernel=fl.last_kernel,
+        head = dict(H=H, W=W, C=C, f=head_f, s=head_s, M=head_M, R=10, white=white, kernel=fl.last_kernel, pad=pads[-1],
                     variance=float(have.get("variance", 5.0)), q_mu=have.get("q_mu"), q_sqrt=have.get("q_sqrt"))
         if fl.last_kernel == "rbf":
             # dense head on the flattened features: one lengthscale per dimension, k-means++ inducing points (models.py:24-27,160-168)

@@ -18,10 +18,16 @@ class View:
 
 
 class FullView(View):
-    """The full view uses all patches of the image (conv_gp/views.py:18-68)."""
+    """The full view uses all patches of the image (conv_gp/views.py:18-68).  ``padding`` p >= 0: the patches of the image with p zero
+    pixels added on all four sides, across all channels; ``input_size`` stays the unpadded size, ``padded_size`` is the geometry the
+    sliding window (and the device layer) sees, and ``out_image_*``, ``patch_count`` and ``as_maps`` follow it."""
 
-    def __init__(self, input_size, filter_size, feature_maps, stride=1):
+    def __init__(self, input_size, filter_size, feature_maps, stride=1, padding=0):
         self.input_size = list(input_size)
+        self.padding = int(padding)
+        if self.padding < 0:
+            raise ValueError("padding must be >= 0, got %d" % self.padding)
+        self.padded_size = [self.input_size[0] + 2 * self.padding, self.input_size[1] + 2 * self.padding]
         self.stride = int(stride)
         self.dilation = 1
         self.filter_size = int(filter_size)
@@ -40,9 +46,16 @@ class FullView(View):
         return self.out_image_height * self.out_image_width
 
     def _out_image_size(self):
-        h = (self.input_size[0] - self.patch_shape[0]) // self.stride + 1
-        w = (self.input_size[1] - self.patch_shape[1]) // self.stride + 1
+        h = (self.padded_size[0] - self.patch_shape[0]) // self.stride + 1
+        w = (self.padded_size[1] - self.patch_shape[1]) // self.stride + 1
         return h, w
+
+    def pad(self, NHWC_X):
+        """[N, H, W, C] -> [N, H + 2p, W + 2p, C] with the zero border (the array itself when p == 0)."""
+        p = self.padding
+        if p == 0:
+            return NHWC_X
+        return np.ascontiguousarray(np.pad(np.asarray(NHWC_X, np.float64), ((0, 0), (p, p), (p, p), (0, 0))))
 
     def _extract(self, NHWC_X, pnl):
         ctx = dev.get_context()
@@ -53,6 +66,8 @@ class FullView(View):
         P, L = self.patch_count, self.patch_length
         if N == 0:
             return np.zeros((P, 0, L) if pnl else (0, P, L))
+        X = self.pad(X)
+        H, W = self.padded_size
         dX = ctx.to_device(X)
         out = ctx.empty((P, N, L) if pnl else (N, P, L))
         ctx._check(dev.lib().dcgp_extract_patches(ctx.handle, dX.ptr, N, H, W, Cc, self.filter_size, self.stride,

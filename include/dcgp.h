@@ -244,6 +244,15 @@ int dcgp_model_set_head(dcgp_model* model, int H, int W, int C, int f, int strid
                         int white, int kernel_type, double variance, double lengthscale,
                         const double* Z_host, const double* w_host,
                         const double* q_mu_host, const double* q_sqrt_host);
+/* Symmetric zero padding of `pad` >= 0 pixels on all four sides of layer `layer`'s input image, across all channels: the output is
+ * ((H + 2 pad - f) / stride + 1) x ((W + 2 pad - f) / stride + 1).  The layer (a conv layer or a patch head) is added with the PADDED
+ * H, W; this call records that its input is its predecessor's output (X for layer 0, which stays [N][H W C] in the unpadded geometry
+ * in every call: forward, gradient, input gradient, evaluation, dataset) with the border added on the device.  The first forward
+ * checks, before anything is launched, that predecessor output + 2 pad is the layer's H, W, that the channels agree, and refuses a
+ * dense head (per-dimension lengthscales); this call itself refuses a layer that does not exist, pad < 0 and a border that leaves
+ * no image inside the layer's H x W.  pad = 0 (the default) is the unpadded layer, on exactly the unpadded code path.
+ * Padding is no parameter: checkpoints do not hold it.                                                                        */
+int dcgp_model_set_input_padding(dcgp_model* model, int layer, int pad);
 /* keep every layer's (sample, mean, var) of the next forward passes for dcgp_model_layer_output   */
 int dcgp_model_set_keep_outputs(dcgp_model* model, int on);
 /* Push a changed parameter: which = "Z", "Z0", "q_mu", "q_sqrt", "w", "variance", "lengthscale", or
