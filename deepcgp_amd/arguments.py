@@ -22,6 +22,8 @@ FLAGS = (
     ("--filter-sizes", str, "5,5", "patch size of each layer incl. the head"),
     ("--strides", str, "2,1", "patch stride of each layer incl. the head"),
     ("--paddings", str, "", "zero padding (pixels per side) of each layer's input incl. the head, comma separated; '' = no padding anywhere"),
+    ("--augment-shift", int, 0, "training images are shifted by up to this many pixels either way along both axes, zero fill ('pad and random-crop'); 0 = off"),
+    ("--augment-flip", None, False, "training images are flipped left-right with probability one half"),
     ("--base-kernel", str, "rbf", "base kernel of the conv layers: rbf | acos | matern32 | matern52"),
     ("--white", None, False, "whitened variational parameters"),
     ("--last-kernel", str, "conv", "head kernel: conv | add | rbf"),
@@ -61,6 +63,16 @@ def parse_paddings(flags, n_layers):
     if pads[-1] > 0 and getattr(flags, "last_kernel", "conv") == "rbf":
         raise ValueError("--paddings: the dense head of --last-kernel rbf takes no padding (last entry %d)" % pads[-1])
     return pads
+
+
+def parse_augmentation(flags):
+    """The ``augment.Augmentation`` of ``--augment-shift`` / ``--augment-flip`` (one that does nothing without them).  A negative shift raises
+    ValueError; its upper bound, min(H, W) of the images, is checked where the geometry is known (``DGP_Base.set_augmentation``)."""
+    from .augment import Augmentation
+    shift = int(getattr(flags, "augment_shift", 0) or 0)
+    if shift < 0:
+        raise ValueError("--augment-shift: must be >= 0, got %d" % shift)
+    return Augmentation(shift, bool(getattr(flags, "augment_flip", False)))
 
 
 def train_steps(flags):

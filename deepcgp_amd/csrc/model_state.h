@@ -84,6 +84,10 @@ struct dcgp_model {
   int32_t* run_idx = nullptr; size_t run_idx_cap = 0;
   double* run_X = nullptr; size_t run_X_cap = 0;
   void* run_Y = nullptr; size_t run_Y_cap = 0;   // (bytes)
+  // augmentation of a run's batches (dcgp_model_set_augmentation; augment.hip): the caller's image geometry, the largest shift and whether to
+  // flip.  Off (the default): the run gathers with gather_batch_kernel, exactly as before.
+  int aug_H = 0, aug_W = 0, aug_C = 0, aug_shift = 0, aug_hflip = 0;
+  bool augmenting() const { return aug_shift > 0 || aug_hflip != 0; }
   // zero padding of a layer's input (dcgp_model_set_input_padding; pad.hip): layer l was added with the PADDED H, W and reads a padded copy of
   // its predecessor's sample (of X for layer 0).  pad_in[l]: that copy as the most recent forward left it (a workspace; layer 0's per bank) --
   // the reverse pass reads it, nothing overwrites it before the model's next forward.  pad_ok: the geometry was checked since the last change.
@@ -144,6 +148,11 @@ int model_backward_data(dcgp_model* model, const double* X, int N, int S, int de
 // src [reps][rows][H + 2p][W + 2p][C] summed over the replicas
 int pad_images(dcgp_ctx* ctx, hipStream_t stream, const double* src, long rows, int H, int W, int C, int p, double* dst);
 int crop_images(dcgp_ctx* ctx, hipStream_t stream, const double* src, int reps, long rows, int H, int W, int C, int p, double* dst);
+// augment.hip: nullptr, or what is wrong with an augmentation's geometry / the augmenting gather of a run's step (rows idx_dev[0 .. batch) of the
+// resident set into run_X on ctx->stream, image b with the draw of (seed, b); targets as gather_batch_kernel copies them)
+const char* augment_geometry_error(int H, int W, int C, int max_shift);
+int gather_augment_batch(dcgp_model* model, const int32_t* idx_dev, int batch, uint64_t seed, const int32_t* y32, const double* yf, int D,
+                         int32_t* yb32, double* ybf);
 // input_grad.hip: dX of a scalar-lengthscale RBF patch layer from E / cs in one launch (the product on the matrix pipe, the fold in LDS);
 // extra [rows P][L] or nullptr is added to the patch gradients before the fold.  _ok: the shape is covered (otherwise the product + col2im pair)
 bool patch_adjoint_fused_ok(const LayerState& L, long rows);

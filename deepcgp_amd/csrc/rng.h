@@ -26,7 +26,10 @@ static __device__ __forceinline__ double philox_normal(uint64_t seed, uint32_t s
   double u2 = ((double)c[2] + 0.5) * (1.0 / 4294967296.0);
   return sqrt(-2.0 * log(u1)) * cospi(2.0 * u2);
 }
-
+// Counter word 3 is a tag: every philox_normal counter carries 0x5eed5eed there, whatever its stream id.  The raw-word form of the same generator,
+// philox4x32_10 (augment_map.h: plain C++, because the host draws with it too), is used with another tag -- the augmentation draws of a training
+// run take word 2 = DCGP_AUG_STREAM and word 3 = DCGP_AUG_TAG under the step's own seed, so no draw of theirs is a counter of the layers' noise.
+// A further user of the raw words takes a tag of its own.
 
 // Where a rank's output element sits in the GLOBAL batch: a rank holds images [lo, lo + Nl) of Ng, its rows are (sample s, local
 // image n) -> s * Nl + n, W outputs each.  The noise of element o is drawn at the counter of the same (sample, image, output) of the

@@ -2,6 +2,8 @@
 // own learning rate, go through one call (dcgp_model_train_run_adam) -- gpflow.actions.Loop(self.loop, stop=test_every) of the reference's
 // Experiment._optimize with the optimiser it set up (conv_gp/experiment.py:38-49,84-108).  A step of the run is dcgp_model_train_step_adam on a
 // batch that a gather kernel writes from the resident set: no image crosses the bus per step, and the results are that call's bit for bit.
+// With an augmentation set (dcgp_model_set_augmentation) the gather is augment.hip's, which also shifts and flips each image by a draw made on the
+// device; without one it is gather_batch_kernel below, as it always was.
 //
 // Stream order.  Every step of the run ends in the wait dcgp_model_train_step_adam ends in, and the host enqueues step i + 1 behind it.  It has to:
 // the kernels of a step take the base kernels' hyper-parameters (variance, lengthscale) by value from the host-side layer state, which the update of
@@ -82,6 +84,23 @@ int dcgp_model_set_dataset(dcgp_model* model, const double* X_host, const void* 
   return DCGP_OK;
 }
 
+int dcgp_model_set_augmentation(dcgp_model* model, int H, int W, int C, int max_shift, int hflip) {
+  if (!model) return DCGP_ERR_ARG;
+  dcgp_ctx* ctx = model->ctx;
+  if (model->enq_seq != model->col_seq) return ctx_fail(ctx, DCGP_ERR_ARG, "set_augmentation: enqueued steps are still to be collected");
+  if (max_shift == 0 && hflip == 0) {   // off: the geometry plays no part
+    model->aug_H = model->aug_W = model->aug_C = model->aug_shift = model->aug_hflip = 0;
+    return DCGP_OK;
+  }
+  if (!model->has_head || model->layers.empty()) return ctx_fail(ctx, DCGP_ERR_ARG, "set_augmentation: the model has no head layer yet");
+  if (const char* why = augment_geometry_error(H, W, C, max_shift))
+    return ctx_fail(ctx, DCGP_ERR_ARG, "set_augmentation: %s (H %d W %d C %d max_shift %d)", why, H, W, C, max_shift);
+  if ((long)H * W * C != model->image_len())
+    return ctx_fail(ctx, DCGP_ERR_ARG, "set_augmentation: %d x %d x %d is not the model's image of %ld values", H, W, C, model->image_len());
+  model->aug_H = H; model->aug_W = W; model->aug_C = C; model->aug_shift = max_shift; model->aug_hflip = hflip != 0;
+  return DCGP_OK;
+}
+
 int dcgp_model_train_run_adam(dcgp_model* model, const int32_t* idx_host, int steps, int batch, double scale, const double* lr_host, uint64_t seed0,
                               int dedup_layer0, double beta1, double beta2, double eps, double* elbo_host, int* steps_done, int* info_host) {
   if (!model) return DCGP_ERR_ARG;
@@ -95,6 +114,9 @@ int dcgp_model_train_run_adam(dcgp_model* model, const int32_t* idx_host, int st
   if (!model->ds_X || model->ds_n <= 0) return ctx_fail(ctx, DCGP_ERR_ARG, "train_run_adam: no dataset attached (dcgp_model_set_dataset)");
   if (model->enq_seq != model->col_seq) return ctx_fail(ctx, DCGP_ERR_ARG, "train_run_adam: enqueued steps are still to be collected");
   if (!(beta1 >= 0 && beta1 < 1) || !(beta2 >= 0 && beta2 < 1) || !(eps > 0)) return ctx_fail(ctx, DCGP_ERR_ARG, "train_run_adam: bad optimiser arguments");
+  if (model->augmenting() && (long)model->aug_H * model->aug_W * model->aug_C != model->ds_len)
+    return ctx_fail(ctx, DCGP_ERR_ARG, "train_run_adam: the augmentation's %d x %d x %d images are not the attached set's rows of %ld", model->aug_H,
+                    model->aug_W, model->aug_C, model->ds_len);
   for (int i = 0; i < steps; ++i)
     if (!(lr_host[i] > 0)) return ctx_fail(ctx, DCGP_ERR_ARG, "train_run_adam: learning rate of step %d is not > 0", i);
   const size_t count = (size_t)steps * batch;
@@ -112,10 +134,15 @@ int dcgp_model_train_run_adam(dcgp_model* model, const int32_t* idx_host, int st
   const double* yf = D ? (const double*)model->ds_Y : nullptr;
   int32_t* yb32 = D ? nullptr : (int32_t*)model->run_Y;
   double* ybf = D ? (double*)model->run_Y : nullptr;
+  const bool augment = model->augmenting();
   for (int i = 0; i < steps; ++i) {
-    hipLaunchKernelGGL(gather_batch_kernel, dim3(batch), dim3(256), 0, ctx->stream, model->ds_X, len, model->run_idx + (size_t)i * batch, batch,
-                       model->ds_n, model->run_X, y32, yf, D, yb32, ybf);
-    LAUNCH_CHECK(ctx);
+    if (augment) {   // the same rows, each shifted and flipped by the draw of (this step's seed, its batch position)
+      DCGP_TRY(gather_augment_batch(model, model->run_idx + (size_t)i * batch, batch, seed0 + (uint64_t)i, y32, yf, D, yb32, ybf));
+    } else {
+      hipLaunchKernelGGL(gather_batch_kernel, dim3(batch), dim3(256), 0, ctx->stream, model->ds_X, len, model->run_idx + (size_t)i * batch, batch,
+                         model->ds_n, model->run_X, y32, yf, D, yb32, ybf);
+      LAUNCH_CHECK(ctx);
+    }
     double out[3] = {0.0, 0.0, 0.0};
     const int rc = train_step_adam_run(model, model->run_X, yb32, batch, scale, nullptr, seed0 + (uint64_t)i, dedup_layer0, lr_host[i], beta1, beta2, eps,
                                        0, out, info_host, ybf);

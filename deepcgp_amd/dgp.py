@@ -68,6 +68,7 @@ class DGP_Base:
         self._model = None
         self._batch_rng = np.random.RandomState(0)    # Minibatch(seed=0)
         self._dataset = None          # (rows, attached without arguments?) of the set attach_dataset put on the device
+        self.augmentation = None      # the Augmentation set_augmentation put on the device model (None: off)
         if not self.layers or not isinstance(self.layers[-1], SVGP_Layer):
             raise ValueError("the last layer must be an SVGP_Layer")
         for l in self.layers[:-1]:
@@ -528,13 +529,74 @@ class DGP_Base:
             self._ctx._check(dev.lib().dcgp_model_set_dataset(self._model, None, None, 0, 0))
         self._dataset = None
 
+    # ---- training-time augmentation ---------------------------------------------------------------
+    def _image_geometry(self):
+        """(H, W, C) of one image of the caller's X, from the first layer's view (unpadded); a dense head-only model has none."""
+        l = self.layers[0]
+        if len(self.layers) > 1:
+            return int(l.view.input_size[0]), int(l.view.input_size[1]), int(l.feature_maps_in)
+        if hasattr(l.kern, "base_kernel"):
+            v = l.kern.view
+            return int(v.input_size[0]), int(v.input_size[1]), int(v.feature_maps)
+        raise ValueError("augmentation needs image geometry: this model is a dense head alone (--last-kernel rbf without conv layers), its "
+                         "inputs are vectors of %d features, not H x W x C images" % int(l.kern.input_dim))
+
+    def _checked_augmentation(self, aug):
+        """(H, W, C, max_shift, hflip) of an Augmentation on this model's images; ValueError when it does not fit them."""
+        H, W, Cc = self._image_geometry()
+        t = int(aug.max_shift)
+        if t < 0:
+            raise ValueError("augmentation: max_shift must be >= 0, got %d" % t)
+        if t >= min(H, W):
+            raise ValueError("augmentation: max_shift %d must be < min(H, W) = %d of the model's %d x %d x %d images (--augment-shift)"
+                             % (t, min(H, W), H, W, Cc))
+        return H, W, Cc, t, int(bool(aug.hflip))
+
+    def set_augmentation(self, aug):
+        """Augment the batches of ``train_run`` on the device (dcgp_model_set_augmentation): ``aug`` an ``augment.Augmentation``; None, or one
+        that does nothing, switches it off.  The geometry is the first layer's view's (unpadded); a dense head-only model raises ValueError.
+        Only ``train_run`` consults it (and ``augment``): evaluation, prediction, ``input_gradient``, the loggers and the per-step calls see
+        their images as they are.  No parameter: checkpoints do not hold it.  Not allowed while enqueued steps are outstanding."""
+        args = self._checked_augmentation(aug) if aug else (0, 0, 0, 0, 0)
+        if not aug and self._model is None:      # nothing built, nothing to switch off
+            self.augmentation = None
+            return
+        self._build()
+        try:
+            self._ctx._check(dev.lib().dcgp_model_set_augmentation(self._model, *args))
+        except dev.DcgpError as e:
+            if e.code != dev.ERR_ARG:
+                raise
+            raise ValueError(str(e)) from None       # (enqueued steps still to be collected: the library's own check)
+        self.augmentation = aug if aug else None
+
+    def augment(self, X, seed):
+        """The model's augmentation on an explicit batch, on the device (dcgp_augment_images): image b with the draw of (seed, b) --
+        ``augment.apply(X, *augment.draw(seed, len(X), max_shift, hflip))`` to the bit.  X [N, H W C] or [N, H, W, C]; returns a new array
+        of X's shape.  Without an augmentation set: a copy of X."""
+        X = np.ascontiguousarray(X, np.float64)
+        if not self.augmentation or X.shape[0] == 0:
+            return X.copy()
+        self._build()
+        H, W, Cc, t, hflip = self._checked_augmentation(self.augmentation)
+        if X.size != X.shape[0] * H * W * Cc:
+            raise ValueError("augment: images of shape %r, the model's are %d x %d x %d" % (X.shape[1:], H, W, Cc))
+        ctx = self._ctx
+        dX, out = ctx.to_device(X), ctx.empty(X.shape)
+        ctx._check(dev.lib().dcgp_augment_images(ctx.handle, dX.ptr, X.shape[0], H, W, Cc, t, hflip, int(seed) & 0xFFFFFFFFFFFFFFFF, out.ptr))
+        return out.numpy()
+
     def train_run(self, idx, lr, seed=0, scale=None, beta1=0.9, beta2=0.999, epsilon=1e-8):
         """``steps`` training steps in one device call (dcgp_model_train_run_adam) -- ``Loop(self.loop, stop=test_every)`` of
         conv_gp/experiment.py:38-49.  ``idx`` [steps, batch]: the rows of the attached set each step trains on; ``lr``: a scalar or one rate
         per step; step i draws its noise from ``seed + i``; ``scale`` defaults to num_data / batch.  Returns the steps' ELBOs; they, the
         parameters and the optimiser state are those of ``steps`` calls ``train_step(X[idx[i]], Y[idx[i]], lr[i], seed=seed + i)`` bit for
         bit.  Raises what ``train_step`` raises, with the failing step in the message and in the exception's ``.step`` and the ELBOs of the
-        completed steps in its ``.history``; bad arguments raise ``ValueError`` before anything is launched."""
+        completed steps in its ``.history``; bad arguments raise ``ValueError`` before anything is launched.
+        With an augmentation set (``set_augmentation``) the gather also shifts and flips each image, with draws made on the device: step i is
+        then ``train_step(augment.apply(X[idx[i]], *augment.draw(seed + i, batch, max_shift, hflip)), Y[idx[i]], lr[i], seed=seed + i)``, bit
+        for bit (X[idx[i]] as [batch, H, W, C]).  Targets are untouched; with ``dedup_layer0`` an image is augmented once per step and its S
+        replicas share the result (the batch is tiled afterwards)."""
         self._build()
         ctx, L = self._ctx, dev.lib()
         if self._dataset is None:

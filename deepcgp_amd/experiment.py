@@ -1,7 +1,8 @@
 """The experiment driver -- the counterpart of conv_gp/experiment.py (``Experiment``) and of the script around it
 (conv_gp/mnist.py): flags -> data -> model -> ``test_every`` optimiser steps per period -> a ``log.csv`` row and a checkpoint per period.
 
-A period of Adam steps is ONE device call (``DGP_Base.train_run``) on a training set that is uploaded once, when the model is set up.
+A period of Adam steps is ONE device call (``DGP_Base.train_run``) on a training set that is uploaded once, when the model is set up;
+``--augment-shift`` / ``--augment-flip`` augment its batches on the device (SGD and NatGrad: the same batches, one device call per step).
 
     python -m deepcgp_amd.experiment --name run --data digits.npz -M 16,16 --feature-maps 2 --filter-sizes 3,3 --strides 1,1
 """
@@ -10,7 +11,7 @@ import os
 import numpy as np
 
 from . import utils
-from .arguments import default_parser, train_steps
+from .arguments import default_parser, parse_augmentation, train_steps
 from .models import ModelBuilder, index_table, learning_rate, lr_table, save_model_parameters, train
 
 
@@ -20,6 +21,7 @@ class Experiment(object):
     def __init__(self, flags):
         self.flags = flags
         self.seed = int(getattr(flags, "seed", 0))
+        self.augmentation = parse_augmentation(flags)     # --augment-shift / --augment-flip: training batches only
         self._load_data()
         self._setup_model()
         self._setup_optimizer()
@@ -54,7 +56,8 @@ class Experiment(object):
             self.model.pull_parameters()
         else:
             self.last_elbos = np.array(train(self.model, k, lr=fl.lr, lr_decay_steps=fl.lr_decay_steps, global_step=self.global_step,
-                                             seed=self.seed + self.global_step, optimizer=fl.optimizer, gamma=fl.gamma))
+                                             seed=self.seed + self.global_step, optimizer=fl.optimizer, gamma=fl.gamma,
+                                             augment=self.augmentation))
         self.global_step += k
         self.model.global_step = self.global_step
 
@@ -80,6 +83,7 @@ class Experiment(object):
         self.model.dedup_layer0 = True     # as models.train: the first layer sees S identical copies of the batch
         if self.flags.optimizer == "Adam":
             self.model.attach_dataset()    # once: every period draws its minibatches from it on the device
+            self.model.set_augmentation(self.augmentation)     # ... and shifts / flips them there (the shift's upper bound is checked here)
 
     def _setup_optimizer(self):
         if self.flags.optimizer not in ["Adam", "NatGrad", "SGD"]:

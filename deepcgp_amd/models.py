@@ -131,7 +131,7 @@ def _train_adam(model, steps, lr, lr_decay_steps, global_step, seed, callback, r
 
 
 def train(model, steps, lr=0.01, lr_decay_steps=50000, global_step=0, seed=0, callback=None, optimizer="Adam", gamma=0.001,
-          max_retries=5, dedup_layer0=True):
+          max_retries=5, dedup_layer0=True, augment=None):
     """The reference's optimisation loop (conv_gp/experiment.py:84-108 + gpflow.actions.Loop at :44).  Every step draws a
     minibatch and evaluates the ELBO and its gradient on the device (``compute_gradients``), then
       "Adam":    one device Adam step on every parameter; the whole span is ONE call (``train_run``: the training set resident on the
@@ -143,6 +143,10 @@ def train(model, steps, lr=0.01, lr_decay_steps=50000, global_step=0, seed=0, ca
     ``dedup_layer0`` (default on): propagate() tiles the minibatch S times, so the first layer sees S identical copies;
     its conditional and reverse pass are evaluated on the distinct images only -- same ELBO, same gradients, about half the
     step time at the headline configuration.
+    ``augment``: an ``augment.Augmentation`` for the span (None: whatever the model has set stays); it is set on the model
+    (``set_augmentation``) and the model's earlier one restored afterwards.  The step of global index g augments batch position b with the draw
+    of (seed + g, b) under every optimiser -- inside ``train_run`` for Adam, through ``model.augment(X[idx], seed + g)`` for the others -- so the
+    same flags give the same batches.
     Returns the list of ELBO values; the Python-side parameter objects are refreshed at the end (``pull_parameters``)."""
     if optimizer not in ("Adam", "NatGrad", "SGD"):
         raise ValueError("Not a supported optimizer. Try Adam or NatGrad.")     # experiment.py:109-110
@@ -156,6 +160,10 @@ def train(model, steps, lr=0.01, lr_decay_steps=50000, global_step=0, seed=0, ca
         # every rank would draw the same minibatch and the all-reduced gradients would count it once per rank
         raise NotImplementedError("train() drives one GPU; shard the minibatch per rank and call compute_gradients / adam_step yourself")
     dedup_before, model.dedup_layer0 = model.dedup_layer0, bool(dedup_layer0)
+    augment_before = getattr(model, "augmentation", None)
+    if augment is not None:
+        model.set_augmentation(augment)
+    augmenting = bool(getattr(model, "augmentation", None))
     nl = len(model.layers)
     for li in range(nl):
         for which in ("q_mu", "q_sqrt"):
@@ -165,7 +173,8 @@ def train(model, steps, lr=0.01, lr_decay_steps=50000, global_step=0, seed=0, ca
     for i in range(0 if optimizer == "Adam" else int(steps)):
         idx = rng.choice(n, size=bs, replace=False)
         step = global_step + i
-        elbo, _ = model.compute_gradients(model.X[idx], model.Y[idx], seed=seed + step, fetch=False)
+        Xb = model.augment(model.X[idx], seed + step) if augmenting else model.X[idx]
+        elbo, _ = model.compute_gradients(Xb, model.Y[idx], seed=seed + step, fetch=False)
         if optimizer == "NatGrad":
             # a step that leaves the positive-definite cone is retried with gamma scaled by 0.2, at most max_retries
             # times over the run -- the InvalidArgumentError / step_back_gamma handling of experiment.py:36-49
@@ -177,7 +186,7 @@ def train(model, steps, lr=0.01, lr_decay_steps=50000, global_step=0, seed=0, ca
                     steps_back += 1
                     if steps_back > max_retries:
                         raise
-            model.compute_gradients(model.X[idx], model.Y[idx], seed=seed + step, fetch=False)
+            model.compute_gradients(Xb, model.Y[idx], seed=seed + step, fetch=False)
         if optimizer == "SGD":
             model.sgd_step(learning_rate(lr, step, lr_decay_steps))
         else:
@@ -186,6 +195,8 @@ def train(model, steps, lr=0.01, lr_decay_steps=50000, global_step=0, seed=0, ca
         if callback is not None:
             callback(step + 1, elbo)
     model.dedup_layer0 = dedup_before
+    if augment is not None:
+        model.set_augmentation(augment_before)
     model.pull_parameters()
     return history
 

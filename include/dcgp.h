@@ -349,6 +349,24 @@ int dcgp_model_set_dataset(dcgp_model* model, const double* X_host, const void* 
 int dcgp_model_train_run_adam(dcgp_model* model, const int32_t* idx_host /* [steps][batch] */, int steps, int batch, double scale,
                               const double* lr_host /* [steps] */, uint64_t seed0, int dedup_layer0, double beta1, double beta2, double eps,
                               double* elbo_host /* [steps] */, int* steps_done, int* info_host);
+/* Training-time augmentation of a run's batches, on the device -- what a user of the reference does on the host between session.run calls
+ * (its Minibatch tensors, conv_gp/experiment.py:38-49, hold the images as they are; the reference has no augmentation of its own), here without
+ * giving up the resident set.  Model state that dcgp_model_train_run_adam consults; nothing else does: evaluation, prediction, input gradients
+ * and the per-step entry points see their X as it is.  H, W, C: the caller's image geometry, H * W * C == the model's row length (the unpadded
+ * geometry of dcgp_model_set_dataset; a padded first layer still pads afterwards).  Image I of batch position b of step i becomes
+ *     F[y][x][c] = I[y][flip ? W - 1 - x : x][c],   out[y][x][c] = F[y - dy][x - dx][c] inside the image, 0.0 outside
+ * with (dy, dx, flip) drawn on the device from Philox4x32-10 under the step's seed seed0 + i at counter b (csrc/augment_map.h: the words, the
+ * tag that keeps them apart from the layers' noise, dy = word0 % (2 max_shift + 1) - max_shift, dx likewise from word1, flip = hflip ? word2 & 1
+ * : 0; modulo bias about (2 max_shift + 1) / 2^32).  Targets are untouched.  With dedup_layer0 an image is augmented once per step: the batch is
+ * tiled afterwards.  Step i of an augmenting run is dcgp_model_train_step_adam on dcgp_augment_images(rows idx[i], seed0 + i), bit for bit.
+ * max_shift == 0 && hflip == 0 switches augmentation off (H, W, C are then ignored): the run gathers on exactly the code path it had.
+ * DCGP_ERR_ARG, with a message: H * W * C is not the model's row length, max_shift < 0, max_shift >= min(H, W), the model has no head yet,
+ * enqueued steps are still to be collected.  No parameter: checkpoints do not hold it. */
+int dcgp_model_set_augmentation(dcgp_model* model, int H, int W, int C, int max_shift, int hflip);
+/* The same transform on a caller's batch: X [N][H][W][C] -> out [N][H][W][C] (device pointers; out may not alias X), image b with the draw of
+ * (seed, b) -- the host-side augmentation loop a user of the reference writes around its feed (conv_gp/experiment.py:84-108), as one launch.
+ * Every value of out is written.  Asynchronous on the ctx stream.  DCGP_ERR_ARG as above for the geometry and max_shift. */
+int dcgp_augment_images(dcgp_ctx* ctx, const double* X, int N, int H, int W, int C, int max_shift, int hflip, uint64_t seed, double* out);
 /* Multi-rank training step (one process per GPU, dcgp_comm_init_rank): how a step's gradient is exchanged inside dcgp_model_train_step_adam.
  * 0 (default): ncclAllReduce of every layer's gradient block, every rank then updates every parameter.  1: ncclReduceScatter of the block
  * (each rank receives the sum of its shard only -- dcgp_shard_range), Adam on that shard of the layer's parameter block, ncclAllGather
