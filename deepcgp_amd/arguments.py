@@ -24,6 +24,9 @@ FLAGS = (
     ("--paddings", str, "", "zero padding (pixels per side) of each layer's input incl. the head, comma separated; '' = no padding anywhere"),
     ("--augment-shift", int, 0, "training images are shifted by up to this many pixels either way along both axes, zero fill ('pad and random-crop'); 0 = off"),
     ("--augment-flip", None, False, "training images are flipped left-right with probability one half"),
+    ("--test-shift", int, 0, "test-time augmentation: the test images are also evaluated shifted by this many pixels (zero fill), the predictive distribution averaged over the views; 0 = off"),
+    ("--test-flip", None, False, "test-time augmentation: every view also mirrored left-right"),
+    ("--test-views", str, "cross", "which shifts --test-shift N takes: cross (0 and +-N along each axis, 5 views) | grid (all (2N+1)^2 shifts)"),
     ("--base-kernel", str, "rbf", "base kernel of the conv layers: rbf | acos | matern32 | matern52"),
     ("--white", None, False, "whitened variational parameters"),
     ("--last-kernel", str, "conv", "head kernel: conv | add | rbf"),
@@ -73,6 +76,23 @@ def parse_augmentation(flags):
     if shift < 0:
         raise ValueError("--augment-shift: must be >= 0, got %d" % shift)
     return Augmentation(shift, bool(getattr(flags, "augment_flip", False)))
+
+
+def parse_test_views(flags):
+    """The views [V, 3] of ``--test-shift`` / ``--test-flip`` / ``--test-views`` (``augment.views``), or None with the flags at their defaults:
+    the test set is then evaluated as it is.  A negative shift or an unknown pattern raise ValueError; the shift's upper bound, min(H, W) of the
+    images, is checked where the geometry is known (``DGP_Base.evaluate``)."""
+    from .augment import VIEW_PATTERNS, views
+    shift = int(getattr(flags, "test_shift", 0) or 0)
+    flip = bool(getattr(flags, "test_flip", False))
+    pattern = getattr(flags, "test_views", "cross") or "cross"
+    if shift < 0:
+        raise ValueError("--test-shift: must be >= 0, got %d" % shift)
+    if pattern not in VIEW_PATTERNS:
+        raise ValueError("--test-views: expected %s, got %r" % (" | ".join(VIEW_PATTERNS), pattern))
+    if shift == 0 and not flip:
+        return None
+    return views(shift, flip, pattern)
 
 
 def train_steps(flags):

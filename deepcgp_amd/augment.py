@@ -1,4 +1,4 @@
-"""Training-time augmentation, the host mirror in NumPy of csrc/augment_map.h: a random shift by (dy, dx) in [-t, t]^2 with zero fill ("pad by
+"""Augmentation, the host mirror in NumPy of csrc/augment_map.h: a random shift by (dy, dx) in [-t, t]^2 with zero fill ("pad by
 t and random-crop") and a random horizontal flip per image.
 
     F[y][x][c]   = I[y][W - 1 - x if flip else x][c]
@@ -6,7 +6,10 @@ t and random-crop") and a random horizontal flip per image.
 
 The device draws (dy, dx, flip) itself (dcgp_model_set_augmentation, dcgp_augment_images): Philox4x32-10 under the step's seed at counter
 (position, stream word, tag word); ``draw`` is the same arithmetic, so ``apply(X, *draw(seed, len(X), t, hflip))`` is what the device writes,
-to the bit -- the transform only moves values.  Nothing here touches the device."""
+to the bit -- the transform only moves values.
+
+Test-time augmentation uses the same transform with a fixed table in place of the draw: ``views`` lists (dy, dx, flip) triples, ``apply_views``
+is the mirror of the device's view gather (dcgp_view_images, and inside ``DGP_Base.evaluate(views=...)``).  Nothing here touches the device."""
 import numpy as np
 
 AUG_STREAM, AUG_TAG = 0x0a095eed, 0xa0951f7b        # counter words 2 and 3 (csrc/augment_map.h); the layers' noise has 0x5eed5eed in word 3
@@ -58,6 +61,65 @@ def apply(X_nhwc, dy, dx, flip):
             continue
         out[b, max(y, 0):H + min(y, 0), max(x, 0):W + min(x, 0)] = F[max(-y, 0):H + min(-y, 0), max(-x, 0):W + min(-x, 0)]
     return out
+
+
+VIEW_PATTERNS = ("cross", "grid")
+
+
+def views(max_shift=0, hflip=False, pattern="cross"):
+    """The views of test-time augmentation, an int32 array [V, 3] of (dy, dx, flip): the identity first, no duplicates.  ``pattern`` "cross":
+    (0, 0), (+-t, 0), (0, +-t) with t = ``max_shift`` -- 5 views; "grid": all (2t + 1)^2 shifts of [-t, t]^2.  ``hflip`` doubles the list: the
+    unflipped views first, then the same shifts of the mirrored image.  t = 0 without ``hflip`` is [(0, 0, 0)], which evaluates as no views do."""
+    t = int(max_shift)
+    if t < 0:
+        raise ValueError("views: max_shift must be >= 0, got %d" % t)
+    if pattern not in VIEW_PATTERNS:
+        raise ValueError("views: pattern must be one of %s, got %r" % (" | ".join(VIEW_PATTERNS), pattern))
+    if pattern == "cross":
+        shifts = [(0, 0), (-t, 0), (t, 0), (0, -t), (0, t)]
+    else:
+        shifts = [(0, 0)] + [(dy, dx) for dy in range(-t, t + 1) for dx in range(-t, t + 1)]
+    seen, out = set(), []
+    for s in shifts:
+        if s not in seen:
+            seen.add(s)
+            out.append(s)
+    rows = [(dy, dx, f) for f in ((0, 1) if hflip else (0,)) for dy, dx in out]
+    return np.array(rows, np.int32).reshape(-1, 3)
+
+
+def check_views(views, H, W, per_axis=False):
+    """``views`` as an int32 array [V, 3], checked against H x W images: V >= 1, integer entries, |dy| and |dx| < min(H, W), flip in {0, 1}.
+    ValueError otherwise -- the checks of dcgp_model_set_eval_views, made before anything reaches the device.  ``per_axis``: the bound of the
+    gather alone (dcgp_view_images, ``apply_views``), |dy| < H and |dx| < W -- a view may keep a single row or column."""
+    a = np.asarray(views)
+    if a.ndim != 2 or a.shape[1] != 3:
+        raise ValueError("views: expected an array [V, 3] of (dy, dx, flip), got shape %r" % (a.shape,))
+    if a.shape[0] == 0:
+        raise ValueError("views: the list is empty (pass views=None for none)")
+    if a.dtype.kind not in "iu":
+        if a.dtype.kind != "f" or not np.all(a == np.round(a)):
+            raise ValueError("views: entries must be integers")
+    a = a.astype(np.int64)
+    m = min(int(H), int(W))
+    if per_axis:
+        if np.any(np.abs(a[:, 0]) >= int(H)) or np.any(np.abs(a[:, 1]) >= int(W)):
+            raise ValueError("views: |dy| must be < H and |dx| < W of the %d x %d images: a larger shift leaves no pixel" % (H, W))
+    elif np.any(np.abs(a[:, :2]) >= m):
+        raise ValueError("views: |dy| and |dx| must be < min(H, W) = %d of the %d x %d images" % (m, H, W))
+    if np.any((a[:, 2] != 0) & (a[:, 2] != 1)):
+        raise ValueError("views: flip must be 0 or 1")
+    return np.ascontiguousarray(a, np.int32)
+
+
+def apply_views(X_nhwc, views):
+    """The views of a batch [N, H, W, C]: [V * N, H, W, C], view-major -- view v of image i at row v * N + i, ``apply`` per view.  What
+    dcgp_view_images writes, to the bit.  A shift may go up to H - 1 rows and W - 1 columns (an evaluation's views: below min(H, W))."""
+    X = np.asarray(X_nhwc)
+    if X.ndim != 4:
+        raise ValueError("apply_views: images must be [N, H, W, C], got %r" % (X.shape,))
+    v = check_views(views, X.shape[1], X.shape[2], per_axis=True)
+    return np.concatenate([apply(X, int(dy), int(dx), int(f)) for dy, dx, f in v], axis=0)
 
 
 class Augmentation(object):

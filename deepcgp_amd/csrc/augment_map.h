@@ -68,3 +68,35 @@ DCGP_AUG_HD inline long augment_source_index(long i, int H, int W, int C, int dy
   const int s = augment_source_in_row(j, W, C, dx, flip);
   return s < 0 ? -1 : (long)sy * WC + s;
 }
+
+// ---- Deterministic views (test-time augmentation): a table views [V][3] of (dy, dx, flip) in place of the draw, the same map ----
+// Destination row r of a view-major batch [V][n] images: view r / n of source image r % n (n >= 1, 0 <= r < V n).
+struct ViewRow {
+  int v, i;
+};
+DCGP_AUG_HD inline ViewRow view_row(long r, int n) {
+  ViewRow q;
+  q.v = (int)(r / n);
+  q.i = (int)(r - (long)q.v * n);
+  return q;
+}
+
+DCGP_AUG_HD inline AugmentDraw view_draw(const int32_t* views, int v) {
+  AugmentDraw d;
+  d.dy = views[3 * v]; d.dx = views[3 * v + 1]; d.flip = views[3 * v + 2];
+  return d;
+}
+
+// nullptr, or what is wrong with a table of V views of H x W images (the geometry itself: augment_geometry_error).  per_axis (the gather on a
+// caller's batch): |dy| < H and |dx| < W, a view keeps at least one row and one column of its image.  Otherwise (a model's evaluation): a shift
+// of min(H, W) or more along either axis is refused whatever the axis -- the bound of the training-time shift.
+inline const char* view_table_error(const int32_t* views, int V, int H, int W, bool per_axis) {
+  const int m = H < W ? H : W, my = per_axis ? H : m, mx = per_axis ? W : m;
+  for (int v = 0; v < V; ++v) {
+    const int32_t dy = views[3 * v], dx = views[3 * v + 1], f = views[3 * v + 2];
+    if (dy <= -my || dy >= my || dx <= -mx || dx >= mx)
+      return per_axis ? "a view's |dy| must be < H and its |dx| < W: a larger shift leaves no pixel of the image" : "a view's |dy| and |dx| must be < min(H, W)";
+    if (f != 0 && f != 1) return "a view's flip must be 0 or 1";
+  }
+  return nullptr;
+}

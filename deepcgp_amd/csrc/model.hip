@@ -1102,7 +1102,10 @@ namespace {
 //   (layer_impl.h: ev_aux).  The chain of a batch (factor_reuse 0, or the first batch) writes the parameter-only state of its bank
 //   on its own stream: done_ev[bank] -- recorded on the main stream behind the tail of the last batch on that bank -- orders it.
 //   Workspaces: batch 0 is the largest, every later request is served by what it grew.
-// tail(lo, n, o): the tail launch of the batch of n images from image lo on, on the head's rows o; sum(st): the launch behind the last batch, which
+// With views set (dcgp_model_set_eval_views; not the single identity view) a batch of n images becomes its V n view images, view-major in a per-model
+// workspace (augment.hip: view v of image i at row v n + i), forward_all runs on those, and its head rows [S][V n][K] -- row s V n + v n + i =
+// (s V + v) n + i -- are S V samples of n images to the tail: the predictive distribution of an image is the mixture over samples and views.
+// tail(lo, n, SV, o): the tail launch of the batch of n images from image lo on, on the head's rows o = SV samples of them; sum(st): the launch behind the last batch, which
 // leaves `nres` words in res -- [2] the first non-positive pivot of st, [3] the labels outside [0, K) -- read back into h.
 template <class Tail, class Sum>
 int eval_batches(dcgp_model* model, const double* X, int N_total, int batch, int S, const double* const* zs, uint64_t seed, const char* who,
@@ -1111,6 +1114,17 @@ int eval_batches(dcgp_model* model, const double* X, int N_total, int batch, int
   const int nl = (int)model->layers.size();
   const int K = model->layers[nl - 1]->R;
   const long in_len = model->image_len();   // one image of X (unpadded: a padded first layer pads its batch on the device)
+  const bool views = model->eval_views_active();
+  const int V = views ? model->eval_V : 1;
+  double* vw = nullptr;
+  if (views) {
+    if ((long)model->ev_H * model->ev_W * model->ev_C != in_len)
+      return ctx_fail(ctx, DCGP_ERR_ARG, "%s: the views' %d x %d x %d images are not the model's of %ld values", who, model->ev_H, model->ev_W, model->ev_C, in_len);
+    const long nmax = N_total < batch ? N_total : batch;
+    if ((long)S * V * nmax > 0x7fffffffL) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: S * V * batch = %d * %d * %ld head rows exceed 2^31 - 1", who, S, V, nmax);
+    vw = (double*)ws_get(ctx, "m" + std::to_string(model->id) + "_eval_views", (size_t)V * nmax * in_len * sizeof(double));
+    if (!vw) return DCGP_ERR_ALLOC;
+  }
   DCGP_TRY(ensure_events(model));
   StreamGuard guard(ctx);
   std::vector<const double*> zb(nl, nullptr);
@@ -1118,17 +1132,24 @@ int eval_batches(dcgp_model* model, const double* X, int N_total, int batch, int
   for (int b = 0; b < nb; ++b) {
     const long lo = (long)b * batch;
     const int n = (int)(N_total - lo < batch ? N_total - lo : batch);
-    // noise: per layer the batches' [S][n_b][D_l] tables back to back, batch b's from S * lo * D_l on
+    // noise: per layer the batches' [S][V n_b][D_l] tables back to back, batch b's from S * V * lo * D_l on (V = 1 without views)
     for (int l = 0; l < nl && zs; ++l) {
       const LayerState& L = *model->layers[l];
       const long D = L.is_head ? L.R : (long)L.v.P * L.R;
-      zb[l] = zs[l] ? zs[l] + (long)S * lo * D : nullptr;
+      zb[l] = zs[l] ? zs[l] + (long)S * V * lo * D : nullptr;
+    }
+    // the batch forward_all sees: the caller's images, or their views (the workspace is rewritten behind the previous batch's tail, on its stream)
+    const double* Xb = X + lo * in_len;
+    if (views) {
+      DCGP_TRY(gather_eval_views(model, Xb, n, vw));
+      Xb = vw;
     }
     int rows = 0;
-    DCGP_TRY(forward_all(model, X + lo * in_len, n, S, zs ? zb.data() : nullptr, seed + (uint64_t)b, 0, false, false, &rows));
+    DCGP_TRY(forward_all(model, Xb, V * n, S, zs ? zb.data() : nullptr, seed + (uint64_t)b, 0, false, false, &rows));
     const auto& o = model->outs[nl - 1];
-    if (rows != S * n || o.width != K) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: head rows %d x %d, expected %d x %d", who, rows, o.width, S * n, K);
-    DCGP_TRY(tail(lo, n, o));
+    if (rows != S * V * n || o.width != K)
+      return ctx_fail(ctx, DCGP_ERR_ARG, "%s: head rows %d x %d, expected %d x %d", who, rows, o.width, S * V * n, K);
+    DCGP_TRY(tail(lo, n, S * V, o));
     HIP_TRY(ctx, hipEventRecord(model->ev_eval[model->bank], ctx->stream));
     DCGP_TRY(forward_done(model, model->ev_eval[model->bank]));
   }
@@ -1162,7 +1183,10 @@ int evaluate_impl(dcgp_model* model, const double* X, const int32_t* y, int N_to
   const Targets targets = Targets::of(y, yf, K);
   DCGP_TRY(lik_check_targets(ctx, lik, targets, who));
   if (!yf && K < 2) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: the last layer has %d outputs, a multi-class likelihood needs >= 2", who, K);
-  if (!yf && (long)S * K + K > kEvalMaxSlots) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: S = %d samples of %d classes exceed the tail's LDS", who, S, K);
+  const int V = model->eval_views_active() ? model->eval_V : 1;   // (eval_batches: S * V samples per image)
+  if (!yf && (long)S * V * K + K > kEvalMaxSlots)
+    return V > 1 ? ctx_fail(ctx, DCGP_ERR_ARG, "%s: S = %d samples of V = %d views of %d classes exceed the tail's LDS (S * V * K + K <= %d)", who, S, V, K, kEvalMaxSlots)
+                 : ctx_fail(ctx, DCGP_ERR_ARG, "%s: S = %d samples of %d classes exceed the tail's LDS", who, S, K);
   // the per-image results of the whole set: requested once, before batch 0
   const std::string mp = "m" + std::to_string(model->id) + "_";
   EvalOut eo;
@@ -1175,7 +1199,7 @@ int evaluate_impl(dcgp_model* model, const double* X, const int32_t* y, int N_to
   double h[4];
   DCGP_TRY(eval_batches(
       model, X, N_total, batch, S, zs, seed, who,
-      [&](long lo, int n, const dcgp_model::Out& o) { return lik_eval_tail(ctx, lik, o.mean, o.var, targets, n, S, K, lo, eo); },
+      [&](long lo, int n, int SV, const dcgp_model::Out& o) { return lik_eval_tail(ctx, lik, o.mean, o.var, targets, n, SV, K, lo, eo); },
       [&](const FactorStatus& st) { return lik_eval_sum(ctx, lik, eo, N_total, st, res); }, res, h, 4, info_host));
   out_host[0] = h[0];
   out_host[1] = h[1];
@@ -1202,6 +1226,9 @@ int uncertainty_impl(dcgp_model* model, const double* X, const int32_t* y, const
   const Targets targets{y, yf, K, f64y};
   DCGP_TRY(lik_check_targets(ctx, lik, targets, who));
   if (!f64y && K < 2) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: the last layer has %d outputs, a multi-class likelihood needs >= 2", who, K);
+  const int V = model->eval_views_active() ? model->eval_V : 1;   // (eval_batches: S * V samples per image)
+  if (!f64y && V > 1 && (long)S * V * K + K + kUncExtraSlots > kEvalMaxSlots)
+    return ctx_fail(ctx, DCGP_ERR_ARG, "%s: S = %d samples of V = %d views of %d classes exceed the tail's LDS (S * V * K + K + %d <= %d)", who, S, V, K, kUncExtraSlots, kEvalMaxSlots);
   if (!f64y && (long)S * K + K + kUncExtraSlots > kEvalMaxSlots)
     return ctx_fail(ctx, DCGP_ERR_ARG, "%s: S = %d samples of %d classes exceed the tail's LDS (S * K + K + %d <= %d)", who, S, K, kUncExtraSlots, kEvalMaxSlots);
   const bool labels = f64y ? yf != nullptr : y != nullptr;
@@ -1229,7 +1256,7 @@ int uncertainty_impl(dcgp_model* model, const double* X, const int32_t* y, const
   double h[9];
   DCGP_TRY(eval_batches(
       model, X, N_total, batch, S, zs, seed, who,
-      [&](long lo, int n, const dcgp_model::Out& o) { return lik_unc_tail(ctx, lik, o.mean, o.var, targets, n, S, K, lo, u); },
+      [&](long lo, int n, int SV, const dcgp_model::Out& o) { return lik_unc_tail(ctx, lik, o.mean, o.var, targets, n, SV, K, lo, u); },
       [&](const FactorStatus& st) { return unc_sum(ctx, sa, st, res); }, res, h, 9, info_host));
   out_host[0] = h[0];
   out_host[1] = h[1];

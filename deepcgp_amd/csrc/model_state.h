@@ -88,6 +88,12 @@ struct dcgp_model {
   // flip.  Off (the default): the run gathers with gather_batch_kernel, exactly as before.
   int aug_H = 0, aug_W = 0, aug_C = 0, aug_shift = 0, aug_hflip = 0;
   bool augmenting() const { return aug_shift > 0 || aug_hflip != 0; }
+  // views of an evaluation (dcgp_model_set_eval_views; augment.hip, eval_batches): the table [eval_V][3] of (dy, dx, flip) on the host and on the
+  // device, and the caller's image geometry.  Off (eval_V == 0, the default) and the single identity view: the evaluation runs exactly as before.
+  std::vector<int32_t> eval_views;
+  int32_t* d_eval_views = nullptr; size_t eval_views_cap = 0;
+  int eval_V = 0, ev_H = 0, ev_W = 0, ev_C = 0;
+  bool eval_views_active() const { return eval_V > 1 || (eval_V == 1 && (eval_views[0] != 0 || eval_views[1] != 0 || eval_views[2] != 0)); }
   // zero padding of a layer's input (dcgp_model_set_input_padding; pad.hip): layer l was added with the PADDED H, W and reads a padded copy of
   // its predecessor's sample (of X for layer 0).  pad_in[l]: that copy as the most recent forward left it (a workspace; layer 0's per bank) --
   // the reverse pass reads it, nothing overwrites it before the model's next forward.  pad_ok: the geometry was checked since the last change.
@@ -98,7 +104,7 @@ struct dcgp_model {
   long image_len() const { const auto& v = layers[0]->v; return (long)(v.H - 2 * pad[0]) * (v.W - 2 * pad[0]) * v.C; }
 
   ~dcgp_model() {
-    hipFree(ds_X); hipFree(ds_Y); hipFree(run_idx); hipFree(run_X); hipFree(run_Y);
+    hipFree(ds_X); hipFree(ds_Y); hipFree(run_idx); hipFree(run_X); hipFree(run_Y); hipFree(d_eval_views);
     if (h_ring) hipHostFree(h_ring);
     for (auto& e : ring_ev) if (e) hipEventDestroy(e);
     for (auto& gs : groups) for (auto& gr : gs) gr.release();
@@ -153,6 +159,8 @@ int crop_images(dcgp_ctx* ctx, hipStream_t stream, const double* src, int reps, 
 const char* augment_geometry_error(int H, int W, int C, int max_shift);
 int gather_augment_batch(dcgp_model* model, const int32_t* idx_dev, int batch, uint64_t seed, const int32_t* y32, const double* yf, int D,
                          int32_t* yb32, double* ybf);
+// augment.hip: the model's eval_V views of X [n] images into out [eval_V][n] images (view-major), on ctx->stream
+int gather_eval_views(dcgp_model* model, const double* X, int n, double* out);
 // input_grad.hip: dX of a scalar-lengthscale RBF patch layer from E / cs in one launch (the product on the matrix pipe, the fold in LDS);
 // extra [rows P][L] or nullptr is added to the patch gradients before the fold.  _ok: the shape is covered (otherwise the product + col2im pair)
 bool patch_adjoint_fused_ok(const LayerState& L, long rows);

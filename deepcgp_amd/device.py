@@ -108,6 +108,8 @@ _SIGS = {
     "dcgp_model_train_run_adam": [_vp, _vp, _i, _i, _d, _vp, _u64, _i, _d, _d, _d, _vp, _ip, _ip],
     "dcgp_model_set_augmentation": [_vp, _i, _i, _i, _i, _i],
     "dcgp_augment_images": [_vp, _vp, _i, _i, _i, _i, _i, _i, _u64, _vp],
+    "dcgp_model_set_eval_views": [_vp, _i, _i, _i, _i, _vp],
+    "dcgp_view_images": [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp],
     "dcgp_model_get_param": [_vp, _i, C.c_char_p, _vp, C.c_size_t],
     "dcgp_model_set_grad_shards": [_vp, _i],
     "dcgp_model_set_shard": [_vp, _i, _i],

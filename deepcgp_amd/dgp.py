@@ -4,21 +4,24 @@ it (/root/reference/conv_gp/models.py:65-70, conv_gp/utils/tensorboard.py:22-35,
 (``predict_f``, ``predict_all_layers``, ``predict_density``) and a one-call test-set ``evaluate``.  The whole forward ELBO of a
 minibatch is ONE call into the HIP library (``dcgp_elbo_forward``); parameters live on the device and
 are pushed when changed (``sync_parameters``)."""
+import contextlib
 import ctypes as C
 
 import numpy as np
 
+from . import augment as _augment
 from . import device as dev
 from .kernels import JITTER
 from .layers import ConvLayer, SVGP_Layer
 from .likelihoods import Bernoulli, Gaussian, Poisson, Softmax, StudentT
 
 
-def batched_noise(zs, N, S, batch_size, dims=None):
+def batched_noise(zs, N, S, batch_size, dims=None, V=None):
     """Explicit noise of a whole set, per layer ``[S, N, D]`` (indexed by image, as ``dist.shard_batch`` slices it), in the layout
     ``dcgp_model_evaluate`` reads: per layer the batches' ``[S, n_b, D]`` tables back to back, batch b = images
     ``[b * batch_size, min((b + 1) * batch_size, N))``.  ``dims``: the layers' D (a table of another size raises).  Returns one
-    flat array (or None) per layer."""
+    flat array (or None) per layer.  ``V``: an evaluation over V views (dcgp_model_set_eval_views) -- per layer ``[S, V, N, D]``, the noise of
+    view v of image i, into the batches' ``[S, V n_b, D]`` tables (row v n_b + i); a table of another size raises ValueError."""
     if zs is None:
         return None
     out = []
@@ -26,9 +29,19 @@ def batched_noise(zs, N, S, batch_size, dims=None):
         if z is None:
             out.append(None)
             continue
+        if V is not None:
+            D = -1 if dims is None else dims[i]
+            if D > 0 and np.size(z) != S * V * N * D:
+                raise ValueError("zs[%d]: %d values, an evaluation over views takes [S, V, N, D] = [%d, %d, %d, %d]" % (i, np.size(z), S, V, N, D))
+            z = np.reshape(z, (S, V, N, D))
+            out.append(np.concatenate([z[:, :, lo:lo + batch_size].reshape(-1) for lo in range(0, N, batch_size)]) if N else np.zeros(0))
+            continue
         z = np.reshape(z, (S, N, -1 if dims is None else dims[i]))
         out.append(np.concatenate([z[:, lo:lo + batch_size].reshape(-1) for lo in range(0, N, batch_size)]) if N else np.zeros(0))
     return out
+
+
+EVAL_MAX_SLOTS, UNC_EXTRA_SLOTS = 8192, 48      # csrc/layer.h: kEvalMaxSlots, kUncExtraSlots (the multi-class tails' LDS, in doubles)
 
 
 class Parameter:
@@ -556,7 +569,7 @@ class DGP_Base:
         """Augment the batches of ``train_run`` on the device (dcgp_model_set_augmentation): ``aug`` an ``augment.Augmentation``; None, or one
         that does nothing, switches it off.  The geometry is the first layer's view's (unpadded); a dense head-only model raises ValueError.
         Only ``train_run`` consults it (and ``augment``): evaluation, prediction, ``input_gradient``, the loggers and the per-step calls see
-        their images as they are.  No parameter: checkpoints do not hold it.  Not allowed while enqueued steps are outstanding."""
+        their images as they are (test-time augmentation is ``evaluate(views=...)``, a per-call argument).  No parameter: checkpoints do not hold it.  Not allowed while enqueued steps are outstanding."""
         args = self._checked_augmentation(aug) if aug else (0, 0, 0, 0, 0)
         if not aug and self._model is None:      # nothing built, nothing to switch off
             self.augmentation = None
@@ -909,6 +922,39 @@ class DGP_Base:
     def _out_dims(self):
         return [l.num_outputs for l in self.layers]
 
+    # ---- test-time augmentation --------------------------------------------------------------------
+    @contextlib.contextmanager
+    def _eval_views(self, views, S, who, extra_slots=0):
+        """The views of ONE evaluation call: checked on the host (ValueError before anything is launched), set on the device model
+        (dcgp_model_set_eval_views) for the body and cleared behind it, also when the body raises -- the model keeps no view state.  Yields V,
+        or None without views."""
+        if views is None:
+            yield None
+            return
+        H, W, Cc = self._image_geometry()          # (a dense head alone: ValueError, it has no images)
+        v = _augment.check_views(views, H, W)
+        V, K = int(v.shape[0]), self.layers[-1].num_outputs
+        if not self.float_targets and int(S) * V * K + K + extra_slots > EVAL_MAX_SLOTS:
+            raise ValueError("%s: S = %d samples of V = %d views of %d classes exceed the tail's LDS: S * V * K + K%s = %d > %d"
+                             % (who, int(S), V, K, " + %d" % extra_slots if extra_slots else "", int(S) * V * K + K + extra_slots,
+                                EVAL_MAX_SLOTS))
+        self._build()
+        L = dev.lib()
+
+        def call(*args):
+            try:
+                self._ctx._check(L.dcgp_model_set_eval_views(self._model, *args))
+            except dev.DcgpError as e:
+                if e.code != dev.ERR_ARG:
+                    raise
+                raise ValueError(str(e)) from None
+
+        call(H, W, Cc, V, v.ctypes.data)
+        try:
+            yield V
+        finally:
+            call(0, 0, 0, 0, None)
+
     def _eval_call(self, X, Y, S, batch_size, seed, flat_zs, want_p_mean, density_only=False):
         self._build()
         ctx, L = self._ctx, dev.lib()
@@ -965,19 +1011,22 @@ class DGP_Base:
                                               ym.ptr if ym else None, out, C.byref(info)), info)
         return ld.numpy(), (ym.numpy() if ym else None), (out[0], out[1])
 
-    def predict_density(self, X, Y, S, zs=None, seed=0):
+    def predict_density(self, X, Y, S, zs=None, seed=0, views=None):
         """Log predictive density of each label, N x 1: logsumexp_s log p(y | f_s) - log S (doubly_stochastic_dgp
         DGP_Base.predict_density with the RobustMax likelihood).  Gaussian likelihood: N x D, per output
         logsumexp_s log N(y; Fmean_s, Fvar_s + variance) - log S; Bernoulli: N x D, per output logsumexp_s log p(y | p_s) - log S with
         p_s = probit(Fmean_s / sqrt(1 + Fvar_s)); StudentT, Poisson: N x D, per output logsumexp_s ld_s - log S with ld_s the 20-node
-        log density of sample s.  One device call; ``zs`` per layer [S, N, D]."""
+        log density of sample s.  One device call; ``zs`` per layer [S, N, D].  ``views`` [V, 3] (``augment.views``): test-time
+        augmentation as in ``evaluate`` -- the logsumexp runs over the S V (sample, view) members, minus log(S V); ``zs`` is then
+        [S, V, N, D] per layer."""
         N = np.shape(X)[0]
         if N == 0:
             return np.zeros((0, self.layers[-1].num_outputs if self.float_targets else 1))
-        ld, _, _ = self._eval_call(X, Y, S, N, seed, batched_noise(zs, N, S, N, self._out_dims()), False, density_only=True)
+        with self._eval_views(views, S, "predict_density") as V:
+            ld, _, _ = self._eval_call(X, Y, S, N, seed, batched_noise(zs, N, S, N, self._out_dims(), V), False, density_only=True)
         return ld if self.float_targets else ld.reshape(N, 1)
 
-    def evaluate(self, X, Y, S=5, batch_size=32, seed=0, zs=None, per_image=False):
+    def evaluate(self, X, Y, S=5, batch_size=32, seed=0, zs=None, per_image=False, views=None):
         """A whole test set in one device call (dcgp_model_evaluate): batches of ``batch_size`` images, batch i drawing its noise
         from ``seed + i`` as ``AccuracyLogger`` does, or from ``zs`` (per layer [S, N, D], indexed by image over the whole set).
         Returns {"accuracy", "mean_log_density", "n"}, with ``per_image`` also "log_density" [N] and "p_mean" [N, K] (the
@@ -986,7 +1035,17 @@ class DGP_Base:
         "y_mean" [N, D].  Bernoulli likelihood: {"accuracy", "mean_log_density", "n"}, the accuracy over all N x D entries (an entry is
         correct when its label is 1 exactly where the sample-mean p > 0.5), with ``per_image`` also "log_density" [N] (summed over the
         D outputs) and "p_mean" [N, D] (the sample-mean p).  StudentT, Poisson: what a Gaussian model returns, "y_mean" the sample-mean
-        E_y.  Rank-local: nothing is reduced across ranks."""
+        E_y.  Rank-local: nothing is reduced across ranks.
+
+        ``views``: test-time augmentation, an int array [V, 3] of (dy, dx, flip) (``augment.views``; None: the images as they are).  Every
+        batch is then evaluated on the V shifted / mirrored views of its images (``augment.apply_views``, formed on the device) in the same
+        call, and the predictive distribution of an image is the uniform mixture over the S samples AND the V views,
+        p(y | x) = 1 / (S V) sum_{s, v} p(y | f_s(view_v(x))): "p_mean" / "y_mean" average over the S V members, "log_density" is the log of
+        the mixture density (logsumexp over the members - log(S V) -- not the mean of per-view log densities), accuracy / rmse are those of
+        the averaged prediction.  Batch i still draws from ``seed + i``, for its V n_i view images; ``zs`` per layer is [S, V, N, D], the
+        noise of view v of image i.  The views hold for this call only: the model keeps no view state.  views=[(0, 0, 0)] is views=None, bit
+        for bit.  ValueError before anything is launched: a table that is not [V, 3] or is empty, |dy| or |dx| >= min(H, W), a flip outside
+        {0, 1}, a dense head alone (no images), S V K + K above the multi-class tails' 8192 LDS slots, ``zs`` of another size."""
         N = np.shape(X)[0]
         if int(batch_size) <= 0:
             raise ValueError("batch_size must be positive, got %r" % (batch_size,))
@@ -997,8 +1056,9 @@ class DGP_Base:
                 if per_image:
                     out["log_density"], out["y_mean"] = np.zeros(0), np.zeros((0, D))
                 return out
-            ld, ym, (sq, total) = self._eval_call(X, Y, S, batch_size, seed, batched_noise(zs, N, S, int(batch_size), self._out_dims()),
-                                                 per_image)
+            with self._eval_views(views, S, "evaluate") as V:
+                ld, ym, (sq, total) = self._eval_call(X, Y, S, batch_size, seed,
+                                                     batched_noise(zs, N, S, int(batch_size), self._out_dims(), V), per_image)
             out = {"mean_log_density": total / N, "rmse": float(np.sqrt(sq / (N * D))), "n": N}
             if per_image:
                 out["log_density"], out["y_mean"] = ld, ym
@@ -1008,8 +1068,9 @@ class DGP_Base:
             if per_image:
                 out["log_density"], out["p_mean"] = np.zeros(0), np.zeros((0, self.layers[-1].num_outputs))
             return out
-        ld, pm, (correct, total) = self._eval_call(X, Y, S, batch_size, seed, batched_noise(zs, N, S, int(batch_size), self._out_dims()),
-                                                 per_image)
+        with self._eval_views(views, S, "evaluate") as V:
+            ld, pm, (correct, total) = self._eval_call(X, Y, S, batch_size, seed,
+                                                     batched_noise(zs, N, S, int(batch_size), self._out_dims(), V), per_image)
         entries = N * self.layers[-1].num_outputs if self.bernoulli else N
         out = {"accuracy": correct / entries, "mean_log_density": total / N, "n": N}
         if per_image:
@@ -1064,7 +1125,7 @@ class DGP_Base:
         out["prediction"] = np.zeros(per, np.int32)
         return out
 
-    def evaluate_uncertainty(self, X, Y, S=5, batch_size=32, seed=0, zs=None, bins=15, per_image=False):
+    def evaluate_uncertainty(self, X, Y, S=5, batch_size=32, seed=0, zs=None, bins=15, per_image=False, views=None):
         """``evaluate`` with the uncertainty of the predictions kept, still one device call (dcgp_model_evaluate_uncertainty): everything
         ``evaluate`` returns for the same arguments, bit for bit, plus -- in nats, from the S per-sample probabilities p_s and their mean
         pbar -- "mean_predictive_entropy" (the mean of H(pbar)), "mean_mutual_information" (BALD: H(pbar) - 1/S sum_s H(p_s), the part
@@ -1072,7 +1133,13 @@ class DGP_Base:
         ("ece", "mce", and "reliability": {"count", "confidence", "accuracy"} per bin, NaN where a bin is empty) and the "brier" score.
         With ``per_image`` also "predictive_entropy", "expected_entropy", "mutual_information", "confidence" and "prediction" per image.
         Bernoulli likelihood: every (image, output) entry counts, with the binary entropy, confidence max(pbar, 1 - pbar) and prediction
-        pbar > 0.5; the per-image arrays are N x D.  A Gaussian model has no class probabilities: ValueError.  Rank-local."""
+        pbar > 0.5; the per-image arrays are N x D.  A Gaussian model has no class probabilities: ValueError.  Rank-local.
+
+        ``views`` (``augment.views``): test-time augmentation exactly as in ``evaluate`` -- the members p_s become the S V probabilities
+        p_{s,v} of sample s on view v, pbar their mean.  The expected entropy averages H(p_{s,v}) over the S V members, so the mutual
+        information (BALD) then counts disagreement BETWEEN VIEWS of an image as model uncertainty, together with the disagreement between
+        samples: it is the uncertainty of the augmented predictor, not of the model on the image as it is.  ``zs`` per layer [S, V, N, D];
+        the multi-class limit is S V K + K + 48 <= 8192."""
         if self.gaussian or self.student_t or self.poisson:
             raise ValueError("evaluate_uncertainty: class probabilities need a classification likelihood, this model is %s" % self._lik_name())
         N = np.shape(X)[0]
@@ -1081,15 +1148,16 @@ class DGP_Base:
         bins = int(bins)
         nan = float("nan")
         if N == 0:
-            out = self.evaluate(X, Y, S=S, batch_size=batch_size, seed=seed, zs=zs, per_image=per_image)
+            out = self.evaluate(X, Y, S=S, batch_size=batch_size, seed=seed, zs=zs, per_image=per_image)       # (no image, no view)
             out.update(ece=nan, mce=nan, brier=nan, mean_predictive_entropy=nan, mean_mutual_information=nan,
                        reliability={"count": np.zeros(max(bins, 0), np.int64), "confidence": np.full(max(bins, 0), nan),
                                     "accuracy": np.full(max(bins, 0), nan)})
             if per_image:
                 out.update(self._uncertainty_empty())
             return out
-        arrs, table, h = self._uncertainty_call(X, Y, S, batch_size, seed, batched_noise(zs, N, S, int(batch_size), self._out_dims()), bins,
-                                                per_image)
+        with self._eval_views(views, S, "evaluate_uncertainty", UNC_EXTRA_SLOTS) as V:
+            arrs, table, h = self._uncertainty_call(X, Y, S, batch_size, seed,
+                                                    batched_noise(zs, N, S, int(batch_size), self._out_dims(), V), bins, per_image)
         entries = N * self.layers[-1].num_outputs if self.bernoulli else N
         out = {"accuracy": h[0] / entries, "mean_log_density": h[1] / N, "n": N, "ece": h[2], "mce": h[3], "brier": h[4],
                "mean_predictive_entropy": h[5], "mean_mutual_information": h[6]}
@@ -1101,11 +1169,12 @@ class DGP_Base:
             out.update(arrs)
         return out
 
-    def predict_uncertainty(self, X, S, zs=None, seed=0, batch_size=None):
+    def predict_uncertainty(self, X, S, zs=None, seed=0, batch_size=None, views=None):
         """The per-image uncertainty of unlabelled images (acquisition functions, out-of-distribution scores), one device call:
         {"p_mean", "predictive_entropy", "expected_entropy", "mutual_information", "confidence", "prediction"} as
         ``evaluate_uncertainty(per_image=True)`` returns them.  ``batch_size`` None: one batch of all N images (``predict_proba``'s
-        samples for the same ``seed`` / ``zs``); otherwise batch i draws from ``seed + i``.  Rank-local."""
+        samples for the same ``seed`` / ``zs``); otherwise batch i draws from ``seed + i``.  Rank-local.  ``views``: test-time augmentation
+        as in ``evaluate_uncertainty`` (S V members per image; the mutual information includes the disagreement between views)."""
         if self.gaussian or self.student_t or self.poisson:
             raise ValueError("predict_uncertainty: class probabilities need a classification likelihood, this model is %s" % self._lik_name())
         N = np.shape(X)[0]
@@ -1116,7 +1185,8 @@ class DGP_Base:
         bs = N if batch_size is None else int(batch_size)
         if bs <= 0:
             raise ValueError("batch_size must be positive, got %r" % (batch_size,))
-        arrs, _, _ = self._uncertainty_call(X, None, S, bs, seed, batched_noise(zs, N, S, bs, self._out_dims()), 1, True)
+        with self._eval_views(views, S, "predict_uncertainty", UNC_EXTRA_SLOTS) as V:
+            arrs, _, _ = self._uncertainty_call(X, None, S, bs, seed, batched_noise(zs, N, S, bs, self._out_dims(), V), 1, True)
         return arrs
 
     def KL(self):

@@ -3,6 +3,7 @@
 
 A period of Adam steps is ONE device call (``DGP_Base.train_run``) on a training set that is uploaded once, when the model is set up;
 ``--augment-shift`` / ``--augment-flip`` augment its batches on the device (SGD and NatGrad: the same batches, one device call per step).
+``--test-shift`` / ``--test-flip`` / ``--test-views`` score the test set over shifted and mirrored views (test-time augmentation).
 
     python -m deepcgp_amd.experiment --name run --data digits.npz -M 16,16 --feature-maps 2 --filter-sizes 3,3 --strides 1,1
 """
@@ -11,7 +12,7 @@ import os
 import numpy as np
 
 from . import utils
-from .arguments import default_parser, parse_augmentation, train_steps
+from .arguments import default_parser, parse_augmentation, parse_test_views, train_steps
 from .models import ModelBuilder, index_table, learning_rate, lr_table, save_model_parameters, train
 
 
@@ -22,6 +23,7 @@ class Experiment(object):
         self.flags = flags
         self.seed = int(getattr(flags, "seed", 0))
         self.augmentation = parse_augmentation(flags)     # --augment-shift / --augment-flip: training batches only
+        self.test_views = parse_test_views(flags)         # --test-shift / --test-flip / --test-views: None = the test images as they are
         self._load_data()
         self._setup_model()
         self._setup_optimizer()
@@ -92,9 +94,11 @@ class Experiment(object):
 
     def _setup_logger(self):
         X_test = self.X_test.reshape(self.X_test.shape[0], -1)
+        accuracy = (utils.AccuracyLogger(X_test, self.Y_test) if self.test_views is None
+                    else utils.TTAAccuracyLogger(X_test, self.Y_test, self.test_views))
         loggers = [
             utils.GlobalStepLogger(),
-            utils.AccuracyLogger(X_test, self.Y_test),
+            accuracy,
             utils.LogLikelihoodLogger(),
         ]
         self.log = utils.Log(self.flags.log_dir, self.flags.name, loggers)

@@ -237,6 +237,24 @@ class AccuracyLogger(object):
         return correct / max(Y.size, 1)
 
 
+class TTAAccuracyLogger(object):
+    """Test accuracy under test-time augmentation: ``DGP_Base.evaluate(views=views)``'s accuracy -- the arg-max of the class probabilities
+    averaged over the samples AND the views (``augment.views``) -- with AccuracyLogger's batching (32 images, five samples, batch i drawing from
+    seed + i), the whole set in one device call.  The column keeps AccuracyLogger's title: the driver logs one or the other."""
+    title = 'test_accuracy'
+
+    def __init__(self, X_test, Y_test, views, batch_size=32, num_samples=5):
+        self.X_test = X_test
+        self.Y_test = Y_test if np.ndim(Y_test) == 2 and np.asarray(Y_test).dtype.kind == "f" else np.reshape(Y_test, (-1,))
+        self.views = np.asarray(views)
+        self.batch_size, self.num_samples = int(batch_size), int(num_samples)
+
+    def __call__(self, model, seed=0):
+        if getattr(model, "gaussian", False) or getattr(model, "student_t", False) or getattr(model, "poisson", False):
+            raise ValueError("TTAAccuracyLogger: accuracy needs a classification likelihood, this model is %s" % model._lik_name())
+        return model.evaluate(self.X_test, self.Y_test, S=self.num_samples, batch_size=self.batch_size, seed=seed, views=self.views)["accuracy"]
+
+
 def adversarial_examples(model, X, Y, epsilon, steps=1, step_size=None, clip=None, objective="density", S=None, seed=0, zs=None):
     """Adversarial images in the L-infinity ball of radius ``epsilon`` around X, same shape as X.  ``steps=1`` is the fast gradient sign
     method, X - epsilon sign(dJ/dX): it lowers the objective (the log density of the true label) to first order; ``steps > 1`` is its
@@ -292,32 +310,38 @@ class AdversarialAccuracyLogger(object):
 class UncertaintyLogger(object):
     """Calibration and uncertainty of the test predictions with AccuracyLogger's batching (32 images, five samples, batch i drawing
     from seed + i): the dataset dict of ``DGP_Base.evaluate_uncertainty`` -- accuracy, mean log density, ECE, MCE, Brier score, mean
-    predictive entropy, mean mutual information and the reliability table -- the whole set in one device call."""
+    predictive entropy, mean mutual information and the reliability table -- the whole set in one device call.  ``views``: test-time
+    augmentation (``augment.views``; None: the images as they are)."""
     title = 'test_uncertainty'
 
-    def __init__(self, X_test, Y_test, S=5, bins=15, batch_size=32):
+    def __init__(self, X_test, Y_test, S=5, bins=15, batch_size=32, views=None):
+        self.views = views
         self.X_test = X_test
         self.Y_test = Y_test if np.ndim(Y_test) == 2 and np.asarray(Y_test).dtype.kind == "f" else np.reshape(Y_test, (-1,))
         self.num_samples, self.bins, self.batch_size = int(S), int(bins), int(batch_size)
 
     def __call__(self, model, seed=0):
-        return model.evaluate_uncertainty(self.X_test, self.Y_test, S=self.num_samples, batch_size=self.batch_size, seed=seed, bins=self.bins)
+        kw = {} if self.views is None else {"views": self.views}      # (without views: the call it always made)
+        return model.evaluate_uncertainty(self.X_test, self.Y_test, S=self.num_samples, batch_size=self.batch_size, seed=seed, bins=self.bins, **kw)
 
 
 class TestLogDensityLogger(object):
     """Mean test log predictive density with AccuracyLogger's batching (32 images, five samples, batch i drawing from seed + i):
-    ``DGP_Base.evaluate``, the whole set in one device call."""
+    ``DGP_Base.evaluate``, the whole set in one device call.  ``views``: test-time augmentation (``augment.views``; None: the images as they
+    are) -- the log of the density averaged over samples and views."""
     title = 'test_log_likelihood'
     __test__ = False   # (not a pytest class despite the name)
 
-    def __init__(self, X_test, Y_test, batch_size=32, num_samples=5):
+    def __init__(self, X_test, Y_test, batch_size=32, num_samples=5, views=None):
+        self.views = views
         # labels are flattened; float targets N x D (a Gaussian likelihood) are kept as they are
         self.X_test = X_test
         self.Y_test = Y_test if np.ndim(Y_test) == 2 and np.asarray(Y_test).dtype.kind == "f" else np.reshape(Y_test, (-1,))
         self.batch_size, self.num_samples = int(batch_size), int(num_samples)
 
     def __call__(self, model, seed=0):
-        return model.evaluate(self.X_test, self.Y_test, S=self.num_samples, batch_size=self.batch_size, seed=seed)["mean_log_density"]
+        kw = {} if self.views is None else {"views": self.views}      # (without views: the call it always made)
+        return model.evaluate(self.X_test, self.Y_test, S=self.num_samples, batch_size=self.batch_size, seed=seed, **kw)["mean_log_density"]
 
 
 class LogLikelihoodLogger(object):

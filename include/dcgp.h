@@ -367,6 +367,29 @@ int dcgp_model_set_augmentation(dcgp_model* model, int H, int W, int C, int max_
  * (seed, b) -- the host-side augmentation loop a user of the reference writes around its feed (conv_gp/experiment.py:84-108), as one launch.
  * Every value of out is written.  Asynchronous on the ctx stream.  DCGP_ERR_ARG as above for the geometry and max_shift. */
 int dcgp_augment_images(dcgp_ctx* ctx, const double* X, int N, int H, int W, int C, int max_shift, int hflip, uint64_t seed, double* out);
+/* Test-time augmentation: the evaluation of a model trained on shifted and flipped images averages its predictive distribution over a few
+ * shifted and mirrored views of each test image -- what a user of the reference does on the host around its per-batch predict_y loop
+ * (conv_gp/utils/log.py), V passes and a hand-made mean; here inside the one evaluation call.  views_host [V][3] int32 (host): (dy, dx, flip)
+ * per view, the transform of dcgp_model_set_augmentation with the draw replaced by the table (flip first, then the shift, zero fill).
+ * Model state that dcgp_model_evaluate(_f64y), dcgp_model_predict_density(_f64y) and dcgp_model_evaluate_uncertainty(_f64y) consult; nothing
+ * else does: dcgp_model_predict_y, propagate, the ELBO, the training steps and runs, input gradients and patch evidence see their X as it is.
+ * With views set, a batch of n images becomes V n images, view v of image i at row v n + i, ONE forward pass on them with S samples leaves
+ * head rows [S][V n][K], and since row s V n + v n + i = (s V + v) n + i the tails see S V samples of n images:
+ *     p(y | x) = 1 / (S V) sum_{s, v} p(y | f_s(view_v(x))),
+ * the log density the log of that mixture, p_mean / y_mean, accuracy / squared error, entropies, BALD and calibration those of the S V members
+ * (the mutual information then counts disagreement between views as model uncertainty).  z_per_layer: batch b's table per layer is
+ * [S][V n_b][D_l], from S * V * lo_b * D_l on.  Limits: S * V * K + K <= 8192 (+ 48 for the uncertainty tail), S * V * batch < 2^31.
+ * H, W, C: the model's unpadded first-layer image (a padded first layer pads the views as it pads any batch).  V == 0 clears the setting
+ * (H, W, C are then ignored); the single view (0, 0, 0) evaluates on exactly the code path of no views.
+ * DCGP_ERR_ARG, with a message: another geometry than the model's, |dy| or |dx| >= min(H, W), a flip outside {0, 1}, a dense head alone (its
+ * inputs are feature vectors), no head yet, enqueued steps still to be collected.  No parameter: checkpoints do not hold it. */
+int dcgp_model_set_eval_views(dcgp_model* model, int H, int W, int C, int V, const int32_t* views_host /* [V][3] */);
+/* The views of a caller's batch: X [N][H][W][C] -> out [V * N][H][W][C] (device pointers; out may not alias X), view v of image i at row
+ * v * N + i -- the gather the evaluation runs per batch, as one launch.  Every value of out is written.  Returns when the launch is done.
+ * The gather itself moves values under any shift that leaves a pixel: here the bound is per axis, |dy| < H and |dx| < W (a view of one
+ * surviving row or column is allowed), where the model setting keeps the training-time bound min(H, W).  DCGP_ERR_ARG for the geometry, a
+ * shift past that bound, a flip outside {0, 1}, V < 1, out aliasing X. */
+int dcgp_view_images(dcgp_ctx* ctx, const double* X, int N, int H, int W, int C, int V, const int32_t* views_host /* [V][3] */, double* out);
 /* Multi-rank training step (one process per GPU, dcgp_comm_init_rank): how a step's gradient is exchanged inside dcgp_model_train_step_adam.
  * 0 (default): ncclAllReduce of every layer's gradient block, every rank then updates every parameter.  1: ncclReduceScatter of the block
  * (each rank receives the sum of its shard only -- dcgp_shard_range), Adam on that shard of the layer's parameter block, ncclAllGather
