@@ -615,95 +615,6 @@ __global__ __launch_bounds__(256) void ard_finish_kernel(const double* __restric
   const double r = block_sum_256(acc, red);
   if (t == 0) gard[d] = -sd * r;
 }
-// ---- optimiser ---------------------------------------------------------------------------------------------------
-// tf.train.AdamOptimizer / GradientDescentOptimizer on gpflow's unconstrained variables, ascending the ELBO.  transform 0: identity;
-// 1: gpflow transforms.positive (x = softplus(u) + 1e-6): the parameter is held constrained, moved through u.
-// ONE launch for every parameter group of every layer (a launch per group: ten 5 us launches and 2 x layers small copies on a 1.5 ms
-// step): block b works on group g with first_block[g] <= b < first_block[g + 1].  A layer's kernel hyper-parameters live on the host
-// (they are launch arguments of the forward pass): their current values arrive as arguments, the updated ones go to the device copy
-// and straight into a pinned host slot.
-struct OptGroup {
-  double* p; const double* g; double* m; double* v;   // parameter, gradient, Adam moments (unused by SGD)
-  double* recip;                                      // != null: 1 / p is kept here as well (the dense head's staging scale)
-  long n;
-  int transform, hyp_layer;                           // hyp_layer >= 0: p is that layer's {variance, p1, p2} triple
-  // sharded step (OptArgs::sharded): the group's offset in its layer's gradient block, the layer, and whether it only passes through
-  long off; int layer, frozen;
-  int hold;                                           // hyp_layer >= 0: bit i set = element i of the triple is held (set_trainable on one ArcCosine parameter)
-};
-constexpr int OPT_GROUPS_MAX = 48;
-struct OptArgs {
-  OptGroup grp[OPT_GROUPS_MAX];
-  int first_block[OPT_GROUPS_MAX + 1];
-  int ng, sgd;
-  double lr, b1, b2, eps;            // lr: Adam's bias-corrected step size, or the plain SGD rate
-  double hyp_in[8][3];
-  double* host_out;                  // [8][3] pinned
-  const double* status;              // != null: a non-zero word there (the step's factorisation failed) leaves every parameter untouched
-  // Sharded step (dcgp_model_set_grad_exchange 1): only the elements whose position in the layer's block lies in [sh_lo, sh_hi) are updated --
-  // the gradient there is this rank's reduce-scattered sum -- and every value of the range, updated or frozen, also goes to stage[layer]
-  // (the block's layout), which the all-gather then completes.  stage_only: the parameter arrays are left alone (the debug entry's other ranks).
-  int sharded, stage_only;
-  long sh_lo[8], sh_hi[8];
-  double* stage[8];
-};
-__global__ __launch_bounds__(256) void opt_step_kernel(OptArgs a) {
-  if (a.status && *a.status != 0.0) return;
-  int gi = 0;
-  while (gi + 1 < a.ng && (int)blockIdx.x >= a.first_block[gi + 1]) ++gi;
-  const OptGroup& G = a.grp[gi];
-  const long i = (long)((int)blockIdx.x - a.first_block[gi]) * 256 + threadIdx.x;
-  if (i >= G.n) return;
-  if (a.sharded && (G.off + i < a.sh_lo[G.layer] || G.off + i >= a.sh_hi[G.layer])) return;
-  const double x = G.hyp_layer >= 0 ? a.hyp_in[G.hyp_layer][i] : G.p[i];
-  double out;
-  if (G.frozen || (G.hyp_layer >= 0 && ((G.hold >> (int)i) & 1))) {
-    out = x;
-  } else if (a.sgd) {   // plain gradient ascent on the ELBO in the unconstrained space
-    const double gr = G.g[i];
-    if (G.transform == 1) {
-      const double y = x - 1e-6;
-      double u = y > 35.0 ? y : log(expm1(y));
-      u += a.lr * gr * -expm1(-y);
-      out = (u > 35.0 ? u : log1p(exp(u))) + 1e-6;
-    } else {
-      out = x + a.lr * gr;
-    }
-  } else {
-    double gr = -G.g[i];                               // minimise -ELBO
-    double u = x;
-    if (G.transform == 1) {
-      const double y = x - 1e-6;
-      u = y > 35.0 ? y : log(expm1(y));               // softplus^-1
-      gr *= -expm1(-y);                                // dx/du = sigmoid(u) = 1 - exp(-y)
-    }
-    const double mi = a.b1 * G.m[i] + (1.0 - a.b1) * gr;
-    const double vi = a.b2 * G.v[i] + (1.0 - a.b2) * gr * gr;
-    G.m[i] = mi;
-    G.v[i] = vi;
-    u -= a.lr * mi / (sqrt(vi) + a.eps);
-    out = G.transform == 1 ? (u > 35.0 ? u : log1p(exp(u))) + 1e-6 : u;
-  }
-  if (a.sharded) a.stage[G.layer][G.off + i] = out;
-  if (G.frozen || a.stage_only) return;
-  G.p[i] = out;
-  if (G.recip) G.recip[i] = 1.0 / out;
-  if (G.hyp_layer >= 0) a.host_out[3 * G.hyp_layer + i] = out;
-}
-// behind the all-gather: the other ranks' shards of the staged block into this rank's parameter arrays
-__global__ __launch_bounds__(256) void opt_unstage_kernel(OptArgs a) {
-  if (a.status && *a.status != 0.0) return;
-  int gi = 0;
-  while (gi + 1 < a.ng && (int)blockIdx.x >= a.first_block[gi + 1]) ++gi;
-  const OptGroup& G = a.grp[gi];
-  const long i = (long)((int)blockIdx.x - a.first_block[gi]) * 256 + threadIdx.x;
-  if (i >= G.n || G.frozen) return;
-  if (G.off + i >= a.sh_lo[G.layer] && G.off + i < a.sh_hi[G.layer]) return;   // this rank's own shard: already in place
-  const double out = a.stage[G.layer][G.off + i];
-  G.p[i] = out;
-  if (G.recip) G.recip[i] = 1.0 / out;
-  if (G.hyp_layer >= 0) a.host_out[3 * G.hyp_layer + i] = out;
-}
 
 // ---- host helpers ------------------------------------------------------------------------------------------------
 struct Bk {   // per-backward bookkeeping
@@ -770,7 +681,9 @@ int add_scalar(Bk& bk, LayerState& L, int which, const double* part, long n, dou
 }
 struct ScalarPart { int which; const double* part; long n; double scale; };
 int add_scalars(Bk& bk, LayerState& L, std::initializer_list<ScalarPart> parts) {
-  for (const ScalarPart& p : parts) DCGP_TRY(add_scalar(bk, L, p.which, p.part, p.n, p.scale));
+  for (const ScalarPart& p : parts) {
+    if (p.part) DCGP_TRY(add_scalar(bk, L, p.which, p.part, p.n, p.scale));   // (null: a sum this base kernel does not have)
+  }
   return DCGP_OK;
 }
 int flush_scalars(Bk& bk) {
@@ -794,6 +707,37 @@ int im2col(dcgp_ctx* ctx, const LayerState& L, const double* Xin, int n_mod, lon
                      L.v.Ho, L.v.Wo, L.v.L, Xcol);
   LAUNCH_CHECK(ctx);
   return DCGP_OK;
+}
+
+// row chunks of an E-form launch (a thread per column and chunk): enough to put a few thousand blocks on the chip, 16 rows or more each
+struct RowChunks { unsigned nb; int chunks, rpc; };
+RowChunks row_chunks(int M, long Kc) {
+  const unsigned nb = blocks_for(Kc);
+  const int chunks = std::min((int)std::min<long>(16, std::max<long>(1, 2048 / nb)), (M + 15) / 16);
+  const int rpc = (M + chunks - 1) / chunks;
+  return {nb, (M + rpc - 1) / rpc, rpc};
+}
+
+// out[m] = sum_c A[m][c] over Kc columns: per-chunk partial sums (4096 columns or more a chunk, at most 32 chunks), then their sum
+int row_sums(Bk& bk, const double* A, long ld, long Kc, int M, double* out) {
+  dcgp_ctx* ctx = bk.ctx;
+  const int chunks = (int)std::min<long>(32, (Kc + 4095) / 4096);
+  const long cpc = round_up_l((Kc + chunks - 1) / chunks, 256);
+  double* rsp = bk.ws("pb_rsp", (size_t)chunks * M);
+  NEED(rsp);
+  hipLaunchKernelGGL(rowsum_big_kernel, dim3(M, chunks), dim3(256), 0, ctx->stream, A, ld, Kc, cpc, M, rsp);
+  LAUNCH_CHECK(ctx);
+  hipLaunchKernelGGL(sum_chunks_kernel, dim3(blocks_for(M)), dim3(256), 0, ctx->stream, rsp, chunks, (long)M, out);
+  LAUNCH_CHECK(ctx);
+  return DCGP_OK;
+}
+
+// a workspace of at least min_bytes that the forward pass left for the layer being processed; nullptr, with the context's error set, if it is not there
+const double* forward_left(Bk& bk, const char* name, size_t min_bytes, const char* what) {
+  auto it = bk.ctx->ws.find(bk.pfx + name);
+  if (it != bk.ctx->ws.end() && it->second.second >= min_bytes) return (const double*)it->second.first;
+  ctx_fail(bk.ctx, DCGP_ERR_ARG, "grad: the forward pass left no %s", what);
+  return nullptr;
 }
 
 // the hyper-parameter partial sums a Gram backward left in its scratch (`tag`) -> the layer's scalar slots
@@ -860,16 +804,7 @@ int patch_backward(Bk& bk, LayerState& L, const double* E, long ld, long Kc, con
   const double inv_l2 = cz != 0.0 ? cz : 1.0 / (L.ls * L.ls);   // cz: the ArcCosine adjoint passes its weight variance (and its own row vector)
   double* rs = rs_in ? const_cast<double*>(rs_in) : bk.ws("pb_rs", M);
   NEED(rs);
-  if (!rs_in && !bk.data_only) {
-    const int chunks = (int)std::min<long>(32, (Kc + 4095) / 4096);
-    const long cpc = round_up_l((Kc + chunks - 1) / chunks, 256);
-    double* rsp = bk.ws("pb_rsp", (size_t)chunks * M);
-    NEED(rsp);
-    hipLaunchKernelGGL(rowsum_big_kernel, dim3(M, chunks), dim3(256), 0, ctx->stream, E, ld, Kc, cpc, M, rsp);
-    LAUNCH_CHECK(ctx);
-    hipLaunchKernelGGL(sum_chunks_kernel, dim3(blocks_for(M)), dim3(256), 0, ctx->stream, rsp, chunks, (long)M, rs);
-    LAUNCH_CHECK(ctx);
-  }
+  if (!rs_in && !bk.data_only) DCGP_TRY(row_sums(bk, E, ld, Kc, M, rs));
   const double* Zp = Zuse ? Zuse : L.Z;
   if (!bk.data_only) {   // dZ += (E Xcol - rs o Z) / l^2: one product over the columns (split along k), the correction in its epilogue
     GenGemm e = mk(E, ld, 1, Xcol, Ld, 1, dz_out ? dz_out : L.gZ, Ld, M, Ld, (int)Kc);
@@ -1195,30 +1130,66 @@ int cond_backward_finish(Bk& bk, const Lanes& ln, LayerState& L, const double* A
   return DCGP_OK;
 }
 
-int e_form(Bk& bk, LayerState& L, const double* dK, long lddk, int pdiv, const double* w, double wscale, const double* K, long ldk,
-           double* E, long lde, long Kc, double* cs, double* raw) {
+// K_uf adjoint of the layer's base kernel: E [M x Kc], its column sums cs and the kernel's hyper-parameter sums (into the layer's scalar slots) from
+// dK = d ELBO / dK_uf and the stored K.  Column c reads dK[m][c / pdiv], times w[c % pdiv] * wscale where w is given (the head's patch weights; raw
+// then gets the unweighted column sums, for d w).  RBF: E = dK o K.  Matern: E = dK o (-2 dk/drho) over the product Z Xcol^T, then the RBF's form
+// as it is.  ArcCosine: E = F1, cs = colsum(F2) / A, and out: rs = rowsum(F2) / Q, cz = the weight variance, which patch_backward takes in the
+// place of rowsum(E) and 1 / l^2.  The chunks' sums are added by a second launch, except that the RBF kernel with one chunk writes cs (and raw) itself.
+struct KufAdjoint { const double* rs = nullptr; double cz = 0.0; };
+int kuf_adjoint(Bk& bk, LayerState& L, const double* dK, long lddk, int pdiv, const double* w, double wscale, const double* K, long ldk,
+                const double* Xcol, long Kc, double* E, long lde, double* cs, double* raw, KufAdjoint* out) {
   dcgp_ctx* ctx = bk.ctx;
-  const unsigned nb = blocks_for(Kc);
-  // enough row chunks to put a few thousand blocks on the chip
-  int chunks = (int)std::min<long>(16, std::max<long>(1, 2048 / nb));
-  chunks = std::min(chunks, (L.M + 15) / 16);
-  const int rpc = (L.M + chunks - 1) / chunks;
-  chunks = (L.M + rpc - 1) / rpc;
-  double* pv = bk.ws("ef_pv", (size_t)nb * chunks);
-  double* pl = bk.ws("ef_pl", (size_t)nb * chunks);
-  double* csp = chunks > 1 ? bk.ws("ef_csp", (size_t)chunks * Kc) : cs;
-  double* rawp = raw ? (chunks > 1 ? bk.ws("ef_rawp", (size_t)chunks * Kc) : raw) : nullptr;
+  const int M = L.M, Ld = L.v.L, bt = L.base_type;
+  if (bt != 0 && (pdiv != 1 || w || raw || lddk != lde || ldk != lde)) return ctx_fail(ctx, DCGP_ERR_ARG, "grad: only the RBF adjoint takes patch weights or mixed leading dimensions");
+  const RowChunks rc = row_chunks(M, Kc);
+  const dim3 grid(rc.nb, rc.chunks);
+  const long np = (long)rc.nb * rc.chunks;
+  const bool direct = bt == 0 && rc.chunks == 1;
+  double* pv = bk.ws("ef_pv", np);
+  double* pl = bk.ws("ef_pl", np);                                   // lengthscale | ArcCosine weight variance
+  double* pb = bt == 1 ? bk.ws("ef_pb", np) : nullptr;               // ArcCosine bias variance
+  double* csp = direct ? cs : bk.ws("ef_csp", (size_t)rc.chunks * Kc);
+  double* rawp = raw && !direct ? bk.ws("ef_rawp", (size_t)rc.chunks * Kc) : raw;
+  double* xn = bt == 0 ? nullptr : bk.ws(bt == 1 ? "acos_xn" : "mat_xn", Kc);
+  double* F2 = bt == 1 ? bk.ws("acos_F2", (size_t)L.Mp * lde) : nullptr;
   NEED(pv); NEED(pl); NEED(csp);
   if (raw) NEED(rawp);
-  hipLaunchKernelGGL(e_form_kernel, dim3(nb, chunks), dim3(256), 0, ctx->stream, dK, lddk, pdiv, w, wscale, K, ldk, E, lde, L.M, rpc, Kc,
-                     1.0 / L.variance, 2.0 * L.ls * L.ls, csp, rawp, pv, pl);
-  LAUNCH_CHECK(ctx);
-  if (chunks > 1) {
-    if (raw) hipLaunchKernelGGL(sum_chunks2_kernel, dim3(blocks_for(Kc)), dim3(256), 0, ctx->stream, csp, rawp, chunks, Kc, cs, raw);
-    else hipLaunchKernelGGL(sum_chunks_kernel, dim3(blocks_for(Kc)), dim3(256), 0, ctx->stream, csp, chunks, Kc, cs);
+  double lscale = 1.0;   // of the second sum (the variance sum: 1 / variance throughout)
+  if (bt != 0) {
+    NEED(xn);
+    hipLaunchKernelGGL(rownorm_kernel, dim3(blocks_for(Kc)), dim3(256), 0, ctx->stream, Xcol, Kc, Ld, xn);
     LAUNCH_CHECK(ctx);
   }
-  DCGP_TRY(add_scalars(bk, L, {{0, pv, (long)nb * chunks, 1.0 / L.variance}, {1, pl, (long)nb * chunks, 1.0 / (L.ls * L.ls * L.ls)}}));
+  if (bt == 0) {
+    hipLaunchKernelGGL(e_form_kernel, grid, dim3(256), 0, ctx->stream, dK, lddk, pdiv, w, wscale, K, ldk, E, lde, M, rc.rpc, Kc, 1.0 / L.variance,
+                       2.0 * L.ls * L.ls, csp, rawp, pv, pl);
+    lscale = 1.0 / (L.ls * L.ls * L.ls);
+  } else if (bt == 1) {
+    NEED(F2); NEED(pb);
+    hipLaunchKernelGGL(acos_e_form_kernel, grid, dim3(256), 0, ctx->stream, dK, E, lde, K, F2, M, rc.rpc, Kc, L.variance, L.acos_w, L.acos_b, L.zn, xn,
+                       csp, pv, pl, pb);
+  } else {
+    DCGP_TRY(gemm_gen(ctx, mk(L.Z, Ld, 1, Xcol, 1, Ld, E, lde, M, (int)Kc, Ld)));   // z_m . x_c
+    const double inv_l2 = 1.0 / (L.ls * L.ls);
+    hipLaunchKernelGGL(bt == 2 ? matern_e_form_kernel<2> : matern_e_form_kernel<3>, grid, dim3(256), 0, ctx->stream, dK, E, lde, K, M, rc.rpc, Kc,
+                       L.variance, inv_l2, L.zn, xn, csp, pv, pl);
+    lscale = inv_l2 / L.ls;
+  }
+  LAUNCH_CHECK(ctx);
+  if (!direct) {
+    if (raw) hipLaunchKernelGGL(sum_chunks2_kernel, dim3(blocks_for(Kc)), dim3(256), 0, ctx->stream, csp, rawp, rc.chunks, Kc, cs, raw);
+    else hipLaunchKernelGGL(sum_chunks_kernel, dim3(blocks_for(Kc)), dim3(256), 0, ctx->stream, csp, rc.chunks, Kc, cs);
+    LAUNCH_CHECK(ctx);
+  }
+  DCGP_TRY(add_scalars(bk, L, {{0, pv, np, 1.0 / L.variance}, {1, pl, np, lscale}, {2, pb, np, 1.0}}));
+  if (bt == 1) {   // rowsum(F2) / Q
+    double* rs = bk.ws("acos_rs", M);
+    NEED(rs);
+    DCGP_TRY(row_sums(bk, F2, lde, Kc, M, rs));
+    hipLaunchKernelGGL(acos_divide_kernel, dim3(blocks_for(M)), dim3(256), 0, ctx->stream, rs, L.zn, M, L.acos_w, L.acos_b);
+    LAUNCH_CHECK(ctx);
+    *out = {rs, L.acos_w};
+  }
   return DCGP_OK;
 }
 
@@ -1277,20 +1248,29 @@ int layer_tail(Bk& bk, const Lanes& ln, LayerState& L, const double* S, const do
   return DCGP_OK;
 }
 
+// dXin [rows, H, W, C] from E and cs in one launch (fuse_dx: input_grad.hip, `extra` as there) or from the patch gradients dXcol by col2im's gather
+int patches_to_dx(Bk& bk, LayerState& L, bool fuse_dx, const double* E, long ld, const double* cs, const double* Xin, int rows, int n_mod,
+                  const double* extra, const double* dXcol, double* dXin) {
+  if (fuse_dx) return patch_adjoint_fused(bk.ctx, L, E, ld, cs, Xin, rows, n_mod, extra, dXin);
+  const long n = (long)rows * L.v.H * L.v.W * L.v.C;
+  hipLaunchKernelGGL(col2im_kernel, dim3(blocks_for(n)), dim3(256), 0, bk.ctx->stream, dXcol, rows, L.v.H, L.v.W, L.v.C, L.v.f, L.v.s, L.v.Ho,
+                     L.v.Wo, L.v.L, dXin);
+  LAUNCH_CHECK(bk.ctx);
+  return DCGP_OK;
+}
+
 // ConvLayer backward.  Xin: the layer's input images ([n_mod, H, W, C], row n reads image n % n_mod); gm / gv [rows * P][R].
 int conv_backward(Bk& bk, LayerState& L, const double* Xin, int rows, int n_mod, const double* gm, const double* gv, double* dXin) {
   dcgp_ctx* ctx = bk.ctx;
-  const int M = L.M, Mp = L.Mp, P = L.v.P, Ld = L.v.L;
+  const int Mp = L.Mp, P = L.v.P, Ld = L.v.L;
   const long Kc = (long)rows * P, ld = col_ld(Kc);
   Lanes ln = lanes_of(ctx);
   if (bk.data_only) { ln.forked = false; ln.chain = ln.tail = ln.main; }
   DCGP_TRY(begin_layer(bk, L));
   // forward leftovers (conv_forward / cond_core workspaces)
-  auto itB = ctx->ws.find(bk.pfx + "Kuf"), itA = ctx->ws.find(bk.pfx + "A1");
-  if (itB == ctx->ws.end() || itA == ctx->ws.end() || itA->second.second < (size_t)Mp * ld * sizeof(double))
-    return ctx_fail(ctx, DCGP_ERR_ARG, "grad: the forward pass left no K_uf / A1 for this layer");
-  const double* Kuf = (const double*)itB->second.first;
-  const double* A1 = (const double*)itA->second.first;
+  const double* Kuf = forward_left(bk, "Kuf", 0, "K_uf / A1 for this layer");
+  const double* A1 = forward_left(bk, "A1", (size_t)Mp * ld * sizeof(double), "K_uf / A1 for this layer");
+  if (!Kuf || !A1) return DCGP_ERR_ARG;
   double* dKuf = bk.ws("dKuf", (size_t)Mp * ld);
   double* E = bk.ws("E", (size_t)Mp * ld);       // (not over dK_uf: the chain stream still reads that)
   double* S = bk.ws("S", (size_t)Mp * Mp);
@@ -1306,75 +1286,11 @@ int conv_backward(Bk& bk, LayerState& L, const double* Xin, int rows, int n_mod,
   if (!fuse_dx) DCGP_TRY(im2col(ctx, L, Xin, n_mod, Kc, Xcol));
   double* dXcol = nullptr;
   if (dXin && !fuse_dx) { dXcol = bk.ws("dXcol", (size_t)Kc * Ld); NEED(dXcol); }
-  if (L.base_type == 1) {   // ArcCosine(order 0): F1, F2 beside it, the RBF machinery on (F1, rowsum(F2) / Q, colsum(F2) / A, w)
-    const unsigned nb = blocks_for(Kc);
-    int chunks = (int)std::min<long>(16, std::max<long>(1, 2048 / nb));
-    chunks = std::min(chunks, (M + 15) / 16);
-    const int rpc = (M + chunks - 1) / chunks;
-    chunks = (M + rpc - 1) / rpc;
-    double* F2 = bk.ws("acos_F2", (size_t)Mp * ld);
-    double* xn = bk.ws("acos_xn", Kc);
-    double* csp = bk.ws("ef_csp", (size_t)chunks * Kc);
-    double* pv = bk.ws("ef_pv", (size_t)nb * chunks);
-    double* pw = bk.ws("ef_pl", (size_t)nb * chunks);
-    double* pb = bk.ws("ef_pb", (size_t)nb * chunks);
-    double* rs2 = bk.ws("acos_rs", M);
-    double* rsp = bk.ws("pb_rsp", (size_t)32 * M);
-    NEED(F2); NEED(xn); NEED(csp); NEED(pv); NEED(pw); NEED(pb); NEED(rs2); NEED(rsp);
-    hipLaunchKernelGGL(rownorm_kernel, dim3(blocks_for(Kc)), dim3(256), 0, ctx->stream, Xcol, Kc, Ld, xn);
-    LAUNCH_CHECK(ctx);
-    hipLaunchKernelGGL(acos_e_form_kernel, dim3(nb, chunks), dim3(256), 0, ctx->stream, dKuf, E, ld, Kuf, F2, M, rpc, Kc, L.variance, L.acos_w, L.acos_b,
-                       L.zn, xn, csp, pv, pw, pb);
-    LAUNCH_CHECK(ctx);
-    hipLaunchKernelGGL(sum_chunks_kernel, dim3(blocks_for(Kc)), dim3(256), 0, ctx->stream, csp, chunks, Kc, cs);
-    LAUNCH_CHECK(ctx);
-    DCGP_TRY(add_scalars(bk, L, {{0, pv, (long)nb * chunks, 1.0 / L.variance}, {1, pw, (long)nb * chunks, 1.0}, {2, pb, (long)nb * chunks, 1.0}}));
-    {   // rowsum(F2) / Q
-      const int rch = (int)std::min<long>(32, (Kc + 4095) / 4096);
-      const long cpc = round_up_l((Kc + rch - 1) / rch, 256);
-      hipLaunchKernelGGL(rowsum_big_kernel, dim3(M, rch), dim3(256), 0, ctx->stream, F2, ld, Kc, cpc, M, rsp);
-      LAUNCH_CHECK(ctx);
-      hipLaunchKernelGGL(sum_chunks_kernel, dim3(blocks_for(M)), dim3(256), 0, ctx->stream, rsp, rch, (long)M, rs2);
-      LAUNCH_CHECK(ctx);
-      hipLaunchKernelGGL(acos_divide_kernel, dim3(blocks_for(M)), dim3(256), 0, ctx->stream, rs2, L.zn, M, L.acos_w, L.acos_b);
-      LAUNCH_CHECK(ctx);
-    }
-    DCGP_TRY(patch_backward(bk, L, E, ld, Kc, cs, Xcol, dXcol, 0, nullptr, nullptr, rs2, L.acos_w));
-  } else if (L.base_type == 2 || L.base_type == 3) {   // Matern32 / Matern52: E = dK o (-2 dk/drho), then the RBF machinery as it is
-    const unsigned nb = blocks_for(Kc);
-    int chunks = (int)std::min<long>(16, std::max<long>(1, 2048 / nb));
-    chunks = std::min(chunks, (M + 15) / 16);
-    const int rpc = (M + chunks - 1) / chunks;
-    chunks = (M + rpc - 1) / rpc;
-    double* xn = bk.ws("mat_xn", Kc);
-    double* csp = bk.ws("ef_csp", (size_t)chunks * Kc);
-    double* pv = bk.ws("ef_pv", (size_t)nb * chunks);
-    double* pl = bk.ws("ef_pl", (size_t)nb * chunks);
-    NEED(xn); NEED(csp); NEED(pv); NEED(pl);
-    hipLaunchKernelGGL(rownorm_kernel, dim3(blocks_for(Kc)), dim3(256), 0, ctx->stream, Xcol, Kc, Ld, xn);
-    LAUNCH_CHECK(ctx);
-    DCGP_TRY(gemm_gen(ctx, mk(L.Z, Ld, 1, Xcol, 1, Ld, E, ld, M, (int)Kc, Ld)));   // z_m . x_c
-    const double inv_l2 = 1.0 / (L.ls * L.ls);
-    hipLaunchKernelGGL(L.base_type == 2 ? matern_e_form_kernel<2> : matern_e_form_kernel<3>, dim3(nb, chunks), dim3(256), 0, ctx->stream, dKuf, E, ld, Kuf,
-                       M, rpc, Kc, L.variance, inv_l2, L.zn, xn, csp, pv, pl);
-    LAUNCH_CHECK(ctx);
-    hipLaunchKernelGGL(sum_chunks_kernel, dim3(blocks_for(Kc)), dim3(256), 0, ctx->stream, csp, chunks, Kc, cs);
-    LAUNCH_CHECK(ctx);
-    DCGP_TRY(add_scalars(bk, L, {{0, pv, (long)nb * chunks, 1.0 / L.variance}, {1, pl, (long)nb * chunks, inv_l2 / L.ls}}));
-    DCGP_TRY(patch_backward(bk, L, E, ld, Kc, cs, Xcol, dXcol, 0));
-  } else {
-    DCGP_TRY(e_form(bk, L, dKuf, ld, 1, nullptr, 1.0, Kuf, ld, E, ld, Kc, cs, nullptr));
-    DCGP_TRY(patch_backward(bk, L, E, ld, Kc, cs, Xcol, dXcol, 0));
-  }
+  KufAdjoint ka;
+  DCGP_TRY(kuf_adjoint(bk, L, dKuf, ld, 1, nullptr, 1.0, Kuf, ld, Xcol, Kc, E, ld, cs, nullptr, &ka));
+  DCGP_TRY(patch_backward(bk, L, E, ld, Kc, cs, Xcol, dXcol, 0, nullptr, nullptr, ka.rs, ka.cz));
   if (dXin) {
-    if (fuse_dx) {
-      DCGP_TRY(patch_adjoint_fused(ctx, L, E, ld, cs, Xin, rows, n_mod, nullptr, dXin));
-    } else {
-      const long n = (long)rows * L.v.H * L.v.W * L.v.C;
-      hipLaunchKernelGGL(col2im_kernel, dim3(blocks_for(n)), dim3(256), 0, ctx->stream, dXcol, rows, L.v.H, L.v.W, L.v.C, L.v.f, L.v.s, L.v.Ho,
-                         L.v.Wo, Ld, dXin);
-      LAUNCH_CHECK(ctx);
-    }
+    DCGP_TRY(patches_to_dx(bk, L, fuse_dx, E, ld, cs, Xin, rows, n_mod, nullptr, dXcol, dXin));
     if (L.identity_mean) {
       hipLaunchKernelGGL(idmean_backward_kernel, dim3(blocks_for(Kc)), dim3(256), 0, ctx->stream, gm, Kc, L.R, P, L.v.Wo, L.v.H, L.v.W, L.v.C,
                          L.v.f, L.v.s, dXin);
@@ -1398,9 +1314,8 @@ int dense_head_backward(Bk& bk, LayerState& L, const double* Xin, int rows, int 
   const long ld = col_ld(rows);
   if (L.v.P != 1 || L.kernel_type != 0) return ctx_fail(ctx, DCGP_ERR_ARG, "grad: ARD lengthscales need the single-patch head");
   DCGP_TRY(begin_layer(bk, L));
-  auto itB = ctx->ws.find(bk.pfx + "Kzx");
-  if (itB == ctx->ws.end()) return ctx_fail(ctx, DCGP_ERR_ARG, "grad: the forward pass left no K_zx for the head");
-  const double* Kzx = (const double*)itB->second.first;
+  const double* Kzx = forward_left(bk, "Kzx", 0, "K_zx for the head");
+  if (!Kzx) return DCGP_ERR_ARG;
   double* A1 = bk.ws("A1h", (size_t)Mp * ld);
   double* dKzx = bk.ws("dKzx", (size_t)Mp * ld);
   double* S = bk.ws("S", (size_t)Mp * Mp);
@@ -1416,31 +1331,30 @@ int dense_head_backward(Bk& bk, LayerState& L, const double* Xin, int rows, int 
   Lanes ln = lanes_of(ctx);
   ln.forked = false; ln.chain = ln.tail = ln.main;   // (a few hundred columns, one patch: everything in line on the main stream)
   DCGP_TRY(cond_backward_main(bk, ln, L, A1, ld, rows, gm, gv, dKzx, gkd, false));
+  if (!bk.data_only) {
+    DCGP_TRY(cond_backward_finish(bk, ln, L, A1, ld, rows, dKzx, S, bk.kl_early && !L.white, false));
+    if (!bk.kl_early) DCGP_TRY(kl_products(bk, L, L.white ? nullptr : S, false));
+    DCGP_TRY(kl_apply(bk, L, false));
+    DCGP_TRY(add_scalar(bk, L, 0, gkd, rows, 1.0));             // Kdiag = variance
+  }
+  hipLaunchKernelGGL(scale_rows_kernel, dim3(blocks_for((long)M * D)), dim3(256), 0, ctx->stream, L.Z, M, (long)M, D, L.in_scale, Zs);
+  LAUNCH_CHECK(ctx);
+  hipLaunchKernelGGL(scale_rows_kernel, dim3(blocks_for((long)rows * D)), dim3(256), 0, ctx->stream, Xin, n_mod, (long)rows, D, L.in_scale, Xs);
+  LAUNCH_CHECK(ctx);
+  if (!bk.data_only) {
+    HIP_TRY(ctx, hipMemsetAsync(dZs, 0, (size_t)M * D * sizeof(double), ctx->stream));
+    DCGP_TRY(kuu_backward(bk, L, Zs, S, Mp, true, dZs));
+  }
+  KufAdjoint ka;
+  DCGP_TRY(kuf_adjoint(bk, L, dKzx, ld, 1, nullptr, 1.0, Kzx, ld, Xs, rows, dKzx, ld, cs, nullptr, &ka));   // E over dKzx (P == 1: K_zx is the full response)
+  DCGP_TRY(patch_backward(bk, L, dKzx, ld, rows, cs, Xs, dXs, 0, Zs, dZs, ka.rs, ka.cz));
   if (bk.data_only) {   // x / l -> K_zx -> the conditional: dX = s o (E^T Zs - cs o Xs)
-    hipLaunchKernelGGL(scale_rows_kernel, dim3(blocks_for((long)M * D)), dim3(256), 0, ctx->stream, L.Z, M, (long)M, D, L.in_scale, Zs);
-    LAUNCH_CHECK(ctx);
-    hipLaunchKernelGGL(scale_rows_kernel, dim3(blocks_for((long)rows * D)), dim3(256), 0, ctx->stream, Xin, n_mod, (long)rows, D, L.in_scale, Xs);
-    LAUNCH_CHECK(ctx);
-    DCGP_TRY(e_form(bk, L, dKzx, ld, 1, nullptr, 1.0, Kzx, ld, dKzx, ld, rows, cs, nullptr));
-    DCGP_TRY(patch_backward(bk, L, dKzx, ld, rows, cs, Xs, dXs, 0, Zs, dZs));
     if (dXin) {
       hipLaunchKernelGGL(scale_rows_kernel, dim3(blocks_for((long)rows * D)), dim3(256), 0, ctx->stream, dXs, rows, (long)rows, D, L.in_scale, dXin);
       LAUNCH_CHECK(ctx);
     }
     return DCGP_OK;
   }
-  DCGP_TRY(cond_backward_finish(bk, ln, L, A1, ld, rows, dKzx, S, bk.kl_early && !L.white, false));
-  if (!bk.kl_early) DCGP_TRY(kl_products(bk, L, L.white ? nullptr : S, false));
-  DCGP_TRY(kl_apply(bk, L, false));
-  DCGP_TRY(add_scalar(bk, L, 0, gkd, rows, 1.0));             // Kdiag = variance
-  hipLaunchKernelGGL(scale_rows_kernel, dim3(blocks_for((long)M * D)), dim3(256), 0, ctx->stream, L.Z, M, (long)M, D, L.in_scale, Zs);
-  LAUNCH_CHECK(ctx);
-  hipLaunchKernelGGL(scale_rows_kernel, dim3(blocks_for((long)rows * D)), dim3(256), 0, ctx->stream, Xin, n_mod, (long)rows, D, L.in_scale, Xs);
-  LAUNCH_CHECK(ctx);
-  HIP_TRY(ctx, hipMemsetAsync(dZs, 0, (size_t)M * D * sizeof(double), ctx->stream));
-  DCGP_TRY(kuu_backward(bk, L, Zs, S, Mp, true, dZs));
-  DCGP_TRY(e_form(bk, L, dKzx, ld, 1, nullptr, 1.0, Kzx, ld, dKzx, ld, rows, cs, nullptr));   // E over dKzx (P == 1: K_zx is the full response)
-  DCGP_TRY(patch_backward(bk, L, dKzx, ld, rows, cs, Xs, dXs, 0, Zs, dZs));
   hipLaunchKernelGGL(ard_finish_kernel, dim3(D), dim3(256), 0, ctx->stream, dZs, Zs, M, dXs, Xs, (long)rows, D, L.in_scale, L.gZ, dXin, L.gard);
   LAUNCH_CHECK(ctx);
   DCGP_TRY(end_layer(bk, L));
@@ -1456,9 +1370,8 @@ int head_backward(Bk& bk, LayerState& L, const double* Xin, int rows, int n_mod,
   const long ld = col_ld(rows), Kc = (long)rows * P, ldf = col_ld(Kc);
   if (L.in_scale) return dense_head_backward(bk, L, Xin, rows, n_mod, gm, gv, dXin);
   DCGP_TRY(begin_layer(bk, L));
-  auto itB = ctx->ws.find(bk.pfx + "Kzx");
-  if (itB == ctx->ws.end()) return ctx_fail(ctx, DCGP_ERR_ARG, "grad: the forward pass left no K_zx for the head");
-  const double* Kzx = (const double*)itB->second.first;
+  const double* Kzx = forward_left(bk, "Kzx", 0, "K_zx for the head");
+  if (!Kzx) return DCGP_ERR_ARG;
   double* A1 = bk.ws("A1h", (size_t)Mp * ld);
   double* dKzx = bk.ws("dKzx", (size_t)Mp * ld);
   double* S = bk.ws("S", (size_t)Mp * Mp);
@@ -1494,14 +1407,15 @@ int head_backward(Bk& bk, LayerState& L, const double* Xin, int rows, int n_mod,
   }
   DCGP_TRY(im2col(ctx, L, Xin, n_mod, Kc, Xcol));
   // Kzx[m][n] = 1/P sum_p w_p k(Z_m, x_np)
-  DCGP_TRY(e_form(bk, L, dKzx, ld, P, L.w, 1.0 / P, Kfull, ldf, E, ldf, Kc, cs, raw));
+  KufAdjoint ka;
+  DCGP_TRY(kuf_adjoint(bk, L, dKzx, ld, P, L.w, 1.0 / P, Kfull, ldf, Xcol, Kc, E, ldf, cs, raw, &ka));
   if (!bk.data_only) {
     hipLaunchKernelGGL(strided_sum_kernel, dim3(P), dim3(256), 0, ctx->stream, raw, rows, P, 1.0 / P, 1, L.gw);
     LAUNCH_CHECK(ctx);
   }
   // (the input gradient's pass, see conv_backward: the K_zx part of dX comes from the fused launch below, ConvKernel's K_diag part rides in as `extra`)
   const bool fuse_dx = bk.data_only && dXin && patch_adjoint_fused_ok(L, rows);
-  DCGP_TRY(patch_backward(bk, L, E, ldf, Kc, cs, Xcol, dXin && !fuse_dx ? dXcol : nullptr, 0, nullptr, nullptr, nullptr, 0.0, &ln));
+  DCGP_TRY(patch_backward(bk, L, E, ldf, Kc, cs, Xcol, dXin && !fuse_dx ? dXcol : nullptr, 0, nullptr, nullptr, ka.rs, ka.cz, &ln));
   // Kdiag
   if (L.kernel_type == 0) {
     const double inv_l2 = 1.0 / (L.ls * L.ls);
@@ -1541,14 +1455,7 @@ int head_backward(Bk& bk, LayerState& L, const double* Xin, int rows, int n_mod,
     LAUNCH_CHECK(ctx);
     ++bk.slot_v;
   }
-  if (dXin && fuse_dx) {
-    DCGP_TRY(patch_adjoint_fused(ctx, L, E, ldf, cs, Xin, rows, n_mod, L.kernel_type == 0 ? dXcol : nullptr, dXin));
-  } else if (dXin) {
-    const long n = (long)rows * L.v.H * L.v.W * L.v.C;
-    hipLaunchKernelGGL(col2im_kernel, dim3(blocks_for(n)), dim3(256), 0, ctx->stream, dXcol, rows, L.v.H, L.v.W, L.v.C, L.v.f, L.v.s, L.v.Ho,
-                       L.v.Wo, Ld, dXin);
-    LAUNCH_CHECK(ctx);
-  }
+  if (dXin) DCGP_TRY(patches_to_dx(bk, L, fuse_dx, E, ldf, cs, Xin, rows, n_mod, L.kernel_type == 0 ? dXcol : nullptr, dXcol, dXin));
   if (bk.data_only) return DCGP_OK;
   // the main stream's part of the head ends here (dX is out): it goes on to the layer below (see conv_backward)
   if (ln.forked) HIP_TRY(ctx, hipEventRecord(ctx->ev_g[3], ctx->stream));
@@ -1787,8 +1694,6 @@ int model_backward_data(dcgp_model* m, const double* X, int N, int S, int dedup_
 
 // Adam step enqueued behind the reverse pass (dcgp_model_train_step_adam): lr is the bias-corrected rate
 struct AdamReq { double lr_t, beta1, beta2, eps; };
-static int opt_enqueue(dcgp_model* model, const char* who, bool sgd, double lr, double beta1, double beta2, double eps, const double* status, int vranks);
-static int opt_readback(dcgp_model* model);
 
 static int elbo_grad_run(dcgp_model* model, const double* X, const int32_t* y, int N, double scale, const double* const* z_per_layer_host,
                          uint64_t seed, int dedup_layer0, double* out_host, int* info_host, const AdamReq* adam, const double* yf = nullptr) {
@@ -1886,278 +1791,3 @@ int train_step_adam_run(dcgp_model* model, const double* X, const int32_t* y, in
   model->adam_t = t_use;
   return DCGP_OK;
 }
-
-extern "C" {
-
-int dcgp_model_get_grad(dcgp_model* model, int layer, const char* which, double* out_host, size_t count) {
-  if (!model || !which || !out_host) return DCGP_ERR_ARG;
-  dcgp_ctx* ctx = model->ctx;
-  if (!strcmp(which, "likelihood_variance")) {   // model-wide, `layer` is ignored: the last slot of the head's gradient block
-    const LayerState* H = model->has_head ? model->layers.back().get() : nullptr;
-    if (model->lik_kind != 1 || !H || !H->glik) return ctx_fail(ctx, DCGP_ERR_ARG, "get_grad(likelihood_variance): no Gaussian-likelihood gradient (dcgp_elbo_grad_f64y first)");
-    if (count != 1) return ctx_fail(ctx, DCGP_ERR_ARG, "get_grad(likelihood_variance): expected 1 value");
-    HIP_TRY(ctx, hipMemcpyAsync(out_host, H->glik, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return DCGP_OK;
-  }
-  if (!strcmp(which, "likelihood_scale")) {   // model-wide, `layer` is ignored: the last slot of the head's gradient block
-    const LayerState* H = model->has_head ? model->layers.back().get() : nullptr;
-    if (model->lik_kind != 4 || !H || !H->glik) return ctx_fail(ctx, DCGP_ERR_ARG, "get_grad(likelihood_scale): no StudentT-likelihood gradient (dcgp_elbo_grad_f64y first)");
-    if (count != 1) return ctx_fail(ctx, DCGP_ERR_ARG, "get_grad(likelihood_scale): expected 1 value");
-    HIP_TRY(ctx, hipMemcpyAsync(out_host, H->glik, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return DCGP_OK;
-  }
-  if (layer < 0 || layer >= (int)model->layers.size()) return ctx_fail(ctx, DCGP_ERR_ARG, "get_grad: no layer %d", layer);
-  LayerState& L = *model->layers[layer];
-  if (!L.gZ) return ctx_fail(ctx, DCGP_ERR_ARG, "get_grad: call dcgp_elbo_grad first");
-  const double* src = nullptr;
-  size_t n = 0;
-  if (!strcmp(which, "Z")) { src = L.gZ; n = (size_t)L.M * L.v.L; }
-  else if (!strcmp(which, "q_mu")) { src = L.gq_mu; n = (size_t)L.M * L.R; }
-  else if (!strcmp(which, "q_sqrt")) { src = L.gq_sqrt; n = (size_t)L.R * L.M * L.M; }
-  else if (!strcmp(which, "variance")) { src = L.gscal; n = 1; }
-  else if (!strcmp(which, "lengthscale") || !strcmp(which, "weight_variances")) { src = L.gscal + 1; n = 1; }
-  else if (!strcmp(which, "bias_variance")) { src = L.gscal + 2; n = 1; }
-  else if (!strcmp(which, "w")) {
-    if (!L.is_head) return ctx_fail(ctx, DCGP_ERR_ARG, "get_grad: only the head has patch weights");
-    src = L.gw; n = (size_t)L.v.P;
-  } else if (!strcmp(which, "ard_lengthscales")) {
-    if (!L.ard || !L.gard) return ctx_fail(ctx, DCGP_ERR_ARG, "get_grad: this layer has no ARD lengthscales");
-    src = L.gard; n = (size_t)L.v.L;
-  } else return ctx_fail(ctx, DCGP_ERR_ARG, "get_grad: unknown parameter '%s'", which);
-  if (count != n) return ctx_fail(ctx, DCGP_ERR_ARG, "get_grad(%s): expected %zu values, got %zu", which, n, count);
-  HIP_TRY(ctx, hipMemcpyAsync(out_host, src, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return DCGP_OK;
-}
-
-}  // extern "C"
-
-extern "C" {
-
-int dcgp_model_set_grad_shards(dcgp_model* model, int shards) {
-  if (!model || shards < 0) return DCGP_ERR_ARG;
-  model->grad_shards = shards;
-  return DCGP_OK;
-}
-
-int dcgp_model_grad_block(dcgp_model* model, int layer, double** block_dev, size_t* count) {
-  if (!model || !block_dev || !count) return DCGP_ERR_ARG;
-  if (layer < 0 || layer >= (int)model->layers.size()) return ctx_fail(model->ctx, DCGP_ERR_ARG, "grad_block: no layer %d", layer);
-  LayerState& L = *model->layers[layer];
-  DCGP_TRY(L.ensure_grads());
-  *block_dev = L.gZ;
-  *count = L.grad_block_count();
-  return DCGP_OK;
-}
-
-// one optimiser step over every trainable group of the model (sgd: plain ascent, otherwise Adam with the bias-corrected rate lr)
-static int opt_readback(dcgp_model* model);
-static int opt_enqueue(dcgp_model* model, const char* who, bool sgd, double lr, double beta1, double beta2, double eps, const double* status, int vranks);
-static int opt_step(dcgp_model* model, const char* who, bool sgd, double lr, double beta1, double beta2, double eps, int vranks = 0) {
-  DCGP_TRY(opt_enqueue(model, who, sgd, lr, beta1, beta2, eps, nullptr, vranks));
-  HIP_TRY(model->ctx, hipStreamSynchronize(model->ctx->stream));
-  return opt_readback(model);
-}
-// the launch alone, behind whatever the stream holds (status: see OptArgs).
-// vranks > 0 (debugging aid, dcgp_model_debug_sharded_adam): the sharded step of `vranks` ranks played on this one GPU from rank 0's point of
-// view -- its own shard for real, the others' into the staging block only, then the unstage pass.
-static int opt_enqueue(dcgp_model* model, const char* who, bool sgd, double lr, double beta1, double beta2, double eps, const double* status, int vranks = 0) {
-  dcgp_ctx* ctx = model->ctx;
-  const int nl = (int)model->layers.size();
-  if (nl > 8) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: at most 8 layers", who);
-  const bool comm_sharded = ctx->comm && ctx->nranks > 1 && model->grad_exchange == 1 && model->grad_scattered;
-  const bool sharded = comm_sharded || vranks > 0;
-  ++model->param_version;   // the parameters change: parameter-only state of earlier steps is not reused (model_state.h)
-  // Moments are rank-local in exchange mode 1: a rank holds m / v of its own shard only.  A full update on top of them (exchange mode 0, or an
-  // optimiser step behind dcgp_elbo_grad) would move every element outside the shard with stale or zero moments -- differently on every rank.
-  if (!sgd && !comm_sharded && vranks == 0 && model->sharded_steps > 0)
-    return ctx_fail(ctx, DCGP_ERR_ARG, "%s: %llu sharded Adam steps were taken on this model (exchange mode 1): its moments cover this rank's shard only, "
-                    "a full update would let the replicas diverge", who, (unsigned long long)model->sharded_steps);
-  if (comm_sharded && !sgd) ++model->sharded_steps;
-  const int nranks = vranks > 0 ? vranks : ctx->nranks, rank = vranks > 0 ? 0 : ctx->rank;
-  OptArgs a{};
-  a.sgd = sgd ? 1 : 0; a.lr = lr; a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.status = status;
-  a.sharded = sharded ? 1 : 0;
-  double* h = ctx->h_scratch;   // 64 pinned doubles: {variance, p1, p2} per layer
-  if (hipHostGetDevicePointer((void**)&a.host_out, h, 0) != hipSuccess) return ctx_fail(ctx, DCGP_ERR_HIP, "%s: pinned slot not mapped", who);
-  int nb = 0, cur_layer = 0;
-  const double* blk0 = nullptr;
-  auto add = [&](double* p, const double* g, double* const* mv, long n, int transform, int hyp_layer, double* recip, bool frozen) -> int {
-    if (n <= 0 || (frozen && !sharded)) return DCGP_OK;
-    if (a.ng >= OPT_GROUPS_MAX) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: too many parameter groups", who);
-    OptGroup& G = a.grp[a.ng];
-    G.p = p; G.g = g; G.m = mv[0]; G.v = mv[1]; G.recip = recip; G.n = n; G.transform = transform; G.hyp_layer = hyp_layer;
-    G.off = (long)(g - blk0); G.layer = cur_layer; G.frozen = frozen ? 1 : 0;
-    a.first_block[a.ng++] = nb;
-    nb += (int)blocks_for(n);
-    return DCGP_OK;
-  };
-  long shard[8] = {};
-  for (int li = 0; li < nl; ++li) {
-    LayerState& L = *model->layers[li];
-    if (!L.gZ) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: call dcgp_elbo_grad first", who);
-    DCGP_TRY(L.ensure_adam());   // (SGD: for the device copy of the hyper-parameters)
-    cur_layer = li; blk0 = L.gZ;
-    if (sharded) {
-      DCGP_TRY(L.ensure_stage());
-      if (nranks - 1 > (int)LayerState::kGradBlockPad) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: more ranks than the gradient block is padded for", who);
-      DCGP_TRY(dcgp_shard_range((long)L.grad_block_count(), nranks, rank, &a.sh_lo[li], &a.sh_hi[li], &shard[li]));
-      a.stage[li] = L.pstage;
-    }
-    a.hyp_in[li][0] = L.variance; a.hyp_in[li][1] = L.base_type == 1 ? L.acos_w : L.ls; a.hyp_in[li][2] = L.base_type == 1 ? L.acos_b : 1.0;
-    DCGP_TRY(add(L.Z, L.gZ, L.aZ, (long)L.M * L.v.L, 0, -1, nullptr, (L.frozen & 1u) != 0));
-    DCGP_TRY(add(L.q_mu, L.gq_mu, L.aq_mu, (long)L.M * L.R, 0, -1, nullptr, (L.frozen & 2u) != 0));
-    if (L.has_qsqrt) DCGP_TRY(add(L.q_sqrt, L.gq_sqrt, L.aq_sqrt, (long)L.R * L.M * L.M, 0, -1, nullptr, (L.frozen & 4u) != 0));   // upper triangle: zero gradient, zero step
-    if (L.is_head && L.w) DCGP_TRY(add(L.w, L.gw, L.aw, (long)L.v.P, 0, -1, nullptr, (L.frozen & 8u) != 0));
-    const int ng_hyp = a.ng;
-    DCGP_TRY(add(L.hyp, L.gscal, L.ahyp, 3, 1, li, nullptr, (L.frozen & 16u) != 0));
-    if (a.ng > ng_hyp) a.grp[ng_hyp].hold = (int)((L.frozen >> 5) & 3u) << 1;   // bits 32 / 64: elements 1 / 2 of the triple stay where they are
-    if (L.ard) DCGP_TRY(add(L.ard, L.gard, L.aard, (long)L.v.L, 1, -1, L.in_scale, (L.frozen & 16u) != 0));   // dense head: per-dimension lengthscales and the staging scale 1 / l
-    if (L.glik) {   // Gaussian likelihood variance / StudentT scale: the last slot of the head's block, moments beside it on the device
-      if (!model->d_lik) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: the head's block has a likelihood slot but the model no Gaussian likelihood", who);
-      double* lik_mv[2] = {model->d_lik + 1, model->d_lik + 2};
-      DCGP_TRY(add(model->d_lik, L.glik, lik_mv, 1, 1, -1, nullptr, model->lik_frozen));
-    }
-  }
-  a.first_block[a.ng] = nb;
-  if (nb <= 0) return DCGP_OK;
-  hipLaunchKernelGGL(opt_step_kernel, dim3(nb), dim3(256), 0, ctx->stream, a);
-  LAUNCH_CHECK(ctx);
-  if (!sharded) return DCGP_OK;
-  if (vranks > 0) {   // the other ranks' shards: into the staging block only
-    for (int r = 1; r < vranks; ++r) {
-      OptArgs b = a;
-      b.stage_only = 1;
-      for (int li = 0; li < nl; ++li) DCGP_TRY(dcgp_shard_range((long)model->layers[li]->grad_block_count(), vranks, r, &b.sh_lo[li], &b.sh_hi[li], nullptr));
-      hipLaunchKernelGGL(opt_step_kernel, dim3(nb), dim3(256), 0, ctx->stream, b);
-      LAUNCH_CHECK(ctx);
-    }
-  } else {
-    for (int li = 0; li < nl; ++li) DCGP_TRY(all_gather_f64_async(ctx, model->layers[li]->pstage, (size_t)shard[li]));
-  }
-  hipLaunchKernelGGL(opt_unstage_kernel, dim3(nb), dim3(256), 0, ctx->stream, a);
-  LAUNCH_CHECK(ctx);
-  return DCGP_OK;
-}
-// the updated kernel hyper-parameters back into the host-side layer state (the stream must have been synchronised)
-static int opt_readback(dcgp_model* model) {
-  const double* h = model->ctx->h_scratch;
-  const int nl = (int)model->layers.size();
-  for (int li = 0; li < nl; ++li) {
-    LayerState& L = *model->layers[li];
-    if (L.frozen & 16u) continue;
-    L.variance = h[3 * li];
-    if (L.base_type == 1) { L.acos_w = h[3 * li + 1]; L.acos_b = h[3 * li + 2]; } else L.ls = h[3 * li + 1];
-  }
-  return DCGP_OK;
-}
-
-int dcgp_model_adam_step(dcgp_model* model, double lr, double beta1, double beta2, double eps, int t) {
-  if (!model || t < 0 || !(lr > 0) || !(beta1 >= 0 && beta1 < 1) || !(beta2 >= 0 && beta2 < 1) || !(eps > 0))
-    return model ? ctx_fail(model->ctx, DCGP_ERR_ARG, "adam_step: bad arguments") : DCGP_ERR_ARG;
-  // t == 0: the model's own count of Adam steps since its moment buffers were created (they start at zero with it) --
-  // what tf.train.AdamOptimizer's beta powers do for a freshly built optimiser, whatever global_step a checkpoint carried
-  if (t == 0) t = ++model->adam_t; else model->adam_t = t;
-  const double lr_t = lr * sqrt(1.0 - pow(beta2, (double)t)) / (1.0 - pow(beta1, (double)t));
-  return opt_step(model, "adam_step", false, lr_t, beta1, beta2, eps);
-}
-
-// Multi-rank training step: how the ranks exchange a step's gradient (0: all-reduce, every rank updates everything; 1: reduce-scatter, each rank
-// updates its shard of every layer's parameter block, all-gather of the parameters -- SURVEY section 5).  Applies to dcgp_model_train_step_adam;
-// dcgp_elbo_grad alone always all-reduces (its caller wants the whole gradient).
-int dcgp_model_set_grad_exchange(dcgp_model* model, int mode) {
-  if (!model || (mode != 0 && mode != 1)) return model ? ctx_fail(model->ctx, DCGP_ERR_ARG, "set_grad_exchange: mode 0 or 1") : DCGP_ERR_ARG;
-  if (mode == 0 && model->grad_exchange == 1 && model->sharded_steps > 0)
-    return ctx_fail(model->ctx, DCGP_ERR_ARG, "set_grad_exchange: %llu sharded Adam steps were taken: the moments are rank-local (each rank holds its own shard's), "
-                    "the all-reduce route cannot continue from them", (unsigned long long)model->sharded_steps);
-  model->grad_exchange = mode;
-  return DCGP_OK;
-}
-// Debugging aid: one Adam step (dcgp_model_adam_step's arguments) taken the way `ranks` ranks would take it in exchange mode 1, played on this one
-// GPU from rank 0's point of view -- shard 0 updated in place, the other shards through the staging block and the unstage pass.  The gradient must be
-// the complete one (dcgp_elbo_grad).  Parameters and moments come out bit-identical to dcgp_model_adam_step's (tests/test_gpu_model.py).
-int dcgp_model_debug_sharded_adam(dcgp_model* model, int ranks, double lr, double beta1, double beta2, double eps, int t) {
-  if (!model || ranks < 1 || t < 0 || !(lr > 0) || !(beta1 >= 0 && beta1 < 1) || !(beta2 >= 0 && beta2 < 1) || !(eps > 0))
-    return model ? ctx_fail(model->ctx, DCGP_ERR_ARG, "debug_sharded_adam: bad arguments") : DCGP_ERR_ARG;
-  if (t == 0) t = ++model->adam_t; else model->adam_t = t;
-  const double lr_t = lr * sqrt(1.0 - pow(beta2, (double)t)) / (1.0 - pow(beta1, (double)t));
-  return opt_step(model, "debug_sharded_adam", false, lr_t, beta1, beta2, eps, ranks);
-}
-
-int dcgp_model_sgd_step(dcgp_model* model, double lr) {
-  if (!model || !(lr > 0)) return model ? ctx_fail(model->ctx, DCGP_ERR_ARG, "sgd_step: bad arguments") : DCGP_ERR_ARG;
-  return opt_step(model, "sgd_step", true, lr, 0.0, 0.0, 0.0);
-}
-
-int dcgp_model_set_trainable(dcgp_model* model, int layer, const char* which, int on) {
-  if (!model || !which) return DCGP_ERR_ARG;
-  if (!strcmp(which, "likelihood_variance")) {   // model-wide, `layer` is ignored
-    if (model->lik_kind != 1) return ctx_fail(model->ctx, DCGP_ERR_ARG, "set_trainable(likelihood_variance): not a Gaussian-likelihood model");
-    model->lik_frozen = !on;
-    return DCGP_OK;
-  }
-  if (!strcmp(which, "likelihood_scale")) {   // model-wide, `layer` is ignored
-    if (model->lik_kind != 4) return ctx_fail(model->ctx, DCGP_ERR_ARG, "set_trainable(likelihood_scale): not a StudentT-likelihood model");
-    model->lik_frozen = !on;
-    return DCGP_OK;
-  }
-  if (layer < 0 || layer >= (int)model->layers.size()) return ctx_fail(model->ctx, DCGP_ERR_ARG, "set_trainable: no layer %d", layer);
-  LayerState& L = *model->layers[layer];
-  unsigned bit = 0;
-  if (!strcmp(which, "Z")) bit = 1u;
-  else if (!strcmp(which, "q_mu")) bit = 2u;
-  else if (!strcmp(which, "q_sqrt")) bit = 4u;
-  else if (!strcmp(which, "w")) bit = 8u;
-  else if (!strcmp(which, "variance") || !strcmp(which, "lengthscale") || !strcmp(which, "hyper")) bit = 16u;
-  else if (L.base_type == 1 && !strcmp(which, "weight_variances")) bit = 32u;   // one ArcCosine parameter alone (the other and the variance go on moving)
-  else if (L.base_type == 1 && !strcmp(which, "bias_variance")) bit = 64u;
-  else return ctx_fail(model->ctx, DCGP_ERR_ARG, "set_trainable: unknown parameter '%s'", which);
-  if (on) L.frozen &= ~bit; else L.frozen |= bit;
-  return DCGP_OK;
-}
-
-int dcgp_model_get_param(dcgp_model* model, int layer, const char* which, double* out_host, size_t count) {
-  if (!model || !which || !out_host) return DCGP_ERR_ARG;
-  dcgp_ctx* ctx = model->ctx;
-  if (!strcmp(which, "likelihood_variance")) {   // model-wide, `layer` is ignored
-    if (model->lik_kind != 1) return ctx_fail(ctx, DCGP_ERR_ARG, "get_param(likelihood_variance): not a Gaussian-likelihood model");
-    if (count != 1) return ctx_fail(ctx, DCGP_ERR_ARG, "get_param(likelihood_variance): expected 1 value");
-    HIP_TRY(ctx, hipMemcpyAsync(out_host, model->d_lik, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return DCGP_OK;
-  }
-  if (!strcmp(which, "likelihood_scale")) {   // model-wide, `layer` is ignored
-    if (model->lik_kind != 4) return ctx_fail(ctx, DCGP_ERR_ARG, "get_param(likelihood_scale): not a StudentT-likelihood model");
-    if (count != 1) return ctx_fail(ctx, DCGP_ERR_ARG, "get_param(likelihood_scale): expected 1 value");
-    HIP_TRY(ctx, hipMemcpyAsync(out_host, model->d_lik, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return DCGP_OK;
-  }
-  if (layer < 0 || layer >= (int)model->layers.size()) return ctx_fail(ctx, DCGP_ERR_ARG, "get_param: no layer %d", layer);
-  LayerState& L = *model->layers[layer];
-  const double* src = nullptr;
-  size_t n = 0;
-  if (!strcmp(which, "variance") || !strcmp(which, "lengthscale") || !strcmp(which, "weight_variances") || !strcmp(which, "bias_variance")) {
-    if (count != 1) return ctx_fail(ctx, DCGP_ERR_ARG, "get_param(%s): expected 1 value", which);
-    out_host[0] = which[0] == 'v' ? L.variance : (which[0] == 'l' ? L.ls : (which[0] == 'w' ? L.acos_w : L.acos_b));
-    return DCGP_OK;
-  }
-  if (!strcmp(which, "Z")) { src = L.Z; n = (size_t)L.M * L.v.L; }
-  else if (!strcmp(which, "q_mu")) { src = L.q_mu; n = (size_t)L.M * L.R; }
-  else if (!strcmp(which, "q_sqrt")) { src = L.q_sqrt; n = (size_t)L.R * L.M * L.M; }
-  else if (!strcmp(which, "w")) {
-    if (!L.w) return ctx_fail(ctx, DCGP_ERR_ARG, "get_param: only the head has patch weights");
-    src = L.w; n = (size_t)L.v.P;
-  } else if (!strcmp(which, "ard_lengthscales")) {
-    if (!L.ard) return ctx_fail(ctx, DCGP_ERR_ARG, "get_param: this layer has no ARD lengthscales");
-    src = L.ard; n = (size_t)L.v.L;
-  } else return ctx_fail(ctx, DCGP_ERR_ARG, "get_param: unknown parameter '%s'", which);
-  if (count != n) return ctx_fail(ctx, DCGP_ERR_ARG, "get_param(%s): expected %zu values, got %zu", which, n, count);
-  HIP_TRY(ctx, hipMemcpyAsync(out_host, src, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return DCGP_OK;
-}
-
-}  // extern "C"

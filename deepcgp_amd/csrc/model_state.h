@@ -1,4 +1,4 @@
-// Internal: the device-resident model (layers + per-step outputs), shared by model.hip (forward) and grad.hip (backward).
+// Internal: the device-resident model (layers + per-step outputs), shared by model.hip (forward), grad.hip (backward) and optim.hip (update).
 #pragma once
 #include "layer_impl.h"
 
@@ -133,6 +133,11 @@ int elbo_forward_collect_impl(dcgp_model* model, uint64_t ticket, double* out_ho
 // grad.hip: reverse pass over the state the forward left behind; fills every layer's gradient buffers (the likelihood's seeds, the reverse walk over
 // the layers, the join of its side streams, the likelihood's own gradient and the collectives)
 int model_backward(dcgp_model* model, const Targets& targets, const double* X, int N, double scale, int dedup_layer0);
+// optim.hip: one optimiser launch over every trainable group of the model, behind whatever the stream holds (sgd: plain ascent, otherwise Adam with
+// the bias-corrected rate lr; status != null: a non-zero word there leaves every parameter untouched) / once the stream has been synchronised, the
+// updated kernel hyper-parameters back into the host-side layer state
+int opt_enqueue(dcgp_model* model, const char* who, bool sgd, double lr, double beta1, double beta2, double eps, const double* status, int vranks = 0);
+int opt_readback(dcgp_model* model);
 // enqueue == false: 1 if a training step's forward should hand the KL adjoint's products to the side stream, else 0;
 // enqueue == true: do it (wait_fork: behind ctx->ev_fork, recorded where the parameter-only chain ended)
 int grad_kl_early(dcgp_model* model, bool enqueue, bool wait_fork);

@@ -1,0 +1,368 @@
+// optim.hip -- the optimiser steps on the gradients the reverse pass (grad.hip) leaves in every layer's gradient block, and the C API that reads
+// parameters and gradients back or freezes them.  opt_enqueue / opt_readback are also what a training step (grad.hip: elbo_grad_run) ends on.
+#include "model_state.h"
+
+namespace {
+
+inline unsigned blocks_for(long n, int per = 256) { return (unsigned)((n + per - 1) / per); }
+
+// tf.train.AdamOptimizer / GradientDescentOptimizer on gpflow's unconstrained variables, ascending the ELBO.  transform 0: identity;
+// 1: gpflow transforms.positive (x = softplus(u) + 1e-6): the parameter is held constrained, moved through u.
+// ONE launch for every parameter group of every layer (a launch per group: ten 5 us launches and 2 x layers small copies on a 1.5 ms
+// step): block b works on group g with first_block[g] <= b < first_block[g + 1].  A layer's kernel hyper-parameters live on the host
+// (they are launch arguments of the forward pass): their current values arrive as arguments, the updated ones go to the device copy
+// and straight into a pinned host slot.
+struct OptGroup {
+  double* p; const double* g; double* m; double* v;   // parameter, gradient, Adam moments (unused by SGD)
+  double* recip;                                      // != null: 1 / p is kept here as well (the dense head's staging scale)
+  long n;
+  int transform, hyp_layer;                           // hyp_layer >= 0: p is that layer's {variance, p1, p2} triple
+  // sharded step (OptArgs::sharded): the group's offset in its layer's gradient block, the layer, and whether it only passes through
+  long off; int layer, frozen;
+  int hold;                                           // hyp_layer >= 0: bit i set = element i of the triple is held (set_trainable on one ArcCosine parameter)
+};
+constexpr int OPT_GROUPS_MAX = 48;
+struct OptArgs {
+  OptGroup grp[OPT_GROUPS_MAX];
+  int first_block[OPT_GROUPS_MAX + 1];
+  int ng, sgd;
+  double lr, b1, b2, eps;            // lr: Adam's bias-corrected step size, or the plain SGD rate
+  double hyp_in[8][3];
+  double* host_out;                  // [8][3] pinned
+  const double* status;              // != null: a non-zero word there (the step's factorisation failed) leaves every parameter untouched
+  // Sharded step (dcgp_model_set_grad_exchange 1): only the elements whose position in the layer's block lies in [sh_lo, sh_hi) are updated --
+  // the gradient there is this rank's reduce-scattered sum -- and every value of the range, updated or frozen, also goes to stage[layer]
+  // (the block's layout), which the all-gather then completes.  stage_only: the parameter arrays are left alone (the debug entry's other ranks).
+  int sharded, stage_only;
+  long sh_lo[8], sh_hi[8];
+  double* stage[8];
+};
+__global__ __launch_bounds__(256) void opt_step_kernel(OptArgs a) {
+  if (a.status && *a.status != 0.0) return;
+  int gi = 0;
+  while (gi + 1 < a.ng && (int)blockIdx.x >= a.first_block[gi + 1]) ++gi;
+  const OptGroup& G = a.grp[gi];
+  const long i = (long)((int)blockIdx.x - a.first_block[gi]) * 256 + threadIdx.x;
+  if (i >= G.n) return;
+  if (a.sharded && (G.off + i < a.sh_lo[G.layer] || G.off + i >= a.sh_hi[G.layer])) return;
+  const double x = G.hyp_layer >= 0 ? a.hyp_in[G.hyp_layer][i] : G.p[i];
+  double out;
+  if (G.frozen || (G.hyp_layer >= 0 && ((G.hold >> (int)i) & 1))) {
+    out = x;
+  } else if (a.sgd) {   // plain gradient ascent on the ELBO in the unconstrained space
+    const double gr = G.g[i];
+    if (G.transform == 1) {
+      const double y = x - 1e-6;
+      double u = y > 35.0 ? y : log(expm1(y));
+      u += a.lr * gr * -expm1(-y);
+      out = (u > 35.0 ? u : log1p(exp(u))) + 1e-6;
+    } else {
+      out = x + a.lr * gr;
+    }
+  } else {
+    double gr = -G.g[i];                               // minimise -ELBO
+    double u = x;
+    if (G.transform == 1) {
+      const double y = x - 1e-6;
+      u = y > 35.0 ? y : log(expm1(y));               // softplus^-1
+      gr *= -expm1(-y);                                // dx/du = sigmoid(u) = 1 - exp(-y)
+    }
+    const double mi = a.b1 * G.m[i] + (1.0 - a.b1) * gr;
+    const double vi = a.b2 * G.v[i] + (1.0 - a.b2) * gr * gr;
+    G.m[i] = mi;
+    G.v[i] = vi;
+    u -= a.lr * mi / (sqrt(vi) + a.eps);
+    out = G.transform == 1 ? (u > 35.0 ? u : log1p(exp(u))) + 1e-6 : u;
+  }
+  if (a.sharded) a.stage[G.layer][G.off + i] = out;
+  if (G.frozen || a.stage_only) return;
+  G.p[i] = out;
+  if (G.recip) G.recip[i] = 1.0 / out;
+  if (G.hyp_layer >= 0) a.host_out[3 * G.hyp_layer + i] = out;
+}
+// behind the all-gather: the other ranks' shards of the staged block into this rank's parameter arrays
+__global__ __launch_bounds__(256) void opt_unstage_kernel(OptArgs a) {
+  if (a.status && *a.status != 0.0) return;
+  int gi = 0;
+  while (gi + 1 < a.ng && (int)blockIdx.x >= a.first_block[gi + 1]) ++gi;
+  const OptGroup& G = a.grp[gi];
+  const long i = (long)((int)blockIdx.x - a.first_block[gi]) * 256 + threadIdx.x;
+  if (i >= G.n || G.frozen) return;
+  if (G.off + i >= a.sh_lo[G.layer] && G.off + i < a.sh_hi[G.layer]) return;   // this rank's own shard: already in place
+  const double out = a.stage[G.layer][G.off + i];
+  G.p[i] = out;
+  if (G.recip) G.recip[i] = 1.0 / out;
+  if (G.hyp_layer >= 0) a.host_out[3 * G.hyp_layer + i] = out;
+}
+
+}  // namespace
+
+// the launch alone, behind whatever the stream holds (status: see OptArgs).
+// vranks > 0 (debugging aid, dcgp_model_debug_sharded_adam): the sharded step of `vranks` ranks played on this one GPU from rank 0's point of
+// view -- its own shard for real, the others' into the staging block only, then the unstage pass.
+int opt_enqueue(dcgp_model* model, const char* who, bool sgd, double lr, double beta1, double beta2, double eps, const double* status, int vranks) {
+  dcgp_ctx* ctx = model->ctx;
+  const int nl = (int)model->layers.size();
+  if (nl > 8) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: at most 8 layers", who);
+  const bool comm_sharded = ctx->comm && ctx->nranks > 1 && model->grad_exchange == 1 && model->grad_scattered;
+  const bool sharded = comm_sharded || vranks > 0;
+  ++model->param_version;   // the parameters change: parameter-only state of earlier steps is not reused (model_state.h)
+  // Moments are rank-local in exchange mode 1: a rank holds m / v of its own shard only.  A full update on top of them (exchange mode 0, or an
+  // optimiser step behind dcgp_elbo_grad) would move every element outside the shard with stale or zero moments -- differently on every rank.
+  if (!sgd && !comm_sharded && vranks == 0 && model->sharded_steps > 0)
+    return ctx_fail(ctx, DCGP_ERR_ARG, "%s: %llu sharded Adam steps were taken on this model (exchange mode 1): its moments cover this rank's shard only, "
+                    "a full update would let the replicas diverge", who, (unsigned long long)model->sharded_steps);
+  if (comm_sharded && !sgd) ++model->sharded_steps;
+  const int nranks = vranks > 0 ? vranks : ctx->nranks, rank = vranks > 0 ? 0 : ctx->rank;
+  OptArgs a{};
+  a.sgd = sgd ? 1 : 0; a.lr = lr; a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.status = status;
+  a.sharded = sharded ? 1 : 0;
+  double* h = ctx->h_scratch;   // 64 pinned doubles: {variance, p1, p2} per layer
+  if (hipHostGetDevicePointer((void**)&a.host_out, h, 0) != hipSuccess) return ctx_fail(ctx, DCGP_ERR_HIP, "%s: pinned slot not mapped", who);
+  int nb = 0, cur_layer = 0;
+  const double* blk0 = nullptr;
+  auto add = [&](double* p, const double* g, double* const* mv, long n, int transform, int hyp_layer, double* recip, bool frozen) -> int {
+    if (n <= 0 || (frozen && !sharded)) return DCGP_OK;
+    if (a.ng >= OPT_GROUPS_MAX) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: too many parameter groups", who);
+    OptGroup& G = a.grp[a.ng];
+    G.p = p; G.g = g; G.m = mv[0]; G.v = mv[1]; G.recip = recip; G.n = n; G.transform = transform; G.hyp_layer = hyp_layer;
+    G.off = (long)(g - blk0); G.layer = cur_layer; G.frozen = frozen ? 1 : 0;
+    a.first_block[a.ng++] = nb;
+    nb += (int)blocks_for(n);
+    return DCGP_OK;
+  };
+  long shard[8] = {};
+  for (int li = 0; li < nl; ++li) {
+    LayerState& L = *model->layers[li];
+    if (!L.gZ) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: call dcgp_elbo_grad first", who);
+    DCGP_TRY(L.ensure_adam());   // (SGD: for the device copy of the hyper-parameters)
+    cur_layer = li; blk0 = L.gZ;
+    if (sharded) {
+      DCGP_TRY(L.ensure_stage());
+      if (nranks - 1 > (int)LayerState::kGradBlockPad) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: more ranks than the gradient block is padded for", who);
+      DCGP_TRY(dcgp_shard_range((long)L.grad_block_count(), nranks, rank, &a.sh_lo[li], &a.sh_hi[li], &shard[li]));
+      a.stage[li] = L.pstage;
+    }
+    a.hyp_in[li][0] = L.variance; a.hyp_in[li][1] = L.base_type == 1 ? L.acos_w : L.ls; a.hyp_in[li][2] = L.base_type == 1 ? L.acos_b : 1.0;
+    DCGP_TRY(add(L.Z, L.gZ, L.aZ, (long)L.M * L.v.L, 0, -1, nullptr, (L.frozen & 1u) != 0));
+    DCGP_TRY(add(L.q_mu, L.gq_mu, L.aq_mu, (long)L.M * L.R, 0, -1, nullptr, (L.frozen & 2u) != 0));
+    if (L.has_qsqrt) DCGP_TRY(add(L.q_sqrt, L.gq_sqrt, L.aq_sqrt, (long)L.R * L.M * L.M, 0, -1, nullptr, (L.frozen & 4u) != 0));   // upper triangle: zero gradient, zero step
+    if (L.is_head && L.w) DCGP_TRY(add(L.w, L.gw, L.aw, (long)L.v.P, 0, -1, nullptr, (L.frozen & 8u) != 0));
+    const int ng_hyp = a.ng;
+    DCGP_TRY(add(L.hyp, L.gscal, L.ahyp, 3, 1, li, nullptr, (L.frozen & 16u) != 0));
+    if (a.ng > ng_hyp) a.grp[ng_hyp].hold = (int)((L.frozen >> 5) & 3u) << 1;   // bits 32 / 64: elements 1 / 2 of the triple stay where they are
+    if (L.ard) DCGP_TRY(add(L.ard, L.gard, L.aard, (long)L.v.L, 1, -1, L.in_scale, (L.frozen & 16u) != 0));   // dense head: per-dimension lengthscales and the staging scale 1 / l
+    if (L.glik) {   // Gaussian likelihood variance / StudentT scale: the last slot of the head's block, moments beside it on the device
+      if (!model->d_lik) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: the head's block has a likelihood slot but the model no Gaussian likelihood", who);
+      double* lik_mv[2] = {model->d_lik + 1, model->d_lik + 2};
+      DCGP_TRY(add(model->d_lik, L.glik, lik_mv, 1, 1, -1, nullptr, model->lik_frozen));
+    }
+  }
+  a.first_block[a.ng] = nb;
+  if (nb <= 0) return DCGP_OK;
+  hipLaunchKernelGGL(opt_step_kernel, dim3(nb), dim3(256), 0, ctx->stream, a);
+  LAUNCH_CHECK(ctx);
+  if (!sharded) return DCGP_OK;
+  if (vranks > 0) {   // the other ranks' shards: into the staging block only
+    for (int r = 1; r < vranks; ++r) {
+      OptArgs b = a;
+      b.stage_only = 1;
+      for (int li = 0; li < nl; ++li) DCGP_TRY(dcgp_shard_range((long)model->layers[li]->grad_block_count(), vranks, r, &b.sh_lo[li], &b.sh_hi[li], nullptr));
+      hipLaunchKernelGGL(opt_step_kernel, dim3(nb), dim3(256), 0, ctx->stream, b);
+      LAUNCH_CHECK(ctx);
+    }
+  } else {
+    for (int li = 0; li < nl; ++li) DCGP_TRY(all_gather_f64_async(ctx, model->layers[li]->pstage, (size_t)shard[li]));
+  }
+  hipLaunchKernelGGL(opt_unstage_kernel, dim3(nb), dim3(256), 0, ctx->stream, a);
+  LAUNCH_CHECK(ctx);
+  return DCGP_OK;
+}
+// the updated kernel hyper-parameters back into the host-side layer state (the stream must have been synchronised)
+int opt_readback(dcgp_model* model) {
+  const double* h = model->ctx->h_scratch;
+  const int nl = (int)model->layers.size();
+  for (int li = 0; li < nl; ++li) {
+    LayerState& L = *model->layers[li];
+    if (L.frozen & 16u) continue;
+    L.variance = h[3 * li];
+    if (L.base_type == 1) { L.acos_w = h[3 * li + 1]; L.acos_b = h[3 * li + 2]; } else L.ls = h[3 * li + 1];
+  }
+  return DCGP_OK;
+}
+
+// one optimiser step over every trainable group of the model (sgd: plain ascent, otherwise Adam with the bias-corrected rate lr)
+static int opt_step(dcgp_model* model, const char* who, bool sgd, double lr, double beta1, double beta2, double eps, int vranks = 0) {
+  DCGP_TRY(opt_enqueue(model, who, sgd, lr, beta1, beta2, eps, nullptr, vranks));
+  HIP_TRY(model->ctx, hipStreamSynchronize(model->ctx->stream));
+  return opt_readback(model);
+}
+
+extern "C" {
+
+int dcgp_model_adam_step(dcgp_model* model, double lr, double beta1, double beta2, double eps, int t) {
+  if (!model || t < 0 || !(lr > 0) || !(beta1 >= 0 && beta1 < 1) || !(beta2 >= 0 && beta2 < 1) || !(eps > 0))
+    return model ? ctx_fail(model->ctx, DCGP_ERR_ARG, "adam_step: bad arguments") : DCGP_ERR_ARG;
+  // t == 0: the model's own count of Adam steps since its moment buffers were created (they start at zero with it) --
+  // what tf.train.AdamOptimizer's beta powers do for a freshly built optimiser, whatever global_step a checkpoint carried
+  if (t == 0) t = ++model->adam_t; else model->adam_t = t;
+  const double lr_t = lr * sqrt(1.0 - pow(beta2, (double)t)) / (1.0 - pow(beta1, (double)t));
+  return opt_step(model, "adam_step", false, lr_t, beta1, beta2, eps);
+}
+
+// Multi-rank training step: how the ranks exchange a step's gradient (0: all-reduce, every rank updates everything; 1: reduce-scatter, each rank
+// updates its shard of every layer's parameter block, all-gather of the parameters -- SURVEY section 5).  Applies to dcgp_model_train_step_adam;
+// dcgp_elbo_grad alone always all-reduces (its caller wants the whole gradient).
+int dcgp_model_set_grad_exchange(dcgp_model* model, int mode) {
+  if (!model || (mode != 0 && mode != 1)) return model ? ctx_fail(model->ctx, DCGP_ERR_ARG, "set_grad_exchange: mode 0 or 1") : DCGP_ERR_ARG;
+  if (mode == 0 && model->grad_exchange == 1 && model->sharded_steps > 0)
+    return ctx_fail(model->ctx, DCGP_ERR_ARG, "set_grad_exchange: %llu sharded Adam steps were taken: the moments are rank-local (each rank holds its own shard's), "
+                    "the all-reduce route cannot continue from them", (unsigned long long)model->sharded_steps);
+  model->grad_exchange = mode;
+  return DCGP_OK;
+}
+// Debugging aid: one Adam step (dcgp_model_adam_step's arguments) taken the way `ranks` ranks would take it in exchange mode 1, played on this one
+// GPU from rank 0's point of view -- shard 0 updated in place, the other shards through the staging block and the unstage pass.  The gradient must be
+// the complete one (dcgp_elbo_grad).  Parameters and moments come out bit-identical to dcgp_model_adam_step's (tests/test_gpu_model.py).
+int dcgp_model_debug_sharded_adam(dcgp_model* model, int ranks, double lr, double beta1, double beta2, double eps, int t) {
+  if (!model || ranks < 1 || t < 0 || !(lr > 0) || !(beta1 >= 0 && beta1 < 1) || !(beta2 >= 0 && beta2 < 1) || !(eps > 0))
+    return model ? ctx_fail(model->ctx, DCGP_ERR_ARG, "debug_sharded_adam: bad arguments") : DCGP_ERR_ARG;
+  if (t == 0) t = ++model->adam_t; else model->adam_t = t;
+  const double lr_t = lr * sqrt(1.0 - pow(beta2, (double)t)) / (1.0 - pow(beta1, (double)t));
+  return opt_step(model, "debug_sharded_adam", false, lr_t, beta1, beta2, eps, ranks);
+}
+
+int dcgp_model_sgd_step(dcgp_model* model, double lr) {
+  if (!model || !(lr > 0)) return model ? ctx_fail(model->ctx, DCGP_ERR_ARG, "sgd_step: bad arguments") : DCGP_ERR_ARG;
+  return opt_step(model, "sgd_step", true, lr, 0.0, 0.0, 0.0);
+}
+
+int dcgp_model_set_trainable(dcgp_model* model, int layer, const char* which, int on) {
+  if (!model || !which) return DCGP_ERR_ARG;
+  if (!strcmp(which, "likelihood_variance")) {   // model-wide, `layer` is ignored
+    if (model->lik_kind != 1) return ctx_fail(model->ctx, DCGP_ERR_ARG, "set_trainable(likelihood_variance): not a Gaussian-likelihood model");
+    model->lik_frozen = !on;
+    return DCGP_OK;
+  }
+  if (!strcmp(which, "likelihood_scale")) {   // model-wide, `layer` is ignored
+    if (model->lik_kind != 4) return ctx_fail(model->ctx, DCGP_ERR_ARG, "set_trainable(likelihood_scale): not a StudentT-likelihood model");
+    model->lik_frozen = !on;
+    return DCGP_OK;
+  }
+  if (layer < 0 || layer >= (int)model->layers.size()) return ctx_fail(model->ctx, DCGP_ERR_ARG, "set_trainable: no layer %d", layer);
+  LayerState& L = *model->layers[layer];
+  unsigned bit = 0;
+  if (!strcmp(which, "Z")) bit = 1u;
+  else if (!strcmp(which, "q_mu")) bit = 2u;
+  else if (!strcmp(which, "q_sqrt")) bit = 4u;
+  else if (!strcmp(which, "w")) bit = 8u;
+  else if (!strcmp(which, "variance") || !strcmp(which, "lengthscale") || !strcmp(which, "hyper")) bit = 16u;
+  else if (L.base_type == 1 && !strcmp(which, "weight_variances")) bit = 32u;   // one ArcCosine parameter alone (the other and the variance go on moving)
+  else if (L.base_type == 1 && !strcmp(which, "bias_variance")) bit = 64u;
+  else return ctx_fail(model->ctx, DCGP_ERR_ARG, "set_trainable: unknown parameter '%s'", which);
+  if (on) L.frozen &= ~bit; else L.frozen |= bit;
+  return DCGP_OK;
+}
+
+int dcgp_model_get_param(dcgp_model* model, int layer, const char* which, double* out_host, size_t count) {
+  if (!model || !which || !out_host) return DCGP_ERR_ARG;
+  dcgp_ctx* ctx = model->ctx;
+  if (!strcmp(which, "likelihood_variance")) {   // model-wide, `layer` is ignored
+    if (model->lik_kind != 1) return ctx_fail(ctx, DCGP_ERR_ARG, "get_param(likelihood_variance): not a Gaussian-likelihood model");
+    if (count != 1) return ctx_fail(ctx, DCGP_ERR_ARG, "get_param(likelihood_variance): expected 1 value");
+    HIP_TRY(ctx, hipMemcpyAsync(out_host, model->d_lik, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return DCGP_OK;
+  }
+  if (!strcmp(which, "likelihood_scale")) {   // model-wide, `layer` is ignored
+    if (model->lik_kind != 4) return ctx_fail(ctx, DCGP_ERR_ARG, "get_param(likelihood_scale): not a StudentT-likelihood model");
+    if (count != 1) return ctx_fail(ctx, DCGP_ERR_ARG, "get_param(likelihood_scale): expected 1 value");
+    HIP_TRY(ctx, hipMemcpyAsync(out_host, model->d_lik, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return DCGP_OK;
+  }
+  if (layer < 0 || layer >= (int)model->layers.size()) return ctx_fail(ctx, DCGP_ERR_ARG, "get_param: no layer %d", layer);
+  LayerState& L = *model->layers[layer];
+  const double* src = nullptr;
+  size_t n = 0;
+  if (!strcmp(which, "variance") || !strcmp(which, "lengthscale") || !strcmp(which, "weight_variances") || !strcmp(which, "bias_variance")) {
+    if (count != 1) return ctx_fail(ctx, DCGP_ERR_ARG, "get_param(%s): expected 1 value", which);
+    out_host[0] = which[0] == 'v' ? L.variance : (which[0] == 'l' ? L.ls : (which[0] == 'w' ? L.acos_w : L.acos_b));
+    return DCGP_OK;
+  }
+  if (!strcmp(which, "Z")) { src = L.Z; n = (size_t)L.M * L.v.L; }
+  else if (!strcmp(which, "q_mu")) { src = L.q_mu; n = (size_t)L.M * L.R; }
+  else if (!strcmp(which, "q_sqrt")) { src = L.q_sqrt; n = (size_t)L.R * L.M * L.M; }
+  else if (!strcmp(which, "w")) {
+    if (!L.w) return ctx_fail(ctx, DCGP_ERR_ARG, "get_param: only the head has patch weights");
+    src = L.w; n = (size_t)L.v.P;
+  } else if (!strcmp(which, "ard_lengthscales")) {
+    if (!L.ard) return ctx_fail(ctx, DCGP_ERR_ARG, "get_param: this layer has no ARD lengthscales");
+    src = L.ard; n = (size_t)L.v.L;
+  } else return ctx_fail(ctx, DCGP_ERR_ARG, "get_param: unknown parameter '%s'", which);
+  if (count != n) return ctx_fail(ctx, DCGP_ERR_ARG, "get_param(%s): expected %zu values, got %zu", which, n, count);
+  HIP_TRY(ctx, hipMemcpyAsync(out_host, src, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return DCGP_OK;
+}
+
+int dcgp_model_get_grad(dcgp_model* model, int layer, const char* which, double* out_host, size_t count) {
+  if (!model || !which || !out_host) return DCGP_ERR_ARG;
+  dcgp_ctx* ctx = model->ctx;
+  if (!strcmp(which, "likelihood_variance")) {   // model-wide, `layer` is ignored: the last slot of the head's gradient block
+    const LayerState* H = model->has_head ? model->layers.back().get() : nullptr;
+    if (model->lik_kind != 1 || !H || !H->glik) return ctx_fail(ctx, DCGP_ERR_ARG, "get_grad(likelihood_variance): no Gaussian-likelihood gradient (dcgp_elbo_grad_f64y first)");
+    if (count != 1) return ctx_fail(ctx, DCGP_ERR_ARG, "get_grad(likelihood_variance): expected 1 value");
+    HIP_TRY(ctx, hipMemcpyAsync(out_host, H->glik, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return DCGP_OK;
+  }
+  if (!strcmp(which, "likelihood_scale")) {   // model-wide, `layer` is ignored: the last slot of the head's gradient block
+    const LayerState* H = model->has_head ? model->layers.back().get() : nullptr;
+    if (model->lik_kind != 4 || !H || !H->glik) return ctx_fail(ctx, DCGP_ERR_ARG, "get_grad(likelihood_scale): no StudentT-likelihood gradient (dcgp_elbo_grad_f64y first)");
+    if (count != 1) return ctx_fail(ctx, DCGP_ERR_ARG, "get_grad(likelihood_scale): expected 1 value");
+    HIP_TRY(ctx, hipMemcpyAsync(out_host, H->glik, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return DCGP_OK;
+  }
+  if (layer < 0 || layer >= (int)model->layers.size()) return ctx_fail(ctx, DCGP_ERR_ARG, "get_grad: no layer %d", layer);
+  LayerState& L = *model->layers[layer];
+  if (!L.gZ) return ctx_fail(ctx, DCGP_ERR_ARG, "get_grad: call dcgp_elbo_grad first");
+  const double* src = nullptr;
+  size_t n = 0;
+  if (!strcmp(which, "Z")) { src = L.gZ; n = (size_t)L.M * L.v.L; }
+  else if (!strcmp(which, "q_mu")) { src = L.gq_mu; n = (size_t)L.M * L.R; }
+  else if (!strcmp(which, "q_sqrt")) { src = L.gq_sqrt; n = (size_t)L.R * L.M * L.M; }
+  else if (!strcmp(which, "variance")) { src = L.gscal; n = 1; }
+  else if (!strcmp(which, "lengthscale") || !strcmp(which, "weight_variances")) { src = L.gscal + 1; n = 1; }
+  else if (!strcmp(which, "bias_variance")) { src = L.gscal + 2; n = 1; }
+  else if (!strcmp(which, "w")) {
+    if (!L.is_head) return ctx_fail(ctx, DCGP_ERR_ARG, "get_grad: only the head has patch weights");
+    src = L.gw; n = (size_t)L.v.P;
+  } else if (!strcmp(which, "ard_lengthscales")) {
+    if (!L.ard || !L.gard) return ctx_fail(ctx, DCGP_ERR_ARG, "get_grad: this layer has no ARD lengthscales");
+    src = L.gard; n = (size_t)L.v.L;
+  } else return ctx_fail(ctx, DCGP_ERR_ARG, "get_grad: unknown parameter '%s'", which);
+  if (count != n) return ctx_fail(ctx, DCGP_ERR_ARG, "get_grad(%s): expected %zu values, got %zu", which, n, count);
+  HIP_TRY(ctx, hipMemcpyAsync(out_host, src, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return DCGP_OK;
+}
+
+int dcgp_model_set_grad_shards(dcgp_model* model, int shards) {
+  if (!model || shards < 0) return DCGP_ERR_ARG;
+  model->grad_shards = shards;
+  return DCGP_OK;
+}
+
+int dcgp_model_grad_block(dcgp_model* model, int layer, double** block_dev, size_t* count) {
+  if (!model || !block_dev || !count) return DCGP_ERR_ARG;
+  if (layer < 0 || layer >= (int)model->layers.size()) return ctx_fail(model->ctx, DCGP_ERR_ARG, "grad_block: no layer %d", layer);
+  LayerState& L = *model->layers[layer];
+  DCGP_TRY(L.ensure_grads());
+  *block_dev = L.gZ;
+  *count = L.grad_block_count();
+  return DCGP_OK;
+}
+
+}  // extern "C"

@@ -47,7 +47,7 @@ def grad_shard_range(n, world, rank):
 
 def adam_update(p, g, m, v, lr_t, beta1=0.9, beta2=0.999, eps=1e-8):
     """tf.train.AdamOptimizer's update of plain (untransformed) values ASCENDING the objective whose gradient is g, in place on (p, m, v):
-    the arithmetic of opt_step_kernel (csrc/grad.hip) for transform-0 groups, for the host-side mirror of the sharded step."""
+    the arithmetic of opt_step_kernel (csrc/optim.hip) for transform-0 groups, for the host-side mirror of the sharded step."""
     gr = -g
     m *= beta1; m += (1.0 - beta1) * gr
     v *= beta2; v += (1.0 - beta2) * gr * gr

@@ -51,6 +51,7 @@ CASES_M256 = {
     "mnist3_M72": dict(_MNIST, convs=_MNIST3, M=72, N=3, c=1.0, a=0.1),
     "small3_M20": dict(hwc=(14, 14, 1), convs=_SMALL3, head=(3, 1), M=20, N=3, c=1.0, a=0.1),
     "small3_white_M20": dict(hwc=(14, 14, 1), convs=_SMALL3, head=(3, 1), M=20, N=3, c=1.0, a=0.1, white=True),
+    "small3_M12": dict(hwc=(12, 12, 1), convs=_SMALL3, head=(3, 1), M=12, N=4, c=1.0, a=0.1),     # M <= 16: one row chunk in the K_uf adjoint
     "odd_M33": dict(hwc=(13, 13, 2), convs=[(4, 3, 13)], head=(2, 1), M=33, N=5, c=1.0, a=0.1),
     "additive_M24": dict(hwc=(12, 12, 1), convs=[(3, 1, 3)], head=(3, 1), M=24, N=3, c=1.0, a=0.1, additive=True),
     "dense_ard_M24": dict(hwc=(12, 12, 1), convs=[(3, 1, 3)], head=(3, 1), M=24, N=3, c=1.0, a=0.1, head_kernel="rbf"),

@@ -23,12 +23,14 @@ below the entry floor).  S = 2 except the two ch cases, S = 4 (15 x 4 x 144 = 86
     mnist3_M72        72   3   1.0  0.1   9.3e-01 (L0 Z)             4.6e-04 (L2 Z)       0.025 (L1)
     small3_M20        20   3   1.0  0.1   1.9e+00 (L2 variance)      1.9e-02 (L1 Z)       0.000 (L0)
     small3_white_M20  20   3   1.0  0.1   2.0e-03 (L0 lengthscales)  4.3e-02 (L2 q_mu)    0.001 (L2)
+    small3_M12        12   4   1.0  0.1   6.3e+00 (L2 variance)      1.3e-03 (L2 Z)       0.001 (L2)
     odd_M33           33   5   1.0  0.1   7.6e+01 (L0 variance)      1.0e-02 (L1 Z)       0.002 (L1)
     additive_M24      24   3   1.0  0.1   1.2e+01 (L0 variance)      1.4e-02 (L1 q_mu)    0.002 (L1)
     dense_ard_M24     24   3   1.0  0.1   1.2e+01 (L0 variance)      5.9e-03 (L1 Z)       0.001 (L1)
     conv2d_mean_M24   24   3   1.0  0.1   1.2e+01 (L1 variance)      2.2e-02 (L1 q_mu)    0.002 (L1)
 
-The last three are the model variants the textbook forward supports (12 x 12 x 1 images, conv (3, 1, 3), head (3, 1)): the additive head,
+small3_M12 (12 x 12 x 1 images, small3's layers) is the case at M <= 16: the K_uf adjoint (csrc/grad.hip, kuf_adjoint) then runs on one row chunk
+and writes its column sums without the second launch.  The last three are the model variants the textbook forward supports (12 x 12 x 1 images, conv (3, 1, 3), head (3, 1)): the additive head,
 the dense RBF(ARD) head, Conv2dMean.  The arc-cosine base kernel has this module's scheme in tests/test_gpu_acos.py, at non-unit variance,
 weight_variances and bias_variance: its reference (tests/acos_ref.py) has leaves for all three and writes K_uu's diagonal as the closed
 form of the variance alone, so autograd never differentiates acos at the coincident points (slope 2e7 at 1 - 1e-15).
@@ -40,6 +42,7 @@ Largest error over the groups of a case, group-wise (|a - b|max / |want|max) / e
     ch_M256 2.6e-11 / 5.3e-7      ch_M200 2.0e-11 / 2.2e-8      ch_white_M256 2.4e-11 / 2.9e-8    h_M256 2.9e-11 / 1.8e-8
     mnist3_M256 5.9e-10 / 3.3e-7  mnist3_M72 7.7e-11 / 6.2e-9   small3_M20 3.5e-13 / 3.4e-10      small3_white_M20 1.0e-11 / 3.8e-11
     odd_M33 2.6e-12 / 7.4e-9      additive_M24 4.0e-12 / 3.5e-9 dense_ard_M24 1.1e-12 / 6.2e-10   conv2d_mean_M24 4.9e-12 / 4.2e-10
+    small3_M12 4.8e-12 / 5.4e-9
 
 TOL_E = ten times the largest entry-wise floor = 5.3e-6, inside the 1e-5 it may not exceed (no case needed its c moved).
 
@@ -48,6 +51,7 @@ Largest device-vs-autograd error seen per case on an MI355X, over all the routes
     ch_M256 3.1e-11 / 3.3e-7      ch_M200 8.6e-12 / 4.1e-8      ch_white_M256 1.3e-12 / 1.8e-8    h_M256 2.7e-11 / 7.3e-9
     mnist3_M256 3.1e-9 / 1.8e-7   mnist3_M72 2.0e-11 / 5.4e-9   small3_M20 5.1e-13 / 2.9e-11      small3_white_M20 3.3e-11 / 3.3e-11
     odd_M33 6.2e-12 / 6.4e-9      additive_M24 1.1e-11 / 2.9e-9 dense_ard_M24 1.4e-12 / 3.0e-10   conv2d_mean_M24 5.3e-12 / 2.6e-10
+    small3_M12 4.3e-12 / 4.0e-9
 """
 import copy
 import functools
