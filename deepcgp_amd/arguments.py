@@ -33,6 +33,8 @@ FLAGS = (
     ("--likelihood", str, "robustmax", "multi-class likelihood: robustmax | softmax"),
     ("--gamma", float, 0.001, "NatGrad step size"),
     ("--identity-mean", None, False, "Conv2dMean identity mean function on the conv layers"),
+    ("--mean-filter", str, "centre0", "initial filter of the conv layers' mean function (needs --identity-mean): centre0 (Conv2dMean's: channel 0 into map 0) | channels (every channel into its own map) | sum (every channel into every map)"),
+    ("--train-mean", None, False, "train the mean function's filter with the other parameters (needs --identity-mean)"),
     ("--load-model", str, None, "checkpoint (.npy, reference key set) to start from"),
 )
 REQUIRED = ("--name",)

@@ -1202,7 +1202,7 @@ int layer_fills(Bk& bk, LayerState& L) {
     return DCGP_OK;
   }
   HIP_TRY(bk.ctx, hipMemsetAsync(L.gZ, 0, (size_t)L.M * L.v.L * sizeof(double), bk.ctx->stream));
-  HIP_TRY(bk.ctx, hipMemsetAsync(L.gw, 0, ((size_t)L.v.P + 3 + (L.is_head ? (size_t)L.v.L : 0) + L.lik_slots) * sizeof(double), bk.ctx->stream));   // gw, gscal, gard, glik
+  HIP_TRY(bk.ctx, hipMemsetAsync(L.gw, 0, ((size_t)L.v.P + 3 + (L.is_head ? (size_t)L.v.L : 0) + L.lik_slots + L.mean_slots()) * sizeof(double), bk.ctx->stream));   // gw, gscal, gard, glik, gmean_W
   if (!L.has_qsqrt) HIP_TRY(bk.ctx, hipMemsetAsync(L.gq_sqrt, 0, (size_t)L.R * L.M * L.M * sizeof(double), bk.ctx->stream));
   return DCGP_OK;
 }
@@ -1296,8 +1296,11 @@ int conv_backward(Bk& bk, LayerState& L, const double* Xin, int rows, int n_mod,
                          L.v.f, L.v.s, dXin);
       LAUNCH_CHECK(ctx);
     }
+    if (L.mean_W) DCGP_TRY(conv_mean_backward_dx(ctx, L, gm, rows, dXin));   // the filter mean's adjoint (conv_mean.hip): gm is d / d mean, as the oracle uses it
   }
   if (bk.data_only) return DCGP_OK;
+  // the filter's own gradient from the patches the pass holds (a frozen filter keeps the zero of the block's fill)
+  if (L.mean_W && L.mean_trainable) DCGP_TRY(conv_mean_backward_filter(ctx, L, Xcol, gm, Kc, L.gmean_W));
   // The main stream's part of this layer ends here (dX is out): it goes straight on to the layer below.
   if (ln.forked) HIP_TRY(ctx, hipEventRecord(ctx->ev_g[3], ctx->stream));
   DCGP_TRY(cond_backward_finish(bk, ln, L, A1, ld, Kc, dKuf, S, false, bk.last_layer && ln.forked));

@@ -12,6 +12,12 @@ int additive_kdiag_async(dcgp_ctx* ctx, int N, int P, double variance, const dou
 int reparam_async(dcgp_ctx* ctx, const double* mean, const double* var, const double* z, size_t n, double jitter,
                   double* out);
 int allreduce_sum_f64_async(dcgp_ctx* ctx, double* buf_dev, int n);
+struct LayerState;
+// conv_mean.hip: the linear convolutional mean of a conv layer (LayerState::mean_W) added to its outputs / its adjoints
+int conv_mean_add(dcgp_ctx* ctx, const LayerState& L, const double* X, int n_mod, long col0, long Kc, int rep, long rep_stride, double* out_mean,
+                  double* out_sample);
+int conv_mean_backward_dx(dcgp_ctx* ctx, const LayerState& L, const double* gm, int rows, double* dXin);
+int conv_mean_backward_filter(dcgp_ctx* ctx, const LayerState& L, const double* Xcol, const double* gm, long Kc, double* gW);
 
 struct LayerState {
   dcgp_ctx* ctx = nullptr;
@@ -54,6 +60,11 @@ struct LayerState {
   double *aZ[2] = {}, *aq_mu[2] = {}, *aq_sqrt[2] = {}, *aw[2] = {}, *ahyp[2] = {}, *hyp = nullptr;
   // optimiser: parameters excluded from dcgp_model_adam_step / dcgp_model_sgd_step (bit 0 Z, 1 q_mu, 2 q_sqrt, 3 w, 4 hyper-parameters)
   unsigned frozen = 0;
+  // linear convolutional mean function (conv layers; dcgp_model_set_mean_filter, conv_mean.hip): the filter W [L][R] (nullptr: none), its gradient
+  // at the very end of the layer's gradient block, its Adam moments, and whether the optimiser steps move it
+  double *mean_W = nullptr, *gmean_W = nullptr, *amean_W[2] = {};
+  bool mean_trainable = false;
+  size_t mean_slots() const { return mean_W ? (size_t)v.L * R : 0; }
   std::shared_ptr<void> natgrad_state;   // scratch of dcgp_model_natgrad_step (natgrad.hip), created on first use
   std::vector<void*> owned;
 
@@ -127,7 +138,7 @@ struct LayerState {
   // head of a Gaussian-likelihood model: one more slot at the very end of the block, d ELBO / d likelihood variance (glik)
   int lik_slots = 0;
   double* glik = nullptr;
-  size_t grad_block_count() const { return (size_t)M * v.L + (size_t)M * R + (size_t)R * M * M + (size_t)v.P + 3 + (is_head ? (size_t)v.L : 0) + (size_t)lik_slots; }
+  size_t grad_block_count() const { return (size_t)M * v.L + (size_t)M * R + (size_t)R * M * M + (size_t)v.P + 3 + (is_head ? (size_t)v.L : 0) + (size_t)lik_slots + mean_slots(); }
   int ensure_grads() {
     if (gZ) return DCGP_OK;
     double* blk = dalloc(grad_block_count() + kGradBlockPad);   // (padding: the sharded exchange rounds the block up to ranks x shard)
@@ -136,6 +147,7 @@ struct LayerState {
     gZ = blk; gq_mu = gZ + (size_t)M * v.L; gq_sqrt = gq_mu + (size_t)M * R; gw = gq_sqrt + (size_t)R * M * M; gscal = gw + v.P;
     gard = is_head ? gscal + 3 : nullptr;   // [L] d / d ARD lengthscales (dense head), zero otherwise
     glik = lik_slots ? gscal + 3 + (is_head ? v.L : 0) : nullptr;
+    gmean_W = mean_W ? gscal + 3 + (is_head ? v.L : 0) + lik_slots : nullptr;
     return DCGP_OK;
   }
   int ensure_adam() {
@@ -152,6 +164,11 @@ struct LayerState {
     }
     hyp = dalloc(3);
     if (!hyp) return ctx_fail(ctx, DCGP_ERR_ALLOC, "layer: optimiser state allocation failed");
+    if (mean_W)
+      for (int k = 0; k < 2; ++k) {
+        if (!(amean_W[k] = dalloc(mean_slots()))) return ctx_fail(ctx, DCGP_ERR_ALLOC, "layer: optimiser state allocation failed");
+        HIP_TRY(ctx, hipMemsetAsync(amean_W[k], 0, mean_slots() * sizeof(double), ctx->stream));
+      }
     if (ard)
       for (int k = 0; k < 2; ++k) {
         if (!(aard[k] = dalloc(v.L))) return ctx_fail(ctx, DCGP_ERR_ALLOC, "layer: optimiser state allocation failed");
@@ -339,7 +356,11 @@ static inline int conv_forward(dcgp_ctx* ctx, LayerState& L, const double* X, in
       if (prep_done) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, prep_done, 0));
       else if (factor_done) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, factor_done, 0));
       if (ride_head) { fa.head = *ride_head; fa.head_n = ride_rows; }
-      return conv_fused(ctx, fa);
+      if (!L.mean_W) return conv_fused(ctx, fa);
+      // a filter mean completes mean and sample in a pass behind the launch: rows of the head may not have read the sample inside it (model.hip: plan_step)
+      if (ride_head && ride_rows > 0) return ctx_fail(ctx, DCGP_ERR_ARG, "conv layer: a layer with a mean filter cannot carry the head's rows");
+      DCGP_TRY(conv_fused(ctx, fa));
+      return conv_mean_add(ctx, L, X, n_mod, 0, Kc, rep, rep_stride, out_mean, out_sample);
     }
     if (ride_head) return ctx_fail(ctx, DCGP_ERR_ARG, "conv layer: the step was planned to carry the head's rows in a launch the layer does not take");
   }
@@ -404,6 +425,7 @@ static inline int conv_forward(dcgp_ctx* ctx, LayerState& L, const double* X, in
       fa.n_mod = n_mod;
     }
     DCGP_TRY(finalize_layer(ctx, fa));
+    if (L.mean_W) DCGP_TRY(conv_mean_add(ctx, L, X, n_mod, (long)r0 * P, kc, rep, rep_stride, out_mean, out_sample));
   }
   return DCGP_OK;
 }

@@ -216,7 +216,8 @@ StepPlan plan_step(const dcgp_model* m, int N, int S, int dedup, bool need_kl, b
   p.mark = (long)p.rows0 * L0.v.P >= 8192 ? ForkMark::BehindFirstLayer : ForkMark::BehindChain;
   const int nl = (int)m->layers.size();
   // (a padded head sweeps the padded copy of the sample: the ride reads the sample itself)
-  if (nl >= 2 && m->layers[nl - 1]->is_head && !m->layers[nl - 2]->is_head && m->pad[nl - 1] == 0) {
+  // (a layer with a mean filter completes its sample in a pass behind its launch, conv_mean.hip: no row may read the sample inside the launch)
+  if (nl >= 2 && m->layers[nl - 1]->is_head && !m->layers[nl - 2]->is_head && m->pad[nl - 1] == 0 && !m->layers[nl - 2]->mean_W) {
     const int li = nl - 2;
     const LayerState& Lc = *m->layers[li];
     const LayerState& Lh = *m->layers[nl - 1];
@@ -676,7 +677,8 @@ int dcgp_model_factor_groups(dcgp_model* model, int cap, int* count_out, int* Mp
 }
 
 int dcgp_model_set_param(dcgp_model* model, int layer, const char* which, const double* value_host, size_t count) {
-  if (model) ++model->param_version;   // (whatever becomes of the call: the parameter-only state of earlier steps is not reused)
+  // (whatever becomes of the call: the parameter-only state of earlier steps is not reused -- but for the mean filter, which is no input of it)
+  if (model && !(which && !strcmp(which, "mean_filter"))) ++model->param_version;
   if (!model || !which || !value_host) return DCGP_ERR_ARG;
   dcgp_ctx* ctx = model->ctx;
   if (!strcmp(which, "likelihood_epsilon")) {   // model-wide, `layer` is ignored
@@ -711,6 +713,10 @@ int dcgp_model_set_param(dcgp_model* model, int layer, const char* which, const 
   if (!strcmp(which, "w")) {
     if (!L.w) return ctx_fail(ctx, DCGP_ERR_ARG, "set_param: only the head has patch weights");
     DCGP_TRY(expect((size_t)L.v.P)); return L.upload(L.w, value_host, count);
+  }
+  if (!strcmp(which, "mean_filter")) {
+    if (!L.mean_W) return ctx_fail(ctx, DCGP_ERR_ARG, "set_param(mean_filter): layer %d has no mean filter (dcgp_model_set_mean_filter)", layer);
+    DCGP_TRY(expect(L.mean_slots())); return L.upload(L.mean_W, value_host, count);
   }
   if (!strcmp(which, "variance")) { DCGP_TRY(expect(1)); if (!(value_host[0] > 0)) return ctx_fail(ctx, DCGP_ERR_ARG, "variance must be > 0"); L.variance = value_host[0]; return DCGP_OK; }
   if (!strcmp(which, "lengthscale")) { DCGP_TRY(expect(1)); if (!(value_host[0] > 0)) return ctx_fail(ctx, DCGP_ERR_ARG, "lengthscale must be > 0"); L.ls = value_host[0]; return DCGP_OK; }

@@ -21,7 +21,7 @@ struct OptGroup {
   long off; int layer, frozen;
   int hold;                                           // hyp_layer >= 0: bit i set = element i of the triple is held (set_trainable on one ArcCosine parameter)
 };
-constexpr int OPT_GROUPS_MAX = 48;
+constexpr int OPT_GROUPS_MAX = 56;   // 8 layers of up to 6 groups, and a mean filter on each of the 7 conv layers below a head
 struct OptArgs {
   OptGroup grp[OPT_GROUPS_MAX];
   int first_block[OPT_GROUPS_MAX + 1];
@@ -152,6 +152,7 @@ int opt_enqueue(dcgp_model* model, const char* who, bool sgd, double lr, double 
     DCGP_TRY(add(L.hyp, L.gscal, L.ahyp, 3, 1, li, nullptr, (L.frozen & 16u) != 0));
     if (a.ng > ng_hyp) a.grp[ng_hyp].hold = (int)((L.frozen >> 5) & 3u) << 1;   // bits 32 / 64: elements 1 / 2 of the triple stay where they are
     if (L.ard) DCGP_TRY(add(L.ard, L.gard, L.aard, (long)L.v.L, 1, -1, L.in_scale, (L.frozen & 16u) != 0));   // dense head: per-dimension lengthscales and the staging scale 1 / l
+    if (L.mean_W) DCGP_TRY(add(L.mean_W, L.gmean_W, L.amean_W, (long)L.mean_slots(), 0, -1, nullptr, !L.mean_trainable));   // the mean filter (conv_mean.hip)
     if (L.glik) {   // Gaussian likelihood variance / StudentT scale: the last slot of the head's block, moments beside it on the device
       if (!model->d_lik) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: the head's block has a likelihood slot but the model no Gaussian likelihood", who);
       double* lik_mv[2] = {model->d_lik + 1, model->d_lik + 2};
@@ -251,6 +252,11 @@ int dcgp_model_set_trainable(dcgp_model* model, int layer, const char* which, in
   }
   if (layer < 0 || layer >= (int)model->layers.size()) return ctx_fail(model->ctx, DCGP_ERR_ARG, "set_trainable: no layer %d", layer);
   LayerState& L = *model->layers[layer];
+  if (!strcmp(which, "mean_filter")) {
+    if (!L.mean_W) return ctx_fail(model->ctx, DCGP_ERR_ARG, "set_trainable(mean_filter): layer %d has no mean filter (dcgp_model_set_mean_filter)", layer);
+    L.mean_trainable = on != 0;
+    return DCGP_OK;
+  }
   unsigned bit = 0;
   if (!strcmp(which, "Z")) bit = 1u;
   else if (!strcmp(which, "q_mu")) bit = 2u;
@@ -299,6 +305,9 @@ int dcgp_model_get_param(dcgp_model* model, int layer, const char* which, double
   } else if (!strcmp(which, "ard_lengthscales")) {
     if (!L.ard) return ctx_fail(ctx, DCGP_ERR_ARG, "get_param: this layer has no ARD lengthscales");
     src = L.ard; n = (size_t)L.v.L;
+  } else if (!strcmp(which, "mean_filter")) {
+    if (!L.mean_W) return ctx_fail(ctx, DCGP_ERR_ARG, "get_param: this layer has no mean filter");
+    src = L.mean_W; n = L.mean_slots();
   } else return ctx_fail(ctx, DCGP_ERR_ARG, "get_param: unknown parameter '%s'", which);
   if (count != n) return ctx_fail(ctx, DCGP_ERR_ARG, "get_param(%s): expected %zu values, got %zu", which, n, count);
   HIP_TRY(ctx, hipMemcpyAsync(out_host, src, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -342,6 +351,9 @@ int dcgp_model_get_grad(dcgp_model* model, int layer, const char* which, double*
   } else if (!strcmp(which, "ard_lengthscales")) {
     if (!L.ard || !L.gard) return ctx_fail(ctx, DCGP_ERR_ARG, "get_grad: this layer has no ARD lengthscales");
     src = L.gard; n = (size_t)L.v.L;
+  } else if (!strcmp(which, "mean_filter")) {
+    if (!L.mean_W || !L.gmean_W) return ctx_fail(ctx, DCGP_ERR_ARG, "get_grad: this layer has no mean filter");
+    src = L.gmean_W; n = L.mean_slots();
   } else return ctx_fail(ctx, DCGP_ERR_ARG, "get_grad: unknown parameter '%s'", which);
   if (count != n) return ctx_fail(ctx, DCGP_ERR_ARG, "get_grad(%s): expected %zu values, got %zu", which, n, count);
   HIP_TRY(ctx, hipMemcpyAsync(out_host, src, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));

@@ -114,6 +114,8 @@ _SIGS = {
     "dcgp_model_set_grad_shards": [_vp, _i],
     "dcgp_model_set_shard": [_vp, _i, _i],
     "dcgp_model_set_input_padding": [_vp, _i, _i],
+    "dcgp_model_set_mean_filter": [_vp, _i, _vp, _i],
+    "dcgp_debug_conv_mean_time": [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _dp],
     "dcgp_model_grad_block": [_vp, _i, C.POINTER(_vp), C.POINTER(C.c_size_t)],
     "dcgp_model_sgd_step": [_vp, _d],
     "dcgp_model_set_grad_exchange": [_vp, _i],

@@ -149,7 +149,7 @@ class DGP_Base:
         Conv2dMean whose conv_filter was changed afterwards would run as the centre-pixel mean at the model level and through its
         generic __call__ at the layer level -- a silent disagreement)."""
         for li, l in enumerate(self.layers[:-1]):
-            now = (bool(l.identity_mean), getattr(l, "generic_mean", None) is not None)
+            now = (bool(l.identity_mean), getattr(l, "generic_mean", None) is not None, getattr(l, "filter_mean", None) is not None)
             if now != self._built_means[li]:
                 raise ValueError("layer %d: mean function changed after the device model was built (identity_mean %r -> %r, generic "
                                  "%r -> %r); build a new model" % (li, self._built_means[li][0], now[0], self._built_means[li][1], now[1]))
@@ -158,7 +158,8 @@ class DGP_Base:
         if self._model is not None:
             self._check_means()
             return
-        self._built_means = [(bool(l.identity_mean), getattr(l, "generic_mean", None) is not None) for l in self.layers[:-1]]
+        self._built_means = [(bool(l.identity_mean), getattr(l, "generic_mean", None) is not None, getattr(l, "filter_mean", None) is not None)
+                             for l in self.layers[:-1]]
         ctx = self._ctx = dev.get_context()
         L = dev.lib()
         h = C.c_void_p()
@@ -169,14 +170,17 @@ class DGP_Base:
             if getattr(l, "generic_mean", None) is not None:
                 # the one-call ELBO adds Conv2dMean's centre pixel inside the layer launch (the only mean the reference builds,
                 # conv_gp/models.py:95-99); an arbitrary callable exists at the layer level only
-                raise ValueError("layer %d: the model path takes mean_function None / Zero() / Conv2dMean with its initial filter; "
-                                 "got %r" % (li, l.mean_function))
+                raise ValueError("layer %d: the model path takes mean_function None / Zero() / Conv2dMean with its initial filter "
+                                 "(or a LinearConv2dMean, whose filter lives on the device); got %r" % (li, l.mean_function))
             keep = [np.ascontiguousarray(a, np.float64) for a in (l.feature.Z, l.Z_prior, l.q_mu, l.q_sqrt)]
             Hp, Wp = getattr(v, "padded_size", v.input_size[:2])      # the device layer is a VALID layer on the padded image
             ctx._check(L.dcgp_model_add_conv_layer(
                 self._model, Hp, Wp, l.feature_maps_in, v.filter_size, v.stride,
                 l.num_inducing, l.gp_count, int(l.white), int(l.identity_mean), l.base_kernel.variance,
                 getattr(l.base_kernel, "lengthscales", 1.0), *[a.ctypes.data for a in keep]))
+            if l.filter_mean is not None:      # LinearConv2dMean: its filter [f, f, C, R] is the device's [L][R] as it stands (csrc/conv_mean.hip)
+                W = self._mean_filter_host(l)
+                ctx._check(L.dcgp_model_set_mean_filter(self._model, li, W.ctypes.data, int(bool(l.filter_mean.trainable))))
             desc = np.ascontiguousarray(l.base_kernel._describe(), np.float64)
             if desc[0] != 0.0:   # not the RBF the constructor call describes (ArcCosine, conv_gp/models.py:118-119)
                 ctx._check(L.dcgp_model_set_param(self._model, li, b"base_kernel",
@@ -217,6 +221,16 @@ class DGP_Base:
             par = np.ascontiguousarray(self.likelihood._params(), np.float64)
             ctx._check(L.dcgp_model_set_likelihood_params(self._model, self.likelihood.kind, par.ctypes.data, par.size))
 
+    @staticmethod
+    def _mean_filter_host(layer):
+        """A layer's LinearConv2dMean filter as one contiguous float64 [f, f, C, R] array (ValueError for another shape)."""
+        mf, v = layer.filter_mean, layer.view
+        W = np.ascontiguousarray(mf.conv_filter, np.float64)
+        shape = (v.filter_size, v.filter_size, v.feature_maps, layer.gp_count)
+        if W.shape != shape:
+            raise ValueError("LinearConv2dMean.conv_filter must be %s, got %s" % (shape, W.shape))
+        return W
+
     def push_likelihood_nodes(self):
         """Softmax likelihood: copy ``likelihood.nodes`` [Q, K] to the built device model (dcgp_model_set_likelihood_nodes).  The table is no
         parameter: factor reuse keeps its chain.  Not allowed while enqueued steps are outstanding."""
@@ -247,6 +261,8 @@ class DGP_Base:
                     push(li, "w", l.kern.patch_weights)
             else:
                 push(li, "Z0", l.Z_prior)
+                if l.filter_mean is not None:
+                    push(li, "mean_filter", self._mean_filter_host(l))
         push(0, "likelihood_epsilon", float(getattr(self.likelihood, "epsilon", 1e-3)))
         if self.gaussian:
             push(0, "likelihood_variance", float(self.likelihood.variance))
@@ -280,6 +296,10 @@ class DGP_Base:
             out.append(Parameter(base + "/feature/Z", lambda l=l: l.feature.Z, lambda v, l=l: setattr(l.feature, "Z", np.array(v, np.float64))))
             out.append(Parameter(base + "/q_mu", lambda l=l: l.q_mu, lambda v, l=l: setattr(l, "q_mu", np.array(v, np.float64))))
             out.append(Parameter(base + "/q_sqrt", lambda l=l: l.q_sqrt, lambda v, l=l: setattr(l, "q_sqrt", np.array(v, np.float64))))
+            if not head and getattr(l, "filter_mean", None) is not None:      # LinearConv2dMean only (the reference freezes Conv2dMean's filter)
+                out.append(Parameter(base + "/mean_function/conv_filter", lambda l=l: l.filter_mean.conv_filter,
+                                     lambda v, l=l: setattr(l.filter_mean, "conv_filter",
+                                                            np.array(v, np.float64).reshape(np.shape(l.filter_mean.conv_filter)))))
             if head and not dense:
                 out.append(Parameter(base + "/kern/patch_weights", lambda l=l: l.kern.patch_weights,
                                      lambda v, l=l: setattr(l.kern, "patch_weights", np.array(v, np.float64))))
@@ -362,7 +382,8 @@ class DGP_Base:
         """(ELBO, [per-layer dict]) -- the value and gradient TensorFlow hands the optimiser at
         conv_gp/experiment.py:84-108, from the hand-written reverse pass (csrc/grad.hip).  Keys: ``Z``,
         ``q_mu``, ``q_sqrt`` (lower triangle), ``variance``, ``lengthscales`` and, for the head,
-        ``patch_weights``; all with respect to the constrained values."""
+        ``patch_weights``; a conv layer with a ``LinearConv2dMean`` adds ``mean_filter`` [f, f, C, R] (zero while the filter is frozen);
+        all with respect to the constrained values."""
         self._build()
         ctx, L = self._ctx, dev.lib()
         dX = ctx.as_device(np.reshape(X, (np.shape(X)[0], -1)) if not isinstance(X, dev.DeviceArray) else X)
@@ -393,6 +414,8 @@ class DGP_Base:
             if not head and not hasattr(l.base_kernel, "lengthscales"):   # ArcCosine(order 0) base kernel
                 del shapes["lengthscale"]
                 shapes["weight_variances"], shapes["bias_variance"] = (), ()
+            if not head and l.filter_mean is not None:
+                shapes["mean_filter"] = np.shape(l.filter_mean.conv_filter)
             g = {}
             for which, shp in shapes.items():
                 buf = np.empty(shp, np.float64)
@@ -702,8 +725,14 @@ class DGP_Base:
     def set_trainable(self, layer, which, on):
         """param.set_trainable(on) for the device optimiser steps: which in Z, q_mu, q_sqrt, w, hyper (every kernel parameter of the layer);
         weight_variances, bias_variance (that one parameter of an ArcCosine conv layer); "likelihood_variance" (Gaussian likelihood,
-        ``layer`` ignored); "likelihood_scale" (StudentT likelihood, ``layer`` ignored)."""
+        ``layer`` ignored); "likelihood_scale" (StudentT likelihood, ``layer`` ignored); "mean_filter" (the filter of a conv layer's
+        ``LinearConv2dMean``: frozen, its gradient is not formed either)."""
         self._build()
+        if which == "mean_filter":
+            mf = getattr(self.layers[int(layer)], "filter_mean", None) if 0 <= int(layer) < len(self.layers) - 1 else None
+            if mf is None:
+                raise ValueError("set_trainable: layer %d has no LinearConv2dMean" % int(layer))
+            mf.trainable = bool(on)
         self._ctx._check(dev.lib().dcgp_model_set_trainable(self._model, int(layer), which.encode(), int(bool(on))))
 
     def natgrad_step(self, gamma):
@@ -743,6 +772,8 @@ class DGP_Base:
                 kern.bias_variance = float(pull(li, "bias_variance", ()))
             if head and hasattr(l.kern, "patch_weights"):
                 l.kern.patch_weights = pull(li, "w", np.shape(l.kern.patch_weights))
+            if not head and l.filter_mean is not None:
+                l.filter_mean.conv_filter = pull(li, "mean_filter", np.shape(l.filter_mean.conv_filter))
         if self.gaussian:
             self.likelihood.variance = float(pull(0, "likelihood_variance", ()))
         if self.student_t:

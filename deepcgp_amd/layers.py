@@ -150,8 +150,9 @@ class ConvLayer(Layer):
     """conv_gp/layers.py:52-161.  ``mean_function``: a ``deepcgp_amd.mean_functions`` object as the reference builds them
     (``Conv2dMean(filter_size, feature_maps_in, feature_maps_out, stride)`` or ``Zero()``, conv_gp/models.py:95-99), any callable
     on the NHWC image returning N x num_outputs (or N x H' x W' x gp_count) values, or the aliases None / 'zero' / 'conv2d'.
-    A ``Conv2dMean`` with the filter its constructor built is added inside the layer's own launch; any other callable through
-    its ``__call__`` (the model-level one-call ELBO path takes the former only)."""
+    A ``Conv2dMean`` with the filter its constructor built is added inside the layer's own launch; a ``LinearConv2dMean`` (any filter,
+    optionally trained) lives on the device model and is added behind the layer's launch (``filter_mean``; csrc/conv_mean.hip); any other
+    callable through its ``__call__`` (the model-level one-call ELBO path takes the first two only)."""
 
     def __init__(self, base_kernel, mean_function, feature=None, view=None, white=False, gp_count=1,
                  q_mu=None, q_sqrt=None, **kwargs):
@@ -179,7 +180,23 @@ class ConvLayer(Layer):
                 q_sqrt = np.tile(np.eye(self.num_inducing)[None, :, :], [self.gp_count, 1, 1])
         self.q_sqrt = np.array(q_sqrt, np.float64)
         self.mean_function = mean_function
+        self.filter_mean                     # (a LinearConv2dMean of another geometry than the view's raises here)
         self._build_prior_cholesky()
+
+    @property
+    def filter_mean(self):
+        """The ``LinearConv2dMean`` of this layer, or None: the mean the device model evaluates, differentiates and trains through its
+        filter (csrc/conv_mean.hip).  Its geometry must be the view's: same filter size, stride, input channels, and gp_count maps."""
+        mf = self.mean_function
+        if not getattr(mf, 'is_linear_conv2d_mean', False):
+            return None
+        v = self.view
+        have = (mf.filter_size, mf.stride, mf.feature_maps_in, mf.feature_maps_out)
+        want = (v.filter_size, v.stride, v.feature_maps, self.gp_count)
+        if have != want:
+            raise ValueError("LinearConv2dMean(filter_size, feature_maps_in, feature_maps_out, stride) = %r does not match the layer's view "
+                             "and gp_count %r" % ((have[0], have[2], have[3], have[1]), (want[0], want[2], want[3], want[1])))
+        return mf
 
     @property
     def identity_mean(self):
@@ -202,7 +219,7 @@ class ConvLayer(Layer):
         """A callable mean function the kernels do not add themselves (``mean + self.mean_function(mean_view)``, layers.py:133-134)."""
         mf = self.mean_function
         from .mean_functions import Zero
-        if mf is None or isinstance(mf, (str, Zero)) or self.identity_mean:
+        if mf is None or isinstance(mf, (str, Zero)) or self.identity_mean or self.filter_mean is not None:
             if isinstance(mf, str) and mf not in ('zero', 'conv2d'):
                 raise ValueError("mean_function %r: expected a callable, None, 'zero' or 'conv2d'" % (mf,))
             return None
@@ -212,10 +229,12 @@ class ConvLayer(Layer):
 
     def _generic_mean_value(self, X4):
         mf = self.generic_mean
+        N = X4.shape[0]
+        if mf is None and self.filter_mean is not None:      # the layer's own window: the filter sees the zero-padded image
+            return np.asarray(self.filter_mean(self.view.pad(X4)), np.float64).reshape(N, self.num_outputs)
         if mf is None:
             return None
         val = np.asarray(mf(self.view.mean_view(X4, None)), np.float64)
-        N = X4.shape[0]
         if val.size != N * self.num_outputs:
             raise ValueError("mean_function returned %s values for %d x %d outputs" % (val.shape, N, self.num_outputs))
         return val.reshape(N, self.num_outputs)

@@ -7,6 +7,9 @@ convolution runs on the device: patches through ``dcgp_extract_patches``, the fi
 ``ConvLayer`` recognises a ``Conv2dMean`` whose filter is still the one its constructor built (the reference freezes it:
 ``conv_mean.set_trainable(False)``, models.py:100) and adds the centre pixel inside its own launch instead
 (``csrc/cond.hip`` finalize / ``csrc/conv_fused.hip`` epilogue); any other callable is evaluated through ``__call__`` and added.
+
+``LinearConv2dMean`` is this repository's own: the same convolution with ANY filter, evaluated, differentiated and optionally trained on
+the device inside every model-level call (``csrc/conv_mean.hip``, dcgp_model_set_mean_filter) -- the skip path of a deep stack.
 """
 import numpy as np
 
@@ -20,7 +23,9 @@ class MeanFunction:
         raise NotImplementedError
 
     def set_trainable(self, flag):
-        """The reference calls ``conv_mean.set_trainable(False)`` (models.py:100); the filter is never trained on this path."""
+        """The reference calls ``conv_mean.set_trainable(False)`` (models.py:100).  Only a ``LinearConv2dMean``'s filter is ever trained
+        (the device optimiser steps move it while the flag is set when the model is built; ``DGP_Base.set_trainable(li, "mean_filter",
+        on)`` switches a built model); on the other classes the flag is recorded and nothing reads it."""
         self.trainable = bool(flag)
 
 
@@ -92,6 +97,63 @@ class Conv2dMean(IdentityConv2dMean):
     def has_initial_filter(self):
         """True while ``conv_filter`` is what ``_init_filter`` built: the case the layer kernels add themselves."""
         return np.array_equal(np.asarray(self.conv_filter), self._init_filter())
+
+    def __call__(self, NHWC_X):
+        value = self._conv(NHWC_X)
+        return value.reshape(value.shape[0], -1)
+
+
+MEAN_FILTERS = ("centre0", "channels", "sum")
+
+
+def conv_mean_filter(kind, filter_size, feature_maps_in, feature_maps_out):
+    """The named filters [f, f, Cin, Cout] of ``LinearConv2dMean``: ``"centre0"`` Conv2dMean's (the centre pixel of channel 0 into map 0),
+    ``"channels"`` the centre pixel of channel c into map c for c < min(Cin, Cout) -- every channel skips to its own map; with Cin == Cout,
+    stride 1 and a padding of f // 2 a true residual block -- and ``"sum"`` IdentityConv2dMean's (every channel's centre into every map).
+    They have a centre, so ``filter_size`` must be odd (ValueError)."""
+    f, Cin, Cout = int(filter_size), int(feature_maps_in), int(feature_maps_out)
+    if kind not in MEAN_FILTERS:
+        raise ValueError("mean filter %r: expected one of %s or an array [f, f, Cin, Cout]" % (kind, ", ".join(MEAN_FILTERS)))
+    if f % 2 == 0:
+        raise ValueError("mean filter %r: a named filter copies the centre pixel and needs an odd filter_size, got %d" % (kind, f))
+    W = np.zeros((f, f, Cin, Cout))
+    c0 = f // 2
+    if kind == "centre0":
+        W[c0, c0, 0, 0] = 1.0
+    elif kind == "channels":
+        for c in range(min(Cin, Cout)):
+            W[c0, c0, c, c] = 1.0
+    else:
+        W[c0, c0, :, :] = 1.0
+    return W
+
+
+class LinearConv2dMean(IdentityConv2dMean):
+    """m(x)[n, p, r] = sum_l patch_p(x_n)[l] W[l, r]: a VALID convolution of the image the layer's window sees with ``conv_filter``
+    [f, f, Cin, Cout] (``filter``: one of ``MEAN_FILTERS`` or an array of that shape, any f), flattened to N x (P * Cout), patch-major like
+    ``Conv2dMean``.  On a ``ConvLayer`` whose view has the same geometry (anything else raises ValueError there) the model-level calls run
+    it on the device -- forward, reverse pass, input gradient, and with ``trainable`` the optimiser steps; the layer-level calls add
+    ``__call__``'s value."""
+
+    is_linear_conv2d_mean = True
+
+    def __init__(self, filter_size, feature_maps_in, feature_maps_out, stride=1, filter="channels", trainable=False):
+        self.filter_size = int(filter_size)
+        self.feature_maps_in = int(feature_maps_in)
+        self.feature_maps_out = int(feature_maps_out)
+        self.stride = int(stride)
+        self.trainable = bool(trainable)
+        shape = (self.filter_size, self.filter_size, self.feature_maps_in, self.feature_maps_out)
+        if isinstance(filter, str):
+            self.conv_filter = conv_mean_filter(filter, *shape[1:])
+        else:
+            W = np.array(filter, np.float64)
+            if W.shape != shape:
+                raise ValueError("filter must be one of %s or an array %s, got shape %s" % (", ".join(MEAN_FILTERS), shape, W.shape))
+            self.conv_filter = W
+
+    def _init_filter(self):
+        return np.array(self.conv_filter, np.float64)
 
     def __call__(self, NHWC_X):
         value = self._conv(NHWC_X)

@@ -7,6 +7,7 @@ from .kernels import RBF, ArcCosine, Matern32, Matern52, ConvKernel, AdditivePat
 from .layers import ConvLayer, SVGP_Layer
 from .likelihoods import MultiClass, Softmax
 from .mean_functions import Conv2dMean, IdentityConv2dMean  # noqa: F401  (the names conv_gp/models.py:11 imports)
+from .mean_functions import MEAN_FILTERS, LinearConv2dMean, conv_mean_filter
 from .views import FullView
 from .arguments import parse_paddings
 
@@ -44,6 +45,11 @@ def build_layers_from_spec(spec):
         if mf == "conv2d":      # --identity-mean: Conv2dMean(filter_size, NHWC[3], feature_map, stride=stride), conv_gp/models.py:95-97
             mf = Conv2dMean(c["f"], c["C"], c["R"], stride=c["s"])
             mf.set_trainable(False)                                                            # models.py:100
+        if c.get("mean_filter") is not None:      # a linear convolutional mean on the device: its filter [f, f, C, R] (or [f f C, R]) and whether it is trained
+            if mf is not None:
+                raise ValueError("a conv entry takes mean_function or mean_filter, not both")
+            W = np.array(c["mean_filter"], np.float64).reshape(c["f"], c["f"], c["C"], c["R"])
+            mf = LinearConv2dMean(c["f"], c["C"], c["R"], stride=c["s"], filter=W, trainable=bool(c.get("mean_trainable", False)))
         layer = ConvLayer(base, mf,
                           feature=PatchInducingFeatures(c["Z"]), view=view, white=c["white"], gp_count=c["R"],
                           q_mu=c["q_mu"], q_sqrt=c["q_sqrt"])
@@ -382,6 +388,22 @@ def identity_conv(NHWC_X, filter_size, feature_maps_in, feature_maps_out, stride
     return np.repeat(centre[..., None], feature_maps_out, axis=-1)
 
 
+def filter_conv(NHWC_X, conv_filter, stride, count=1000):
+    """``identity_conv`` for a layer with a ``LinearConv2dMean``: the same random-subset draw, propagated through ``conv_filter``
+    [f, f, Cin, Cout] (VALID, NHWC) -- what the layer emits at initialisation, where q_mu is zero.  Host NumPy, one product per filter tap."""
+    X = NHWC_X[np.random.choice(np.arange(NHWC_X.shape[0]), size=min(count, NHWC_X.shape[0]))]
+    W = np.asarray(conv_filter, np.float64)
+    f, _, Cin, Cout = W.shape
+    n, H, Wd, C = X.shape
+    Ho, Wo = (H - f) // stride + 1, (Wd - f) // stride + 1
+    out = np.zeros((n, Ho, Wo, Cout))
+    for kh in range(f):
+        for kw in range(f):
+            if np.any(W[kh, kw]):
+                out += X[:, kh:kh + (Ho - 1) * stride + 1:stride, kw:kw + (Wo - 1) * stride + 1:stride, :] @ W[kh, kw]
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------
 # flags -> architecture -> neutral model spec -> layers  (the job of conv_gp/models.py:35-247)
 # ---------------------------------------------------------------------------------------------------
@@ -394,6 +416,7 @@ CHECKPOINT_FIELDS = (
     ("base_kernel/variance", "variance"),          # conv_kernel/base_kernel/... (conv layers), kern/base_kernel/... (patch heads)
     ("base_kernel/lengthscales", "ls"),
     ("kern/patch_weights", "w"),
+    ("mean_function/conv_filter", "mean_filter"),  # a conv layer's LinearConv2dMean (--mean-filter / --train-mean)
     ("kern/variance", "variance"),                 # dense RBF head (--last-kernel rbf): the kernel sits directly under kern/
     ("kern/lengthscales", "ls"),
 )
@@ -461,6 +484,27 @@ class ModelBuilder(object):
         """--paddings: one zero-padding width per GP layer (head included); all zeros without the flag."""
         return parse_paddings(self.flags, len(parse_ints(self.flags.M)))
 
+    def mean_flags(self):
+        """(mean kind, trainable) of --identity-mean / --mean-filter / --train-mean.  Kind None: no mean function; "conv2d": the reference's
+        frozen Conv2dMean inside the layer launch (the flags' defaults under --identity-mean, exactly as before); otherwise a name of
+        ``MEAN_FILTERS``: a ``LinearConv2dMean`` with that initial filter -- any non-default filter, and ``centre0`` itself with --train-mean.
+        Either flag without --identity-mean and an unknown filter name raise ValueError naming the flag."""
+        fl = self.flags
+        identity = bool(getattr(fl, "identity_mean", False))
+        kind = getattr(fl, "mean_filter", "centre0") or "centre0"
+        train = bool(getattr(fl, "train_mean", False))
+        if kind not in MEAN_FILTERS:
+            raise ValueError("--mean-filter: expected %s, got %r" % (" | ".join(MEAN_FILTERS), kind))
+        if not identity:
+            if kind != "centre0":
+                raise ValueError("--mean-filter %s: a mean filter needs --identity-mean" % kind)
+            if train:
+                raise ValueError("--train-mean: a trainable mean filter needs --identity-mean")
+            return None, False
+        if kind == "centre0" and not train:
+            return "conv2d", False
+        return kind, train
+
     # ---- stages -> spec ----------------------------------------------------------------------------
     def spec(self):
         fl = self.flags
@@ -475,6 +519,7 @@ class ModelBuilder(object):
         if fl.last_kernel not in ("conv", "add", "rbf"):
             raise ValueError("Invalid last layer kernel")
         white = bool(fl.white)
+        mean_kind, train_mean = self.mean_flags()
         spec = {"S": int(fl.num_samples), "num_data": int(self.X_train.shape[0]), "convs": []}
         images = self.X_train                              # what the next layer is initialised on
         for li, (M, f, s, R) in enumerate(convs):
@@ -487,8 +532,14 @@ class ModelBuilder(object):
                 variance=float(have.get("variance", 5.0)), ls=float(have.get("ls", 5.0)),     # models.py:114-117
                 q_mu=have.get("q_mu"), q_sqrt=have.get("q_sqrt"),
                 q_sqrt_scale=None if "q_sqrt" in have else 1e-5,                               # start with low variance (models.py:136-138)
-                mean_function="conv2d" if getattr(fl, "identity_mean", False) else None))
-            images = identity_conv(images, f, C, R, s)                                          # models.py:29-33,104
+                mean_function="conv2d" if mean_kind == "conv2d" else None))
+            if mean_kind not in (None, "conv2d"):             # LinearConv2dMean: the checkpoint's filter, else the named one
+                W = have["mean_filter"] if "mean_filter" in have else conv_mean_filter(mean_kind, f, C, R)
+                spec["convs"][-1].update(mean_filter=np.array(W, np.float64).reshape(f, f, C, R), mean_trainable=train_mean)
+            if mean_kind in (None, "conv2d", "centre0"):
+                images = identity_conv(images, f, C, R, s)                                      # models.py:29-33,104
+            else:      # the same draw through the layer's own filter: the next layer's inducing patches are cut from what this one will emit
+                images = filter_conv(images, spec["convs"][-1]["mean_filter"], s)
         have = stored.get(n_layers - 1, {})
         _, H, W, C = images.shape
         images = zero_pad(images, pads[-1])

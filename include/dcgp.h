@@ -253,6 +253,18 @@ int dcgp_model_set_head(dcgp_model* model, int H, int W, int C, int f, int strid
  * no image inside the layer's H x W.  pad = 0 (the default) is the unpadded layer, on exactly the unpadded code path.
  * Padding is no parameter: checkpoints do not hold it.                                                                        */
 int dcgp_model_set_input_padding(dcgp_model* model, int layer, int pad);
+/* A linear convolutional mean function on conv layer `layer` (conv_gp/mean_functions.py:6-41 with any filter; added to the conditional's
+ * mean at conv_gp/layers.py:133-134): m(x)[n, p, r] = sum_l patch_p(x_n)[l] W[l][r] on the layer's own window -- its f, stride and, through
+ * the padded copy the layer reads, its padding.  filter_host [f*f*C][R] in FullView's (kh, kw, c) element order: the reference's
+ * conv_filter [f, f, C, R] flattened.  Every entry point that goes through the model evaluates it (one launch behind the layer's own,
+ * added to mean and sample; such a layer carries no head rows), differentiates it (dX for the layers below and dcgp_model_input_grad) and,
+ * with trainable != 0, forms its gradient (L R slots at the very end of the layer's gradient block, zero while frozen) and moves it in the
+ * optimiser steps.  Allowed before the layer's first gradient step; calling it again replaces values and flag.  DCGP_ERR_ARG on the
+ * head, on a layer added with identity_mean (the in-launch Conv2dMean), once the layer's gradient block exists, or while enqueued steps
+ * are still to be collected.  The filter is "mean_filter" in dcgp_model_set_param / _get_param / _get_grad / _set_trainable
+ * (conv_gp/mean_functions.py:6-41, conv_gp/layers.py:133-134).  It is no input of the factorisation chain: writing it starts no new
+ * parameter version, so dcgp_model_set_factor_reuse keeps its chain.  No atomics: two runs give the same bits. */
+int dcgp_model_set_mean_filter(dcgp_model* model, int layer, const double* filter_host /* [f*f*C][R] */, int trainable);
 /* keep every layer's (sample, mean, var) of the next forward passes for dcgp_model_layer_output   */
 int dcgp_model_set_keep_outputs(dcgp_model* model, int on);
 /* Push a changed parameter: which = "Z", "Z0", "q_mu", "q_sqrt", "w", "variance", "lengthscale", or
@@ -261,7 +273,9 @@ int dcgp_model_set_keep_outputs(dcgp_model* model, int on);
  * (p1 = lengthscale; conv layers only), or "ard_lengthscales" = one lengthscale
  * per input dimension for a single-patch head (H = W = f = 1, C = D): gpflow RBF(D, ARD=True) on the flattened
  * features, the dense head of --last-kernel rbf (conv_gp/models.py:160-168).  "likelihood_epsilon" (one value in
- * (0, 1), `layer` ignored) is the RobustMax epsilon of the ELBO / predict_y entry points (default 1e-3).  */
+ * (0, 1), `layer` ignored) is the RobustMax epsilon of the ELBO / predict_y entry points (default 1e-3).
+ * "mean_filter" [f*f*C, R]: the filter of a conv layer given one by dcgp_model_set_mean_filter (conv_gp/mean_functions.py:6-41,
+ * conv_gp/layers.py:133-134); it alone starts no new parameter version.  */
 int dcgp_model_set_param(dcgp_model* model, int layer, const char* which, const double* value_host,
                          size_t count);
 
@@ -299,7 +313,8 @@ int dcgp_elbo_grad(dcgp_model* model, const double* X, const int32_t* y, int N, 
                    int* info_host);
 /* which = "Z" [M, L], "q_mu" [M, R], "q_sqrt" [R, M, M], "variance" [1], "lengthscale" [1] (RBF) or "weight_variances" [1] and
  * "bias_variance" [1] (ArcCosine conv layers), "w" [P] (head),
- * "ard_lengthscales" [D] (dense RBF(ARD) head; its scalar "lengthscale" gradient is 0). */
+ * "ard_lengthscales" [D] (dense RBF(ARD) head; its scalar "lengthscale" gradient is 0),
+ * "mean_filter" [f*f*C, R] (a conv layer with a filter mean, conv_gp/mean_functions.py:6-41, conv_gp/layers.py:133-134; zero while the filter is frozen). */
 int dcgp_model_get_grad(dcgp_model* model, int layer, const char* which, double* out_host, size_t count);
 /* Data parallelism of the gradient: every rank holds a shard of the batch and the full parameters.  The data part of
  * the gradient is a sum over shards, the KL part is replicated, so each rank computes scale * data_grad(shard) -
@@ -413,7 +428,8 @@ int dcgp_model_sgd_step(dcgp_model* model, double lr);
  * precision matrix is not positive definite: the reference's loop then scales gamma by 0.2 and retries (:36-49). */
 int dcgp_model_natgrad_step(dcgp_model* model, double gamma, int* info_host);
 /* param.set_trainable(False / True) (conv_gp/experiment.py:93-95, models.py:100): parameters switched off are left
- * alone by the Adam / SGD steps.  which = "Z", "q_mu", "q_sqrt", "w", or "hyper" (variance and lengthscale). */
+ * alone by the Adam / SGD steps.  which = "Z", "q_mu", "q_sqrt", "w", "hyper" (variance and lengthscale), or "mean_filter" (a conv layer
+ * with a filter mean, conv_gp/mean_functions.py:6-41, conv_gp/layers.py:133-134: frozen, its gradient is not formed either). */
 int dcgp_model_set_trainable(dcgp_model* model, int layer, const char* which, int on);
 /* current (constrained) value of a parameter, names as dcgp_model_get_grad; the inverse of dcgp_model_set_param -- what
  * sess.run(param.constrained_tensor) returns when the reference writes its checkpoint (conv_gp/experiment.py:56-64) */
@@ -687,6 +703,11 @@ int dcgp_debug_plan_head_ride(const long long* query, int n_query, const long lo
 int dcgp_debug_mfma_f64_rate(dcgp_ctx* ctx, double* tflops_out);
 int dcgp_debug_store_rate(dcgp_ctx* ctx, int N, int P, int M, double* gbs_out);
 int dcgp_debug_set_sweep_trace(dcgp_ctx* ctx, long long* buf_dev, long n_workgroups, const char* family /* "kuf", "kuf_long", "head_sweep"; NULL: any */);
+/* The three kernels of a filter mean (csrc/conv_mean.hip; dcgp_model_set_mean_filter) alone, on a conv layer H x W x C with filter f, `stride`, R maps,
+ * `rows` images and `rep` replicas of its output, each beside a copy kernel moving the bytes the kernel has to move (tools/conv_mean_time.py): `iters`
+ * launches between two events behind a warm-up.  out_us[8] = microseconds per launch {conv_mean_add, its copy, conv_mean_backward_dx, its copy,
+ * conv_mean_backward_filter (both stages), its copy, 0, 0}. */
+int dcgp_debug_conv_mean_time(dcgp_ctx* ctx, int H, int W, int C, int f, int stride, int R, int rows, int rep, int iters, double* out_us);
 
 #ifdef __cplusplus
 }
