@@ -97,9 +97,12 @@ def oracle_gradient(spec, X, Y, zs):
 
 
 # ---- torch --------------------------------------------------------------------------------------------------------------------------
-def torch_forward(spec, X, Y, zs, x_leaf=False):
+def torch_forward(spec, X, Y, zs, x_leaf=False, ve=None):
     """dict(elbo, kl, leaves [{name: tensor}] per layer -- ``mean_filter`` [f, f, C, R] among a conv layer's where it has one --, mean, var
-    [S, N, R] of the head, data [N] = 1/S sum_s E_q[log p(y_n | f_sn)], X the input tensor (a leaf when x_leaf), F [per conv layer samples])."""
+    [S, N, R] of the head, data [N] = 1/S sum_s E_q[log p(y_n | f_sn)], X the input tensor (a leaf when x_leaf), F [per conv layer samples]).
+    ``ve``: another likelihood's rule (tests/compose_ref.py), a callable (mean, var [S, N, R]) -> E_q[log p(y | f)] as [S, N] or [S, N, R]
+    (summed over R, averaged over S) or the per-image average [N] itself; None: RobustMax on the labels Y.  A conv entry with
+    ``mean_function`` "conv2d" adds Conv2dMean's centre pixel."""
     import torch
     import test_oracle_autograd as toa
     from matern_ref import NU2, torch_gram
@@ -141,7 +144,10 @@ def torch_forward(spec, X, Y, zs, x_leaf=False):
         kff = p["variance"] * torch.ones(cols.shape[0], dtype=T)
         mean, var = toa._conditional(Kuu, Kuf, kff, p["q_mu"], p["q_sqrt"], c["white"])
         mean, var = mean.reshape(S * N, P * R), var.reshape(S * N, P * R)
-        assert c.get("mean_function") is None
+        assert c.get("mean_function") in (None, "conv2d") and not (c.get("mean_function") and c.get("mean_filter") is not None)
+        if c.get("mean_function") == "conv2d":      # Conv2dMean: the centre pixel of the (padded) patch's channel 0 into map 0
+            centre = pt.reshape(S * N, P, c["f"], c["f"], c["C"])[:, :, c["f"] // 2, c["f"] // 2, 0]
+            mean = mean + torch.cat([centre[:, :, None], torch.zeros(S * N, P, R - 1, dtype=T)], 2).reshape(S * N, P * R)
         if c.get("mean_filter") is not None:
             p["mean_filter"] = leaf(np.reshape(c["mean_filter"], (c["f"], c["f"], c["C"], R)))
             mean = mean + (cols @ p["mean_filter"].reshape(-1, R)).reshape(S * N, P * R)
@@ -168,8 +174,12 @@ def torch_forward(spec, X, Y, zs, x_leaf=False):
     Kuu = toa._rbf(p["Z"], p["Z"], p["variance"], p["lengthscales"]) + JITTER * torch.eye(M, dtype=T)
     mean, var = toa._conditional(Kuu, Kzx, kdiag, p["q_mu"], p["q_sqrt"], h["white"])
     kl = kl + toa._gauss_kl(p["q_mu"], p["q_sqrt"], None if h["white"] else Kuu)
-    y = torch.tensor(np.tile(np.asarray(Y).reshape(1, N), [S, 1]).reshape(S * N), dtype=torch.long)
-    data = toa._robustmax_ve(mean, var, y).reshape(S, N).mean(0)
+    if ve is None:
+        y = torch.tensor(np.tile(np.asarray(Y).reshape(1, N), [S, 1]).reshape(S * N), dtype=torch.long)
+        data = toa._robustmax_ve(mean, var, y).reshape(S, N).mean(0)
+    else:
+        data = ve(mean.reshape(S, N, -1), var.reshape(S, N, -1))
+        data = data if data.dim() == 1 else data.reshape(S, N, -1).sum(2).mean(0)
     elbo = data.sum() * (spec["num_data"] / N) - kl
     return dict(elbo=elbo, kl=kl, leaves=leaves, mean=mean.reshape(S, N, -1), var=var.reshape(S, N, -1), data=data, X=Xt, F=samples)
 

@@ -67,6 +67,18 @@ def test_elbo_vs_numpy(ctx, case, D, white, dedup):
     model.close()
 
 
+def _torch_bern_rule(m, v, Y):
+    """The probit rule of tests/bernoulli_ref.py in torch, at the device's 20 Gauss-Hermite nodes: m, v [S, N, D] tensors, Y [N, D] in
+    {0, 1} -> [S, N, D]; shared with tests/compose_ref.py."""
+    import torch
+    gx, gw = np.polynomial.hermite.hermgauss(20)
+    gx, gw = torch.tensor(gx, dtype=torch.float64), torch.tensor(gw / math.sqrt(math.pi), dtype=torch.float64)
+    F = m[..., None] + torch.sqrt(torch.clamp(2.0 * v, min=1e-10))[..., None] * gx
+    p = torch.special.ndtr(F) * (1 - 2e-3) + 1e-3
+    pos = torch.tensor(np.asarray(Y) == 1)[None, :, :, None]
+    return (torch.where(pos, torch.log(p), torch.log(1 - p)) * gw).sum(-1)      # [S, N, D]
+
+
 def _torch_bern(spec, X, Ylab, Y, zs):
     import torch
     import test_oracle_autograd as ta
@@ -76,12 +88,7 @@ def _torch_bern(spec, X, Ylab, Y, zs):
     y = torch.tensor(np.tile(np.asarray(Ylab).reshape(1, N), [S, 1]).reshape(S * N), dtype=torch.long)
     ve_rm = ta._robustmax_ve(m.reshape(S * N, -1), v.reshape(S * N, -1), y).reshape(S, N).mean(0).sum()
     kl = ve_rm * (spec["num_data"] / N) - e_rm
-    gx, gw = np.polynomial.hermite.hermgauss(20)
-    gx, gw = torch.tensor(gx, dtype=torch.float64), torch.tensor(gw / math.sqrt(math.pi), dtype=torch.float64)
-    F = m[..., None] + torch.sqrt(torch.clamp(2.0 * v, min=1e-10))[..., None] * gx
-    p = torch.special.ndtr(F) * (1 - 2e-3) + 1e-3
-    pos = torch.tensor(Y == 1)[None, :, :, None]
-    ve = (torch.where(pos, torch.log(p), torch.log(1 - p)) * gw).sum(-1)      # [S, N, D]
+    ve = _torch_bern_rule(m, v, Y)
     return ve.sum(2).mean(0).sum() * (spec["num_data"] / N) - kl, leaves
 
 

@@ -112,6 +112,12 @@ def test_targets_and_parameters(ctx):
     assert not rm.gaussian and rm.Y.dtype == np.int32 and isinstance(rm.likelihood, MultiClass)
 
 
+def _torch_gauss_rule(m, v, yt, s2t):
+    """E_q[log N(y; f, s2)] in closed form on tensors m, v, yt of one (broadcast) shape; shared with tests/compose_ref.py."""
+    import torch
+    return -0.5 * torch.log(2 * np.pi * s2t) - 0.5 * ((yt - m) ** 2 + v) / s2t
+
+
 def _torch_gauss(spec, X, Ylab, Y, zs, s2):
     import torch
     import test_oracle_autograd as ta
@@ -123,7 +129,7 @@ def _torch_gauss(spec, X, Ylab, Y, zs, s2):
     kl = ve_rm * (spec["num_data"] / N) - e_rm
     s2t = torch.tensor(s2, dtype=torch.float64, requires_grad=True)
     yt = torch.tensor(Y, dtype=torch.float64)[None]
-    ve = -0.5 * torch.log(2 * np.pi * s2t) - 0.5 * ((yt - m) ** 2 + v) / s2t
+    ve = _torch_gauss_rule(m, v, yt, s2t)
     e = ve.sum(2).mean(0).sum() * (spec["num_data"] / N) - kl
     return e, leaves, s2t
 
