@@ -22,4 +22,5 @@ struct GenGemm {
   int phi = 0;             // Murray's Phi on the result (before accumulation): strictly lower part kept, diagonal halved, the rest zero
   int lower_compact = 0;   // set by the launcher: the grid enumerates the tiles on / below the diagonal only
 };
+// Which kernel, tile, split and grid a call takes is decided by plan_gemm() (gemm_plan.h) and by nothing else; gemm_gen() launches from that plan.
 int gemm_gen(dcgp_ctx* ctx, const GenGemm& g);

@@ -5,12 +5,15 @@
 // patch columns) are split along k into a partial buffer and summed in a fixed order -- no atomics, so gradients are
 // reproducible run to run.  The forward path's tuned kernel is gemm.hip; this one trades peak rate for generality.
 #include <cstdlib>
+#include <cstring>
+#include <tuple>
 
 #include "gemm_gen.h"
+#include "gemm_plan.h"
 
 namespace {
 
-constexpr int GK = 16;
+constexpr int GK = gemm_plan::kGK;
 // LDS tile layouts.  An operand whose rows (columns) are contiguous in memory is staged [k][m] with row stride GT + 16
 // (the two 16-lane halves of a ds_read_b64 hit disjoint banks); one whose contraction index is contiguous is staged
 // [m][k] with row stride LDK = 17, so that each thread's consecutive k land next to each other and the fragment reads
@@ -207,7 +210,7 @@ __global__ void splitk_reduce_kernel(GenGemm g, int ksplit, const double* part) 
 // of 32 x 32 on 12 waves, three blocks a wave (the general kernel's three 128 x 128 tiles compute 48 such blocks), 96 MFMAs of a wave between two
 // barriers, the column scale applied to the B fragment as it leaves LDS.  grid (k ranges, outputs): the ranges are chosen so that the launch is one
 // workgroup per CU; the partial sums meet in splitk_reduce_kernel (fixed order, both triangles stored).
-constexpr int SY_ROWS = 256, SY_KC = 32, SY_LD = SY_KC + 1, SY_NT = 768;
+constexpr int SY_ROWS = gemm_plan::kSyRows, SY_KC = gemm_plan::kSyKC, SY_LD = gemm_plan::kSyLD, SY_NT = gemm_plan::kSyNT;
 // the 36 blocks on and below the diagonal of the 8 x 8 grid, row by row; wave w owns entries 3 w .. 3 w + 2.  A kernel ARGUMENT: as a constant table
 // the compiler specialised the whole kernel per wave (twelve copies of the loop, 400 KB of code)
 struct SyBlocks { unsigned char b[36][2]; };
@@ -336,139 +339,123 @@ __global__ __launch_bounds__(SY_NT) void syrk_kscale_kernel(GenGemm g, int kchun
 
 }  // namespace
 
-template <int GT, int NT, int WT>
-static int gemm_gen_launch(dcgp_ctx* ctx, const GenGemm& g, int slots_per_round) {
-  const int nt_m = (g.M + GT - 1) / GT, nt_n = (g.N + GT - 1) / GT;
-  long tiles = (long)nt_m * nt_n * g.batch;
-  if (g.lower_only) {                 // tiles above the diagonal exit at once
-    long live = 0;
-    for (int bi = 0; bi < nt_m; ++bi) live += (bi + 1 < nt_n ? bi + 1 : nt_n);
-    tiles = live * g.batch;
-  }
-  // split long contractions so that the launch fills the chip: a whole number of rounds of co-resident workgroups
-  // (the 32-tile configuration serves launches that cannot fill the chip: it splits earlier and finer)
-  constexpr int SPLIT_MIN_K = GT == 32 ? 1024 : 2048, SPLIT_CHUNK = GT == 32 ? 128 : 512;
-  int ksplit = 1;
-  if (g.K >= SPLIT_MIN_K && tiles < slots_per_round) {
-    ksplit = (int)((slots_per_round + tiles - 1) / tiles);
-    if (tiles * ksplit > slots_per_round && ksplit > 1) --ksplit;   // stay within one round rather than spill a few workgroups into a second
-    const int max_split = g.K / SPLIT_CHUNK;
-    if (ksplit > max_split) ksplit = max_split;
-    if (ksplit < 1) ksplit = 1;
-  }
-  int kchunk = g.K;
-  double* part = nullptr;
-  if (ksplit > 1) {
-    kchunk = round_up((g.K + ksplit - 1) / ksplit, GK);
-    ksplit = (g.K + kchunk - 1) / kchunk;
-    // one partial buffer per stream: the backward pass runs two chains concurrently
-    char pname[48];
-    snprintf(pname, sizeof pname, "gemm_gen_part@%p", (void*)ctx->stream);
-    part = (double*)ws_get(ctx, pname, (size_t)ksplit * g.batch * g.M * g.N * sizeof(double));
-    if (!part) return DCGP_ERR_ALLOC;
-  }
-  if ((long)g.batch * ksplit > 65535) return ctx_fail(ctx, DCGP_ERR_ARG, "gemm_gen: batch %d x split %d too large", g.batch, ksplit);
-  dim3 grid(nt_n, nt_m, g.batch * ksplit);
-  GenGemm gk = g;
-  if (g.lower_only && (part || g.accumulate)) {   // nothing has to be written above the diagonal: visit the live tiles only
-    if (g.M != g.N) return ctx_fail(ctx, DCGP_ERR_ARG, "gemm_gen: lower_only needs a square output");
-    gk.lower_compact = 1;
-    grid = dim3((unsigned)(tiles / g.batch), 1, g.batch * ksplit);
-  }
-  const bool akf = g.a_cs == 1, bkf = g.b_rs == 1;
-  // 16-byte loads: the contiguous stride is 1 and every other stride, the base and the k origin of a split keep 16-byte alignment
-  auto even = [](long x) { return (x & 1) == 0; };
-  const bool a_vec = (akf ? even(g.a_rs) : (g.a_rs == 1 && even(g.a_cs))) && even(g.a_bs) && ((uintptr_t)g.A % 16 == 0);
-  const bool b_vec = (bkf ? even(g.b_cs) : (g.b_cs == 1 && even(g.b_rs))) && even(g.b_bs) && ((uintptr_t)g.B % 16 == 0);
-  const bool vec = a_vec && b_vec;
-#define GG_LAUNCH(AK, BKK, V) hipLaunchKernelGGL((gemm_gen_kernel<GT, NT, WT, AK, BKK, V>), grid, dim3(NT), 0, ctx->stream, gk, kchunk, part)
-  if (akf && bkf) { if (vec) GG_LAUNCH(true, true, true); else GG_LAUNCH(true, true, false); }
-  else if (akf) { if (vec) GG_LAUNCH(true, false, true); else GG_LAUNCH(true, false, false); }
-  else if (bkf) { if (vec) GG_LAUNCH(false, true, true); else GG_LAUNCH(false, true, false); }
-  else { if (vec) GG_LAUNCH(false, false, true); else GG_LAUNCH(false, false, false); }
-#undef GG_LAUNCH
+// the query of gemm_plan.h for a call on this ctx
+static gemm_plan::Query gemm_query(const dcgp_ctx* ctx, const GenGemm& g) {
+  gemm_plan::Query q;
+  q.M = g.M; q.N = g.N; q.K = g.K; q.batch = g.batch;
+  q.a_rs = g.a_rs; q.a_cs = g.a_cs; q.a_bs = g.a_bs; q.b_rs = g.b_rs; q.b_cs = g.b_cs; q.b_bs = g.b_bs;
+  q.accumulate = g.accumulate != 0; q.colscale = g.colscale != nullptr; q.kscale = g.kscale != nullptr; q.sub = g.sub_v != nullptr;
+  q.lower_only = g.lower_only != 0; q.mirror = g.mirror != 0; q.phi = g.phi != 0;
+  q.a_aligned = (uintptr_t)g.A % 16 == 0; q.b_aligned = (uintptr_t)g.B % 16 == 0;
+  q.same_ab = g.A == g.B;
+  q.null_ptr = !g.A || !g.B || !g.C;
+  q.gemm_tile = ctx->opt.gemm_tile; q.no_syrk = ctx->opt.no_syrk; q.n_cus = ctx->n_cus;
+  return q;
+}
+
+// the partial buffer of a planned split: one per stream (the backward pass runs two chains concurrently)
+static double* gemm_part(dcgp_ctx* ctx, const gemm_plan::Plan& p) {
+  char pname[48];
+  snprintf(pname, sizeof pname, "gemm_gen_part@%p", (void*)ctx->stream);
+  return (double*)ws_get(ctx, pname, (size_t)p.part_doubles * sizeof(double));
+}
+
+static int splitk_reduce_launch(dcgp_ctx* ctx, const GenGemm& g, const gemm_plan::Plan& p, const double* part) {
+  hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)p.reduce_blocks), dim3(256), 0, ctx->stream, g, p.ksplit, part);
   LAUNCH_CHECK(ctx);
-  if (part) {
-    const long total = (long)g.M * g.N * g.batch;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, g, ksplit, part);
-    LAUNCH_CHECK(ctx);
-  }
   return DCGP_OK;
 }
 
-// the symmetric long contraction of the reverse pass on its own kernel (syrk_kscale_kernel): A diag(kscale) A^T, k contiguous, <= 256 rows
-static bool syrk_applies(const dcgp_ctx* ctx, const GenGemm& g) {
-  return !ctx->opt.no_syrk && g.A == g.B && g.a_bs == g.b_bs && g.a_cs == 1 && g.b_rs == 1 && g.a_rs == g.b_cs && g.M == g.N && g.M <= SY_ROWS &&
-         g.M > 128 && g.K >= 8192 && g.lower_only && g.mirror && g.kscale && !g.colscale && !g.sub_v && !g.phi && (g.a_rs & 1) == 0 &&
-         (g.a_bs & 1) == 0 && (uintptr_t)g.A % 16 == 0 && g.batch <= 64 && (long)g.M * g.a_rs * 8 < 0x7fffffffL;
+// the general kernel as planned (gemm_plan.h: plan_general): nothing is decided here, threads and wave tile come from the table the plan reports from
+template <int GT>
+static int gemm_gen_launch(dcgp_ctx* ctx, const GenGemm& g, const gemm_plan::Plan& p) {
+  constexpr int NT = gemm_plan::threads_of(GT), WT = gemm_plan::wave_tile_of(GT);  double* part = nullptr;
+  if (p.ksplit > 1) {
+    part = gemm_part(ctx, p);
+    if (!part) return DCGP_ERR_ALLOC;
+  }
+  const dim3 grid((unsigned)p.grid_x, (unsigned)p.grid_y, (unsigned)p.grid_z);
+  const int kchunk = p.kchunk;
+  GenGemm gk = g;
+  gk.lower_compact = p.lower_compact;
+#define GG_LAUNCH(AK, BKK, V) hipLaunchKernelGGL((gemm_gen_kernel<GT, NT, WT, AK, BKK, V>), grid, dim3(NT), 0, ctx->stream, gk, kchunk, part)
+  if (p.akf && p.bkf) { if (p.vec) GG_LAUNCH(true, true, true); else GG_LAUNCH(true, true, false); }
+  else if (p.akf) { if (p.vec) GG_LAUNCH(true, false, true); else GG_LAUNCH(true, false, false); }
+  else if (p.bkf) { if (p.vec) GG_LAUNCH(false, true, true); else GG_LAUNCH(false, true, false); }
+  else { if (p.vec) GG_LAUNCH(false, false, true); else GG_LAUNCH(false, false, false); }
+#undef GG_LAUNCH
+  LAUNCH_CHECK(ctx);
+  return part ? splitk_reduce_launch(ctx, g, p, part) : DCGP_OK;
 }
-static int syrk_launch(dcgp_ctx* ctx, const GenGemm& g) {
-  const int cus = ctx->n_cus > 0 ? ctx->n_cus : 256;
-  int ksplit = cus / g.batch;   // one workgroup per CU, no second round
-  if (ksplit < 1) ksplit = 1;
-  if (ksplit > g.K / 256) ksplit = g.K / 256;
-  const int kchunk = round_up((g.K + ksplit - 1) / ksplit, SY_KC);
-  ksplit = (g.K + kchunk - 1) / kchunk;
-  char pname[48];
-  snprintf(pname, sizeof pname, "gemm_gen_part@%p", (void*)ctx->stream);
-  double* part = (double*)ws_get(ctx, pname, (size_t)ksplit * g.batch * g.M * g.N * sizeof(double));
+
+// the symmetric long contraction of the reverse pass on its own kernel (syrk_kscale_kernel), as planned (gemm_plan.h: syrk_applies, plan_syrk)
+static int syrk_launch(dcgp_ctx* ctx, const GenGemm& g, const gemm_plan::Plan& p) {
+  double* part = gemm_part(ctx, p);
   if (!part) return DCGP_ERR_ALLOC;
-  const size_t lds = (size_t)(2 * SY_ROWS * SY_LD + 2 * SY_KC) * sizeof(double);
   static bool attr_set[64] = {};   // per device: the attribute is the device's, and a process may hold ctxs on several
   const int dv = ctx->device >= 0 && ctx->device < 64 ? ctx->device : 0;
   if (!attr_set[dv]) {
-    HIP_TRY(ctx, hipFuncSetAttribute((const void*)syrk_kscale_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HIP_TRY(ctx, hipFuncSetAttribute((const void*)syrk_kscale_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
     attr_set[dv] = true;
   }
-  hipLaunchKernelGGL(syrk_kscale_kernel, dim3(ksplit, g.batch), dim3(SY_NT), lds, ctx->stream, g, kchunk, part, sy_blocks_host());
+  hipLaunchKernelGGL(syrk_kscale_kernel, dim3((unsigned)p.grid_x, (unsigned)p.grid_y), dim3(SY_NT), (size_t)p.lds, ctx->stream, g, p.kchunk, part, sy_blocks_host());
   LAUNCH_CHECK(ctx);
-  const long total = (long)g.M * g.N * g.batch;
-  hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, g, ksplit, part);
-  LAUNCH_CHECK(ctx);
-  return DCGP_OK;
+  return splitk_reduce_launch(ctx, g, p, part);
 }
 
 int gemm_gen(dcgp_ctx* ctx, const GenGemm& g) {
-  if (g.M <= 0 || g.N <= 0 || g.batch <= 0) return DCGP_OK;
-  if (!g.A || !g.B || !g.C || g.K < 0) return ctx_fail(ctx, DCGP_ERR_ARG, "gemm_gen: bad arguments");
-  if (syrk_applies(ctx, g)) return syrk_launch(ctx, g);
-  // 256 CUs; 4 co-resident 64-tile workgroups per CU (40 KB LDS each), 2 of the 128-tile ones (72 KB, 1024 threads)
-  // the 1024-thread 128-tile (twice the flop per operand byte) pays off where it can fill its 512 slots, split included:
-  // the tiled batch's contractions (K = 46080 columns at the headline size), M = 1024.  With a few thousand columns and
-  // M = 256 (de-duplicated first layer) its ~270 workgroups lose to ~900 64-tiles (training step 2.05 -> 1.93 ms)
+  // every decision of the launch is plan_gemm's (gemm_plan.h), which the CPU suite reaches through dcgp_debug_plan_gemm
 #ifdef DCGP_EXPERIMENTS
-  static const long big_fill = getenv("DCGP_GEMM_BIG_FILL") ? atol(getenv("DCGP_GEMM_BIG_FILL")) : 512;
-  static const long small_wgs = getenv("DCGP_GEMM_SMALL_WGS") ? atol(getenv("DCGP_GEMM_SMALL_WGS")) : 256;
+  static const long big_fill = getenv("DCGP_GEMM_BIG_FILL") ? atol(getenv("DCGP_GEMM_BIG_FILL")) : gemm_plan::kBigFill;
+  static const long small_wgs = getenv("DCGP_GEMM_SMALL_WGS") ? atol(getenv("DCGP_GEMM_SMALL_WGS")) : gemm_plan::kSmallWgs;
+  const gemm_plan::Plan p = gemm_plan::plan_gemm(gemm_query(ctx, g), big_fill, small_wgs);
 #else
-  constexpr long big_fill = 512, small_wgs = 256;
+  const gemm_plan::Plan p = gemm_plan::plan_gemm(gemm_query(ctx, g));
 #endif
-  if (ctx->opt.gemm_tile == 32) return gemm_gen_launch<32, 256, 16>(ctx, g, 1024);     // A/B switch
-  if (ctx->opt.gemm_tile == 64) return gemm_gen_launch<64, 256, 32>(ctx, g, 1024);
-  if (ctx->opt.gemm_tile == 128) return gemm_gen_launch<128, 1024, 32>(ctx, g, 512);
-  const long tiles128 = (long)((g.M + 127) / 128) * ((g.N + 127) / 128) * g.batch / (g.lower_only ? 2 : 1);
-  if (g.M >= 128 && g.N >= 128 && g.K >= 4096 && tiles128 * (g.K / 512) >= big_fill) return gemm_gen_launch<128, 1024, 32>(ctx, g, 512);
-  // the M x M x M products of the Cholesky / KL adjoint chains would launch a few dozen 64-tile workgroups on 256 CUs and
-  // take as long as one wave needs for its 32 x 32 x K block (K x 64 cycles of fp64 MFMA); 32-tiles with a 16 x 16 block per
-  // wave put four times as many CUs to work on a quarter of that each.  Likewise the long contractions with a narrow
-  // output (d alpha = A1 gm: M x R): a handful of tiles, split into 128-deep chunks instead of 512-deep ones
-  const long wgs = (long)((g.M + 63) / 64) * ((g.N + 63) / 64) * g.batch / (g.lower_only ? 2 : 1);
-  const long max_wgs = wgs * (g.K >= 2048 ? g.K / 512 : 1);   // what the 64-tile configuration could launch, split included
-  if (max_wgs <= small_wgs) return gemm_gen_launch<32, 256, 16>(ctx, g, 1024);
-  return gemm_gen_launch<64, 256, 32>(ctx, g, 1024);
+  switch (p.error) {
+    case gemm_plan::kOk: break;
+    case gemm_plan::kBatchSplit: return ctx_fail(ctx, DCGP_ERR_ARG, "gemm_gen: batch %d x split %d too large", g.batch, p.ksplit);
+    case gemm_plan::kLowerNotSquare: return ctx_fail(ctx, DCGP_ERR_ARG, "gemm_gen: lower_only needs a square output");
+    default: return ctx_fail(ctx, DCGP_ERR_ARG, "gemm_gen: bad arguments");
+  }
+  if (p.route == gemm_plan::kNothing) return DCGP_OK;
+  if (p.route == gemm_plan::kSyrk) return syrk_launch(ctx, g, p);
+  if (p.tile == 32) return gemm_gen_launch<32>(ctx, g, p);
+  if (p.tile == 64) return gemm_gen_launch<64>(ctx, g, p);
+  return gemm_gen_launch<128>(ctx, g, p);
+}
+
+// debugging aid (tests, no device needed): the plan of a call from a flat query; field orders in include/dcgp.h
+extern "C" int dcgp_debug_plan_gemm(const long long* query, int n_query, long long* plan, int n_plan) {
+  using gemm_plan::Plan;
+  using gemm_plan::Query;
+  if (!query || !plan || n_query != Query::kFields || n_plan != Plan::kFields) return DCGP_ERR_ARG;
+  Query q;
+  auto fields = Query::fields(q);
+  static_assert(std::tuple_size<decltype(fields)>::value == Query::kFields, "the flat query covers every field");
+  std::apply([&](auto&... f) { ((f = (long)*query++), ...); }, fields);
+  const Plan p = gemm_plan::plan_gemm(q);
+  const long long flat[Plan::kFields] = {p.route, p.error, p.tile, p.threads, p.wave_tile, p.ksplit, p.kchunk, p.lower_compact, p.akf, p.bkf, p.vec,
+                                         p.grid_x, p.grid_y, p.grid_z, p.part_doubles, p.reduce_blocks, p.lds};
+  memcpy(plan, flat, sizeof flat);
+  return DCGP_OK;
 }
 
 // C-ABI view of the same kernel (tests drive every layout / edge case through it)
 extern "C" int dcgp_gemm_strided(dcgp_ctx* ctx, const double* A, long a_rs, long a_cs, long a_bs, const double* B, long b_rs, long b_cs,
                                  long b_bs, double* C, long c_rs, long c_bs, int M, int N, int K, int batch, double alpha, int accumulate,
-                                 const double* colscale, long cs_s, long cs_bs, const double* kscale, long ks_s, long ks_bs, int lower_only) {
+                                 const double* colscale, long cs_s, long cs_bs, const double* kscale, long ks_s, long ks_bs, int flags) {
   if (!ctx) return DCGP_ERR_ARG;
-  if (!A || !B || !C || M < 0 || N < 0 || K < 0 || batch < 0 || c_rs < N) return ctx_fail(ctx, DCGP_ERR_ARG, "gemm_strided: bad arguments");
+  if (!A || !B || !C || M < 0 || N < 0 || K < 0 || batch < 0 || c_rs < N || (flags & ~3)) return ctx_fail(ctx, DCGP_ERR_ARG, "gemm_strided: bad arguments");
+  // flags bit 0: lower_only, bit 1: mirror, as in dcgp_gemm_strided_ex (0 and 1 are what the argument meant as `lower_only`)
+  if ((flags & 2) && M != N) return ctx_fail(ctx, DCGP_ERR_ARG, "gemm_strided: mirror needs a square result");
+  if ((flags & 2) && !(flags & 1)) return ctx_fail(ctx, DCGP_ERR_ARG, "gemm_strided: mirror goes with lower_only");
   GenGemm g;
   g.A = A; g.a_rs = a_rs; g.a_cs = a_cs; g.a_bs = a_bs;
   g.B = B; g.b_rs = b_rs; g.b_cs = b_cs; g.b_bs = b_bs;
   g.C = C; g.c_rs = c_rs; g.c_bs = c_bs;
   g.M = M; g.N = N; g.K = K; g.batch = batch; g.alpha = alpha; g.accumulate = accumulate;
-  g.colscale = colscale; g.cs_s = cs_s; g.cs_bs = cs_bs; g.kscale = kscale; g.ks_s = ks_s; g.ks_bs = ks_bs; g.lower_only = lower_only;
+  g.colscale = colscale; g.cs_s = cs_s; g.cs_bs = cs_bs; g.kscale = kscale; g.ks_s = ks_s; g.ks_bs = ks_bs; g.lower_only = flags & 1; g.mirror = (flags >> 1) & 1;
   DCGP_TRY(gemm_gen(ctx, g));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return DCGP_OK;

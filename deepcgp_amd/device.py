@@ -155,6 +155,7 @@ _SIGS = {
     "dcgp_debug_set_fused_trace": [_vp, _vp],
     "dcgp_debug_fused_plan": [_vp, _vp],
     "dcgp_debug_plan_layer_launch": [_vp, _i, _vp, _i],
+    "dcgp_debug_plan_gemm": [_vp, _i, _vp, _i],
     "dcgp_debug_head_ride": [_vp, _vp],
     "dcgp_debug_plan_head_ride": [_vp, _i, _vp, _i, C.c_longlong, _vp, _i],
     "dcgp_debug_comm_gate": [_vp, _i, _ip],
@@ -345,12 +346,15 @@ class Context:
         return out
 
     # strided GEMM on device arrays ---------------------------------------------------------------
-    def gemm(self, A, a_strides, B, b_strides, C_out, c_rs, c_bs, M, N, K, batch=1, alpha=1.0, accumulate=False):
+    def gemm(self, A, a_strides, B, b_strides, C_out, c_rs, c_bs, M, N, K, batch=1, alpha=1.0, accumulate=False, flags=0):
         """C_b(i, j) (+)= alpha sum_k A_b(i, k) B_b(k, j) with A_b(i, k) = A[b a_bs + i a_rs + k a_cs] etc. (element strides:
-        ``a_strides = (a_rs, a_cs, a_bs)``); dcgp_gemm_strided, the MFMA fp64 GEMM of csrc/gemm_gen.hip."""
+        ``a_strides = (a_rs, a_cs, a_bs)``); dcgp_gemm_strided, the MFMA fp64 GEMM of csrc/gemm_gen.hip.  ``flags`` bit 0: lower_only (zero
+        above the diagonal), bit 1 (with bit 0, square results): mirror (the lower triangle also stored transposed).
+        The wrapper passes no colscale / kscale, so it always takes the general kernel: the symmetric long contraction's own kernel (kscale with
+        mirror and A == B) is reached through lib().dcgp_gemm_strided directly, as tests/test_gpu_gemm.py does."""
         self._check(lib().dcgp_gemm_strided(self.handle, A.ptr, a_strides[0], a_strides[1], a_strides[2], B.ptr, b_strides[0],
                                             b_strides[1], b_strides[2], C_out.ptr, c_rs, c_bs, M, N, K, batch, float(alpha),
-                                            int(bool(accumulate)), None, 0, 0, None, 0, 0, 0))
+                                            int(bool(accumulate)), None, 0, 0, None, 0, 0, int(flags)))
 
     # multi-GPU ---------------------------------------------------------------------------------
     def comm_init(self, nranks, rank, unique_id):

@@ -626,11 +626,15 @@ int dcgp_model_layer_output(dcgp_model* model, int layer, double* out_sample, do
  * the adjoints of conv_gp/conditionals.py:50,58, runs on it):
  *   C_b(i, j) (+)= alpha * colscale_b[j] * sum_k A_b(i, k) * kscale_b[k] * B_b(k, j),   b = 0 .. batch-1,
  *   A_b(i, k) = A[b a_bs + i a_rs + k a_cs],  B_b(k, j) = B[b b_bs + k b_rs + j b_cs],  C_b(i, j) = C[b c_bs + i c_rs + j];
- * colscale / kscale may be NULL; lower_only writes 0 above the diagonal of a square result.  Device pointers. */
+ * colscale / kscale may be NULL.  flags bit 0: lower_only -- 0 is written above the diagonal (before accumulation); bit 1 (with bit 0, square
+ * results only): mirror -- the entries below the diagonal are also stored transposed and nothing else is written above it (with accumulate:
+ * the lower triangle accumulates, the upper one is its mirror image).  0 and 1 are what this argument meant when it was `lower_only`; other
+ * bits are refused.  kscale with flags = 3 on A == B (k contiguous, 129 .. 256 rows, K >= 8192) is the reverse pass's W_r, which has a kernel
+ * of its own (dcgp_debug_plan_gemm says which kernel serves a call).  Device pointers. */
 int dcgp_gemm_strided(dcgp_ctx* ctx, const double* A, long a_rs, long a_cs, long a_bs, const double* B, long b_rs,
                       long b_cs, long b_bs, double* C, long c_rs, long c_bs, int M, int N, int K, int batch,
                       double alpha, int accumulate, const double* colscale, long cs_s, long cs_bs,
-                      const double* kscale, long ks_s, long ks_bs, int lower_only);
+                      const double* kscale, long ks_s, long ks_bs, int flags);
 /* The same product with the epilogues of the kernel adjoints (dZ = (E X - rowsum(E) o Z) / l^2 and its kin, Murray's Phi of the Cholesky
  * adjoint, symmetric products computed on the lower tiles only):
  *   C_b(i, j) (+)= alpha * (sum_k A_b(i, k) B_b(k, j) - sub_v[b sv_bs + i] * sub_x[b sx_bs + i sx_rs + j])      (sub_v, sub_x: both or neither)
@@ -684,6 +688,17 @@ int dcgp_debug_fused_plan(dcgp_ctx* ctx, int* out4);
  *   each an IEEE double BIT-CAST into its 64-bit slot (0.0: not simulated): one item per strip, prologues ahead, replicas sharing a prologue}.
  * dcgp_debug_fused_plan's four values are persist, n_items, pre_n and pre_D of the plan of the launch.  DCGP_ERR_ARG unless n_query == 29, n_plan == 24. */
 int dcgp_debug_plan_layer_launch(const long long* query, int n_query, long long* plan, int n_plan);
+/* How a call of the strided GEMM is launched (csrc/gemm_plan.h, plan_gemm: the function gemm_gen() itself launches from), for a call described by
+ * integers alone: needs no ctx and no device.
+ * query[24] = {M, N, K, batch, a_rs, a_cs, a_bs, b_rs, b_cs, b_bs, accumulate, colscale given, kscale given, sub_v / sub_x given, lower_only, mirror,
+ *   phi, the A pointer is a multiple of 16 bytes, the B pointer is, A and B are the same pointer, one of A / B / C is NULL, then the ctx options
+ *   gemm_tile and no_syrk, n_cus (compute units of the device)}.
+ * plan[17] = {route (0: nothing to do, 1: gemm_gen_kernel, 2: syrk_kscale_kernel), error (0: none, 1: bad arguments, 2: batch x split > 65535,
+ *   3: a lower_only result on the compact grid that is not square; with an error nothing is launched), tile, threads, tile of a wave, ksplit (1: direct
+ *   store), kchunk (columns of a range), lower_compact (the grid enumerates the tiles on / below the diagonal only), AKF, BKF, VEC (the kernel's
+ *   template switches), grid x, y, z, doubles of the partial buffer, workgroups of the reduction behind it (both 0 unless split), dynamic LDS bytes}.
+ * DCGP_ERR_ARG unless n_query == 24, n_plan == 17. */
+int dcgp_debug_plan_gemm(const long long* query, int n_query, long long* plan, int n_plan);
 /* Head rows riding the layer kernel's persistent launch (csrc/fused_plan.h, plan_head_ride; ctx option head_ride, 0: never).
  * dcgp_debug_head_ride: out2 = {head rows the ctx's most recent layer-kernel launch carried (0: none), launches of the ctx that carried any}.
  * dcgp_debug_plan_head_ride (no ctx, no device): the decision for the launch that `query` (as above) is planned as and

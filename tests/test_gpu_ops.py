@@ -841,7 +841,8 @@ def test_kmeans_matches_numpy_lloyd(ctx):
 def test_strided_gemm_layouts_edges_and_epilogues(ctx, mode):
     """dcgp_gemm_strided (csrc/gemm_gen.hip, every product of the reverse pass): all four operand layouts, sizes off the
     tile grid, batches, accumulation, column / k scaling, lower-triangular output, long contractions through the
-    deterministic split-k path (64- and 128-tile kernels) -- against NumPy."""
+    deterministic split-k path -- against NumPy.  Every run below takes the 32-tile configuration <32, 256, 16> (the launch plan of each
+    is pinned in tests/test_host_gemm_plan.py); the 64 and 128 tiles are the business of tests/test_gpu_gemm.py."""
     from deepcgp_amd import device as dev
     L = dev.lib()
     rng = np.random.default_rng(1)
@@ -880,16 +881,17 @@ def test_strided_gemm_layouts_edges_and_epilogues(ctx, mode):
     run(37, 53, 19, batch=3, alpha=-0.5)
     run(64, 64, 16, accumulate=True)
     run(65, 129, 33, colscale=True, kscale=True)
-    run(96, 96, 40, batch=2, lower=True)                        # rectangular grid, zeros above the diagonal
-    run(96, 96, 40, batch=2, lower=True, accumulate=True)       # compact lower-tile grid
-    run(20, 7, 5000, kscale=True)                               # split-k, 64-tile kernel
-    run(130, 130, 4100, batch=2, lower=True, alpha=2.0)         # split-k, 128-tile kernel, compact grid
-    run(256, 25, 9000, accumulate=True)                         # tall contraction into a narrow result
+    run(96, 96, 40, batch=2, lower=True)                        # 32 tile, rectangular grid, zeros above the diagonal
+    run(96, 96, 40, batch=2, lower=True, accumulate=True)       # 32 tile, compact lower-tile grid
+    run(20, 7, 5000, kscale=True)                               # 32 tile, split-k in 35 ranges
+    run(130, 130, 4100, batch=2, lower=True, alpha=2.0)         # 32 tile, split-k in 29 ranges, compact grid
+    run(256, 25, 9000, accumulate=True)                         # tall contraction into a narrow result: 32 tile, 63 ranges
 
 
 def test_strided_gemm_adjoint_epilogues(ctx):
     """dcgp_gemm_strided_ex: the row-scaled correction (E X - rowsum(E) o Z), Murray's Phi and the mirrored store of a symmetric
-    product, direct store and split-k, batches, accumulation -- against NumPy."""
+    product, direct store and split-k, batches, accumulation -- against NumPy.  Every run takes the 32-tile configuration (planned in
+    tests/test_host_gemm_plan.py; the other tiles: tests/test_gpu_gemm.py)."""
     from deepcgp_amd import device as dev
     L = dev.lib()
     rng = np.random.default_rng(2)
@@ -921,10 +923,10 @@ def test_strided_gemm_adjoint_epilogues(ctx):
             assert err <= 1e-11 * max(np.abs(want).max(), 1.0) * max(K, 1) ** 0.5, (M, N, K, batch, flags, err)
             assert np.array_equal(out[b][:, N:], C0[b][:, N:])
     run(37, 53, 19, batch=2, alpha=0.7, sub=True)
-    run(256, 25, 9000, accumulate=True, sub=True)               # split-k: the correction in the reduction's epilogue
+    run(256, 25, 9000, accumulate=True, sub=True)               # split-k (32 tile, 63 ranges): the correction in the reduction's epilogue
     run(70, 70, 33, batch=3, flags=4)                           # Phi, direct store
-    run(40, 40, 3000, flags=4, alpha=-1.0)                      # Phi behind split-k (32-tile kernel)
-    run(96, 96, 40, batch=2, flags=3, sym=True)                 # mirrored store, rectangular grid
-    run(130, 130, 4100, batch=2, flags=3, sym=True, alpha=2.0)  # mirrored store, split-k, 128-tile kernel, compact grid
+    run(40, 40, 3000, flags=4, alpha=-1.0)                      # Phi behind split-k (32 tile, 21 ranges)
+    run(96, 96, 40, batch=2, flags=3, sym=True)                 # mirrored store, 32 tile, rectangular grid
+    run(130, 130, 4100, batch=2, flags=3, sym=True, alpha=2.0)  # mirrored store, split-k (32 tile, 29 ranges), compact grid
     with pytest.raises(dev.DcgpError):
         run(8, 9, 4, flags=1)                                    # lower_only needs a square result
