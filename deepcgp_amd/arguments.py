@@ -36,6 +36,8 @@ FLAGS = (
     ("--mean-filter", str, "centre0", "initial filter of the conv layers' mean function (needs --identity-mean): centre0 (Conv2dMean's: channel 0 into map 0) | channels (every channel into its own map) | sum (every channel into every map)"),
     ("--train-mean", None, False, "train the mean function's filter with the other parameters (needs --identity-mean)"),
     ("--load-model", str, None, "checkpoint (.npy, reference key set) to start from"),
+    ("--keep-optimizer", None, False, "write the optimiser's state (Adam moments, step count, minibatch generator) beside every checkpoint as <name>.opt.npz; with --load-model X, continue from X.opt.npz: the resumed run is the interrupted one, bit for bit"),
+    ("--clip-norm", float, 0.0, "clip every Adam / SGD step's gradient to this global norm on the device and log the period's mean pre-clip norm (grad_norm); 0 = off"),
 )
 REQUIRED = ("--name",)
 
@@ -95,6 +97,14 @@ def parse_test_views(flags):
     if shift == 0 and not flip:
         return None
     return views(shift, flip, pattern)
+
+
+def parse_clip_norm(flags):
+    """``--clip-norm`` as a float: 0.0 (off) when the flag is absent; a negative value or NaN raises ValueError."""
+    value = float(getattr(flags, "clip_norm", 0.0) or 0.0)
+    if not value >= 0.0:
+        raise ValueError("--clip-norm: must be >= 0 (0 = off), got %r" % (value,))
+    return value
 
 
 def train_steps(flags):

@@ -1734,6 +1734,7 @@ static int elbo_grad_run(dcgp_model* model, const double* X, const int32_t* y, i
   model->grad_follows = false;
   model->gkl_state = 0;
   if (rc != DCGP_OK) {
+    model->norm_pending = false;   // (a failed step records no norm)
     for (bool& f : model->kl_early) f = false;
     for (int& f : model->prep_early) f = 0;
     hipStreamSynchronize(ctx->stream);
@@ -1764,6 +1765,7 @@ int dcgp_model_train_step_adam_f64y(dcgp_model* model, const double* X, const do
                                     uint64_t seed, int dedup_layer0, double lr, double beta1, double beta2, double eps, int t, double* out_host,
                                     int* info_host) {
   if (!model || !X || !y || N <= 0 || !out_host) return model ? ctx_fail(model->ctx, DCGP_ERR_ARG, "train_step_adam_f64y: bad args") : DCGP_ERR_ARG;
+  model->grad_norms.clear();   // (a run clears once, in front of its first step)
   return train_step_adam_run(model, X, nullptr, N, scale, z_per_layer_host, seed, dedup_layer0, lr, beta1, beta2, eps, t, out_host, info_host, y);
 }
 
@@ -1771,6 +1773,7 @@ int dcgp_model_train_step_adam(dcgp_model* model, const double* X, const int32_t
                                uint64_t seed, int dedup_layer0, double lr, double beta1, double beta2, double eps, int t, double* out_host,
                                int* info_host) {
   if (!model || !X || !y || N <= 0 || !out_host) return model ? ctx_fail(model->ctx, DCGP_ERR_ARG, "train_step_adam: bad args") : DCGP_ERR_ARG;
+  model->grad_norms.clear();   // (a run clears once, in front of its first step)
   return train_step_adam_run(model, X, y, N, scale, z_per_layer_host, seed, dedup_layer0, lr, beta1, beta2, eps, t, out_host, info_host, nullptr);
 }
 

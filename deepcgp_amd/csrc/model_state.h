@@ -33,6 +33,13 @@ struct dcgp_model {
   int prep_early[8] = {};    // per layer: bit 0 its zero fills, G^T and the factor's lower triangle, bit 1 S_r = G_r G_r^T were enqueued by grad_kl_early
   bool kl_early[8] = {};     // per layer: grad_kl_early enqueued its kl_products for the step in flight (consumed by model_backward)
   int adam_t = 0;        // Adam steps taken on this model's moment buffers (bias correction; dcgp_model_adam_step with t = 0)
+  // clipping by global norm (dcgp_model_set_grad_clip; optim.hip): 0 = off.  d_clip[0]: the step's scale c, read by the update; d_clip[1 ..]: the
+  // norm's per-block partial sums (grow-only, allocated with the first clipped step).  grad_norms: the pre-clip norms of the most recent
+  // optimiser call's steps (opt_readback appends one per step; the entry points clear it)
+  double grad_clip = 0.0;
+  double* d_clip = nullptr; size_t clip_cap = 0;
+  bool norm_pending = false;   // the step in flight left its norm in the pinned slot
+  std::vector<double> grad_norms;
   int shard_lo = 0, shard_global = 0;   // this rank's first image and the global batch (dcgp_model_set_shard): device-RNG counters
   int grad_exchange = 0; // multi-rank training step (dcgp_model_train_step_adam): 0 all-reduce of every layer's gradient block + the full update on every rank,
                          // 1 reduce-scatter -> Adam on this rank's shard -> all-gather of the parameters (dcgp_model_set_grad_exchange)
@@ -104,7 +111,7 @@ struct dcgp_model {
   long image_len() const { const auto& v = layers[0]->v; return (long)(v.H - 2 * pad[0]) * (v.W - 2 * pad[0]) * v.C; }
 
   ~dcgp_model() {
-    hipFree(ds_X); hipFree(ds_Y); hipFree(run_idx); hipFree(run_X); hipFree(run_Y); hipFree(d_eval_views);
+    hipFree(ds_X); hipFree(ds_Y); hipFree(run_idx); hipFree(run_X); hipFree(run_Y); hipFree(d_eval_views); hipFree(d_clip);
     if (h_ring) hipHostFree(h_ring);
     for (auto& e : ring_ev) if (e) hipEventDestroy(e);
     for (auto& gs : groups) for (auto& gr : gs) gr.release();

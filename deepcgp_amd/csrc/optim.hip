@@ -21,6 +21,7 @@ struct OptGroup {
   long off; int layer, frozen;
   int hold;                                           // hyp_layer >= 0: bit i set = element i of the triple is held (set_trainable on one ArcCosine parameter)
 };
+constexpr int kNormSlot = 32;        // ctx->h_scratch[32]: a clipped step's norm (the hyper-parameter triples take [0, 24))
 constexpr int OPT_GROUPS_MAX = 56;   // 8 layers of up to 6 groups, and a mean filter on each of the 7 conv layers below a head
 struct OptArgs {
   OptGroup grp[OPT_GROUPS_MAX];
@@ -36,7 +37,64 @@ struct OptArgs {
   int sharded, stage_only;
   long sh_lo[8], sh_hi[8];
   double* stage[8];
+  // Clipping by global norm (dcgp_model_set_grad_clip; the CLIP instance of the update and the two norm kernels only): clip[0] the step's scale c,
+  // clip[1 + b] block b's partial sum of g_u^2; norm_out: the pinned slot the norm itself goes to
+  double* clip;
+  double max_norm;
+  double* norm_out;
 };
+// The gradient the update moves element i of group G by, in the unconstrained space, as the two factors the update multiplies: g_u = g * f, g the
+// gradient with respect to the constrained value x and f = dx/du (1, or sigmoid(u) = 1 - exp(-y) under transform 1).  false: the update leaves the
+// element where it is (a frozen group, a held element of a hyper-parameter triple) -- it is no part of the norm either.  The clipped update and the
+// norm both take g_u from here.
+__device__ __forceinline__ bool opt_grad_u(const OptGroup& G, long i, double x, double* g, double* f) {
+  if (G.frozen || (G.hyp_layer >= 0 && ((G.hold >> (int)i) & 1))) return false;
+  *g = G.g[i];
+  *f = G.transform == 1 ? -expm1(-(x - 1e-6)) : 1.0;
+  return true;
+}
+// the sum of v over a block of 256 threads (four waves of 64), the same tree every time: lanes by halving within a wave, then the four waves' sums
+// through LDS.  Every thread of the block calls it; every thread gets the sum.
+__device__ __forceinline__ double block_sum_256(double v, double* red /* 4 doubles of LDS */) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
+// Norm, first stage: the update's grid over the update's group table; block b leaves the sum of g_u^2 over its 256 elements in clip[1 + b].  (The
+// parameter is read where the transform needs it only: the large groups are identity-transform.)
+__global__ __launch_bounds__(256) void opt_norm_partial_kernel(OptArgs a) {
+  if (a.status && *a.status != 0.0) return;
+  __shared__ double red[4];
+  int gi = 0;
+  while (gi + 1 < a.ng && (int)blockIdx.x >= a.first_block[gi + 1]) ++gi;
+  const OptGroup& G = a.grp[gi];
+  const long i = (long)((int)blockIdx.x - a.first_block[gi]) * 256 + threadIdx.x;
+  double sq = 0.0;
+  if (i < G.n) {
+    const double x = G.transform != 1 ? 0.0 : (G.hyp_layer >= 0 ? a.hyp_in[G.hyp_layer][i] : G.p[i]);
+    double g, f;
+    if (opt_grad_u(G, i, x, &g, &f)) { const double gu = g * f; sq = gu * gu; }
+  }
+  const double sum = block_sum_256(sq, red);
+  if (threadIdx.x == 0) a.clip[1 + blockIdx.x] = sum;
+}
+// Norm, second stage (one block): thread t adds the partial sums t, t + 256, ... in index order, the 256 results go through the same tree -- the
+// value depends on the partial sums alone, not on which block wrote when.  Leaves the scale in clip[0] and the norm in the pinned slot.
+__global__ __launch_bounds__(256) void opt_norm_final_kernel(OptArgs a, int nb) {
+  if (a.status && *a.status != 0.0) return;
+  __shared__ double red[4];
+  double s = 0.0;
+  for (int b = threadIdx.x; b < nb; b += 256) s += a.clip[1 + b];
+  const double sum = block_sum_256(s, red);
+  if (threadIdx.x == 0) {
+    const double norm = sqrt(sum);
+    a.clip[0] = norm <= a.max_norm ? 1.0 : a.max_norm / norm;   // max_norm / max(norm, max_norm), and 1.0 for max_norm = +inf
+    *a.norm_out = norm;
+  }
+}
+// CLIP: the step on c * g_u, c from clip[0] (the norm kernels in front of it); the other instance is the step as it always was and reads nothing of it
+template <bool CLIP>
 __global__ __launch_bounds__(256) void opt_step_kernel(OptArgs a) {
   if (a.status && *a.status != 0.0) return;
   int gi = 0;
@@ -47,7 +105,38 @@ __global__ __launch_bounds__(256) void opt_step_kernel(OptArgs a) {
   if (a.sharded && (G.off + i < a.sh_lo[G.layer] || G.off + i >= a.sh_hi[G.layer])) return;
   const double x = G.hyp_layer >= 0 ? a.hyp_in[G.hyp_layer][i] : G.p[i];
   double out;
-  if (G.frozen || (G.hyp_layer >= 0 && ((G.hold >> (int)i) & 1))) {
+  if constexpr (CLIP) {
+    const double c = a.clip[0];
+    double g, f;
+    if (!opt_grad_u(G, i, x, &g, &f)) {
+      out = x;
+    } else if (a.sgd) {   // (the products in the unclipped step's order: c == 1.0 is that step to the bit)
+      const double gr = c * g;
+      if (G.transform == 1) {
+        const double y = x - 1e-6;
+        double u = y > 35.0 ? y : log(expm1(y));
+        u += a.lr * gr * f;
+        out = (u > 35.0 ? u : log1p(exp(u))) + 1e-6;
+      } else {
+        out = x + a.lr * gr;
+      }
+    } else {
+      double gr = -g;
+      double u = x;
+      if (G.transform == 1) {
+        const double y = x - 1e-6;
+        u = y > 35.0 ? y : log(expm1(y));
+        gr *= f;
+      }
+      gr *= c;
+      const double mi = a.b1 * G.m[i] + (1.0 - a.b1) * gr;
+      const double vi = a.b2 * G.v[i] + (1.0 - a.b2) * gr * gr;
+      G.m[i] = mi;
+      G.v[i] = vi;
+      u -= a.lr * mi / (sqrt(vi) + a.eps);
+      out = G.transform == 1 ? (u > 35.0 ? u : log1p(exp(u))) + 1e-6 : u;
+    }
+  } else if (G.frozen || (G.hyp_layer >= 0 && ((G.hold >> (int)i) & 1))) {
     out = x;
   } else if (a.sgd) {   // plain gradient ascent on the ELBO in the unconstrained space
     const double gr = G.g[i];
@@ -106,6 +195,12 @@ int opt_enqueue(dcgp_model* model, const char* who, bool sgd, double lr, double 
   if (nl > 8) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: at most 8 layers", who);
   const bool comm_sharded = ctx->comm && ctx->nranks > 1 && model->grad_exchange == 1 && model->grad_scattered;
   const bool sharded = comm_sharded || vranks > 0;
+  const bool clip = model->grad_clip > 0.0;
+  model->norm_pending = false;
+  // a rank of a sharded update holds its shard of the gradient only: the norm would need an exchange of its own
+  if (clip && sharded)
+    return ctx_fail(ctx, DCGP_ERR_ARG, "%s: gradient clipping is on (dcgp_model_set_grad_clip) and the update is sharded (exchange mode 1): a rank sees "
+                    "only its shard of the gradient, the global norm is not formed across ranks", who);
   ++model->param_version;   // the parameters change: parameter-only state of earlier steps is not reused (model_state.h)
   // Moments are rank-local in exchange mode 1: a rank holds m / v of its own shard only.  A full update on top of them (exchange mode 0, or an
   // optimiser step behind dcgp_elbo_grad) would move every element outside the shard with stale or zero moments -- differently on every rank.
@@ -161,15 +256,40 @@ int opt_enqueue(dcgp_model* model, const char* who, bool sgd, double lr, double 
   }
   a.first_block[a.ng] = nb;
   if (nb <= 0) return DCGP_OK;
-  hipLaunchKernelGGL(opt_step_kernel, dim3(nb), dim3(256), 0, ctx->stream, a);
-  LAUNCH_CHECK(ctx);
+  if (clip) {   // norm and scale behind the gradient, in front of the update, on the step's stream
+    if (model->clip_cap < (size_t)nb + 1) {
+      HIP_TRY(ctx, hipDeviceSynchronize());   // (nothing may still read the smaller buffer)
+      hipFree(model->d_clip); model->d_clip = nullptr; model->clip_cap = 0;
+      if (hipMalloc((void**)&model->d_clip, ((size_t)nb + 1) * sizeof(double)) != hipSuccess)
+        return ctx_fail(ctx, DCGP_ERR_ALLOC, "%s: allocation of the norm's %d partial sums failed", who, nb);
+      model->clip_cap = (size_t)nb + 1;
+    }
+    a.clip = model->d_clip; a.max_norm = model->grad_clip; a.norm_out = a.host_out + kNormSlot;
+    {
+      ScopedTimer tm(ctx, "opt_norm");
+      hipLaunchKernelGGL(opt_norm_partial_kernel, dim3(nb), dim3(256), 0, ctx->stream, a);
+      LAUNCH_CHECK(ctx);
+      hipLaunchKernelGGL(opt_norm_final_kernel, dim3(1), dim3(256), 0, ctx->stream, a, nb);
+      LAUNCH_CHECK(ctx);
+    }
+    ScopedTimer tm(ctx, "opt_step_clip");
+    hipLaunchKernelGGL(opt_step_kernel<true>, dim3(nb), dim3(256), 0, ctx->stream, a);
+    LAUNCH_CHECK(ctx);
+    model->norm_pending = true;
+    return DCGP_OK;
+  }
+  {
+    ScopedTimer tm(ctx, "opt_step");
+    hipLaunchKernelGGL(opt_step_kernel<false>, dim3(nb), dim3(256), 0, ctx->stream, a);
+    LAUNCH_CHECK(ctx);
+  }
   if (!sharded) return DCGP_OK;
   if (vranks > 0) {   // the other ranks' shards: into the staging block only
     for (int r = 1; r < vranks; ++r) {
       OptArgs b = a;
       b.stage_only = 1;
       for (int li = 0; li < nl; ++li) DCGP_TRY(dcgp_shard_range((long)model->layers[li]->grad_block_count(), vranks, r, &b.sh_lo[li], &b.sh_hi[li], nullptr));
-      hipLaunchKernelGGL(opt_step_kernel, dim3(nb), dim3(256), 0, ctx->stream, b);
+      hipLaunchKernelGGL(opt_step_kernel<false>, dim3(nb), dim3(256), 0, ctx->stream, b);
       LAUNCH_CHECK(ctx);
     }
   } else {
@@ -183,6 +303,10 @@ int opt_enqueue(dcgp_model* model, const char* who, bool sgd, double lr, double 
 int opt_readback(dcgp_model* model) {
   const double* h = model->ctx->h_scratch;
   const int nl = (int)model->layers.size();
+  if (model->norm_pending) {   // a clipped step: its pre-clip norm, beside the triples
+    model->grad_norms.push_back(h[kNormSlot]);
+    model->norm_pending = false;
+  }
   for (int li = 0; li < nl; ++li) {
     LayerState& L = *model->layers[li];
     if (L.frozen & 16u) continue;
@@ -208,6 +332,7 @@ int dcgp_model_adam_step(dcgp_model* model, double lr, double beta1, double beta
   // what tf.train.AdamOptimizer's beta powers do for a freshly built optimiser, whatever global_step a checkpoint carried
   if (t == 0) t = ++model->adam_t; else model->adam_t = t;
   const double lr_t = lr * sqrt(1.0 - pow(beta2, (double)t)) / (1.0 - pow(beta1, (double)t));
+  model->grad_norms.clear();
   return opt_step(model, "adam_step", false, lr_t, beta1, beta2, eps);
 }
 
@@ -228,13 +353,18 @@ int dcgp_model_set_grad_exchange(dcgp_model* model, int mode) {
 int dcgp_model_debug_sharded_adam(dcgp_model* model, int ranks, double lr, double beta1, double beta2, double eps, int t) {
   if (!model || ranks < 1 || t < 0 || !(lr > 0) || !(beta1 >= 0 && beta1 < 1) || !(beta2 >= 0 && beta2 < 1) || !(eps > 0))
     return model ? ctx_fail(model->ctx, DCGP_ERR_ARG, "debug_sharded_adam: bad arguments") : DCGP_ERR_ARG;
+  if (model->grad_clip > 0.0)   // (refused in front of the step count: opt_enqueue's own check is the multi-rank step's)
+    return ctx_fail(model->ctx, DCGP_ERR_ARG, "debug_sharded_adam: gradient clipping is on (dcgp_model_set_grad_clip) and the update is sharded: a rank sees "
+                    "only its shard of the gradient, the global norm is not formed across ranks");
   if (t == 0) t = ++model->adam_t; else model->adam_t = t;
   const double lr_t = lr * sqrt(1.0 - pow(beta2, (double)t)) / (1.0 - pow(beta1, (double)t));
+  model->grad_norms.clear();
   return opt_step(model, "debug_sharded_adam", false, lr_t, beta1, beta2, eps, ranks);
 }
 
 int dcgp_model_sgd_step(dcgp_model* model, double lr) {
   if (!model || !(lr > 0)) return model ? ctx_fail(model->ctx, DCGP_ERR_ARG, "sgd_step: bad arguments") : DCGP_ERR_ARG;
+  model->grad_norms.clear();
   return opt_step(model, "sgd_step", true, lr, 0.0, 0.0, 0.0);
 }
 
@@ -358,6 +488,97 @@ int dcgp_model_get_grad(dcgp_model* model, int layer, const char* which, double*
   if (count != n) return ctx_fail(ctx, DCGP_ERR_ARG, "get_grad(%s): expected %zu values, got %zu", which, n, count);
   HIP_TRY(ctx, hipMemcpyAsync(out_host, src, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return DCGP_OK;
+}
+
+// Adam's moments of one parameter group (names as dcgp_model_get_param's groups; "hyper": the triple, "likelihood": the model's one slot)
+static int adam_group(dcgp_model* model, int layer, const char* which, const char* who, size_t count, double** m, double** v) {
+  dcgp_ctx* ctx = model->ctx;
+  if (model->sharded_steps > 0)
+    return ctx_fail(ctx, DCGP_ERR_ARG, "%s: %llu sharded Adam steps were taken on this model (exchange mode 1): its moments cover this rank's shard only",
+                    who, (unsigned long long)model->sharded_steps);
+  size_t n = 0;
+  if (!strcmp(which, "likelihood")) {   // model-wide, `layer` is ignored
+    if (!model->d_lik || (model->lik_kind != 1 && model->lik_kind != 4))
+      return ctx_fail(ctx, DCGP_ERR_ARG, "%s(likelihood): this model's likelihood has no trainable parameter", who);
+    *m = model->d_lik + 1; *v = model->d_lik + 2; n = 1;
+  } else {
+    if (layer < 0 || layer >= (int)model->layers.size()) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: no layer %d", who, layer);
+    LayerState& L = *model->layers[layer];
+    DCGP_TRY(L.ensure_adam());
+    double* const* mv = nullptr;
+    if (!strcmp(which, "Z")) { mv = L.aZ; n = (size_t)L.M * L.v.L; }
+    else if (!strcmp(which, "q_mu")) { mv = L.aq_mu; n = (size_t)L.M * L.R; }
+    else if (!strcmp(which, "q_sqrt")) { mv = L.aq_sqrt; n = (size_t)L.R * L.M * L.M; }
+    else if (!strcmp(which, "hyper")) { mv = L.ahyp; n = 3; }
+    else if (!strcmp(which, "w")) {
+      if (!L.is_head || !L.w) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: only the head has patch weights", who);
+      mv = L.aw; n = (size_t)L.v.P;
+    } else if (!strcmp(which, "ard_lengthscales")) {
+      if (!L.ard) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: this layer has no ARD lengthscales", who);
+      mv = L.aard; n = (size_t)L.v.L;
+    } else if (!strcmp(which, "mean_filter")) {
+      if (!L.mean_W) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: this layer has no mean filter", who);
+      mv = L.amean_W; n = L.mean_slots();
+    } else return ctx_fail(ctx, DCGP_ERR_ARG, "%s: unknown parameter group '%s'", who, which);
+    if (!mv[0] || !mv[1]) return ctx_fail(ctx, DCGP_ERR_ARG, "%s(%s): the group has no moment buffers", who, which);
+    *m = mv[0]; *v = mv[1];
+  }
+  if (count != n) return ctx_fail(ctx, DCGP_ERR_ARG, "%s(%s): expected %zu values, got %zu", who, which, n, count);
+  return DCGP_OK;
+}
+
+int dcgp_model_get_adam_state(dcgp_model* model, int layer, const char* which, double* m_host, double* v_host, size_t count) {
+  if (!model || !which || !m_host || !v_host) return model ? ctx_fail(model->ctx, DCGP_ERR_ARG, "get_adam_state: NULL pointer") : DCGP_ERR_ARG;
+  dcgp_ctx* ctx = model->ctx;
+  double *m = nullptr, *v = nullptr;
+  DCGP_TRY(adam_group(model, layer, which, "get_adam_state", count, &m, &v));
+  HIP_TRY(ctx, hipMemcpyAsync(m_host, m, count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(v_host, v, count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return DCGP_OK;
+}
+
+int dcgp_model_set_adam_state(dcgp_model* model, int layer, const char* which, const double* m_host, const double* v_host, size_t count) {
+  if (!model || !which || !m_host || !v_host) return model ? ctx_fail(model->ctx, DCGP_ERR_ARG, "set_adam_state: NULL pointer") : DCGP_ERR_ARG;
+  dcgp_ctx* ctx = model->ctx;
+  if (model->enq_seq != model->col_seq) return ctx_fail(ctx, DCGP_ERR_ARG, "set_adam_state: enqueued steps are still to be collected");
+  double *m = nullptr, *v = nullptr;
+  DCGP_TRY(adam_group(model, layer, which, "set_adam_state", count, &m, &v));
+  HIP_TRY(ctx, hipMemcpyAsync(m, m_host, count * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(v, v_host, count * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return DCGP_OK;
+}
+
+int dcgp_model_get_adam_t(dcgp_model* model, int* t) {
+  if (!model || !t) return model ? ctx_fail(model->ctx, DCGP_ERR_ARG, "get_adam_t: NULL pointer") : DCGP_ERR_ARG;
+  *t = model->adam_t;
+  return DCGP_OK;
+}
+
+int dcgp_model_set_adam_t(dcgp_model* model, int t) {
+  if (!model) return DCGP_ERR_ARG;
+  if (t < 0) return ctx_fail(model->ctx, DCGP_ERR_ARG, "set_adam_t: t must be >= 0, got %d", t);
+  if (model->enq_seq != model->col_seq) return ctx_fail(model->ctx, DCGP_ERR_ARG, "set_adam_t: enqueued steps are still to be collected");
+  model->adam_t = t;
+  return DCGP_OK;
+}
+
+int dcgp_model_set_grad_clip(dcgp_model* model, double max_norm) {
+  if (!model) return DCGP_ERR_ARG;
+  if (!(max_norm >= 0.0)) return ctx_fail(model->ctx, DCGP_ERR_ARG, "set_grad_clip: max_norm must be >= 0 (0: off, +inf: measure only), got %g", max_norm);
+  if (model->enq_seq != model->col_seq) return ctx_fail(model->ctx, DCGP_ERR_ARG, "set_grad_clip: enqueued steps are still to be collected");
+  model->grad_clip = max_norm;
+  model->grad_norms.clear();
+  return DCGP_OK;
+}
+
+int dcgp_model_grad_norms(dcgp_model* model, double* out_host, int cap, int* count_out) {
+  if (!model || !count_out || cap < 0 || (cap > 0 && !out_host)) return model ? ctx_fail(model->ctx, DCGP_ERR_ARG, "grad_norms: bad arguments") : DCGP_ERR_ARG;
+  const int n = (int)model->grad_norms.size();
+  *count_out = n;
+  for (int i = 0; i < n && i < cap; ++i) out_host[i] = model->grad_norms[i];
   return DCGP_OK;
 }
 

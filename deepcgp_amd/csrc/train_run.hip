@@ -135,6 +135,7 @@ int dcgp_model_train_run_adam(dcgp_model* model, const int32_t* idx_host, int st
   int32_t* yb32 = D ? nullptr : (int32_t*)model->run_Y;
   double* ybf = D ? (double*)model->run_Y : nullptr;
   const bool augment = model->augmenting();
+  model->grad_norms.clear();   // clipping on: every step's wait leaves its pre-clip norm here (opt_readback)
   for (int i = 0; i < steps; ++i) {
     if (augment) {   // the same rows, each shifted and flipped by the draw of (this step's seed, its batch position)
       DCGP_TRY(gather_augment_batch(model, model->run_idx + (size_t)i * batch, batch, seed0 + (uint64_t)i, y32, yf, D, yb32, ybf));

@@ -118,6 +118,12 @@ _SIGS = {
     "dcgp_debug_conv_mean_time": [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _dp],
     "dcgp_model_grad_block": [_vp, _i, C.POINTER(_vp), C.POINTER(C.c_size_t)],
     "dcgp_model_sgd_step": [_vp, _d],
+    "dcgp_model_get_adam_state": [_vp, _i, C.c_char_p, _vp, _vp, C.c_size_t],
+    "dcgp_model_set_adam_state": [_vp, _i, C.c_char_p, _vp, _vp, C.c_size_t],
+    "dcgp_model_get_adam_t": [_vp, _ip],
+    "dcgp_model_set_adam_t": [_vp, _i],
+    "dcgp_model_set_grad_clip": [_vp, _d],
+    "dcgp_model_grad_norms": [_vp, _vp, _i, _ip],
     "dcgp_model_set_grad_exchange": [_vp, _i],
     "dcgp_model_debug_sharded_adam": [_vp, _i, _d, _d, _d, _d, _i],
     "dcgp_shard_range": [C.c_long, _i, _i, C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_long)],

@@ -714,6 +714,98 @@ class DGP_Base:
         """Plain gradient ascent step in the unconstrained space (the "SGD" branch, conv_gp/experiment.py:100-103)."""
         self._ctx._check(dev.lib().dcgp_model_sgd_step(self._model, float(lr)))
 
+    # ---- optimiser state and gradient clipping ----------------------------------------------------
+    def _optimizer_groups(self):
+        """[(key prefix, layer, group name, shape)] of every parameter group the device optimiser keeps Adam moments for
+        (dcgp_model_get_adam_state's names), in the groups' own shapes."""
+        out = []
+        for li, l in enumerate(self.layers):
+            head = li == len(self.layers) - 1
+            base = "layers/%d/" % li
+            out.append((base + "Z", li, "Z", np.shape(l.feature.Z)))
+            out.append((base + "q_mu", li, "q_mu", np.shape(l.q_mu)))
+            out.append((base + "q_sqrt", li, "q_sqrt", np.shape(l.q_sqrt)))
+            if head:      # (a dense head keeps its single weight's slot)
+                out.append((base + "w", li, "w", (int(np.size(l.kern.patch_weights)) if hasattr(l.kern, "patch_weights") else 1,)))
+            out.append((base + "hyper", li, "hyper", (3,)))
+            if head and getattr(l.kern, "ARD", False):
+                out.append((base + "ard_lengthscales", li, "ard_lengthscales", (int(np.size(l.kern.lengthscales)),)))
+            if not head and l.filter_mean is not None:
+                out.append((base + "mean_filter", li, "mean_filter", np.shape(l.filter_mean.conv_filter)))
+        if self.gaussian or self.student_t:
+            out.append(("likelihood", 0, "likelihood", (1,)))
+        return out
+
+    def optimizer_state(self):
+        """The device optimiser's own state: ``{"t": Adam's step count, "<group>/m": first moments, "<group>/v": second moments}`` for every
+        group of ``_optimizer_groups`` -- ``layers/<i>/<Z | q_mu | q_sqrt | w | hyper | ard_lengthscales | mean_filter>`` and ``likelihood`` --
+        in the unconstrained space the optimiser works in.  A model that has never stepped reports zeros and ``t = 0``.  With the parameters
+        (``pull_parameters``) it is everything a later step depends on: see ``set_optimizer_state``."""
+        self._build()
+        ctx, L = self._ctx, dev.lib()
+        t = C.c_int(0)
+        ctx._check(L.dcgp_model_get_adam_t(self._model, C.byref(t)))
+        state = {"t": int(t.value)}
+        for key, li, which, shape in self._optimizer_groups():
+            m, v = np.empty(shape, np.float64), np.empty(shape, np.float64)
+            ctx._check(L.dcgp_model_get_adam_state(self._model, li, which.encode(), m.ctypes.data, v.ctypes.data, m.size))
+            state[key + "/m"], state[key + "/v"] = m, v
+        return state
+
+    def set_optimizer_state(self, state):
+        """Put an ``optimizer_state()`` back (of this model or of one with the same layers): the next step is then the step the other model
+        would have taken at the same parameters.  A missing or extra key or a wrong shape raises ValueError naming the key; nothing is
+        written in that case."""
+        self._build()
+        ctx, L = self._ctx, dev.lib()
+        groups = self._optimizer_groups()
+        want = {"t": ()}
+        for key, _, _, shape in groups:
+            want[key + "/m"] = want[key + "/v"] = tuple(shape)
+        for key in want:
+            if key not in state:
+                raise ValueError("set_optimizer_state: key %r is missing" % key)
+        for key in state:
+            if key not in want:
+                raise ValueError("set_optimizer_state: unexpected key %r" % key)
+        arrays = {}
+        for key, shape in want.items():
+            a = np.asarray(state[key])
+            if a.shape != shape:
+                raise ValueError("set_optimizer_state: %r has shape %r, expected %r" % (key, a.shape, shape))
+            arrays[key] = np.ascontiguousarray(a, np.float64)
+        t = int(state["t"])
+        if t < 0:
+            raise ValueError("set_optimizer_state: 't' must be >= 0, got %d" % t)
+        for key, li, which, _ in groups:
+            m, v = arrays[key + "/m"], arrays[key + "/v"]
+            ctx._check(L.dcgp_model_set_adam_state(self._model, li, which.encode(), m.ctypes.data, v.ctypes.data, m.size))
+        ctx._check(L.dcgp_model_set_adam_t(self._model, t))
+
+    def set_grad_clip(self, max_norm):
+        """Clip every Adam / SGD step's gradient by its global norm on the device (dcgp_model_set_grad_clip; ``tf.clip_by_global_norm`` on the
+        unconstrained variables the optimiser moves): the step uses ``g * max_norm / max(norm, max_norm)``.  0 switches it off (the default),
+        ``inf`` measures the norm and scales nothing.  The natural-gradient update is not clipped.  Negative or NaN raises ValueError."""
+        max_norm = float(max_norm)
+        if not max_norm >= 0.0:
+            raise ValueError("set_grad_clip: max_norm must be >= 0 (0: off, inf: measure only), got %r" % (max_norm,))
+        self._build()
+        self._ctx._check(dev.lib().dcgp_model_set_grad_clip(self._model, max_norm))
+        self.grad_clip = max_norm
+
+    @property
+    def last_grad_norms(self):
+        """Pre-clip global gradient norms of the steps of the most recent optimiser call (dcgp_model_grad_norms): one value after ``adam_step``,
+        ``sgd_step`` or ``train_step``, one per completed step after ``train_run``; empty while clipping is off."""
+        self._build()
+        ctx, L = self._ctx, dev.lib()
+        n = C.c_int(0)
+        ctx._check(L.dcgp_model_grad_norms(self._model, None, 0, C.byref(n)))
+        out = np.empty(n.value, np.float64)
+        if n.value:
+            ctx._check(L.dcgp_model_grad_norms(self._model, out.ctypes.data, n.value, C.byref(n)))
+        return out
+
     def set_shard(self, first_image, global_batch):
         """Multi-GPU: this rank holds images [first_image, first_image + N) of a minibatch of ``global_batch`` images (dist.shard_range).
         Also sets ``global_batch`` for the default ELBO scale.  The device RNG then draws every element at its position in the un-sharded

@@ -4,6 +4,8 @@
 A period of Adam steps is ONE device call (``DGP_Base.train_run``) on a training set that is uploaded once, when the model is set up;
 ``--augment-shift`` / ``--augment-flip`` augment its batches on the device (SGD and NatGrad: the same batches, one device call per step).
 ``--test-shift`` / ``--test-flip`` / ``--test-views`` score the test set over shifted and mirrored views (test-time augmentation).
+``--keep-optimizer`` writes the optimiser's state beside every checkpoint and, with ``--load-model``, continues from it: the resumed run is the
+interrupted one bit for bit.  ``--clip-norm`` clips every Adam / SGD step's gradient by its global norm on the device.
 
     python -m deepcgp_amd.experiment --name run --data digits.npz -M 16,16 --feature-maps 2 --filter-sizes 3,3 --strides 1,1
 """
@@ -12,8 +14,9 @@ import os
 import numpy as np
 
 from . import utils
-from .arguments import default_parser, parse_augmentation, parse_test_views, train_steps
-from .models import ModelBuilder, index_table, learning_rate, lr_table, save_model_parameters, train
+from .arguments import default_parser, parse_augmentation, parse_clip_norm, parse_test_views, train_steps
+from .models import (ModelBuilder, index_table, learning_rate, lr_table, restore_optimizer_state, save_model_parameters, save_optimizer_state,
+                     train)
 
 
 class Experiment(object):
@@ -24,6 +27,9 @@ class Experiment(object):
         self.seed = int(getattr(flags, "seed", 0))
         self.augmentation = parse_augmentation(flags)     # --augment-shift / --augment-flip: training batches only
         self.test_views = parse_test_views(flags)         # --test-shift / --test-flip / --test-views: None = the test images as they are
+        self.clip_norm = parse_clip_norm(flags)           # --clip-norm: 0.0 = off (no call into the model, no logger)
+        self.keep_optimizer = bool(getattr(flags, "keep_optimizer", False))
+        self._period_norms = np.zeros(0)                  # pre-clip gradient norms of the period that just ended (--clip-norm)
         self._load_data()
         self._setup_model()
         self._setup_optimizer()
@@ -55,11 +61,17 @@ class Experiment(object):
             idx = index_table(self._rng, n, bs, k)
             lrs = lr_table(fl.lr, self.global_step, k, fl.lr_decay_steps)
             self.last_elbos = self.model.train_run(idx, lrs, seed=self.seed + self.global_step)
+            if self.clip_norm > 0:
+                self._period_norms = np.array(self.model.last_grad_norms)
             self.model.pull_parameters()
         else:
+            norms = []      # --clip-norm: one optimiser call per step here, its norm read behind each
+            watch = (lambda step, elbo: norms.extend(self.model.last_grad_norms)) if self.clip_norm > 0 else None
             self.last_elbos = np.array(train(self.model, k, lr=fl.lr, lr_decay_steps=fl.lr_decay_steps, global_step=self.global_step,
                                              seed=self.seed + self.global_step, optimizer=fl.optimizer, gamma=fl.gamma,
-                                             augment=self.augmentation))
+                                             augment=self.augmentation, callback=watch))
+            if self.clip_norm > 0:
+                self._period_norms = np.array(norms)
         self.global_step += k
         self.model.global_step = self.global_step
 
@@ -72,25 +84,37 @@ class Experiment(object):
             model_name = self.flags.name
         return os.path.join(self.flags.log_dir, model_name + '.npy')
 
+    def _optimizer_path(self, model_name=None):
+        """The sidecar of ``_model_path(model_name)`` (--keep-optimizer)."""
+        return self._model_path(model_name)[:-len('.npy')] + '.opt.npz'
+
     def _save_model_parameters(self):
         utils.ensure_dir(self.flags.log_dir)
         save_model_parameters(self.model, self._model_path(), self.global_step)
+        if self.keep_optimizer:
+            save_optimizer_state(self.model, self._optimizer_path(), self.global_step, rng=self._rng)
 
     def _setup_model(self):
         model_builder = ModelBuilder(self.flags, self.X_train, self.Y_train, model_path=self._model_path(self.flags.load_model))
         self.model = model_builder.build()
         # global_step goes on from a loaded checkpoint; Adam's bias correction restarts with the optimiser (include/dcgp.h, dcgp_model_adam_step)
+        # unless --keep-optimizer puts the optimiser's state back (_setup_optimizer)
         self.global_step = int(model_builder.global_step or 0)
         self.model.global_step = self.global_step
         self.model.dedup_layer0 = True     # as models.train: the first layer sees S identical copies of the batch
         if self.flags.optimizer == "Adam":
             self.model.attach_dataset()    # once: every period draws its minibatches from it on the device
             self.model.set_augmentation(self.augmentation)     # ... and shifts / flips them there (the shift's upper bound is checked here)
+        if self.clip_norm > 0:
+            self.model.set_grad_clip(self.clip_norm)
 
     def _setup_optimizer(self):
         if self.flags.optimizer not in ["Adam", "NatGrad", "SGD"]:
             raise ValueError("Not a supported optimizer. Try Adam or NatGrad.")
         self._rng = np.random.default_rng(self.seed)     # the minibatch draws
+        if self.keep_optimizer and getattr(self.flags, "load_model", None) is not None:
+            # the run goes on where the checkpoint's run stood: moments, step count, prior patches and the generator of the minibatch draws
+            restore_optimizer_state(self.model, self._optimizer_path(self.flags.load_model), self.global_step, rng=self._rng)
 
     def _setup_logger(self):
         X_test = self.X_test.reshape(self.X_test.shape[0], -1)
@@ -101,6 +125,8 @@ class Experiment(object):
             accuracy,
             utils.LogLikelihoodLogger(),
         ]
+        if parse_clip_norm(self.flags) > 0:      # --clip-norm: the period's mean pre-clip gradient norm
+            loggers.append(utils.GradNormLogger(lambda: getattr(self, "_period_norms", ())))
         self.log = utils.Log(self.flags.log_dir, self.flags.name, loggers)
         self.log.write_flags(self.flags)
 

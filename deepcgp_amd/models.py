@@ -86,6 +86,67 @@ def save_model_parameters(model, path, global_step=0):
     return params
 
 
+OPTIMIZER_STATE_FORMAT = 1
+
+
+def save_optimizer_state(model, path, global_step, rng=None):
+    """Write the sidecar of a checkpoint (``--keep-optimizer``): an ``.npz`` with ``format``, ``global_step``, the arrays of
+    ``model.optimizer_state()`` under ``opt/<key>``, and -- with ``rng``, a ``numpy.random.Generator`` -- its bit generator's state as a JSON
+    string (``rng``).  It also holds what a later step depends on and the reference's checkpoint has no key for: every conv layer's prior
+    inducing patches (``prior/<i>/Z``; the checkpoint's Z is the trained one, a model built from it alone takes that for its prior).
+    Nothing in it is pickled.  Returns the dict that was written."""
+    import json
+    out = {"format": np.array(OPTIMIZER_STATE_FORMAT, np.int64), "global_step": np.array(int(global_step), np.int64)}
+    for key, value in model.optimizer_state().items():
+        out["opt/" + key] = np.asarray(value)
+    for li, l in enumerate(getattr(model, "layers", [])[:-1]):
+        out["prior/%d/Z" % li] = np.array(l.Z_prior, np.float64)
+    if rng is not None:
+        out["rng"] = np.array(json.dumps(rng.bit_generator.state))
+    with open(path, "wb") as fh:      # (np.savez would append .npz to another suffix)
+        np.savez(fh, **out)
+    return out
+
+
+def load_optimizer_state(path):
+    """Read a sidecar ``save_optimizer_state`` wrote (``allow_pickle=False``): ``{"global_step": int, "state": the dict
+    ``set_optimizer_state`` takes, "prior": {layer: Z}, "rng": the bit generator's state dict or None}``.  A missing file or another
+    format raises ValueError naming the path."""
+    import json
+    import os
+    if not os.path.exists(path):
+        raise ValueError("optimizer state %s not found (written beside a checkpoint by --keep-optimizer)" % path)
+    with np.load(path, allow_pickle=False) as z:
+        if "format" not in z.files or int(z["format"]) != OPTIMIZER_STATE_FORMAT:
+            raise ValueError("optimizer state %s: not format %d" % (path, OPTIMIZER_STATE_FORMAT))
+        state = {k[len("opt/"):]: np.array(z[k]) for k in z.files if k.startswith("opt/")}
+        prior = {int(k.split("/")[1]): np.array(z[k]) for k in z.files if k.startswith("prior/")}
+        rng = json.loads(str(z["rng"][()])) if "rng" in z.files else None
+        step = int(z["global_step"])
+    if "t" in state:
+        state["t"] = int(state["t"])
+    return {"global_step": step, "state": state, "prior": prior, "rng": rng}
+
+
+def restore_optimizer_state(model, path, global_step, rng=None):
+    """``load_optimizer_state(path)`` into ``model`` (and ``rng``'s bit generator): the prior inducing patches, the moments and the step count.
+    A sidecar of another ``global_step`` than the checkpoint's raises ValueError naming the path."""
+    side = load_optimizer_state(path)
+    if side["global_step"] != int(global_step):
+        raise ValueError("optimizer state %s is of global_step %d, the checkpoint of %d" % (path, side["global_step"], int(global_step)))
+    for li, Z in side["prior"].items():
+        layer = model.layers[li]
+        if np.shape(Z) != np.shape(layer.Z_prior):
+            raise ValueError("optimizer state %s: prior/%d/Z has shape %r, the layer's is %r" % (path, li, np.shape(Z), np.shape(layer.Z_prior)))
+        layer.Z_prior = np.array(Z, np.float64)
+        layer._build_prior_cholesky()
+    model.sync_parameters()      # (the prior's patches travel with the parameters)
+    model.set_optimizer_state(side["state"])
+    if rng is not None and side["rng"] is not None:
+        rng.bit_generator.state = side["rng"]
+    return side
+
+
 def learning_rate(lr, global_step, lr_decay_steps, decay_rate=0.1):
     """tf.train.exponential_decay(..., staircase=True) of conv_gp/experiment.py:71-73."""
     return float(lr) * decay_rate ** (int(global_step) // int(lr_decay_steps))
@@ -348,6 +409,19 @@ class TestLogDensityLogger(object):
     def __call__(self, model, seed=0):
         kw = {} if self.views is None else {"views": self.views}      # (without views: the call it always made)
         return model.evaluate(self.X_test, self.Y_test, S=self.num_samples, batch_size=self.batch_size, seed=seed, **kw)["mean_log_density"]
+
+
+class GradNormLogger(object):
+    """Mean pre-clip global gradient norm over the steps of the period that just ended (``--clip-norm``): ``norms()`` returns them, the driver
+    collects them from ``DGP_Base.last_grad_norms`` after every optimiser call.  NaN for a period without a clipped step."""
+    title = 'grad_norm'
+
+    def __init__(self, norms):
+        self.norms = norms
+
+    def __call__(self, model, seed=0):
+        norms = np.asarray(self.norms(), np.float64)
+        return float(norms.mean()) if norms.size else float("nan")
 
 
 class LogLikelihoodLogger(object):

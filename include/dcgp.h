@@ -422,6 +422,28 @@ int dcgp_model_debug_sharded_adam(dcgp_model* model, int ranks, double lr, doubl
 /* Plain gradient ascent in the same unconstrained space (gpflow.train.GradientDescentOptimizer, the "SGD" branch
  * at conv_gp/experiment.py:100-103). */
 int dcgp_model_sgd_step(dcgp_model* model, double lr);
+/* The optimiser's own state, so that an interrupted run can go on as the run it was: Adam's moments m, v of one parameter group (in the
+ * unconstrained space, the group's own layout) to / from the host, and the step count of its bias correction.  which = "Z", "q_mu", "q_sqrt",
+ * "w", "hyper" (3 values: variance, p1, p2 as dcgp_model_get_grad orders them), "ard_lengthscales", "mean_filter", or "likelihood" (1 value:
+ * the Gaussian variance / StudentT scale; `layer` ignored).  A model that has never stepped reports zeros and t = 0.  DCGP_ERR_ARG: unknown
+ * name, wrong count, a group the layer does not have; set: enqueued steps still to be collected; both: sharded Adam steps were taken
+ * (exchange mode 1: the moments are rank-local). */
+int dcgp_model_get_adam_state(dcgp_model* model, int layer, const char* which, double* m_host, double* v_host, size_t count);
+int dcgp_model_set_adam_state(dcgp_model* model, int layer, const char* which, const double* m_host, const double* v_host, size_t count);
+int dcgp_model_get_adam_t(dcgp_model* model, int* t);
+int dcgp_model_set_adam_t(dcgp_model* model, int t /* >= 0 */);
+/* Clipping by global norm in the device optimiser (tf.clip_by_global_norm on gpflow's unconstrained variables): with g_u the gradient the
+ * update uses for every element it moves (softplus factor included; frozen groups and held elements left out), norm = sqrt(sum g_u^2) and
+ * c = max_norm / max(norm, max_norm); Adam and SGD step on c g_u.  The norm is formed on the device between the gradient and the update (two
+ * small launches); norm <= max_norm gives c = 1.0 exactly and the unclipped step to the bit.  max_norm 0 (default): off, the step is launched
+ * as it always was; +inf: the norm is measured, nothing is scaled; negative or NaN: DCGP_ERR_ARG.  The natural-gradient update is not clipped.
+ * With clipping on, a sharded update (exchange mode 1 on more than one rank, dcgp_model_debug_sharded_adam) returns DCGP_ERR_ARG: a rank sees
+ * only its shard of the gradient. */
+int dcgp_model_set_grad_clip(dcgp_model* model, double max_norm);
+/* The pre-clip norms of the steps of the most recent optimiser call: one after dcgp_model_adam_step / _sgd_step / _train_step_adam, steps_done
+ * after dcgp_model_train_run_adam; none while clipping is off, none for a step that was not positive definite.  *count_out: how many there
+ * are; the first min(cap, *count_out) go to out_host. */
+int dcgp_model_grad_norms(dcgp_model* model, double* out_host, int cap, int* count_out);
 /* One natural-gradient step of size gamma on every layer's (q_mu, q_sqrt) from the gradients of the last dcgp_elbo_grad:
  * gpflow.train.NatGradOptimizer(gamma) on var_list = [(l.q_mu, l.q_sqrt)] (conv_gp/experiment.py:90-99), natural-parameter
  * form theta <- theta + gamma dELBO/d eta.  Returns DCGP_ERR_NOT_PD (nothing written, *info = failing column) when a new
