@@ -35,6 +35,8 @@ FLAGS = (
     ("--identity-mean", None, False, "Conv2dMean identity mean function on the conv layers"),
     ("--mean-filter", str, "centre0", "initial filter of the conv layers' mean function (needs --identity-mean): centre0 (Conv2dMean's: channel 0 into map 0) | channels (every channel into its own map) | sum (every channel into every map)"),
     ("--train-mean", None, False, "train the mean function's filter with the other parameters (needs --identity-mean)"),
+    ("--latent-gps", str, "", "mixed conv layers: latent GPs of each conv layer, comma separated; a layer with G > 0 holds G GPs and emits its --feature-maps count as a trainable linear mix of them; 0 = that layer unmixed; '' = no mixing anywhere"),
+    ("--freeze-mixing", None, False, "keep the mixing matrices of --latent-gps at their initial values"),
     ("--load-model", str, None, "checkpoint (.npy, reference key set) to start from"),
     ("--keep-optimizer", None, False, "write the optimiser's state (Adam moments, step count, minibatch generator) beside every checkpoint as <name>.opt.npz; with --load-model X, continue from X.opt.npz: the resumed run is the interrupted one, bit for bit"),
     ("--clip-norm", float, 0.0, "clip every Adam / SGD step's gradient to this global norm on the device and log the period's mean pre-clip norm (grad_norm); 0 = off"),
@@ -70,6 +72,23 @@ def parse_paddings(flags, n_layers):
     if pads[-1] > 0 and getattr(flags, "last_kernel", "conv") == "rbf":
         raise ValueError("--paddings: the dense head of --last-kernel rbf takes no padding (last entry %d)" % pads[-1])
     return pads
+
+
+def parse_latent_gps(flags, n_convs):
+    """The ``--latent-gps`` list of a model of ``n_convs`` conv layers: ``n_convs`` ints >= 0 (0: that layer unmixed), all zero when the flag is
+    absent or ''.  A wrong length, a negative or non-integer entry raise ValueError."""
+    text = getattr(flags, "latent_gps", "") or ""
+    if text.strip() == "":
+        return [0] * n_convs
+    try:
+        gps = [int(t) for t in text.split(",")]
+    except ValueError:
+        raise ValueError("--latent-gps: expected comma-separated integers, got %r" % (text,))
+    if len(gps) != n_convs:
+        raise ValueError("--latent-gps: %d entries for %d conv layers (one per conv layer, like --feature-maps)" % (len(gps), n_convs))
+    if any(g < 0 for g in gps):
+        raise ValueError("--latent-gps: entries must be >= 0 (0 = unmixed), got %r" % (text,))
+    return gps
 
 
 def parse_augmentation(flags):

@@ -19,7 +19,7 @@ constexpr int kChans = 4;               // the adjoint: channels a thread holds 
 inline unsigned blocks_for(long n, int per = 256) { return (unsigned)((n + per - 1) / per); }
 
 struct MeanGeom { int H, W, C, f, s, Wo, P, L, R; };
-MeanGeom geom_of(const LayerState& L) { return MeanGeom{L.v.H, L.v.W, L.v.C, L.v.f, L.v.s, L.v.Wo, L.v.P, L.v.L, L.R}; }
+MeanGeom geom_of(const LayerState& L) { return MeanGeom{L.v.H, L.v.W, L.v.C, L.v.f, L.v.s, L.v.Wo, L.v.P, L.v.L, L.Rout}; }
 
 // one thread per (column j, map r), r fastest: the R threads of a column read the same patch (one fetch per wave), the writes are contiguous, and a
 // de-duplicated first layer of a few thousand columns still puts R times as many threads on the chip.
@@ -131,9 +131,9 @@ int conv_mean_backward_filter(dcgp_ctx* ctx, const LayerState& L, const double* 
   if (Kc > 0x7fffffffL) return ctx_fail(ctx, DCGP_ERR_ARG, "conv_mean_backward_filter: %ld columns exceed one product", Kc);
   GenGemm e;
   e.A = Xcol; e.a_rs = 1; e.a_cs = L.v.L;        // A(l, c) = Xcol[c][l]
-  e.B = gm; e.b_rs = L.R; e.b_cs = 1;            // B(c, r) = gm[c][r]
-  e.C = gW; e.c_rs = L.R;
-  e.M = L.v.L; e.N = L.R; e.K = (int)Kc;
+  e.B = gm; e.b_rs = L.Rout; e.b_cs = 1;         // B(c, r) = gm[c][r]
+  e.C = gW; e.c_rs = L.Rout;
+  e.M = L.v.L; e.N = L.Rout; e.K = (int)Kc;
   ScopedTimer t(ctx, "conv_mean_backward_filter");
   return gemm_gen(ctx, e);
 }
@@ -207,7 +207,7 @@ extern "C" int dcgp_model_set_mean_filter(dcgp_model* model, int layer, const do
   if (L.identity_mean)
     return ctx_fail(ctx, DCGP_ERR_ARG, "set_mean_filter: layer %d was added with identity_mean (the in-launch Conv2dMean); add it without to give it a filter", layer);
   if (model->enq_seq != model->col_seq) return ctx_fail(ctx, DCGP_ERR_ARG, "set_mean_filter: enqueued steps are still to be collected");
-  const size_t n = (size_t)L.v.L * L.R;
+  const size_t n = (size_t)L.v.L * L.Rout;
   if (!L.mean_W) {
     // the filter's gradient takes L R slots at the end of the layer's gradient block: the block must not exist yet
     if (L.gZ || L.pstage || L.hyp) return ctx_fail(ctx, DCGP_ERR_ARG, "set_mean_filter: layer %d has taken a gradient step; give it its filter before the first", layer);

@@ -634,6 +634,9 @@ struct Bk {   // per-backward bookkeeping
   // model_backward_data (the input gradient): only the data path runs -- the column-wise adjoint of each conditional, the patch kernel's adjoint with
   // respect to the patches, dX.  Nothing is written outside the "g_" workspaces: no gradient block, no scalar slot, no chain, no KL, no dZ.
   bool data_only = false;
+  // a mixed layer (mix.hip): what the walk hands its conv_backward beside the latent (gm, gv) -- the gradient gF of its Rout maps for the mean filter's
+  // adjoints [rows P][Rout] (summed over the replicas of a de-duplicated first layer), and for gW every replica's columns: u and gF [mix_cols][.]
+  const double* mix_gF = nullptr; const double* mix_gF_all = nullptr; long mix_cols = 0;
   double* ws(const char* name, size_t n_doubles) { return (double*)ws_get(ctx, pfx + "g_" + name, (n_doubles ? n_doubles : 1) * sizeof(double)); }
 };
 
@@ -1202,7 +1205,7 @@ int layer_fills(Bk& bk, LayerState& L) {
     return DCGP_OK;
   }
   HIP_TRY(bk.ctx, hipMemsetAsync(L.gZ, 0, (size_t)L.M * L.v.L * sizeof(double), bk.ctx->stream));
-  HIP_TRY(bk.ctx, hipMemsetAsync(L.gw, 0, ((size_t)L.v.P + 3 + (L.is_head ? (size_t)L.v.L : 0) + L.lik_slots + L.mean_slots()) * sizeof(double), bk.ctx->stream));   // gw, gscal, gard, glik, gmean_W
+  HIP_TRY(bk.ctx, hipMemsetAsync(L.gw, 0, ((size_t)L.v.P + 3 + (L.is_head ? (size_t)L.v.L : 0) + L.lik_slots + L.mean_slots() + L.mix_slots()) * sizeof(double), bk.ctx->stream));   // gw, gscal, gard, glik, gmean_W, gmix_W
   if (!L.has_qsqrt) HIP_TRY(bk.ctx, hipMemsetAsync(L.gq_sqrt, 0, (size_t)L.R * L.M * L.M * sizeof(double), bk.ctx->stream));
   return DCGP_OK;
 }
@@ -1267,6 +1270,18 @@ int conv_backward(Bk& bk, LayerState& L, const double* Xin, int rows, int n_mod,
   Lanes ln = lanes_of(ctx);
   if (bk.data_only) { ln.forked = false; ln.chain = ln.tail = ln.main; }
   DCGP_TRY(begin_layer(bk, L));
+  const double* gmf = gm;   // the mean function's adjoint: d / d mean of the layer's maps
+  if (L.mix_W) {
+    if (!bk.mix_gF || !bk.mix_gF_all) return ctx_fail(ctx, DCGP_ERR_ARG, "grad: a mixed layer takes its gradient from the layer above it");
+    gmf = bk.mix_gF;
+    if (!bk.data_only && L.mix_trainable) {   // gW behind the block's fill (a frozen matrix keeps its zero)
+      int nwg; long cpw;
+      mix_w_plan(bk.mix_cols, &nwg, &cpw);
+      double* part = bk.ws("mix_part", (size_t)nwg * L.mix_slots());
+      NEED(part);
+      DCGP_TRY(mix_backward_w(ctx, L.R, L.Rout, L.lat_sample, bk.mix_gF_all, bk.mix_cols, part, L.gmix_W));
+    }
+  }
   // forward leftovers (conv_forward / cond_core workspaces)
   const double* Kuf = forward_left(bk, "Kuf", 0, "K_uf / A1 for this layer");
   const double* A1 = forward_left(bk, "A1", (size_t)Mp * ld * sizeof(double), "K_uf / A1 for this layer");
@@ -1292,15 +1307,15 @@ int conv_backward(Bk& bk, LayerState& L, const double* Xin, int rows, int n_mod,
   if (dXin) {
     DCGP_TRY(patches_to_dx(bk, L, fuse_dx, E, ld, cs, Xin, rows, n_mod, nullptr, dXcol, dXin));
     if (L.identity_mean) {
-      hipLaunchKernelGGL(idmean_backward_kernel, dim3(blocks_for(Kc)), dim3(256), 0, ctx->stream, gm, Kc, L.R, P, L.v.Wo, L.v.H, L.v.W, L.v.C,
+      hipLaunchKernelGGL(idmean_backward_kernel, dim3(blocks_for(Kc)), dim3(256), 0, ctx->stream, gmf, Kc, L.R, P, L.v.Wo, L.v.H, L.v.W, L.v.C,
                          L.v.f, L.v.s, dXin);
       LAUNCH_CHECK(ctx);
     }
-    if (L.mean_W) DCGP_TRY(conv_mean_backward_dx(ctx, L, gm, rows, dXin));   // the filter mean's adjoint (conv_mean.hip): gm is d / d mean, as the oracle uses it
+    if (L.mean_W) DCGP_TRY(conv_mean_backward_dx(ctx, L, gmf, rows, dXin));   // the filter mean's adjoint (conv_mean.hip): gm is d / d mean, as the oracle uses it
   }
   if (bk.data_only) return DCGP_OK;
   // the filter's own gradient from the patches the pass holds (a frozen filter keeps the zero of the block's fill)
-  if (L.mean_W && L.mean_trainable) DCGP_TRY(conv_mean_backward_filter(ctx, L, Xcol, gm, Kc, L.gmean_W));
+  if (L.mean_W && L.mean_trainable) DCGP_TRY(conv_mean_backward_filter(ctx, L, Xcol, gmf, Kc, L.gmean_W));
   // The main stream's part of this layer ends here (dX is out): it goes straight on to the layer below.
   if (ln.forked) HIP_TRY(ctx, hipEventRecord(ctx->ev_g[3], ctx->stream));
   DCGP_TRY(cond_backward_finish(bk, ln, L, A1, ld, Kc, dKuf, S, false, bk.last_layer && ln.forked));
@@ -1597,6 +1612,7 @@ static int backward_walk(Bk& bk, const double* X, int N, int S, int dedup_layer0
       }
       rows_l = N;
     }
+    if (!L.is_head && L.mix_W && li == nl - 1) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: a mixed layer must have a layer above it", who);
     const int n_mod = li == 0 ? N : rows_l;
     const long img = (long)L.v.H * L.v.W * L.v.C;
     double* dXin = li == 0 ? out_dX : nullptr;   // (layer 0 of a training step: no dX)
@@ -1617,24 +1633,43 @@ static int backward_walk(Bk& bk, const double* X, int N, int S, int dedup_layer0
       break;
     }
     auto& o = m->outs[li - 1];
-    const long n = (long)o.rows * o.width;
+    LayerState& Lb = *m->layers[li - 1];
+    const long n_out = (long)o.rows * o.width;
+    const long n = Lb.is_head ? n_out : (long)o.rows * Lb.v.P * Lb.R;   // the (d mean, d var) the layer below takes: its GPs' (== n_out unless it is mixed)
     gm = (double*)ws_get(ctx, mp + std::to_string(li - 1) + "_g_gm", (size_t)n * sizeof(double));
     gv = (double*)ws_get(ctx, mp + std::to_string(li - 1) + "_g_gv", (size_t)n * sizeof(double));
     NEED(gm); NEED(gv);
-    LayerState& Lb = *m->layers[li - 1];
     if (pad > 0) {   // the sample's gradient is the interior of the padded input's
-      double* dcrop = (double*)ws_get(ctx, bk.pfx + "g_dXcrop", (size_t)n * sizeof(double));
+      double* dcrop = (double*)ws_get(ctx, bk.pfx + "g_dXcrop", (size_t)n_out * sizeof(double));
       NEED(dcrop);
       DCGP_TRY(crop_images(ctx, ctx->stream, dXin, 1, o.rows, L.v.H - 2 * pad, L.v.W - 2 * pad, L.v.C, pad, dcrop));
       dXin = dcrop;
     }
-    if (li - 1 == 0 && dedup_layer0 && !Lb.is_head && o.rows == S * N && S > 1) {   // S gradients per element of the shared conditional: summed here
-      const long n0 = (long)N * o.width;
-      hipLaunchKernelGGL(sample_backward_dedup_kernel, dim3(blocks_for(n0)), dim3(256), 0, ctx->stream, dXin, o.sample, o.mean, o.var, m->jitter, S, n0,
-                         gm, gv);
+    const bool dedup_below = li - 1 == 0 && dedup_layer0 && !Lb.is_head && o.rows == S * N && S > 1;
+    const double *dF = dXin, *smp = o.sample, *mean = o.mean, *var = o.var;
+    bk.mix_gF = bk.mix_gF_all = nullptr; bk.mix_cols = 0;
+    if (!Lb.is_head && Lb.mix_W) {   // a mixed layer (mix.hip): gu = gF W^T on every replica's columns, then the sample's adjoint on its latent triple
+      const long cols = (long)o.rows * Lb.v.P;
+      double* gu = (double*)ws_get(ctx, mp + std::to_string(li - 1) + "_g_gu", (size_t)n * sizeof(double));
+      NEED(gu);
+      DCGP_TRY(mix_backward_latent(ctx, Lb.mix_W, Lb.R, Lb.Rout, dXin, cols, gu));
+      bk.mix_gF_all = dXin; bk.mix_cols = cols; bk.mix_gF = dXin;
+      if (dedup_below && Lb.mean_W) {   // the mean filter sees the N distinct images: its adjoint takes the replicas' sum
+        const long n0 = (long)N * o.width;
+        double* gF0 = (double*)ws_get(ctx, mp + std::to_string(li - 1) + "_g_gF0", (size_t)n0 * sizeof(double));
+        NEED(gF0);
+        hipLaunchKernelGGL(reduce_replicas1_kernel, dim3(blocks_for(n0)), dim3(256), 0, ctx->stream, dXin, S, n0, gF0);
+        LAUNCH_CHECK(ctx);
+        bk.mix_gF = gF0;
+      }
+      dF = gu; smp = Lb.lat_sample; mean = Lb.lat_mean; var = Lb.lat_var;
+    }
+    if (dedup_below) {   // S gradients per element of the shared conditional: summed here
+      const long n0 = n / S;
+      hipLaunchKernelGGL(sample_backward_dedup_kernel, dim3(blocks_for(n0)), dim3(256), 0, ctx->stream, dF, smp, mean, var, m->jitter, S, n0, gm, gv);
       dedup_done = true;
     } else {
-      hipLaunchKernelGGL(sample_backward_kernel, dim3(blocks_for(n)), dim3(256), 0, ctx->stream, dXin, o.sample, o.mean, o.var, m->jitter, n, gm, gv);
+      hipLaunchKernelGGL(sample_backward_kernel, dim3(blocks_for(n)), dim3(256), 0, ctx->stream, dF, smp, mean, var, m->jitter, n, gm, gv);
     }
     LAUNCH_CHECK(ctx);
   }

@@ -18,6 +18,13 @@ int conv_mean_add(dcgp_ctx* ctx, const LayerState& L, const double* X, int n_mod
                   double* out_sample);
 int conv_mean_backward_dx(dcgp_ctx* ctx, const LayerState& L, const double* gm, int rows, double* dXin);
 int conv_mean_backward_filter(dcgp_ctx* ctx, const LayerState& L, const double* Xcol, const double* gm, long Kc, double* gW);
+// mix.hip: a mixed conv layer's G latent outputs into its R maps through W [G][R] (LayerState::mix_W) / the adjoints
+constexpr int kMixMaxMaps = 64;   // G and R of a mixing
+int mix_forward(dcgp_ctx* ctx, const double* W, int G, int R, const double* u, const double* gm, const double* gv, long col0, long Kc, int rep,
+                long lat_stride, long out_stride, double* out_sample, double* out_mean, double* out_var);
+int mix_backward_latent(dcgp_ctx* ctx, const double* W, int G, int R, const double* gF, long Kc, double* gu);
+void mix_w_plan(long Kc, int* nwg, long* cpw);
+int mix_backward_w(dcgp_ctx* ctx, int G, int R, const double* u, const double* gF, long Kc, double* part, double* gW);
 
 struct LayerState {
   dcgp_ctx* ctx = nullptr;
@@ -64,7 +71,28 @@ struct LayerState {
   // at the very end of the layer's gradient block, its Adam moments, and whether the optimiser steps move it
   double *mean_W = nullptr, *gmean_W = nullptr, *amean_W[2] = {};
   bool mean_trainable = false;
-  size_t mean_slots() const { return mean_W ? (size_t)v.L * R : 0; }
+  size_t mean_slots() const { return mean_W ? (size_t)v.L * Rout : 0; }
+  // mixing (conv layers; dcgp_model_set_mixing, mix.hip): the layer's R = gp_count latent GPs leave it as Rout maps through W [R][Rout] (nullptr:
+  // unmixed, Rout == R).  Its gradient sits behind the mean filter's at the very end of the gradient block; W is unconstrained.  lat_*: the layer's
+  // own (sample u, mean, var), R wide, as its kernels wrote them -- the reverse pass reads them (grow-only, lat_cap doubles each).
+  int Rout = 0;
+  double *mix_W = nullptr, *gmix_W = nullptr, *amix_W[2] = {}, *mix_buf = nullptr;
+  size_t mix_cap = 0;
+  bool mix_trainable = false;
+  size_t mix_slots() const { return mix_W ? (size_t)R * Rout : 0; }
+  double *lat_sample = nullptr, *lat_mean = nullptr, *lat_var = nullptr;
+  size_t lat_cap = 0;
+  int ensure_latent(size_t n) {
+    if (lat_cap >= n) return DCGP_OK;
+    hipDeviceSynchronize();   // steps in flight on any stream may still use them
+    for (double** p : {&lat_sample, &lat_mean, &lat_var}) {
+      for (size_t i = 0; i < owned.size() && *p; ++i)
+        if (owned[i] == (void*)*p) { hipFree(*p); owned.erase(owned.begin() + i); break; }
+      if (!(*p = dalloc(n))) return ctx_fail(ctx, DCGP_ERR_ALLOC, "layer: latent output allocation failed");
+    }
+    lat_cap = n;
+    return DCGP_OK;
+  }
   std::shared_ptr<void> natgrad_state;   // scratch of dcgp_model_natgrad_step (natgrad.hip), created on first use
   std::vector<void*> owned;
 
@@ -85,7 +113,7 @@ struct LayerState {
       return ctx_fail(c, DCGP_ERR_ARG, "layer: bad geometry H=%d W=%d C=%d f=%d s=%d M=%d R=%d", H, W, C, f, s, M_, R_);
     if (!(var > 0.0) || !(ls_ > 0.0)) return ctx_fail(c, DCGP_ERR_ARG, "layer: variance and lengthscale must be > 0");
     v.set(H, W, C, f, s);
-    M = M_; R = R_; white = white_; identity_mean = idm; kernel_type = ktype; variance = var; ls = ls_;
+    M = M_; R = Rout = R_; white = white_; identity_mean = idm; kernel_type = ktype; variance = var; ls = ls_;
     Mp = round_up(M, 16);
     Lp = round_up(v.L, 4);
     Lz = sweep_lq(v.L);
@@ -138,7 +166,7 @@ struct LayerState {
   // head of a Gaussian-likelihood model: one more slot at the very end of the block, d ELBO / d likelihood variance (glik)
   int lik_slots = 0;
   double* glik = nullptr;
-  size_t grad_block_count() const { return (size_t)M * v.L + (size_t)M * R + (size_t)R * M * M + (size_t)v.P + 3 + (is_head ? (size_t)v.L : 0) + (size_t)lik_slots + mean_slots(); }
+  size_t grad_block_count() const { return (size_t)M * v.L + (size_t)M * R + (size_t)R * M * M + (size_t)v.P + 3 + (is_head ? (size_t)v.L : 0) + (size_t)lik_slots + mean_slots() + mix_slots(); }
   int ensure_grads() {
     if (gZ) return DCGP_OK;
     double* blk = dalloc(grad_block_count() + kGradBlockPad);   // (padding: the sharded exchange rounds the block up to ranks x shard)
@@ -148,6 +176,7 @@ struct LayerState {
     gard = is_head ? gscal + 3 : nullptr;   // [L] d / d ARD lengthscales (dense head), zero otherwise
     glik = lik_slots ? gscal + 3 + (is_head ? v.L : 0) : nullptr;
     gmean_W = mean_W ? gscal + 3 + (is_head ? v.L : 0) + lik_slots : nullptr;
+    gmix_W = mix_W ? gscal + 3 + (is_head ? v.L : 0) + lik_slots + mean_slots() : nullptr;
     return DCGP_OK;
   }
   int ensure_adam() {
@@ -168,6 +197,11 @@ struct LayerState {
       for (int k = 0; k < 2; ++k) {
         if (!(amean_W[k] = dalloc(mean_slots()))) return ctx_fail(ctx, DCGP_ERR_ALLOC, "layer: optimiser state allocation failed");
         HIP_TRY(ctx, hipMemsetAsync(amean_W[k], 0, mean_slots() * sizeof(double), ctx->stream));
+      }
+    if (mix_W)
+      for (int k = 0; k < 2; ++k) {
+        if (!(amix_W[k] = dalloc(mix_slots()))) return ctx_fail(ctx, DCGP_ERR_ALLOC, "layer: optimiser state allocation failed");
+        HIP_TRY(ctx, hipMemsetAsync(amix_W[k], 0, mix_slots() * sizeof(double), ctx->stream));
       }
     if (ard)
       for (int k = 0; k < 2; ++k) {
@@ -332,6 +366,15 @@ static inline int conv_forward(dcgp_ctx* ctx, LayerState& L, const double* X, in
   const long Kc = (long)rows * P;
   if (Kc > 0x7fffff00L) return ctx_fail(ctx, DCGP_ERR_ARG, "conv layer: %ld patch columns exceed the 32-bit tile index", Kc);
   const long ldb = col_ld(Kc);
+  // a mixed layer (mix.hip): the layer's kernels fill its own latent triple, R wide; a pass behind them writes the Rout-wide outputs, and a mean
+  // filter (on the Rout maps) adds into those
+  const long out_stride = rep_stride / L.R * L.Rout;
+  double *const mix_sample = out_sample, *const mix_mean = out_mean, *const mix_var = out_var;
+  if (L.mix_W) {
+    if (!L.lat_sample || L.lat_cap < (size_t)(rep > 1 ? (long)rep * rep_stride : Kc * L.R))
+      return ctx_fail(ctx, DCGP_ERR_ARG, "conv layer: a mixed layer without its latent buffers");
+    out_sample = L.lat_sample; out_mean = L.lat_mean; out_var = L.lat_var;
+  }
   {
     // one launch for the whole layer where the shape allows (conv_fused.hip): the strip of K_uf / A1 a workgroup owns
     // stays in LDS from the patch gather to the sample
@@ -356,11 +399,15 @@ static inline int conv_forward(dcgp_ctx* ctx, LayerState& L, const double* X, in
       if (prep_done) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, prep_done, 0));
       else if (factor_done) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, factor_done, 0));
       if (ride_head) { fa.head = *ride_head; fa.head_n = ride_rows; }
-      if (!L.mean_W) return conv_fused(ctx, fa);
+      if (!L.mean_W && !L.mix_W) return conv_fused(ctx, fa);
       // a filter mean completes mean and sample in a pass behind the launch: rows of the head may not have read the sample inside it (model.hip: plan_step)
+      if (ride_head && ride_rows > 0 && L.mix_W) return ctx_fail(ctx, DCGP_ERR_ARG, "conv layer: a mixed layer cannot carry the head's rows");
       if (ride_head && ride_rows > 0) return ctx_fail(ctx, DCGP_ERR_ARG, "conv layer: a layer with a mean filter cannot carry the head's rows");
       DCGP_TRY(conv_fused(ctx, fa));
-      return conv_mean_add(ctx, L, X, n_mod, 0, Kc, rep, rep_stride, out_mean, out_sample);
+      if (L.mix_W)
+        DCGP_TRY(mix_forward(ctx, L.mix_W, L.R, L.Rout, out_sample, out_mean, out_var, 0, Kc, rep, rep_stride, out_stride, mix_sample, mix_mean, mix_var));
+      if (L.mean_W) return conv_mean_add(ctx, L, X, n_mod, 0, Kc, rep, out_stride, mix_mean, mix_sample);
+      return DCGP_OK;
     }
     if (ride_head) return ctx_fail(ctx, DCGP_ERR_ARG, "conv layer: the step was planned to carry the head's rows in a launch the layer does not take");
   }
@@ -425,7 +472,9 @@ static inline int conv_forward(dcgp_ctx* ctx, LayerState& L, const double* X, in
       fa.n_mod = n_mod;
     }
     DCGP_TRY(finalize_layer(ctx, fa));
-    if (L.mean_W) DCGP_TRY(conv_mean_add(ctx, L, X, n_mod, (long)r0 * P, kc, rep, rep_stride, out_mean, out_sample));
+    if (L.mix_W)
+      DCGP_TRY(mix_forward(ctx, L.mix_W, L.R, L.Rout, out_sample, out_mean, out_var, (long)r0 * P, kc, rep, rep_stride, out_stride, mix_sample, mix_mean, mix_var));
+    if (L.mean_W) DCGP_TRY(conv_mean_add(ctx, L, X, n_mod, (long)r0 * P, kc, rep, out_stride, mix_mean, mix_sample));
   }
   return DCGP_OK;
 }

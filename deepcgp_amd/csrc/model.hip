@@ -216,8 +216,9 @@ StepPlan plan_step(const dcgp_model* m, int N, int S, int dedup, bool need_kl, b
   p.mark = (long)p.rows0 * L0.v.P >= 8192 ? ForkMark::BehindFirstLayer : ForkMark::BehindChain;
   const int nl = (int)m->layers.size();
   // (a padded head sweeps the padded copy of the sample: the ride reads the sample itself)
-  // (a layer with a mean filter completes its sample in a pass behind its launch, conv_mean.hip: no row may read the sample inside the launch)
-  if (nl >= 2 && m->layers[nl - 1]->is_head && !m->layers[nl - 2]->is_head && m->pad[nl - 1] == 0 && !m->layers[nl - 2]->mean_W) {
+  // (a layer with a mean filter completes its sample in a pass behind its launch, conv_mean.hip: no row may read the sample inside the launch;
+  // a mixed layer's launch writes its latent sample, the maps the head reads come out of the pass behind it, mix.hip)
+  if (nl >= 2 && m->layers[nl - 1]->is_head && !m->layers[nl - 2]->is_head && m->pad[nl - 1] == 0 && !m->layers[nl - 2]->mean_W && !m->layers[nl - 2]->mix_W) {
     const int li = nl - 2;
     const LayerState& Lc = *m->layers[li];
     const LayerState& Lh = *m->layers[nl - 1];
@@ -266,9 +267,9 @@ int check_padding(dcgp_model* m) {
                       L.v.H, L.v.W, p);
     if (li == 0) continue;
     const LayerState& B = *m->layers[li - 1];
-    if (B.is_head || B.v.Ho + 2 * p != L.v.H || B.v.Wo + 2 * p != L.v.W || B.R != L.v.C)
+    if (B.is_head || B.v.Ho + 2 * p != L.v.H || B.v.Wo + 2 * p != L.v.W || B.Rout != L.v.C)
       return ctx_fail(ctx, DCGP_ERR_ARG, "padding: layer %d takes %d x %d x %d, layer %d produces %d x %d x %d and the padding is %d", li, L.v.H, L.v.W, L.v.C,
-                      li - 1, B.v.Ho, B.v.Wo, B.R, p);
+                      li - 1, B.v.Ho, B.v.Wo, B.Rout, p);
   }
   m->pad_ok = true;
   return DCGP_OK;
@@ -299,16 +300,17 @@ int run_layer(dcgp_model* m, const StepPlan& p, const StepIn& in, int li, const 
   hipEvent_t fdone = (li == 0 && p.chain_beside()) ? m->ev_factor[p.bank] : nullptr;   // later layers are stream-ordered behind layer 0
   hipEvent_t pdone = p.chain_beside() ? m->ev_prep[p.bank][li] : nullptr;
   if (!L.is_head) {
-    const int width = L.v.P * L.R;
+    const int width = L.v.P * L.Rout, lat_width = L.v.P * L.R;   // channels leaving the layer / its GPs (the same unless the layer is mixed, mix.hip)
     const bool expand = in.dedup && li == 0;          // N distinct images -> S*N sampled rows
     const int out_rows = expand ? in.S * in.N : rows;
     DCGP_TRY(ensure_out(m, li, out_rows, width));
+    if (L.mix_W) DCGP_TRY(L.ensure_latent((size_t)out_rows * lat_width));
     auto& o = m->outs[li];
     // device RNG: with a shard declared (dcgp_model_set_shard) every element draws at its counter in the un-sharded batch, one
     // stream per layer -- the step's value is then independent of the number of ranks; otherwise one stream per (layer, rank)
     RngMap rm;
     const bool sharded = m->shard_global > 0;
-    if (sharded && (m->shard_global != in.N || m->shard_lo != 0)) { rm.W = width; rm.Nl = in.N; rm.Ng = m->shard_global; rm.lo = m->shard_lo; }
+    if (sharded && (m->shard_global != in.N || m->shard_lo != 0)) { rm.W = lat_width; rm.Nl = in.N; rm.Ng = m->shard_global; rm.lo = m->shard_lo; }
     HeadUnitsArgs ride;
     if (li == p.ride_layer && (phase & 2)) {   // the head's Kzx rows ride this launch: the sweep head_forward would plan, on this layer's sample
       LayerState& Lh = *m->layers[li + 1];
@@ -318,7 +320,7 @@ int run_layer(dcgp_model* m, const StepPlan& p, const StepIn& in, int li, const 
       ride = head_sweep_shape(ctx, Lh, o.sample, out_rows, out_rows, B, ldh);
       head_units_plan(&ride);
     }
-    DCGP_TRY(conv_forward(ctx, L, F, rows, n_mod, expand ? in.S : 1, (long)in.N * width, z, in.seed, (uint32_t)(li + 1 + (sharded ? 0 : 64 * ctx->rank)),
+    DCGP_TRY(conv_forward(ctx, L, F, rows, n_mod, expand ? in.S : 1, (long)in.N * lat_width, z, in.seed, (uint32_t)(li + 1 + (sharded ? 0 : 64 * ctx->rank)),
                           m->jitter, o.sample, m->keep_outputs ? o.mean : nullptr, m->keep_outputs ? o.var : nullptr, pfx,
                           fdone, pdone, phase, m->keep_state, &rm, li == 0 ? (int)p.first_one_launch : -1,
                           (li == p.ride_layer && (phase & 2)) ? &ride : nullptr, p.ride_rows));
@@ -501,6 +503,12 @@ int forward_all(dcgp_model* m, const double* X, int N, int S, const double* cons
     return ctx_fail(ctx, DCGP_ERR_ARG, "forward: %d images from image %d on overrun the declared global batch of %d (dcgp_model_set_shard)", N,
                     m->shard_lo, m->shard_global);
   DCGP_TRY(check_padding(m));
+  for (int li = 0; li + 1 < nl; ++li) {   // a mixed layer's maps are the next layer's channels (a dense head's single patch: all of them)
+    const LayerState &A = *m->layers[li], &B = *m->layers[li + 1];
+    const bool dense = B.is_head && B.v.H == 1 && B.v.W == 1;
+    if (A.mix_W && B.v.C != (dense ? A.v.P : 1) * A.Rout)
+      return ctx_fail(ctx, DCGP_ERR_ARG, "forward: layer %d is mixed into %d maps, layer %d takes C = %d channels", li, A.Rout, li + 1, B.v.C);
+  }
   DCGP_TRY(ensure_events(m));
   const StepPlan p = plan_step(m, N, S, dedup, need_kl, pipelined);
   StepIn in{X, N, S, zs, seed, dedup, need_kl};
@@ -717,6 +725,10 @@ int dcgp_model_set_param(dcgp_model* model, int layer, const char* which, const 
   if (!strcmp(which, "mean_filter")) {
     if (!L.mean_W) return ctx_fail(ctx, DCGP_ERR_ARG, "set_param(mean_filter): layer %d has no mean filter (dcgp_model_set_mean_filter)", layer);
     DCGP_TRY(expect(L.mean_slots())); return L.upload(L.mean_W, value_host, count);
+  }
+  if (!strcmp(which, "mixing")) {
+    if (!L.mix_W) return ctx_fail(ctx, DCGP_ERR_ARG, "set_param(mixing): layer %d is not mixed (dcgp_model_set_mixing)", layer);
+    DCGP_TRY(expect(L.mix_slots())); return L.upload(L.mix_W, value_host, count);
   }
   if (!strcmp(which, "variance")) { DCGP_TRY(expect(1)); if (!(value_host[0] > 0)) return ctx_fail(ctx, DCGP_ERR_ARG, "variance must be > 0"); L.variance = value_host[0]; return DCGP_OK; }
   if (!strcmp(which, "lengthscale")) { DCGP_TRY(expect(1)); if (!(value_host[0] > 0)) return ctx_fail(ctx, DCGP_ERR_ARG, "lengthscale must be > 0"); L.ls = value_host[0]; return DCGP_OK; }

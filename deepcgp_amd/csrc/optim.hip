@@ -22,7 +22,7 @@ struct OptGroup {
   int hold;                                           // hyp_layer >= 0: bit i set = element i of the triple is held (set_trainable on one ArcCosine parameter)
 };
 constexpr int kNormSlot = 32;        // ctx->h_scratch[32]: a clipped step's norm (the hyper-parameter triples take [0, 24))
-constexpr int OPT_GROUPS_MAX = 56;   // 8 layers of up to 6 groups, and a mean filter on each of the 7 conv layers below a head
+constexpr int OPT_GROUPS_MAX = 56;   // 7 conv layers of up to 6 groups (Z, q_mu, q_sqrt, hyper, mean filter, mixing) below a head of up to 7
 struct OptArgs {
   OptGroup grp[OPT_GROUPS_MAX];
   int first_block[OPT_GROUPS_MAX + 1];
@@ -248,6 +248,7 @@ int opt_enqueue(dcgp_model* model, const char* who, bool sgd, double lr, double 
     if (a.ng > ng_hyp) a.grp[ng_hyp].hold = (int)((L.frozen >> 5) & 3u) << 1;   // bits 32 / 64: elements 1 / 2 of the triple stay where they are
     if (L.ard) DCGP_TRY(add(L.ard, L.gard, L.aard, (long)L.v.L, 1, -1, L.in_scale, (L.frozen & 16u) != 0));   // dense head: per-dimension lengthscales and the staging scale 1 / l
     if (L.mean_W) DCGP_TRY(add(L.mean_W, L.gmean_W, L.amean_W, (long)L.mean_slots(), 0, -1, nullptr, !L.mean_trainable));   // the mean filter (conv_mean.hip)
+    if (L.mix_W) DCGP_TRY(add(L.mix_W, L.gmix_W, L.amix_W, (long)L.mix_slots(), 0, -1, nullptr, !L.mix_trainable));   // the mixing matrix (mix.hip), unconstrained
     if (L.glik) {   // Gaussian likelihood variance / StudentT scale: the last slot of the head's block, moments beside it on the device
       if (!model->d_lik) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: the head's block has a likelihood slot but the model no Gaussian likelihood", who);
       double* lik_mv[2] = {model->d_lik + 1, model->d_lik + 2};
@@ -387,6 +388,11 @@ int dcgp_model_set_trainable(dcgp_model* model, int layer, const char* which, in
     L.mean_trainable = on != 0;
     return DCGP_OK;
   }
+  if (!strcmp(which, "mixing")) {
+    if (!L.mix_W) return ctx_fail(model->ctx, DCGP_ERR_ARG, "set_trainable(mixing): layer %d is not mixed (dcgp_model_set_mixing)", layer);
+    L.mix_trainable = on != 0;
+    return DCGP_OK;
+  }
   unsigned bit = 0;
   if (!strcmp(which, "Z")) bit = 1u;
   else if (!strcmp(which, "q_mu")) bit = 2u;
@@ -438,6 +444,9 @@ int dcgp_model_get_param(dcgp_model* model, int layer, const char* which, double
   } else if (!strcmp(which, "mean_filter")) {
     if (!L.mean_W) return ctx_fail(ctx, DCGP_ERR_ARG, "get_param: this layer has no mean filter");
     src = L.mean_W; n = L.mean_slots();
+  } else if (!strcmp(which, "mixing")) {
+    if (!L.mix_W) return ctx_fail(ctx, DCGP_ERR_ARG, "get_param: this layer is not mixed");
+    src = L.mix_W; n = L.mix_slots();
   } else return ctx_fail(ctx, DCGP_ERR_ARG, "get_param: unknown parameter '%s'", which);
   if (count != n) return ctx_fail(ctx, DCGP_ERR_ARG, "get_param(%s): expected %zu values, got %zu", which, n, count);
   HIP_TRY(ctx, hipMemcpyAsync(out_host, src, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -484,6 +493,9 @@ int dcgp_model_get_grad(dcgp_model* model, int layer, const char* which, double*
   } else if (!strcmp(which, "mean_filter")) {
     if (!L.mean_W || !L.gmean_W) return ctx_fail(ctx, DCGP_ERR_ARG, "get_grad: this layer has no mean filter");
     src = L.gmean_W; n = L.mean_slots();
+  } else if (!strcmp(which, "mixing")) {
+    if (!L.mix_W || !L.gmix_W) return ctx_fail(ctx, DCGP_ERR_ARG, "get_grad: this layer is not mixed");
+    src = L.gmix_W; n = L.mix_slots();
   } else return ctx_fail(ctx, DCGP_ERR_ARG, "get_grad: unknown parameter '%s'", which);
   if (count != n) return ctx_fail(ctx, DCGP_ERR_ARG, "get_grad(%s): expected %zu values, got %zu", which, n, count);
   HIP_TRY(ctx, hipMemcpyAsync(out_host, src, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -520,6 +532,9 @@ static int adam_group(dcgp_model* model, int layer, const char* which, const cha
     } else if (!strcmp(which, "mean_filter")) {
       if (!L.mean_W) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: this layer has no mean filter", who);
       mv = L.amean_W; n = L.mean_slots();
+    } else if (!strcmp(which, "mixing")) {
+      if (!L.mix_W) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: this layer is not mixed", who);
+      mv = L.amix_W; n = L.mix_slots();
     } else return ctx_fail(ctx, DCGP_ERR_ARG, "%s: unknown parameter group '%s'", who, which);
     if (!mv[0] || !mv[1]) return ctx_fail(ctx, DCGP_ERR_ARG, "%s(%s): the group has no moment buffers", who, which);
     *m = mv[0]; *v = mv[1];

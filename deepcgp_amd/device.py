@@ -116,6 +116,10 @@ _SIGS = {
     "dcgp_model_set_input_padding": [_vp, _i, _i],
     "dcgp_model_set_mean_filter": [_vp, _i, _vp, _i],
     "dcgp_debug_conv_mean_time": [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _dp],
+    "dcgp_model_set_mixing": [_vp, _i, _vp, _i, _i],
+    "dcgp_mix_forward": [_vp, _vp, _i, _i, _vp, _vp, _vp, C.c_long, C.c_long, _i, C.c_long, C.c_long, _vp, _vp, _vp],
+    "dcgp_mix_backward": [_vp, _vp, _i, _i, _vp, _vp, C.c_long, _vp, _vp],
+    "dcgp_debug_mix_time": [_vp, _i, _i, C.c_long, _i, _dp],
     "dcgp_model_grad_block": [_vp, _i, C.POINTER(_vp), C.POINTER(C.c_size_t)],
     "dcgp_model_sgd_step": [_vp, _d],
     "dcgp_model_get_adam_state": [_vp, _i, C.c_char_p, _vp, _vp, C.c_size_t],

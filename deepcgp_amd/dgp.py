@@ -13,6 +13,7 @@ from . import augment as _augment
 from . import device as dev
 from .kernels import JITTER
 from .layers import ConvLayer, SVGP_Layer
+from .mean_functions import conv_mean_filter
 from .likelihoods import Bernoulli, Gaussian, Poisson, Softmax, StudentT
 
 
@@ -178,6 +179,14 @@ class DGP_Base:
                 self._model, Hp, Wp, l.feature_maps_in, v.filter_size, v.stride,
                 l.num_inducing, l.gp_count, int(l.white), int(l.identity_mean), l.base_kernel.variance,
                 getattr(l.base_kernel, "lengthscales", 1.0), *[a.ctypes.data for a in keep]))
+            if l.mixing is not None:           # G = gp_count latent GPs into R maps (csrc/mix.hip); ahead of the mean filter, which has R columns
+                W = self._mixing_host(l)
+                ctx._check(L.dcgp_model_set_mixing(self._model, li, W.ctypes.data, W.shape[0], W.shape[1]))
+                if not getattr(l, "mixing_trainable", True):
+                    ctx._check(L.dcgp_model_set_trainable(self._model, li, b"mixing", 0))
+            if l.centre_mean:                  # a mixed layer's Conv2dMean: the frozen centre-pixel filter on the R maps
+                W = np.ascontiguousarray(conv_mean_filter("centre0", v.filter_size, v.feature_maps, l.feature_maps_out), np.float64)
+                ctx._check(L.dcgp_model_set_mean_filter(self._model, li, W.ctypes.data, 0))
             if l.filter_mean is not None:      # LinearConv2dMean: its filter [f, f, C, R] is the device's [L][R] as it stands (csrc/conv_mean.hip)
                 W = self._mean_filter_host(l)
                 ctx._check(L.dcgp_model_set_mean_filter(self._model, li, W.ctypes.data, int(bool(l.filter_mean.trainable))))
@@ -226,9 +235,17 @@ class DGP_Base:
         """A layer's LinearConv2dMean filter as one contiguous float64 [f, f, C, R] array (ValueError for another shape)."""
         mf, v = layer.filter_mean, layer.view
         W = np.ascontiguousarray(mf.conv_filter, np.float64)
-        shape = (v.filter_size, v.filter_size, v.feature_maps, layer.gp_count)
+        shape = (v.filter_size, v.filter_size, v.feature_maps, layer.feature_maps_out)
         if W.shape != shape:
             raise ValueError("LinearConv2dMean.conv_filter must be %s, got %s" % (shape, W.shape))
+        return W
+
+    @staticmethod
+    def _mixing_host(layer):
+        """A mixed layer's W as one contiguous float64 [gp_count, feature_maps_out] array (ValueError for another shape)."""
+        W = np.ascontiguousarray(layer.mixing, np.float64)
+        if W.shape != (layer.gp_count, layer.feature_maps_out):
+            raise ValueError("ConvLayer.mixing must be %s, got %s" % ((layer.gp_count, layer.feature_maps_out), W.shape))
         return W
 
     def push_likelihood_nodes(self):
@@ -263,6 +280,8 @@ class DGP_Base:
                 push(li, "Z0", l.Z_prior)
                 if l.filter_mean is not None:
                     push(li, "mean_filter", self._mean_filter_host(l))
+                if l.mixing is not None:
+                    push(li, "mixing", self._mixing_host(l))
         push(0, "likelihood_epsilon", float(getattr(self.likelihood, "epsilon", 1e-3)))
         if self.gaussian:
             push(0, "likelihood_variance", float(self.likelihood.variance))
@@ -300,6 +319,9 @@ class DGP_Base:
                 out.append(Parameter(base + "/mean_function/conv_filter", lambda l=l: l.filter_mean.conv_filter,
                                      lambda v, l=l: setattr(l.filter_mean, "conv_filter",
                                                             np.array(v, np.float64).reshape(np.shape(l.filter_mean.conv_filter)))))
+            if not head and getattr(l, "mixing", None) is not None:
+                out.append(Parameter(base + "/mixing/W", lambda l=l: l.mixing,
+                                     lambda v, l=l: setattr(l, "mixing", np.array(v, np.float64).reshape(np.shape(l.mixing)))))
             if head and not dense:
                 out.append(Parameter(base + "/kern/patch_weights", lambda l=l: l.kern.patch_weights,
                                      lambda v, l=l: setattr(l.kern, "patch_weights", np.array(v, np.float64))))
@@ -315,7 +337,10 @@ class DGP_Base:
             if z is None:
                 arr[i] = None
                 continue
-            D = self.layers[i].num_outputs
+            D = self._out_dims()[i]
+            if np.size(z) != S * N * D:
+                raise ValueError("zs[%d] has %d values, layer %d draws S x N x D = %d x %d x %d = %d (a mixed layer: one per patch and latent GP)"
+                                 % (i, np.size(z), i, S, N, D, S * N * D))
             dz = ctx.to_device(np.reshape(z, (S, N, D)))
             keep.append(dz)
             arr[i] = dz.ptr
@@ -382,7 +407,8 @@ class DGP_Base:
         """(ELBO, [per-layer dict]) -- the value and gradient TensorFlow hands the optimiser at
         conv_gp/experiment.py:84-108, from the hand-written reverse pass (csrc/grad.hip).  Keys: ``Z``,
         ``q_mu``, ``q_sqrt`` (lower triangle), ``variance``, ``lengthscales`` and, for the head,
-        ``patch_weights``; a conv layer with a ``LinearConv2dMean`` adds ``mean_filter`` [f, f, C, R] (zero while the filter is frozen);
+        ``patch_weights``; a conv layer with a ``LinearConv2dMean`` adds ``mean_filter`` [f, f, C, R] (zero while the filter is frozen), a mixed
+        conv layer ``mixing`` [G, R] (zero while frozen);
         all with respect to the constrained values."""
         self._build()
         ctx, L = self._ctx, dev.lib()
@@ -416,6 +442,8 @@ class DGP_Base:
                 shapes["weight_variances"], shapes["bias_variance"] = (), ()
             if not head and l.filter_mean is not None:
                 shapes["mean_filter"] = np.shape(l.filter_mean.conv_filter)
+            if not head and l.mixing is not None:
+                shapes["mixing"] = np.shape(l.mixing)
             g = {}
             for which, shp in shapes.items():
                 buf = np.empty(shp, np.float64)
@@ -732,13 +760,15 @@ class DGP_Base:
                 out.append((base + "ard_lengthscales", li, "ard_lengthscales", (int(np.size(l.kern.lengthscales)),)))
             if not head and l.filter_mean is not None:
                 out.append((base + "mean_filter", li, "mean_filter", np.shape(l.filter_mean.conv_filter)))
+            if not head and l.mixing is not None:
+                out.append((base + "mixing", li, "mixing", np.shape(l.mixing)))
         if self.gaussian or self.student_t:
             out.append(("likelihood", 0, "likelihood", (1,)))
         return out
 
     def optimizer_state(self):
         """The device optimiser's own state: ``{"t": Adam's step count, "<group>/m": first moments, "<group>/v": second moments}`` for every
-        group of ``_optimizer_groups`` -- ``layers/<i>/<Z | q_mu | q_sqrt | w | hyper | ard_lengthscales | mean_filter>`` and ``likelihood`` --
+        group of ``_optimizer_groups`` -- ``layers/<i>/<Z | q_mu | q_sqrt | w | hyper | ard_lengthscales | mean_filter | mixing>`` and ``likelihood`` --
         in the unconstrained space the optimiser works in.  A model that has never stepped reports zeros and ``t = 0``.  With the parameters
         (``pull_parameters``) it is everything a later step depends on: see ``set_optimizer_state``."""
         self._build()
@@ -818,13 +848,18 @@ class DGP_Base:
         """param.set_trainable(on) for the device optimiser steps: which in Z, q_mu, q_sqrt, w, hyper (every kernel parameter of the layer);
         weight_variances, bias_variance (that one parameter of an ArcCosine conv layer); "likelihood_variance" (Gaussian likelihood,
         ``layer`` ignored); "likelihood_scale" (StudentT likelihood, ``layer`` ignored); "mean_filter" (the filter of a conv layer's
-        ``LinearConv2dMean``: frozen, its gradient is not formed either)."""
+        ``LinearConv2dMean``: frozen, its gradient is not formed either); "mixing" (a mixed conv layer's W, likewise)."""
         self._build()
         if which == "mean_filter":
             mf = getattr(self.layers[int(layer)], "filter_mean", None) if 0 <= int(layer) < len(self.layers) - 1 else None
             if mf is None:
                 raise ValueError("set_trainable: layer %d has no LinearConv2dMean" % int(layer))
             mf.trainable = bool(on)
+        if which == "mixing":
+            l = self.layers[int(layer)] if 0 <= int(layer) < len(self.layers) - 1 else None
+            if getattr(l, "mixing", None) is None:
+                raise ValueError("set_trainable: layer %d is not mixed" % int(layer))
+            l.mixing_trainable = bool(on)
         self._ctx._check(dev.lib().dcgp_model_set_trainable(self._model, int(layer), which.encode(), int(bool(on))))
 
     def natgrad_step(self, gamma):
@@ -866,6 +901,8 @@ class DGP_Base:
                 l.kern.patch_weights = pull(li, "w", np.shape(l.kern.patch_weights))
             if not head and l.filter_mean is not None:
                 l.filter_mean.conv_filter = pull(li, "mean_filter", np.shape(l.filter_mean.conv_filter))
+            if not head and l.mixing is not None:
+                l.mixing = pull(li, "mixing", np.shape(l.mixing))
         if self.gaussian:
             self.likelihood.variance = float(pull(0, "likelihood_variance", ()))
         if self.student_t:
@@ -907,6 +944,10 @@ class DGP_Base:
         the image-pair K and the batched conditional, one call each for all S samples; the samples come from one
         dcgp_reparam_full_cov launch per layer.  Noise: ``zs[l]`` [S, N, D_l] where given, else np.random.default_rng(seed) --
         these draws cannot match the on-device draws the mean-field path makes for the same seed.  Rank-local."""
+        for li, l in enumerate(self.layers[:-1]):
+            if getattr(l, "mixing", None) is not None:
+                raise NotImplementedError("full-covariance predictions through a mixed layer are not provided (layer %d has a mixing W %r)"
+                                          % (li, np.shape(l.mixing)))
         self.pull_parameters()
         from .layers import reparameterize_full_cov
         X = np.asarray(X, np.float64)
@@ -1043,7 +1084,8 @@ class DGP_Base:
         return self.propagate(X, S=S, zs=zs, seed=seed)
 
     def _out_dims(self):
-        return [l.num_outputs for l in self.layers]
+        """Noise values per row and layer: one per output, for a mixed conv layer one per (patch, latent GP)."""
+        return [getattr(l, "num_latent_outputs", l.num_outputs) for l in self.layers]
 
     # ---- test-time augmentation --------------------------------------------------------------------
     @contextlib.contextmanager

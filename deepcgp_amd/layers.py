@@ -115,6 +115,44 @@ class MultiOutputConvKernel:
         return np.full((P, N), self.base_kernel.variance)
 
 
+def mixing_matrix(kind, G, R, seed=0):
+    """A mixed ConvLayer's W [G, R]: ``"identity"`` (needs G == R), ``"random"`` (entries N(0, 1/G) from ``RandomState(seed)``: a map's
+    variance is about a latent's), or an array [G, R] taken as it is."""
+    G, R = int(G), int(R)
+    if G < 1 or R < 1:
+        raise ValueError("mixing_matrix: G and R must be >= 1, got %d and %d" % (G, R))
+    if isinstance(kind, str):
+        if kind == "identity":
+            if G != R:
+                raise ValueError("mixing_matrix('identity') needs G == R, got %d and %d" % (G, R))
+            return np.eye(G)
+        if kind == "random":
+            return np.random.RandomState(int(seed)).standard_normal((G, R)) / np.sqrt(G)
+        raise ValueError("mixing_matrix: kind %r, expected 'identity', 'random' or an array [G, R]" % (kind,))
+    W = np.array(kind, np.float64)
+    if W.shape != (G, R):
+        raise ValueError("mixing_matrix: the array must be [%d, %d], got %r" % (G, R, W.shape))
+    return W
+
+
+def mix_forward(W, u, gm, gv):
+    """(sample, mean, var) [K, R] of latent (u, gm, gv) [K, G] through W [G, R] on the device (dcgp_mix_forward); an input may be None, its
+    output is then None."""
+    ctx = dev.get_context()
+    W = np.ascontiguousarray(W, np.float64)
+    G, R = W.shape
+    first = next(a for a in (u, gm, gv) if a is not None)
+    cols = int(np.size(first)) // G
+    ins = [None if a is None else ctx.to_device(np.reshape(np.asarray(a, np.float64), (cols, G))) for a in (u, gm, gv)]
+    outs = [None if a is None else ctx.empty((cols, R)) for a in ins]
+    dW = ctx.to_device(W)
+    if cols:
+        ctx._check(dev.lib().dcgp_mix_forward(ctx.handle, dW.ptr, G, R, *[a.ptr if a else None for a in ins], 0, cols, 1, 0, 0,
+                                              *[a.ptr if a else None for a in outs]))
+    shape = first.shape[:-1] + (first.shape[-1] // G * R,)
+    return tuple(None if a is None else a.numpy().reshape(shape) for a in outs)
+
+
 class Layer:
     """doubly_stochastic_dgp.layers.Layer: conditional_SND / sample_from_conditional on top of a
     subclass's conditional_ND (subclassed at conv_gp/layers.py:52)."""
@@ -152,17 +190,30 @@ class ConvLayer(Layer):
     on the NHWC image returning N x num_outputs (or N x H' x W' x gp_count) values, or the aliases None / 'zero' / 'conv2d'.
     A ``Conv2dMean`` with the filter its constructor built is added inside the layer's own launch; a ``LinearConv2dMean`` (any filter,
     optionally trained) lives on the device model and is added behind the layer's launch (``filter_mean``; csrc/conv_mean.hip); any other
-    callable through its ``__call__`` (the model-level one-call ELBO path takes the first two only)."""
+    callable through its ``__call__`` (the model-level one-call ELBO path takes the first two only).
+
+    ``mixing``: None, or W [G, R] with G = ``gp_count``: the layer holds G latent GPs and emits R feature maps, a trainable linear mix of them
+    (gpflow's SharedMixed... / LinearCoregionalization; csrc/mix.hip).  Sample, then mix: ``sample = (gm + z sqrt(gv + jitter)) W + m(x)`` with
+    ``z`` of P * G values a row; ``conditional_ND`` returns the marginals ``gm W + m(x)``, ``gv W^2``.  The mean function then has
+    ``feature_maps_out = R`` maps (a ``Conv2dMean`` runs as the frozen centre-pixel filter), the KL term stays the G latent GPs'."""
 
     def __init__(self, base_kernel, mean_function, feature=None, view=None, white=False, gp_count=1,
-                 q_mu=None, q_sqrt=None, **kwargs):
+                 q_mu=None, q_sqrt=None, mixing=None, **kwargs):
         self.base_kernel = base_kernel
         self.view = view
         self.feature_maps_in = self.view.feature_maps
         self.gp_count = int(gp_count)
         self.patch_count = self.view.patch_count
         self.patch_length = self.view.patch_length
-        self.num_outputs = self.patch_count * self.gp_count
+        self.mixing = None
+        if mixing is not None:
+            W = np.array(mixing, np.float64)
+            if W.ndim != 2 or W.shape[0] != self.gp_count or W.shape[1] < 1:
+                raise ValueError("mixing must be [gp_count, R] = [%d, R >= 1], got shape %r" % (self.gp_count, W.shape))
+            self.mixing = W
+        self.feature_maps_out = self.gp_count if self.mixing is None else int(self.mixing.shape[1])
+        self.num_outputs = self.patch_count * self.feature_maps_out
+        self.num_latent_outputs = self.patch_count * self.gp_count
         self.conv_kernel = MultiOutputConvKernel(base_kernel, int(np.prod(view.input_size)) * view.feature_maps,
                                                  patch_count=self.patch_count)
         self.white = bool(white)
@@ -192,7 +243,7 @@ class ConvLayer(Layer):
             return None
         v = self.view
         have = (mf.filter_size, mf.stride, mf.feature_maps_in, mf.feature_maps_out)
-        want = (v.filter_size, v.stride, v.feature_maps, self.gp_count)
+        want = (v.filter_size, v.stride, v.feature_maps, self.feature_maps_out)
         if have != want:
             raise ValueError("LinearConv2dMean(filter_size, feature_maps_in, feature_maps_out, stride) = %r does not match the layer's view "
                              "and gp_count %r" % ((have[0], have[2], have[3], have[1]), (want[0], want[2], want[3], want[1])))
@@ -201,7 +252,16 @@ class ConvLayer(Layer):
     @property
     def identity_mean(self):
         """The mean the layer kernels add themselves: Conv2dMean's centre pixel of input channel 0 into output map 0
-        (conv_gp/mean_functions.py:28-41), geometry equal to the view's."""
+        (conv_gp/mean_functions.py:28-41), geometry equal to the view's.  Not on a mixed layer: see ``centre_mean``."""
+        return self.mixing is None and self._conv2d_initial()
+
+    @property
+    def centre_mean(self):
+        """A mixed layer's Conv2dMean: the same centre pixel into output map 0 of the R maps, which the layer's own launch cannot add (it
+        writes the latent maps): the device model runs it as the frozen ``centre0`` filter (csrc/conv_mean.hip)."""
+        return self.mixing is not None and self._conv2d_initial()
+
+    def _conv2d_initial(self):
         mf = self.mean_function
         if isinstance(mf, str):
             return mf == 'conv2d'
@@ -212,14 +272,14 @@ class ConvLayer(Layer):
         v = self.view
         return (getattr(mf, 'filter_size', v.filter_size) == v.filter_size and getattr(mf, 'stride', v.stride) == v.stride and
                 getattr(mf, 'feature_maps_in', v.feature_maps) == v.feature_maps and
-                getattr(mf, 'feature_maps_out', self.gp_count) == self.gp_count)
+                getattr(mf, 'feature_maps_out', self.feature_maps_out) == self.feature_maps_out)
 
     @property
     def generic_mean(self):
         """A callable mean function the kernels do not add themselves (``mean + self.mean_function(mean_view)``, layers.py:133-134)."""
         mf = self.mean_function
         from .mean_functions import Zero
-        if mf is None or isinstance(mf, (str, Zero)) or self.identity_mean or self.filter_mean is not None:
+        if mf is None or isinstance(mf, (str, Zero)) or self._conv2d_initial() or self.filter_mean is not None:
             if isinstance(mf, str) and mf not in ('zero', 'conv2d'):
                 raise ValueError("mean_function %r: expected a callable, None, 'zero' or 'conv2d'" % (mf,))
             return None
@@ -232,6 +292,12 @@ class ConvLayer(Layer):
         N = X4.shape[0]
         if mf is None and self.filter_mean is not None:      # the layer's own window: the filter sees the zero-padded image
             return np.asarray(self.filter_mean(self.view.pad(X4)), np.float64).reshape(N, self.num_outputs)
+        if mf is None and self.centre_mean:
+            v = self.view
+            c0, st = v.filter_size // 2, v.stride
+            val = np.zeros((N, v.patch_count, self.feature_maps_out))
+            val[:, :, 0] = v.pad(X4)[:, c0:c0 + (v.out_image_height - 1) * st + 1:st, c0:c0 + (v.out_image_width - 1) * st + 1:st, 0].reshape(N, v.patch_count)
+            return val.reshape(N, self.num_outputs)
         if mf is None:
             return None
         val = np.asarray(mf(self.view.mean_view(X4, None)), np.float64)
@@ -242,6 +308,8 @@ class ConvLayer(Layer):
     def conditional_ND(self, ND_X, full_cov=False):
         """mean, var of q(f | m, S), each N x (patch_count * gp_count), HWC column order."""
         if full_cov:
+            if self.mixing is not None:
+                raise NotImplementedError("full_cov=True through a mixed layer (mixing W [%d, %d]) is not provided" % self.mixing.shape)
             return self._conditional_full_cov(ND_X)
         return self._forward(ND_X, None)[1:]
 
@@ -270,6 +338,25 @@ class ConvLayer(Layer):
         return mean, var
 
     def _forward(self, ND_X, z):
+        """(sample or None, mean, var), each N x num_outputs."""
+        if self.mixing is None:
+            return self._forward_gp(ND_X, z)
+        # a mixed layer: the G latent GPs' conditional, the sample in the latent space, then the three mixes in one operator call (csrc/mix.hip)
+        ND_X = np.ascontiguousarray(ND_X, np.float64)
+        N, v = ND_X.shape[0], self.view
+        _, gm, gv = self._forward_gp(ND_X, None)
+        if N == 0:
+            return (None if z is None else np.zeros((0, self.num_outputs))), np.zeros((0, self.num_outputs)), np.zeros((0, self.num_outputs))
+        u = None if z is None else reparameterize(gm, gv, np.reshape(z, gm.shape))
+        smp, mean, var = mix_forward(self.mixing, u, gm, gv)
+        extra = self._generic_mean_value(ND_X.reshape(N, v.input_size[0], v.input_size[1], self.feature_maps_in))
+        if extra is not None:
+            mean = mean + extra
+            smp = None if smp is None else smp + extra
+        return smp, mean, var
+
+    def _forward_gp(self, ND_X, z):
+        """The layer's gp_count GPs: (sample or None, mean, var), each N x num_latent_outputs -- with the mean function unless the layer is mixed."""
         ctx = dev.get_context()
         ND_X = np.ascontiguousarray(ND_X, np.float64)
         N = ND_X.shape[0]
@@ -277,7 +364,7 @@ class ConvLayer(Layer):
         H, W = v.input_size[0], v.input_size[1]
         if ND_X.shape[1] != H * W * self.feature_maps_in:
             raise ValueError("expected N x %d inputs, got %s" % (H * W * self.feature_maps_in, ND_X.shape))
-        D = self.num_outputs
+        D = self.num_latent_outputs
         if N == 0:
             return np.zeros((0, D)), np.zeros((0, D)), np.zeros((0, D))
         if not isinstance(self.base_kernel, RBF):
@@ -296,7 +383,7 @@ class ConvLayer(Layer):
             ds.ptr if ds else None, dm.ptr, dv.ptr, C.byref(info))
         ctx._check(rc, info)
         smp, mean, var = (ds.numpy() if ds else None), dm.numpy(), dv.numpy()
-        extra = self._generic_mean_value(ND_X.reshape(N, H, W, self.feature_maps_in))
+        extra = None if self.mixing is not None else self._generic_mean_value(ND_X.reshape(N, H, W, self.feature_maps_in))
         if extra is not None:
             mean = mean + extra
             smp = None if smp is None else smp + extra
@@ -313,8 +400,8 @@ class ConvLayer(Layer):
         PMN_Kuf = self.conv_kernel.Kuf(self.feature.Z, (X4, v))
         Knn = np.full((v.patch_count, N), self.base_kernel.variance)
         mean, var = conditional(PMN_Kuf, MM_Kuu, Knn, self.q_mu, q_sqrt=self.q_sqrt, white=self.white)   # N x P x R, R x P x N
-        mean = mean.reshape(N, self.num_outputs)
-        var = np.transpose(var, (2, 1, 0)).reshape(N, self.num_outputs)
+        mean = mean.reshape(N, self.num_latent_outputs)
+        var = np.transpose(var, (2, 1, 0)).reshape(N, self.num_latent_outputs)
         if self.identity_mean:
             f, st = v.filter_size, v.stride
             Ho, Wo = v.out_image_height, v.out_image_width
@@ -322,7 +409,7 @@ class ConvLayer(Layer):
             centre = v.pad(X4)[:, c0:c0 + (Ho - 1) * st + 1:st, c0:c0 + (Wo - 1) * st + 1:st, 0]
             mean = mean.copy()
             mean.reshape(N, v.patch_count, self.gp_count)[:, :, 0] += centre.reshape(N, v.patch_count)
-        extra = self._generic_mean_value(X4)
+        extra = None if self.mixing is not None else self._generic_mean_value(X4)
         if extra is not None:
             mean = mean + extra
         sample = None if z is None else reparameterize(mean, var, np.reshape(z, mean.shape))
@@ -333,9 +420,12 @@ class ConvLayer(Layer):
             return Layer.sample_from_conditional(self, X, z=z, full_cov=True)
         X = np.asarray(X, np.float64)
         S, N, D = X.shape
+        Dz = self.num_latent_outputs      # noise per row: one value per (patch, GP)
         if z is None:
-            z = np.random.standard_normal((S, N, self.num_outputs))
-        s, m, v = self._forward(X.reshape(S * N, D), np.reshape(z, (S * N, self.num_outputs)))
+            z = np.random.standard_normal((S, N, Dz))
+        if np.size(z) != S * N * Dz:
+            raise ValueError("z has %d values, the layer draws S x N x %d = %d" % (np.size(z), Dz, S * N * Dz))
+        s, m, v = self._forward(X.reshape(S * N, D), np.reshape(z, (S * N, Dz)))
         shape = (S, N, self.num_outputs)
         return s.reshape(shape), m.reshape(shape), v.reshape(shape)
 

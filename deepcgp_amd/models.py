@@ -4,12 +4,12 @@ import numpy as np
 
 from .dgp import DGP_Base
 from .kernels import RBF, ArcCosine, Matern32, Matern52, ConvKernel, AdditivePatchKernel, PatchInducingFeatures, InducingPoints
-from .layers import ConvLayer, SVGP_Layer
+from .layers import ConvLayer, SVGP_Layer, mixing_matrix
 from .likelihoods import MultiClass, Softmax
 from .mean_functions import Conv2dMean, IdentityConv2dMean  # noqa: F401  (the names conv_gp/models.py:11 imports)
 from .mean_functions import MEAN_FILTERS, LinearConv2dMean, conv_mean_filter
 from .views import FullView
-from .arguments import parse_paddings
+from .arguments import parse_latent_gps, parse_paddings
 
 
 def parse_ints(int_string):
@@ -27,7 +27,9 @@ BASE_KERNELS = {"rbf": RBF, "acos": ArcCosine, "matern32": Matern32, "matern52":
 
 
 def build_layers_from_spec(spec):
-    """Layers of a neutral model spec.  An entry's optional ``pad`` is the zero padding of its input; its ``H``, ``W`` stay unpadded."""
+    """Layers of a neutral model spec.  An entry's optional ``pad`` is the zero padding of its input; its ``H``, ``W`` stay unpadded.  A conv
+    entry's optional ``mix_W`` [R, Rout] mixes its R GPs into Rout maps (``mix_trainable``, default True: whether the optimiser moves it); its
+    mean function then has Rout maps and the next entry's ``C`` is Rout."""
     if spec["head"].get("kernel", "conv") == "rbf" and spec["head"].get("pad", 0):
         raise ValueError("--paddings: the dense head of --last-kernel rbf takes no padding (pad %d)" % spec["head"]["pad"])
     layers = []
@@ -41,18 +43,28 @@ def build_layers_from_spec(spec):
             base = ArcCosine(view.patch_length, order=0, variance=av, weight_variances=aw, bias_variance=ab)
         else:
             base = BASE_KERNELS[kind](view.patch_length, c["variance"], c["ls"])
+        mix_W = None if c.get("mix_W") is None else np.array(c["mix_W"], np.float64)
+        if mix_W is not None and (mix_W.ndim != 2 or mix_W.shape[0] != c["R"]):
+            raise ValueError("a conv entry's mix_W must be [R, Rout] = [%d, Rout], got shape %r" % (c["R"], mix_W.shape))
+        Rout = c["R"] if mix_W is None else int(mix_W.shape[1])      # maps leaving the layer
         mf = c.get("mean_function")
         if mf == "conv2d":      # --identity-mean: Conv2dMean(filter_size, NHWC[3], feature_map, stride=stride), conv_gp/models.py:95-97
-            mf = Conv2dMean(c["f"], c["C"], c["R"], stride=c["s"])
+            mf = Conv2dMean(c["f"], c["C"], Rout, stride=c["s"])
             mf.set_trainable(False)                                                            # models.py:100
         if c.get("mean_filter") is not None:      # a linear convolutional mean on the device: its filter [f, f, C, R] (or [f f C, R]) and whether it is trained
             if mf is not None:
                 raise ValueError("a conv entry takes mean_function or mean_filter, not both")
-            W = np.array(c["mean_filter"], np.float64).reshape(c["f"], c["f"], c["C"], c["R"])
-            mf = LinearConv2dMean(c["f"], c["C"], c["R"], stride=c["s"], filter=W, trainable=bool(c.get("mean_trainable", False)))
-        layer = ConvLayer(base, mf,
-                          feature=PatchInducingFeatures(c["Z"]), view=view, white=c["white"], gp_count=c["R"],
-                          q_mu=c["q_mu"], q_sqrt=c["q_sqrt"])
+            W = np.array(c["mean_filter"], np.float64).reshape(c["f"], c["f"], c["C"], Rout)
+            mf = LinearConv2dMean(c["f"], c["C"], Rout, stride=c["s"], filter=W, trainable=bool(c.get("mean_trainable", False)))
+        if mix_W is None:
+            layer = ConvLayer(base, mf,
+                              feature=PatchInducingFeatures(c["Z"]), view=view, white=c["white"], gp_count=c["R"],
+                              q_mu=c["q_mu"], q_sqrt=c["q_sqrt"])
+        else:
+            layer = ConvLayer(base, mf,
+                              feature=PatchInducingFeatures(c["Z"]), view=view, white=c["white"], gp_count=c["R"],
+                              q_mu=c["q_mu"], q_sqrt=c["q_sqrt"], mixing=mix_W)
+            layer.mixing_trainable = bool(c.get("mix_trainable", True))
         layer.Z_prior = np.array(c.get("Z0", c["Z"]), np.float64)
         layer._build_prior_cholesky()
         layers.append(layer)
@@ -490,7 +502,8 @@ CHECKPOINT_FIELDS = (
     ("base_kernel/variance", "variance"),          # conv_kernel/base_kernel/... (conv layers), kern/base_kernel/... (patch heads)
     ("base_kernel/lengthscales", "ls"),
     ("kern/patch_weights", "w"),
-    ("mean_function/conv_filter", "mean_filter"),  # a conv layer's LinearConv2dMean (--mean-filter / --train-mean)
+    ("mean_function/conv_filter", "mean_filter"),
+    ("mixing/W", "mix_W"),                         # a mixed conv layer's W [G, R] (--latent-gps)  # a conv layer's LinearConv2dMean (--mean-filter / --train-mean)
     ("kern/variance", "variance"),                 # dense RBF head (--last-kernel rbf): the kernel sits directly under kern/
     ("kern/lengthscales", "ls"),
 )
@@ -594,6 +607,7 @@ class ModelBuilder(object):
             raise ValueError("Invalid last layer kernel")
         white = bool(fl.white)
         mean_kind, train_mean = self.mean_flags()
+        latent = parse_latent_gps(fl, len(convs))         # --latent-gps: G per conv layer, 0 = unmixed
         spec = {"S": int(fl.num_samples), "num_data": int(self.X_train.shape[0]), "convs": []}
         images = self.X_train                              # what the next layer is initialised on
         for li, (M, f, s, R) in enumerate(convs):
@@ -601,12 +615,16 @@ class ModelBuilder(object):
             _, H, W, C = images.shape                          # (H, W stay the unpadded size; "pad" carries the border)
             images = zero_pad(images, pads[li])                # inducing patches and the next layer's images: from what the window sees
             Z = have["Z"] if "Z" in have else PatchInducingFeatures.from_images(images, M, f).Z
+            G = latent[li] or R                                # the layer's GPs; R stays the maps it emits
             spec["convs"].append(dict(
-                H=H, W=W, C=C, f=f, s=s, M=M, R=R, Z=Z, Z0=Z, white=white, base=fl.base_kernel, pad=pads[li],
+                H=H, W=W, C=C, f=f, s=s, M=M, R=G, Z=Z, Z0=Z, white=white, base=fl.base_kernel, pad=pads[li],
                 variance=float(have.get("variance", 5.0)), ls=float(have.get("ls", 5.0)),     # models.py:114-117
                 q_mu=have.get("q_mu"), q_sqrt=have.get("q_sqrt"),
                 q_sqrt_scale=None if "q_sqrt" in have else 1e-5,                               # start with low variance (models.py:136-138)
                 mean_function="conv2d" if mean_kind == "conv2d" else None))
+            if latent[li]:      # a mixed layer: the checkpoint's W, else N(0, 1/G) entries seeded by the layer index
+                W = have["mix_W"] if "mix_W" in have else mixing_matrix("random", G, R, seed=li)
+                spec["convs"][-1].update(mix_W=mixing_matrix(W, G, R), mix_trainable=not bool(getattr(fl, "freeze_mixing", False)))
             if mean_kind not in (None, "conv2d"):             # LinearConv2dMean: the checkpoint's filter, else the named one
                 W = have["mean_filter"] if "mean_filter" in have else conv_mean_filter(mean_kind, f, C, R)
                 spec["convs"][-1].update(mean_filter=np.array(W, np.float64).reshape(f, f, C, R), mean_trainable=train_mean)

@@ -265,6 +265,22 @@ int dcgp_model_set_input_padding(dcgp_model* model, int layer, int pad);
  * (conv_gp/mean_functions.py:6-41, conv_gp/layers.py:133-134).  It is no input of the factorisation chain: writing it starts no new
  * parameter version, so dcgp_model_set_factor_reuse keeps its chain.  No atomics: two runs give the same bits. */
 int dcgp_model_set_mean_filter(dcgp_model* model, int layer, const double* filter_host /* [f*f*C][R] */, int trainable);
+/* A mixed conv layer (csrc/mix.hip; gpflow's SharedMixed... / LinearCoregionalization on the patches): the layer's G = gp_count latent GPs leave it as R
+ * feature maps, sample[j, r] = sum_g u[j, g] W[g, r] of the latent sample u (sample, then mix: P * G noise values a row, the counters of an unmixed
+ * layer of gp_count G), mean[j, r] = sum_g gm[j, g] W[g, r], var[j, r] = sum_g gv[j, g] W[g, r]^2; a mean filter then has R columns and adds into the
+ * maps.  The KL term is the G latent GPs'.  W_host [G][R], unconstrained, trainable until dcgp_model_set_trainable(.., "mixing", 0); NULL switches the
+ * mixing off again.  W is "mixing" in dcgp_model_set_param / _get_param / _get_grad / _set_trainable and the moment accessors; its gradient sits at
+ * the very end of the layer's gradient block.  Starts a new parameter version.  DCGP_ERR_ARG, naming the number: G other than the layer's gp_count, R
+ * outside 1 .. 64 or other than the channels C the next layer takes, the head, a layer added with identity_mean (give it the centre-pixel filter
+ * through dcgp_model_set_mean_filter), a layer that has its mean filter already or has taken a gradient step, enqueued steps still to be collected.
+ * A mixed layer cannot carry the head's rows in its launch, and it is not the model's last layer.  No atomics: two runs give the same bits. */
+int dcgp_model_set_mixing(dcgp_model* model, int layer, const double* W_host /* [G][R] or NULL */, int G, int R);
+/* The mixing's kernels as operators (device pointers, synchronous).  Forward: columns col0 .. col0 + Kc - 1, replica s < rep of column j at
+ * s * lat_stride + j * G of u / gm / gv and at s * out_stride + j * R of sample / mean / var (each output and its input may be NULL). */
+int dcgp_mix_forward(dcgp_ctx* ctx, const double* W_dev, int G, int R, const double* u_dev, const double* gm_dev, const double* gv_dev, long col0, long Kc,
+                     int rep, long lat_stride, long out_stride, double* sample_dev, double* mean_dev, double* var_dev);
+/* Backward on Kc columns: gu [Kc][G] = gF W^T and gW [G][R] = u^T gF (either may be NULL); gW's partial sums have a fixed order. */
+int dcgp_mix_backward(dcgp_ctx* ctx, const double* W_dev, int G, int R, const double* u_dev, const double* gF_dev, long Kc, double* gu_dev, double* gW_dev);
 /* keep every layer's (sample, mean, var) of the next forward passes for dcgp_model_layer_output   */
 int dcgp_model_set_keep_outputs(dcgp_model* model, int on);
 /* Push a changed parameter: which = "Z", "Z0", "q_mu", "q_sqrt", "w", "variance", "lengthscale", or
@@ -745,6 +761,11 @@ int dcgp_debug_set_sweep_trace(dcgp_ctx* ctx, long long* buf_dev, long n_workgro
  * launches between two events behind a warm-up.  out_us[8] = microseconds per launch {conv_mean_add, its copy, conv_mean_backward_dx, its copy,
  * conv_mean_backward_filter (both stages), its copy, 0, 0}. */
 int dcgp_debug_conv_mean_time(dcgp_ctx* ctx, int H, int W, int C, int f, int stride, int R, int rows, int rep, int iters, double* out_us);
+
+/* The three kernels of a mixing (csrc/mix.hip) alone on Kc columns, G latent GPs, R maps, each beside a copy kernel moving the bytes the kernel has to
+ * move (tools/mixing_time.py).  out_us[8] = microseconds per launch {mix_forward, its copy, mix_backward_latent, its copy, mix_backward_w (both
+ * stages), its copy, 0, 0}. */
+int dcgp_debug_mix_time(dcgp_ctx* ctx, int G, int R, long Kc, int iters, double* out_us);
 
 #ifdef __cplusplus
 }
