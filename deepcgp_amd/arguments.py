@@ -28,6 +28,7 @@ FLAGS = (
     ("--test-flip", None, False, "test-time augmentation: every view also mirrored left-right"),
     ("--test-views", str, "cross", "which shifts --test-shift N takes: cross (0 and +-N along each axis, 5 views) | grid (all (2N+1)^2 shifts)"),
     ("--base-kernel", str, "rbf", "base kernel of the conv layers: rbf | acos | matern32 | matern52"),
+    ("--ard", None, False, "per-dimension (ARD) lengthscales on the conv layers' base kernel: one per patch element, f*f*C a layer (needs --base-kernel rbf)"),
     ("--white", None, False, "whitened variational parameters"),
     ("--last-kernel", str, "conv", "head kernel: conv | add | rbf"),
     ("--likelihood", str, "robustmax", "multi-class likelihood: robustmax | softmax"),

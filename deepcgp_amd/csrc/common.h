@@ -364,6 +364,9 @@ struct PatchRbfArgs {
   const double* w = nullptr; double scale = 1; int reduce = 0;
   // the sweep runs beside the latency-bound side-stream chain: hold it to two workgroups per CU (see patch_rbf)
   int share_cu = 0;
+  // [L] or nullptr: 1 / lengthscale per PATCH element (a conv layer's RBF(ARD=True)): the gathered operand is scaled, ZT / zn arrive scaled.  Last, so
+  // that the fields above keep their places in the argument block.
+  const double* patch_scale = nullptr;
 };
 int patch_rbf(dcgp_ctx* ctx, const PatchRbfArgs& a, const char* timer_name);
 int head_sweep(dcgp_ctx* ctx, const PatchRbfArgs& a, const double* w, const double** kd_partial, int* n_pairs, double* kd_scale);

@@ -260,8 +260,10 @@ __global__ __launch_bounds__(256) void kuu_backward_kernel(const double* __restr
 // A patch row (kh fixed) is ONE contiguous run of f C doubles of the image, and so is its place in Xcol: block (n, oh) copies the
 // Wo f runs of its patch row -- thread (run slot, j): no division inside the loop.  (One thread per element with 64-bit index
 // arithmetic: 26 us for the head's 41 MB at the headline size; one 250-element patch per block: 28.)
+// SC (an ARD conv layer): Xcol[.][l] = patch[l] * sc[l], the patch divided by its per-dimension lengthscales while it is gathered
+template <bool SC>
 __global__ __launch_bounds__(256) void im2col_kernel(const double* __restrict__ X, int n_mod, int H, int W, int C, int f, int s, int Ho, int Wo,
-                                                     int L, double* __restrict__ Xcol) {
+                                                     int L, double* __restrict__ Xcol, const double* __restrict__ sc) {
   const int fc = f * C, n = blockIdx.x / Ho, oh = blockIdx.x - n * Ho;
   const int per = fc >= 256 ? 1 : 256 / fc;               // runs in flight per pass
   const int slot = fc >= 256 ? 0 : threadIdx.x / fc, j0 = fc >= 256 ? threadIdx.x : threadIdx.x - slot * fc;
@@ -273,13 +275,18 @@ __global__ __launch_bounds__(256) void im2col_kernel(const double* __restrict__ 
     const int ow = r / f, kh = r - ow * f;
     const double* __restrict__ src = img + ((long)(oh * s + kh) * W + ow * s) * C;
     double* __restrict__ dst = out + (long)ow * L + kh * fc;
-    for (int j = j0; j < fc; j += 256) dst[j] = src[j];
+    for (int j = j0; j < fc; j += 256) {
+      if constexpr (SC) dst[j] = src[j] * sc[kh * fc + j];
+      else dst[j] = src[j];
+    }
   }
 }
 
 // dX[n][h][w][ch] = sum over the patches that contain the pixel (adjoint of extract_patches; gather, no atomics)
+// SC (an ARD conv layer): dXcol holds the gradient of the SCALED patches, element l of a patch counts sc[l] times
+template <bool SC>
 __global__ void col2im_kernel(const double* __restrict__ dXcol, int N, int H, int W, int C, int f, int s, int Ho, int Wo, int L,
-                              double* __restrict__ dX) {
+                              double* __restrict__ dX, const double* __restrict__ sc) {
   const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= (long)N * H * W * C) return;
   const int ch = (int)(idx % C);
@@ -297,7 +304,9 @@ __global__ void col2im_kernel(const double* __restrict__ dXcol, int N, int H, in
       if (ww < 0 || ww % s) continue;
       const int ow = ww / s;
       if (ow >= Wo) continue;
-      acc += dXcol[((long)n * P + oh * Wo + ow) * L + (kh * f + kw) * C + ch];
+      const double g = dXcol[((long)n * P + oh * Wo + ow) * L + (kh * f + kw) * C + ch];
+      if constexpr (SC) acc = fma(g, sc[(kh * f + kw) * C + ch], acc);
+      else acc += g;
     }
   }
   dX[idx] = acc;
@@ -616,6 +625,49 @@ __global__ __launch_bounds__(256) void ard_finish_kernel(const double* __restric
   if (t == 0) gard[d] = -sd * r;
 }
 
+// ---- ARD conv layer: RBF(f f C, ARD=True) on the patches ------------------------------------------------------------
+// part[c][d] = sum over the rows r of chunk c of dXs[r][d] Xs[r][d]: the patches' share of the lengthscale gradient, in a fixed order.
+// 256 / D rows in flight per pass (D <= 256), one otherwise.
+__global__ __launch_bounds__(256) void ard_xsum_kernel(const double* __restrict__ dXs, const double* __restrict__ Xs, long rows, int D, long rpc,
+                                                       double* __restrict__ part) {
+  __shared__ double red[256];
+  const int t = threadIdx.x, Dq = D < 256 ? D : 256, per = 256 / Dq, rr = t / Dq, dd = t - rr * Dq;
+  const long r0 = (long)blockIdx.x * rpc, r1 = r0 + rpc < rows ? r0 + rpc : rows;
+  for (int d0 = 0; d0 < D; d0 += Dq) {
+    const int d = d0 + dd;
+    double acc = 0.0;
+    if (rr < per && d < D)
+      for (long r = r0 + rr; r < r1; r += per) acc = fma(dXs[r * D + d], Xs[r * D + d], acc);
+    red[t] = acc;
+    __syncthreads();
+    if (rr == 0 && d < D) {
+      double sum = 0.0;
+      for (int q = 0; q < per; ++q) sum += red[q * Dq + dd];
+      part[(long)blockIdx.x * D + d] = sum;
+    }
+    __syncthreads();
+  }
+}
+// The chain rule back through x o s, z o s (s = 1 / lengthscales), one block per patch element d: gZ[m][d] = dZs[m][d] s_d and
+// gard[d] = -s_d (sum_m dZs Zs + sum_m dZ0s Z0s [the frozen prior's Gram matrix, unwhitened layers] + sum_c xpart[c][d])
+__global__ __launch_bounds__(256) void ard_conv_finish_kernel(const double* __restrict__ dZs, const double* __restrict__ Zs, const double* __restrict__ dZ0s,
+                                                              const double* __restrict__ Z0s, int M, int D, const double* __restrict__ xpart, int chunks,
+                                                              const double* __restrict__ s, double* __restrict__ gZ, double* __restrict__ gard) {
+  __shared__ double red[256];
+  const int d = blockIdx.x, t = threadIdx.x;
+  const double sd = s[d];
+  double acc = 0.0;
+  for (int m = t; m < M; m += 256) {
+    const double g = dZs[(long)m * D + d];
+    acc = fma(g, Zs[(long)m * D + d], acc);
+    gZ[(long)m * D + d] = g * sd;
+    if (dZ0s) acc = fma(dZ0s[(long)m * D + d], Z0s[(long)m * D + d], acc);
+  }
+  for (int c = t; c < chunks; c += 256) acc += xpart[(long)c * D + d];
+  const double r = block_sum_256(acc, red);
+  if (t == 0) gard[d] = -sd * r;
+}
+
 // ---- host helpers ------------------------------------------------------------------------------------------------
 struct Bk {   // per-backward bookkeeping
   dcgp_model* m;
@@ -703,11 +755,12 @@ int flush_scalars(Bk& bk) {
   return DCGP_OK;
 }
 
-int im2col(dcgp_ctx* ctx, const LayerState& L, const double* Xin, int n_mod, long Kc, double* Xcol) {
+// sc: nullptr, or [L] factors of the patch elements (an ARD conv layer's 1 / lengthscales)
+int im2col(dcgp_ctx* ctx, const LayerState& L, const double* Xin, int n_mod, long Kc, double* Xcol, const double* sc = nullptr) {
   const long rows = Kc / L.v.P;
   if (rows * L.v.Ho > 0x7fffffffL) return ctx_fail(ctx, DCGP_ERR_ARG, "grad: too many patch rows");
-  hipLaunchKernelGGL(im2col_kernel, dim3((unsigned)(rows * L.v.Ho)), dim3(256), 0, ctx->stream, Xin, n_mod, L.v.H, L.v.W, L.v.C, L.v.f, L.v.s,
-                     L.v.Ho, L.v.Wo, L.v.L, Xcol);
+  hipLaunchKernelGGL(sc ? im2col_kernel<true> : im2col_kernel<false>, dim3((unsigned)(rows * L.v.Ho)), dim3(256), 0, ctx->stream, Xin, n_mod, L.v.H, L.v.W,
+                     L.v.C, L.v.f, L.v.s, L.v.Ho, L.v.Wo, L.v.L, Xcol, sc);
   LAUNCH_CHECK(ctx);
   return DCGP_OK;
 }
@@ -871,7 +924,19 @@ int kl_products(Bk& bk, LayerState& L, double* Sacc, bool s_first) {
   GenGemm g5 = mk(KiL, Rm, 1, KiL, 1, Rm, Sk, Mp, M, M, (int)Rm);     // all r at once, stacked along k
   g5.alpha = 0.5 * kw; g5.accumulate = 1;
   DCGP_TRY(gemm_gen(ctx, g5));
-  if (!Sacc) DCGP_TRY(kuu_backward(bk, L, L.Z0, Sk, Mp, false, nullptr, "klz", true));   // frozen Z0: hyper-parameters only
+  if (!Sacc && L.in_scale) {
+    // ARD conv layer: K_p(Z0) is the Gram matrix of Z0 o s, so it depends on the lengthscales although Z0 is frozen -- the adjoint with respect to
+    // the scaled rows stays in scratch (conv_layer_ard_finish turns it into the prior's share of gard; nothing of it goes to gZ)
+    double* Z0s = bk.ws("klz_Zs", (size_t)M * L.v.L);
+    double* dZ0s = bk.ws("klz_dZs", (size_t)M * L.v.L);
+    NEED(Z0s); NEED(dZ0s);
+    hipLaunchKernelGGL(scale_rows_kernel, dim3(blocks_for((long)M * L.v.L)), dim3(256), 0, ctx->stream, L.Z0, M, (long)M, L.v.L, L.in_scale, Z0s);
+    LAUNCH_CHECK(ctx);
+    HIP_TRY(ctx, hipMemsetAsync(dZ0s, 0, (size_t)M * L.v.L * sizeof(double), ctx->stream));
+    DCGP_TRY(kuu_backward(bk, L, Z0s, Sk, Mp, true, dZ0s, "klz", true));
+  } else if (!Sacc) {
+    DCGP_TRY(kuu_backward(bk, L, L.Z0, Sk, Mp, false, nullptr, "klz", true));   // frozen Z0: hyper-parameters only
+  }
   return DCGP_OK;
 }
 int kl_apply(Bk& bk, LayerState& L, bool frozen_prior) {
@@ -1205,7 +1270,7 @@ int layer_fills(Bk& bk, LayerState& L) {
     return DCGP_OK;
   }
   HIP_TRY(bk.ctx, hipMemsetAsync(L.gZ, 0, (size_t)L.M * L.v.L * sizeof(double), bk.ctx->stream));
-  HIP_TRY(bk.ctx, hipMemsetAsync(L.gw, 0, ((size_t)L.v.P + 3 + (L.is_head ? (size_t)L.v.L : 0) + L.lik_slots + L.mean_slots() + L.mix_slots()) * sizeof(double), bk.ctx->stream));   // gw, gscal, gard, glik, gmean_W, gmix_W
+  HIP_TRY(bk.ctx, hipMemsetAsync(L.gw, 0, ((size_t)L.v.P + 3 + L.ard_slots() + L.lik_slots + L.mean_slots() + L.mix_slots()) * sizeof(double), bk.ctx->stream));   // gw, gscal, gard, glik, gmean_W, gmix_W
   if (!L.has_qsqrt) HIP_TRY(bk.ctx, hipMemsetAsync(L.gq_sqrt, 0, (size_t)L.R * L.M * L.M * sizeof(double), bk.ctx->stream));
   return DCGP_OK;
 }
@@ -1221,6 +1286,14 @@ int end_layer(Bk& bk, LayerState& L) {
   hipLaunchKernelGGL(scal_finish_kernel, dim3(1), dim3(64), 0, bk.ctx->stream, L.gslots, L.gscal);
   LAUNCH_CHECK(bk.ctx);
   return DCGP_OK;
+}
+
+// row chunks of ard_xsum_kernel on Kc patch rows: a few hundred blocks of 256 rows or more
+struct ArdChunks { int chunks; long rpc; };
+ArdChunks ard_chunks(long Kc) {
+  const long chunks = std::max<long>(1, std::min<long>(512, (Kc + 255) / 256));
+  const long rpc = (Kc + chunks - 1) / chunks;
+  return {(int)((Kc + rpc - 1) / rpc), rpc};
 }
 
 // What is left of a layer, on the tail stream.  Behind the conditional's own dq_mu / dq_sqrt (ev_g[1], ev_g[4]): the KL pieces.  Behind
@@ -1242,8 +1315,27 @@ int layer_tail(Bk& bk, const Lanes& ln, LayerState& L, const double* S, const do
     DCGP_TRY(kl_products(bk, L, const_cast<double*>(S), false));
     DCGP_TRY(kl_apply(bk, L, frozen_prior));
   }
-  DCGP_TRY(kuu_backward(bk, L, L.Z, S, L.Mp, true, nullptr, "kuu", false, ln.forked ? ctx->ev_g[3] : nullptr));
-  DCGP_TRY(end_layer(bk, L));
+  if (L.in_scale && !L.is_head) {
+    // ARD conv layer (conv_backward): the Gram adjoint on the scaled rows, then the chain rule through the scaling.  Everything it reads is there:
+    // the patch adjoint's dZs and the patches' sums behind ev_g[3] (waited for inside kuu_backward), the prior's share behind kl_apply
+    const size_t nz = (size_t)L.M * L.v.L;
+    double *Zs = bk.ws("Zs", nz), *dZs = bk.ws("dZs", nz);
+    NEED(Zs); NEED(dZs);
+    DCGP_TRY(kuu_backward(bk, L, Zs, S, L.Mp, true, dZs, "kuu", false, ln.forked ? ctx->ev_g[3] : nullptr));
+    const bool prior = !L.white;
+    const ArdChunks ac = ard_chunks(n_kd);
+    double* xpart = bk.ws("ard_xpart", (size_t)ac.chunks * L.v.L);
+    NEED(xpart);
+    hipLaunchKernelGGL(ard_conv_finish_kernel, dim3(L.v.L), dim3(256), 0, ctx->stream, dZs, Zs, prior ? bk.ws("klz_dZs", nz) : nullptr,
+                       prior ? bk.ws("klz_Zs", nz) : nullptr, L.M, L.v.L, xpart, ac.chunks, L.in_scale, L.gZ, L.gard);
+    LAUNCH_CHECK(ctx);
+    DCGP_TRY(end_layer(bk, L));
+    // the scalar "lengthscale" slot collected d / d(unit lengthscale): meaningless here, and L.ls must stay 1 (as for the dense head)
+    HIP_TRY(ctx, hipMemsetAsync(L.gscal + 1, 0, sizeof(double), ctx->stream));
+  } else {
+    DCGP_TRY(kuu_backward(bk, L, L.Z, S, L.Mp, true, nullptr, "kuu", false, ln.forked ? ctx->ev_g[3] : nullptr));
+    DCGP_TRY(end_layer(bk, L));
+  }
   if (ln.forked) {
     HIP_TRY(ctx, hipEventRecord(ctx->ev_kl, ctx->stream));
     bk.side_pending = true;
@@ -1252,12 +1344,13 @@ int layer_tail(Bk& bk, const Lanes& ln, LayerState& L, const double* S, const do
 }
 
 // dXin [rows, H, W, C] from E and cs in one launch (fuse_dx: input_grad.hip, `extra` as there) or from the patch gradients dXcol by col2im's gather
+// sc: nullptr, or [L]: dXcol is the gradient of the patches times sc (an ARD conv layer; not with fuse_dx)
 int patches_to_dx(Bk& bk, LayerState& L, bool fuse_dx, const double* E, long ld, const double* cs, const double* Xin, int rows, int n_mod,
-                  const double* extra, const double* dXcol, double* dXin) {
-  if (fuse_dx) return patch_adjoint_fused(bk.ctx, L, E, ld, cs, Xin, rows, n_mod, extra, dXin);
+                  const double* extra, const double* dXcol, double* dXin, const double* sc = nullptr) {
+  if (fuse_dx) return sc ? ctx_fail(bk.ctx, DCGP_ERR_ARG, "grad: the one-launch patch adjoint takes no patch scale") : patch_adjoint_fused(bk.ctx, L, E, ld, cs, Xin, rows, n_mod, extra, dXin);
   const long n = (long)rows * L.v.H * L.v.W * L.v.C;
-  hipLaunchKernelGGL(col2im_kernel, dim3(blocks_for(n)), dim3(256), 0, bk.ctx->stream, dXcol, rows, L.v.H, L.v.W, L.v.C, L.v.f, L.v.s, L.v.Ho,
-                     L.v.Wo, L.v.L, dXin);
+  hipLaunchKernelGGL(sc ? col2im_kernel<true> : col2im_kernel<false>, dim3(blocks_for(n)), dim3(256), 0, bk.ctx->stream, dXcol, rows, L.v.H, L.v.W, L.v.C,
+                     L.v.f, L.v.s, L.v.Ho, L.v.Wo, L.v.L, dXin, sc);
   LAUNCH_CHECK(bk.ctx);
   return DCGP_OK;
 }
@@ -1293,19 +1386,41 @@ int conv_backward(Bk& bk, LayerState& L, const double* Xin, int rows, int n_mod,
   double* cs = bk.ws("cs", Kc);
   double* Xcol = bk.ws("Xcol", (size_t)Kc * Ld);
   NEED(dKuf); NEED(E); NEED(S); NEED(gvs); NEED(cs); NEED(Xcol);
+  // ARD (per-dimension lengthscales, L.in_scale; L.ls == 1): dense_head_backward's scheme on the patches.  The unit-lengthscale adjoints below run on
+  // the scaled copies Xcol o s (im2col scales while it gathers) and Zs = Z o s and leave dZs / dXs; col2im applies s to dXs on its way to dX, and
+  // layer_tail ends with gZ = s o dZs and gard_l = -s_l (sum_m dZs Zs + sum_k dXs Xs + the frozen prior's share).  dXs is formed on the first layer
+  // too, where no dX is wanted: the lengthscale gradient needs it.
+  const double* sc = L.in_scale;
+  double *Zs = nullptr, *dZs = nullptr;
+  if (sc) {
+    Zs = bk.ws("Zs", (size_t)L.M * Ld); NEED(Zs);
+    hipLaunchKernelGGL(scale_rows_kernel, dim3(blocks_for((long)L.M * Ld)), dim3(256), 0, ctx->stream, L.Z, L.M, (long)L.M, Ld, sc, Zs);   // (ahead of ev_g[1]: the tail stream reads it)
+    LAUNCH_CHECK(ctx);
+    if (!bk.data_only) {
+      dZs = bk.ws("dZs", (size_t)L.M * Ld); NEED(dZs);
+      HIP_TRY(ctx, hipMemsetAsync(dZs, 0, (size_t)L.M * Ld * sizeof(double), ctx->stream));
+    }
+  }
   // main stream: the column-wise adjoint of the conditional, then the patch-kernel adjoint -> dX.  The M x M chain behind the conditional
   // runs beside them on the chain stream, what needs its result on the tail stream (Lanes).
   DCGP_TRY(cond_backward_main(bk, ln, L, A1, ld, Kc, gm, gv, dKuf, gvs, bk.last_layer && ln.forked));
   // the input gradient's pass: dX in one launch from E and cs where the shape is covered (input_grad.hip) -- no Xcol, no dXcol, no col2im
   const bool fuse_dx = bk.data_only && dXin && patch_adjoint_fused_ok(L, rows);
-  if (!fuse_dx) DCGP_TRY(im2col(ctx, L, Xin, n_mod, Kc, Xcol));
+  if (!fuse_dx) DCGP_TRY(im2col(ctx, L, Xin, n_mod, Kc, Xcol, sc));
   double* dXcol = nullptr;
-  if (dXin && !fuse_dx) { dXcol = bk.ws("dXcol", (size_t)Kc * Ld); NEED(dXcol); }
+  if ((dXin && !fuse_dx) || (sc && !bk.data_only)) { dXcol = bk.ws("dXcol", (size_t)Kc * Ld); NEED(dXcol); }
   KufAdjoint ka;
   DCGP_TRY(kuf_adjoint(bk, L, dKuf, ld, 1, nullptr, 1.0, Kuf, ld, Xcol, Kc, E, ld, cs, nullptr, &ka));
-  DCGP_TRY(patch_backward(bk, L, E, ld, Kc, cs, Xcol, dXcol, 0, nullptr, nullptr, ka.rs, ka.cz));
+  DCGP_TRY(patch_backward(bk, L, E, ld, Kc, cs, Xcol, dXcol, 0, Zs, dZs, ka.rs, ka.cz));
+  if (sc && !bk.data_only) {   // the patches' share of the lengthscale gradient, before dXs is consumed
+    const ArdChunks ac = ard_chunks(Kc);
+    double* xpart = bk.ws("ard_xpart", (size_t)ac.chunks * Ld);
+    NEED(xpart);
+    hipLaunchKernelGGL(ard_xsum_kernel, dim3(ac.chunks), dim3(256), 0, ctx->stream, dXcol, Xcol, Kc, Ld, ac.rpc, xpart);
+    LAUNCH_CHECK(ctx);
+  }
   if (dXin) {
-    DCGP_TRY(patches_to_dx(bk, L, fuse_dx, E, ld, cs, Xin, rows, n_mod, nullptr, dXcol, dXin));
+    DCGP_TRY(patches_to_dx(bk, L, fuse_dx, E, ld, cs, Xin, rows, n_mod, nullptr, dXcol, dXin, sc));
     if (L.identity_mean) {
       hipLaunchKernelGGL(idmean_backward_kernel, dim3(blocks_for(Kc)), dim3(256), 0, ctx->stream, gmf, Kc, L.R, P, L.v.Wo, L.v.H, L.v.W, L.v.C,
                          L.v.f, L.v.s, dXin);
@@ -1315,7 +1430,16 @@ int conv_backward(Bk& bk, LayerState& L, const double* Xin, int rows, int n_mod,
   }
   if (bk.data_only) return DCGP_OK;
   // the filter's own gradient from the patches the pass holds (a frozen filter keeps the zero of the block's fill)
-  if (L.mean_W && L.mean_trainable) DCGP_TRY(conv_mean_backward_filter(ctx, L, Xcol, gmf, Kc, L.gmean_W));
+  if (L.mean_W && L.mean_trainable) {
+    const double* Xraw = Xcol;
+    if (sc) {   // the filter sees the patches themselves, not patches o s
+      double* xr = bk.ws("Xraw", (size_t)Kc * Ld);
+      NEED(xr);
+      DCGP_TRY(im2col(ctx, L, Xin, n_mod, Kc, xr));
+      Xraw = xr;
+    }
+    DCGP_TRY(conv_mean_backward_filter(ctx, L, Xraw, gmf, Kc, L.gmean_W));
+  }
   // The main stream's part of this layer ends here (dX is out): it goes straight on to the layer below.
   if (ln.forked) HIP_TRY(ctx, hipEventRecord(ctx->ev_g[3], ctx->stream));
   DCGP_TRY(cond_backward_finish(bk, ln, L, A1, ld, Kc, dKuf, S, false, bk.last_layer && ln.forked));

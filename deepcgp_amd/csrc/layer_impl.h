@@ -47,7 +47,7 @@ struct LayerState {
   bool has_qsqrt = true;
   // parameters in the caller's layout (device)
   double *Z = nullptr, *Z0 = nullptr, *q_mu = nullptr, *q_sqrt = nullptr, *w = nullptr;
-  double* in_scale = nullptr;   // [L] 1 / ARD lengthscale per input dimension, or nullptr (set_param "ard_lengthscales"; single-patch head only)
+  double* in_scale = nullptr;   // [L] 1 / ARD lengthscale per input dimension, or nullptr (set_param "ard_lengthscales"; the single-patch head or a conv layer)
   double* ard = nullptr;        // [L] the ARD lengthscales themselves (optimiser state; in_scale is refreshed from it)
   double *gard = nullptr, *aard[2] = {};   // their gradient (inside the gradient block) and Adam moments
   // derived every step.  Two banks of them: a step's parameter-only chain writes the bank of its parity, so that the chain of
@@ -166,17 +166,19 @@ struct LayerState {
   // head of a Gaussian-likelihood model: one more slot at the very end of the block, d ELBO / d likelihood variance (glik)
   int lik_slots = 0;
   double* glik = nullptr;
-  size_t grad_block_count() const { return (size_t)M * v.L + (size_t)M * R + (size_t)R * M * M + (size_t)v.P + 3 + (is_head ? (size_t)v.L : 0) + (size_t)lik_slots + mean_slots() + mix_slots(); }
+  // [L] d / d ARD lengthscales behind gscal: every head keeps the room (the dense head uses it), a conv layer once it has the lengthscales
+  size_t ard_slots() const { return (is_head || ard) ? (size_t)v.L : 0; }
+  size_t grad_block_count() const { return (size_t)M * v.L + (size_t)M * R + (size_t)R * M * M + (size_t)v.P + 3 + ard_slots() + (size_t)lik_slots + mean_slots() + mix_slots(); }
   int ensure_grads() {
     if (gZ) return DCGP_OK;
     double* blk = dalloc(grad_block_count() + kGradBlockPad);   // (padding: the sharded exchange rounds the block up to ranks x shard)
     gslots = dalloc(48);
     if (!blk || !gslots) return ctx_fail(ctx, DCGP_ERR_ALLOC, "layer: gradient allocation failed");
     gZ = blk; gq_mu = gZ + (size_t)M * v.L; gq_sqrt = gq_mu + (size_t)M * R; gw = gq_sqrt + (size_t)R * M * M; gscal = gw + v.P;
-    gard = is_head ? gscal + 3 : nullptr;   // [L] d / d ARD lengthscales (dense head), zero otherwise
-    glik = lik_slots ? gscal + 3 + (is_head ? v.L : 0) : nullptr;
-    gmean_W = mean_W ? gscal + 3 + (is_head ? v.L : 0) + lik_slots : nullptr;
-    gmix_W = mix_W ? gscal + 3 + (is_head ? v.L : 0) + lik_slots + mean_slots() : nullptr;
+    gard = ard_slots() ? gscal + 3 : nullptr;   // [L] d / d ARD lengthscales (dense head, ARD conv layer), zero otherwise
+    glik = lik_slots ? gscal + 3 + ard_slots() : nullptr;
+    gmean_W = mean_W ? gscal + 3 + ard_slots() + lik_slots : nullptr;
+    gmix_W = mix_W ? gscal + 3 + ard_slots() + lik_slots + mean_slots() : nullptr;
     return DCGP_OK;
   }
   int ensure_adam() {
@@ -227,6 +229,11 @@ struct LayerState {
   }
   // step 1 of the forward: everything that depends only on this layer's parameters
   int prepare(double jitter) {
+    if (in_scale) {   // ARD: the Gram matrices, Z^T and |z|^2 of the scaled rows come from the one-launch preparation's SC forms (prep.hip)
+      PrepArgs pa;
+      pa.nl = 1; pa.l[0] = prep_args(jitter);
+      return prepare_all(ctx, pa, 0x3fu);
+    }
     DCGP_TRY(rbf_gram_padded(ctx, Z, M, v.L, base(), jitter, g.K, Mp, Mp));
     if (g.Kp) DCGP_TRY(rbf_gram_padded(ctx, Z0, M, v.L, base(), jitter, g.Kp, Mp, Mp));
     DCGP_TRY(z_transpose_norms(ctx, Z, M, v.L, ZT, Mp, Lp, zn));
@@ -314,6 +321,10 @@ static inline ConvFusedArgs conv_fused_shape(const LayerState& L, long rows) {
   fa.ZS = L.ZS; fa.Lz = L.Lz; fa.csq = sqrt(1.4426950408889634074) / L.ls;
   fa.LinvT = L.g.LinvT; fa.G = L.has_qsqrt ? L.g.G : nullptr; fa.alpha = L.g.alpha; fa.R = L.R; fa.Rp = L.g.Rp;
   fa.Kc = (int)std::min<long>(rows * L.v.P, 0x7fffffffL); fa.knn = L.variance; fa.idm = L.identity_mean;
+  // Per-dimension lengthscales (L.in_scale on a conv layer): the one-launch kernel has no instance that scales the gathered patch, so the query
+  // describes a layer without patches -- plan_layer_launch refuses P <= 0, and with it conv_fused_ok and conv_fused_rides_head -- and the layer takes
+  // the sweep + GEMM route at every M.  The plan (plan_step) and the dispatch (conv_forward) both ask through here.
+  if (L.in_scale) fa.P = 0;
   return fa;
 }
 // Whether a model's first layer on `rows` images is ONE launch behind the factorisation (nothing of it can run beside the chain) or opens with a sweep
@@ -434,9 +445,10 @@ static inline int conv_forward(dcgp_ctx* ctx, LayerState& L, const double* X, in
     a.bk = L.base();
     a.out = B; a.sM = ldc; a.sN = P; a.sP = 1;
     a.share_cu = phase == 1;
+    a.patch_scale = L.in_scale;   // ARD: the sweep's scaling instance (rbf.hip); ZT / zn are those of Z o s
     if ((phase & 1) || chunked) {
       bool done = false;
-      if (a.bk.type == 0) {   // RBF: the unit sweep in its storing form (head_units.hip)
+      if (a.bk.type == 0 && !L.in_scale) {   // RBF: the unit sweep in its storing form (head_units.hip)
         HeadUnitsArgs h;
         h.X = X; h.n_mod = n_mod; h.N = nr; h.n0 = r0;
         h.H = L.v.H; h.W = L.v.W; h.C = L.v.C; h.f = L.v.f; h.s = L.v.s; h.Wo = L.v.Wo; h.P = P; h.L = L.v.L; h.Lq = L.Lz;

@@ -735,8 +735,15 @@ int dcgp_model_set_param(dcgp_model* model, int layer, const char* which, const 
   if (!strcmp(which, "ard_lengthscales")) {
     // gpflow RBF(D, ARD=True) on the flattened features (--last-kernel rbf, conv_gp/models.py:160-168): a head whose
     // single patch is the whole input (P == 1); x / l and Z / l are formed while the operands are staged
-    if (!L.is_head || L.v.P != 1) return ctx_fail(ctx, DCGP_ERR_ARG, "set_param(ard_lengthscales): only a single-patch head takes per-dimension lengthscales");
+    // A conv layer (gpflow RBF(f f C, ARD=True) as its base kernel): one lengthscale per patch element; the patch sweep scales the gathered patch
+    // (rbf.hip: patch_rbf_body ARD), the preparation scales Z for both Gram matrices, Z^T and |z|^2 (prep.hip: the SC forms).
+    if (L.is_head && L.v.P != 1) return ctx_fail(ctx, DCGP_ERR_ARG, "set_param(ard_lengthscales): only a single-patch head takes per-dimension lengthscales");
+    if (!L.is_head && L.base_type != 0)
+      return ctx_fail(ctx, DCGP_ERR_ARG, "set_param(ard_lengthscales): layer %d: only the RBF base kernel takes per-dimension lengthscales", layer);
     DCGP_TRY(expect((size_t)L.v.L));
+    // the lengthscales' gradient lies inside the layer's gradient block, whose layout is fixed by the first reverse pass or sharded step
+    if (!L.is_head && !L.ard && (L.gZ || L.pstage || L.hyp))
+      return ctx_fail(ctx, DCGP_ERR_ARG, "set_param(ard_lengthscales): layer %d: set the lengthscales before the model's first training step", layer);
     std::vector<double> inv(count);
     for (size_t i = 0; i < count; ++i) {
       if (!(value_host[i] > 0)) return ctx_fail(ctx, DCGP_ERR_ARG, "lengthscales must be > 0");

@@ -231,6 +231,46 @@ static int kuf_impl(dcgp_ctx* ctx, const double* X, int N, int H, int W, int C, 
   return DCGP_OK;
 }
 
+// gpflow RBF(f f C, ARD=True) on the patches: the sweep's scaling instance (rbf.hip) on Z^T and |z|^2 of Z o s (prep.hip, task 2 in its SC form)
+int dcgp_kuf_patches_rbf_ard(dcgp_ctx* ctx, const double* X, int N, int H, int W, int C, int f, int stride, const double* Z, int M, double variance,
+                             const double* lengthscales, double* out, int layout) {
+  ARG_CHECK(ctx && X && Z && out && lengthscales && N > 0 && M > 0 && f > 0 && stride > 0 && f <= H && f <= W && C > 0 && variance > 0 &&
+                (layout == 0 || layout == 1),
+            "kuf_patches_rbf_ard: bad args");
+  ViewGeom v;
+  v.set(H, W, C, f, stride);
+  const int Mp = round_up(M, 16), Lp = round_up(v.L, 4);
+  std::vector<double> s(v.L);
+  HIP_TRY(ctx, hipMemcpyAsync(s.data(), lengthscales, (size_t)v.L * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  for (int l = 0; l < v.L; ++l) {
+    if (!(s[l] > 0)) return ctx_fail(ctx, DCGP_ERR_ARG, "kuf_patches_rbf_ard: lengthscale %d of %d is not positive", l, v.L);
+    s[l] = 1.0 / s[l];
+  }
+  double* sc = (double*)ws_get(ctx, "op_ard_s", (size_t)v.L * sizeof(double));
+  double* ZT = (double*)ws_get(ctx, "op_ZT", (size_t)Lp * Mp * sizeof(double));
+  double* zn = (double*)ws_get(ctx, "op_zn", (size_t)Mp * sizeof(double));
+  if (!sc || !ZT || !zn) return DCGP_ERR_ALLOC;
+  HIP_TRY(ctx, hipMemcpyAsync(sc, s.data(), (size_t)v.L * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  PrepArgs pa;
+  pa.nl = 1;
+  PrepLayerArgs& p = pa.l[0];
+  p.Z = Z; p.in_scale = sc; p.ZT = ZT; p.zn = zn; p.M = M; p.Mp = Mp; p.L = v.L; p.Lp = Lp;
+  DCGP_TRY(prepare_all(ctx, pa, 1u << 2));
+  PatchRbfArgs a;
+  a.X = X; a.N = N; a.n_mod = N;
+  a.H = H; a.W = W; a.C = C; a.f = f; a.s = stride; a.Ho = v.Ho; a.Wo = v.Wo; a.P = v.P; a.L = v.L;
+  a.ZT = ZT; a.zn = zn; a.M = M; a.Mp = Mp; a.Lp = Lp;
+  a.bk = rbf_bk(variance, 1.0);
+  a.patch_scale = sc;
+  a.out = out;
+  if (layout == 0) { a.sP = (long)M * N; a.sM = N; a.sN = 1; }
+  else { a.sM = (long)N * v.P; a.sN = v.P; a.sP = 1; }
+  DCGP_TRY(patch_rbf(ctx, a, "kuf_ard"));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // (s on the host outlives its upload)
+  return DCGP_OK;
+}
+
 int dcgp_potrf_lower(dcgp_ctx* ctx, double* A_MM, int M, int* info_host) {
   ARG_CHECK(ctx && A_MM && M > 0, "potrf_lower: bad args");
   if (info_host) *info_host = 0;

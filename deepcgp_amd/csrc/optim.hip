@@ -246,7 +246,8 @@ int opt_enqueue(dcgp_model* model, const char* who, bool sgd, double lr, double 
     const int ng_hyp = a.ng;
     DCGP_TRY(add(L.hyp, L.gscal, L.ahyp, 3, 1, li, nullptr, (L.frozen & 16u) != 0));
     if (a.ng > ng_hyp) a.grp[ng_hyp].hold = (int)((L.frozen >> 5) & 3u) << 1;   // bits 32 / 64: elements 1 / 2 of the triple stay where they are
-    if (L.ard) DCGP_TRY(add(L.ard, L.gard, L.aard, (long)L.v.L, 1, -1, L.in_scale, (L.frozen & 16u) != 0));   // dense head: per-dimension lengthscales and the staging scale 1 / l
+    if (a.ng > ng_hyp && L.ard && !L.is_head) a.grp[ng_hyp].hold |= 2;          // an ARD conv layer: the scalar lengthscale is the unit the vector is measured in, held at 1
+    if (L.ard) DCGP_TRY(add(L.ard, L.gard, L.aard, (long)L.v.L, 1, -1, L.in_scale, (L.frozen & (16u | 128u)) != 0));   // dense head, ARD conv layer: per-dimension lengthscales and the scale 1 / l
     if (L.mean_W) DCGP_TRY(add(L.mean_W, L.gmean_W, L.amean_W, (long)L.mean_slots(), 0, -1, nullptr, !L.mean_trainable));   // the mean filter (conv_mean.hip)
     if (L.mix_W) DCGP_TRY(add(L.mix_W, L.gmix_W, L.amix_W, (long)L.mix_slots(), 0, -1, nullptr, !L.mix_trainable));   // the mixing matrix (mix.hip), unconstrained
     if (L.glik) {   // Gaussian likelihood variance / StudentT scale: the last slot of the head's block, moments beside it on the device
@@ -401,6 +402,10 @@ int dcgp_model_set_trainable(dcgp_model* model, int layer, const char* which, in
   else if (!strcmp(which, "variance") || !strcmp(which, "lengthscale") || !strcmp(which, "hyper")) bit = 16u;
   else if (L.base_type == 1 && !strcmp(which, "weight_variances")) bit = 32u;   // one ArcCosine parameter alone (the other and the variance go on moving)
   else if (L.base_type == 1 && !strcmp(which, "bias_variance")) bit = 64u;
+  else if (!strcmp(which, "ard_lengthscales")) {   // the per-dimension lengthscales alone (the variance goes on moving; "hyper" holds both)
+    if (!L.ard) return ctx_fail(model->ctx, DCGP_ERR_ARG, "set_trainable(ard_lengthscales): layer %d has no ARD lengthscales", layer);
+    bit = 128u;
+  }
   else return ctx_fail(model->ctx, DCGP_ERR_ARG, "set_trainable: unknown parameter '%s'", which);
   if (on) L.frozen &= ~bit; else L.frozen |= bit;
   return DCGP_OK;

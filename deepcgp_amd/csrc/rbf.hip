@@ -110,13 +110,18 @@ __device__ __forceinline__ int patch_base(int p, int P, int Wo, int s, int W, in
 // into MFMA registers, PR_D sub-steps ahead -- no LDS staging, no barrier in the k loop.  (Staged through LDS in chunks of 32
 // rows it cost two barriers and one exposed memory latency per chunk: 8 chunks at the head's L = 250, ~40 us per workgroup
 // where the MFMAs need 7.)
-template <int BT>
+// ARD (a compile-time instance, chosen by patch_rbf): per-dimension lengthscales on the patches, gpflow RBF(L, ARD=True) as a conv layer's base kernel.
+// The scale s_l = 1 / lengthscale_l belongs to the patch ELEMENT l, not to the pixel (one pixel sits at different l in overlapping patches), so it
+// is applied to the gathered B operand: a table ksc [Lp] in LDS behind koff (zero on the padded rows l >= L), read with the offsets a group of
+// sub-steps ahead.  The running |x|^2 comes from the scaled operand registers; Z^T and |z|^2 arrive scaled (prep.hip, the SC forms).
+template <int BT, bool ARD = false>
 __device__ __forceinline__ void patch_rbf_body(const PatchRbfArgs& a, const int bx, const int by, const int bz) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int HWC = a.H * a.W * a.C;
   double* img = smem;                                   // [HWC] (+pad to even)
   double* red = img + ((HWC + 1) & ~1);                 // [2][PR_BM] (reduce mode)
   int* koff = reinterpret_cast<int*>(red + 3 * PR_BM);  // [Lp]  (red: [2][PR_BM] reduce scratch, then [PR_BM] |z|^2)
+  [[maybe_unused]] double* ksc = reinterpret_cast<double*>(koff + a.Lp);   // [Lp] (ARD; Lp is a multiple of 4: 16-byte aligned)
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
@@ -165,6 +170,7 @@ __device__ __forceinline__ void patch_rbf_body(const PatchRbfArgs& a, const int 
     int c = ll % a.C, t = ll / a.C;
     int kw = t % a.f, kh = t / a.f;
     koff[l] = (kh * a.W + kw) * a.C + c;
+    if constexpr (ARD) ksc[l] = l < a.L ? a.patch_scale[l] : 0.0;
   }
   // (zoff: this lane's A-operand columns: rows m0 + wm*32 + x*16 + lcol of Z (columns of Z^T); beyond Mp: re-read the last one, dropped later)
   double* znl = red + 2 * PR_BM;   // behind the reduce scratch: |z|^2 of the workgroup's 64 rows (koff follows)
@@ -201,14 +207,18 @@ __device__ __forceinline__ void patch_rbf_body(const PatchRbfArgs& a, const int 
     // dependent LDS round trips per step; with fewer than four waves on the SIMD -- the second round of a 1.5-round grid --
     // nothing covered them).  Only the last sub-step can reach k >= L, so only gathers that may be the last carry the mask.
     constexpr int G = PR_D + 1;
-    auto offs = [&](int k4, int (&ko)[G]) {
+    auto offs = [&](int k4, int (&ko)[G], [[maybe_unused]] double (&so)[ARD ? G : 1]) {
 #pragma unroll
-      for (int u = 0; u < G; ++u) ko[u] = koff[4 * min(k4 + u, nk4 - 1) + lrow];
+      for (int u = 0; u < G; ++u) {
+        ko[u] = koff[4 * min(k4 + u, nk4 - 1) + lrow];
+        if constexpr (ARD) so[u] = ksc[4 * min(k4 + u, nk4 - 1) + lrow];
+      }
     };
-    auto gather = [&](int ko, bool kin, double (&bv)[2]) {
+    auto gather = [&](int ko, [[maybe_unused]] double so, bool kin, double (&bv)[2]) {
 #pragma unroll
       for (int y = 0; y < 2; ++y) {
-        const double v = img[pb[y] + ko];
+        double v = img[pb[y] + ko];
+        if constexpr (ARD) v *= so;   // (so is 0 on a padded row: such a row adds exactly zero to the product and to the norm)
         bv[y] = kin ? v : 0.0;
       }
     };
@@ -227,30 +237,36 @@ __device__ __forceinline__ void patch_rbf_body(const PatchRbfArgs& a, const int 
     primed = false;
     const bool last_in = 4 * (nk4 - 1) + lrow < a.L;
     int kc[G], kn[G];
+    double sc[ARD ? G : 1] = {}, sn[ARD ? G : 1] = {};   // ARD: the scales of the sub-steps whose offsets kc / kn hold
+    auto at = [](const double (&so)[ARD ? G : 1], int u) { return so[ARD ? u : 0]; };
     double bc[2], bn[2];
-    offs(0, kc);
-    gather(kc[0], nk4 > 1 || last_in, bc);
+    offs(0, kc, sc);
+    gather(kc[0], at(sc, 0), nk4 > 1 || last_in, bc);
     // full groups cover sub-steps [0, T), T the largest multiple of G that leaves the last sub-step to the tail
     const int T = ((nk4 - 1) / G) * G;
     int t = 0;
     for (; t < T; t += G) {   // no conditionals around the loads
-      offs(t + G, kn);
+      offs(t + G, kn, sn);
 #pragma unroll
       for (int u = 0; u < G; ++u) {
         ldz(min(t + u + PR_D, nk4 - 1), ring[(u + PR_D) % G]);
-        if (u < PR_D) gather(kc[u + 1], true, bn);
-        else gather(kn[0], t + G < nk4 - 1 || last_in, bn);   // t + G <= T <= nk4 - 1: may be the last sub-step
+        if (u < PR_D) gather(kc[u + 1], at(sc, u + 1), true, bn);
+        else gather(kn[0], at(sn, 0), t + G < nk4 - 1 || last_in, bn);   // t + G <= T <= nk4 - 1: may be the last sub-step
         mma(ring[u], bc);
         bc[0] = bn[0]; bc[1] = bn[1];
       }
 #pragma unroll
       for (int u = 0; u < G; ++u) kc[u] = kn[u];
+      if constexpr (ARD) {
+#pragma unroll
+        for (int u = 0; u < G; ++u) sc[u] = sn[u];
+      }
     }
     ldz(min(t + PR_D, nk4 - 1), ring[PR_D]);   // the tail can be G sub-steps long; kc holds their offsets
 #pragma unroll
     for (int u = 0; u < G; ++u)
       if (t + u < nk4) {
-        if (u < PR_D && t + u + 1 < nk4) gather(kc[u + 1], t + u + 1 < nk4 - 1 || last_in, bn);
+        if (u < PR_D && t + u + 1 < nk4) gather(kc[u + 1], at(sc, u + 1), t + u + 1 < nk4 - 1 || last_in, bn);
         mma(ring[u], bc);
         bc[0] = bn[0]; bc[1] = bn[1];
       }
@@ -311,6 +327,11 @@ __device__ __forceinline__ void patch_rbf_body(const PatchRbfArgs& a, const int 
 template <int BT>
 __global__ __launch_bounds__(256, BT == 0 ? 4 : 2) void patch_rbf_kernel(PatchRbfArgs a) {   // the acos epilogue needs the registers
   patch_rbf_body<BT>(a, blockIdx.x, blockIdx.y, blockIdx.z);
+}
+// RBF with per-dimension lengthscales (patch_rbf_body: ARD).  Three waves per SIMD: the scales of two groups of sub-steps are 16 more VGPRs than the
+// scalar instance's 128 -- held to four waves it spilled 17 dwords a lane into the k loop (46080 columns of 5 x 5 x 1 patches: 61 us against 52)
+__global__ __launch_bounds__(256, 3) void patch_rbf_ard_kernel(PatchRbfArgs a) {
+  patch_rbf_body<0, true>(a, blockIdx.x, blockIdx.y, blockIdx.z);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -568,7 +589,9 @@ int patch_rbf(dcgp_ctx* ctx, const PatchRbfArgs& a, const char* timer_name) {
   if (a.n_mod <= 0) return ctx_fail(ctx, DCGP_ERR_ARG, "patch_rbf: n_mod must be positive");
   if (a.Mp % PR_BM != 0 && a.Mp % 16 != 0) return ctx_fail(ctx, DCGP_ERR_ARG, "patch_rbf: Mp must be a multiple of 16");
   const int HWC = a.H * a.W * a.C;
-  size_t lds = (size_t)(((HWC + 1) & ~1) + 3 * PR_BM) * sizeof(double) + (size_t)a.Lp * sizeof(int);
+  if (a.patch_scale && (a.bk.type != 0 || a.in_scale || (a.Lp & 3)))
+    return ctx_fail(ctx, DCGP_ERR_ARG, "patch_rbf: per-dimension lengthscales go with the RBF kernel, Lp a multiple of 4 and no image scale");
+  size_t lds = (size_t)(((HWC + 1) & ~1) + 3 * PR_BM) * sizeof(double) + (size_t)a.Lp * sizeof(int) + (a.patch_scale ? (size_t)a.Lp * sizeof(double) : 0);
   if ((long)a.Lp * a.Mp * 8 >= (1L << 31)) return ctx_fail(ctx, DCGP_ERR_ARG, "patch_rbf: Z^T exceeds 2 GiB");
   if (lds > 160 * 1024) return ctx_fail(ctx, DCGP_ERR_ARG, "patch_rbf: image of %d doubles does not fit LDS", HWC);
   // A sweep that overlaps the factorisation chain would otherwise starve it: its thousands of short 128-VGPR
@@ -581,7 +604,8 @@ int patch_rbf(dcgp_ctx* ctx, const PatchRbfArgs& a, const char* timer_name) {
   const int p_tiles = (a.P + PR_BP - 1) / PR_BP;
   dim3 grid(a.reduce ? 1 : p_tiles, (a.Mp + PR_BM - 1) / PR_BM, a.N);
   ScopedTimer t(ctx, timer_name);
-  if (a.bk.type == 0) hipLaunchKernelGGL(patch_rbf_kernel<0>, grid, dim3(256), lds, ctx->stream, a);
+  if (a.patch_scale) hipLaunchKernelGGL(patch_rbf_ard_kernel, grid, dim3(256), lds, ctx->stream, a);
+  else if (a.bk.type == 0) hipLaunchKernelGGL(patch_rbf_kernel<0>, grid, dim3(256), lds, ctx->stream, a);
   else if (a.bk.type == 1) hipLaunchKernelGGL(patch_rbf_kernel<1>, grid, dim3(256), lds, ctx->stream, a);
   else if (a.bk.type == 2) hipLaunchKernelGGL(patch_rbf_kernel<2>, grid, dim3(256), lds, ctx->stream, a);
   else if (a.bk.type == 3) hipLaunchKernelGGL(patch_rbf_kernel<3>, grid, dim3(256), lds, ctx->stream, a);

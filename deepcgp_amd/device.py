@@ -64,6 +64,7 @@ _SIGS = {
     "dcgp_extract_patches": [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i],
     "dcgp_kuu_rbf": [_vp, _vp, _i, _i, _d, _d, _d, _vp],
     "dcgp_kuf_patches_rbf": [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _d, _d, _vp, _i],
+    "dcgp_kuf_patches_rbf_ard": [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _d, _vp, _vp, _i],
     "dcgp_kuu_acos": [_vp, _vp, _i, _i, _d, _d, _d, _d, _vp],
     "dcgp_kuf_patches_acos": [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _d, _d, _d, _vp, _i],
     "dcgp_kuu_matern": [_vp, _vp, _i, _i, _i, _d, _d, _d, _vp],

@@ -178,7 +178,7 @@ class DGP_Base:
             ctx._check(L.dcgp_model_add_conv_layer(
                 self._model, Hp, Wp, l.feature_maps_in, v.filter_size, v.stride,
                 l.num_inducing, l.gp_count, int(l.white), int(l.identity_mean), l.base_kernel.variance,
-                getattr(l.base_kernel, "lengthscales", 1.0), *[a.ctypes.data for a in keep]))
+                1.0 if getattr(l.base_kernel, "ARD", False) else getattr(l.base_kernel, "lengthscales", 1.0), *[a.ctypes.data for a in keep]))
             if l.mixing is not None:           # G = gp_count latent GPs into R maps (csrc/mix.hip); ahead of the mean filter, which has R columns
                 W = self._mixing_host(l)
                 ctx._check(L.dcgp_model_set_mixing(self._model, li, W.ctypes.data, W.shape[0], W.shape[1]))
@@ -194,6 +194,9 @@ class DGP_Base:
             if desc[0] != 0.0:   # not the RBF the constructor call describes (ArcCosine, conv_gp/models.py:118-119)
                 ctx._check(L.dcgp_model_set_param(self._model, li, b"base_kernel",
                                                   desc.ctypes.data, desc.size))
+            if getattr(l.base_kernel, "ARD", False):     # RBF(f f C, ARD=True): one lengthscale per patch element (csrc/rbf.hip: the sweep's ARD instance)
+                ls = np.ascontiguousarray(l.base_kernel.lengthscales, np.float64)
+                ctx._check(L.dcgp_model_set_param(self._model, li, b"ard_lengthscales", ls.ctypes.data, ls.size))
         h_ = self.layers[-1]
         if hasattr(h_.kern, "base_kernel"):      # ConvKernel / AdditivePatchKernel head (--last-kernel conv | add)
             v = h_.kern.view
@@ -434,9 +437,10 @@ class DGP_Base:
             shapes = {"Z": (M, np.shape(l.feature.Z)[1]), "q_mu": (M, R), "q_sqrt": (R, M, M), "variance": (), "lengthscale": ()}
             if head and hasattr(l.kern, "patch_weights"):
                 shapes["w"] = (np.size(l.kern.patch_weights),)
-            if head and getattr(l.kern, "ARD", False):       # dense RBF(ARD) head: one lengthscale per input dimension
+            ard = l.kern if head else l.base_kernel
+            if getattr(ard, "ARD", False):       # dense RBF(ARD) head, ARD conv layer: one lengthscale per input dimension / patch element
                 del shapes["lengthscale"]
-                shapes["ard_lengthscales"] = (np.size(l.kern.lengthscales),)
+                shapes["ard_lengthscales"] = (np.size(ard.lengthscales),)
             if not head and not hasattr(l.base_kernel, "lengthscales"):   # ArcCosine(order 0) base kernel
                 del shapes["lengthscale"]
                 shapes["weight_variances"], shapes["bias_variance"] = (), ()
@@ -756,8 +760,9 @@ class DGP_Base:
             if head:      # (a dense head keeps its single weight's slot)
                 out.append((base + "w", li, "w", (int(np.size(l.kern.patch_weights)) if hasattr(l.kern, "patch_weights") else 1,)))
             out.append((base + "hyper", li, "hyper", (3,)))
-            if head and getattr(l.kern, "ARD", False):
-                out.append((base + "ard_lengthscales", li, "ard_lengthscales", (int(np.size(l.kern.lengthscales)),)))
+            ard = l.kern if head else l.base_kernel
+            if getattr(ard, "ARD", False):
+                out.append((base + "ard_lengthscales", li, "ard_lengthscales", (int(np.size(ard.lengthscales)),)))
             if not head and l.filter_mean is not None:
                 out.append((base + "mean_filter", li, "mean_filter", np.shape(l.filter_mean.conv_filter)))
             if not head and l.mixing is not None:
@@ -846,7 +851,8 @@ class DGP_Base:
 
     def set_trainable(self, layer, which, on):
         """param.set_trainable(on) for the device optimiser steps: which in Z, q_mu, q_sqrt, w, hyper (every kernel parameter of the layer);
-        weight_variances, bias_variance (that one parameter of an ArcCosine conv layer); "likelihood_variance" (Gaussian likelihood,
+        weight_variances, bias_variance (that one parameter of an ArcCosine conv layer); ard_lengthscales (the per-dimension lengthscales of
+        an ARD layer alone, its variance goes on moving); "likelihood_variance" (Gaussian likelihood,
         ``layer`` ignored); "likelihood_scale" (StudentT likelihood, ``layer`` ignored); "mean_filter" (the filter of a conv layer's
         ``LinearConv2dMean``: frozen, its gradient is not formed either); "mixing" (a mixed conv layer's W, likewise)."""
         self._build()

@@ -15,7 +15,8 @@ class RBF:
     Scalar lengthscale: the base kernel of the conv layers / ConvKernel heads (conv_gp/models.py:114-117,178-185).
     ``ARD=True`` (one lengthscale per input dimension): the dense head of ``--last-kernel rbf`` on the flattened features
     (conv_gp/models.py:160-168), used with ``InducingPoints``; inputs are divided by the lengthscales and the unit-
-    lengthscale kernel evaluated, which is gpflow's own formulation."""
+    lengthscale kernel evaluated, which is gpflow's own formulation.  Also a conv layer's base kernel (``--ard``): one lengthscale per
+    patch element, ``input_dim = f * f * C``; not the base kernel of a patch head."""
 
     def __init__(self, input_dim, variance=1.0, lengthscales=1.0, ARD=False):
         self.input_dim = int(input_dim)
@@ -71,8 +72,12 @@ class RBF:
         return [0.0, self.variance, 1.0 if self.ARD else self.lengthscales, 0.0]
 
     def _kuf(self, ctx, dX, N, H, W, C, f, s, dZ, M, out, layout):
-        if self.ARD:
-            raise NotImplementedError("ARD lengthscales belong to the dense head (conv_gp/models.py:160-168)")
+        if self.ARD:     # one lengthscale per patch element: the sweep's scaling instance (dZ holds the unscaled Z)
+            if f * f * C != self.input_dim:
+                raise ValueError("RBF(ARD=True) with %d lengthscales on patches of length %d" % (self.input_dim, f * f * C))
+            dls = ctx.to_device(np.ascontiguousarray(self.lengthscales, np.float64))
+            ctx._check(dev.lib().dcgp_kuf_patches_rbf_ard(ctx.handle, dX.ptr, N, H, W, C, f, s, dZ.ptr, M, self.variance, dls.ptr, out.ptr, layout))
+            return
         ctx._check(dev.lib().dcgp_kuf_patches_rbf(ctx.handle, dX.ptr, N, H, W, C, f, s, dZ.ptr, M, self.variance,
                                                   self.lengthscales, out.ptr, layout))
 

@@ -367,7 +367,7 @@ class ConvLayer(Layer):
         D = self.num_latent_outputs
         if N == 0:
             return np.zeros((0, D)), np.zeros((0, D)), np.zeros((0, D))
-        if not isinstance(self.base_kernel, RBF):
+        if not isinstance(self.base_kernel, RBF) or self.base_kernel.ARD:    # (ARD: the one-call operator takes one lengthscale)
             return self._forward_composed(ND_X, z)
         Hp, Wp = v.padded_size
         dX, dZ = ctx.to_device(v.pad(ND_X.reshape(N, H, W, self.feature_maps_in))), ctx.to_device(self.feature.Z)

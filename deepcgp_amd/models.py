@@ -41,6 +41,8 @@ def build_layers_from_spec(spec):
         if kind == "acos":      # optional key acos = (variance, weight_variances, bias_variance); absent: gpflow's defaults
             av, aw, ab = c.get("acos", (1.0, 1.0, 1.0))
             base = ArcCosine(view.patch_length, order=0, variance=av, weight_variances=aw, bias_variance=ab)
+        elif kind == "rbf" and np.ndim(c["ls"]) > 0:      # ls [L]: one lengthscale per patch element (--ard)
+            base = RBF(view.patch_length, c["variance"], c["ls"], ARD=True)
         else:
             base = BASE_KERNELS[kind](view.patch_length, c["variance"], c["ls"])
         mix_W = None if c.get("mix_W") is None else np.array(c["mix_W"], np.float64)
@@ -592,6 +594,27 @@ class ModelBuilder(object):
             return "conv2d", False
         return kind, train
 
+    def ard_flag(self):
+        """--ard: every conv layer's RBF base kernel gets one lengthscale per patch element (gpflow's RBF(L, ARD=True)).  It needs
+        --base-kernel rbf: with another base kernel ValueError names both flags."""
+        ard = bool(getattr(self.flags, "ard", False))
+        if ard and self.flags.base_kernel != "rbf":
+            raise ValueError("--ard needs --base-kernel rbf, got --base-kernel %s (per-dimension lengthscales are provided for the RBF "
+                             "base kernel only)" % self.flags.base_kernel)
+        return ard
+
+    def _conv_lengthscales(self, li, have, L, ard):
+        """A conv layer's ``ls``: the checkpoint's value or the reference's initial 5.0 -- with --ard broadcast to the L patch elements; a
+        stored vector without --ard raises ValueError naming the flag."""
+        ls = np.asarray(have.get("ls", 5.0), np.float64)
+        if ard:
+            if ls.size not in (1, L):
+                raise ValueError("--ard: layer %d's checkpoint holds %d lengthscales, its patches have %d elements" % (li, ls.size, L))
+            return np.broadcast_to(ls.reshape(-1), (L,)).copy()
+        if ls.size != 1:
+            raise ValueError("layer %d's checkpoint holds %d lengthscales (a model trained with --ard): pass --ard to load it" % (li, ls.size))
+        return float(ls.reshape(()))
+
     # ---- stages -> spec ----------------------------------------------------------------------------
     def spec(self):
         fl = self.flags
@@ -608,6 +631,7 @@ class ModelBuilder(object):
         white = bool(fl.white)
         mean_kind, train_mean = self.mean_flags()
         latent = parse_latent_gps(fl, len(convs))         # --latent-gps: G per conv layer, 0 = unmixed
+        ard = self.ard_flag()                              # --ard: per-dimension lengthscales on the conv layers
         spec = {"S": int(fl.num_samples), "num_data": int(self.X_train.shape[0]), "convs": []}
         images = self.X_train                              # what the next layer is initialised on
         for li, (M, f, s, R) in enumerate(convs):
@@ -618,7 +642,7 @@ class ModelBuilder(object):
             G = latent[li] or R                                # the layer's GPs; R stays the maps it emits
             spec["convs"].append(dict(
                 H=H, W=W, C=C, f=f, s=s, M=M, R=G, Z=Z, Z0=Z, white=white, base=fl.base_kernel, pad=pads[li],
-                variance=float(have.get("variance", 5.0)), ls=float(have.get("ls", 5.0)),     # models.py:114-117
+                variance=float(have.get("variance", 5.0)), ls=self._conv_lengthscales(li, have, f * f * C, ard),     # models.py:114-117
                 q_mu=have.get("q_mu"), q_sqrt=have.get("q_sqrt"),
                 q_sqrt_scale=None if "q_sqrt" in have else 1e-5,                               # start with low variance (models.py:136-138)
                 mean_function="conv2d" if mean_kind == "conv2d" else None))

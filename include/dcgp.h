@@ -86,6 +86,15 @@ int dcgp_kuu_rbf(dcgp_ctx* ctx, const double* Z, int M, int L, double variance, 
 int dcgp_kuf_patches_rbf(dcgp_ctx* ctx, const double* X, int N, int H, int W, int C, int f, int stride,
                          const double* Z, int M, double variance, double lengthscale,
                          double* out, int layout);
+/* MultiOutputConvKernel.Kuf (conv_gp/layers.py:23-32) with gpflow.kernels.RBF(f*f*C, ARD=True) as the base kernel:
+ * k(x, z) = variance * exp(-1/2 sum_l (x_l - z_l)^2 / lengthscales[l]^2), one lengthscale per patch element
+ * l = (kh*f + kw)*C + c.  The arguments of dcgp_kuf_patches_rbf with a DEVICE array of L = f*f*C lengthscales (all > 0)
+ * in place of the scalar; same layouts.  The patch is divided by the lengthscales where it is gathered (a pixel sits at
+ * different l in overlapping patches), Z while its transpose is formed.  K_uu of such a kernel: dcgp_kuu_rbf on the
+ * rows Z / lengthscales with lengthscale 1.                                                                          */
+int dcgp_kuf_patches_rbf_ard(dcgp_ctx* ctx, const double* X, int N, int H, int W, int C, int f, int stride,
+                             const double* Z, int M, double variance, const double* lengthscales,
+                             double* out, int layout);
 /* The same two matrices for the ArcCosine(order = 0) base kernel that `--base-kernel acos` selects for the conv
  * layers (conv_gp/models.py:118-119; gpflow.kernels.ArcCosine: k = variance * (pi - theta) / pi,
  * theta = acos(1e-15 + (1 - 2e-15) cos), cos from <x,z> = weight_variance * x.z + bias_variance; Kdiag = variance). */
