@@ -158,9 +158,9 @@ extern "C" int dcgp_model_set_eval_views(dcgp_model* model, int H, int W, int C,
     return ctx_fail(ctx, DCGP_ERR_ARG, "set_eval_views: %d x %d x %d is not the model's image of %d x %d x %d", H, W, C, L0.v.H - 2 * p, L0.v.W - 2 * p, L0.v.C);
   const size_t bytes = (size_t)V * 3 * sizeof(int32_t);
   if (bytes > model->eval_views_cap) {
-    hipFree(model->d_eval_views);
+    dev_free(ctx, model->d_eval_views);
     model->d_eval_views = nullptr; model->eval_views_cap = 0;
-    if (hipMalloc((void**)&model->d_eval_views, bytes) != hipSuccess) return ctx_fail(ctx, DCGP_ERR_ALLOC, "set_eval_views: allocation failed");
+    if (dev_alloc(ctx, (void**)&model->d_eval_views, bytes, "eval_views") != hipSuccess) return ctx_fail(ctx, DCGP_ERR_ALLOC, "set_eval_views: allocation failed");
     model->eval_views_cap = bytes;
   }
   // (no evaluation is in flight: each one ends in a stream synchronisation)

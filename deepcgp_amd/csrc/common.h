@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/dcgp.h"
+#include "dev_guard.h"
 #include "fused_plan.h"
 
 typedef double d4 __attribute__((ext_vector_type(4)));
@@ -82,9 +83,17 @@ struct DcgpOptions {
   long fused_abl = 0, rb_mixed = 0;   // timing builds only (make EXPERIMENTS=1)
 };
 long* dcgp_option_slot(DcgpOptions* o, const char* name);   // nullptr: no such option (ctx.hip)
-// debugging aid, process-wide, DCGP_POISON_WS read once: fresh device allocations of the library are filled with NaNs;
-// `name` != nullptr additionally applies DCGP_POISON_ONLY (only workspaces whose name contains that string)
+// debugging aids, process-wide, each read once.  DCGP_POISON_WS: fresh device allocations of the library are filled with NaNs;
+// `name` != nullptr additionally applies DCGP_POISON_ONLY (only allocations whose label contains that string).  DCGP_GUARD_WS=<bytes>: every
+// allocation is followed by that many guard bytes (0: off)
 bool dcgp_poison(const char* name = nullptr);
+size_t dcgp_guard_bytes();
+struct dcgp_ctx;
+// The library's one device allocator (ctx.hip): hipMalloc / hipFree of exactly `bytes`, plus the two debugging modes above.  Guard mode: the
+// allocation is registered in the ctx under `label`, its guard of 0xFF bytes starts at `bytes`, and dev_free checks it (a broken one is
+// remembered in the ctx for dcgp_debug_check_guards).  The pointer handed out is always the allocation's base.
+hipError_t dev_alloc(dcgp_ctx* ctx, void** p, size_t bytes, const char* label);
+void dev_free(dcgp_ctx* ctx, void* p);
 
 struct dcgp_ctx {
   int device = 0;
@@ -122,6 +131,7 @@ struct dcgp_ctx {
   std::string ws_tag;   // suffix of the chain's / KL terms' scratch names: steps in flight on the two banks must not share them
   // named, grow-only device workspaces owned by the ctx
   std::map<std::string, std::pair<void*, size_t>> ws;
+  dev_guard::Registry guards;   // guard mode (DCGP_GUARD_WS) only: the live allocations of dev_alloc and the violations their frees found
   // timing
   bool timing = false;
   int timing_mode = 0;   // 1: every bracketed kernel family; 2: only the roofline kernels (conv_fused, gemm_cond_s3, kuf), every 7th launch

@@ -59,6 +59,51 @@ bool dcgp_poison(const char* name) {
   return poison && (!name || !only || strstr(name, only) != nullptr);
 }
 
+size_t dcgp_guard_bytes() {
+  static const size_t guard = dev_guard::parse_bytes(getenv("DCGP_GUARD_WS"));
+  return guard;
+}
+
+// The one place the library takes and returns device memory.  `cap` >= `bytes` is what is taken when both debugging modes are off (ws_get's
+// round-up); with both off this is hipMalloc(cap) and nothing else.
+// Debugging aids.  Poison: the fresh allocation is filled with NaNs (all-ones bit pattern), so that any read of memory a kernel was supposed to
+// have written first shows up in the results.  Guard: `guard` bytes of 0xFF stand behind the REQUESTED bytes (a round-up's slack is part of the
+// guard) and are checked when the allocation is freed and by dcgp_debug_check_guards: a store past the end of a buffer shows up there, a load
+// fetches NaNs.  tests/test_gpu_memcheck.py runs every feature family under both and demands bit-identical results and whole guards.
+static hipError_t dev_alloc_cap(dcgp_ctx* ctx, void** p, size_t bytes, size_t cap, const char* label) {
+  const size_t guard = dcgp_guard_bytes();
+  const size_t total = guard ? bytes + guard : cap;   // guard >= 256 > any round-up slack: total >= cap
+  const hipError_t e = hipMalloc(p, total);
+  if (e != hipSuccess) { *p = nullptr; return e; }
+  const bool poison = dcgp_poison(label);
+  if (poison) hipMemset(*p, 0xFF, guard ? bytes : cap);
+  if (guard) {
+    hipMemset((char*)*p + bytes, 0xFF, guard);
+    if (ctx) ctx->guards.add(*p, bytes, label);
+  }
+  if (poison || guard) hipDeviceSynchronize();   // the ctx streams are non-blocking: the fill must have landed before any kernel writes the buffer
+  return hipSuccess;
+}
+hipError_t dev_alloc(dcgp_ctx* ctx, void** p, size_t bytes, const char* label) { return dev_alloc_cap(ctx, p, bytes, bytes, label); }
+
+// guard of a registered allocation back to the host: offset of its first byte that is not 0xFF, -1 whole (or unreadable: reported as offset 0)
+static long guard_scan_device(const void* p, const dev_guard::Entry& e) {
+  std::vector<unsigned char> h(dcgp_guard_bytes());
+  if (hipMemcpy(h.data(), (const char*)p + e.bytes, h.size(), hipMemcpyDeviceToHost) != hipSuccess) return 0;
+  return dev_guard::scan(h.data(), h.size());
+}
+
+void dev_free(dcgp_ctx* ctx, void* p) {
+  if (!p) return;
+  dev_guard::Entry e;
+  if (dcgp_guard_bytes() && ctx && ctx->guards.remove(p, &e)) {
+    hipDeviceSynchronize();   // whatever still writes near the buffer has to have landed
+    const long off = guard_scan_device(p, e);
+    if (off >= 0) ctx->guards.remember(e, off);
+  }
+  hipFree(p);
+}
+
 void* ws_get(dcgp_ctx* ctx, const std::string& name, size_t bytes) {
   if (bytes == 0) bytes = 16;
   auto it = ctx->ws.find(name);
@@ -66,20 +111,15 @@ void* ws_get(dcgp_ctx* ctx, const std::string& name, size_t bytes) {
   if (it != ctx->ws.end()) {
     // in-flight kernels (either stream) may still use the old buffer
     hipDeviceSynchronize();
-    hipFree(it->second.first);
+    dev_free(ctx, it->second.first);
     ctx->ws.erase(it);
   }
   void* p = nullptr;
-  size_t cap = (bytes + 255) / 256 * 256;
-  if (hipMalloc(&p, cap) != hipSuccess) {
-    ctx_fail(ctx, DCGP_ERR_ALLOC, "workspace '%s': hipMalloc(%zu) failed", name.c_str(), cap);
+  // guard mode: the capacity is the request itself, so that a larger request for the same name gets a buffer (and a guard) of its own size
+  size_t cap = dcgp_guard_bytes() ? bytes : (bytes + 255) / 256 * 256;
+  if (dev_alloc_cap(ctx, &p, bytes, cap, name.c_str()) != hipSuccess) {
+    ctx_fail(ctx, DCGP_ERR_ALLOC, "workspace '%s': allocation of %zu bytes failed", name.c_str(), cap);
     return nullptr;
-  }
-  // debugging aid: fresh workspaces filled with NaNs (all-ones bit pattern) so that any read of memory a kernel was
-  // supposed to have written first shows up in the results (the GPU suite is run this way once per change of the reverse pass)
-  if (dcgp_poison(name.c_str())) {
-    hipMemset(p, 0xFF, cap);
-    hipDeviceSynchronize();   // the ctx streams are non-blocking: the fill must have landed before any kernel writes the buffer
   }
   ctx->ws[name] = {p, cap};
   return p;
@@ -219,7 +259,7 @@ int dcgp_ctx_destroy(dcgp_ctx* ctx) {
   hipSetDevice(ctx->device);
   hipDeviceSynchronize();
   dcgp_comm_destroy(ctx);
-  for (auto& kv : ctx->ws) hipFree(kv.second.first);
+  for (auto& kv : ctx->ws) dev_free(ctx, kv.second.first);
   for (auto& pe : ctx->pending) {
     hipEventDestroy(pe.start);
     hipEventDestroy(pe.stop);
@@ -252,14 +292,14 @@ int dcgp_malloc(dcgp_ctx* ctx, size_t bytes, void** dptr) {
   if (!ctx || !dptr) return DCGP_ERR_ARG;
   *dptr = nullptr;
   if (bytes == 0) bytes = 16;
-  if (hipMalloc(dptr, bytes) != hipSuccess) return ctx_fail(ctx, DCGP_ERR_ALLOC, "hipMalloc(%zu) failed", bytes);
+  if (dev_alloc(ctx, dptr, bytes, "dcgp_malloc") != hipSuccess) return ctx_fail(ctx, DCGP_ERR_ALLOC, "allocation of %zu bytes failed", bytes);
   return DCGP_OK;
 }
 int dcgp_free(dcgp_ctx* ctx, void* dptr) {
   if (!ctx) return DCGP_ERR_ARG;
   if (!dptr) return DCGP_OK;
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  HIP_TRY(ctx, hipFree(dptr));
+  dev_free(ctx, dptr);
   return DCGP_OK;
 }
 int dcgp_h2d(dcgp_ctx* ctx, void* dst, const void* src, size_t bytes) {
@@ -295,6 +335,42 @@ int dcgp_workspace_query(dcgp_ctx* ctx, size_t* bytes_out, int* count_out) {
   for (auto& kv : ctx->ws) total += kv.second.second;
   if (bytes_out) *bytes_out = total;
   if (count_out) *count_out = (int)ctx->ws.size();
+  return DCGP_OK;
+}
+
+int dcgp_debug_guard_bytes(dcgp_ctx* ctx, long* out) {
+  if (!ctx || !out) return DCGP_ERR_ARG;
+  *out = (long)dcgp_guard_bytes();
+  return DCGP_OK;
+}
+
+int dcgp_debug_check_guards(dcgp_ctx* ctx, long* n_bad_out, char* report, int report_len) {
+  if (!ctx || !n_bad_out) return DCGP_ERR_ARG;
+  std::vector<dev_guard::Violation> bad;
+  bad.swap(ctx->guards.freed_bad);
+  if (dcgp_guard_bytes()) {
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    for (auto& kv : ctx->guards.live) {
+      const long off = guard_scan_device(kv.first, kv.second);
+      if (off < 0) continue;
+      bad.push_back(dev_guard::Violation{kv.second.label, kv.second.bytes, off, false});
+      // reported once: the guard is made whole again, so that the next check speaks of what happened since
+      HIP_TRY(ctx, hipMemset((char*)kv.first + kv.second.bytes, 0xFF, dcgp_guard_bytes()));
+    }
+    HIP_TRY(ctx, hipDeviceSynchronize());
+  }
+  *n_bad_out = (long)bad.size();
+  dev_guard::write_report(bad, report, report_len);
+  return DCGP_OK;
+}
+
+int dcgp_debug_touch_guard(dcgp_ctx* ctx, void* dptr, long offset_past_end) {
+  if (!ctx) return DCGP_ERR_ARG;
+  const dev_guard::Entry* e = dcgp_guard_bytes() ? ctx->guards.find(dptr) : nullptr;
+  if (!e || offset_past_end < 0 || (size_t)offset_past_end >= dcgp_guard_bytes())
+    return ctx_fail(ctx, DCGP_ERR_ARG, "touch_guard: guard mode off, pointer not registered or offset outside the guard");
+  const unsigned char zero = 0;
+  HIP_TRY(ctx, hipMemcpy((char*)dptr + e->bytes + offset_past_end, &zero, 1, hipMemcpyHostToDevice));
   return DCGP_OK;
 }
 

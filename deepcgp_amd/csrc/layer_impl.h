@@ -87,7 +87,7 @@ struct LayerState {
     hipDeviceSynchronize();   // steps in flight on any stream may still use them
     for (double** p : {&lat_sample, &lat_mean, &lat_var}) {
       for (size_t i = 0; i < owned.size() && *p; ++i)
-        if (owned[i] == (void*)*p) { hipFree(*p); owned.erase(owned.begin() + i); break; }
+        if (owned[i] == (void*)*p) { dev_free(ctx, *p); owned.erase(owned.begin() + i); break; }
       if (!(*p = dalloc(n))) return ctx_fail(ctx, DCGP_ERR_ALLOC, "layer: latent output allocation failed");
     }
     lat_cap = n;
@@ -97,12 +97,11 @@ struct LayerState {
   std::vector<void*> owned;
 
   ~LayerState() {
-    for (void* p : owned) hipFree(p);
+    for (void* p : owned) dev_free(ctx, p);
   }
   double* dalloc(size_t n_doubles) {
     void* p = nullptr;
-    if (hipMalloc(&p, (n_doubles ? n_doubles : 2) * sizeof(double)) != hipSuccess) return nullptr;
-    if (dcgp_poison()) { hipMemset(p, 0xFF, (n_doubles ? n_doubles : 2) * sizeof(double)); hipDeviceSynchronize(); }   // debugging aid, see ws_get (ctx.hip)
+    if (dev_alloc(ctx, &p, (n_doubles ? n_doubles : 2) * sizeof(double), is_head ? "head_layer" : "conv_layer") != hipSuccess) return nullptr;
     owned.push_back(p);
     return (double*)p;
   }
@@ -258,20 +257,17 @@ struct FactorGroup {
   double* d_yw = nullptr;
   int max_R = 0;
   bool ride = false;   // some matrix of the group carries right-hand sides
+  dcgp_ctx* owner = nullptr;   // the ctx upload() allocated under
   void release() {
-    if (dK) hipFree(dK);
-    if (dLinv) hipFree(dLinv);
-    if (dLinvT) hipFree(dLinvT);
-    if (d_info) hipFree(d_info);
-    if (d_rhs) hipFree(d_rhs);
-    if (d_yw) hipFree(d_yw);
+    for (void* p : {(void*)dK, (void*)dLinv, (void*)dLinvT, (void*)d_info, (void*)d_rhs, (void*)d_yw}) dev_free(owner, p);
     dK = dLinv = dLinvT = nullptr; d_info = nullptr; d_rhs = nullptr; d_yw = nullptr; uploaded = false;
   }
   int upload(dcgp_ctx* ctx) {
     if (uploaded) return DCGP_OK;
     const size_t n = K.size();
-    if (hipMalloc((void**)&dK, n * sizeof(double*)) != hipSuccess || hipMalloc((void**)&dLinv, n * sizeof(double*)) != hipSuccess ||
-        hipMalloc((void**)&dLinvT, n * sizeof(double*)) != hipSuccess || hipMalloc((void**)&d_info, n * sizeof(int)) != hipSuccess)
+    owner = ctx;
+    if (dev_alloc(ctx, (void**)&dK, n * sizeof(double*), "fg_dK") != hipSuccess || dev_alloc(ctx, (void**)&dLinv, n * sizeof(double*), "fg_dLinv") != hipSuccess ||
+        dev_alloc(ctx, (void**)&dLinvT, n * sizeof(double*), "fg_dLinvT") != hipSuccess || dev_alloc(ctx, (void**)&d_info, n * sizeof(int), "fg_info") != hipSuccess)
       return ctx_fail(ctx, DCGP_ERR_ALLOC, "factor group: allocation failed");
     HIP_TRY(ctx, hipMemcpy(dK, K.data(), n * sizeof(double*), hipMemcpyHostToDevice));
     HIP_TRY(ctx, hipMemcpy(dLinv, Linv.data(), n * sizeof(double*), hipMemcpyHostToDevice));
@@ -279,9 +275,8 @@ struct FactorGroup {
     if (ride) {
       size_t total = 0;
       for (auto& r : rhs) total += (r.Lq || r.qmu) ? (size_t)r.R * Mp * Mp + (size_t)Mp * r.Rp : 0;
-      if (hipMalloc((void**)&d_yw, (total ? total : 2) * sizeof(double)) != hipSuccess || hipMalloc((void**)&d_rhs, n * sizeof(ChainRhs)) != hipSuccess)
+      if (dev_alloc(ctx, (void**)&d_yw, (total ? total : 2) * sizeof(double), "fg_yw") != hipSuccess || dev_alloc(ctx, (void**)&d_rhs, n * sizeof(ChainRhs), "fg_rhs") != hipSuccess)
         return ctx_fail(ctx, DCGP_ERR_ALLOC, "factor group: allocation failed");
-      if (dcgp_poison()) { hipMemset(d_yw, 0xFF, (total ? total : 2) * sizeof(double)); hipDeviceSynchronize(); }
       size_t off = 0;
       for (auto& r : rhs) {
         r.Yw = d_yw + off;

@@ -66,9 +66,8 @@ int ensure_events(dcgp_model* m) {
 
 int ensure(dcgp_ctx* ctx, double** p, size_t* cap, size_t n) {
   if (*cap >= n && *p) return DCGP_OK;
-  if (*p) { hipDeviceSynchronize(); hipFree(*p); *p = nullptr; }   // steps in flight on any stream may still use it
-  if (hipMalloc((void**)p, (n ? n : 2) * sizeof(double)) != hipSuccess) return ctx_fail(ctx, DCGP_ERR_ALLOC, "model: allocation failed");
-  if (dcgp_poison()) { hipMemset(*p, 0xFF, (n ? n : 2) * sizeof(double)); hipDeviceSynchronize(); }   // debugging aid, see ws_get
+  if (*p) { hipDeviceSynchronize(); dev_free(ctx, *p); *p = nullptr; }   // steps in flight on any stream may still use it
+  if (dev_alloc(ctx, (void**)p, (n ? n : 2) * sizeof(double), "model_scratch") != hipSuccess) return ctx_fail(ctx, DCGP_ERR_ALLOC, "model: allocation failed");
   *cap = n;
   return DCGP_OK;
 }
@@ -78,15 +77,12 @@ int ensure_out(dcgp_model* m, int li, int rows, int width) {
   size_t n = (size_t)rows * width;
   if (o.cap < n) {
     hipDeviceSynchronize();   // steps in flight on any stream may still use them
-    hipFree(o.sample); hipFree(o.mean); hipFree(o.var);
+    dev_free(m->ctx, o.sample); dev_free(m->ctx, o.mean); dev_free(m->ctx, o.var);
     o.sample = o.mean = o.var = nullptr;
-    if (hipMalloc((void**)&o.sample, n * sizeof(double)) != hipSuccess || hipMalloc((void**)&o.mean, n * sizeof(double)) != hipSuccess ||
-        hipMalloc((void**)&o.var, n * sizeof(double)) != hipSuccess)
+    if (dev_alloc(m->ctx, (void**)&o.sample, n * sizeof(double), "out_sample") != hipSuccess ||
+        dev_alloc(m->ctx, (void**)&o.mean, n * sizeof(double), "out_mean") != hipSuccess ||
+        dev_alloc(m->ctx, (void**)&o.var, n * sizeof(double), "out_var") != hipSuccess)
       return ctx_fail(m->ctx, DCGP_ERR_ALLOC, "model: output allocation failed");
-    if (dcgp_poison()) {
-      hipMemset(o.sample, 0xFF, n * sizeof(double)); hipMemset(o.mean, 0xFF, n * sizeof(double)); hipMemset(o.var, 0xFF, n * sizeof(double));
-      hipDeviceSynchronize();
-    }
     o.cap = n;
   }
   o.rows = rows; o.width = width;
@@ -516,7 +512,7 @@ int forward_all(dcgp_model* m, const double* X, int N, int S, const double* cons
   m->bank = p.bank;
   for (auto& l : m->layers) DCGP_TRY(l->use_bank(p.bank));
   DCGP_TRY(build_groups(m, p.bank));
-  if (!m->d_scal && hipMalloc((void**)&m->d_scal, 128 * sizeof(double)) != hipSuccess)
+  if (!m->d_scal && dev_alloc(ctx, (void**)&m->d_scal, 128 * sizeof(double), "d_scal") != hipSuccess)
     return ctx_fail(ctx, DCGP_ERR_ALLOC, "model: allocation failed");
   double* scal = m->d_scal + 64 * p.bank;
   m->outs.resize(nl);
@@ -581,7 +577,7 @@ int dcgp_model_destroy(dcgp_model* model) {
   const std::string tag = "~m" + std::to_string(model->id) + "b";   // the chain's scratch (forward_all's ws_tag)
   for (auto it = ctx->ws.begin(); it != ctx->ws.end();) {
     if (it->first.compare(0, pfx.size(), pfx) == 0 || it->first.find(tag) != std::string::npos) {
-      hipFree(it->second.first);
+      dev_free(ctx, it->second.first);
       it = ctx->ws.erase(it);
     } else {
       ++it;
@@ -817,7 +813,7 @@ int dcgp_model_set_likelihood(dcgp_model* model, int kind, double variance) {
   H.lik_slots = kind == 1 ? 1 : 0;   // (only the Gaussian variance takes a slot: a Bernoulli block is a RobustMax one)
   if (kind != 1) return DCGP_OK;
   if (!model->d_lik) {   // {variance, Adam m, Adam v}
-    if (hipMalloc((void**)&model->d_lik, 3 * sizeof(double)) != hipSuccess) return ctx_fail(ctx, DCGP_ERR_ALLOC, "set_likelihood: device allocation failed");
+    if (dev_alloc(ctx, (void**)&model->d_lik, 3 * sizeof(double), "d_lik") != hipSuccess) return ctx_fail(ctx, DCGP_ERR_ALLOC, "set_likelihood: device allocation failed");
     const double init[3] = {variance, 0.0, 0.0};
     HIP_TRY(ctx, hipMemcpyAsync(model->d_lik, init, sizeof init, hipMemcpyHostToDevice, ctx->stream));
   } else {
@@ -851,7 +847,7 @@ int dcgp_model_set_likelihood_params(dcgp_model* model, int kind, const double* 
   H.lik_slots = kind == 4 ? 1 : 0;   // (the StudentT scale takes the Gaussian variance's slot: a Poisson block is a RobustMax one)
   if (kind == 5) { model->lik_binsize = p0; return DCGP_OK; }
   model->lik_nu = p1; model->lik_cnu = student_t_const(p1);
-  if (!model->d_lik && hipMalloc((void**)&model->d_lik, 3 * sizeof(double)) != hipSuccess)   // {scale, Adam m, Adam v}
+  if (!model->d_lik && dev_alloc(ctx, (void**)&model->d_lik, 3 * sizeof(double), "d_lik") != hipSuccess)   // {scale, Adam m, Adam v}
     return ctx_fail(ctx, DCGP_ERR_ALLOC, "set_likelihood_params: device allocation failed");
   const double init[3] = {p0, 0.0, 0.0};
   HIP_TRY(ctx, hipMemcpyAsync(model->d_lik, init, fresh ? sizeof init : sizeof(double), hipMemcpyHostToDevice, ctx->stream));

@@ -111,7 +111,7 @@ struct dcgp_model {
   long image_len() const { const auto& v = layers[0]->v; return (long)(v.H - 2 * pad[0]) * (v.W - 2 * pad[0]) * v.C; }
 
   ~dcgp_model() {
-    hipFree(ds_X); hipFree(ds_Y); hipFree(run_idx); hipFree(run_X); hipFree(run_Y); hipFree(d_eval_views); hipFree(d_clip);
+    for (void* p : {(void*)ds_X, ds_Y, (void*)run_idx, (void*)run_X, run_Y, (void*)d_eval_views, (void*)d_clip}) dev_free(ctx, p);
     if (h_ring) hipHostFree(h_ring);
     for (auto& e : ring_ev) if (e) hipEventDestroy(e);
     for (auto& gs : groups) for (auto& gr : gs) gr.release();
@@ -122,8 +122,8 @@ struct dcgp_model {
       if (ev_eval[b]) hipEventDestroy(ev_eval[b]);
       for (auto& e : ev_prep[b]) if (e) hipEventDestroy(e);
     }
-    for (auto& o : outs) { hipFree(o.sample); hipFree(o.mean); hipFree(o.var); }
-    hipFree(d_scal); hipFree(d_ve); hipFree(d_kd); hipFree(d_lik); hipFree(d_nodes);
+    for (auto& o : outs) { dev_free(ctx, o.sample); dev_free(ctx, o.mean); dev_free(ctx, o.var); }
+    for (double* p : {d_scal, d_ve, d_kd, d_lik, d_nodes}) dev_free(ctx, p);
   }
 };
 

@@ -94,14 +94,15 @@ struct NatGradState {   // per layer: fixed buffers + the pointer tables of the 
   double *v1 = nullptr, *v2 = nullptr, *theta = nullptr, *munew = nullptr;
   FactorGroup f1, f2, f3;
   std::vector<void*> owned;
+  dcgp_ctx* ctx = nullptr;
+  explicit NatGradState(dcgp_ctx* c) : ctx(c) {}
   ~NatGradState() {
     f1.release(); f2.release(); f3.release();
-    for (void* p : owned) hipFree(p);
+    for (void* p : owned) dev_free(ctx, p);
   }
   double* alloc(size_t n) {
     void* p = nullptr;
-    if (hipMalloc(&p, n * sizeof(double)) != hipSuccess) return nullptr;
-    if (dcgp_poison()) { hipMemset(p, 0xFF, n * sizeof(double)); hipDeviceSynchronize(); }   // debugging aid, see ws_get
+    if (dev_alloc(ctx, &p, n * sizeof(double), "natgrad") != hipSuccess) return nullptr;
     owned.push_back(p);
     return (double*)p;
   }
@@ -121,7 +122,7 @@ extern "C" int dcgp_model_natgrad_step(dcgp_model* model, double gamma, int* inf
     const int M = L.M, Mp = L.Mp, R = L.R;
     const long mm = (long)Mp * Mp, bsz = (long)R * mm;
     if (!L.natgrad_state) {
-      L.natgrad_state = std::shared_ptr<void>(new NatGradState(), [](void* p) { delete static_cast<NatGradState*>(p); });
+      L.natgrad_state = std::shared_ptr<void>(new NatGradState(ctx), [](void* p) { delete static_cast<NatGradState*>(p); });
       NatGradState& s = *static_cast<NatGradState*>(L.natgrad_state.get());
       double** all[] = {&s.Sq, &s.SqInv, &s.SqInvT, &s.Pm, &s.T1, &s.Sbar, &s.Sinv, &s.Prec, &s.PrecInv, &s.PrecInvT, &s.Snew, &s.SnewInv, &s.SnewInvT};
       for (double** p : all)

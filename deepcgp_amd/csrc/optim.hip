@@ -261,8 +261,8 @@ int opt_enqueue(dcgp_model* model, const char* who, bool sgd, double lr, double 
   if (clip) {   // norm and scale behind the gradient, in front of the update, on the step's stream
     if (model->clip_cap < (size_t)nb + 1) {
       HIP_TRY(ctx, hipDeviceSynchronize());   // (nothing may still read the smaller buffer)
-      hipFree(model->d_clip); model->d_clip = nullptr; model->clip_cap = 0;
-      if (hipMalloc((void**)&model->d_clip, ((size_t)nb + 1) * sizeof(double)) != hipSuccess)
+      dev_free(ctx, model->d_clip); model->d_clip = nullptr; model->clip_cap = 0;
+      if (dev_alloc(ctx, (void**)&model->d_clip, ((size_t)nb + 1) * sizeof(double), "d_clip") != hipSuccess)
         return ctx_fail(ctx, DCGP_ERR_ALLOC, "%s: allocation of the norm's %d partial sums failed", who, nb);
       model->clip_cap = (size_t)nb + 1;
     }

@@ -514,8 +514,8 @@ int dcgp_model_set_likelihood_nodes(dcgp_model* model, const double* nodes_host,
   const size_t count = (size_t)Q * K;
   if (count > model->nodes_cap) {
     double* fresh = nullptr;
-    if (hipMalloc((void**)&fresh, count * sizeof(double)) != hipSuccess) return ctx_fail(ctx, DCGP_ERR_ALLOC, "set_likelihood_nodes: device allocation failed");
-    hipFree(model->d_nodes);
+    if (dev_alloc(ctx, (void**)&fresh, count * sizeof(double), "lik_nodes") != hipSuccess) return ctx_fail(ctx, DCGP_ERR_ALLOC, "set_likelihood_nodes: device allocation failed");
+    dev_free(ctx, model->d_nodes);
     model->d_nodes = fresh;
     model->nodes_cap = count;
   }

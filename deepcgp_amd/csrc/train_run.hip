@@ -44,8 +44,8 @@ __global__ __launch_bounds__(256) void gather_batch_kernel(const double* __restr
 template <class T>
 int grow(dcgp_ctx* ctx, T** p, size_t* cap, size_t bytes) {
   if (*cap >= bytes && *p) return DCGP_OK;
-  if (*p) { HIP_TRY(ctx, hipDeviceSynchronize()); hipFree(*p); *p = nullptr; *cap = 0; }
-  if (hipMalloc((void**)p, bytes) != hipSuccess) return ctx_fail(ctx, DCGP_ERR_ALLOC, "train_run: allocation of %zu bytes failed", bytes);
+  if (*p) { HIP_TRY(ctx, hipDeviceSynchronize()); dev_free(ctx, *p); *p = nullptr; *cap = 0; }
+  if (dev_alloc(ctx, (void**)p, bytes, "train_run") != hipSuccess) return ctx_fail(ctx, DCGP_ERR_ALLOC, "train_run: allocation of %zu bytes failed", bytes);
   *cap = bytes;
   return DCGP_OK;
 }
@@ -63,7 +63,7 @@ int dcgp_model_set_dataset(dcgp_model* model, const double* X_host, const void* 
   if (model->enq_seq != model->col_seq) return ctx_fail(ctx, DCGP_ERR_ARG, "set_dataset: enqueued steps are still to be collected");
   if (model->ds_X || model->ds_Y) {   // nothing may still read the earlier set
     HIP_TRY(ctx, hipDeviceSynchronize());
-    hipFree(model->ds_X); hipFree(model->ds_Y);
+    dev_free(ctx, model->ds_X); dev_free(ctx, model->ds_Y);
     model->ds_X = nullptr; model->ds_Y = nullptr; model->ds_n = 0; model->ds_len = 0; model->ds_D = 0;
   }
   if (n == 0) return DCGP_OK;
@@ -73,8 +73,8 @@ int dcgp_model_set_dataset(dcgp_model* model, const double* X_host, const void* 
   const long len = model->image_len();   // the caller's images: a padded first layer pads them on the device
   const int D = y_is_f64 ? model->layers.back()->R : 0;
   const size_t xb = (size_t)n * len * sizeof(double), yb = y_is_f64 ? (size_t)n * D * sizeof(double) : (size_t)n * sizeof(int32_t);
-  if (hipMalloc((void**)&model->ds_X, xb) != hipSuccess || hipMalloc(&model->ds_Y, yb) != hipSuccess) {
-    hipFree(model->ds_X); hipFree(model->ds_Y);
+  if (dev_alloc(ctx, (void**)&model->ds_X, xb, "dataset_X") != hipSuccess || dev_alloc(ctx, &model->ds_Y, yb, "dataset_Y") != hipSuccess) {
+    dev_free(ctx, model->ds_X); dev_free(ctx, model->ds_Y);
     model->ds_X = nullptr; model->ds_Y = nullptr;
     return ctx_fail(ctx, DCGP_ERR_ALLOC, "set_dataset: allocation of %zu + %zu bytes failed", xb, yb);
   }

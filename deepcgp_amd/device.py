@@ -55,6 +55,9 @@ _SIGS = {
     "dcgp_memset": [_vp, _vp, _i, _sz],
     "dcgp_sync": [_vp],
     "dcgp_workspace_query": [_vp, C.POINTER(_sz), _ip],
+    "dcgp_debug_guard_bytes": [_vp, C.POINTER(C.c_long)],
+    "dcgp_debug_check_guards": [_vp, C.POINTER(C.c_long), C.c_char_p, _i],
+    "dcgp_debug_touch_guard": [_vp, _vp, C.c_long],
     "dcgp_ctx_set_option": [_vp, C.c_char_p, C.c_long],
     "dcgp_ctx_get_option": [_vp, C.c_char_p, C.POINTER(C.c_long)],
     "dcgp_timing_enable": [_vp, _i],
@@ -296,6 +299,24 @@ class Context:
         b, n = _sz(0), C.c_int(0)
         self._check(lib().dcgp_workspace_query(self.handle, C.byref(b), C.byref(n)))
         return b.value, n.value
+
+    # guarded allocations (DCGP_GUARD_WS; csrc/dev_guard.h) -------------------------------------------
+    def guard_bytes(self):
+        """Guard bytes behind every device allocation of the library (dcgp_debug_guard_bytes); 0: the mode is off."""
+        v = C.c_long(0)
+        self._check(lib().dcgp_debug_guard_bytes(self.handle, C.byref(v)))
+        return v.value
+
+    def check_guards(self):
+        """(n_bad, report): guards written to since the last check, live allocations' and those found when a buffer was freed
+        (dcgp_debug_check_guards); the report names label, requested bytes and first bad offset of up to eight."""
+        n, buf = C.c_long(0), C.create_string_buffer(4096)
+        self._check(lib().dcgp_debug_check_guards(self.handle, C.byref(n), buf, len(buf)))
+        return n.value, buf.value.decode()
+
+    def touch_guard(self, dev_array, offset_past_end):
+        """Clears one byte of the guard of `dev_array` (dcgp_debug_touch_guard): shows that check_guards sees it."""
+        self._check(lib().dcgp_debug_touch_guard(self.handle, dev_array.ptr, int(offset_past_end)))
 
     def measured_mfma_f64_tflops(self):
         """Sustained v_mfma_f64_16x16x4_f64 rate of this device right now (csrc/peaks.hip; ~85 ms)."""

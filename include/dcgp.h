@@ -53,6 +53,20 @@ int dcgp_sync(dcgp_ctx* ctx);
  * caller-provided workspaces; the library grows its own lazily instead (nothing on the reference side owns scratch memory either:
  * TensorFlow allocates graph temporaries itself), so the query reports what has been taken so far.                               */
 int dcgp_workspace_query(dcgp_ctx* ctx, size_t* bytes_out, int* count_out);
+/* Debugging aids of the library's device allocator (csrc/ctx.hip, csrc/dev_guard.h), both process-wide and read once.  DCGP_POISON_WS: every
+ * fresh device allocation of the library (workspaces, layer and model buffers, dcgp_malloc) is filled with 0xFF bytes (NaNs).  DCGP_GUARD_WS=<bytes>
+ * (not a number: 4096; rounded up to a multiple of 256): every allocation is followed by that many guard bytes of 0xFF, starting at the REQUESTED
+ * size, and checked when it is freed.  tests/test_gpu_memcheck.py runs every feature family under both.
+ * dcgp_debug_guard_bytes: *out = the guard size in bytes, 0 when the mode is off. */
+int dcgp_debug_guard_bytes(dcgp_ctx* ctx, long* out);
+/* Synchronises the device and reads back the guard of every live allocation; *n_bad_out = guards with a byte that is no longer 0xFF, plus the
+ * broken guards that frees have found since the last call.  report (may be NULL; report_len bytes, always terminated): label, requested bytes
+ * and offset of the first bad byte past the requested end, for the first eight of them.  A violation is reported once: a live allocation's
+ * guard is made whole again and the remembered ones are cleared.  Mode off: *n_bad_out = 0. */
+int dcgp_debug_check_guards(dcgp_ctx* ctx, long* n_bad_out, char* report, int report_len);
+/* Copies one zero byte to dptr + requested bytes + offset_past_end, i.e. into the guard of an allocation of this ctx: the way to show that the
+ * checker sees a byte.  DCGP_ERR_ARG unless guard mode is on, dptr is a registered allocation and 0 <= offset_past_end < the guard size. */
+int dcgp_debug_touch_guard(dcgp_ctx* ctx, void* dptr, long offset_past_end);
 /* A/B and debugging switches (csrc/common.h: DcgpOptions).  A ctx reads the environment variable DCGP_<NAME> once, in
  * dcgp_ctx_create, as the switch's initial value; afterwards only these calls change it -- no getenv on the step path.  Names are
  * lower case ("no_fused_layer", "kl_side", ...); an unknown name is DCGP_ERR_ARG.  dcgp_ctx_get_option also answers "n_cus": the
