@@ -47,6 +47,8 @@ struct DcgpOptions {
   long fused_rep_share = -1;     // persistent layer kernel on a tiled batch: the strips that show the same images at the same patches share one prologue, handed over by
                                  // the first of them (-1: where the simulated deal has it ahead; 0: never -- the launch of fused_pre alone)
   long head_ride = -1;           // the head's Kzx sweep as items of the layer kernel's persistent launch (-1: where fused_plan.h: plan_head_ride admits it; 0: never)
+  long head_ride_tail = -1;      // ... and the rest of the head's sweep behind them, so that no sweep launch follows (fused_plan.h: plan_head_tail; -1: where its simulated deal
+                                 // has it ahead; 0: never; 1: wherever the launch can carry it; 2, 4: the same with that many sub-row items per row -- A/B)
   long fused_wgs = 0;            // persistent layer kernel: this many workgroups instead of one per slot of the chip (0: all; tests: several rounds on a small layer)
   long fused_stagger = -1;       // persistent layer kernel: microseconds the second workgroup of a CU holds back (-1: default; 0: none)
   long kl_side = 0;              // KL terms by their own launches on the side stream instead of inside the tail launch
@@ -126,6 +128,7 @@ struct dcgp_ctx {
   hipEvent_t ev_aux = nullptr, ev_aux2 = nullptr;  // fork / join of a short side-stream excursion inside a layer
   std::string err;
   int last_head_rows = 0; long head_ride_launches = 0;   // debugging aid (dcgp_debug_head_ride)
+  int last_tail_kd = 0, last_tail_sub = 0, last_tail_parts = 0; long head_sweeps_skipped = 0;   // debugging aid (dcgp_debug_head_tail)
   unsigned fused_head_epoch = 0;  // ... and the strips' done-flags of a launch that carries head rows
   unsigned fused_pre_epoch = 0;   // the hand-over area of the layer kernel (conv_fused.hip): launches that used it so far
   std::string ws_tag;   // suffix of the chain's / KL terms' scratch names: steps in flight on the two banks must not share them

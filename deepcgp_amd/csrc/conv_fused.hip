@@ -70,7 +70,8 @@ __device__ __forceinline__ int frag_of(int w, int W, int c) { return (c >> 1) * 
 // BTP: 0 RBF, 1 ArcCosine, 2 RBF on 5 x 5 x 10 patches (the in-kernel sweep walks patch rows; an instance of its own so that the others do not carry its registers),
 // 3 Matern32, 4 Matern52 (ArcCosine's route: raw dot products, the norms applied after the sweep)
 // HEAD: the launch also carries the rows of the head's patch sweep (a.head_n items behind the last strip item: below).  An instance of its own, launched only where
-// fused_plan::plan_head_ride says so: every other launch runs the code it ran before.
+// fused_plan::plan_head_ride says so: every other launch runs the code it ran before.  HEAD = 2: and behind the rows the rest of the head's sweep (a.tail_n tail
+// items; fused_plan::plan_head_tail) -- again an instance of its own, so that the launch that carries rows alone is the code it was.
 template <int FN, int NS, int MAXF, int NT, int BTP, int ABL = 0, int HEAD = 0>
 __global__ __launch_bounds__(NT) void conv_fused_kernel(ConvFusedArgs a_in) {
   constexpr int BT = BTP == 1 ? 1 : (BTP == 3 ? 2 : (BTP == 4 ? 3 : 0));   // BaseKernel type
@@ -117,7 +118,7 @@ __global__ __launch_bounds__(NT) void conv_fused_kernel(ConvFusedArgs a_in) {
     __syncthreads();
   }
   // (a workgroup that starts when every item has been dealt -- more workgroups than CUs it may run on -- has nothing to do but sign off)
-  const int first_limit = HEAD ? a.n_items + a.head_n : (a.pre_n > 0 ? a.n_items : 0x7fffffff);
+  const int first_limit = HEAD ? a.n_items + a.head_n + a.tail_n : (a.pre_n > 0 ? a.n_items : 0x7fffffff);
   for (int it = 0; strip_next < first_limit; ++it) {
   // every strip sees the kernarg pointer and the thread index as new values: nothing of a strip's set-up (argument words, per-lane offsets of every
   // phase) is then loop-invariant, hoisted and kept live across the whole body -- as plain invariants they cost 240 spilled VGPRs at 16 waves
@@ -130,9 +131,27 @@ __global__ __launch_bounds__(NT) void conv_fused_kernel(ConvFusedArgs a_in) {
     // The row's input is this layer's sample of the strips that cover its columns: each sets its flag word to the launch's epoch behind its coherent
     // stores.  Head rows are dealt behind every strip item, so a strip a row waits for is an earlier item, held by a workgroup that is running and that
     // waits for nothing a head row produces (the invariant of the A1 hand-over; the same bounded spin, and a row that gave up leaves NaNs).
+    // Tail items (behind the a.head_n whole rows; fused_plan.h: plan_head_tail, the same decoding as fused_plan::tail_item): the rest of the head's sweep, so that
+    // no sweep launch follows.  Item t < (rows - head_n) parts: part q = t % parts of row head_n + t / parts -- the Z-fragment units [q upp, q upp + upp), one per
+    // wave, and behind the last part's units the row's Kdiag chunks.  The head_n items behind those: the Kdiag chunks of a row that rode whole, one per wave.
+    // A chunk is the one the stand-alone launch's plan gives the row (a.head.seg[1 ..]: the plan's Kdiag segments -- chunk size, count and first row of
+    // each), so its partial sum lands in the same kd slot with the same boundaries.  A tail item waits for its row's strips like a whole row, and the invariant is the same: tail items are dealt behind every strip item and every
+    // whole row, the strips they wait for are earlier items held by running workgroups, and no item waits for a head item.
     if (strip_next >= a.n_items) {
       int* tk = reinterpret_cast<int*>(smem + a.lds_main + a.lds_img + BN);
-      const int row = strip_next - a.n_items;
+      const int hit = strip_next - a.n_items;
+      int row = hit, kz_lo = 0, kz_n = -1, kd = 0;   // kz_n < 0: a whole row, unit (wave + row) % W on every wave
+      if (HEAD > 1 && hit >= a.head_n) {
+        const int t = hit - a.head_n, n_sub = a.tail_n - a.head_n;
+        if (t >= n_sub) { row = t - n_sub; kz_n = 0; kd = 1; }
+        else {
+          const int j = t, rr = j / a.tail_parts, part = j - rr * a.tail_parts;
+          row = a.head_n + rr;
+          kz_lo = part * a.tail_upp;
+          kz_n = min(a.tail_upp, a.head.nfm - kz_lo);
+          kd = part == a.tail_parts - 1 ? 1 : 0;
+        }
+      }
       if (tid == 0) {
         const int s_hi = (row * a.P + a.P - 1) / BN;
         int ok = 1;
@@ -147,9 +166,26 @@ __global__ __launch_bounds__(NT) void conv_fused_kernel(ConvFusedArgs a_in) {
       }
       __syncthreads();
       if (tk[1]) {
-        head_units_dev::head_units_body<0, 50, 0, NT, true>(ap->head, row);
+        if constexpr (HEAD > 1) {
+        // what this wave runs: (segment, unit) -- segment 0 is the Kzx units, a unit past its segment's count is no work
+        const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+        int sg = 0, u = 0x7fff;
+        if (kz_n < 0) u = (wv + row) & (W - 1);
+        else if (wv < kz_n) u = kz_lo + wv;
+        else if (kd) {
+          sg = 1;
+          for (int q = 2; q < 6; ++q)
+            if (q < a.head.nseg && row >= a.head.seg[q].img0) sg = q;
+          u = wv - kz_n;
+        }
+        head_units_dev::head_units_body<0, 50, 0, NT, true, true>(ap->head, row, sg, u);
+        } else {
+          head_units_dev::head_units_body<0, 50, 0, NT, true>(ap->head, row);
+        }
       } else {
-        for (int m = tid; m < a.head.kzx_rows; m += NT) a.head.kzx[(long)m * a.head.ldk + row] = __builtin_nan("");
+        const int m_lo = kz_n < 0 ? 0 : 16 * kz_lo, m_hi = kz_n < 0 ? a.head.kzx_rows : min(16 * (kz_lo + kz_n), a.head.kzx_rows);
+        for (int m = m_lo + tid; m < m_hi; m += NT) a.head.kzx[(long)m * a.head.ldk + row] = __builtin_nan("");
+        if (HEAD > 1 && kd && tid < a.head.n_kd) a.head.kd[(long)row * a.head.n_kd + tid] = __builtin_nan("");
       }
       if (tid == 0) tk[0] = atomicAdd(a.dyn, 1);
       __syncthreads();   // (and every wave is done with the row's image)
@@ -867,9 +903,9 @@ int launch_instance(dcgp_ctx* ctx, const ConvFusedArgs& a, const Plan& p) {
 }
 template <int I>
 int launch_fused(dcgp_ctx* ctx, const ConvFusedArgs& a, const Plan& p) {
-  if (a.head_n > 0) {   // head rows ride: the 64-column strip on 16 waves, RBF (plan_head_ride admits nothing else)
+  if (a.head_n > 0 || a.tail_parts > 0) {   // head rows ride: the 64-column strip on 16 waves, RBF (plan_head_ride admits nothing else)
     if constexpr (I == 0) {
-      if (!p.patch_rows && a.bk.type == 0) return launch_instance<0, 0, 1>(ctx, a, p);
+      if (!p.patch_rows && a.bk.type == 0) return a.tail_parts > 0 ? launch_instance<0, 0, 2>(ctx, a, p) : launch_instance<0, 0, 1>(ctx, a, p);
     }
     return ctx_fail(ctx, DCGP_ERR_ARG, "conv_fused: head rows on a launch that cannot carry them (shape %d)", I);
   }
@@ -958,6 +994,42 @@ extern "C" int dcgp_debug_plan_head_ride(const long long* query, int n_query, co
   return DCGP_OK;
 }
 
+// debugging aid (tests): {Kdiag items, sub-row items, sub-row items per row of the head's tail that the most recent layer-kernel launch of the ctx carried,
+// head sweep launches the ctx has skipped because a layer launch had run the whole sweep}
+extern "C" int dcgp_debug_head_tail(dcgp_ctx* ctx, long long* out4) {
+  if (!ctx || !out4) return DCGP_ERR_ARG;
+  out4[0] = ctx->last_tail_kd; out4[1] = ctx->last_tail_sub; out4[2] = ctx->last_tail_parts; out4[3] = ctx->head_sweeps_skipped;
+  return DCGP_OK;
+}
+
+// debugging aid (tests, no device needed): fused_plan::plan_head_tail for the launch plan_layer_launch gives the flat query, and what tail item `item` (0: the
+// first behind the whole rows) is: out[14] = {ok, why (fused_plan::TailWhy), whole rows, parts, units per part, item index of tail item 0, tail items, then of
+// `item`: row, first unit, end unit, carries the row's Kdiag chunks, first and last strip of the row, the latest item that writes samples of the row}
+extern "C" int dcgp_debug_plan_head_tail(const long long* query, int n_query, const long long* ride, int n_ride, const long long* tail, int n_tail, long long item,
+                                         long long* out, int n_out) {
+  if (!query || !ride || !tail || !out || n_query != Query::kFields || n_ride != fused_plan::RideQuery::kFields || n_tail != fused_plan::TailQuery::kFields || n_out != 14)
+    return DCGP_ERR_ARG;
+  Query q;
+  std::apply([&](auto&... f) { ((f = (long)*query++), ...); }, Query::fields(q));
+  fused_plan::RideQuery r;
+  r.next_is_head = ride[0]; r.head_form = ride[1]; r.head_HWC = ride[2]; r.head_lds = ride[3]; r.head_nfm = ride[4]; r.in_flight = ride[5]; r.chain_beside = ride[6];
+  r.head_ride = ride[7];
+  fused_plan::TailQuery t;
+  t.head_ride_tail = tail[0]; t.n_kd = tail[1];
+  const Plan p = fused_plan::plan_layer_launch(q);
+  const fused_plan::Tail tl = fused_plan::plan_head_tail(q, p, r, t);
+  fused_plan::TailItem ti{-1, 0, 0, 0};
+  long lo = 0, hi = -1, last = -1;
+  if (tl.ok && item >= 0 && item < tl.n_items) {
+    ti = fused_plan::tail_item(tl, r.head_nfm, item);
+    fused_plan::ride_row_strips(ti.row, q.P, kShapes[p.shape].FN * 16, &lo, &hi);
+    for (long st = lo; st <= hi; ++st) last = std::max(last, fused_plan::ride_sample_item(p, st));
+  }
+  const long long flat[14] = {tl.ok, tl.why, tl.n_rows, tl.parts, tl.upp, tl.first_item, tl.n_items, ti.row, ti.kz_lo, ti.kz_hi, ti.kd, lo, hi, last};
+  memcpy(out, flat, sizeof flat);
+  return DCGP_OK;
+}
+
 // debugging aid (tests, no device needed): the plan of a layer launch from a flat query; field orders in include/dcgp.h
 extern "C" int dcgp_debug_plan_layer_launch(const long long* query, int n_query, long long* plan, int n_plan) {
   if (!query || !plan || n_query != Query::kFields || n_plan != Plan::kFields) return DCGP_ERR_ARG;
@@ -992,6 +1064,23 @@ int conv_fused_rides_head(const dcgp_ctx* ctx, const ConvFusedArgs& a, bool keep
   return fused_plan::plan_head_ride(q, fused_plan::plan_layer_launch(q), r).n_rows;
 }
 
+int conv_fused_head_tail(const dcgp_ctx* ctx, const ConvFusedArgs& a, bool keeps_state, bool head_form, long head_HWC, long head_lds, long head_nfm, long head_n_kd,
+                         bool in_flight, bool chain_beside, int* n_rows) {
+  *n_rows = 0;
+  if (ctx->opt.no_fused_layer) return 0;
+  Query q = fused_query(ctx, a);
+  q.keeps_state = keeps_state;
+  fused_plan::RideQuery r;
+  r.next_is_head = 1; r.head_form = head_form; r.head_HWC = head_HWC; r.head_lds = head_lds; r.head_nfm = head_nfm; r.in_flight = in_flight;
+  r.chain_beside = chain_beside; r.head_ride = ctx->opt.head_ride;
+  fused_plan::TailQuery t;
+  t.head_ride_tail = ctx->opt.head_ride_tail; t.n_kd = head_n_kd;
+  const fused_plan::Tail tail = fused_plan::plan_head_tail_memo(q, r, t);
+  if (!tail.ok) return 0;
+  *n_rows = tail.n_rows;
+  return tail.parts;
+}
+
 int conv_fused(dcgp_ctx* ctx, const ConvFusedArgs& a_in) {
   if (a_in.Kc <= 0) return DCGP_OK;
   const Plan p = fused_plan::plan_layer_launch(fused_query(ctx, a_in));
@@ -1010,7 +1099,45 @@ int conv_fused(dcgp_ctx* ctx, const ConvFusedArgs& a_in) {
   }
   if (p.cu_slots) DCGP_TRY(ws_zeroed(ctx, "fused_cu_slots", 1024 * sizeof(int), &a.cu_slots));
   ctx->last_head_rows = 0;
-  if (a.head_n > 0) {
+  ctx->last_tail_kd = ctx->last_tail_sub = ctx->last_tail_parts = 0;
+  a.tail_n = a.tail_upp = 0;
+  if (a.tail_parts > 0) {
+    // The head's whole sweep rides (fused_plan::plan_head_tail, asked again about the launch itself): `head` becomes segment 0 = the Kzx units and, behind it, the
+    // Kdiag segments of the sweep launch's own plan -- a chunk has the boundaries and the slot it has there.
+    fused_plan::RideQuery rq;
+    rq.next_is_head = 1; rq.head_form = 1; rq.head_HWC = a.head.HWC; rq.head_lds = (long)head_units_lds(a.head); rq.head_nfm = a.head.nfm;
+    rq.head_ride = ctx->opt.head_ride;
+    fused_plan::TailQuery tq;
+    tq.head_ride_tail = ctx->opt.head_ride_tail; tq.n_kd = a.head.n_kd;
+    const fused_plan::Tail tail = fused_plan::plan_head_tail_memo(fused_query(ctx, a_in), rq, tq);
+    if (!tail.ok || tail.n_rows != a.head_n || tail.parts != a.tail_parts || a.head.X != a.out_sample || a.head.N != a_in.Kc / a_in.P || a.head.n_mod < a.head.N ||
+        a.head.n0 != 0 || !a.head.kzx || !a.head.kd || a.head.kuf || a.head.kfull || a.head.trace)
+      return ctx_fail(ctx, DCGP_ERR_ARG, "conv_fused: the launch cannot carry the head's sweep (reason %d)", tail.why);
+    HuSeg segs[6];
+    int ns = 1, next_img = 0;
+    for (int g = 0; g < a.head.nseg; ++g) {
+      const HuSeg& s = a.head.seg[g];
+      if (s.kind != 1) continue;
+      if (ns >= 6 || s.img0 != next_img || s.upw != 1 || s.C < 1 || s.C > a.head.n_kd || s.T < 1)
+        return ctx_fail(ctx, DCGP_ERR_ARG, "conv_fused: the head's Kdiag segments are not the plan the tail items were written for");
+      segs[ns] = s;
+      next_img = g + 1 < a.head.nseg ? a.head.seg[g + 1].img0 : a.head.N;   // (segments of one kind follow each other: the next one's first row ends this one)
+      ++ns;
+    }
+    if (ns < 2) return ctx_fail(ctx, DCGP_ERR_ARG, "conv_fused: the head's sweep has no Kdiag chunks to carry");
+    segs[0] = HuSeg{};
+    a.head.nseg = ns;
+    for (int g = 0; g < ns; ++g) a.head.seg[g] = segs[g];
+    a.head.n_wgs = a.head_n + tail.n_items; a.head.upw = 1;
+    a.tail_n = tail.n_items; a.tail_upp = tail.upp;
+    bool cleared = false;
+    DCGP_TRY(ws_zeroed(ctx, "fused_head_flag", (size_t)p.n_strips * sizeof(unsigned), &a.head_flag, ctx->fused_head_epoch == 0xffffffffu, &cleared));
+    if (cleared) ctx->fused_head_epoch = 0;
+    a.head_epoch = ++ctx->fused_head_epoch;
+    ctx->last_head_rows = a.head_n;
+    ctx->last_tail_kd = a.head_n; ctx->last_tail_sub = tail.n_items - a.head_n; ctx->last_tail_parts = tail.parts;
+    ++ctx->head_ride_launches;
+  } else if (a.head_n > 0) {
     // Head rows ride (decided by the step's plan through fused_plan::plan_head_ride; asked again here about the launch itself: a launch that cannot carry
     // them is refused, not run without them).  `head` becomes a launch plan of one workgroup per row that runs the row's Kzx units, one per wave.
     fused_plan::RideQuery rq;

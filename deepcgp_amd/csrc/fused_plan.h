@@ -96,6 +96,7 @@ class DealSim {
     else if (kind == kPrologueOnly) ready_[(size_t)slot] = run(kCostPrologue + kCostHandOver, 0.0);
     else run(kCostHandOver + outputs + kCostEpilogue, ready_[(size_t)slot]);
   }
+  void give_cost(double cost) { run(cost, 0.0); }   // an item of a given cost that waits for no hand-over (a head row, an item of the head's tail)
   double makespan() const { return end_; }
   std::vector<double> free_times() const {   // when each workgroup is done with its last item
     std::vector<double> out;
@@ -363,9 +364,9 @@ struct Ride {
 // Counts tried at the headline: 144 rows (three per spare workgroup) 1420 steps/s, 192 (four: 2.4 a row) 1410, 224 1405, 240 1389, all 320 1387, none 1385
 constexpr double kCostHeadRow = 3.0;
 // rows that fit in front of the end of the launch's last strip, over the workgroups of the simulated deal (the deal of plan p, item by item)
-inline long ride_room(const Query& q, const Plan& p) {
-  const long S = p.persist, strips = p.n_strips, R = q.R;
-  DealSim d(S, R, p.pre_n);
+// the items of plan p, in the order the counter deals them
+inline void deal_plan_items(DealSim& d, const Query& q, const Plan& p) {
+  const long strips = p.n_strips, R = q.R;
   if (p.pre_D > 0) {
     for (long i = 0; i < strips; ++i) {
       if (i < p.pre_D) d.give(kLeaving, i);
@@ -380,6 +381,10 @@ inline long ride_room(const Query& q, const Plan& p) {
   } else {
     for (long i = 0; i < strips; ++i) d.give(kWhole);
   }
+}
+inline long ride_room(const Query& q, const Plan& p) {
+  DealSim d(p.persist, q.R, p.pre_n);
+  deal_plan_items(d, q, p);
   long room = 0;
   for (double t : d.free_times()) room += (long)((d.makespan() - t + kEps) / kCostHeadRow);
   return room;
@@ -413,6 +418,123 @@ inline void ride_row_strips(long row, long P, long BN, long* lo, long* hi) { *lo
 inline long ride_sample_item(const Plan& p, long strip) {
   if (p.pre_n > 0 && p.pre_D == 0 && strip >= p.pre_first && strip < p.pre_first + p.pre_n) return p.n_strips + (strip - p.pre_first) * p.pre_sq;
   return strip;
+}
+
+// ---- The head's whole sweep in the launch (conv_fused.hip: HEAD, tail items) ------------------------------------------------------------------------------
+// Behind the whole rows of plan_head_ride the counter deals the REST of the head's sweep, so that no sweep launch follows the layer kernel:
+//   * `parts` sub-row items per row that did not ride whole: part q runs the Z-fragment units [q upp, q upp + upp) of the row, one per wave, and the last part the
+//     row's Kdiag chunks on the waves behind its units -- a round of such items puts two to three waves on a SIMD where a round of whole rows puts four on
+//     a third of the chip;
+//   * then one Kdiag item per row that rode whole: the row's Kdiag chunks, one per wave (the chunks of the stand-alone launch's plan, same boundaries, same slots).
+//     They wait for strips that are long done and are short, so they go LAST and fill the workgroups up behind the sub-row items, whose rows' strips end with the
+//     launch's last round (dealt first they measured 0.703 - 0.726 ms per headline step over the whole-row counts, last 0.6990 - 0.6998: profiles/head_tail_ab.txt).
+// Every tail item sits behind every strip item and behind the whole rows, and waits for the strips of its row exactly as a whole row does: a strip it
+// waits for is an earlier item, held by a running workgroup that waits for nothing a head item produces.
+struct TailQuery {
+  long head_ride_tail = -1;   // the ctx option of the same name: -1 chosen, 0 never, 1 always where eligible, k = 2 / 4 the same with k parts per row (A/B)
+  long n_kd = 0;         // Kdiag slots per row of the head's sweep plan (head_units_plan): the most chunks a row has; 0: the sweep has no Kdiag chunks
+  static constexpr int kFields = 2;
+};
+enum TailWhy { kTailRides = 0, kTailOff, kTailNoRide, kTailGeometry, kTailFewWorkgroups, kTailNoGain };
+struct Tail {
+  int ok = 0, why = kTailOff;
+  int n_rows = 0;       // whole rows in front (items first_item - n_rows .. first_item - 1): Ride::n_rows of the launch that carries the tail
+  int parts = 1, upp = 0;   // sub-row items per row that did not ride whole, Z-fragment units of each
+  int first_item = 0;   // item of the first tail item
+  int n_items = 0;      // tail items: (rows - n_rows) * parts sub-row items, row by row, then n_rows Kdiag items
+  double units_sweep = 0.0, units_tail = 0.0;   // the simulated launch + sweep launch, and the launch that carries the tail (0: not simulated)
+};
+struct TailItem { int row, kz_lo, kz_hi, kd; };   // the Z-fragment units [kz_lo, kz_hi) of `row`, and (kd) the row's Kdiag chunks
+inline TailItem tail_item(const Tail& t, long nfm, long i) {
+  const long n_sub = t.n_items - t.n_rows;
+  if (i >= n_sub) return TailItem{(int)(i - n_sub), 0, 0, 1};
+  const long row = t.n_rows + i / t.parts, part = i % t.parts;
+  return TailItem{(int)row, (int)(part * t.upp), (int)std::min<long>(nfm, (part + 1) * t.upp), part == t.parts - 1 ? 1 : 0};
+}
+// Prices in outputs of the second product (15.4 us), fitted to the layer kernel's measured length at the headline (profiles/head_tail_ab.txt, kernel stats: the
+// launch with 144 whole rows 535.4 us = this simulation's 33.25; + the tail as halves 573.3, as quarters 583.8, 320 whole rows 582.5, + their 320 Kdiag items
+// 585.1): a Kdiag item (set-up of the row's image and one chunk per wave on two to four waves: they fill gaps), a sub-row item of half / a quarter of a
+// 16-fragment row, and what the tail replaces -- the sweep launch and its boundary, with Kzx rows left in it (44.4 us + ~6 between the launches: the step gains
+// 13.3 us where the kernels' sum gains 7.2) / with Kdiag chunks only (24.3 + 6)
+constexpr double kCostTailKd = 0.9, kCostTailHalf = 1.4, kCostTailQuarter = 0.95;
+constexpr double kCostSweepKzx = 3.3, kCostSweepKd = 2.0;
+constexpr double kTailMargin = 0.5;   // the tail must save half an output (~8 us) to be chosen
+inline bool tail_parts_ok(long parts, long nfm, long n_kd, long waves) {
+  if (parts < 1 || parts > nfm) return false;
+  const long upp = (nfm + parts - 1) / parts;
+  return (parts - 1) * upp < nfm && (nfm - (parts - 1) * upp) + n_kd <= waves;   // no empty part; the last part's units and the Kdiag chunks are one wave each
+}
+inline double tail_units(const Query& q, const Plan& p, long rows, long n_rows, long parts) {
+  DealSim d(p.persist, q.R, p.pre_n);
+  deal_plan_items(d, q, p);
+  for (long i = 0; i < n_rows; ++i) d.give_cost(kCostHeadRow);
+  if (parts <= 0) return d.makespan();
+  const double part = parts >= 4 ? kCostTailQuarter : (parts >= 2 ? kCostTailHalf : kCostHeadRow);
+  for (long i = 0; i < (rows - n_rows) * parts; ++i) d.give_cost(part);
+  for (long i = 0; i < n_rows; ++i) d.give_cost(kCostTailKd);
+  return d.makespan();
+}
+inline Tail plan_head_tail(const Query& q, const Plan& p, const RideQuery& r, const TailQuery& t) {
+  Tail out;
+  auto no = [&](int why) { out.ok = 0; out.why = why; return out; };
+  if (t.head_ride_tail == 0) return no(kTailOff);
+  // eligible where plan_head_ride is: a launch whose deal merely has no room for a whole row can still carry the tail
+  const Ride ride = plan_head_ride(q, p, r);
+  if (!ride.ok && ride.why != kRideNoRoom) return no(kTailNoRide);
+  const long waves = kShapes[0].NT / 64, nfm = r.head_nfm, rows = q.Kc / q.P;
+  if (t.n_kd < 1 || t.n_kd > waves) return no(kTailGeometry);
+  const bool chosen = t.head_ride_tail < 0;
+  // (the prices were measured with one workgroup on every CU of the device: nothing else is chosen)
+  if (chosen && p.persist != (q.n_cus > 0 ? q.n_cus : 256)) return no(kTailFewWorkgroups);
+  long parts = 0;
+  if (t.head_ride_tail > 1) {
+    if (!tail_parts_ok(t.head_ride_tail, nfm, t.n_kd, waves)) return no(kTailGeometry);
+    parts = t.head_ride_tail;
+  }
+  // the whole rows in front are plan_head_ride's: the spare workgroup time is best spent on whole rows (four waves a SIMD), and with the Kdiag items last the
+  // step measured the same from 144 to 208 of them (0.6990 - 0.6998 ms; 96: 0.7032, 224: 0.6992 - 0.7026, all 320: 0.7056)
+  const long n_rows = ride.ok ? ride.n_rows : 0;
+  if (chosen) {
+    out.units_sweep = tail_units(q, p, rows, n_rows, 0) + (n_rows < rows ? kCostSweepKzx : kCostSweepKd);
+    double best = out.units_sweep - kTailMargin;
+    long best_parts = 0;
+    for (long s : {2L, 4L, 1L}) {
+      if (!tail_parts_ok(s, nfm, t.n_kd, waves)) continue;
+      const double u = tail_units(q, p, rows, n_rows, s);
+      if (u < best - kEps) { best = u; best_parts = s; }
+    }
+    if (!best_parts) return no(kTailNoGain);
+    parts = best_parts;
+    out.units_tail = best;
+  } else if (!parts) {
+    for (long s : {1L, 4L, 2L})
+      if (tail_parts_ok(s, nfm, t.n_kd, waves)) parts = s;   // (two parts where the row has them)
+    if (!parts) return no(kTailGeometry);
+  }
+  out.ok = 1; out.why = kTailRides;
+  out.n_rows = (int)n_rows;
+  out.parts = (int)parts; out.upp = (int)((nfm + parts - 1) / parts);
+  out.first_item = p.n_items + (int)n_rows;
+  out.n_items = (int)(n_rows + (rows - n_rows) * parts);
+  return out;
+}
+// ... for the plan of q itself (p = plan_layer_launch(q)), remembered: a step asks twice, launch after launch, and the simulated deals above are ~1500 items
+// each -- tens of microseconds of host time in front of a step's first launch
+inline Tail plan_head_tail_memo(const Query& q, const RideQuery& r, const TailQuery& t) {
+  if (t.head_ride_tail == 0) return Tail{};
+  static std::mutex mu;
+  static std::map<std::tuple<Query, std::tuple<long, long, long, long, long, long, long, long, long, long>>, Tail> memo;
+  const auto key = std::make_tuple(q, std::make_tuple(r.next_is_head, r.head_form, r.head_HWC, r.head_lds, r.head_nfm, r.in_flight, r.chain_beside, r.head_ride,
+                                                      t.head_ride_tail, t.n_kd));
+  {
+    std::lock_guard<std::mutex> lock(mu);
+    const auto it = memo.find(key);
+    if (it != memo.end()) return it->second;
+  }
+  const Tail out = plan_head_tail(q, plan_layer_launch(q), r, t);
+  std::lock_guard<std::mutex> lock(mu);
+  if (memo.size() > 256) memo.clear();
+  return memo[key] = out;
 }
 
 }  // namespace fused_plan

@@ -50,8 +50,11 @@ __device__ __forceinline__ int fdiv_small(int i, float inv_d) { return (int)(((f
 // block: the workgroup of the launch plan (a.seg) that the caller plays.  COH: the image is read by agent-scope loads -- rows that workgroups of the SAME launch
 // have just written on another XCD (conv_fused.hip: head rows); the values, and everything computed from them, are the same.
 #define HU_LDX(i) (COH ? __hip_atomic_load(Xn + (i), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : Xn[i])
-template <int NK4, int TL, int WMODE, int NT, bool COH = false>
-__device__ __forceinline__ void head_units_body(const __attribute__((address_space(4))) HeadUnitsArgs& a, const int block) {
+// SEL: the caller names the work itself instead of a workgroup of the plan -- `block` is the image, and each wave passes its segment sel_sg (a.seg: kind, chunk
+// size and count) and its unit sel_u (>= the segment's units: the wave has nothing to run), both wave-uniform.  The set-up is the workgroup's, whatever its
+// waves run (conv_fused.hip: whole rows and the tail items of the head's sweep).
+template <int NK4, int TL, int WMODE, int NT, bool COH = false, bool SEL = false>
+__device__ __forceinline__ void head_units_body(const __attribute__((address_space(4))) HeadUnitsArgs& a, const int block, const int sel_sg = 0, const int sel_u = 0) {
   extern __shared__ __attribute__((aligned(16))) double smem[];   // the caller's dynamic LDS, from its start
   constexpr bool WRITE = WMODE == 1 || WMODE == 2;
   constexpr bool KEEP = WMODE == 3;
@@ -85,14 +88,16 @@ __device__ __forceinline__ void head_units_body(const __attribute__((address_spa
   const int tid = threadIdx.x, lane = tid & 63, lrow = lane >> 4, lcol = lane & 15;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   // this workgroup's segment of the launch (HuSeg, common.h), its image and its place among the image's workgroups
-  int sg = 0;
+  int sg = SEL ? sel_sg : 0;
+  if constexpr (!SEL) {
 #pragma unroll
-  for (int q = 1; q < 6; ++q)
-    if (q < a.nseg && block >= a.seg[q].wg0) sg = q;
+    for (int q = 1; q < 6; ++q)
+      if (q < a.nseg && block >= a.seg[q].wg0) sg = q;
+  }
   const int seg_kind = a.seg[sg].kind, seg_T = a.seg[sg].T, seg_C = a.seg[sg].C;
-  const int wloc = block - a.seg[sg].wg0, wpi = a.seg[sg].wpi;
-  const int nloc = wloc / wpi, bw = wloc - nloc * wpi;
-  const int n = a.seg[sg].img0 + nloc;   // storing form: n < a.n_base
+  const int wloc = SEL ? 0 : block - a.seg[sg].wg0, wpi = SEL ? 1 : a.seg[sg].wpi;
+  const int nloc = SEL ? 0 : wloc / wpi, bw = wloc - nloc * wpi;
+  const int n = SEL ? block : a.seg[sg].img0 + nloc;   // storing form: n < a.n_base
   const double* __restrict__ Xn = a.X + (long)((a.n0 + n) % a.n_mod) * HWC;
   auto ldi = [&](int byte_off) { return *reinterpret_cast<const double*>(imgb + byte_off); };
   // stamps for tools/sweep_trace.py (a.trace == nullptr in normal use: one scalar branch each).  [0] wall clock (100 MHz) at entry,
@@ -195,7 +200,7 @@ __device__ __forceinline__ void head_units_body(const __attribute__((address_spa
   // (a workgroup covers WPG * upw consecutive units, wave w the units w, w + WPG, ...: one set-up for upw units per wave)
   stamp(3);
   const int seg_upw = a.seg[sg].upw;
-  int u = WPG * seg_upw * bw + ((wave + n) & (WPG - 1));
+  int u = SEL ? sel_u : WPG * seg_upw * bw + ((wave + n) & (WPG - 1));
   const int n_units = seg_kind == 1 ? seg_C : (WRITE ? a.nfm * a.st_split : a.nfm);
   if (u >= n_units) {
     if (tr && lane == 0) tr[6] = (long long)wall_clock64();

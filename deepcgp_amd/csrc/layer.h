@@ -144,6 +144,9 @@ struct ConvFusedArgs {
   // head rows riding the launch (fused_plan.h: plan_head_ride; conv_fused.hip: HEAD).  The caller sets head_n = the rows that ride (0 .. head_n - 1) and `head` = the head's sweep
   // arguments (out_sample is its X, row for row); the launcher makes `head` a plan of one workgroup per row that runs the Kzx units only, and sets the flags.
   int head_n = 0;
+  // ... and the rest of the head's sweep behind them (fused_plan.h: plan_head_tail).  The caller sets tail_parts = Tail::parts (0: no tail; head_n is then Tail::n_rows, which
+  // may be 0) and leaves the sweep plan's Kdiag segments, `kd` and `n_kd` in `head`; the launcher sets tail_n = the tail items and tail_upp = the units of a sub-row item.
+  int tail_parts = 0, tail_upp = 0, tail_n = 0;
   unsigned* head_flag = nullptr; unsigned head_epoch = 0;   // [n_strips]: a strip's samples are written once its word is the launch's epoch
   HeadUnitsArgs head;
 };
@@ -165,6 +168,10 @@ int conv_fused(dcgp_ctx* ctx, const ConvFusedArgs& a);
 // pass); 0: none (fused_plan.h: plan_head_ride -- the one place that decides)
 int conv_fused_rides_head(const dcgp_ctx* ctx, const ConvFusedArgs& a, bool keeps_state, bool head_form, long head_HWC, long head_lds, long head_nfm, bool in_flight,
                            bool chain_beside);
+// whether that launch carries the head's WHOLE sweep, so that no sweep launch follows it (head_n_kd: the Kdiag slots per row of the sweep's plan): the sub-row
+// items per row (0: no -- the answer of conv_fused_rides_head holds), and in *n_rows the whole rows in front of them (fused_plan.h: plan_head_tail)
+int conv_fused_head_tail(const dcgp_ctx* ctx, const ConvFusedArgs& a, bool keeps_state, bool head_form, long head_HWC, long head_lds, long head_nfm, long head_n_kd,
+                         bool in_flight, bool chain_beside, int* n_rows);
 
 // KL pieces of one layer -> kl4[0..3] = {mahalanobis, logdet_q, logdet_p, trace} (device)
 int kl_layer(dcgp_ctx* ctx, const GpMats& g, const double* Lp, const double* LpinvT, int white, const char* ws_prefix,

@@ -356,14 +356,14 @@ static inline bool head_sweep_rides_form(const dcgp_ctx* ctx, const LayerState& 
 
 // ConvLayer.conditional_ND (+ sampling) on `rows` input images taken as X[(n % n_mod)]
 // ride_head, ride_rows: the planned sweep of the head that follows, whose Kzx rows 0 .. ride_rows - 1 this layer's launch carries (fused_plan.h: plan_head_ride;
-// nullptr: none)
+// nullptr: none); ride_tail > 0: behind them the rest of that sweep, ride_tail sub-row items per row that did not ride whole (plan_head_tail; ride_rows may be 0)
 // planned_one_launch: -1, or the route a step's plan placed its streams and events for (0 sweep + GEMM, 1 the one-launch kernel): a different answer here
 // is refused, not run
 static inline int conv_forward(dcgp_ctx* ctx, LayerState& L, const double* X, int rows, int n_mod, int rep, long rep_stride,
                  const double* z, uint64_t seed, uint32_t stream_id, double jitter, double* out_sample, double* out_mean,
                  double* out_var, const std::string& pfx, hipEvent_t factor_done = nullptr,
                                hipEvent_t prep_done = nullptr, int phase = 3, bool keep_state = true, const RngMap* rmap = nullptr,
-                               int planned_one_launch = -1, const HeadUnitsArgs* ride_head = nullptr, int ride_rows = 0) {
+                               int planned_one_launch = -1, const HeadUnitsArgs* ride_head = nullptr, int ride_rows = 0, int ride_tail = 0) {
   // phase bit 0: the K_uf sweep (needs only Z); bit 1: conditional + finalize (needs the factorisation).  The model
   // path enqueues bit 0 of its first layer BEFORE the long side-stream sequence so that the sweep is not held up
   // by the host still enqueueing the factorisation chain.
@@ -404,11 +404,11 @@ static inline int conv_forward(dcgp_ctx* ctx, LayerState& L, const double* X, in
       // G / alpha are recorded behind the factorisation on the chain's stream: one wait covers both
       if (prep_done) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, prep_done, 0));
       else if (factor_done) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, factor_done, 0));
-      if (ride_head) { fa.head = *ride_head; fa.head_n = ride_rows; }
+      if (ride_head) { fa.head = *ride_head; fa.head_n = ride_rows; fa.tail_parts = ride_tail; }
       if (!L.mean_W && !L.mix_W) return conv_fused(ctx, fa);
       // a filter mean completes mean and sample in a pass behind the launch: rows of the head may not have read the sample inside it (model.hip: plan_step)
-      if (ride_head && ride_rows > 0 && L.mix_W) return ctx_fail(ctx, DCGP_ERR_ARG, "conv layer: a mixed layer cannot carry the head's rows");
-      if (ride_head && ride_rows > 0) return ctx_fail(ctx, DCGP_ERR_ARG, "conv layer: a layer with a mean filter cannot carry the head's rows");
+      if (ride_head && (ride_rows > 0 || ride_tail > 0) && L.mix_W) return ctx_fail(ctx, DCGP_ERR_ARG, "conv layer: a mixed layer cannot carry the head's rows");
+      if (ride_head && (ride_rows > 0 || ride_tail > 0)) return ctx_fail(ctx, DCGP_ERR_ARG, "conv layer: a layer with a mean filter cannot carry the head's rows");
       DCGP_TRY(conv_fused(ctx, fa));
       if (L.mix_W)
         DCGP_TRY(mix_forward(ctx, L.mix_W, L.R, L.Rout, out_sample, out_mean, out_var, 0, Kc, rep, rep_stride, out_stride, mix_sample, mix_mean, mix_var));
@@ -490,10 +490,11 @@ static inline int conv_forward(dcgp_ctx* ctx, LayerState& L, const double* X, in
 static inline int head_forward(dcgp_ctx* ctx, LayerState& L, const double* X, int rows, int n_mod, double* kd, double* out_mean,
                  double* out_var, const std::string& pfx, hipEvent_t factor_done = nullptr,
                                hipEvent_t prep_done = nullptr, int sweep_mode = 0, bool* early_done = nullptr,
-                               bool keep_k = false, KlOffer* kl = nullptr, int kzx_done = 0) {
+                               bool keep_k = false, KlOffer* kl = nullptr, int kzx_done = 0, bool sweep_done = false) {
   // kzx_done: the layer kernel in front has run the Kzx units of the rows below it (conv_forward: ride_head) -- the sweep launch is the Kzx units of the other
   // rows and the same Kdiag chunks (the plan is made with every Kzx unit and those rows are then taken out: a unit's value, a chunk's sum do not depend on
   // where in the launch they run)
+  // sweep_done (with kzx_done = rows): it has run the Kdiag chunks of that plan as well, every partial sum in its slot of "kdiag_partial" -- no sweep launch at all
   // kl: the KL pieces of an ELBO step, for the one-launch conditional to carry (layer.h: KlOffer)
   // keep_k (a training step): the unit sweep also leaves every patch response in the "<pfx>g_Kfull" workspace [Mp][col_ld(rows P)] and sets
   // L.kfull_ready (the reverse pass would otherwise evaluate them all again)
@@ -543,6 +544,7 @@ static inline int head_forward(dcgp_ctx* ctx, LayerState& L, const double* X, in
         if (sweep_mode != 0 || h.kfull || h.nseg < 2 || h.seg[0].kind != 0)
           return ctx_fail(ctx, DCGP_ERR_ARG, "head: its Kzx rows were run by the layer kernel, but the sweep is not the one that was planned");
         if (kzx_done > rows) return ctx_fail(ctx, DCGP_ERR_ARG, "head: more Kzx rows done than the head has");
+        if (sweep_done && kzx_done != rows) return ctx_fail(ctx, DCGP_ERR_ARG, "head: the whole sweep is done, but not every Kzx row");
         const int gone = h.seg[0].wpi * kzx_done;   // their workgroups
         for (int q = 1; q < h.nseg; ++q) h.seg[q].wg0 -= gone;
         h.n_wgs -= gone;
@@ -552,7 +554,11 @@ static inline int head_forward(dcgp_ctx* ctx, LayerState& L, const double* X, in
           --h.nseg;
         }
       }
-      if (sweep_mode != 2) DCGP_TRY(head_units(ctx, h));
+      if (sweep_done) {
+        // (the sweep launch's table of 2^(j / 256) stays a workspace of the ctx whichever route its steps take: the next step may be one that falls back)
+        if (!exp2_table(ctx)) return DCGP_ERR_ALLOC;
+        ++ctx->head_sweeps_skipped;
+      } else if (sweep_mode != 2) DCGP_TRY(head_units(ctx, h));
       if (sweep_mode == 1) {
         if (early_done) *early_done = true;
         return DCGP_OK;
@@ -574,7 +580,7 @@ static inline int head_forward(dcgp_ctx* ctx, LayerState& L, const double* X, in
       return finalize_layer(ctx, fa);
     }
   }
-  if (kzx_done) return ctx_fail(ctx, DCGP_ERR_ARG, "head: its Kzx rows were run by the layer kernel, but the head does not take the unit sweep");
+  if (kzx_done || sweep_done) return ctx_fail(ctx, DCGP_ERR_ARG, "head: its Kzx rows were run by the layer kernel, but the head does not take the unit sweep");
   if (sweep_mode == 1) return DCGP_OK;   // not the unit-sweep route: nothing is launched ahead
   if (L.kernel_type == 0 && a.bk.type == 0 && head_cond_fused_ok(L.g) && !unfused) {
     // ConvKernel head, M <= 256: Kzx and Kdiag in one launch, then the whole conditional in one launch that adds up the Kdiag

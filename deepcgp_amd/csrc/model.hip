@@ -183,6 +183,9 @@ struct StepPlan {
   // The conv layer whose persistent launch also runs the Kzx units of the head's rows 0 .. ride_rows - 1, in the workgroup time its partial last round
   // leaves (-1: none; fused_plan.h: plan_head_ride decides).  The head's sweep launch is then the other rows' Kzx units and the Kdiag chunks.
   int ride_layer = -1, ride_rows = 0;
+  // ... and behind those rows the rest of the head's sweep -- ride_tail sub-row items per row that did not ride whole, every Kdiag chunk -- so that the head
+  // launches no sweep at all (0: no; fused_plan.h: plan_head_tail decides, and ride_rows is then its count of whole rows, which may be 0)
+  int ride_tail = 0;
   bool chain_beside() const { return chain_s != main_s; }   // events only where another stream waits for them: each record is a packet in front of the next launch
 };
 // what the caller of a step hands over
@@ -225,9 +228,18 @@ StepPlan plan_step(const dcgp_model* m, int N, int S, int dedup, bool need_kl, b
     HeadUnitsArgs h = head_sweep_shape(ctx, Lh, nullptr, rows_out, rows_out, nullptr, col_ld(rows_out));
     head_units_plan(&h);
     const bool form = head_sweep_rides_form(ctx, Lh, h) && !(m->keep_state && m->grad_follows);
-    if (li > 0 || p.first_one_launch)
-      p.ride_rows = conv_fused_rides_head(ctx, fa, m->keep_state, form, h.HWC, (long)head_units_lds(h), h.nfm, pipelined, p.chain_beside() && !p.reuse);
-    if (p.ride_rows > 0) p.ride_layer = li;
+    if (li > 0 || p.first_one_launch) {
+      // (the sweep's Kdiag slots per row are those of the plan WITH its Kzx units: the plan head_forward makes)
+      static double kzx_placeholder;
+      HeadUnitsArgs hk = h;
+      hk.kzx = &kzx_placeholder;
+      head_units_plan(&hk);
+      int tail_rows = 0;
+      p.ride_tail = conv_fused_head_tail(ctx, fa, m->keep_state, form, h.HWC, (long)head_units_lds(h), h.nfm, hk.n_kd, pipelined, p.chain_beside() && !p.reuse, &tail_rows);
+      if (p.ride_tail > 0) p.ride_rows = tail_rows;
+      else p.ride_rows = conv_fused_rides_head(ctx, fa, m->keep_state, form, h.HWC, (long)head_units_lds(h), h.nfm, pipelined, p.chain_beside() && !p.reuse);
+    }
+    if (p.ride_rows > 0 || p.ride_tail > 0) p.ride_layer = li;
   }
   return p;
 }
@@ -315,11 +327,15 @@ int run_layer(dcgp_model* m, const StepPlan& p, const StepIn& in, int li, const 
       if (!B) return DCGP_ERR_ALLOC;
       ride = head_sweep_shape(ctx, Lh, o.sample, out_rows, out_rows, B, ldh);
       head_units_plan(&ride);
+      if (p.ride_tail > 0) {   // the partial sums go where head_forward's conditional reads them
+        ride.kd = (double*)ws_get(ctx, "kdiag_partial", (size_t)out_rows * ride.n_kd * sizeof(double));
+        if (!ride.kd) return DCGP_ERR_ALLOC;
+      }
     }
     DCGP_TRY(conv_forward(ctx, L, F, rows, n_mod, expand ? in.S : 1, (long)in.N * lat_width, z, in.seed, (uint32_t)(li + 1 + (sharded ? 0 : 64 * ctx->rank)),
                           m->jitter, o.sample, m->keep_outputs ? o.mean : nullptr, m->keep_outputs ? o.var : nullptr, pfx,
                           fdone, pdone, phase, m->keep_state, &rm, li == 0 ? (int)p.first_one_launch : -1,
-                          (li == p.ride_layer && (phase & 2)) ? &ride : nullptr, p.ride_rows));
+                          (li == p.ride_layer && (phase & 2)) ? &ride : nullptr, p.ride_rows, p.ride_tail));
     *out_rows_p = out_rows;
     return DCGP_OK;
   }
@@ -328,7 +344,8 @@ int run_layer(dcgp_model* m, const StepPlan& p, const StepIn& in, int li, const 
   DCGP_TRY(ensure(ctx, &m->d_kd, &m->kd_cap, (size_t)rows));
   DCGP_TRY(head_forward(ctx, L, F, rows, n_mod, m->d_kd, o.mean, o.var, pfx, fdone, pdone,
                         phase == 1 ? 1 : (phase == 2 && *head_swept ? 2 : 0), phase == 1 ? head_swept : nullptr,
-                        m->keep_state && m->grad_follows, kl, (p.ride_layer == li - 1 && p.ride_layer >= 0) ? p.ride_rows : 0));
+                        m->keep_state && m->grad_follows, kl, (p.ride_layer == li - 1 && p.ride_layer >= 0) ? (p.ride_tail > 0 ? rows : p.ride_rows) : 0,
+                        p.ride_layer == li - 1 && p.ride_layer >= 0 && p.ride_tail > 0));
   *out_rows_p = rows;
   if (phase != 1 && m->keep_outputs) {
     // the head's sample is not needed by the ELBO; produce it only on request

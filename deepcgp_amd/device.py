@@ -172,6 +172,8 @@ _SIGS = {
     "dcgp_debug_plan_gemm": [_vp, _i, _vp, _i],
     "dcgp_debug_head_ride": [_vp, _vp],
     "dcgp_debug_plan_head_ride": [_vp, _i, _vp, _i, C.c_longlong, _vp, _i],
+    "dcgp_debug_head_tail": [_vp, _vp],
+    "dcgp_debug_plan_head_tail": [_vp, _i, _vp, _i, _vp, _i, C.c_longlong, _vp, _i],
     "dcgp_debug_comm_gate": [_vp, _i, _ip],
     "dcgp_debug_mfma_f64_rate": [_vp, _dp],
     "dcgp_debug_store_rate": [_vp, _i, _i, _i, _dp],

@@ -772,6 +772,18 @@ int dcgp_debug_plan_gemm(const long long* query, int n_query, long long* plan, i
  *   strip whose samples are `row`, the latest item that writes any of them (-1 where it does not ride or `row` is out of range)}. */
 int dcgp_debug_head_ride(dcgp_ctx* ctx, long long* out2);
 int dcgp_debug_plan_head_ride(const long long* query, int n_query, const long long* ride, int n_ride, long long row, long long* out, int n_out);
+/* The head's WHOLE sweep in that launch, so that no sweep launch follows it (csrc/fused_plan.h, plan_head_tail; ctx option head_ride_tail: -1 where the simulated
+ * deal has it ahead, 0 never, 1 wherever the launch can carry it, 2 / 4 the same with that many sub-row items per row).  Behind the whole rows of plan_head_ride
+ * the counter deals `parts` sub-row items per row that did not ride whole (the last of them also runs the row's Kdiag chunks), then one Kdiag item per row that did.
+ * dcgp_debug_head_tail: out4 = {Kdiag items, sub-row items, parts of the ctx's most recent layer-kernel launch (0: it carried no tail), head sweep launches
+ *   the ctx has skipped because a layer launch had run the whole sweep}.
+ * dcgp_debug_plan_head_tail (no ctx, no device): query and ride as above, tail[2] = {the ctx option head_ride_tail, Kdiag slots per row of the sweep's plan};
+ *   out[14] = {ok, why (0 rides, 1 option off, 2 plan_head_ride does not admit the launch, 3 geometry, 4 chosen only with a workgroup on every CU, 5 the simulated
+ *   deal has no gain), whole rows in front, parts, Z-fragment units of a part, item of tail item 0, tail items, then of tail item `item`: its row, first and end
+ *   unit, whether it runs the row's Kdiag chunks, first and last strip of the row, the latest item that writes samples of it (row -1 where `item` is out of range)}. */
+int dcgp_debug_head_tail(dcgp_ctx* ctx, long long* out4);
+int dcgp_debug_plan_head_tail(const long long* query, int n_query, const long long* ride, int n_ride, const long long* tail, int n_tail, long long item,
+                              long long* out, int n_out);
 /* The same for the patch sweeps (csrc/head_units.hip; tools/sweep_trace.py): [n_workgroups][waves per workgroup][8] int64 -- wall clock at entry,
  * shader clock at entry / image staged / set-up done / first unit done / last unit done, wall clock at exit, units run.            */
 /* The ceilings bench.py prices kernels against, measured on this device (csrc/peaks.hip): the sustained fp64 MFMA rate (TFLOP/s, 4 waves
