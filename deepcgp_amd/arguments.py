@@ -29,6 +29,7 @@ FLAGS = (
     ("--test-views", str, "cross", "which shifts --test-shift N takes: cross (0 and +-N along each axis, 5 views) | grid (all (2N+1)^2 shifts)"),
     ("--base-kernel", str, "rbf", "base kernel of the conv layers: rbf | acos | matern32 | matern52"),
     ("--ard", None, False, "per-dimension (ARD) lengthscales on the conv layers' base kernel: one per patch element, f*f*C a layer (needs --base-kernel rbf)"),
+    ("--inducing-init", str, "kmeans", "how the inducing patches (dense head: inducing points) a checkpoint does not hold are chosen: kmeans (centres of 100 M random patches, the reference's) | greedy (M of the same candidates by greedy conditional variance under the layer's own kernel)"),
     ("--white", None, False, "whitened variational parameters"),
     ("--last-kernel", str, "conv", "head kernel: conv | add | rbf"),
     ("--likelihood", str, "robustmax", "multi-class likelihood: robustmax | softmax"),
@@ -117,6 +118,17 @@ def parse_test_views(flags):
     if shift == 0 and not flip:
         return None
     return views(shift, flip, pattern)
+
+
+INDUCING_INITS = ("kmeans", "greedy")
+
+
+def parse_inducing_init(flags):
+    """``--inducing-init`` as one of ``INDUCING_INITS``: "kmeans" when the flag is absent; an unknown value raises ValueError naming the flag."""
+    value = getattr(flags, "inducing_init", "kmeans") or "kmeans"
+    if value not in INDUCING_INITS:
+        raise ValueError("--inducing-init: expected %s, got %r" % (" | ".join(INDUCING_INITS), value))
+    return value
 
 
 def parse_clip_norm(flags):

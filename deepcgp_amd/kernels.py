@@ -365,6 +365,81 @@ def _cluster_patches(NHWC_X, M, patch_size):
     return kmeans(sample, M, distinct_start=True)
 
 
+def _greedy_kernel_args(base_kernel):
+    """(type, variance, p1, p2, ARD lengthscales or None) of ``dcgp_greedy_variance`` for a base kernel: ``_describe()``'s codes."""
+    if not isinstance(base_kernel, (RBF, ArcCosine, _Matern)):
+        raise TypeError("greedy_variance: base_kernel must be an RBF, ArcCosine, Matern32 or Matern52, got %r" % (base_kernel,))
+    kind, variance, p1, p2 = base_kernel._describe()
+    ard = np.ascontiguousarray(base_kernel.lengthscales, np.float64) if getattr(base_kernel, "ARD", False) else None
+    return int(kind), float(variance), float(p1), float(p2), ard
+
+
+def _greedy_fill(rows, n_greedy, residual, k):
+    """The k selected rows: the ``n_greedy`` greedy picks, then -- the greedy phase stalled at the floor -- the candidates of largest residual
+    (ties: lower index) that are not picked yet and whose residual is not exactly 0 (a copy of a pick).  Fewer than k usable candidates:
+    ValueError giving their number."""
+    rows = np.asarray(rows[:n_greedy], np.int64)
+    if n_greedy >= k:
+        return rows[:k]
+    residual = np.asarray(residual, np.float64)
+    usable = residual > 0.0
+    usable[rows] = False
+    pool = np.flatnonzero(usable)
+    if n_greedy + pool.size < k:
+        raise ValueError("greedy_variance: only %d usable candidates (%d selected above the floor, %d more with a non-zero residual) for k = %d"
+                         % (n_greedy + pool.size, n_greedy, pool.size, k))
+    order = pool[np.argsort(-residual[pool], kind="stable")]      # pool ascends, the sort is stable: ties go to the lower index
+    return np.concatenate([rows, order[:k - n_greedy]])
+
+
+def greedy_variance_device(points, k, base_kernel, min_variance=JITTER, factor=False):
+    """dcgp_greedy_variance as it is: {"rows" [k] (-1 behind n_greedy), "n_greedy", "trace" [k], "residual" [n], "factor" [k, n] or None}."""
+    import ctypes as C
+    P = np.ascontiguousarray(points, np.float64)
+    if P.ndim != 2:
+        raise ValueError("greedy_variance: points must be [n, d], got shape %r" % (P.shape,))
+    n, d = P.shape
+    k = int(k)
+    if k < 1 or n < k:
+        raise ValueError("greedy_variance: k = %d rows of n = %d candidates" % (k, n))
+    if d != base_kernel.input_dim:
+        raise ValueError("expected inputs of length %d, got %d" % (base_kernel.input_dim, d))
+    kind, variance, p1, p2, ard = _greedy_kernel_args(base_kernel)
+    ctx = dev.get_context()
+    dP = ctx.to_device(P)
+    dls = ctx.to_device(ard) if ard is not None else None
+    rows, trace, resid = ctx.empty((k,), np.int32), ctx.empty((k,)), ctx.empty((n,))
+    fac = ctx.empty((k, n)) if factor else None
+    ng = C.c_int(0)
+    ctx._check(dev.lib().dcgp_greedy_variance(ctx.handle, dP.ptr, n, d, k, kind, variance, p1, p2, dls.ptr if dls else None,
+                                              float(min_variance), rows.ptr, trace.ptr, resid.ptr, fac.ptr if fac else None, C.byref(ng)))
+    return {"rows": rows.numpy(), "n_greedy": ng.value, "trace": trace.numpy(), "residual": resid.numpy(),
+            "factor": fac.numpy() if fac else None}
+
+
+def greedy_variance(points, k, base_kernel, min_variance=JITTER, return_info=False):
+    """Greedy conditional-variance selection (dcgp_greedy_variance; Burt, Rasmussen & van der Wilk 2020): ``k`` rows of ``points`` [n, d], each
+    the candidate whose prior variance under ``base_kernel`` -- an ``RBF`` (scalar or ``ARD=True``), ``ArcCosine``, ``Matern32`` or
+    ``Matern52`` -- conditioned on the rows chosen before it is largest.  The greedy phase stops at ``min_variance`` (default: the jitter
+    K_uu receives anyway, below which it cannot tell candidates apart); the remaining rows are then taken in decreasing residual
+    (``_greedy_fill``).  Returns Z [k, d]; ``return_info=True`` adds {"rows", "n_greedy", "trace", "residual"}: the chosen row indices, how
+    many of them the greedy phase picked, the candidates' Nystrom trace tr(K_ff - Q_ff) after every greedy pick, the final residual."""
+    P = np.ascontiguousarray(points, np.float64)
+    out = greedy_variance_device(P, k, base_kernel, min_variance)
+    chosen = _greedy_fill(out["rows"], out["n_greedy"], out["residual"], int(k))
+    Z = P[chosen].copy()
+    if return_info:
+        return Z, {"rows": chosen, "n_greedy": out["n_greedy"], "trace": out["trace"], "residual": out["residual"]}
+    return Z
+
+
+def _greedy_patches(NHWC_X, M, patch_size, base_kernel, min_variance):
+    """The greedy counterpart of ``_cluster_patches``: the same 100 * M patches (same generator, same order), M of them selected."""
+    from .models import draw_patches
+    sample = draw_patches(np.asarray(NHWC_X, np.float64), 100 * M, patch_size)
+    return greedy_variance(sample, M, base_kernel, min_variance=min_variance, return_info=True)
+
+
 class InducingPoints:
     """gpflow.features.InducingPoints(Z) -- the dense head's feature (conv_gp/models.py:168)."""
 
@@ -385,8 +460,19 @@ class PatchInducingFeatures:
         return self.Z.shape[0]
 
     @classmethod
-    def from_images(cls, NHWC_X, M, patch_size):
-        return cls(_cluster_patches(NHWC_X, M, patch_size))
+    def from_images(cls, NHWC_X, M, patch_size, method="kmeans", base_kernel=None, min_variance=JITTER):
+        """``method="kmeans"``: the reference's recipe, centres of 100 M random patches.  ``"greedy"``: M of the same patches by conditional
+        variance under ``base_kernel`` (``greedy_variance``); the selection's info stays on the feature as ``init_info``."""
+        if method == "kmeans":
+            return cls(_cluster_patches(NHWC_X, M, patch_size))
+        if method != "greedy":
+            raise ValueError("from_images: method must be 'kmeans' or 'greedy', got %r" % (method,))
+        if base_kernel is None:
+            raise ValueError("from_images: method 'greedy' needs the layer's base_kernel")
+        Z, info = _greedy_patches(NHWC_X, M, patch_size, base_kernel, min_variance)
+        feature = cls(Z)
+        feature.init_info = info
+        return feature
 
 
 def Kuu(feature, kern, jitter=0.0):

@@ -2,14 +2,15 @@
 from the neutral model spec used by the benchmarks and parity tests (deepcgp_amd.synthetic)."""
 import numpy as np
 
+from . import kernels as _kernels
 from .dgp import DGP_Base
-from .kernels import RBF, ArcCosine, Matern32, Matern52, ConvKernel, AdditivePatchKernel, PatchInducingFeatures, InducingPoints
+from .kernels import JITTER, RBF, ArcCosine, Matern32, Matern52, ConvKernel, AdditivePatchKernel, PatchInducingFeatures, InducingPoints
 from .layers import ConvLayer, SVGP_Layer, mixing_matrix
 from .likelihoods import MultiClass, Softmax
 from .mean_functions import Conv2dMean, IdentityConv2dMean  # noqa: F401  (the names conv_gp/models.py:11 imports)
 from .mean_functions import MEAN_FILTERS, LinearConv2dMean, conv_mean_filter
 from .views import FullView
-from .arguments import parse_latent_gps, parse_paddings
+from .arguments import parse_inducing_init, parse_latent_gps, parse_paddings
 
 
 def parse_ints(int_string):
@@ -615,6 +616,33 @@ class ModelBuilder(object):
             raise ValueError("layer %d's checkpoint holds %d lengthscales (a model trained with --ard): pass --ard to load it" % (li, ls.size))
         return float(ls.reshape(()))
 
+    def _conv_base_kernel(self, li, have, L, ard):
+        """The base kernel conv layer ``li`` starts with, as ``build_layers_from_spec`` will build it from the spec entry: what
+        --inducing-init greedy selects its inducing patches under."""
+        kind = self.flags.base_kernel
+        if kind == "acos":
+            return ArcCosine(L, order=0)
+        variance, ls = float(have.get("variance", 5.0)), self._conv_lengthscales(li, have, L, ard)
+        if ard:
+            return RBF(L, variance, ls, ARD=True)
+        return BASE_KERNELS[kind](L, variance, ls)
+
+    @staticmethod
+    def _report_stall(li, info, M):
+        if info["n_greedy"] < M:
+            print("layer {}: greedy selection stopped at {} of M = {} inducing points (conditional variance floor {}); "
+                  "the rest are filled by residual.".format(li, info["n_greedy"], M, JITTER))
+
+    def _greedy_patches(self, li, images, M, f, base_kernel):
+        feature = PatchInducingFeatures.from_images(images, M, f, method="greedy", base_kernel=base_kernel)
+        self._report_stall(li, feature.init_info, M)
+        return feature.Z
+
+    def _greedy_select(self, li, rows, M, base_kernel):
+        Z, info = _kernels.greedy_variance(rows, M, base_kernel, return_info=True)
+        self._report_stall(li, info, M)
+        return Z
+
     # ---- stages -> spec ----------------------------------------------------------------------------
     def spec(self):
         fl = self.flags
@@ -632,13 +660,17 @@ class ModelBuilder(object):
         mean_kind, train_mean = self.mean_flags()
         latent = parse_latent_gps(fl, len(convs))         # --latent-gps: G per conv layer, 0 = unmixed
         ard = self.ard_flag()                              # --ard: per-dimension lengthscales on the conv layers
+        init = parse_inducing_init(fl)                     # --inducing-init: kmeans (the reference's) | greedy
         spec = {"S": int(fl.num_samples), "num_data": int(self.X_train.shape[0]), "convs": []}
         images = self.X_train                              # what the next layer is initialised on
         for li, (M, f, s, R) in enumerate(convs):
             have = stored.get(li, {})
             _, H, W, C = images.shape                          # (H, W stay the unpadded size; "pad" carries the border)
             images = zero_pad(images, pads[li])                # inducing patches and the next layer's images: from what the window sees
-            Z = have["Z"] if "Z" in have else PatchInducingFeatures.from_images(images, M, f).Z
+            if init == "kmeans" or "Z" in have:
+                Z = have["Z"] if "Z" in have else PatchInducingFeatures.from_images(images, M, f).Z
+            else:               # --inducing-init greedy: M of the same candidates, by conditional variance under the kernel the layer starts with
+                Z = self._greedy_patches(li, images, M, f, self._conv_base_kernel(li, have, f * f * C, ard))
             G = latent[li] or R                                # the layer's GPs; R stays the maps it emits
             spec["convs"].append(dict(
                 H=H, W=W, C=C, f=f, s=s, M=M, R=G, Z=Z, Z0=Z, white=white, base=fl.base_kernel, pad=pads[li],
@@ -673,13 +705,19 @@ class ModelBuilder(object):
             head["ls"] = 1.0
             if "Z" in have:
                 head["Z"] = have["Z"]
+            elif init == "greedy":      # all initialisation rows as candidates, a random 100 M of them when there are more
+                rows = flat if flat.shape[0] <= 100 * head_M else flat[np.random.choice(flat.shape[0], 100 * head_M, replace=False)]
+                head["Z"] = self._greedy_select(n_layers - 1, rows, head_M, RBF(flat.shape[1], head["variance"], head["ls_ard"], ARD=True))
             else:
                 from sklearn import cluster
                 head["Z"] = cluster.KMeans(n_clusters=head_M, init="k-means++", n_init=1).fit(flat).cluster_centers_
             head["w"] = np.ones(1)
         else:
             head["ls"] = float(have.get("ls", 5.0))
-            head["Z"] = have["Z"] if "Z" in have else PatchInducingFeatures.from_images(images, head_M, head_f).Z
+            if init == "kmeans" or "Z" in have:
+                head["Z"] = have["Z"] if "Z" in have else PatchInducingFeatures.from_images(images, head_M, head_f).Z
+            else:               # under the head's base kernel, its scalar RBF (not its weighted patch kernel)
+                head["Z"] = self._greedy_patches(n_layers - 1, images, head_M, head_f, RBF(head_f * head_f * C, head["variance"], head["ls"]))
             head["w"] = have.get("w")
         spec["head"] = head
         return spec

@@ -713,6 +713,25 @@ int dcgp_gemm_strided_ex(dcgp_ctx* ctx, const double* A, long a_rs, long a_cs, l
  * when the summed squared centre shift is <= tol.  Deterministic for given initial rows. */
 int dcgp_kmeans(dcgp_ctx* ctx, const double* X, long n, int d, int k, const int32_t* init_rows_host, int max_iter,
                 double tol, double* centers, int* iters_out);
+/* Greedy conditional-variance selection of k of n candidate points X [n, d] (device, row-major) under a base kernel: a partial pivoted
+ * Cholesky factorisation of the candidates' Gram matrix (Burt, Rasmussen & van der Wilk, JMLR 2020; robustgp.ConditionalVariance, the
+ * initialisation gpflow's documentation recommends) -- the kernel-aware alternative to the k-means above; the reference has no counterpart.
+ * The residual starts at the Gram matrix's diagonal (variance; acos: variance (1 - acos(1 - 1e-15) / pi), the entry dcgp_kuu_acos writes).
+ * Pick m takes the candidate of largest residual (ties: lowest index), stops when that is
+ * <= min_variance (*n_greedy_out = m), else sets c_m[i] = (k(x_i, x_j) - sum_{t<m} c_t[j] c_t[i]) / sqrt(d_j) (c_m[j] = sqrt(d_j); 0 where d_i is
+ * already 0) and d_i = max(d_i - c_m[i]^2, 0), d_j = 0.
+ * kernel_type / variance / p1 / p2 as dcgp_model_set_param's "base_kernel" (0 rbf, 1 acos, 2 matern32, 3 matern52; p1 the lengthscale,
+ * or for acos the weight variance with p2 the bias variance); k is evaluated as dcgp_kuu_rbf / _acos / _matern evaluate it.
+ * ard_lengthscales [d] (device) or NULL: per-dimension lengthscales, rbf only (p1 is then not used).
+ * rows_out [k] (device, int32): the picks in order, -1 behind n_greedy.  trace_out [k]: sum_i d_i after every pick (the Nystrom trace
+ * tr(K_ff - Q_ff) of the candidates), the last value repeated behind n_greedy.  residual_out [n]: the final d.  factor_out [k, n] or NULL:
+ * the rows c_m (zero behind n_greedy): factor_out[:, rows]^T is the lower Cholesky factor of K(X[rows]), factor_out^T factor_out the Nystrom
+ * approximation of the candidates' Gram matrix.  n <= 2^31 - 1, k <= 4096, d <= 4096.  One launch per pick, no synchronisation between
+ * them; scratch (the transposed candidates, the factor when factor_out is NULL) is allocated and freed inside the call.  Deterministic.
+ * A residual that is not finite (candidates that are not) is DCGP_ERR_ARG. */
+int dcgp_greedy_variance(dcgp_ctx* ctx, const double* X, long n, int d, int k, int kernel_type, double variance, double p1, double p2,
+                         const double* ard_lengthscales, double min_variance, int32_t* rows_out, double* trace_out,
+                         double* residual_out, double* factor_out, int* n_greedy_out);
 
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI ------------------------------------------ */
 /* Side effect of the two set-up calls below: RCCL prints a version banner to stdout the first time; while the call runs the process's
@@ -732,6 +751,9 @@ int dcgp_allreduce_sum_f64(dcgp_ctx* ctx, double* buf_dev, int n);
  * prove it: closed != 0 -- every such all-reduce enqueued from now on first waits (at most ~4 s) for the gate; 0 -- opens and removes it.
  * main_idle_out (may be NULL): bit 0 -- the ctx's main stream has drained (hipStreamQuery), bit 1 -- the comm stream has. */
 int dcgp_debug_comm_gate(dcgp_ctx* ctx, int closed, int* main_idle_out);
+/* `count` empty launches of `wgs` workgroups, each behind the one before on the ctx's stream; *ms_out = their time by HIP events: what the
+ * kernel boundaries of dcgp_greedy_variance's pivot loop cost by themselves (tools/inducing_init_time.py). */
+int dcgp_debug_empty_launches(dcgp_ctx* ctx, int count, int wgs, double* ms_out);
 /* Device buffer of 8 x 4 x 16 x 16 int64 into which the one-launch conv layer kernel (csrc/conv_fused.hip) stamps the shader
  * clock at its phase boundaries (8 sampled workgroups x 4 strips of a persistent one x 16 waves x 16 stamps = 8192 words); NULL switches it off (tools/fused_trace.py). */
 int dcgp_debug_set_fused_trace(dcgp_ctx* ctx, long long* buf_dev);
