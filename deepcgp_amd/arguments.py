@@ -41,6 +41,8 @@ FLAGS = (
     ("--freeze-mixing", None, False, "keep the mixing matrices of --latent-gps at their initial values"),
     ("--load-model", str, None, "checkpoint (.npy, reference key set) to start from"),
     ("--keep-optimizer", None, False, "write the optimiser's state (Adam moments, step count, minibatch generator) beside every checkpoint as <name>.opt.npz; with --load-model X, continue from X.opt.npz: the resumed run is the interrupted one, bit for bit"),
+    ("--reselect-every", int, 0, "every this many periods of --test-every, before the period's steps, choose every layer's inducing patches again (greedy conditional variance on what the layer receives now, under its trained kernel) and project q(u) onto them; 0 = off"),
+    ("--reselect-images", int, 1000, "training images a re-selection propagates to cut its candidates from"),
     ("--clip-norm", float, 0.0, "clip every Adam / SGD step's gradient to this global norm on the device and log the period's mean pre-clip norm (grad_norm); 0 = off"),
 )
 REQUIRED = ("--name",)
@@ -137,6 +139,26 @@ def parse_clip_norm(flags):
     if not value >= 0.0:
         raise ValueError("--clip-norm: must be >= 0 (0 = off), got %r" % (value,))
     return value
+
+
+def parse_reselect(flags):
+    """(``--reselect-every``, ``--reselect-images``) as ints: (0, 1000) when the flags are absent; 0 periods = off.  A negative period count or
+    fewer than one image raises ValueError naming the flag."""
+    every = getattr(flags, "reselect_every", 0)
+    images = getattr(flags, "reselect_images", 1000)
+    every, images = int(0 if every is None else every), int(1000 if images is None else images)
+    if every < 0:
+        raise ValueError("--reselect-every: must be >= 0 (0 = off), got %d" % every)
+    if images < 1:
+        raise ValueError("--reselect-images: must be >= 1, got %d" % images)
+    return every, images
+
+
+def reselect_due(every, global_step, test_every):
+    """Whether the period that starts at ``global_step`` begins with a re-selection: its index ``global_step // test_every`` is a positive
+    multiple of ``every`` (never the first period: the initialisation has just chosen the patches)."""
+    period = int(global_step) // int(test_every)
+    return every > 0 and period > 0 and period % every == 0
 
 
 def train_steps(flags):

@@ -167,6 +167,8 @@ _SIGS = {
                              _i, _i, _i, _i, _d, _i, _vp, C.c_long, _vp, C.c_long, C.c_long, _i],
     "dcgp_kmeans": [_vp, _vp, C.c_long, _i, _i, _vp, _i, _d, _vp, _ip],
     "dcgp_greedy_variance": [_vp, _vp, C.c_long, _i, _i, _i, _d, _d, _d, _vp, _d, _vp, _vp, _vp, _vp, _ip],
+    "dcgp_cross_gram": [_vp, _vp, C.c_long, _vp, C.c_long, _i, _i, _d, _d, _d, _vp, _vp],
+    "dcgp_inducing_transfer": [_vp, _vp, _i, _vp, _i, _i, _i, _d, _d, _d, _vp, _d, _i, _vp, _vp, _i, _vp, _vp, _ip],
     "dcgp_debug_empty_launches": [_vp, _i, _i, _dp],
     "dcgp_debug_set_fused_trace": [_vp, _vp],
     "dcgp_debug_fused_plan": [_vp, _vp],

@@ -914,6 +914,107 @@ class DGP_Base:
         if self.student_t:
             self.likelihood.scale = float(pull(0, "likelihood_scale", ()))
 
+    # ---- re-selection of the inducing inputs during training -----------------------------------------
+    @staticmethod
+    def _reselect_rng(seed, stream):
+        """The generator of one draw of ``reselect_inducing``: stream 0 the images, 1 + li layer li's candidates.  Never the global one."""
+        return np.random.RandomState(np.array([int(seed) & 0xffffffff, int(stream)], np.uint32))
+
+    def _reselect_kernel(self, li):
+        """The kernel layer ``li`` selects under: a conv layer's base kernel, a patch head's scalar RBF, the dense head's ARD RBF."""
+        l = self.layers[li]
+        if li < len(self.layers) - 1:
+            return l.base_kernel
+        return l.kern.base_kernel if hasattr(l.kern, "base_kernel") else l.kern
+
+    def _reselect_inputs(self, X_rows, Fs):
+        """What every layer receives for the images ``X_rows``, from one propagation's samples ``Fs``: the image (layer 0) or the layer below's
+        sample as that layer's output image -- a mixed layer's emitted maps --, with the layer's own zero border; the dense head: flat rows."""
+        out = []
+        for li, l in enumerate(self.layers):
+            src = X_rows if li == 0 else Fs[li - 1][0]
+            head = li == len(self.layers) - 1
+            v = getattr(l.kern, "view", None) if head else l.view
+            if v is None:
+                out.append(np.ascontiguousarray(src.reshape(src.shape[0], -1), np.float64))
+                continue
+            img = np.asarray(src, np.float64).reshape(src.shape[0], v.input_size[0], v.input_size[1], v.feature_maps)
+            out.append(np.ascontiguousarray(v.pad(img)))
+        return out
+
+    def reselect_candidates(self, li, layer_input, seed, candidates=100):
+        """The candidates layer ``li`` selects from: ``candidates * M`` patches of its input drawn with the generator of (seed, li); the dense
+        head: the flat rows themselves."""
+        l = self.layers[li]
+        if layer_input.ndim == 2:
+            return layer_input
+        head = li == len(self.layers) - 1
+        f = (l.kern.view if head else l.view).filter_size
+        from .models import draw_patches
+        return np.ascontiguousarray(draw_patches(layer_input, int(candidates) * l.num_inducing, f, self._reselect_rng(seed, 1 + li)))
+
+    def reselect_inducing(self, layers=None, images=1000, seed=0, candidates=100, min_variance=JITTER):
+        """Choose the inducing inputs of ``layers`` (default: all) again, from what each layer receives NOW and under the kernel it has NOW,
+        and carry q(u) over.  ``images`` training images (drawn with a generator of ``seed``) go through one ``propagate(S=1, seed=seed)``;
+        per layer, ``candidates * M`` patches of its input (its flat rows for the dense head) are the candidates, ``kernels.greedy_variance``
+        picks M of them, and ``kernels.transfer_inducing`` projects q(u) onto them (q'(u') = int p(u' | u) q(u) du; a transfer is a projection,
+        also onto an unchanged Z).  All layers are computed from the one propagation, then written together: Z, q_mu, q_sqrt, on conv layers
+        the KL prior's patches too; ``sync_parameters`` (a kept factor chain is no longer valid); the Adam moments of those three groups of
+        those layers are zeroed, every other moment and the step count stay.  Fewer than M usable candidates: ValueError; a transfer that is
+        not positive definite: ``NotPositiveDefinite``; the model is unchanged either way.  Not with a shard set (multi-rank models).
+
+        Returns one dict per layer: ``layer``, ``rows`` (the candidates chosen), ``n_greedy``, ``trace_new`` (the candidates' Nystrom trace
+        under the new Z, the selection's last), ``trace_old`` (the same trace under the old Z, with K_uu's jitter), ``kl_before``,
+        ``kl_after`` (the layer's KL term)."""
+        from scipy.linalg import solve_triangular
+        from . import kernels as _k
+        if self.global_batch is not None or getattr(self._ctx or dev.get_context(), "nranks", 1) > 1:
+            raise NotImplementedError("reselect_inducing: not on a sharded (multi-rank) model")
+        n_layers = len(self.layers)
+        which = list(range(n_layers)) if layers is None else sorted(set(int(li) for li in layers))
+        if any(li < 0 or li >= n_layers for li in which):
+            raise ValueError("reselect_inducing: layers must be in 0 .. %d, got %r" % (n_layers - 1, layers))
+        if int(images) < 1 or int(candidates) < 1:
+            raise ValueError("reselect_inducing: images and candidates must be >= 1")
+        self._build()
+        self.pull_parameters()
+        n = self.X.shape[0]
+        idx = self._reselect_rng(seed, 0).choice(n, size=min(int(images), n), replace=False)
+        X_rows = self.X[idx]
+        Fs, _, _ = self.propagate(X_rows, S=1, seed=int(seed))
+        inputs = self._reselect_inputs(X_rows, Fs)
+        new, report = {}, []
+        for li in which:
+            l, kern = self.layers[li], self._reselect_kernel(li)
+            M = l.num_inducing
+            cand = self.reselect_candidates(li, inputs[li], seed, candidates)
+            if cand.shape[0] < M:
+                raise ValueError("reselect_inducing: layer %d has %d candidates for M = %d" % (li, cand.shape[0], M))
+            Z_old = np.ascontiguousarray(l.feature.Z, np.float64)
+            Z_new, info = _k.greedy_variance(cand, M, kern, min_variance=min_variance, return_info=True)
+            q_mu, q_sqrt = _k.transfer_inducing(Z_old, Z_new, kern, l.q_mu, l.q_sqrt, white=l.white, jitter=JITTER)
+            A = solve_triangular(np.linalg.cholesky(kern._gram(Z_old, JITTER)), _k.cross_gram(Z_old, cand, kern), lower=True)
+            kdiag = kern._gram(cand[:1], 0.0)[0, 0]      # the Gram matrix's own diagonal: a constant of the kernel
+            new[li] = (Z_new, q_mu, q_sqrt)
+            report.append({"layer": li, "rows": info["rows"], "n_greedy": int(info["n_greedy"]), "trace_new": float(info["trace"][-1]),
+                           "trace_old": float(cand.shape[0] * kdiag - np.sum(A * A)), "kl_before": float(l.KL())})
+        # nothing has been written so far: every selection and transfer went through
+        for li, (Z_new, q_mu, q_sqrt) in new.items():
+            l = self.layers[li]
+            l.feature.Z, l.q_mu, l.q_sqrt = Z_new, q_mu, q_sqrt
+            if li < n_layers - 1:
+                l.Z_prior = np.array(Z_new, np.float64)
+                l._build_prior_cholesky()
+        self.sync_parameters()
+        L, ctx = dev.lib(), self._ctx
+        for key, li, name, shape in self._optimizer_groups():
+            if li in new and name in ("Z", "q_mu", "q_sqrt") and key.startswith("layers/"):
+                zero = np.zeros(shape, np.float64)
+                ctx._check(L.dcgp_model_set_adam_state(self._model, li, name.encode(), zero.ctypes.data, zero.ctypes.data, zero.size))
+        for entry in report:
+            entry["kl_after"] = float(self.layers[entry["layer"]].KL())
+        return report
+
     def propagate(self, X, full_cov=False, S=1, zs=None, seed=0):
         """(Fs, Fmeans, Fvars): per layer S x N x D_l arrays (doubly_stochastic_dgp DGP_Base.propagate); full_cov=True: see
         ``_propagate_full_cov`` (Fvars S x N x N x D_l)."""

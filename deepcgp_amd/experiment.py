@@ -6,6 +6,7 @@ A period of Adam steps is ONE device call (``DGP_Base.train_run``) on a training
 ``--test-shift`` / ``--test-flip`` / ``--test-views`` score the test set over shifted and mirrored views (test-time augmentation).
 ``--keep-optimizer`` writes the optimiser's state beside every checkpoint and, with ``--load-model``, continues from it: the resumed run is the
 interrupted one bit for bit.  ``--clip-norm`` clips every Adam / SGD step's gradient by its global norm on the device.
+``--reselect-every N`` starts every N-th period by choosing the inducing patches again from what each layer receives now and carrying q(u) over.
 
     python -m deepcgp_amd.experiment --name run --data digits.npz -M 16,16 --feature-maps 2 --filter-sizes 3,3 --strides 1,1
 """
@@ -14,7 +15,7 @@ import os
 import numpy as np
 
 from . import utils
-from .arguments import default_parser, parse_augmentation, parse_clip_norm, parse_test_views, train_steps
+from .arguments import default_parser, parse_augmentation, parse_clip_norm, parse_reselect, parse_test_views, reselect_due, train_steps
 from .models import (ModelBuilder, index_table, learning_rate, lr_table, restore_optimizer_state, save_model_parameters, save_optimizer_state,
                      train)
 
@@ -29,6 +30,7 @@ class Experiment(object):
         self.test_views = parse_test_views(flags)         # --test-shift / --test-flip / --test-views: None = the test images as they are
         self.clip_norm = parse_clip_norm(flags)           # --clip-norm: 0.0 = off (no call into the model, no logger)
         self.keep_optimizer = bool(getattr(flags, "keep_optimizer", False))
+        self.reselect_every, self.reselect_images = parse_reselect(flags)     # --reselect-every: 0 = off (no call into the model)
         self._period_norms = np.zeros(0)                  # pre-clip gradient norms of the period that just ended (--clip-norm)
         self._load_data()
         self._setup_model()
@@ -42,9 +44,20 @@ class Experiment(object):
         self.log.close()
 
     def train_step(self):
+        self._reselect()
         self._optimize()
         self._log_step()
         self._save_model_parameters()
+
+    def _reselect(self):
+        """--reselect-every N: every N-th period (never the first) starts by choosing the inducing patches again and carrying q(u) over
+        (``DGP_Base.reselect_inducing``), whatever the optimiser.  The seed follows the step count, so a resumed run re-selects as the
+        interrupted one would have."""
+        if not reselect_due(getattr(self, "reselect_every", 0), self.global_step, self.flags.test_every):
+            return
+        for r in self.model.reselect_inducing(images=self.reselect_images, seed=self.seed + self.global_step):
+            print("step {}: layer {} re-selected: {} of {} greedy, Nystrom trace {:.6g} -> {:.6g}, KL {:.6g} -> {:.6g}".format(
+                self.global_step, r["layer"], r["n_greedy"], len(r["rows"]), r["trace_old"], r["trace_new"], r["kl_before"], r["kl_after"]))
 
     def _log_step(self):
         entry = self.log.write_entry(self.model)

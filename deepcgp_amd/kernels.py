@@ -440,6 +440,64 @@ def _greedy_patches(NHWC_X, M, patch_size, base_kernel, min_variance):
     return greedy_variance(sample, M, base_kernel, min_variance=min_variance, return_info=True)
 
 
+def _rows_for(name, A, base_kernel):
+    A = np.ascontiguousarray(A, np.float64)
+    if A.ndim != 2 or A.shape[0] < 1:
+        raise ValueError("%s must be [n, d] with n >= 1, got shape %r" % (name, A.shape))
+    if A.shape[1] != base_kernel.input_dim:
+        raise ValueError("expected inputs of length %d, got %d" % (base_kernel.input_dim, A.shape[1]))
+    return A
+
+
+def cross_gram(A, B, base_kernel):
+    """k(a_i, b_j), [m, n], for A [m, d] and B [n, d] under ``base_kernel`` -- an ``RBF`` (scalar or ``ARD=True``), ``ArcCosine``, ``Matern32``
+    or ``Matern52`` (dcgp_cross_gram).  Every entry is the kernel's off-diagonal form: no jitter, also where a row of B equals a row of A."""
+    kind, variance, p1, p2, ard = _greedy_kernel_args(base_kernel)
+    A, B = _rows_for("A", A, base_kernel), _rows_for("B", B, base_kernel)
+    ctx = dev.get_context()
+    dA, dB, out = ctx.to_device(A), ctx.to_device(B), ctx.empty((A.shape[0], B.shape[0]))
+    dls = ctx.to_device(ard) if ard is not None else None
+    ctx._check(dev.lib().dcgp_cross_gram(ctx.handle, dA.ptr, A.shape[0], dB.ptr, B.shape[0], A.shape[1], kind, variance, p1, p2,
+                                         dls.ptr if dls else None, out.ptr))
+    return out.numpy()
+
+
+TRANSFER_FAILED = {1: "K(Z, Z)", 2: "K(Z_new, Z_new)"}      # dcgp_inducing_transfer's info[0]; 3 + r: S' of output r
+
+
+def transfer_inducing(Z, Z_new, base_kernel, q_mu, q_sqrt, white=False, jitter=JITTER):
+    """q(u) = N(q_mu, q_sqrt q_sqrt^T) at the inducing inputs ``Z`` [M, L] moved to ``Z_new`` [M', L]: the projection
+    q'(u') = int p(u' | u) q(u) du under ``base_kernel``'s prior (dcgp_inducing_transfer).  q_mu [M, R], q_sqrt [R, M, M] -> (q_mu' [M', R],
+    q_sqrt' [R, M', M']), lower triangular with exact zeros above a positive diagonal.  ``white``: both in whitened coordinates.
+
+    u and u' carry independent jitter, so the KL to the prior never rises (data processing), chol succeeds however small q_sqrt is -- and a
+    transfer onto an identical Z is a projection, not the identity.  A matrix that is not positive definite raises ``NotPositiveDefinite``
+    (``.which``: 1 K, 2 K_new, 3 + r the new covariance of output r); nothing is returned then and no device output was written."""
+    import ctypes as C
+    kind, variance, p1, p2, ard = _greedy_kernel_args(base_kernel)
+    Z, Zn = _rows_for("Z", Z, base_kernel), _rows_for("Z_new", Z_new, base_kernel)
+    q_mu, q_sqrt = np.ascontiguousarray(q_mu, np.float64), np.ascontiguousarray(q_sqrt, np.float64)
+    M, Mn = Z.shape[0], Zn.shape[0]
+    if q_mu.ndim != 2 or q_mu.shape[0] != M:
+        raise ValueError("q_mu must be [M, R] with M = %d, got shape %r" % (M, q_mu.shape))
+    R = q_mu.shape[1]
+    if q_sqrt.shape != (R, M, M):
+        raise ValueError("q_sqrt must be [R, M, M] = %r, got shape %r" % ((R, M, M), q_sqrt.shape))
+    ctx = dev.get_context()
+    dZ, dZn, dm, dS = ctx.to_device(Z), ctx.to_device(Zn), ctx.to_device(q_mu), ctx.to_device(q_sqrt)
+    dls = ctx.to_device(ard) if ard is not None else None
+    om, oS = ctx.empty((Mn, R)), ctx.empty((R, Mn, Mn))
+    info = (C.c_int * 2)(0, 0)
+    rc = dev.lib().dcgp_inducing_transfer(ctx.handle, dZ.ptr, M, dZn.ptr, Mn, Z.shape[1], kind, variance, p1, p2, dls.ptr if dls else None,
+                                          float(jitter), int(bool(white)), dm.ptr, dS.ptr, R, om.ptr, oS.ptr, info)
+    try:
+        ctx._check(rc, C.c_int(info[1]))
+    except dev.NotPositiveDefinite as e:
+        e.which = info[0]
+        raise
+    return om.numpy(), oS.numpy()
+
+
 class InducingPoints:
     """gpflow.features.InducingPoints(Z) -- the dense head's feature (conv_gp/models.py:168)."""
 

@@ -732,6 +732,28 @@ int dcgp_kmeans(dcgp_ctx* ctx, const double* X, long n, int d, int k, const int3
 int dcgp_greedy_variance(dcgp_ctx* ctx, const double* X, long n, int d, int k, int kernel_type, double variance, double p1, double p2,
                          const double* ard_lengthscales, double min_variance, int32_t* rows_out, double* trace_out,
                          double* residual_out, double* factor_out, int* n_greedy_out);
+/* out [m, n] = k(a_i, b_j) for A [m, d], B [n, d] (device, row-major) under a base kernel; kernel_type / variance / p1 / p2 / ard_lengthscales
+ * as dcgp_greedy_variance.  Every entry is the OFF-diagonal form of the kernel (what dcgp_kuu_* write off their diagonal): no jitter and no
+ * diagonal constant, also where a row of B equals a row of A.  x.z, |x|^2 and |z|^2 are accumulated by one chain over d, so coincident rows
+ * are at distance exactly 0.  m <= 32 * 65535, n <= 2^31 - 1, d <= 4096.  The ARD lengthscales are not read back: non-positive ones give
+ * non-finite entries. */
+int dcgp_cross_gram(dcgp_ctx* ctx, const double* A, long m, const double* B, long n, int d, int kernel_type, double variance, double p1,
+                    double p2, const double* ard_lengthscales, double* out);
+/* q(u) = N(q_mu, q_sqrt_r q_sqrt_r^T) at inducing inputs Z [M, L] projected onto Z_new [M_new, L]: q'(u') = int p(u' | u) q(u) du under the
+ * base kernel's prior.  With K = k(Z, Z) + jitter I = L L^T, Kc = k(Z, Z_new) (dcgp_cross_gram) and Kn = k(Z_new, Z_new) + jitter I = L' L'^T
+ * (K, Kn as dcgp_kuu_* evaluate them):  B = inv(L) Kc, P = inv(L)^T B, out_q_mu = P^T q_mu, T_r = q_sqrt_r^T P,
+ * out_q_sqrt_r = chol(Kn - B^T B + T_r^T T_r): lower triangular, exact zeros above the diagonal, positive diagonal.  u and u' carry
+ * independent jitter (the joint prior is positive definite and Kn - B^T B keeps its smallest eigenvalue near 2 jitter), so a transfer onto the
+ * same Z is a projection, not the identity.  white != 0: q_mu / q_sqrt arrive and leave in whitened coordinates (L q_mu, L q_sqrt_r are
+ * projected; inv(L') of the results is returned -- a product of lower-triangular factors).  q_mu [M, R], q_sqrt [R, M, M] (lower triangle read),
+ * out_q_mu [M_new, R], out_q_sqrt [R, M_new, M_new], all device.  M, M_new <= 1024, R <= 64, L <= 4096.
+ * Everything is enqueued on the ctx's stream and formed in scratch that lives inside the call; the outputs are written by the last two
+ * launches, which read the factorisations' status on the device, and the only host synchronisation is the read of that status.  A matrix
+ * that is not positive definite: DCGP_ERR_NOT_PD, the outputs untouched; info_host [2] (may be NULL): [0] = 0, or 1 for K, 2 for Kn,
+ * 3 + r for S'_r (the first that failed); [1] = its 1-based failing column.  No atomics: the same bits every run. */
+int dcgp_inducing_transfer(dcgp_ctx* ctx, const double* Z, int M, const double* Z_new, int M_new, int L, int kernel_type, double variance,
+                           double p1, double p2, const double* ard_lengthscales, double jitter, int white, const double* q_mu,
+                           const double* q_sqrt, int R, double* out_q_mu, double* out_q_sqrt, int* info_host);
 
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI ------------------------------------------ */
 /* Side effect of the two set-up calls below: RCCL prints a version banner to stdout the first time; while the call runs the process's
