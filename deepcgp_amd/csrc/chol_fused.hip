@@ -17,8 +17,10 @@
 // (Handing panels between the workgroups of ONE launch, through coherent flags and payloads instead of launch boundaries, was built,
 // measured slower and removed: DESIGN.md, "One launch for the whole chain".)
 #include "chol_dev.h"
+#include "chain_plan.h"
 
 using namespace chol_dev;
+static_assert(chain_plan::kNB == NB, "chain_plan.h plans the panels of this kernel");
 
 // phase timestamps for tools/chol_trace.hip (compiled out of the library)
 #ifdef CHOL_TRACE
@@ -143,20 +145,11 @@ __device__ __forceinline__ void rhs_tile(const RlArgs& a, const int b, const int
   const ChainRhs d = a.rhs[b];
   const int Mp = a.Mp, ld = a.ld, np = a.np, p = a.rhs_p;
   // decode: R blocks of rhs_nq items (Lq_q), then alpha's
-  const int tpw = a.rhs_tpw, ng = a.rhs_nt > 0 ? (a.rhs_nt + tpw - 1) / tpw : 1;   // row tiles per workgroup (1 or 2), row groups
-  int q, ct, g;
-  bool final_only = false;
-  if (idx < d.R * a.rhs_nq) {
-    q = idx / a.rhs_nq;
-    const int rem = idx % a.rhs_nq;
-    if (p >= 0 && rem < (p + 1) * ng) { ct = rem / ng; g = rem % ng; }
-    else { ct = p + 1; g = 0; final_only = true; }                     // (only enumerated in the last launch)
-  } else {
-    const int rem = idx - d.R * a.rhs_nq;
-    q = d.R; ct = 0; g = rem;
-    if (p < 0) { if (rem != 0 || !a.rhs_last) return; final_only = true; }
-    else if (rem >= ng) return;
-  }
+  const int tpw = a.rhs_tpw, ng = chain_plan::rhs_groups(a.rhs_nt, tpw);   // row tiles per workgroup (1 or 2), row groups
+  const chain_plan::RhsItem item = chain_plan::decode_rhs(idx, d.R, a.rhs_nq, p, a.rhs_last, ng);
+  if (!item.live) return;
+  const int q = item.q, ct = item.ct, g = item.g;
+  const bool final_only = item.final_only;
   const bool is_alpha = q == d.R;
   const double* __restrict__ B = is_alpha ? d.qmu : (d.Lq ? d.Lq + (long)q * Mp * ld : nullptr);
   if (!B) return;
@@ -169,7 +162,8 @@ __device__ __forceinline__ void rhs_tile(const RlArgs& a, const int b, const int
   double* __restrict__ sq = d.sums + (long)q * (np * (np + 1) / 2);
   const double* __restrict__ Lout = a.Lout + (long)b * Mp * ld;
   const int jl = 32 * (np - 1), nbl = Mp - jl;                                     // the last panel
-  const int r0[2] = {j + 32 + 64 * tpw * g, j + 32 + 64 * tpw * g + 64};            // this group's row tiles
+  const int t0 = chain_plan::rhs_first_tile(g, tpw);
+  const int r0[2] = {j + 32 + 64 * t0, j + 32 + 64 * t0 + 64};                     // this group's row tiles
   const bool live[2] = {lagged && r0[0] < Mp, lagged && tpw == 2 && r0[1] < Mp};
   const bool cont = live[0] && a.rhs_last && g == 0;                               // the first row tile holds the last panel's rows (r0 == jl)
   const bool have_x = a.Xin != nullptr;
@@ -331,23 +325,10 @@ __global__ __launch_bounds__(256, 2) void chol_rl_kernel(RlArgs a) {
   // (the look-ahead workgroup is the launch's critical path and issue-bound: the other workgroups of the chain sharing its SIMDs yield to it)
   int b = blockIdx.y, bx = blockIdx.x;
   if (a.iso_per > 0) {
-    const int lin = blockIdx.x, slot = lin >> 3;
-    const int xcd = (lin + 1) & 7;   // (XCD 7 reads as 0: see iso_per)
-    if (xcd == 0) {
-      if (slot >= a.batch || a.la_idx < 0) return;
-      b = slot; bx = a.la_idx;
-    } else {
-      // the right-hand sides first (the longest workgroups beside the look-ahead ones), then the trailing / inverse tiles
-      const int item = slot * 7 + xcd - 1, nla = a.la_idx >= 0 ? 1 : 0;
-      const int rhs_per = a.rhs ? a.iso_per + nla - a.rhs_base : 0, chain_per = a.iso_per - rhs_per;
-      if (item < a.batch * rhs_per) { b = item / rhs_per; bx = a.rhs_base + item % rhs_per; }
-      else {
-        const int it = item - a.batch * rhs_per;
-        if (it >= a.batch * chain_per) return;
-        b = it / chain_per; bx = it % chain_per;
-        if (nla && bx >= a.la_idx) ++bx;
-      }
-    }
+    // the look-ahead workgroups on one XCD, the right-hand sides and then the trailing / inverse tiles on the seven others (chain_plan.h)
+    const chain_plan::Wg w = chain_plan::decode_iso(blockIdx.x, a.batch, a.iso_per, a.la_idx, a.rhs != nullptr, a.rhs_base);
+    if (!w.live) return;
+    b = w.b; bx = w.bx;
   }
   if (bx == a.la_idx) __builtin_amdgcn_s_setprio(3);
   else __builtin_amdgcn_s_setprio(2);
@@ -686,44 +667,26 @@ int factor_inverse_batched(dcgp_ctx* ctx, double* const* d_A, double* const* d_L
   for (int j = 0; j < Mp; j += NB) {
     RlArgs a;
     a.A = d_A; a.Lout = Lout; a.Y = Y; a.Linv = d_Linv; a.LinvT = d_Linv ? d_LinvT : nullptr; a.Mp = Mp; a.ld = ld; a.j = j; a.info = d_info;
-    const int below = Mp - (j + NB);
-    a.nt = below > 0 ? (below + 63) / 64 : 0;
-    a.nT = a.nt * (a.nt + 1) / 2;
-    a.nct = d_Linv ? (min(j + NB, Mp) + 63) / 64 : 0;
-    const int nY = d_Linv ? (1 + a.nt) * a.nct : 0;
-    int gx = a.nT + nY;
-    const int jp = j / NB;
-    if (Xla) {
-      const size_t slot = (size_t)batch * 2 * NB * NB;
-      if (jp > 0) a.Xin = Xla + (size_t)jp * slot;
-      if (jp + 1 < np_la) { a.Xnext = Xla + (size_t)(jp + 1) * slot; a.la_idx = gx; ++gx; }
-    }
+    // every number of the launch is plan_launch's (chain_plan.h), which the CPU suite reaches through dcgp_debug_plan_chain
+    chain_plan::Query q;
+    q.Mp = Mp; q.batch = batch; q.jp = j / NB; q.has_inv = d_Linv != nullptr; q.rides = d_rhs != nullptr; q.max_R = max_R;
+    q.alone = mode.alone; q.no_iso = ctx->opt.chain_no_iso != 0;
+    const chain_plan::Launch l = chain_plan::plan_launch(q);
+    a.nt = l.nt; a.nT = l.nT; a.nct = l.nct; a.la_idx = l.la_idx;
+    const size_t slot = (size_t)batch * 2 * NB * NB;
+    if (l.has_xin) a.Xin = Xla + (size_t)q.jp * slot;
+    if (l.has_xnext) a.Xnext = Xla + (size_t)(q.jp + 1) * slot;
     if (d_rhs) {   // the right-hand sides: panel jp - 1 here, and the last panel too in the last launch
-      const bool last = jp == np_la - 1;
-      a.batch = batch; a.np = np_la; a.Xall = Xla;
-      if (jp == 0 && Xla) a.Xself = Xla;
-      if (jp > 0 || last) {
-        a.rhs = d_rhs; a.rhs_p = jp - 1; a.rhs_last = last ? 1 : 0;
-        const int below_p = jp > 0 ? Mp - NB * jp : 0;                 // rows below the lagged panel
-        a.rhs_nt = below_p > 0 ? (below_p + 63) / 64 : 0;
-        // one 64-row tile per workgroup while the launch stays inside the resident slots (~400 beside the chain's own tiles), else two
-        const long w1 = (long)batch * (max_R * jp + 1) * (a.rhs_nt > 0 ? a.rhs_nt : 1);
-        a.rhs_tpw = w1 > 400 ? 2 : 1;
-        const int ng = a.rhs_nt > 0 ? (a.rhs_nt + a.rhs_tpw - 1) / a.rhs_tpw : 1;   // row groups (rhs_tile)
-        a.rhs_nq = jp * ng + (last ? 1 : 0);                           // items per Lq_q: (column tile <= jp - 1, group), + the last panel's diagonal tile
-        a.rhs_base = gx > 0 ? gx : 1;
-        gx = a.rhs_base + max_R * a.rhs_nq + (jp > 0 ? ng : 1);        // ... + alpha's
+      a.np = l.np; a.Xall = Xla;
+      if (l.has_xself) a.Xself = Xla;
+      if (l.has_rhs) {
+        a.rhs = d_rhs; a.rhs_p = l.rhs_p; a.rhs_last = l.rhs_last; a.rhs_nt = l.rhs_nt; a.rhs_tpw = l.rhs_tpw; a.rhs_nq = l.rhs_nq; a.rhs_base = l.rhs_base;
       }
     }
+    a.batch = batch; a.iso_per = l.iso_per;
     // gx == 0: last panel of a plain potrf -- only L_jj is left; one workgroup factors and publishes it
-    a.gx_trace = gx > 0 ? gx : 1;
-    if (Xla && !ctx->opt.chain_no_iso && mode.alone) {   // the look-ahead workgroups alone on one XCD (RlArgs::iso_per)
-      a.batch = batch;
-      a.iso_per = (gx > 0 ? gx : 1) - (a.la_idx >= 0 ? 1 : 0);
-      const int items = batch * a.iso_per, slots = (items + 6) / 7;
-      hipLaunchKernelGGL(chol_rl_kernel, dim3(8 * (slots > batch ? slots : batch)), dim3(256), 0, ctx->stream, a);
-    } else
-    hipLaunchKernelGGL(chol_rl_kernel, dim3(gx > 0 ? gx : 1, batch), dim3(256), 0, ctx->stream, a);
+    a.gx_trace = l.gx > 0 ? l.gx : 1;
+    hipLaunchKernelGGL(chol_rl_kernel, dim3(l.grid_x, l.grid_y), dim3(256), 0, ctx->stream, a);
     LAUNCH_CHECK(ctx);
   }
   if (defer_finish) return DCGP_OK;   // inv(L) is complete; the caller copies the factor back (factor_finish_batched) off its critical path
@@ -737,5 +700,49 @@ int factor_finish_batched(dcgp_ctx* ctx, double* const* d_A, int batch, int Mp, 
   if (it == ctx->ws.end()) return ctx_fail(ctx, DCGP_ERR_ARG, "factor_finish: no factorisation to finish");
   hipLaunchKernelGGL(chol_finish_kernel, dim3(Mp, batch), dim3(128), 0, ctx->stream, d_A, (const double*)it->second.first, Mp, ld);
   LAUNCH_CHECK(ctx);
+  return DCGP_OK;
+}
+
+// debugging aid (tests, no device needed): the layout of launch jp of a chain from a flat query, and what every workgroup of its grid decodes to; field
+// orders in include/dcgp.h.  The same plan_launch / decode_iso / decode_rhs that factor_inverse_batched and chol_rl_kernel call.
+extern "C" int dcgp_debug_plan_chain(const long long* query, int n_query, const long long* R_of, int n_R, long long* plan, int n_plan, long long* wgs,
+                                     long n_wgs) {
+  using chain_plan::Launch;
+  using chain_plan::Query;
+  if (!query || !plan || n_query != Query::kFields || n_plan != Launch::kFields) return DCGP_ERR_ARG;
+  Query q;
+  q.Mp = (int)query[0]; q.batch = (int)query[1]; q.jp = (int)query[2]; q.has_inv = query[3] != 0; q.rides = query[4] != 0; q.max_R = (int)query[5];
+  q.alone = query[6] != 0; q.no_iso = query[7] != 0;
+  if (q.Mp <= 0 || q.batch <= 0 || q.jp < 0 || q.jp >= chain_plan::panels(q.Mp) || q.max_R < 0) return DCGP_ERR_ARG;
+  if (q.rides && (!q.has_inv || q.Mp > kChainRhsMaxMp)) return DCGP_ERR_ARG;   // (factor_inverse_batched refuses these)
+  const Launch l = chain_plan::plan_launch(q);
+  const long long flat[Launch::kFields] = {l.np, l.j, l.nt, l.nT, l.nct, l.la_idx, l.has_xla, l.has_xin, l.has_xnext, l.has_xself, l.has_rhs, l.rhs_p,
+                                           l.rhs_last, l.rhs_nt, l.rhs_tpw, l.rhs_ng, l.rhs_nq, l.rhs_base, l.gx, l.iso_per, l.grid_x, l.grid_y,
+                                           l.iso_per > 0, (long long)l.grid_x * l.grid_y};
+  for (int e = 0; e < Launch::kFields; ++e) plan[e] = flat[e];
+  if (!wgs) return DCGP_OK;
+  if (n_wgs != (long)l.grid_x * l.grid_y) return DCGP_ERR_ARG;
+  if (l.has_rhs && (!R_of || n_R != q.batch)) return DCGP_ERR_ARG;
+  for (int y = 0; y < l.grid_y; ++y)
+    for (int x = 0; x < l.grid_x; ++x) {
+      long long* o = wgs + ((long)y * l.grid_x + x) * 8;
+      for (int e = 0; e < 8; ++e) o[e] = 0;
+      o[0] = o[1] = -1;
+      int b = y, bx = x;   // chol_rl_kernel's own walk from here on
+      if (l.iso_per > 0) {
+        const chain_plan::Wg w = chain_plan::decode_iso(x, q.batch, l.iso_per, l.la_idx, l.has_rhs != 0, l.rhs_base);
+        if (!w.live) continue;
+        b = w.b; bx = w.bx;
+      }
+      o[0] = b; o[1] = bx;
+      if (l.has_rhs && bx >= l.rhs_base) {
+        const chain_plan::RhsItem it = chain_plan::decode_rhs(bx - l.rhs_base, (int)R_of[b], l.rhs_nq, l.rhs_p, l.rhs_last, l.rhs_ng);
+        if (!it.live) continue;
+        o[2] = 5; o[3] = it.q; o[4] = it.ct; o[5] = it.g; o[6] = it.final_only; o[7] = chain_plan::rhs_first_tile(it.g, l.rhs_tpw);
+      } else if (bx == l.la_idx) o[2] = 3;
+      else if (l.nT == 0 && l.nct == 0) o[2] = 4;
+      else if (bx < l.nT) { o[2] = 1; o[4] = bx; }
+      else { o[2] = 2; o[3] = (bx - l.nT) / l.nct - 1; o[4] = (bx - l.nT) % l.nct; }
+    }
   return DCGP_OK;
 }

@@ -463,7 +463,7 @@ struct ChainMode {
   bool may_ride = true;   // right-hand sides may ride the chain: not beside a patch sweep (a head-first model: 4250 -> 4200 steps/s).  A property of the
                           // model, not of the step's mode: synchronous and in-flight steps take the same route (bit-identical)
 };
-// left-looking fused Cholesky (+ inverse of the factor when d_Linv != nullptr): one launch per 32-wide panel.
+// right-looking fused Cholesky (+ inverse of the factor when d_Linv != nullptr): one launch per 32-wide panel.
 // d_rhs != nullptr (device array, one entry per matrix; max_R = the largest R among them): right-hand sides ride the chain.
 int factor_inverse_batched(dcgp_ctx* ctx, double* const* d_A, double* const* d_Linv, double* const* d_LinvT, int batch,
                            int Mp, int ld, int* d_info, bool defer_finish = false, const ChainRhs* d_rhs = nullptr, int max_R = 0, ChainMode mode = ChainMode());

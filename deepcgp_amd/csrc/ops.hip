@@ -555,4 +555,54 @@ int dcgp_gauss_kl(dcgp_ctx* ctx, const double* q_mu, const double* q_sqrt, const
   return DCGP_OK;
 }
 
+// debugging aid (tests): the factorisation chain of a model step on caller buffers -- a FactorGroup filled the way build_groups (model.hip) fills one, run()
+// and finish().  Arguments in include/dcgp.h.  No route decision is taken here: chain_can_ride and the ctx's options decide as they do for a model.
+int dcgp_debug_factor_chain(dcgp_ctx* ctx, double* A, double* Linv, double* LinvT, int batch, int Mp, const long long* desc, int n_desc, int flags,
+                            const long long* snap, int n_snap, const double* A_again, int* info_host) {
+  ARG_CHECK(ctx && A && batch > 0 && Mp > 0 && Mp % 16 == 0 && info_host && (flags & ~7) == 0, "debug_factor_chain: bad args");
+  ARG_CHECK((desc ? n_desc == batch * 7 : n_desc == 0) && (snap ? n_snap >= 0 && n_snap % 3 == 0 : n_snap == 0), "debug_factor_chain: bad descriptor / snapshot length");
+  ARG_CHECK(Linv || (!LinvT && !desc), "debug_factor_chain: inv(L)^T and right-hand sides need inv(L)");
+  ChainMode mode;
+  mode.alone = (flags & 1) != 0; mode.may_ride = (flags & 2) != 0;
+  const bool defer_finish = (flags & 4) != 0;
+  const size_t mm = (size_t)Mp * Mp;
+  struct Holder { FactorGroup fg; ~Holder() { fg.release(); } } h;
+  FactorGroup& fg = h.fg;
+  fg.Mp = Mp;
+  for (int b = 0; b < batch; ++b) {
+    ChainRhs r{};
+    if (desc) {
+      const long long* d = desc + (size_t)b * 7;
+      r.R = (int)d[0]; r.Rp = (int)d[1];
+      r.Lq = (const double*)(uintptr_t)d[2]; r.qmu = (const double*)(uintptr_t)d[3];
+      r.G = (double*)(uintptr_t)d[4]; r.alpha = (double*)(uintptr_t)d[5]; r.sums = (double*)(uintptr_t)d[6];
+      ARG_CHECK(r.R >= 0 && r.Rp >= 0 && r.Rp <= 32 && (!(r.Lq || r.qmu) || (r.sums && r.Rp > 0)), "debug_factor_chain: bad descriptor");
+    }
+    fg.K.push_back(A + b * mm);
+    fg.Linv.push_back(Linv ? Linv + b * mm : nullptr);
+    fg.LinvT.push_back(LinvT ? LinvT + b * mm : nullptr);
+    fg.rhs.push_back(r);
+    if (r.Lq || r.qmu) { fg.ride = true; fg.max_R = r.R > fg.max_R ? r.R : fg.max_R; }
+  }
+  if (fg.ride && !chain_can_ride(ctx, Mp, mode))   // (a model takes prep_solve behind the chain then; nothing here would form G / alpha)
+    return ctx_fail(ctx, DCGP_ERR_ARG, "debug_factor_chain: right-hand sides cannot ride this route");
+  for (int pass = 0; pass < (A_again ? 2 : 1); ++pass) {
+    if (pass == 1) DCGP_TRY(d2d(ctx, A, A_again, batch * mm));
+    if (Linv) {
+      DCGP_TRY(fg.run(ctx, defer_finish, mode));
+    } else {   // a plain factor: FactorGroup::run always asks for the inverse, so the chain is called on the group's tables directly
+      DCGP_TRY(fg.upload(ctx));
+      DCGP_TRY(factor_inverse_batched(ctx, fg.dK, nullptr, nullptr, batch, Mp, Mp, fg.d_info, defer_finish, nullptr, 0, mode));
+      fg.deferred = defer_finish;
+    }
+    if (pass == 0)
+      for (int s = 0; s < n_snap; s += 3)
+        HIP_TRY(ctx, hipMemcpyAsync((void*)(uintptr_t)snap[s], (const void*)(uintptr_t)snap[s + 1], (size_t)snap[s + 2], hipMemcpyDeviceToDevice, ctx->stream));
+    DCGP_TRY(fg.finish(ctx));
+    HIP_TRY(ctx, hipMemcpyAsync(info_host + (size_t)pass * batch, fg.d_info, batch * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  return DCGP_OK;
+}
+
 }  // extern "C"

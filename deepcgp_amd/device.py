@@ -174,6 +174,8 @@ _SIGS = {
     "dcgp_debug_fused_plan": [_vp, _vp],
     "dcgp_debug_plan_layer_launch": [_vp, _i, _vp, _i],
     "dcgp_debug_plan_gemm": [_vp, _i, _vp, _i],
+    "dcgp_debug_plan_chain": [_vp, _i, _vp, _i, _vp, _i, _vp, C.c_long],
+    "dcgp_debug_factor_chain": [_vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _i, _vp, _vp],
     "dcgp_debug_head_ride": [_vp, _vp],
     "dcgp_debug_plan_head_ride": [_vp, _i, _vp, _i, C.c_longlong, _vp, _i],
     "dcgp_debug_head_tail": [_vp, _vp],

@@ -804,6 +804,32 @@ int dcgp_debug_plan_layer_launch(const long long* query, int n_query, long long*
  *   template switches), grid x, y, z, doubles of the partial buffer, workgroups of the reduction behind it (both 0 unless split), dynamic LDS bytes}.
  * DCGP_ERR_ARG unless n_query == 24, n_plan == 17. */
 int dcgp_debug_plan_gemm(const long long* query, int n_query, long long* plan, int n_plan);
+/* How launch jp of the factorisation chain is laid out (csrc/chain_plan.h, plan_launch: the function factor_inverse_batched itself launches from) and what
+ * every workgroup of its grid decodes to (decode_iso, decode_rhs: the functions chol_rl_kernel itself calls), from integers alone: needs no ctx and no device.
+ * query[8] = {Mp, batch, jp, inv(L) is formed, right-hand sides ride, max_R (the largest R of the batch), ChainMode::alone, the ctx option chain_no_iso}.
+ * R_of[batch] = R of every matrix (read only where the launch carries right-hand-side items; may be NULL otherwise).
+ * plan[24] = {np, j, nt (64-row tiles below the panel), nT (trailing tiles), nct (64-column tiles of the inverse), la_idx (the look-ahead workgroup, -1: none),
+ *   the hand-over buffer of the diagonal blocks exists, this launch reads its block from it, leaves the next one in it, publishes block 0 into it,
+ *   the launch carries right-hand-side items, rhs_p (the lagged panel they apply, -1: none), rhs_last (they make the last panel final too), rhs_nt (64-row
+ *   tiles below the lagged panel), rhs_tpw (row tiles per workgroup, 1 or 2), row groups, rhs_nq (items per Lq_q), rhs_base (first right-hand-side
+ *   workgroup), gx (workgroups per matrix; 0: one is launched all the same), iso_per, grid x, grid y, the grid is the XCD-isolated 1-D one, its workgroups}.
+ * wgs (may be NULL: the plan only; else n_wgs == grid x * grid y) = [workgroup, blockIdx.y-major][8] = {matrix b, workgroup bx of its row (both -1: the
+ *   workgroup exits at once), kind (0: exits at once, 1: trailing tile, 2: inverse tile, 3: look-ahead, 4: the diagonal block alone, 5: right-hand-side
+ *   item), then for an inverse tile {row tile (-1: the panel's own rows), column tile}, for a right-hand-side item {q (== R: alpha), column tile ct, row
+ *   group g, final_only, the first 64-row tile below the lagged panel that the group updates}, for a trailing tile {0, its number in the lower triangle};
+ *   0 beyond}.
+ * DCGP_ERR_ARG unless n_query == 8 and n_plan == 24, for a jp beyond the matrix and for right-hand sides without inv(L) or beyond Mp = 256. */
+int dcgp_debug_plan_chain(const long long* query, int n_query, const long long* R_of, int n_R, long long* plan, int n_plan, long long* wgs, long n_wgs);
+/* The factorisation chain exactly as a model step runs it, on caller buffers (device pointers unless said otherwise): a factor group filled as a model
+ * fills one, its run() and finish().  A [batch][Mp][Mp] (Mp a multiple of 16, padded with the identity) is overwritten with the factors; Linv / LinvT
+ * [batch][Mp][Mp] or NULL (Linv == NULL: a plain factor).  desc (host, NULL or [batch][7]) = per matrix {R, Rp, Lq, qmu, G, alpha, sums} with the five device
+ * pointers as integers, 0 for none (csrc/common.h, ChainRhs: Lq [R][Mp][Mp], qmu / alpha [Mp][Rp], G [R][Mp][Mp], sums [R + 1][np (np + 1) / 2]).
+ * flags: bit 0 ChainMode::alone, bit 1 ChainMode::may_ride, bit 2 defer_finish.  snap (host, NULL or [n_snap / 3][3] = {destination, source, bytes}): device
+ * copies enqueued between run() and finish() of the first pass.  A_again (NULL or [batch][Mp][Mp]): the chain then runs a second time on the same group
+ * with A overwritten by it.  info_host [batch], or [2][batch] with A_again: 0 or the 1-based column at which a matrix turned out not positive definite.
+ * DCGP_ERR_ARG where a descriptor asks to ride and the mode or the ctx's options (no_rhs_ride) rule that out. */
+int dcgp_debug_factor_chain(dcgp_ctx* ctx, double* A, double* Linv, double* LinvT, int batch, int Mp, const long long* desc, int n_desc, int flags,
+                            const long long* snap, int n_snap, const double* A_again, int* info_host);
 /* Head rows riding the layer kernel's persistent launch (csrc/fused_plan.h, plan_head_ride; ctx option head_ride, 0: never).
  * dcgp_debug_head_ride: out2 = {head rows the ctx's most recent layer-kernel launch carried (0: none), launches of the ctx that carried any}.
  * dcgp_debug_plan_head_ride (no ctx, no device): the decision for the launch that `query` (as above) is planned as and

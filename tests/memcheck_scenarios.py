@@ -441,6 +441,17 @@ def run_operators(res):
         ctx._check(L.dcgp_trtri_lower(ctx.handle, dL.ptr, M, dX.ptr))
         res.add("chain M=%d" % M, (Kuu, Lc, dX.numpy()))
     res.check(ctx, "factorisation chain")
+    # the chain as a model step runs it, right-hand sides riding (tests/chain_cases.py): a full entry, a prior's sums-only entry and one that carries nothing at
+    # Mp = 48; six riding matrices at Mp = 256, two row tiles per workgroup -- the group's Yw, the diagonal blocks' hand-over buffer and the sums
+    import chain_cases as chain
+    for batch, M in (("b", 48), ("d6", 256)):
+        inp = chain.build(batch, M)
+        for alone in (True, False):
+            out = chain.run(ctx, inp, alone=alone, defer=not alone)
+            tag = "chain %s alone=%d" % (chain.case_id(batch, M), alone)
+            res.add(tag, {k: out[k] for k in ("info", "L", "Linv", "LinvT", "G", "alpha")})
+            res.add(tag + "/sums", [s[chain.written_slots(e, inp["Mp"])] if s is not None else None for s, e in zip(out["sums"], inp["ents"])])
+    res.check(ctx, "riding factorisation chain")
 
 
 def main(name):
