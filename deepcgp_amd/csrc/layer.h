@@ -222,57 +222,30 @@ int eval_tail(dcgp_ctx* ctx, const double* mu, const double* var, const int32_t*
               double* logdens, double* p_mean, int* ok);
 int eval_sum(dcgp_ctx* ctx, const double* logdens, const int* ok, long n, const FactorStatus& st, double* res);
 
-// gaussian.hip: the Gaussian likelihood's tails (targets y [n_labels][K] float64, row r reads y[r % n_labels]; s2 the variance's device word).
-// gauss_elbo_tail: elbo_tail's counterpart (same scal / fin / KlTail contract).  gauss_grad: gm, gv [rows][K] and gs2[0] = d / d s2, all
-// times weight.  gauss_predict: out_mean = mu, out_var = var + s2 (either may be nullptr).  gauss_eval_tail / gauss_eval_sum: eval_tail /
-// eval_sum's counterparts (per image the log density summed over K, per (image, k) the log density (ld_nd, may be nullptr) and the
-// sample-mean prediction (y_mean, may be nullptr), per image the squared error; res[4] = {sum of squared errors, sum of log densities,
-// first non-positive pivot, 0}).
-int gauss_elbo_tail(dcgp_ctx* ctx, const double* mu, const double* var, const double* y, int n_rows, int n_labels, int K, const double* s2,
-                    double* ve_rows, double inv_s, double* scal, const ElboFinish& fin, const KlTail* kl = nullptr);
-int gauss_grad(dcgp_ctx* ctx, const double* mu, const double* var, const double* y, int rows, int K, int n_labels, const double* s2,
-               double weight, double* gm, double* gv, double* gs2);
-int gauss_predict(dcgp_ctx* ctx, const double* mu, const double* var, long n, const double* s2, double* out_mean, double* out_var);
-int gauss_eval_tail(dcgp_ctx* ctx, const double* mu, const double* var, const double* y, int n, int S, int K, const double* s2, long lo,
-                    double* logdens, double* ld_nd, double* y_mean, double* sqerr);
-int gauss_eval_sum(dcgp_ctx* ctx, const double* logdens, const double* sqerr, long n, const FactorStatus& st, double* res);
-
-// bernoulli.hip: the Bernoulli (probit) likelihood's tails (targets y [n_labels][K] float64, y == 1 positive; row r reads y[r % n_labels]).
-// bern_elbo_tail: elbo_tail's counterpart (same scal / fin / KlTail contract).  bern_grad: gm, gv [rows][K] times weight.  bern_predict:
-// out_mean = p, out_var = p - p^2 (either may be nullptr).  bern_eval_tail: per image the log density summed over K, per (image, k) the
-// log density (ld_nd, may be nullptr) and the sample-mean p (p_mean, may be nullptr), per image the number of correct outputs as a double;
-// gauss_eval_sum adds those up (res[0] = correct entries, res[1] = sum of log densities).
-int bern_elbo_tail(dcgp_ctx* ctx, const double* mu, const double* var, const double* y, int n_rows, int n_labels, int K, double* ve_rows,
-                   double inv_s, double* scal, const ElboFinish& fin, const KlTail* kl = nullptr);
-int bern_grad(dcgp_ctx* ctx, const double* mu, const double* var, const double* y, int rows, int K, int n_labels, double weight, double* gm,
-              double* gv);
-int bern_predict(dcgp_ctx* ctx, const double* mu, const double* var, long n, double* out_mean, double* out_var);
-int bern_eval_tail(dcgp_ctx* ctx, const double* mu, const double* var, const double* y, int n, int S, int K, long lo, double* logdens,
-                   double* ld_nd, double* p_mean, double* correct);
-
-// quadrature.hip: the tails of the likelihoods that are a per-element log density under the 20-node Gauss-Hermite rule -- kind 4 StudentT(scale,
-// deg_free nu; c_nu = student_t_const(nu)), kind 5 Poisson(exp link, binsize) -- targets y [n_labels][K] float64, row r reads y[r % n_labels].  The
-// StudentT scale is read from its device word `scale` where that is set (a model's), else from scale_val (the stand-alone entry points).
-// quad_elbo_tail: elbo_tail's counterpart (same scal / fin / KlTail contract; 1 <= K <= 1024, else DCGP_ERR_ARG).  quad_grad: gm, gv [rows][K] and, kind 4,
-// gpar[0] = d / d scale, all times weight.  quad_predict: (E_y, V_y) per element (either may be nullptr).  quad_elementwise: per element of [n]
-// what = 0 the variational expectation, 1 (E_y, V_y), 2 the log density of one sample.  quad_eval_tail: per image the log density summed over K,
-// per (image, k) the log density (ld_nd, may be nullptr) and the sample-mean E_y (y_mean, may be nullptr), per image the squared error of
-// that mean; gauss_eval_sum adds those up.
+// pointwise.hip: the tails of the per-output likelihoods -- kind 1 Gaussian(s2), 2 Bernoulli (probit; y == 1 positive), 4 StudentT(scale, deg_free nu;
+// c_nu = student_t_const(nu)), 5 Poisson(exp link, binsize) -- targets y [n_labels][K] float64, row r reads y[r % n_labels].  The trainable parameter
+// (the Gaussian variance, the StudentT scale) is read from its device word `par` where that is set (a model's), else from par_val (the stand-alone
+// entry points).  quad_elbo_tail: elbo_tail's counterpart (same scal / fin / KlTail contract; any K >= 1).  quad_grad: gm, gv [rows][K] and, kinds 1 and 4,
+// gpar[0] = d / d par, all times weight.  quad_elementwise: per element of [n] what = 0 the variational expectation (out_a), 1 (E_y, V_y) (out_a, out_b;
+// either may be nullptr; y unused), 2 the log density of one sample (out_a).  quad_eval_tail / quad_eval_sum: eval_tail / eval_sum's counterparts -- per
+// image the log density summed over K, per (image, k) the log density (ld_nd, may be nullptr) and the sample-mean E_y (y_mean, may be nullptr), per image
+// the score summed over K (the squared error of that mean; Bernoulli: the correct outputs); res[4] = {sum of scores, sum of log densities, first
+// non-positive pivot, 0}.
 struct QuadLik {
-  int kind = 0;                       // 4 StudentT, 5 Poisson
-  const double* scale = nullptr;      // StudentT: the scale's device word, or nullptr: scale_val
-  double scale_val = 1.0, nu = 3.0, c_nu = 0.0, binsize = 1.0;
+  int kind = 0;                       // 1 Gaussian, 2 Bernoulli, 4 StudentT, 5 Poisson
+  const double* par = nullptr;        // Gaussian: the variance's device word, StudentT: the scale's; nullptr: par_val
+  double par_val = 1.0, nu = 3.0, c_nu = 0.0, binsize = 1.0;
 };
 double student_t_const(double nu);    // lgamma((nu + 1) / 2) - lgamma(nu / 2) - log(nu pi) / 2
 int quad_elbo_tail(dcgp_ctx* ctx, const QuadLik& q, const double* mu, const double* var, const double* y, int n_rows, int n_labels, int K,
                    double* ve_rows, double inv_s, double* scal, const ElboFinish& fin, const KlTail* kl = nullptr);
 int quad_grad(dcgp_ctx* ctx, const QuadLik& q, const double* mu, const double* var, const double* y, int rows, int K, int n_labels, double weight,
               double* gm, double* gv, double* gpar);
-int quad_predict(dcgp_ctx* ctx, const QuadLik& q, const double* mu, const double* var, long n, double* out_mean, double* out_var);
 int quad_elementwise(dcgp_ctx* ctx, const QuadLik& q, int what, const double* mu, const double* var, const double* y, long n, double* out_a,
                      double* out_b);
 int quad_eval_tail(dcgp_ctx* ctx, const QuadLik& q, const double* mu, const double* var, const double* y, int n, int S, int K, long lo,
-                   double* logdens, double* ld_nd, double* y_mean, double* sqerr);
+                   double* logdens, double* ld_nd, double* y_mean, double* score);
+int quad_eval_sum(dcgp_ctx* ctx, const double* logdens, const double* score, long n, const FactorStatus& st, double* res);
 
 // softmax.hip: the Softmax likelihood's tails (int32 labels y; nodes [Q][K] on the device, the same table for every row; 2 <= K, 1 <= Q,
 // Q * K <= 4096, else DCGP_ERR_ARG).  softmax_elbo_tail: elbo_tail's counterpart (same scal / fin / KlTail contract); a label outside [0, K) leaves
@@ -292,7 +265,7 @@ int softmax_unc_tail(dcgp_ctx* ctx, const double* mu, const double* var, const i
 int softmax_density_grad(dcgp_ctx* ctx, const double* mu, const double* var, const int32_t* y, int n_img, int S, int K, const double* nodes, int Q,
                          double* J, double* gm, double* gv);
 
-// uncertainty.hip: the uncertainty tails (dcgp_model_evaluate_uncertainty).  unc_tail / bern_unc_tail: eval_tail / bern_eval_tail with the same
+// uncertainty.hip: the uncertainty tails (dcgp_model_evaluate_uncertainty).  unc_tail / bern_unc_tail: eval_tail / quad_eval_tail (Bernoulli) with the same
 // bits for logdens, p_mean and the correct count, plus per entry (image; Bernoulli: (image, output)) at its index in the whole set the
 // predictive entropy, the expected entropy (may be nullptr), their difference, the confidence and the prediction.  y may be nullptr:
 // then logdens, ok and brier are not touched.  unc_tail keeps kUncExtraSlots wave partials beside eval_tail's LDS: S * K + K + 48 <= kEvalMaxSlots.
@@ -328,7 +301,7 @@ struct Likelihood {
   double binsize = 1.0;          // Poisson
   bool float_targets() const { return kind == 1 || kind == 2 || kind == 4 || kind == 5; }    // the _f64y entry points
   int n_params() const { return kind == 1 || kind == 4 ? 1 : 0; }   // trainable words (the Gaussian variance, the StudentT scale): lik_grad_seeds wants a gs2 for each
-  QuadLik quad() const { QuadLik q; q.kind = kind; q.scale = s2; q.nu = nu; q.c_nu = c_nu; q.binsize = binsize; return q; }   // kinds 4, 5
+  QuadLik quad() const { QuadLik q; q.kind = kind; q.par = s2; q.nu = nu; q.c_nu = c_nu; q.binsize = binsize; return q; }   // kinds 1, 2, 4, 5
 };
 struct Targets {
   const int32_t* labels = nullptr; const double* values = nullptr; int K = 1; bool f64 = false;

@@ -1,6 +1,6 @@
 // likelihood.hip -- the one place that knows which likelihood a model has (host code only: no kernels).  Every function takes the
 // Likelihood and the Targets (layer.h) and dispatches once on the kind to the launchers of cond.hip / evaluate.hip / uncertainty.hip /
-// grad.hip / input_grad.hip (RobustMax), gaussian.hip, bernoulli.hip, softmax.hip and quadrature.hip (StudentT, Poisson); what differs between
+// grad.hip / input_grad.hip (RobustMax), softmax.hip and pointwise.hip (Gaussian, Bernoulli, StudentT, Poisson); what differs between
 // their argument lists ends here.
 #include "layer_impl.h"
 
@@ -17,9 +17,9 @@ int lik_check_targets(dcgp_ctx* ctx, const Likelihood& lik, const Targets& t, co
 int lik_elbo_tail(dcgp_ctx* ctx, const Likelihood& lik, const double* mu, const double* var, const Targets& t, int n_rows, int n_labels, int K,
                   double* ve_rows, double inv_s, double* scal, const ElboFinish& fin, const KlTail* kl) {
   switch (lik.kind) {
-    case 1: return gauss_elbo_tail(ctx, mu, var, t.values, n_rows, n_labels, K, lik.s2, ve_rows, inv_s, scal, fin, kl);
-    case 2: return bern_elbo_tail(ctx, mu, var, t.values, n_rows, n_labels, K, ve_rows, inv_s, scal, fin, kl);
     case 3: return softmax_elbo_tail(ctx, mu, var, t.labels, n_rows, n_labels, K, lik.nodes, lik.Q, ve_rows, inv_s, scal, fin, kl);
+    case 1:
+    case 2:
     case 4:
     case 5: return quad_elbo_tail(ctx, lik.quad(), mu, var, t.values, n_rows, n_labels, K, ve_rows, inv_s, scal, fin, kl);
     default: return elbo_tail(ctx, mu, var, t.labels, n_rows, n_labels, K, lik.eps, ve_rows, inv_s, scal, fin, kl);
@@ -28,26 +28,24 @@ int lik_elbo_tail(dcgp_ctx* ctx, const Likelihood& lik, const double* mu, const 
 
 int lik_grad_seeds(dcgp_ctx* ctx, const Likelihood& lik, const double* mu, const double* var, const Targets& t, int rows, int n_labels, int K,
                    double weight, double* gm, double* gv, double* gs2) {
+  if (lik.kind == 1 && (!lik.s2 || !gs2)) return ctx_fail(ctx, DCGP_ERR_ARG, "grad: the Gaussian likelihood has no variance on the device");
+  if (lik.kind == 4 && (!lik.s2 || !gs2)) return ctx_fail(ctx, DCGP_ERR_ARG, "grad: the StudentT likelihood has no scale on the device");
   switch (lik.kind) {
-    case 1:
-      if (!lik.s2 || !gs2) return ctx_fail(ctx, DCGP_ERR_ARG, "grad: the Gaussian likelihood has no variance on the device");
-      return gauss_grad(ctx, mu, var, t.values, rows, K, n_labels, lik.s2, weight, gm, gv, gs2);
-    case 2: return bern_grad(ctx, mu, var, t.values, rows, K, n_labels, weight, gm, gv);
     case 3: return softmax_grad(ctx, mu, var, t.labels, rows, n_labels, K, lik.nodes, lik.Q, weight, gm, gv);
+    case 1:
+    case 2:
     case 4:
-      if (!lik.s2 || !gs2) return ctx_fail(ctx, DCGP_ERR_ARG, "grad: the StudentT likelihood has no scale on the device");
-      return quad_grad(ctx, lik.quad(), mu, var, t.values, rows, K, n_labels, weight, gm, gv, gs2);
-    case 5: return quad_grad(ctx, lik.quad(), mu, var, t.values, rows, K, n_labels, weight, gm, gv, nullptr);
+    case 5: return quad_grad(ctx, lik.quad(), mu, var, t.values, rows, K, n_labels, weight, gm, gv, lik.n_params() ? gs2 : nullptr);
     default: return robustmax_grad(ctx, mu, var, t.labels, rows, n_labels, K, lik.eps, weight, gm, gv);
   }
 }
 
 int lik_predict(dcgp_ctx* ctx, const Likelihood& lik, const double* mu, const double* var, long n, double* out_mean, double* out_var) {
   switch (lik.kind) {
-    case 1: return gauss_predict(ctx, mu, var, n, lik.s2, out_mean, out_var);
-    case 2: return bern_predict(ctx, mu, var, n, out_mean, out_var);
+    case 1:
+    case 2:
     case 4:
-    case 5: return quad_predict(ctx, lik.quad(), mu, var, n, out_mean, out_var);
+    case 5: return quad_elementwise(ctx, lik.quad(), 1, mu, var, nullptr, n, out_mean, out_var);
     default: return ctx_fail(ctx, DCGP_ERR_ARG, "predict_mean_var: not a Gaussian- or Bernoulli-likelihood model (dcgp_model_predict_y)");
   }
 }
@@ -71,8 +69,8 @@ int lik_eval_tail(dcgp_ctx* ctx, const Likelihood& lik, const double* mu, const 
                   const EvalOut& o) {
   const Targets t = all.from(lo);
   switch (lik.kind) {
-    case 1: return gauss_eval_tail(ctx, mu, var, t.values, n, S, K, lik.s2, lo, o.logdens, o.ld_nd, o.p_mean, o.score);
-    case 2: return bern_eval_tail(ctx, mu, var, t.values, n, S, K, lo, o.logdens, o.ld_nd, o.p_mean, o.score);
+    case 1:
+    case 2:
     case 4:
     case 5: return quad_eval_tail(ctx, lik.quad(), mu, var, t.values, n, S, K, lo, o.logdens, o.ld_nd, o.p_mean, o.score);
     case 3: return softmax_eval_tail(ctx, mu, var, t.labels, n, S, K, lik.nodes, lik.Q, lo, o.logdens, o.p_mean, o.ok);
@@ -81,7 +79,7 @@ int lik_eval_tail(dcgp_ctx* ctx, const Likelihood& lik, const double* mu, const 
 }
 
 int lik_eval_sum(dcgp_ctx* ctx, const Likelihood& lik, const EvalOut& o, long n, const FactorStatus& st, double* res) {
-  if (lik.float_targets()) return gauss_eval_sum(ctx, o.logdens, o.score, n, st, res);   // (Bernoulli: the same sum over its correct counts; StudentT, Poisson: squared errors)
+  if (lik.float_targets()) return quad_eval_sum(ctx, o.logdens, o.score, n, st, res);   // (the scores: squared errors; Bernoulli: correct counts)
   return eval_sum(ctx, o.logdens, o.ok, n, st, res);                                      // (Softmax: eval_tail's outputs, the same sum)
 }
 

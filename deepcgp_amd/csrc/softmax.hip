@@ -2,7 +2,7 @@
 // draw replaced by a FIXED table of nodes e [Q][K], standard-normal draws shared by every row: a Q-node rule used the way the 20 Gauss-Hermite
 // nodes are used for RobustMax and Bernoulli).  int32 labels y in [0, K).  Per head row with mean mu [K], variance v [K]:
 //
-//   s_k   = sqrt(max(v_k, 1e-10))                      (d / d v_k = 0 where the clamp holds, as bern_grad_kernel)
+//   s_k   = sqrt(max(v_k, 1e-10))                      (d / d v_k = 0 where the clamp holds, as quad_grad_kernel)
 //   f_q   = mu + s o e_q,  lse_q = logsumexp_k f_q[k]  (max-subtracted),  sig_q = exp(f_q - lse_q)
 //   variational expectation  ve = 1/Q sum_q (f_q[y] - lse_q)
 //     d ve / d mu_k = 1/Q sum_q ([k == y] - sig_q[k]),   d ve / d v_k = 1/Q sum_q ([k == y] - sig_q[k]) e_q[k] / (2 s_k)
@@ -15,7 +15,7 @@
 // evaluate, evaluate_uncertainty and the density objective of input_grad agree on p to the bit).  The price is two exps per (q, k).
 // Groups are small -- sm_group_rows: at most 256 / K rows (the Bernoulli tail's rows per workgroup), 512 / Q and 1024 / (K chunks) -- so
 // a cfg2 step (320 rows, K = 10, Q = 100) is 64 workgroups of ~2 lse items and ~1.4 chunk items per thread, not 320 threads running
-// 1000 exps back to back (the trap bernoulli.hip's comment measures).
+// 1000 exps back to back (the trap pointwise.hip's comment measures).
 #include "model_state.h"
 #include "tail_dev.h"
 #include "unc_dev.h"
@@ -163,7 +163,7 @@ __device__ __forceinline__ void sm_ve_rows(const SmRowsArgs& a, int row0, int nr
   }
 }
 
-// The rows' workgroups, then the KlTail workgroups; the last workgroup to arrive sums the rows and assembles the ELBO as bern_tail_kernel and
+// The rows' workgroups, then the KlTail workgroups; the last workgroup to arrive sums the rows and assembles the ELBO as quad_tail_kernel and
 // elbo_tail_kernel do.  Dynamic LDS: the rows' buffers, at least the 1024 doubles of kl_pieces_block.
 __global__ __launch_bounds__(256) void softmax_tail_kernel(SmRowsArgs a, TailArgs t, KlTail kl, int nb_rows) {
   extern __shared__ __attribute__((aligned(16))) double sm[];

@@ -2,7 +2,7 @@
 // DGP_Base.predict_y leaves to its caller (the S samples of the class probabilities) reduced on the device to the predictive entropy,
 // its expected-entropy / mutual-information (BALD) split, the confidence and the reliability table of the sample-mean prediction.
 //
-//   p[s][k]   the per-sample probabilities of eval_tail_kernel (RobustMax) / bern_eval_tail_kernel (jittered probit), term for term
+//   p[s][k]   the per-sample probabilities of eval_tail_kernel (RobustMax) / quad_eval_tail_kernel<BernoulliDensity> (jittered probit), term for term
 //   pbar      their mean, summed in sample order
 //   H(pbar) = -sum_k pbar[k] log pbar[k]                    predictive entropy      (Bernoulli: the binary entropy h(pbar) per output)
 //   E H     = 1/S sum_s -sum_k p[s][k] log p[s][k]          expected entropy
@@ -15,6 +15,7 @@
 #include "layer_impl.h"
 #include "tail_dev.h"
 #include "unc_dev.h"
+#include "pointwise_dev.h"
 
 namespace {
 
@@ -40,9 +41,6 @@ __global__ __launch_bounds__(kUncThreads) void unc_tail_kernel(UncTailArgs a) {
   unc_tail_finish(a, p, pbar, part);
 }
 
-constexpr double kInvSqrt2 = 0.70710678118654752440;
-__device__ __forceinline__ double probit(double x) { return 0.5 * (1.0 + erf(x * kInvSqrt2)) * (1.0 - 2e-3) + 1e-3; }
-__device__ __forceinline__ double bern_logp(double p, bool pos) { return pos ? log(p) : log(1.0 - p); }
 __device__ __forceinline__ double binary_entropy(double q) { return -q * log(q) - (1.0 - q) * log(1.0 - q); }
 
 struct BernUncArgs {
@@ -58,7 +56,7 @@ struct BernUncArgs {
   int* pred = nullptr;                                        // [N_total][K]
 };
 
-// The Bernoulli counterpart with bern_eval_tail_kernel's geometry: one thread per image, its K outputs and their S samples in index
+// The Bernoulli counterpart with quad_eval_tail_kernel's geometry: one thread per image, its K outputs and their S samples in index
 // order -- the per-image log density is that kernel's sum over the outputs, statement for statement.
 __global__ __launch_bounds__(256) void bern_unc_tail_kernel(BernUncArgs a) {
   const int i = blockIdx.x * 256 + threadIdx.x;

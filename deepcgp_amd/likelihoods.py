@@ -55,7 +55,7 @@ class MultiClass:
 class Gaussian:
     """gpflow 1.x likelihoods.Gaussian(variance) as DS-DGP's BroadcastingLikelihood applies it: one variance shared by every output,
     kept positive by transforms.positive (softplus + 1e-6) when trained.  Targets are float64 N x D.  On the model path
-    (DGP_Base with this likelihood) every tail runs on the device (csrc/gaussian.hip); these methods are the closed forms of the
+    (DGP_Base with this likelihood) every tail runs on the device (csrc/pointwise.hip); these methods are the closed forms of the
     same quantities on host arrays."""
 
     def __init__(self, variance=1.0):
@@ -91,7 +91,7 @@ def _probit(x):
 class Bernoulli:
     """gpflow 1.x likelihoods.Bernoulli(invlink=probit) as DS-DGP's BroadcastingLikelihood applies it: every output an independent
     binary label, float64 targets N x D with Y == 1 positive and anything else negative (gpflow's logdensities.bernoulli).  No
-    trainable parameters.  On the model path (DGP_Base with this likelihood) every tail runs on the device (csrc/bernoulli.hip);
+    trainable parameters.  On the model path (DGP_Base with this likelihood) every tail runs on the device (csrc/pointwise.hip);
     these methods are the same quantities on host arrays, the variational expectations by gpflow's 20-point Gauss-Hermite rule."""
     num_gauss_hermite_points = 20
 
@@ -148,7 +148,7 @@ class _Quadrature:
       variational expectation  sum_i c_i logp(f_i, Y),
       predictive mean E_y = sum_i c_i conditional_mean(f_i), variance sum_i c_i (conditional_variance(f_i) + conditional_mean(f_i)^2) - E_y^2,
       predictive density logsumexp_i (logp(f_i, Y) + log c_i).
-    On the model path (DGP_Base with such a likelihood) every tail runs on the device (csrc/quadrature.hip);
+    On the model path (DGP_Base with such a likelihood) every tail runs on the device (csrc/pointwise.hip);
     ``variational_expectations`` on arrays goes through the device too (dcgp_quad_varexp), the other methods are NumPy."""
     num_gauss_hermite_points = 20
     kind = None

@@ -452,6 +452,18 @@ def run_operators(res):
             res.add(tag, {k: out[k] for k in ("info", "L", "Linv", "LinvT", "G", "alpha")})
             res.add(tag + "/sums", [s[chain.written_slots(e, inp["Mp"])] if s is not None else None for s, e in zip(out["sums"], inp["ents"])])
     res.check(ctx, "riding factorisation chain")
+    # the per-output likelihoods' tails on a head wider than the ELBO tail's 1024 doubles of LDS (tests/test_gpu_pointwise.py: K = 1030, two chunks per row)
+    import compose_ref as cr
+    import test_gpu_pointwise as pw
+    from deepcgp_amd.models import build_from_spec
+    for lik in pw.LIKS:
+        spec, X, Ylab, Y, zs = pw.make_case(1030, lik)
+        model = build_from_spec(copy.deepcopy(spec), X.copy(), Y.copy(), likelihood=cr.make_likelihood(lik))
+        tag = "wide head %s" % lik[0]
+        res.add(tag + "/elbo", model.compute_log_likelihood(X, Y, zs=zs, return_parts=True))
+        res.add(tag + "/grad", model.compute_gradients(X, Y, zs=zs)[1])
+        res.add(tag + "/evaluate", model.evaluate(X, Y, S=spec["S"], batch_size=2, zs=zs, per_image=True))
+        res.close(model, tag)
 
 
 def main(name):

@@ -1,4 +1,4 @@
-"""GPU: the Bernoulli (probit) likelihood end to end (csrc/bernoulli.hip) -- ELBO, gradient, optimisers, predictions, evaluation, errors,
+"""GPU: the Bernoulli (probit) likelihood end to end (csrc/pointwise.hip) -- ELBO, gradient, optimisers, predictions, evaluation, errors,
 checkpoints and learning -- against the oracle's propagate with a NumPy quadrature tail (tests/bernoulli_ref.py) and torch autograd."""
 import ctypes as C
 import math

@@ -1,4 +1,4 @@
-"""GPU: the Gaussian likelihood end to end (csrc/gaussian.hip) -- ELBO, gradient, optimiser slot, predictions, evaluation,
+"""GPU: the Gaussian likelihood end to end (csrc/pointwise.hip) -- ELBO, gradient, optimiser slot, predictions, evaluation,
 learning and checkpoints -- against the oracle's propagate with a NumPy Gaussian tail and torch autograd; plus head widths D = 1 / 3."""
 import ctypes as C
 import os

@@ -31,7 +31,7 @@ SWITCHES = ("DCGP_POISON_WS", "DCGP_POISON_ONLY", "DCGP_GUARD_WS")
 #   compose:ch_72_264-poisson1-acos-conv2d-none 1.0        compose:small3_20_40_24-bernoulli1-matern32-filter-all 1.0
 #   compose:ch_264_72-softmax3-rbf-conv2d-all 1.0          compose:even_s2-multiclass3-rbf-filter-none 0.9
 #   compose:valid2-studentt3-matern52-conv2d-alternate 0.8  compose:ch_res-softmax3-acos-filter-alternate 0.9
-#   ard 0.9   mixed 0.8   evaluate 1.1   train_run 1.0   operators 1.7 (0.7 of it the 242 GEMM cases' host data; ~2.0 since the riding chain's cases)
+#   ard 0.9   mixed 0.8   evaluate 1.1   train_run 1.0   operators 1.7 (0.7 of it the 242 GEMM cases' host data; ~2.0 since the riding chain's cases, ~2.2 with the wide heads of the per-output likelihoods)
 CHILD_TIMEOUT = 6       # seconds: three times the slowest (1.7 s), rounded up
 # Parent commit 99bdb54, cfg2_mnist_CH_M256 after one ELBO: what dcgp_workspace_query gives with both switches unset
 PARENT_WORKSPACE_BYTES, PARENT_WORKSPACE_COUNT = 14074368, 12

@@ -1,4 +1,4 @@
-"""GPU: the StudentT and Poisson likelihoods end to end (csrc/quadrature.hip) -- ELBO, gradient, the operator entries on a hand-made
+"""GPU: the StudentT and Poisson likelihoods end to end (csrc/pointwise.hip) -- ELBO, gradient, the operator entries on a hand-made
 array with the clamp branch, optimisers, predictions, evaluation, errors, checkpoints and learning -- against the oracle's propagate with
 a NumPy / SciPy quadrature tail (tests/quad_ref.py) and torch autograd of the same forward written with torch.distributions."""
 import ctypes as C

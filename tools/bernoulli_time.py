@@ -5,8 +5,8 @@ D = 10 and at D = 1 (binary targets).  Prints one JSON line (milliseconds, media
 
     python tools/bernoulli_time.py [--steps 50] [--warmup 10] [--reps 5] [--only multiclass|bernoulli10|bernoulli1]
 
-The tail kernels' own times come from a kernel trace of the same runs, one likelihood per trace (the Bernoulli kernels have the same
-names at both widths):
+The tail kernels' own times come from a kernel trace of the same runs, one likelihood per trace (the Bernoulli kernels -- the shared kernels' BernoulliDensity instantiations -- have the
+same names at both widths):
     rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o run -- python tools/bernoulli_time.py --steps 20 --reps 1 --warmup 3 --only bernoulli1
 and --kernels summarises those tables (<dir>/run_kernel_stats.csv) into one JSON line (average microseconds of the forward and reverse tails per trace):
     python tools/bernoulli_time.py --kernels multiclass=<stats.csv> bernoulli10=<stats.csv> bernoulli1=<stats.csv>"""
@@ -24,7 +24,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 KINDS = ("multiclass", "bernoulli10", "bernoulli1")
-TAILS = {"forward": ("elbo_tail_kernel", "bern_tail_kernel"), "reverse": ("robustmax_grad_kernel", "bern_grad_kernel")}
+TAILS = {"forward": ("elbo_tail_kernel", "quad_tail_kernel"), "reverse": ("robustmax_grad_kernel", "quad_grad_kernel")}
 
 
 def kernels(pairs):
@@ -37,7 +37,7 @@ def kernels(pairs):
         for tail, names in TAILS.items():
             for name in names:
                 for k, r in rows.items():
-                    if re.search(r"(^|::|\s)%s\(" % re.escape(name), k):   # "void (anonymous namespace)::name(args)"
+                    if re.search(r"(^|::|\s)%s[<(]" % re.escape(name), k):   # "void (anonymous namespace)::name(args)" or "...::name<BernoulliDensity>(args)"
                         out[tail] = {"kernel": name, "calls": int(r["Calls"]), "avg_us": round(float(r["AverageNs"]) / 1e3, 2)}
         res["kernels_avg_us"][label] = out
     print(json.dumps(res))

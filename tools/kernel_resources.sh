@@ -1,5 +1,5 @@
 #!/bin/bash
-# usage: tools/kernel_resources.sh <file.hip> [extra hipcc flags]   -- one line per kernel: VGPRs, spills, occupancy, LDS (hipcc remarks)
+# usage: tools/kernel_resources.sh <file.hip> [extra hipcc flags]   -- one line per kernel: VGPRs, SGPRs, spills, scratch, occupancy, LDS (hipcc remarks)
 F=$1; shift
 cd "$(dirname "$0")/../deepcgp_amd/csrc"
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -c $F -o /tmp/kr_$$.o -Rpass-analysis=kernel-resource-usage "$@" 2>&1 | python3 -c "
@@ -18,6 +18,6 @@ for r in rows:
     try: name = subprocess.run(['/opt/rocm/lib/llvm/bin/llvm-cxxfilt', r['name']], capture_output=True, text=True).stdout.strip()
     except Exception: name = r['name']
     name = re.sub(r'\(anonymous namespace\)::', '', name)[:70]
-    print('%-70s VGPR %4s  AGPR %3s  spillV %3s  spillS %3s  occ %s  LDS %s' % (name, r.get('VGPRs'), r.get('AGPRs'), r.get('VGPRs Spill'), r.get('SGPRs Spill'), r.get('Occupancy [waves/SIMD]'), r.get('LDS Size [bytes/block]')))
+    print('%-70s VGPR %4s  AGPR %3s  SGPR %3s  spillV %3s  spillS %3s  scratch %s  occ %s  LDS %s' % (name, r.get('VGPRs'), r.get('AGPRs'), r.get('TotalSGPRs', r.get('SGPRs')), r.get('VGPRs Spill'), r.get('SGPRs Spill'), r.get('ScratchSize [bytes/lane]'), r.get('Occupancy [waves/SIMD]'), r.get('LDS Size [bytes/block]')))
 "
 rm -f /tmp/kr_$$.o
