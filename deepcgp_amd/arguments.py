@@ -22,6 +22,7 @@ FLAGS = (
     ("--filter-sizes", str, "5,5", "patch size of each layer incl. the head"),
     ("--strides", str, "2,1", "patch stride of each layer incl. the head"),
     ("--paddings", str, "", "zero padding (pixels per side) of each layer's input incl. the head, comma separated; '' = no padding anywhere"),
+    ("--dilations", str, "", "dilation (atrous rate) of each conv layer's window, comma separated, one per conv layer (the head takes none); '' = 1 everywhere"),
     ("--augment-shift", int, 0, "training images are shifted by up to this many pixels either way along both axes, zero fill ('pad and random-crop'); 0 = off"),
     ("--augment-flip", None, False, "training images are flipped left-right with probability one half"),
     ("--test-shift", int, 0, "test-time augmentation: the test images are also evaluated shifted by this many pixels (zero fill), the predictive distribution averaged over the views; 0 = off"),
@@ -57,6 +58,28 @@ def default_parser():
         else:
             parser.add_argument(flag, type=kind, default=default, required=flag in REQUIRED, help=doc)
     return parser
+
+
+def parse_dilations(flags, n_convs):
+    """The ``--dilations`` list of a model of ``n_convs`` conv layers: ``n_convs`` ints >= 1, all ones when the flag is absent or ''.  A
+    wrong length, an entry < 1 or not an integer, and an entry > 1 on a layer whose ``--strides`` entry is not 1 raise ValueError."""
+    text = getattr(flags, "dilations", "") or ""
+    if not text.strip():
+        return [1] * n_convs
+    try:
+        dils = [int(t) for t in text.split(",")]
+    except ValueError:
+        raise ValueError("--dilations: expected comma-separated integers, got %r" % (text,))
+    if len(dils) != n_convs:
+        raise ValueError("--dilations: %d entries for %d conv layers (one per conv layer, like --latent-gps: the head takes no dilation)"
+                         % (len(dils), n_convs))
+    if any(d < 1 for d in dils):
+        raise ValueError("--dilations: entries must be >= 1, got %r" % (text,))
+    strides = [int(t) for t in str(getattr(flags, "strides", "") or "").split(",") if t.strip()]
+    for li, d in enumerate(dils):
+        if d > 1 and li < len(strides) and strides[li] != 1:
+            raise ValueError("--dilations: layer %d has dilation %d and --strides entry %d; a dilated layer needs stride 1" % (li, d, strides[li]))
+    return dils
 
 
 def parse_paddings(flags, n_layers):

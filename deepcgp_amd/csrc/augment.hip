@@ -154,8 +154,9 @@ extern "C" int dcgp_model_set_eval_views(dcgp_model* model, int H, int W, int C,
   if (model->layers.size() == 1 && (L0.in_scale || (L0.v.H == 1 && L0.v.W == 1)))
     return ctx_fail(ctx, DCGP_ERR_ARG, "set_eval_views: a dense head alone takes feature vectors, not H x W x C images: it has no views");
   const int p = model->pad[0];
-  if (H != L0.v.H - 2 * p || W != L0.v.W - 2 * p || C != L0.v.C)
-    return ctx_fail(ctx, DCGP_ERR_ARG, "set_eval_views: %d x %d x %d is not the model's image of %d x %d x %d", H, W, C, L0.v.H - 2 * p, L0.v.W - 2 * p, L0.v.C);
+  const dcgp_model::Geom g0 = model->geom(0);   // (true size: a dilated first layer's v is its phase geometry)
+  if (H != g0.H - 2 * p || W != g0.W - 2 * p || C != L0.v.C)
+    return ctx_fail(ctx, DCGP_ERR_ARG, "set_eval_views: %d x %d x %d is not the model's image of %d x %d x %d", H, W, C, g0.H - 2 * p, g0.W - 2 * p, L0.v.C);
   const size_t bytes = (size_t)V * 3 * sizeof(int32_t);
   if (bytes > model->eval_views_cap) {
     dev_free(ctx, model->d_eval_views);

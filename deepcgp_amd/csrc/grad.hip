@@ -1718,14 +1718,19 @@ static int backward_walk(Bk& bk, const double* X, int N, int S, int dedup_layer0
       m->kl_early[li] = false; m->prep_early[li] = 0;
     }
     const int pad = li < 8 ? m->pad[li] : 0;   // a padded layer read the padded copy its forward left (model.hip: pad_input); its dX has that size
-    const double* Xin = pad > 0 ? m->pad_in[li] : (li == 0 ? X : m->outs[li - 1].sample);
-    if (!Xin) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: layer %d has no padded input from the forward pass", who, li);
+    // a dilated layer (dcgp_model_set_dilation) ran on the d^2 phase sub-images of its (padded) input, which its forward left (model.hip: split_input);
+    // its (gm, gv) arrive in phase layout (below, where they are formed) and its dX comes out in phase layout
+    const int dil = L.is_head ? 1 : m->dil_of(li), dd = dil * dil;
+    const dcgp_model::Geom geo = m->geom(li);   // the true (padded) input size
+    const double* Xin = dil > 1 ? m->dil_in[li] : (pad > 0 ? m->pad_in[li] : (li == 0 ? X : m->outs[li - 1].sample));
+    if (!Xin) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: layer %d has no %s input from the forward pass", who, li, dil > 1 ? "split" : "padded");
     int rows_l = m->outs[li].rows;                  // rows entering == rows leaving ...
     // ... except for a de-duplicated first conv layer: propagate() tiles the batch S times, so layer 0 saw S identical
     // copies; the forward evaluated its conditional on the N distinct images and drew S samples from it.  The S
     // gradients arriving per image add up, and the conditional's reverse pass runs on N rows instead of S N (exact).
     if (li == 0 && dedup_layer0 && !L.is_head && rows_l == S * N && S > 1) {
       if (!dedup_done) {   // (the head-less case: the gradients came from the likelihood, not from a layer above)
+        if (dil > 1) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: a dilated layer takes its gradient from the layer above it", who);
         const long n = (long)N * L.v.P * L.R;
         double* gm0 = (double*)ws_get(ctx, bk.pfx + "g_gm_dedup", (size_t)n * sizeof(double));
         double* gv0 = (double*)ws_get(ctx, bk.pfx + "g_gv_dedup", (size_t)n * sizeof(double));
@@ -1738,19 +1743,27 @@ static int backward_walk(Bk& bk, const double* X, int N, int S, int dedup_layer0
     }
     if (!L.is_head && L.mix_W && li == nl - 1) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: a mixed layer must have a layer above it", who);
     const int n_mod = li == 0 ? N : rows_l;
-    const long img = (long)L.v.H * L.v.W * L.v.C;
+    const long img = (long)L.v.H * L.v.W * L.v.C;   // (one sub-image of a dilated layer)
     double* dXin = li == 0 ? out_dX : nullptr;   // (layer 0 of a training step: no dX)
-    if (li > 0 || (out_dX && (rows_l != N || pad > 0))) {
-      dXin = (double*)ws_get(ctx, bk.pfx + "g_dXin", (size_t)rows_l * img * sizeof(double));
+    if (li > 0 || (out_dX && (rows_l != N || pad > 0 || dil > 1))) {
+      dXin = (double*)ws_get(ctx, bk.pfx + "g_dXin", (size_t)rows_l * dd * img * sizeof(double));
       NEED(dXin);
     }
     if (L.is_head) DCGP_TRY(head_backward(bk, L, Xin, rows_l, n_mod, gm, gv, dXin));
-    else DCGP_TRY(conv_backward(bk, L, Xin, rows_l, n_mod, gm, gv, dXin));
+    else DCGP_TRY(conv_backward(bk, L, Xin, rows_l * dd, n_mod * dd, gm, gv, dXin));
+    if (li == 0 && out_dX && rows_l % N) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: %d rows at layer 0 for %d images", who, rows_l, N);
+    if (dil > 1 && dXin) {   // back to image layout; layer 0's replica sum in the same pass where no crop follows (the crop sums otherwise)
+      const bool last_pass = li == 0 && pad == 0;
+      double* dimg = last_pass ? out_dX : (double*)ws_get(ctx, bk.pfx + "g_dXb2s", (size_t)rows_l * geo.H * geo.W * L.v.C * sizeof(double));
+      NEED(dimg);
+      if (last_pass) DCGP_TRY(b2s_images(ctx, ctx->stream, dXin, rows_l / N, N, geo.H, geo.W, L.v.C, dil, dimg));
+      else DCGP_TRY(b2s_images(ctx, ctx->stream, dXin, 1, rows_l, geo.H, geo.W, L.v.C, dil, dimg));
+      dXin = dimg;
+    }
     if (li == 0) {
-      if (out_dX && rows_l % N) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: %d rows at layer 0 for %d images", who, rows_l, N);
       if (out_dX && pad > 0) {       // crop to the caller's geometry, the replica sum in the same pass
-        DCGP_TRY(crop_images(ctx, ctx->stream, dXin, rows_l / N, N, L.v.H - 2 * pad, L.v.W - 2 * pad, L.v.C, pad, out_dX));
-      } else if (out_dX && rows_l != N) {   // the final replica sum
+        DCGP_TRY(crop_images(ctx, ctx->stream, dXin, rows_l / N, N, geo.H - 2 * pad, geo.W - 2 * pad, L.v.C, pad, out_dX));
+      } else if (out_dX && rows_l != N && dil == 1) {   // the final replica sum (a dilated layer's: in its batch-to-space pass above)
         hipLaunchKernelGGL(reduce_replicas1_kernel, dim3(blocks_for(N * img)), dim3(256), 0, ctx->stream, dXin, rows_l / N, N * img, out_dX);
         LAUNCH_CHECK(ctx);
       }
@@ -1758,28 +1771,43 @@ static int backward_walk(Bk& bk, const double* X, int N, int S, int dedup_layer0
     }
     auto& o = m->outs[li - 1];
     LayerState& Lb = *m->layers[li - 1];
-    const long n_out = (long)o.rows * o.width;
-    const long n = Lb.is_head ? n_out : (long)o.rows * Lb.v.P * Lb.R;   // the (d mean, d var) the layer below takes: its GPs' (== n_out unless it is mixed)
+    // a dilated layer below: its (d mean, d var) are formed in PHASE layout, phantoms included -- the gradient from above is split first (a phantom's
+    // is an exact zero), the triple is the phase-layout one its forward left (a mixed layer's latent triple is in phase layout as it is)
+    const int dil_b = Lb.is_head ? 1 : m->dil_of(li - 1), dd_b = dil_b * dil_b;
+    const long rows_b = (long)o.rows * dd_b;   // rows of the layer below as its kernels count them
+    const long n_out = dil_b > 1 ? rows_b * Lb.v.P * Lb.Rout : (long)o.rows * o.width;
+    const long n = Lb.is_head ? n_out : rows_b * Lb.v.P * Lb.R;   // the (d mean, d var) the layer below takes: its GPs' (== n_out unless it is mixed)
     gm = (double*)ws_get(ctx, mp + std::to_string(li - 1) + "_g_gm", (size_t)n * sizeof(double));
     gv = (double*)ws_get(ctx, mp + std::to_string(li - 1) + "_g_gv", (size_t)n * sizeof(double));
     NEED(gm); NEED(gv);
     if (pad > 0) {   // the sample's gradient is the interior of the padded input's
       double* dcrop = (double*)ws_get(ctx, bk.pfx + "g_dXcrop", (size_t)n_out * sizeof(double));
       NEED(dcrop);
-      DCGP_TRY(crop_images(ctx, ctx->stream, dXin, 1, o.rows, L.v.H - 2 * pad, L.v.W - 2 * pad, L.v.C, pad, dcrop));
+      DCGP_TRY(crop_images(ctx, ctx->stream, dXin, 1, o.rows, geo.H - 2 * pad, geo.W - 2 * pad, L.v.C, pad, dcrop));
       dXin = dcrop;
     }
     const bool dedup_below = li - 1 == 0 && dedup_layer0 && !Lb.is_head && o.rows == S * N && S > 1;
-    const double *dF = dXin, *smp = o.sample, *mean = o.mean, *var = o.var;
+    const double *smp = o.sample, *mean = o.mean, *var = o.var;
+    if (dil_b > 1) {
+      const dcgp_model::Geom gb = m->geom(li - 1);
+      const auto& ph = m->dil_out[li - 1];
+      if (!ph.sample || !ph.mean || !ph.var) return ctx_fail(ctx, DCGP_ERR_ARG, "%s: layer %d has no phase-layout outputs from the forward pass", who, li - 1);
+      double* dsplit = (double*)ws_get(ctx, bk.pfx + "g_dXs2b", (size_t)n_out * sizeof(double));
+      NEED(dsplit);
+      DCGP_TRY(s2b_images(ctx, ctx->stream, dXin, o.rows, gb.Ho, gb.Wo, Lb.Rout, dil_b, dsplit));
+      dXin = dsplit;
+      smp = ph.sample; mean = ph.mean; var = ph.var;
+    }
+    const double* dF = dXin;
     bk.mix_gF = bk.mix_gF_all = nullptr; bk.mix_cols = 0;
     if (!Lb.is_head && Lb.mix_W) {   // a mixed layer (mix.hip): gu = gF W^T on every replica's columns, then the sample's adjoint on its latent triple
-      const long cols = (long)o.rows * Lb.v.P;
+      const long cols = rows_b * Lb.v.P;
       double* gu = (double*)ws_get(ctx, mp + std::to_string(li - 1) + "_g_gu", (size_t)n * sizeof(double));
       NEED(gu);
       DCGP_TRY(mix_backward_latent(ctx, Lb.mix_W, Lb.R, Lb.Rout, dXin, cols, gu));
       bk.mix_gF_all = dXin; bk.mix_cols = cols; bk.mix_gF = dXin;
       if (dedup_below && Lb.mean_W) {   // the mean filter sees the N distinct images: its adjoint takes the replicas' sum
-        const long n0 = (long)N * o.width;
+        const long n0 = n_out / S;
         double* gF0 = (double*)ws_get(ctx, mp + std::to_string(li - 1) + "_g_gF0", (size_t)n0 * sizeof(double));
         NEED(gF0);
         hipLaunchKernelGGL(reduce_replicas1_kernel, dim3(blocks_for(n0)), dim3(256), 0, ctx->stream, dXin, S, n0, gF0);

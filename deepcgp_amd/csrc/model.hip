@@ -204,7 +204,8 @@ StepPlan plan_step(const dcgp_model* m, int N, int S, int dedup, bool need_kl, b
   p.main_s = part ? ctx->stream_m : ctx->stream;
   p.kl_s = ctx->no_side ? p.main_s : (part ? ctx->stream2_m : (pipelined ? (p.bank ? ctx->stream2b : ctx->stream2) : ctx->stream2));
   p.rows0 = dedup ? N : S * N;
-  p.first_one_launch = first_layer_one_launch(ctx, L0, p.rows0);
+  const long rows0k = (long)p.rows0 * m->dil[0] * m->dil[0];   // rows layer 0's kernels see: the phase sub-images of a dilated first layer
+  p.first_one_launch = first_layer_one_launch(ctx, L0, (int)rows0k);
   p.chain_s = p.reuse ? p.main_s : ((pipelined || !p.first_one_launch) ? p.kl_s : p.main_s);
   p.early_sweep = p.chain_beside() && !p.first_one_launch && !ctx->opt.no_early_sweep;
   if (p.early_sweep && !pipelined && !ctx->opt.prep_on_chain) p.prep = L0.is_head ? PrepPlace::SplitSweepFirst : PrepPlace::SplitChainFirst;
@@ -212,12 +213,14 @@ StepPlan plan_step(const dcgp_model* m, int N, int S, int dedup, bool need_kl, b
   for (auto& l : m->layers) one_group = one_group && l->Mp == L0.Mp;
   p.defer = one_group && need_kl && !m->keep_state;
   p.chain = ChainMode{!p.chain_beside() && !pipelined, p.first_one_launch};
-  p.mark = (long)p.rows0 * L0.v.P >= 8192 ? ForkMark::BehindFirstLayer : ForkMark::BehindChain;
+  p.mark = rows0k * L0.v.P >= 8192 ? ForkMark::BehindFirstLayer : ForkMark::BehindChain;
   const int nl = (int)m->layers.size();
   // (a padded head sweeps the padded copy of the sample: the ride reads the sample itself)
+  // (a dilated layer completes its sample in the batch-to-space pass behind its launch, dilate.hip: no row of the head rides that launch)
   // (a layer with a mean filter completes its sample in a pass behind its launch, conv_mean.hip: no row may read the sample inside the launch;
   // a mixed layer's launch writes its latent sample, the maps the head reads come out of the pass behind it, mix.hip)
-  if (nl >= 2 && m->layers[nl - 1]->is_head && !m->layers[nl - 2]->is_head && m->pad[nl - 1] == 0 && !m->layers[nl - 2]->mean_W && !m->layers[nl - 2]->mix_W) {
+  if (nl >= 2 && m->layers[nl - 1]->is_head && !m->layers[nl - 2]->is_head && m->pad[nl - 1] == 0 && !m->layers[nl - 2]->mean_W && !m->layers[nl - 2]->mix_W &&
+      m->dil_of(nl - 2) == 1) {
     const int li = nl - 2;
     const LayerState& Lc = *m->layers[li];
     const LayerState& Lh = *m->layers[nl - 1];
@@ -267,17 +270,19 @@ int check_padding(dcgp_model* m) {
     const int p = m->pad[li];
     if (p == 0) continue;
     const LayerState& L = *m->layers[li];
+    const dcgp_model::Geom gl = m->geom(li);   // (true sizes: a dilated layer's v is its phase geometry)
     if (p < 0) return ctx_fail(ctx, DCGP_ERR_ARG, "padding: layer %d has a negative padding (%d)", li, p);
     if (L.is_head && L.in_scale)   // (per-dimension lengthscales on the flattened input: --last-kernel rbf)
       return ctx_fail(ctx, DCGP_ERR_ARG, "padding: layer %d is a dense head, only conv layers and patch heads take padding", li);
-    if (L.v.H - 2 * p < 1 || L.v.W - 2 * p < 1)
+    if (gl.H - 2 * p < 1 || gl.W - 2 * p < 1)
       return ctx_fail(ctx, DCGP_ERR_ARG, "padding: layer %d was added as %d x %d, smaller than its border of %d (add the layer with the padded size)", li,
-                      L.v.H, L.v.W, p);
+                      gl.H, gl.W, p);
     if (li == 0) continue;
     const LayerState& B = *m->layers[li - 1];
-    if (B.is_head || B.v.Ho + 2 * p != L.v.H || B.v.Wo + 2 * p != L.v.W || B.Rout != L.v.C)
-      return ctx_fail(ctx, DCGP_ERR_ARG, "padding: layer %d takes %d x %d x %d, layer %d produces %d x %d x %d and the padding is %d", li, L.v.H, L.v.W, L.v.C,
-                      li - 1, B.v.Ho, B.v.Wo, B.Rout, p);
+    const dcgp_model::Geom gb = m->geom(li - 1);
+    if (B.is_head || gb.Ho + 2 * p != gl.H || gb.Wo + 2 * p != gl.W || B.Rout != L.v.C)
+      return ctx_fail(ctx, DCGP_ERR_ARG, "padding: layer %d takes %d x %d x %d, layer %d produces %d x %d x %d and the padding is %d", li, gl.H, gl.W, L.v.C,
+                      li - 1, gb.Ho, gb.Wo, B.Rout, p);
   }
   m->pad_ok = true;
   return DCGP_OK;
@@ -289,11 +294,112 @@ int pad_input(dcgp_model* m, hipStream_t stream, int li, int bank, const double*
   const LayerState& L = *m->layers[li];
   const int p = m->pad[li];
   const std::string name = "m" + std::to_string(m->id) + "_" + std::to_string(li) + "_Xpad" + (li == 0 ? "_b" + std::to_string(bank) : std::string());
-  double* dst = (double*)ws_get(ctx, name, (size_t)rows * L.v.H * L.v.W * L.v.C * sizeof(double));
+  const dcgp_model::Geom g = m->geom(li);
+  double* dst = (double*)ws_get(ctx, name, (size_t)rows * g.H * g.W * L.v.C * sizeof(double));
   if (!dst) return DCGP_ERR_ALLOC;
-  DCGP_TRY(pad_images(ctx, stream, src, rows, L.v.H - 2 * p, L.v.W - 2 * p, L.v.C, p, dst));
+  DCGP_TRY(pad_images(ctx, stream, src, rows, g.H - 2 * p, g.W - 2 * p, L.v.C, p, dst));
   m->pad_in[li] = dst;
   *out = dst;
+  return DCGP_OK;
+}
+
+// Dilation (dcgp_model_set_dilation): the checks of every forward of a model with a dilated layer, before anything is enqueued (a handful of
+// integers; nothing is remembered, so no later call can make them stale).  The phase geometry in LayerState::v is this file's own doing; what is
+// checked is that the layers around a dilated layer take and give its TRUE sizes: they size the split batch, the image-layout outputs and the
+// reverse walk's buffers.
+int check_dilation(dcgp_model* m) {
+  if (!m->any_dil) return DCGP_OK;
+  dcgp_ctx* ctx = m->ctx;
+  const int nl = (int)m->layers.size();
+  if (m->shard_global > 0)
+    return ctx_fail(ctx, DCGP_ERR_ARG, "dilation: a sharded model (dcgp_model_set_shard) takes no dilated layer: the noise counters of the un-sharded batch are not laid out for the phase sub-images");
+  for (int li = 0; li < nl && li < 8; ++li) {
+    const int d = m->dil[li];
+    if (d == 1) continue;
+    const LayerState& L = *m->layers[li];
+    const dcgp_model::Geom g = m->geom(li);
+    if (L.is_head || L.v.s != 1 || g.Ho < 1 || g.Wo < 1 || (g.H + d - 1) / d != L.v.H || (g.W + d - 1) / d != L.v.W)   // (set_dilation's own checks)
+      return ctx_fail(ctx, DCGP_ERR_ARG, "dilation: layer %d: dilation %d on %d x %d does not match its phase geometry %d x %d", li, d, g.H, g.W, L.v.H, L.v.W);
+    const LayerState& A = *m->layers[li + 1];   // (a conv layer is never the last: the model has its head)
+    const bool dense = A.is_head && A.v.H == 1 && A.v.W == 1;
+    const dcgp_model::Geom ga = m->geom(li + 1);
+    const int pa = li + 1 < 8 ? m->pad[li + 1] : 0;
+    if (dense ? (long)A.v.C != g.P() * L.Rout : (ga.H - 2 * pa != g.Ho || ga.W - 2 * pa != g.Wo || A.v.C != L.Rout))
+      return ctx_fail(ctx, DCGP_ERR_ARG, "dilation: layer %d takes %d x %d x %d with a padding of %d, layer %d (dilation %d) produces %d x %d x %d", li + 1,
+                      ga.H, ga.W, A.v.C, pa, li, d, g.Ho, g.Wo, L.Rout);
+    if (li == 0) continue;
+    const LayerState& B = *m->layers[li - 1];
+    const dcgp_model::Geom gb = m->geom(li - 1);
+    const int p = m->pad[li];
+    if (B.is_head || gb.Ho + 2 * p != g.H || gb.Wo + 2 * p != g.W || B.Rout != L.v.C)
+      return ctx_fail(ctx, DCGP_ERR_ARG, "dilation: layer %d reads %d x %d x %d, layer %d produces %d x %d x %d and the padding is %d", li, g.H, g.W, L.v.C,
+                      li - 1, gb.Ho, gb.Wo, B.Rout, p);
+  }
+  return DCGP_OK;
+}
+
+// the phase sub-images of layer li's (padded) input (rows images) on `stream`: a workspace of the model, layer 0's per bank
+int split_input(dcgp_model* m, hipStream_t stream, int li, int bank, const double* src, long rows, const double** out) {
+  dcgp_ctx* ctx = m->ctx;
+  const LayerState& L = *m->layers[li];
+  const int d = m->dil[li];
+  const std::string name = "m" + std::to_string(m->id) + "_" + std::to_string(li) + "_Xs2b" + (li == 0 ? "_b" + std::to_string(bank) : std::string());
+  const dcgp_model::Geom g = m->geom(li);
+  double* dst = (double*)ws_get(ctx, name, (size_t)rows * d * d * L.v.H * L.v.W * L.v.C * sizeof(double));
+  if (!dst) return DCGP_ERR_ALLOC;
+  DCGP_TRY(s2b_images(ctx, stream, src, rows, g.H, g.W, L.v.C, d, dst));
+  m->dil_in[li] = dst;
+  *out = dst;
+  return DCGP_OK;
+}
+
+// A dilated conv layer of the data path (run_layer's arguments; F: the phase sub-images split_input left, `rows` and `n_mod` still count images).
+// conv_forward runs on rows * d^2 sub-images into phase-layout buffers (m->dil_out[li]; a mixed layer's latent triple stays in phase layout, the
+// reverse pass reads it there), batch-to-space then writes outs[li] in image layout: what the next layer, the head and keep_outputs see.  The replicas
+// of a de-duplicated first layer are phase-layout batches of N d^2 rows each, and [S][N d^2] is [S N][d^2]: one batch-to-space call covers them.
+// Explicit noise arrives in image layout [rows][P R] and is split the same way, a phantom output's noise being zero.
+int run_dilated_layer(dcgp_model* m, const StepPlan& p, const StepIn& in, int li, const double* F, int rows, int n_mod, int phase, int* out_rows_p) {
+  dcgp_ctx* ctx = m->ctx;
+  LayerState& L = *m->layers[li];
+  const std::string pfx = model_pfx(m) + std::to_string(li) + "_";
+  const int d = m->dil[li], dd = d * d;
+  const dcgp_model::Geom g = m->geom(li);
+  const bool expand = in.dedup && li == 0;
+  const int out_rows = expand ? in.S * in.N : rows;
+  if ((long)out_rows * dd > 0x7fffffffL) return ctx_fail(ctx, DCGP_ERR_ARG, "dilation: layer %d: %d rows x %d phases exceed 2^31 - 1", li, out_rows, dd);
+  const long lat_width = (long)L.v.P * L.R;                       // per sub-image
+  const size_t n_ph = (size_t)out_rows * dd * L.v.P * L.Rout;     // phase layout, phantoms included
+  DCGP_TRY(ensure_out(m, li, out_rows, (int)(g.P() * L.Rout)));
+  if (L.mix_W) DCGP_TRY(L.ensure_latent((size_t)out_rows * dd * lat_width));
+  auto& o = m->outs[li];
+  auto& ph = m->dil_out[li];
+  ph.sample = (double*)ws_get(ctx, pfx + "dil_sample", n_ph * sizeof(double));
+  if (!ph.sample) return DCGP_ERR_ALLOC;
+  ph.mean = ph.var = nullptr;
+  if (m->keep_outputs) {
+    ph.mean = (double*)ws_get(ctx, pfx + "dil_mean", n_ph * sizeof(double));
+    ph.var = (double*)ws_get(ctx, pfx + "dil_var", n_ph * sizeof(double));
+    if (!ph.mean || !ph.var) return DCGP_ERR_ALLOC;
+  }
+  const double* z = in.zs ? in.zs[li] : nullptr;
+  if (z && (phase & 2)) {
+    double* zs = (double*)ws_get(ctx, pfx + "dil_z", (size_t)out_rows * dd * lat_width * sizeof(double));
+    if (!zs) return DCGP_ERR_ALLOC;
+    DCGP_TRY(s2b_images(ctx, ctx->stream, z, out_rows, g.Ho, g.Wo, L.R, d, zs));
+    z = zs;
+  }
+  hipEvent_t fdone = (li == 0 && p.chain_beside()) ? m->ev_factor[p.bank] : nullptr;
+  hipEvent_t pdone = p.chain_beside() ? m->ev_prep[p.bank][li] : nullptr;
+  RngMap rm;   // (a sharded model takes no dilated layer: check_dilation)
+  DCGP_TRY(conv_forward(ctx, L, F, rows * dd, n_mod * dd, expand ? in.S : 1, (long)in.N * dd * lat_width, z, in.seed, (uint32_t)(li + 1 + 64 * ctx->rank), m->jitter,
+                        ph.sample, ph.mean, ph.var, pfx, fdone, pdone, phase, m->keep_state, &rm, li == 0 ? (int)p.first_one_launch : -1, nullptr, 0, 0));
+  *out_rows_p = out_rows;
+  if (!(phase & 2)) return DCGP_OK;
+  DCGP_TRY(b2s_images(ctx, ctx->stream, ph.sample, 1, out_rows, g.Ho, g.Wo, L.Rout, d, o.sample));
+  if (m->keep_outputs) {
+    DCGP_TRY(b2s_images(ctx, ctx->stream, ph.mean, 1, out_rows, g.Ho, g.Wo, L.Rout, d, o.mean));
+    DCGP_TRY(b2s_images(ctx, ctx->stream, ph.var, 1, out_rows, g.Ho, g.Wo, L.Rout, d, o.var));
+  }
   return DCGP_OK;
 }
 
@@ -307,6 +413,7 @@ int run_layer(dcgp_model* m, const StepPlan& p, const StepIn& in, int li, const 
   const double* z = in.zs ? in.zs[li] : nullptr;
   hipEvent_t fdone = (li == 0 && p.chain_beside()) ? m->ev_factor[p.bank] : nullptr;   // later layers are stream-ordered behind layer 0
   hipEvent_t pdone = p.chain_beside() ? m->ev_prep[p.bank][li] : nullptr;
+  if (!L.is_head && m->dil_of(li) > 1) return run_dilated_layer(m, p, in, li, F, rows, n_mod, phase, out_rows_p);
   if (!L.is_head) {
     const int width = L.v.P * L.Rout, lat_width = L.v.P * L.R;   // channels leaving the layer / its GPs (the same unless the layer is mixed, mix.hip)
     const bool expand = in.dedup && li == 0;          // N distinct images -> S*N sampled rows
@@ -488,6 +595,7 @@ int enqueue_layers(dcgp_model* m, const StepPlan& p, const StepIn& in, bool earl
     int out_rows = 0;
     if (last && join_early && kl_join) HIP_TRY(ctx, hipStreamWaitEvent(p.main_s, m->ev_kl[bank], 0));
     if (li > 0 && m->pad[li] > 0) DCGP_TRY(pad_input(m, p.main_s, li, bank, F, rows, &F));   // (layer 0's: forward_all)
+    if (li > 0 && m->dil_of(li) > 1) DCGP_TRY(split_input(m, p.main_s, li, bank, F, rows, &F));   // pad, then split (layer 0's: forward_all)
     DCGP_TRY(run_layer(m, p, in, li, F, rows, n_mod, (li == 0 && early0) ? 2 : 3, &head_swept,
                        (last && in.need_kl && m->kl_in_tail[bank]) ? &offer : nullptr, &out_rows));
     if (li == 0 && m->gkl_state && p.mark == ForkMark::BehindFirstLayer)
@@ -516,10 +624,11 @@ int forward_all(dcgp_model* m, const double* X, int N, int S, const double* cons
     return ctx_fail(ctx, DCGP_ERR_ARG, "forward: %d images from image %d on overrun the declared global batch of %d (dcgp_model_set_shard)", N,
                     m->shard_lo, m->shard_global);
   DCGP_TRY(check_padding(m));
+  DCGP_TRY(check_dilation(m));
   for (int li = 0; li + 1 < nl; ++li) {   // a mixed layer's maps are the next layer's channels (a dense head's single patch: all of them)
     const LayerState &A = *m->layers[li], &B = *m->layers[li + 1];
     const bool dense = B.is_head && B.v.H == 1 && B.v.W == 1;
-    if (A.mix_W && B.v.C != (dense ? A.v.P : 1) * A.Rout)
+    if (A.mix_W && B.v.C != (dense ? m->geom(li).P() : 1) * A.Rout)
       return ctx_fail(ctx, DCGP_ERR_ARG, "forward: layer %d is mixed into %d maps, layer %d takes C = %d channels", li, A.Rout, li + 1, B.v.C);
   }
   DCGP_TRY(ensure_events(m));
@@ -539,6 +648,8 @@ int forward_all(dcgp_model* m, const double* X, int N, int S, const double* cons
   // a padded first layer: X is padded once, here -- the early sweep, the de-duplicated first layer and the replicas of a tiled batch then read an
   // ordinary image.  Per bank: two steps may be in flight.
   if (m->pad[0] > 0) DCGP_TRY(pad_input(m, p.main_s, 0, p.bank, X, N, &in.X));
+  // a dilated first layer: the (padded) batch is split into its phase sub-images once, here, for the same readers
+  if (m->dil[0] > 1) DCGP_TRY(split_input(m, p.main_s, 0, p.bank, in.X, N, &in.X));
 
   bool early0 = false, head_swept = false, kl_join = false;
   if (p.reuse) ++m->chain_skips;   // (never pipelined: p.main_s is ctx->stream as the caller left it)
@@ -609,7 +720,38 @@ int dcgp_model_set_shard(dcgp_model* model, int first_image, int global_batch) {
   if (!model) return DCGP_ERR_ARG;
   if (global_batch < 0 || first_image < 0 || (global_batch > 0 && first_image >= global_batch))
     return ctx_fail(model->ctx, DCGP_ERR_ARG, "set_shard: first image %d of a global batch of %d", first_image, global_batch);
+  if (global_batch > 0 && model->any_dil)
+    return ctx_fail(model->ctx, DCGP_ERR_ARG, "set_shard: the model has a dilated layer (dcgp_model_set_dilation); a sharded model takes none");
   model->shard_lo = first_image; model->shard_global = global_batch;
+  return DCGP_OK;
+}
+
+int dcgp_model_set_dilation(dcgp_model* model, int layer, int d) {
+  if (!model) return DCGP_ERR_ARG;
+  dcgp_ctx* ctx = model->ctx;
+  if (layer < 0 || layer >= (int)model->layers.size() || layer >= 8) return ctx_fail(ctx, DCGP_ERR_ARG, "set_dilation: no layer %d", layer);
+  if (d < 1) return ctx_fail(ctx, DCGP_ERR_ARG, "set_dilation: layer %d: the dilation must be >= 1, got %d", layer, d);
+  LayerState& L = *model->layers[layer];
+  if (d > 1 && L.is_head) return ctx_fail(ctx, DCGP_ERR_ARG, "set_dilation: layer %d is the head, only conv layers take a dilation", layer);
+  if (d > 1 && L.v.s != 1) return ctx_fail(ctx, DCGP_ERR_ARG, "set_dilation: layer %d has stride %d, a dilated layer has stride 1", layer, L.v.s);
+  if (d > 1 && model->shard_global > 0)
+    return ctx_fail(ctx, DCGP_ERR_ARG, "set_dilation: layer %d: a sharded model (dcgp_model_set_shard) takes no dilated layer", layer);
+  if (model->enq_seq != model->col_seq) return ctx_fail(ctx, DCGP_ERR_ARG, "set_dilation: enqueued steps are still to be collected");
+  if (d == model->dil[layer]) return DCGP_OK;
+  const dcgp_model::Geom g = model->geom(layer);   // the true (padded) size: the layer was added with it
+  const int span = d * (L.v.f - 1) + 1;
+  if (span > g.H || span > g.W)
+    return ctx_fail(ctx, DCGP_ERR_ARG, "set_dilation: layer %d: a window of %d taps %d apart spans %d pixels, its padded input is %d x %d", layer, L.v.f, d,
+                    span, g.H, g.W);
+  // the patch count is part of the layout of the layer's gradient block, which is fixed by the first reverse pass or sharded step
+  if (L.gZ || L.pstage || L.hyp)
+    return ctx_fail(ctx, DCGP_ERR_ARG, "set_dilation: layer %d has taken a gradient step; set its dilation before the first", layer);
+  model->dil_H[layer] = g.H; model->dil_W[layer] = g.W;
+  model->dil[layer] = d;
+  L.v.set((g.H + d - 1) / d, (g.W + d - 1) / d, L.v.C, L.v.f, 1);   // what the kernels see from here on: the phase geometry (d == 1: the true size again)
+  model->any_dil = false;
+  for (int q : model->dil) model->any_dil = model->any_dil || q != 1;
+  model->pad_ok = false;    // the padding chain reads the true sizes
   return DCGP_OK;
 }
 
@@ -618,7 +760,7 @@ int dcgp_model_set_input_padding(dcgp_model* model, int layer, int pad) {
   dcgp_ctx* ctx = model->ctx;
   if (layer < 0 || layer >= (int)model->layers.size() || layer >= 8) return ctx_fail(ctx, DCGP_ERR_ARG, "set_input_padding: no layer %d", layer);
   if (pad < 0) return ctx_fail(ctx, DCGP_ERR_ARG, "set_input_padding: layer %d: the padding must be >= 0, got %d", layer, pad);
-  const ViewGeom& v = model->layers[layer]->v;
+  const dcgp_model::Geom v = model->geom(layer);   // (the true size: a dilated layer's own v is its phase geometry)
   if (v.H - 2 * pad < 1 || v.W - 2 * pad < 1)
     return ctx_fail(ctx, DCGP_ERR_ARG, "set_input_padding: layer %d was added as %d x %d, smaller than its border of %d (add the layer with the padded size)",
                     layer, v.H, v.W, pad);
@@ -1173,7 +1315,7 @@ int eval_batches(dcgp_model* model, const double* X, int N_total, int batch, int
     // noise: per layer the batches' [S][V n_b][D_l] tables back to back, batch b's from S * V * lo * D_l on (V = 1 without views)
     for (int l = 0; l < nl && zs; ++l) {
       const LayerState& L = *model->layers[l];
-      const long D = L.is_head ? L.R : (long)L.v.P * L.R;
+      const long D = L.is_head ? L.R : model->geom(l).P() * L.R;   // (image layout: a dilated layer's true patch count)
       zb[l] = zs[l] ? zs[l] + (long)S * V * lo * D : nullptr;
     }
     // the batch forward_all sees: the caller's images, or their views (the workspace is rewritten behind the previous batch's tail, on its stream)

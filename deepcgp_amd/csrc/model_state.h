@@ -107,8 +107,32 @@ struct dcgp_model {
   int pad[8] = {};
   bool any_pad = false, pad_ok = false;
   const double* pad_in[8] = {};
-  // one image of the caller's X: layer 0's geometry without its padding
-  long image_len() const { const auto& v = layers[0]->v; return (long)(v.H - 2 * pad[0]) * (v.W - 2 * pad[0]) * v.C; }
+  // dilation of a conv layer (dcgp_model_set_dilation; dilate.hip): the window's taps sit dil[l] pixels apart.  The layer is added with its true
+  // (padded) input size like any other; dcgp_model_set_dilation keeps that size here (dil_H, dil_W) and switches LayerState::v to the PHASE
+  // geometry -- H = ceil(Hp / d), W = ceil(Wp / d) -- so v is what the kernels see: the layer runs as an ordinary VALID layer on the rows * d^2
+  // phase sub-images of its input (space-to-batch), and its outputs go back to image layout behind it.
+  // dil_in[l]: the split input as the most recent forward left it (a workspace; layer 0's per bank), read by the reverse pass like pad_in[l].
+  // dil_out[l]: the layer's (sample, mean, var) in phase layout, as its kernels wrote them (outs[l] holds the image layout).
+  int dil[8] = {1, 1, 1, 1, 1, 1, 1, 1};
+  int dil_H[8] = {}, dil_W[8] = {};   // the true size of a layer with dil[l] > 1
+  bool any_dil = false;
+  const double* dil_in[8] = {};
+  struct PhaseOut { double *sample = nullptr, *mean = nullptr, *var = nullptr; } dil_out[8];
+  // A layer's true geometry: its (padded) input H x W and its output Ho x Wo, in pixels of the image -- LayerState::v itself unless the layer is
+  // dilated.  Everything that derives the caller's image size or an output width goes through here.  It depends on the layer alone.
+  struct Geom { int H = 0, W = 0, Ho = 0, Wo = 0; long P() const { return (long)Ho * Wo; } };
+  int dil_of(int li) const { return li >= 0 && li < 8 ? dil[li] : 1; }
+  Geom geom(int li) const {
+    const ViewGeom& v = layers[li]->v;
+    const int d = dil_of(li);
+    Geom g;
+    if (d <= 1) { g.H = v.H; g.W = v.W; g.Ho = v.Ho; g.Wo = v.Wo; return g; }
+    g.H = dil_H[li]; g.W = dil_W[li];
+    g.Ho = g.H - d * (v.f - 1); g.Wo = g.W - d * (v.f - 1);
+    return g;
+  }
+  // one image of the caller's X: layer 0's true geometry without its padding
+  long image_len() const { const Geom g = geom(0); return (long)(g.H - 2 * pad[0]) * (g.W - 2 * pad[0]) * layers[0]->v.C; }
 
   ~dcgp_model() {
     for (void* p : {(void*)ds_X, ds_Y, (void*)run_idx, (void*)run_X, run_Y, (void*)d_eval_views, (void*)d_clip}) dev_free(ctx, p);
@@ -166,6 +190,10 @@ int model_backward_data(dcgp_model* model, const double* X, int N, int S, int de
 // src [reps][rows][H + 2p][W + 2p][C] summed over the replicas
 int pad_images(dcgp_ctx* ctx, hipStream_t stream, const double* src, long rows, int H, int W, int C, int p, double* dst);
 int crop_images(dcgp_ctx* ctx, hipStream_t stream, const double* src, int reps, long rows, int H, int W, int C, int p, double* dst);
+// dilate.hip: space-to-batch, dst [rows d^2][ceil(H / d)][ceil(W / d)][C] <- src [rows][H][W][C] with the fill written as zeros / its inverse,
+// dst [rows][H][W][C] <- src [reps][rows d^2][..][..][C] summed over the replicas; a fill entry of src is never read
+int s2b_images(dcgp_ctx* ctx, hipStream_t stream, const double* src, long rows, int H, int W, int C, int d, double* dst);
+int b2s_images(dcgp_ctx* ctx, hipStream_t stream, const double* src, int reps, long rows, int H, int W, int C, int d, double* dst);
 // augment.hip: nullptr, or what is wrong with an augmentation's geometry / the augmenting gather of a run's step (rows idx_dev[0 .. batch) of the
 // resident set into run_X on ctx->stream, image b with the draw of (seed, b); targets as gather_batch_kernel copies them)
 const char* augment_geometry_error(int H, int W, int C, int max_shift);

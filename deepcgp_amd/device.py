@@ -118,8 +118,10 @@ _SIGS = {
     "dcgp_model_set_grad_shards": [_vp, _i],
     "dcgp_model_set_shard": [_vp, _i, _i],
     "dcgp_model_set_input_padding": [_vp, _i, _i],
+    "dcgp_model_set_dilation": [_vp, _i, _i],
     "dcgp_model_set_mean_filter": [_vp, _i, _vp, _i],
     "dcgp_debug_conv_mean_time": [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _dp],
+    "dcgp_debug_dilate_time": [_vp, _i, _i, _i, _i, _i, _i, _dp],
     "dcgp_model_set_mixing": [_vp, _i, _vp, _i, _i],
     "dcgp_mix_forward": [_vp, _vp, _i, _i, _vp, _vp, _vp, C.c_long, C.c_long, _i, C.c_long, C.c_long, _vp, _vp, _vp],
     "dcgp_mix_backward": [_vp, _vp, _i, _i, _vp, _vp, C.c_long, _vp, _vp],

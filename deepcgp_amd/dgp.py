@@ -213,6 +213,9 @@ class DGP_Base:
         if getattr(base, "ARD", False):
             ls = np.ascontiguousarray(base.lengthscales, np.float64)
             ctx._check(L.dcgp_model_set_param(self._model, len(self.layers) - 1, b"ard_lengthscales", ls.ctypes.data, ls.size))
+        for li, l in enumerate(self.layers[:-1]):  # dilation: the layer was added with its true size; the device runs it on the phase sub-images
+            if getattr(l.view, "dilation", 1) > 1:
+                ctx._check(L.dcgp_model_set_dilation(self._model, li, int(l.view.dilation)))
         for li, l in enumerate(self.layers):      # zero padding: the layer's input is its predecessor's output (X for layer 0) plus the border
             v = l.view if li < len(self.layers) - 1 else getattr(l.kern, "view", None)
             if getattr(v, "padding", 0):
@@ -949,9 +952,10 @@ class DGP_Base:
         if layer_input.ndim == 2:
             return layer_input
         head = li == len(self.layers) - 1
-        f = (l.kern.view if head else l.view).filter_size
-        from .models import draw_patches
-        return np.ascontiguousarray(draw_patches(layer_input, int(candidates) * l.num_inducing, f, self._reselect_rng(seed, 1 + li)))
+        v = l.kern.view if head else l.view
+        from .models import draw_patches      # (a dilated layer: its candidates are dilated windows of what it receives)
+        return np.ascontiguousarray(draw_patches(layer_input, int(candidates) * l.num_inducing, v.filter_size, self._reselect_rng(seed, 1 + li),
+                                                 dilation=getattr(v, "dilation", 1)))
 
     def reselect_inducing(self, layers=None, images=1000, seed=0, candidates=100, min_variance=JITTER):
         """Choose the inducing inputs of ``layers`` (default: all) again, from what each layer receives NOW and under the kernel it has NOW,
@@ -1055,6 +1059,9 @@ class DGP_Base:
             if getattr(l, "mixing", None) is not None:
                 raise NotImplementedError("full-covariance predictions through a mixed layer are not provided (layer %d has a mixing W %r)"
                                           % (li, np.shape(l.mixing)))
+            if getattr(l.view, "dilation", 1) > 1:
+                raise NotImplementedError("full-covariance predictions through a dilated layer are not provided (layer %d has dilation %d)"
+                                          % (li, l.view.dilation))
         self.pull_parameters()
         from .layers import reparameterize_full_cov
         X = np.asarray(X, np.float64)

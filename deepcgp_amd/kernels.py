@@ -355,13 +355,13 @@ def kmeans(points, k, max_iter=300, tol=1e-4, rng=None, distinct_start=False):
     return dC.numpy()
 
 
-def _cluster_patches(NHWC_X, M, patch_size):
+def _cluster_patches(NHWC_X, M, patch_size, dilation=1):
     """Inducing patches of PatchInducingFeatures.from_images (conv_gp/kernels.py:147-164): k-means centres of 100 * M patches cut at
     random from random images.  The sample is one vectorised gather (deepcgp_amd.models.draw_patches); Lloyd's iterations run
     on the device (``kmeans``), started from M DISTINCT patches -- on images with large constant regions (MNIST borders) a
     plain random start picks many identical rows, whose clusters then stay empty and leave duplicate inducing patches."""
     from .models import draw_patches
-    sample = draw_patches(np.asarray(NHWC_X, np.float64), 100 * M, patch_size)
+    sample = draw_patches(np.asarray(NHWC_X, np.float64), 100 * M, patch_size, dilation=dilation)
     return kmeans(sample, M, distinct_start=True)
 
 
@@ -433,10 +433,10 @@ def greedy_variance(points, k, base_kernel, min_variance=JITTER, return_info=Fal
     return Z
 
 
-def _greedy_patches(NHWC_X, M, patch_size, base_kernel, min_variance):
+def _greedy_patches(NHWC_X, M, patch_size, base_kernel, min_variance, dilation=1):
     """The greedy counterpart of ``_cluster_patches``: the same 100 * M patches (same generator, same order), M of them selected."""
     from .models import draw_patches
-    sample = draw_patches(np.asarray(NHWC_X, np.float64), 100 * M, patch_size)
+    sample = draw_patches(np.asarray(NHWC_X, np.float64), 100 * M, patch_size, dilation=dilation)
     return greedy_variance(sample, M, base_kernel, min_variance=min_variance, return_info=True)
 
 
@@ -518,16 +518,17 @@ class PatchInducingFeatures:
         return self.Z.shape[0]
 
     @classmethod
-    def from_images(cls, NHWC_X, M, patch_size, method="kmeans", base_kernel=None, min_variance=JITTER):
+    def from_images(cls, NHWC_X, M, patch_size, method="kmeans", base_kernel=None, min_variance=JITTER, dilation=1):
         """``method="kmeans"``: the reference's recipe, centres of 100 M random patches.  ``"greedy"``: M of the same patches by conditional
-        variance under ``base_kernel`` (``greedy_variance``); the selection's info stays on the feature as ``init_info``."""
+        variance under ``base_kernel`` (``greedy_variance``); the selection's info stays on the feature as ``init_info``.  ``dilation``: the
+        candidates are the layer's dilated windows (taps that many pixels apart)."""
         if method == "kmeans":
-            return cls(_cluster_patches(NHWC_X, M, patch_size))
+            return cls(_cluster_patches(NHWC_X, M, patch_size, dilation))
         if method != "greedy":
             raise ValueError("from_images: method must be 'kmeans' or 'greedy', got %r" % (method,))
         if base_kernel is None:
             raise ValueError("from_images: method 'greedy' needs the layer's base_kernel")
-        Z, info = _greedy_patches(NHWC_X, M, patch_size, base_kernel, min_variance)
+        Z, info = _greedy_patches(NHWC_X, M, patch_size, base_kernel, min_variance, dilation)
         feature = cls(Z)
         feature.init_info = info
         return feature

@@ -313,10 +313,16 @@ class ConvLayer(Layer):
             return self._conditional_full_cov(ND_X)
         return self._forward(ND_X, None)[1:]
 
+    def _refuse_dilated_full_cov(self):
+        d = getattr(self.view, "dilation", 1)
+        if d > 1:
+            raise NotImplementedError("full_cov=True through a dilated layer (dilation %d) is not provided" % d)
+
     def _conditional_full_cov(self, ND_X):
         """conv_gp/layers.py:114-126 with full_cov=True: mean N x num_outputs, var N x N x num_outputs (per output = (patch, gp)
         an N x N covariance over the inputs; conditionals._conditional_full_cov documents the per-patch reading).  Off the training
         path (predict_f_full_cov-style calls): composed from the operator-level device calls."""
+        self._refuse_dilated_full_cov()
         ND_X = np.ascontiguousarray(ND_X, np.float64)
         N, v = ND_X.shape[0], self.view
         X4 = ND_X.reshape(N, v.input_size[0], v.input_size[1], self.feature_maps_in)
@@ -339,6 +345,8 @@ class ConvLayer(Layer):
 
     def _forward(self, ND_X, z):
         """(sample or None, mean, var), each N x num_outputs."""
+        if getattr(self.view, "dilation", 1) > 1:
+            return self._forward_dilated(ND_X, z)
         if self.mixing is None:
             return self._forward_gp(ND_X, z)
         # a mixed layer: the G latent GPs' conditional, the sample in the latent space, then the three mixes in one operator call (csrc/mix.hip)
@@ -354,6 +362,42 @@ class ConvLayer(Layer):
             mean = mean + extra
             smp = None if smp is None else smp + extra
         return smp, mean, var
+
+    def _phase_twin(self):
+        """This layer on the phase sub-images of a dilated view: the same parameters, kernel and mean function on an undilated, unpadded
+        view of ``view.phase_size`` (a shallow copy; the centre tap of a sub-image patch is the centre tap of the dilated window)."""
+        import copy
+        from .views import FullView
+        v = self.view
+        twin = copy.copy(self)
+        twin.view = FullView(v.phase_size, v.filter_size, v.feature_maps, 1)
+        twin.patch_count = twin.view.patch_count
+        twin.num_outputs = twin.patch_count * self.feature_maps_out
+        twin.num_latent_outputs = twin.patch_count * self.gp_count
+        twin.conv_kernel = MultiOutputConvKernel(self.base_kernel, int(np.prod(v.phase_size)) * v.feature_maps, patch_count=twin.patch_count)
+        return twin
+
+    def _forward_dilated(self, ND_X, z):
+        """``_forward`` through a dilated view: pad, split into the d^2 phase sub-images on the host (``view.split``), the undilated layer
+        on those (``_phase_twin``), and the outputs merged back into image order; a patch that touched the fill is dropped.  Noise arrives
+        in image order [N, P * gp_count] and is split the same way."""
+        v = self.view
+        d, f = v.dilation, v.filter_size
+        ND_X = np.ascontiguousarray(ND_X, np.float64)
+        N = ND_X.shape[0]
+        if ND_X.shape[1] != v.input_size[0] * v.input_size[1] * self.feature_maps_in:
+            raise ValueError("expected N x %d inputs, got %s" % (v.input_size[0] * v.input_size[1] * self.feature_maps_in, ND_X.shape))
+        Ho, Wo = v.out_image_height, v.out_image_width
+        if N == 0:
+            return (None if z is None else np.zeros((0, self.num_outputs))), np.zeros((0, self.num_outputs)), np.zeros((0, self.num_outputs))
+        Xs = v.split(v.pad(ND_X.reshape(N, v.input_size[0], v.input_size[1], self.feature_maps_in)))
+        zs = None if z is None else v.split(np.reshape(z, (N, Ho, Wo, self.gp_count))).reshape(N * d * d, -1)
+        smp, mean, var = self._phase_twin()._forward(Xs.reshape(N * d * d, -1), zs)
+        Hq, Wq = v.phase_size[0] - f + 1, v.phase_size[1] - f + 1
+
+        def back(a):
+            return None if a is None else v.merge(a.reshape(N * d * d, Hq, Wq, self.feature_maps_out), Ho, Wo).reshape(N, self.num_outputs)
+        return back(smp), back(mean), back(var)
 
     def _forward_gp(self, ND_X, z):
         """The layer's gp_count GPs: (sample or None, mean, var), each N x num_latent_outputs -- with the mean function unless the layer is mixed."""

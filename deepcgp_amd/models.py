@@ -10,7 +10,7 @@ from .likelihoods import MultiClass, Softmax
 from .mean_functions import Conv2dMean, IdentityConv2dMean  # noqa: F401  (the names conv_gp/models.py:11 imports)
 from .mean_functions import MEAN_FILTERS, LinearConv2dMean, conv_mean_filter
 from .views import FullView
-from .arguments import parse_inducing_init, parse_latent_gps, parse_paddings
+from .arguments import parse_dilations, parse_inducing_init, parse_latent_gps, parse_paddings
 
 
 def parse_ints(int_string):
@@ -29,13 +29,14 @@ BASE_KERNELS = {"rbf": RBF, "acos": ArcCosine, "matern32": Matern32, "matern52":
 
 def build_layers_from_spec(spec):
     """Layers of a neutral model spec.  An entry's optional ``pad`` is the zero padding of its input; its ``H``, ``W`` stay unpadded.  A conv
+    entry's optional ``dil`` is its dilation (taps that many pixels apart, stride 1).  A conv
     entry's optional ``mix_W`` [R, Rout] mixes its R GPs into Rout maps (``mix_trainable``, default True: whether the optimiser moves it); its
     mean function then has Rout maps and the next entry's ``C`` is Rout."""
     if spec["head"].get("kernel", "conv") == "rbf" and spec["head"].get("pad", 0):
         raise ValueError("--paddings: the dense head of --last-kernel rbf takes no padding (pad %d)" % spec["head"]["pad"])
     layers = []
     for c in spec["convs"]:
-        view = FullView((c["H"], c["W"]), c["f"], c["C"], c["s"], padding=c.get("pad", 0))
+        view = FullView((c["H"], c["W"]), c["f"], c["C"], c["s"], padding=c.get("pad", 0), dilation=c.get("dil", 1))
         kind = c.get("base", "rbf")
         if kind not in BASE_KERNELS:
             raise ValueError("Not a valid base-kernel value")
@@ -466,30 +467,33 @@ def zero_pad(NHWC_X, p):
     return NHWC_X if not p else np.pad(NHWC_X, ((0, 0), (p, p), (p, p), (0, 0)))
 
 
-def identity_conv(NHWC_X, filter_size, feature_maps_in, feature_maps_out, stride, count=1000):
+def identity_conv(NHWC_X, filter_size, feature_maps_in, feature_maps_out, stride, count=1000, dilation=1):
     """Propagate random images through IdentityConv2dMean to initialise the next layer
-    (conv_gp/models.py:29-33, conv_gp/mean_functions.py:6-26)."""
+    (conv_gp/models.py:29-33, conv_gp/mean_functions.py:6-26).  ``dilation`` d: the window spans d (f - 1) + 1 pixels, its centre tap sits
+    at offset d * (f // 2)."""
     X = NHWC_X[np.random.choice(np.arange(NHWC_X.shape[0]), size=min(count, NHWC_X.shape[0]))]
     n, H, W, C = X.shape
-    Ho, Wo = (H - filter_size) // stride + 1, (W - filter_size) // stride + 1
-    c0 = filter_size // 2
+    span = dilation * (filter_size - 1) + 1
+    Ho, Wo = (H - span) // stride + 1, (W - span) // stride + 1
+    c0 = dilation * (filter_size // 2)
     centre = X[:, c0:c0 + (Ho - 1) * stride + 1:stride, c0:c0 + (Wo - 1) * stride + 1:stride, :].sum(-1)
     return np.repeat(centre[..., None], feature_maps_out, axis=-1)
 
 
-def filter_conv(NHWC_X, conv_filter, stride, count=1000):
+def filter_conv(NHWC_X, conv_filter, stride, count=1000, dilation=1):
     """``identity_conv`` for a layer with a ``LinearConv2dMean``: the same random-subset draw, propagated through ``conv_filter``
     [f, f, Cin, Cout] (VALID, NHWC) -- what the layer emits at initialisation, where q_mu is zero.  Host NumPy, one product per filter tap."""
     X = NHWC_X[np.random.choice(np.arange(NHWC_X.shape[0]), size=min(count, NHWC_X.shape[0]))]
     W = np.asarray(conv_filter, np.float64)
     f, _, Cin, Cout = W.shape
     n, H, Wd, C = X.shape
-    Ho, Wo = (H - f) // stride + 1, (Wd - f) // stride + 1
+    d = int(dilation)                                   # taps d pixels apart
+    Ho, Wo = (H - d * (f - 1) - 1) // stride + 1, (Wd - d * (f - 1) - 1) // stride + 1
     out = np.zeros((n, Ho, Wo, Cout))
     for kh in range(f):
         for kw in range(f):
             if np.any(W[kh, kw]):
-                out += X[:, kh:kh + (Ho - 1) * stride + 1:stride, kw:kw + (Wo - 1) * stride + 1:stride, :] @ W[kh, kw]
+                out += X[:, d * kh:d * kh + (Ho - 1) * stride + 1:stride, d * kw:d * kw + (Wo - 1) * stride + 1:stride, :] @ W[kh, kw]
     return out
 
 
@@ -534,13 +538,16 @@ def read_checkpoint(path, n_layers):
     return int(raw.get("global_step", 0)), records
 
 
-def draw_patches(NHWC_X, count, f, rng=np.random):
+def draw_patches(NHWC_X, count, f, rng=np.random, dilation=1):
     """``count`` f x f patches, each cut at a random position of a random image: [count, f*f*C] in the (kh, kw, c) element order of
-    FullView -- the sample PatchInducingFeatures.from_images clusters (conv_gp/kernels.py:139-164), drawn in one gather."""
+    FullView -- the sample PatchInducingFeatures.from_images clusters (conv_gp/kernels.py:139-164), drawn in one gather.  ``dilation`` d:
+    the patches are dilated windows, taps d pixels apart (the same draws over the positions such a window fits)."""
     n, H, W, C = NHWC_X.shape
+    d = int(dilation)
+    span = d * (f - 1) + 1
     img = rng.randint(0, n, size=count)
-    top, left = rng.randint(0, H - f, size=count), rng.randint(0, W - f, size=count)    # upper bound exclusive, as the reference draws them
-    dy, dx = np.arange(f)[None, :, None], np.arange(f)[None, None, :]
+    top, left = rng.randint(0, H - span, size=count), rng.randint(0, W - span, size=count)    # upper bound exclusive, as the reference draws them
+    dy, dx = d * np.arange(f)[None, :, None], d * np.arange(f)[None, None, :]
     return NHWC_X[img[:, None, None], top[:, None, None] + dy, left[:, None, None] + dx, :].reshape(count, f * f * C)
 
 
@@ -569,6 +576,10 @@ class ModelBuilder(object):
         assert len(fmaps) == len(M) - 1
         convs = [(M[i], filt[i], strd[i], fmaps[i]) for i in range(len(fmaps))]
         return convs, (M[-1], filt[-1], strd[-1])
+
+    def dilations(self):
+        """--dilations: one dilation per conv layer (a head takes none); all ones without the flag."""
+        return parse_dilations(self.flags, len(parse_ints(self.flags.M)) - 1)
 
     def paddings(self):
         """--paddings: one zero-padding width per GP layer (head included); all zeros without the flag."""
@@ -633,8 +644,9 @@ class ModelBuilder(object):
             print("layer {}: greedy selection stopped at {} of M = {} inducing points (conditional variance floor {}); "
                   "the rest are filled by residual.".format(li, info["n_greedy"], M, JITTER))
 
-    def _greedy_patches(self, li, images, M, f, base_kernel):
-        feature = PatchInducingFeatures.from_images(images, M, f, method="greedy", base_kernel=base_kernel)
+    def _greedy_patches(self, li, images, M, f, base_kernel, dilation=1):
+        dil_kw = {"dilation": dilation} if dilation != 1 else {}
+        feature = PatchInducingFeatures.from_images(images, M, f, method="greedy", base_kernel=base_kernel, **dil_kw)
         self._report_stall(li, feature.init_info, M)
         return feature.Z
 
@@ -649,6 +661,7 @@ class ModelBuilder(object):
         convs, (head_M, head_f, head_s) = self.stages()
         n_layers = len(convs) + 1
         pads = self.paddings()
+        dils = self.dilations()
         stored = {}
         if getattr(fl, "load_model", None) is not None:
             self.global_step, stored = read_checkpoint(self.model_path, n_layers)
@@ -667,13 +680,14 @@ class ModelBuilder(object):
             have = stored.get(li, {})
             _, H, W, C = images.shape                          # (H, W stay the unpadded size; "pad" carries the border)
             images = zero_pad(images, pads[li])                # inducing patches and the next layer's images: from what the window sees
+            dil_kw = {"dilation": dils[li]} if dils[li] != 1 else {}      # (an undilated layer: the calls of before)
             if init == "kmeans" or "Z" in have:
-                Z = have["Z"] if "Z" in have else PatchInducingFeatures.from_images(images, M, f).Z
+                Z = have["Z"] if "Z" in have else PatchInducingFeatures.from_images(images, M, f, **dil_kw).Z
             else:               # --inducing-init greedy: M of the same candidates, by conditional variance under the kernel the layer starts with
-                Z = self._greedy_patches(li, images, M, f, self._conv_base_kernel(li, have, f * f * C, ard))
+                Z = self._greedy_patches(li, images, M, f, self._conv_base_kernel(li, have, f * f * C, ard), **dil_kw)
             G = latent[li] or R                                # the layer's GPs; R stays the maps it emits
             spec["convs"].append(dict(
-                H=H, W=W, C=C, f=f, s=s, M=M, R=G, Z=Z, Z0=Z, white=white, base=fl.base_kernel, pad=pads[li],
+                H=H, W=W, C=C, f=f, s=s, M=M, R=G, Z=Z, Z0=Z, white=white, base=fl.base_kernel, pad=pads[li], dil=dils[li],
                 variance=float(have.get("variance", 5.0)), ls=self._conv_lengthscales(li, have, f * f * C, ard),     # models.py:114-117
                 q_mu=have.get("q_mu"), q_sqrt=have.get("q_sqrt"),
                 q_sqrt_scale=None if "q_sqrt" in have else 1e-5,                               # start with low variance (models.py:136-138)
@@ -685,9 +699,9 @@ class ModelBuilder(object):
                 W = have["mean_filter"] if "mean_filter" in have else conv_mean_filter(mean_kind, f, C, R)
                 spec["convs"][-1].update(mean_filter=np.array(W, np.float64).reshape(f, f, C, R), mean_trainable=train_mean)
             if mean_kind in (None, "conv2d", "centre0"):
-                images = identity_conv(images, f, C, R, s)                                      # models.py:29-33,104
+                images = identity_conv(images, f, C, R, s, **dil_kw)                            # models.py:29-33,104
             else:      # the same draw through the layer's own filter: the next layer's inducing patches are cut from what this one will emit
-                images = filter_conv(images, spec["convs"][-1]["mean_filter"], s)
+                images = filter_conv(images, spec["convs"][-1]["mean_filter"], s, **dil_kw)
         have = stored.get(n_layers - 1, {})
         _, H, W, C = images.shape
         images = zero_pad(images, pads[-1])

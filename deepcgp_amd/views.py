@@ -20,16 +20,23 @@ class View:
 class FullView(View):
     """The full view uses all patches of the image (conv_gp/views.py:18-68).  ``padding`` p >= 0: the patches of the image with p zero
     pixels added on all four sides, across all channels; ``input_size`` stays the unpadded size, ``padded_size`` is the geometry the
-    sliding window (and the device layer) sees, and ``out_image_*``, ``patch_count`` and ``as_maps`` follow it."""
+    sliding window (and the device layer) sees, and ``out_image_*``, ``patch_count`` and ``as_maps`` follow it.  ``dilation`` d >= 1
+    (stride 1 only): the window's taps sit d pixels apart -- ``rates`` of tf.extract_image_patches, conv_gp/views.py:24,37 -- so the
+    output is ``padded_size - d (f - 1)``; ``phase_size`` is ceil(padded_size / d), the geometry of the d^2 phase sub-images the device
+    layer runs on (``split`` / ``merge``: space-to-batch and its inverse on the host)."""
 
-    def __init__(self, input_size, filter_size, feature_maps, stride=1, padding=0):
+    def __init__(self, input_size, filter_size, feature_maps, stride=1, padding=0, dilation=1):
         self.input_size = list(input_size)
         self.padding = int(padding)
         if self.padding < 0:
             raise ValueError("padding must be >= 0, got %d" % self.padding)
         self.padded_size = [self.input_size[0] + 2 * self.padding, self.input_size[1] + 2 * self.padding]
         self.stride = int(stride)
-        self.dilation = 1
+        if int(dilation) != dilation or int(dilation) < 1:
+            raise ValueError("dilation must be an integer >= 1, got %r" % (dilation,))
+        self.dilation = int(dilation)
+        if self.dilation > 1 and self.stride != 1:
+            raise ValueError("dilation %d needs stride 1, got stride %d" % (self.dilation, self.stride))
         self.filter_size = int(filter_size)
         self.feature_maps = int(feature_maps)
         self.patch_shape = [self.filter_size, self.filter_size]
@@ -37,7 +44,10 @@ class FullView(View):
         self.patch_count = self._patch_count()
         self.patch_length = self._patch_length()
         if self.out_image_height <= 0 or self.out_image_width <= 0:
-            raise ValueError("filter_size %d does not fit input_size %s" % (filter_size, self.input_size))
+            raise ValueError("filter_size %d%s does not fit input_size %s" % (
+                filter_size, " with dilation %d" % self.dilation if self.dilation > 1 else "", self.input_size))
+        d = self.dilation
+        self.phase_size = [-(-self.padded_size[0] // d), -(-self.padded_size[1] // d)]
 
     def _patch_length(self):
         return self.feature_maps * int(np.prod(self.patch_shape))
@@ -46,9 +56,42 @@ class FullView(View):
         return self.out_image_height * self.out_image_width
 
     def _out_image_size(self):
-        h = (self.padded_size[0] - self.patch_shape[0]) // self.stride + 1
-        w = (self.padded_size[1] - self.patch_shape[1]) // self.stride + 1
+        span = [self.dilation * (f - 1) + 1 for f in self.patch_shape]
+        h = (self.padded_size[0] - span[0]) // self.stride + 1
+        w = (self.padded_size[1] - span[1]) // self.stride + 1
         return h, w
+
+    def split(self, NHWC):
+        """Space-to-batch: [N, H, W, C] -> [N d^2, ceil(H / d), ceil(W / d), C], sub-image (n d + a) d + b = x[n, a::d, b::d], zero
+        where a sub-image is shorter than the largest (the array itself when d == 1)."""
+        d = self.dilation
+        if d == 1:
+            return NHWC
+        x = np.asarray(NHWC, np.float64)
+        N, H, W, Cc = x.shape
+        Hs, Ws = -(-H // d), -(-W // d)
+        out = np.zeros((N, d, d, Hs, Ws, Cc))
+        for a in range(d):
+            for b in range(d):
+                sub = x[:, a::d, b::d]
+                out[:, a, b, :sub.shape[1], :sub.shape[2]] = sub
+        return out.reshape(N * d * d, Hs, Ws, Cc)
+
+    def merge(self, sub, H, W):
+        """Batch-to-space, the inverse of ``split`` on an H x W image: [N d^2, ceil(H / d), ceil(W / d), C] -> [N, H, W, C]; the
+        entries ``split`` filled are dropped."""
+        d = self.dilation
+        if d == 1:
+            return sub
+        sub = np.asarray(sub, np.float64)
+        Hs, Ws = -(-H // d), -(-W // d)
+        sub = sub.reshape(-1, d, d, Hs, Ws, sub.shape[-1])
+        out = np.empty((sub.shape[0], H, W, sub.shape[-1]))
+        for a in range(d):
+            for b in range(d):
+                t = out[:, a::d, b::d]
+                t[...] = sub[:, a, b, :t.shape[1], :t.shape[2]]
+        return out
 
     def pad(self, NHWC_X):
         """[N, H, W, C] -> [N, H + 2p, W + 2p, C] with the zero border (the array itself when p == 0)."""
@@ -68,6 +111,19 @@ class FullView(View):
             return np.zeros((P, 0, L) if pnl else (0, P, L))
         X = self.pad(X)
         H, W = self.padded_size
+        if self.dilation > 1:
+            # the dilated patches are the ordinary patches of the phase sub-images, put back in image order: patch (y, x) is patch
+            # (y // d, x // d) of phase (y % d, x % d)
+            Hs, Ws = self.phase_size
+            f, d = self.filter_size, self.dilation
+            Xs = np.ascontiguousarray(self.split(X))
+            dX = ctx.to_device(Xs)
+            Ps = (Hs - f + 1) * (Ws - f + 1)
+            sub = ctx.empty((N * d * d, Ps, L))
+            ctx._check(dev.lib().dcgp_extract_patches(ctx.handle, dX.ptr, N * d * d, Hs, Ws, Cc, f, 1, sub.ptr, 0))
+            pat = self.merge(sub.numpy().reshape(N * d * d, Hs - f + 1, Ws - f + 1, L), self.out_image_height, self.out_image_width)
+            pat = pat.reshape(N, P, L)
+            return np.ascontiguousarray(pat.transpose(1, 0, 2)) if pnl else pat
         dX = ctx.to_device(X)
         out = ctx.empty((P, N, L) if pnl else (N, P, L))
         ctx._check(dev.lib().dcgp_extract_patches(ctx.handle, dX.ptr, N, H, W, Cc, self.filter_size, self.stride,

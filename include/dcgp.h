@@ -83,7 +83,7 @@ int dcgp_timing_query(dcgp_ctx* ctx, const char* name, int* launches, double* to
 int dcgp_timing_names(dcgp_ctx* ctx, char* buf, size_t buflen);   /* ';'-separated list */
 
 /* ---- patch view: FullView.extract_patches / extract_patches_PNL (conv_gp/views.py:32-54) --- */
-/* X [N,H,W,C] -> out [N,P,L] (pnl == 0) or [P,N,L] (pnl != 0); VALID window, dilation 1;
+/* X [N,H,W,C] -> out [N,P,L] (pnl == 0) or [P,N,L] (pnl != 0); VALID window, dilation 1 (a dilated view splits the images into phase sub-images around this call);
  * p = oh*W' + ow, l = (kh*f + kw)*C + c.                                                         */
 int dcgp_extract_patches(dcgp_ctx* ctx, const double* X, int N, int H, int W, int C, int f, int stride,
                          double* out, int pnl);
@@ -276,6 +276,23 @@ int dcgp_model_set_head(dcgp_model* model, int H, int W, int C, int f, int strid
  * no image inside the layer's H x W.  pad = 0 (the default) is the unpadded layer, on exactly the unpadded code path.
  * Padding is no parameter: checkpoints do not hold it.                                                                        */
 int dcgp_model_set_input_padding(dcgp_model* model, int layer, int pad);
+/* Dilation (atrous rate) d >= 1 of conv layer `layer`: the window's taps sit d pixels apart, so its f x f filter spans d (f - 1) + 1
+ * pixels of the (padded) input Hp x Wp and the output is (Hp - d (f - 1)) x (Wp - d (f - 1)), with the same patch length, Z and M.
+ * Generalises the reference's FullView.dilation = 1, passed as `rates` to tf.extract_image_patches (conv_gp/views.py:24,37).
+ * The layer-adding contract: a dilated layer is added like any other, with its true (padded) input size Hp x Wp and stride 1, and the
+ * layer above with the true output size; this call keeps Hp x Wp in the model and switches the layer's own geometry to the PHASE
+ * geometry ceil(Hp / d) x ceil(Wp / d): the layer runs as an ordinary VALID layer on the d^2 phase sub-images of its input
+ * (space-to-batch on the device, csrc/dilate.hip) and its outputs are put back into image layout behind it.  X, dX, datasets, explicit
+ * noise and dcgp_model_layer_output stay in the caller's image geometry in every call.  The patch count is part of the layout of the
+ * layer's gradient block, so the dilation is set before the model's first gradient step.  This call refuses a layer that does not
+ * exist, d < 1, the head, a layer whose stride is not 1, a window whose span d (f - 1) + 1 exceeds the padded input, a layer that has
+ * taken a gradient step, a sharded model (dcgp_model_set_shard refuses a dilated model in turn) and enqueued steps still to be
+ * collected.  EVERY forward of a model with a dilated layer checks, before anything is launched, that the layers below and above take
+ * and give the dilated layer's true sizes and channels (nothing is remembered between calls: changing a neighbour's padding later is
+ * caught).  d = 1 (the default) is the undilated layer on exactly the undilated code path.  Dilation is no parameter: checkpoints
+ * do not hold it.
+ * Not provided: dilation with stride > 1, a dilated head, per-axis dilation, full covariances through a dilated layer, multi-rank.  */
+int dcgp_model_set_dilation(dcgp_model* model, int layer, int d);
 /* A linear convolutional mean function on conv layer `layer` (conv_gp/mean_functions.py:6-41 with any filter; added to the conditional's
  * mean at conv_gp/layers.py:133-134): m(x)[n, p, r] = sum_l patch_p(x_n)[l] W[l][r] on the layer's own window -- its f, stride and, through
  * the padded copy the layer reads, its padding.  filter_host [f*f*C][R] in FullView's (kh, kw, c) element order: the reference's
@@ -871,6 +888,12 @@ int dcgp_debug_conv_mean_time(dcgp_ctx* ctx, int H, int W, int C, int f, int str
  * move (tools/mixing_time.py).  out_us[8] = microseconds per launch {mix_forward, its copy, mix_backward_latent, its copy, mix_backward_w (both
  * stages), its copy, 0, 0}. */
 int dcgp_debug_mix_time(dcgp_ctx* ctx, int G, int R, long Kc, int iters, double* out_us);
+
+/* The two relayout kernels of a dilated layer (csrc/dilate.hip; dcgp_model_set_dilation) alone on `rows` images H x W x C at rate d, each beside the
+ * same relayout walking its source instead of its destination and beside a copy kernel of the same traffic (tools/dilation_time.py).  out_us[8] =
+ * microseconds per launch {space-to-batch, the same from the image's side (a memset plus a scatter), a copy of the phase batch's size,
+ * batch-to-space, the same from the phase side, a copy of the image batch's size, 0, 0}. */
+int dcgp_debug_dilate_time(dcgp_ctx* ctx, int rows, int H, int W, int C, int d, int iters, double* out_us);
 
 #ifdef __cplusplus
 }
