@@ -83,6 +83,7 @@ struct DcgpOptions {
   long sweep_occ = -1;           // patch sweeps: waves per SIMD a launch is held to so that its rounds come out whole (-1: chosen; 0: off)
   long head_tail = -1;           // head_units: balance of the launch tail (-1: default; see head_units_plan)
   long greedy_wgs = 0;           // greedy inducing-point selection: at most this many workgroups a pivot launch, a lane then takes several columns (0: 1024; tests)
+  long fwd_chunk_rows = 0;       // sweep + GEMM route of a forward-only pass: chunks of at most this many images, also under the 2 GiB slab limit (0: off; tests)
   long fused_abl = 0, rb_mixed = 0;   // timing builds only (make EXPERIMENTS=1)
 };
 long* dcgp_option_slot(DcgpOptions* o, const char* name);   // nullptr: no such option (ctx.hip)

@@ -31,7 +31,7 @@ const OptSlot kOptSlots[] = {
     {"sweep_occ", &DcgpOptions::sweep_occ}, {"share_kb", &DcgpOptions::share_kb}, {"head_upw", &DcgpOptions::head_upw}, {"no_syrk", &DcgpOptions::no_syrk}, {"grad_dz_main", &DcgpOptions::grad_dz_main},
     {"fused_persist", &DcgpOptions::fused_persist}, {"fused_stagger", &DcgpOptions::fused_stagger}, {"fused_pre", &DcgpOptions::fused_pre}, {"fused_parts", &DcgpOptions::fused_parts},
     {"fused_rep_share", &DcgpOptions::fused_rep_share}, {"fused_wgs", &DcgpOptions::fused_wgs}, {"head_ride", &DcgpOptions::head_ride}, {"head_ride_tail", &DcgpOptions::head_ride_tail},
-    {"greedy_wgs", &DcgpOptions::greedy_wgs},
+    {"greedy_wgs", &DcgpOptions::greedy_wgs}, {"fwd_chunk_rows", &DcgpOptions::fwd_chunk_rows},
     {"fused_abl", &DcgpOptions::fused_abl}, {"rb_mixed", &DcgpOptions::rb_mixed},
 };
 }  // namespace

@@ -422,8 +422,10 @@ static inline int conv_forward(dcgp_ctx* ctx, LayerState& L, const double* X, in
   // (sweep, conditional, finalize per chunk; outputs and noise stay indexed by the global column); the training step keeps
   // K_uf and A1 of the whole batch for its reverse pass and is refused by the GEMM as before.
   int chunk_rows = rows;
-  if (!keep_state)
+  if (!keep_state) {
     while (chunk_rows > 1 && (long)Mp * col_ld((long)chunk_rows * P) * 8 >= (1L << 31)) chunk_rows = (chunk_rows + 1) / 2;
+    if (ctx->opt.fwd_chunk_rows > 0 && ctx->opt.fwd_chunk_rows < chunk_rows) chunk_rows = (int)ctx->opt.fwd_chunk_rows;   // (tests: chunks of a small batch)
+  }
   const bool chunked = chunk_rows < rows;
   if (chunked && !(phase & 2)) return DCGP_OK;   // nothing to run ahead: the slab is reused chunk after chunk
   const long ldc = col_ld((long)chunk_rows * P);
