@@ -13,10 +13,11 @@ from deepcgp_amd import synthetic as syn
 import conv_mean_ref as cmr
 import live_specs as ls
 import padding_ref as pr
+import stack_specs as ss
 
 N, S, SEED = 3, 2, 7
 
-# stack -> padding_ref.padded_spec arguments: convs [(f, s, R, pad)], head (f, s, pad), one M per layer
+# stack -> stack_specs.stack_spec arguments: convs [(f, s, R, pad, dil)], head (f, s, pad), one M per layer
 #   ch_res, valid2, even_s2, wide_R   conv_mean_ref.CASES
 #   small3_20_40_24, ch_72_264         the geometry and the Ms of that live_specs.CASES_MIXED entry (Mp 32 / 48 / 32; the head at M > 256)
 #   ch_264_72                          padding_ref.STACKS: the conv layer at M = 264 (sweep + GEMM route), padded by 2
@@ -25,7 +26,7 @@ _KEYS = ("hwc", "convs", "head", "Ms")
 
 
 def _unpadded(k):
-    return dict(hwc=k["hwc"], convs=[c + (0,) for c in k["convs"]], head=k["head"] + (0,), Ms=k["Ms"])
+    return dict(hwc=k["hwc"], convs=[c + (0, 1) for c in k["convs"]], head=k["head"] + (0,), Ms=k["Ms"])
 
 
 STACKS = {
@@ -36,7 +37,7 @@ STACKS = {
     "small3_20_40_24": _unpadded(ls.CASES_MIXED["small3_20_40_24"]),
     "ch_264_72": {k: pr.STACKS["ch_264_72"][k] for k in _KEYS},
     "ch_72_264": _unpadded(ls.CASES_MIXED["ch_72_264"]),
-    "narrow_R1": dict(hwc=(8, 8, 1), convs=[(3, 1, 1, 0)], head=(3, 1, 0), Ms=4),
+    "narrow_R1": dict(hwc=(8, 8, 1), convs=[(3, 1, 1, 0, 1)], head=(3, 1, 0), Ms=4),
 }
 
 # likelihood -> (compose_ref tuple, head width D)
@@ -148,12 +149,12 @@ def targets(lik, D, Ylab, seed=SEED):
 
 
 def make_spec(case, trainable=True):
-    """(spec, likelihood tuple) of a case: padding_ref.padded_spec (live_specs' recipe, c = LENGTHSCALE_C, a = 0.1) with the head cut to the likelihood's
+    """(spec, likelihood tuple) of a case: stack_specs.stack_spec (live_specs' recipe, c = LENGTHSCALE_C, a = 0.1) with the head cut to the likelihood's
     width, the base kernel and the mean put on every conv layer as tests/conv_mean_ref.py::make_case does."""
     k = STACKS[case["stack"]]
     lik, D = LIKELIHOODS[case["likelihood"]]
     nl = len(k["convs"]) + 1
-    spec = pr.padded_spec(whites=whites(case, nl), S=S, seed=SEED, c=LENGTHSCALE_C.get(case["stack"], 1.0), **k)
+    spec = ss.stack_spec(whites=whites(case, nl), S=S, seed=SEED, c=LENGTHSCALE_C.get(case["stack"], 1.0), **k)
     h = spec["head"]
     h["R"], h["q_mu"], h["q_sqrt"] = D, np.array(h["q_mu"][:, :D]), np.array(h["q_sqrt"][:D])
     for c in spec["convs"]:
@@ -172,4 +173,4 @@ def make_case(case, n=N, seed=SEED):
     """(spec, X, Y, zs, likelihood tuple) of a case; ``n`` images."""
     spec, lik = make_spec(case)
     X, Ylab = syn.make_batch(STACKS[case["stack"]]["hwc"], n, seed=seed)
-    return spec, X, targets(lik, spec["head"]["R"], Ylab, seed), pr.make_noise(spec, n, seed=seed), lik
+    return spec, X, targets(lik, spec["head"]["R"], Ylab, seed), ss.make_noise(spec, n, seed=seed), lik

@@ -1,11 +1,11 @@
 """Test helper: ONE torch forward (float64, CPU) for every combination of likelihood, base kernel, padding, per-layer M and whitening, and
 mean function (tests/test_host_compose.py, tests/test_gpu_compose.py).
 
-The layers are tests/conv_mean_ref.py's ``torch_forward`` -- imported, not copied: padding, the RBF / Matern / ArcCosine Gram matrices,
-Conv2dMean's centre pixel, the mean filter as a leaf -- and the likelihood term is a rule ``ve(m, v)`` on the head's marginals [S, N, D], D the
+The layers are tests/torch_ref.py's ``forward`` -- padding, the RBF / Matern / ArcCosine Gram matrices, Conv2dMean's centre pixel, the mean
+filter as a leaf -- and the likelihood term is a rule ``ve(m, v)`` on the head's marginals [S, N, D], D the
 head width of the spec.  Every rule is the one the repository already has:
 
-    ("robustmax", K)             test_oracle_autograd._robustmax_ve (conv_mean_ref.torch_forward's own tail: the same code path, to the bit)
+    ("robustmax", K)             test_oracle_autograd._robustmax_ve (torch_ref.forward's own tail)
     ("softmax", K, Q, seed)      test_gpu_softmax._torch_rule on likelihoods.Softmax(K, Q, seed).nodes
     ("gaussian", s2)             test_gpu_gaussian._torch_gauss_rule, s2 a leaf
     ("bernoulli",)               test_gpu_bernoulli._torch_bern_rule (tests/bernoulli_ref.py's probit rule at the device's 20 nodes)
@@ -17,7 +17,7 @@ test_oracle_autograd._robustmax_predict; Gaussian: the closed form tests/test_gp
 marginals.  Test infrastructure only."""
 import numpy as np
 
-import conv_mean_ref as cmr
+import torch_ref as tr
 
 LIK_PARAM = {"gaussian": "likelihood_variance", "studentt": "likelihood_scale"}      # the names DGP_Base.compute_gradients uses
 FLOAT_TARGETS = ("gaussian", "bernoulli", "studentt", "poisson")
@@ -46,7 +46,7 @@ def softmax_nodes(lik):
 
 
 def rule(lik, Y):
-    """(ve or None, the likelihood's own leaf or None): ``ve(m, v)`` as conv_mean_ref.torch_forward takes it; None = its RobustMax tail."""
+    """(ve or None, the likelihood's own leaf or None): ``ve(m, v)`` as torch_ref.forward takes it; None = its RobustMax tail."""
     import torch
     kind = lik[0]
     if kind == "robustmax":
@@ -71,25 +71,19 @@ def rule(lik, Y):
 
 
 def torch_forward(spec, X, Y, zs, lik, x_leaf=False):
-    """conv_mean_ref.torch_forward's dict with the likelihood's rule as its tail, plus ``lik_leaf`` (the variance / scale tensor or None)."""
+    """torch_ref.forward's dict with the likelihood's rule as its tail, plus ``lik_leaf`` (the variance / scale tensor or None)."""
     D = spec["head"]["R"]
     assert lik[0] not in ("robustmax", "softmax") or lik[1] == D, (lik, D)
     ve, leaf = rule(lik, Y)
-    out = cmr.torch_forward(spec, X, Y, zs, x_leaf=x_leaf, ve=ve)
+    out = tr.forward(spec, X, Y, zs, x_leaf=x_leaf, ve=ve)
     assert out["mean"].shape[2] == D
     out["lik_leaf"] = leaf
     return out
 
 
 def _gradients(out):
-    import torch
-    flat = [(li, k, t) for li, p in enumerate(out["leaves"]) for k, t in p.items()]
-    extra = [out["lik_leaf"]] if out["lik_leaf"] is not None else []
-    tg = torch.autograd.grad(out["elbo"], [t for _, _, t in flat] + extra, retain_graph=True)
-    want = [{} for _ in out["leaves"]]
-    for (li, k, _), g in zip(flat, tg):
-        want[li][k] = np.tril(g.numpy()) if k == "q_sqrt" else g.numpy().copy()
-    return want, (tg[-1].numpy().copy() if extra else None)
+    want, extra = tr.gradients(out, [] if out["lik_leaf"] is None else [out["lik_leaf"]])
+    return want, (extra[0] if extra else None)
 
 
 def torch_reference(spec, X, Y, zs, lik):
@@ -102,10 +96,7 @@ def torch_reference(spec, X, Y, zs, lik):
 
 def torch_input_gradient(spec, X, Y, zs, lik):
     """(J [N], dX [N, H W C]) of DGP_Base.input_gradient(objective="elbo"): J_n = 1/S sum_s E_q[log p(y_n | f_sn)]."""
-    import torch
-    out = torch_forward(spec, X, Y, zs, lik, x_leaf=True)
-    (g,) = torch.autograd.grad(out["data"].sum(), out["X"])
-    return out["data"].detach().numpy(), g.numpy()
+    return tr.input_gradient(spec, X, Y, zs, tr.data_term, ve=rule(lik, Y)[0])
 
 
 def _logmeanexp(l):

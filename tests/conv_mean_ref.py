@@ -7,11 +7,9 @@ tests/test_host_conv_mean.py, tests/test_gpu_conv_mean.py).
   ``elbo_and_grad`` plus ``filter_grad()`` is the whole gradient of a model with such means.
 * ``oracle_model``: tests/padding_ref.py's padded oracle with a ``RefConvMean`` put on every conv layer whose spec entry has ``mean_filter``
   (a padded layer is the oracle layer on the padded geometry behind np.pad: the mean sees the padded image, as the device's does).
-* ``torch_forward`` / ``torch_reference`` / ``torch_input_gradient``: the textbook forward of tests/test_oracle_autograd.py (its helper
-  functions, imported) with F.pad in front of every patch extraction, RBF / Matern / ArcCosine base kernels (the Gram matrices of
-  tests/matern_ref.py and tests/acos_ref.py) and the mean as ``patches @ W`` with W a leaf: autograd gives every group including ``mean_filter``, and dX.  ``oracle.grad.elbo_and_grad`` knows
-  no padded layer (it scatters patch gradients into the layer's own geometry), so the padded stacks take their gradients from here; the
-  two references agree on an unpadded stack (tests/test_host_conv_mean.py).
+* tests/torch_ref.py's forward has the mean as ``patches @ W`` with W a leaf: autograd gives every group including ``mean_filter``, and dX.
+  ``oracle.grad.elbo_and_grad`` knows no padded layer (it scatters patch gradients into the layer's own geometry), so the padded stacks take
+  their gradients from there; the two references agree on an unpadded stack (tests/test_host_conv_mean.py).
 * ``CASES`` / ``make_case``: the stacks of the GPU tests.  Test infrastructure only."""
 import copy
 
@@ -19,6 +17,7 @@ import numpy as np
 
 from deepcgp_amd import synthetic as syn
 import padding_ref as pr
+import stack_specs as ss
 
 
 class RefConvMean:
@@ -96,117 +95,8 @@ def oracle_gradient(spec, X, Y, zs):
     return e, grads
 
 
-# ---- torch --------------------------------------------------------------------------------------------------------------------------
-def torch_forward(spec, X, Y, zs, x_leaf=False, ve=None):
-    """dict(elbo, kl, leaves [{name: tensor}] per layer -- ``mean_filter`` [f, f, C, R] among a conv layer's where it has one --, mean, var
-    [S, N, R] of the head, data [N] = 1/S sum_s E_q[log p(y_n | f_sn)], X the input tensor (a leaf when x_leaf), F [per conv layer samples]).
-    ``ve``: another likelihood's rule (tests/compose_ref.py), a callable (mean, var [S, N, R]) -> E_q[log p(y | f)] as [S, N] or [S, N, R]
-    (summed over R, averaged over S) or the per-image average [N] itself; None: RobustMax on the labels Y.  A conv entry with
-    ``mean_function`` "conv2d" adds Conv2dMean's centre pixel."""
-    import torch
-    import test_oracle_autograd as toa
-    from matern_ref import NU2, torch_gram
-    T, JITTER = toa.T, toa.JITTER
-    S, N = spec["S"], np.shape(X)[0]
-    Xt = torch.tensor(np.asarray(X, np.float64).reshape(N, -1), dtype=T, requires_grad=bool(x_leaf))
-    F = Xt.repeat(S, 1)
-    kl = torch.zeros((), dtype=T)
-    leaves, samples = [], []
-
-    def leaf(a):
-        return torch.tensor(np.array(a, np.float64), dtype=T, requires_grad=True)
-
-    def window(F, e):
-        p = e.get("pad", 0)
-        x = F.reshape(S * N, e["H"], e["W"], e["C"])
-        return toa._patches(torch.nn.functional.pad(x, (0, 0, p, p, p, p)), e["f"], e["s"])
-    for li, c in enumerate(spec["convs"]):
-        p = dict(Z=leaf(c["Z"]), q_mu=leaf(c["q_mu"]), q_sqrt=leaf(c["q_sqrt"]), variance=leaf(c["variance"]), lengthscales=leaf(c["ls"]))
-        leaves.append(p)
-        M, R = c["M"], c["R"]
-        pt = window(F, c)
-        P = pt.shape[1]
-        cols = pt.reshape(S * N * P, -1)
-        base = c.get("base", "rbf")
-        if base in NU2:
-            kern = lambda A, B, same=False, p=p, nu2=NU2[base]: torch_gram(A, B, p["variance"], p["lengthscales"], nu2)   # noqa: E731
-        elif base == "acos":      # tests/acos_ref.py's Gram matrix (K(Z, Z)'s diagonal in closed form); leaves as the device names them
-            import acos_ref
-            av, aw, ab = c.get("acos", (1.0, 1.0, 1.0))
-            del p["lengthscales"]
-            p.update(variance=leaf(av), weight_variances=leaf(aw), bias_variance=leaf(ab))
-            kern = lambda A, B, same=False, p=p: acos_ref.torch_gram(A, B, p["variance"], p["weight_variances"], p["bias_variance"], same=same)   # noqa: E731
-        else:
-            assert base == "rbf", base
-            kern = lambda A, B, same=False, p=p: toa._rbf(A, B, p["variance"], p["lengthscales"])               # noqa: E731
-        Kuu = kern(p["Z"], p["Z"], True) + JITTER * torch.eye(M, dtype=T)
-        Kuf = kern(p["Z"], cols)
-        kff = p["variance"] * torch.ones(cols.shape[0], dtype=T)
-        mean, var = toa._conditional(Kuu, Kuf, kff, p["q_mu"], p["q_sqrt"], c["white"])
-        mean, var = mean.reshape(S * N, P * R), var.reshape(S * N, P * R)
-        assert c.get("mean_function") in (None, "conv2d") and not (c.get("mean_function") and c.get("mean_filter") is not None)
-        if c.get("mean_function") == "conv2d":      # Conv2dMean: the centre pixel of the (padded) patch's channel 0 into map 0
-            centre = pt.reshape(S * N, P, c["f"], c["f"], c["C"])[:, :, c["f"] // 2, c["f"] // 2, 0]
-            mean = mean + torch.cat([centre[:, :, None], torch.zeros(S * N, P, R - 1, dtype=T)], 2).reshape(S * N, P * R)
-        if c.get("mean_filter") is not None:
-            p["mean_filter"] = leaf(np.reshape(c["mean_filter"], (c["f"], c["f"], c["C"], R)))
-            mean = mean + (cols @ p["mean_filter"].reshape(-1, R)).reshape(S * N, P * R)
-        z = torch.tensor(np.asarray(zs[li]).reshape(S * N, P * R), dtype=T)
-        F = mean + z * torch.sqrt(var + JITTER)
-        samples.append(F)
-        Z0 = torch.tensor(np.array(c["Z0"], np.float64), dtype=T)
-        Kp = None if c["white"] else kern(Z0, Z0, True) + JITTER * torch.eye(M, dtype=T)
-        kl = kl + toa._gauss_kl(p["q_mu"], p["q_sqrt"], Kp)
-    h = spec["head"]
-    assert h.get("kernel", "conv") == "conv"
-    M = h["M"]
-    p = dict(Z=leaf(h["Z"]), q_mu=leaf(h["q_mu"]), q_sqrt=leaf(h["q_sqrt"]), variance=leaf(h["variance"]), lengthscales=leaf(h["ls"]),
-             patch_weights=leaf(h["w"]))
-    leaves.append(p)
-    pt = window(F, h)
-    P = pt.shape[1]
-    w = p["patch_weights"]
-    Kall = toa._rbf(p["Z"], pt.reshape(S * N * P, -1), p["variance"], p["lengthscales"]).reshape(M, S * N, P)
-    Kzx = (Kall * w[None, None, :]).sum(2) / P
-    q = pt / p["lengthscales"]
-    Kpp = p["variance"] * torch.exp(-0.5 * torch.cdist(q, q, compute_mode="donot_use_mm_for_euclid_dist") ** 2)
-    kdiag = torch.einsum("npq,p,q->n", Kpp, w, w) / P ** 2
-    Kuu = toa._rbf(p["Z"], p["Z"], p["variance"], p["lengthscales"]) + JITTER * torch.eye(M, dtype=T)
-    mean, var = toa._conditional(Kuu, Kzx, kdiag, p["q_mu"], p["q_sqrt"], h["white"])
-    kl = kl + toa._gauss_kl(p["q_mu"], p["q_sqrt"], None if h["white"] else Kuu)
-    if ve is None:
-        y = torch.tensor(np.tile(np.asarray(Y).reshape(1, N), [S, 1]).reshape(S * N), dtype=torch.long)
-        data = toa._robustmax_ve(mean, var, y).reshape(S, N).mean(0)
-    else:
-        data = ve(mean.reshape(S, N, -1), var.reshape(S, N, -1))
-        data = data if data.dim() == 1 else data.reshape(S, N, -1).sum(2).mean(0)
-    elbo = data.sum() * (spec["num_data"] / N) - kl
-    return dict(elbo=elbo, kl=kl, leaves=leaves, mean=mean.reshape(S, N, -1), var=var.reshape(S, N, -1), data=data, X=Xt, F=samples)
-
-
-def torch_reference(spec, X, Y, zs):
-    """((ELBO, data term, KL), [per-layer {group: gradient}]); q_sqrt's gradient cut to the lower triangle (the parameter)."""
-    import torch
-    out = torch_forward(spec, X, Y, zs)
-    flat = [(li, k, t) for li, p in enumerate(out["leaves"]) for k, t in p.items()]
-    tg = torch.autograd.grad(out["elbo"], [t for _, _, t in flat])
-    want = [{} for _ in out["leaves"]]
-    for (li, k, _), g in zip(flat, tg):
-        want[li][k] = np.tril(g.numpy()) if k == "q_sqrt" else g.numpy().copy()
-    return (out["elbo"].item(), out["data"].sum().item(), out["kl"].item()), want
-
-
-def torch_input_gradient(spec, X, Y, zs):
-    """(J [N], dX [N, H W C]) of DGP_Base.input_gradient(objective="elbo"): J_n = 1/S sum_s E_q[log p(y_n | f_sn)], the per-row quantity of
-    tests/input_grad_ref.py's RobustMax objective, through a forward that has the mean's term; dX in the caller's unpadded geometry."""
-    import torch
-    out = torch_forward(spec, X, Y, zs, x_leaf=True)
-    (g,) = torch.autograd.grad(out["data"].sum(), out["X"])
-    return out["data"].detach().numpy(), g.numpy()
-
-
 # ---- the stacks of the GPU tests ----------------------------------------------------------------------------------------------------
-# name -> padding_ref.padded_spec arguments, N, and the mean filter of every conv layer ("channels" | "centre0" | "random").  S = 2, seed 7.
+# name -> stack_specs.stack_spec arguments (convs [(f, s, R, pad, dil)]), N, and the mean filter of every conv layer ("channels" | "centre0" | "random").  S = 2, seed 7.
 #   ch_res   10 x 10 x 1 -> conv f3 s1 p1 R2 -> conv f3 s1 p1 R2 (C = R = 2: both maps skip, a residual block) -> head f3 p1; M = 12
 #   even_s2  9 x 7 x 3, f4 s2 R3, M = 5: an even filter, H != W, stride 2, L = 48
 #   wide_R   8 x 8 x 1, f3 s1 R17, M = 4: L = 9 is no multiple of 4, R crosses a 16-column fragment
@@ -214,12 +104,12 @@ def torch_input_gradient(spec, X, Y, zs):
 #   valid2   12 x 12 x 1 -> conv f3 s1 R2 -> conv f3 s2 R2 -> head f3 (P = 4), no padding: the stack oracle.grad.elbo_and_grad can differentiate
 #            (on 10 x 10 the head has one patch and d / d patch_weights is dead, 4e-11)
 CASES = {
-    "ch_res": dict(hwc=(10, 10, 1), convs=[(3, 1, 2, 1), (3, 1, 2, 1)], head=(3, 1, 1), Ms=12, N=3, filters="channels"),
-    "ch_res_white": dict(hwc=(10, 10, 1), convs=[(3, 1, 2, 1), (3, 1, 2, 1)], head=(3, 1, 1), Ms=12, N=3, filters="channels", whites=(True, True, True)),
-    "even_s2": dict(hwc=(9, 7, 3), convs=[(4, 2, 3, 0)], head=(2, 1, 0), Ms=5, N=3, filters="random"),
-    "wide_R": dict(hwc=(8, 8, 1), convs=[(3, 1, 17, 0)], head=(3, 1, 0), Ms=4, N=3, filters="random"),
+    "ch_res": dict(hwc=(10, 10, 1), convs=[(3, 1, 2, 1, 1), (3, 1, 2, 1, 1)], head=(3, 1, 1), Ms=12, N=3, filters="channels"),
+    "ch_res_white": dict(hwc=(10, 10, 1), convs=[(3, 1, 2, 1, 1), (3, 1, 2, 1, 1)], head=(3, 1, 1), Ms=12, N=3, filters="channels", whites=(True, True, True)),
+    "even_s2": dict(hwc=(9, 7, 3), convs=[(4, 2, 3, 0, 1)], head=(2, 1, 0), Ms=5, N=3, filters="random"),
+    "wide_R": dict(hwc=(8, 8, 1), convs=[(3, 1, 17, 0, 1)], head=(3, 1, 0), Ms=4, N=3, filters="random"),
     "m264": dict(pr.STACKS["ch_264_72"], filters="random"),
-    "valid2": dict(hwc=(12, 12, 1), convs=[(3, 1, 2, 0), (3, 2, 2, 0)], head=(3, 1, 0), Ms=12, N=3, filters="random"),
+    "valid2": dict(hwc=(12, 12, 1), convs=[(3, 1, 2, 0, 1), (3, 2, 2, 0, 1)], head=(3, 1, 0), Ms=12, N=3, filters="random"),
 }
 
 
@@ -240,7 +130,7 @@ def make_case(name, base=None, trainable=True, **overrides):
     k = dict(CASES[name])
     k.update(overrides)
     N, kind = k.pop("N"), k.pop("filters")
-    spec = add_filters(pr.padded_spec(**k), kind, trainable=trainable)
+    spec = add_filters(ss.stack_spec(**k), kind, trainable=trainable)
     if base is not None:
         for c in spec["convs"]:
             c["base"] = base
@@ -248,7 +138,7 @@ def make_case(name, base=None, trainable=True, **overrides):
                 c["acos"] = (1.7, 0.8, 0.5)
                 c["variance"] = 1.7
     X, Y = syn.make_batch(k["hwc"], N, seed=7)
-    return spec, X, Y, pr.make_noise(spec, N, seed=7)
+    return spec, X, Y, ss.make_noise(spec, N, seed=7)
 
 
 def without_filters(spec, mean_function=None):

@@ -32,6 +32,7 @@ image order, [S, N, P G].  Test infrastructure only."""
 import numpy as np
 
 import dilation_ref as dr
+import stack_specs as ss
 
 TAG = 0x5eed5eed
 _M0, _M1 = 0xD2511F53, 0xCD9E8D57
@@ -71,7 +72,7 @@ def philox_normal(seed, stream, idx):
 
 def layer_geometry(c):
     """(Ho, Wo, G, d) of a conv entry of a spec: its output image, latent GP count and dilation."""
-    ho, wo = dr.out_size(c["H"], c["W"], c["f"], c["s"], c.get("pad", 0), c.get("dil", 1))
+    ho, wo = ss.out_size(c["H"], c["W"], c["f"], c["s"], c.get("pad", 0), c.get("dil", 1))
     return ho, wo, int(c["R"]), int(c.get("dil", 1))
 
 

@@ -57,6 +57,7 @@ from deepcgp_amd import synthetic as syn
 from deepcgp_amd.models import build_from_spec
 import acos_ref as ar
 import live_specs as ls
+import torch_ref as tr
 
 pytestmark = pytest.mark.gpu
 
@@ -76,7 +77,8 @@ def _case(name):
     """(spec, X, Y, zs, e_t, want): the case and its torch reference, computed once per process; liveness asserted before anything else."""
     pytest.importorskip("torch")
     spec, X, Y, zs = ar.acos_case(name)
-    e_t, want = ar.torch_reference(spec, X, Y, zs)
+    ref = tr.reference(spec, X, Y, zs)
+    e_t, want = ref["parts"][0], ref["want"]
     ls.assert_live(name, want)
     return spec, X, Y, zs, e_t, want
 
@@ -136,13 +138,13 @@ def test_forward_value_and_layer_moments(ctx, case):
     torch = pytest.importorskip("torch")
     spec, X, Y, zs, e_t, _ = _case(case)
     with torch.no_grad():
-        out = ar.torch_forward(spec, X, Y, zs)
+        out = tr.forward(spec, X, Y, zs)
     S, N = spec["S"], X.shape[0]
     model = build_from_spec(spec, X, Y)
     e = model.compute_log_likelihood(X, Y, zs=zs)
     _, Fm, Fv = model.propagate(X, S=S, zs=zs)
-    want_m = [m.numpy().reshape(S, N, -1) for m in out["layer_mean"]] + [out["mean"].numpy()]
-    want_v = [v.numpy().reshape(S, N, -1) for v in out["layer_var"]] + [out["var"].numpy()]
+    want_m = [m.numpy().reshape(S, N, -1) for m in out["Fmeans"]] + [out["mean"].numpy()]
+    want_v = [v.numpy().reshape(S, N, -1) for v in out["Fvars"]] + [out["var"].numpy()]
     print("%s forward elbo rel %.3e" % (case, abs(e - e_t) / abs(e_t)))
     assert abs(e - e_t) <= TOL_ELBO * abs(e_t), (case, e, e_t)
     for li in range(len(want_m)):
@@ -167,7 +169,8 @@ def test_adam_steps_match_numpy_on_torch_gradients(ctx):
     for t in range(1, 4):
         z = syn.make_noise(spec, N, seed=100 + t)
         e = model.train_step(X, Y, lr, zs=z, t=t)
-        e_t, g = ar.torch_reference(spec, X, Y, z)
+        ref = tr.reference(spec, X, Y, z)
+        e_t, g = ref["parts"][0], ref["want"]
         print("adam t%d elbo rel %.3e" % (t, abs(e - e_t) / abs(e_t)))
         assert abs(e - e_t) <= 1e-9 * abs(e_t), (t, e, e_t)
         ar.adam_numpy_step(spec, g, state, lr, t)
@@ -281,7 +284,7 @@ def test_input_gradient_matches_torch_autograd(ctx, case, objective):
     import test_oracle_autograd as toa
     spec, X, Y, zs, _, _ = _case(case)
     S, N = spec["S"], X.shape[0]
-    out = ar.torch_forward(spec, X, Y, zs, x_leaf=True)
+    out = tr.forward(spec, X, Y, zs, x_leaf=True)
     if objective == "elbo":
         Jt = out["data"]
     else:

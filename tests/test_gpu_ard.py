@@ -19,7 +19,7 @@ from deepcgp_amd import synthetic as syn
 from deepcgp_amd.models import build_from_spec
 import ard_ref as ar
 import live_specs as ls
-import matern_ref as mr
+import torch_ref as tr
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(120, method="thread")]   # a hung launch ends the run instead of holding the device
 
@@ -152,7 +152,8 @@ def _case(name):
     """(spec, X, Y, zs, e_t, want): the ARD case and its torch reference, computed once per process; never written to."""
     pytest.importorskip("torch")
     spec, X, Y, zs = ar.ard_case(name)
-    e_t, want = mr.torch_reference(spec, X, Y, zs)
+    ref = tr.reference(spec, X, Y, zs)
+    e_t, want = ref["parts"][0], ref["want"]
     ar.assert_live(name, want)
     return spec, X, Y, zs, e_t, want
 
@@ -232,7 +233,8 @@ def test_adam_steps_match_numpy_on_torch_gradients(ctx):
     for t in range(1, 4):
         z = syn.make_noise(spec, N, seed=100 + t)
         e = model.train_step(X, Y, lr, zs=z, t=t)
-        e_t, g = mr.torch_reference(spec, X, Y, z)
+        ref = tr.reference(spec, X, Y, z)
+        e_t, g = ref["parts"][0], ref["want"]
         print("ARD adam t%d elbo rel %.3e" % (t, abs(e - e_t) / abs(e_t)))
         assert abs(e - e_t) <= 1e-8 * abs(e_t), (t, e, e_t)
         ls.adam_numpy_step(spec, g, state, lr, t)
@@ -246,7 +248,7 @@ def test_adam_steps_match_numpy_on_torch_gradients(ctx):
     assert k0.ARD and k0.lengthscales.shape == (9,) and np.all(k0.lengthscales > 0) and not np.array_equal(k0.lengthscales, _case("small3_M20")[0]["convs"][0]["ls"])
     # a model rebuilt from the pulled values gives the device model's ELBO: the staging scale is 1 / the vector
     e_dev = model.compute_log_likelihood(X, Y, zs=zs)
-    e_new = mr.torch_forward(spec, X, Y, zs)["elbo"].item()
+    e_new = tr.forward(spec, X, Y, zs)["elbo"].item()
     assert abs(e_dev - e_new) <= 1e-8 * abs(e_new)
     model.close()
 
@@ -385,7 +387,8 @@ def test_composition_with_mixed_layers(ctx, name, dedup):
     import mixing_ref as mx
     spec, X, Y, zs = mx.make_case(name)
     ar.ardify(spec)
-    (e_t, _, _), want = mx.torch_reference(spec, X, Y, zs)
+    ref = tr.reference(spec, X, Y, zs)
+    e_t, want = ref["parts"][0], ref["want"]
     tag = "ARD mix %s-%s" % (name, "dedup" if dedup else "tiled")
     model = build_from_spec(copy.deepcopy(spec), X, Y)
     model.dedup_layer0 = dedup
@@ -408,7 +411,7 @@ def test_input_gradient_of_both_objectives_and_saliency(ctx, dedup):
     model = build_from_spec(copy.deepcopy(spec), X, Y)
     model.dedup_layer0 = dedup
     for objective, (Jw, gw) in (("elbo", cr.torch_input_gradient(spec, X, Y, zs, ("robustmax", 10))),
-                                ("density", mx.torch_input_gradient(spec, X, Y, zs, objective="density"))):
+                                ("density", tr.input_gradient(spec, X, Y, zs, tr.robustmax_density(Y)))):
         J, dX = model.input_gradient(X, Y, objective=objective, zs=zs)
         bound = INPUT_GRAD_TOL * max(1.0, np.abs(gw).max())
         print("ARD input gradient %s dedup=%s: %.3e bound %.1e |want|max %.3e J %.3e" % (objective, dedup, np.abs(dX - gw).max(), bound, np.abs(gw).max(),

@@ -24,6 +24,7 @@ from deepcgp_amd.likelihoods import Gaussian
 from deepcgp_amd.models import build_from_spec, learning_rate
 import live_specs as ls
 import padding_ref as pr
+import stack_specs as ss
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(120, method="thread")]   # a hung launch ends the run instead of holding the device
 
@@ -45,7 +46,7 @@ def _case(name):
     """(spec, (H, W, C), X pool, labels, float targets [POOL, R]) of a geometry, built once per process and never written to."""
     k = dict(GEOMETRIES[name])
     k.pop("N", None)
-    spec = pr.padded_spec(**k) if name.startswith("padded") else ls.live_spec(S=S, **k)
+    spec = ss.stack_spec(**k) if name.startswith("padded") else ls.live_spec(S=S, **k)
     X, _ = syn.make_batch(k["hwc"], POOL, seed=7)
     rng = np.random.default_rng(99)
     Y = rng.integers(0, 10, POOL).astype(np.int32)

@@ -46,7 +46,7 @@ from deepcgp_amd.models import build_from_spec
 import compose_cases as cc
 import compose_ref as cr
 import live_specs as ls
-import padding_ref as pr
+import stack_specs as ss
 from test_gpu_conv_mean import INPUT_GRAD_TOL, grad_bounds
 from test_gpu_evaluate import RTOL as RTOL_EVAL
 from test_gpu_model import RTOL
@@ -236,7 +236,7 @@ def test_sharded_adam_equals_adam_step_with_variance_slot_and_filters(ctx):
     for sharded in (False, True):
         model = _model(spec, X, Y, lik, False)
         for t in (1, 2):
-            model.compute_gradients(X, Y, zs=pr.make_noise(spec, X.shape[0], seed=50 + t), fetch=False)
+            model.compute_gradients(X, Y, zs=ss.make_noise(spec, X.shape[0], seed=50 + t), fetch=False)
             if sharded:
                 model.debug_sharded_adam(3, 0.05, t)
             else:

@@ -22,12 +22,13 @@ from deepcgp_amd import synthetic as syn
 from deepcgp_amd.models import build_from_spec
 import conv_mean_ref as R
 import live_specs as ls
-import padding_ref as pr
+import stack_specs as ss
 import test_gpu_grad_large_m as large_m
 import test_gpu_grad_m256 as m256
 from test_gpu_evaluate import RTOL as RTOL_EVAL, oracle_log_density
 from test_gpu_model import RTOL
 from test_gpu_ops import RTOL as RTOL_OPS
+import torch_ref as tr
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(120, method="thread")]   # a hung launch ends the run instead of holding the device
 
@@ -67,7 +68,7 @@ def _forward_ref(name, base=None):
         import torch
         from test_oracle_autograd import _robustmax_predict
         with torch.no_grad():
-            out = R.torch_forward(spec, X, Y, zs)
+            out = tr.forward(spec, X, Y, zs)
             S, N, K = out["mean"].shape
             p = _robustmax_predict(out["mean"].reshape(S * N, K), out["var"].reshape(S * N, K)).reshape(S, N, K).numpy()
         Fs = [f.numpy().reshape(S, N, -1) for f in out["F"]]
@@ -90,7 +91,8 @@ def _grad_ref(name, base=None):
             g["q_sqrt"] = np.tril(g["q_sqrt"])
         return (e,), grads
     pytest.importorskip("torch")
-    return R.torch_reference(spec, X, Y, zs)
+    t = tr.reference(spec, X, Y, zs)
+    return t["parts"], t["want"]
 
 
 # ---- 1. forward ---------------------------------------------------------------------------------------------------------------------
@@ -167,8 +169,8 @@ def test_gradient_of_every_group_including_the_filter(ctx, case, dedup):
 def test_input_gradient_has_the_means_term(ctx, name, dedup):
     pytest.importorskip("torch")
     spec, X, Y, zs = _case(name)
-    Jw, want = R.torch_input_gradient(spec, X, Y, zs)
-    _, without = R.torch_input_gradient(R.without_filters(spec), X, Y, zs)
+    Jw, want = tr.input_gradient(spec, X, Y, zs, tr.data_term)
+    _, without = tr.input_gradient(R.without_filters(spec), X, Y, zs, tr.data_term)
     model = build_from_spec(spec, X, Y)
     model.dedup_layer0 = dedup
     J, got = model.input_gradient(X, Y, objective="elbo", zs=zs)
@@ -260,7 +262,7 @@ def test_train_run_equals_the_loop_bit_for_bit_and_the_filter_moves(ctx, dedup):
 def test_a_frozen_filter_stays_put_and_set_trainable_switches_it(ctx):
     spec, X, Y, (a,) = _train_models(False, True, n=1)
     start = dict(_values(a))
-    zs = pr.make_noise(spec, 4, seed=3)
+    zs = ss.make_noise(spec, 4, seed=3)
     for i in range(3):
         a.train_step(X[:4], Y[:4], 0.01, zs=zs)
     now = dict(_values(a))
@@ -290,7 +292,7 @@ def test_sharded_adam_equals_adam_step_with_a_trainable_filter(ctx):
         model = build_from_spec(copy.deepcopy(spec), X, Y)
         model.set_trainable(0, "q_mu", False)
         for t in (1, 2):
-            model.compute_gradients(X, Y, zs=pr.make_noise(spec, X.shape[0], seed=50 + t), fetch=False)
+            model.compute_gradients(X, Y, zs=ss.make_noise(spec, X.shape[0], seed=50 + t), fetch=False)
             if sharded:
                 model.debug_sharded_adam(3, 0.05, t)
             else:
@@ -362,7 +364,7 @@ def test_evaluate_and_predict_y(ctx):
     N, S, bs = 7, 2, 3
     spec, _, _, _ = _case("ch_res")
     X, Y = syn.make_batch(R.CASES["ch_res"]["hwc"], N, seed=23)
-    zs = pr.make_noise(spec, N, seed=23)
+    zs = ss.make_noise(spec, N, seed=23)
     ref, _ = R.oracle_model(spec, X, Y)
     model = build_from_spec(spec, X, Y)
     want, om = oracle_log_density(ref, X, Y, S, zs)

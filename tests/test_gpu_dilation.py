@@ -18,10 +18,12 @@ from deepcgp_amd.models import build_from_spec
 
 import dilation_ref as dr
 import live_specs as ls
+import stack_specs as ss
 import test_gpu_padding as tgp
 from test_gpu_evaluate import RTOL as RTOL_EVAL
 from test_gpu_model import RTOL
 from test_gpu_ops import RTOL as RTOL_OPS
+import torch_ref as tr
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(120, method="thread")]   # a hung launch ends the run instead of holding the device
 
@@ -39,7 +41,7 @@ def _case(name):
 def _torch(name):
     pytest.importorskip("torch")
     spec, X, Y, zs = _case(name)
-    return dr.torch_reference(spec, X, Y, zs)
+    return tr.reference(spec, X, Y, zs)
 
 
 # ---- 1. the stacks against torch ---------------------------------------------------------------------------------------------------------
@@ -59,7 +61,7 @@ def test_dilated_stacks_match_the_torch_forward(ctx, name, dedup):
         print("%s layer %d mean %.3e var %.3e" % (name, i, rel(Fm[i], t["means"][i]), rel(Fv[i], t["vars"][i])))
     e, data, kl = t["parts"]
     assert abs(got[0] - e) <= RTOL * abs(e) and abs(got[1] - data) <= RTOL * abs(data) and abs(got[2] - kl) <= RTOL * max(abs(kl), 1.0), (got, t["parts"])
-    assert [m.shape[-1] for m in Fm] == [o for _, o in dr.output_dims(spec)]
+    assert [m.shape[-1] for m in Fm] == [o for _, o in ss.output_dims(spec)]
     for i in range(len(Fm)):
         assert rel(Fm[i], t["means"][i]) < RTOL_OPS and rel(Fv[i], t["vars"][i]) < RTOL_OPS, (name, i)
     assert model.compute_log_likelihood(X, Y, zs=zs, return_parts=True) == got          # the other bank (and its split batch): the same bits
@@ -72,7 +74,7 @@ def _physical(spec):
     its own on the phase output (the model needs one; its values are not compared)."""
     c = copy.deepcopy(spec["convs"][0])
     d, p = c.pop("dil"), c.pop("pad", 0)
-    c["H"], c["W"] = dr.phase_size(c["H"], c["W"], p, d)
+    c["H"], c["W"] = ss.phase_size(c["H"], c["W"], p, d)
     Rout = c["R"] if c.get("mix_W") is None else np.shape(c["mix_W"])[1]
     Hq, Wq = c["H"] - c["f"] + 1, c["W"] - c["f"] + 1
     head = ls.live_spec((Hq, Wq, Rout), [], (2, 1), 12, 1.0, 0.1, S=spec["S"], seed=3)["head"]
@@ -86,7 +88,7 @@ def _identity(spec, X, Y, zs):
     phys, d, p = _physical(spec)
     S, N = spec["S"], X.shape[0]
     H, W, Cc = c0["H"], c0["W"], c0["C"]
-    Ho, Wo = dr.out_size(H, W, c0["f"], 1, p, d)
+    Ho, Wo = ss.out_size(H, W, c0["f"], 1, p, d)
     G = c0["R"]
     Xs = dr.s2b(np.pad(X.reshape(N, H, W, Cc), ((0, 0), (p, p), (p, p), (0, 0))), d)
     Xs = Xs.reshape(Xs.shape[0], -1)
@@ -161,9 +163,9 @@ def test_model_builder_with_dilations_from_flags(ctx):
     for e, v in zip(spec["convs"], views):
         e.update(pad=v.padding, dil=v.dilation, H=v.input_size[0], W=v.input_size[1])
     Xb, Yb = X[:8].reshape(8, -1), Y[:8].reshape(-1)
-    zs = dr.make_noise(spec, 8, seed=3)
+    zs = ss.make_noise(spec, 8, seed=3)
     e = model.compute_log_likelihood(Xb, Yb, zs=zs)
-    want = dr.torch_reference(spec, Xb, Yb, zs)["parts"][0]
+    want = tr.reference(spec, Xb, Yb, zs)["parts"][0]
     print("--dilations 2,1: ELBO %.9f torch %.9f rel %.3e" % (e, want, abs(e - want) / abs(want)))
     assert abs(e - want) <= RTOL * abs(want), (e, want)
     hist = train(model, 3)
@@ -220,7 +222,7 @@ def test_input_gradient_is_in_the_callers_geometry(ctx, name, objective, dedup):
     autograd through the pad and the unfold."""
     pytest.importorskip("torch")
     spec, X, Y, zs = _case(name)
-    Jw, want = dr.torch_input_gradient(spec, X, Y, zs, objective=objective)
+    Jw, want = tr.input_gradient(spec, X, Y, zs, tr.robustmax_objective(Y, objective))
     model = build_from_spec(spec, X, Y)
     model.dedup_layer0 = dedup
     J, got = model.input_gradient(X, Y, objective=objective, zs=zs)
@@ -250,18 +252,18 @@ def _compose(kind):
     if kind == "mixing":      # G = 2 latent GPs -> R = 3 maps on a dilated layer with phantoms, S = 3
         from deepcgp_amd.layers import mixing_matrix
         k = dict(hwc=(9, 7, 2), head=(3, 1, 0), Ms=12, S=3)
-        spec = dr.dilated_spec(convs=[(3, 3, 0, 2)], **k)
-        lat = dr.dilated_spec(convs=[(3, 2, 0, 2)], **k)["convs"][0]
+        spec = ss.stack_spec(convs=[(3, 1, 3, 0, 2)], **k)
+        lat = ss.stack_spec(convs=[(3, 1, 2, 0, 2)], **k)["convs"][0]
         lat.update(mix_W=0.7 * mixing_matrix("random", 2, 3, seed=5), mix_trainable=True)
         spec["convs"][0] = lat
         X, Y = syn.make_batch(k["hwc"], 3, seed=7)
-        return spec, X, Y, dr.make_noise(spec, 3, seed=7)
+        return spec, X, Y, ss.make_noise(spec, 3, seed=7)
     assert kind == "filter_mean"      # a dilated residual block: Cin == Cout, p = d, LinearConv2dMean("channels", trainable)
     from deepcgp_amd.mean_functions import conv_mean_filter
-    spec = dr.dilated_spec(hwc=(9, 9, 2), convs=[(3, 2, 2, 2)], head=(3, 2, 0), Ms=12)
+    spec = ss.stack_spec(hwc=(9, 9, 2), convs=[(3, 1, 2, 2, 2)], head=(3, 2, 0), Ms=12)
     spec["convs"][0].update(mean_filter=conv_mean_filter("channels", 3, 2, 2), mean_trainable=True)
     X, Y = syn.make_batch((9, 9, 2), 3, seed=7)
-    return spec, X, Y, dr.make_noise(spec, 3, seed=7)
+    return spec, X, Y, ss.make_noise(spec, 3, seed=7)
 
 
 @pytest.mark.parametrize("dedup", [False, True], ids=["tiled", "dedup"])
@@ -272,10 +274,10 @@ def test_compositions_on_a_dilated_layer(ctx, kind, dedup):
     gradient from above in image layout."""
     pytest.importorskip("torch")
     spec, X, Y, zs = _compose(kind)
-    t = dr.torch_reference(spec, X, Y, zs)
+    t = tr.reference(spec, X, Y, zs)
     if kind == "filter_mean":
         c = spec["convs"][0]
-        assert dr.out_size(c["H"], c["W"], c["f"], 1, c["pad"], c["dil"]) == (c["H"], c["W"])      # resolution kept
+        assert ss.out_size(c["H"], c["W"], c["f"], 1, c["pad"], c["dil"]) == (c["H"], c["W"])      # resolution kept
     _check_gradients("%s%s" % (kind, "-dedup" if dedup else ""), spec, X, Y, zs, t, dedup)
     model = build_from_spec(spec, X, Y)
     model.dedup_layer0 = dedup
@@ -340,8 +342,8 @@ def test_evaluation_calls_on_a_dilated_stack(ctx):
     N, S, bs, seed = 7, 2, 3, 11
     spec, _, _, _ = _case("dil3_pad")
     X, Y = syn.make_batch(dr.STACKS["dil3_pad"]["hwc"], N, seed=23)
-    zs = dr.make_noise(spec, N, seed=23)
-    t = dr.torch_reference(spec, X, Y, zs)
+    zs = ss.make_noise(spec, N, seed=23)
+    t = tr.reference(spec, X, Y, zs)
     p, _, ld = cr.predictions(("robustmax", 10), t["means"][-1], t["vars"][-1], Y)
     model = build_from_spec(spec, X, Y)
     r = model.evaluate(X, Y, S=S, batch_size=bs, zs=zs, per_image=True)
@@ -403,7 +405,7 @@ def test_two_steps_in_flight_on_a_model_dilated_at_layer_0(ctx, name):
     another route than the synchronous one, so the bound is RTOL, the project's bound between two routes of one model."""
     spec, X, Y, zs = _case(name)
     X2, Y2 = syn.make_batch(dr.STACKS[name]["hwc"], X.shape[0], seed=19)
-    zs2 = dr.make_noise(spec, X.shape[0], seed=19)
+    zs2 = ss.make_noise(spec, X.shape[0], seed=19)
     model = build_from_spec(spec, X, Y)
     want = [model.compute_log_likelihood(X, Y, zs=zs, return_parts=True), model.compute_log_likelihood(X2, Y2, zs=zs2, return_parts=True)]
     assert want[0] != want[1]
@@ -428,19 +430,19 @@ def test_a_dilated_last_conv_layer_keeps_the_heads_rows_off_its_launch(ctx):
     opts = dict(fused_shape=0, fused_persist=1, fused_wgs=3, head_ride=1000)
     k = dict(Ms=32, S=2, c=1.0, a=0.1)
     N = 3
-    plain = dr.dilated_spec(hwc=(24, 24, 1), convs=[(5, 10, 0, 1)], head=(5, 1, 0), **k)
-    spec = dr.dilated_spec(hwc=(28, 28, 1), convs=[(5, 10, 0, 2)], head=(5, 1, 0), **k)
+    plain = ss.stack_spec(hwc=(24, 24, 1), convs=[(5, 1, 10, 0, 1)], head=(5, 1, 0), **k)
+    spec = ss.stack_spec(hwc=(28, 28, 1), convs=[(5, 1, 10, 0, 2)], head=(5, 1, 0), **k)
     with ctx.options(**opts):
         X0, Y0 = syn.make_batch((24, 24, 1), N, seed=7)
         m0 = build_from_spec(plain, X0, Y0)
         n0 = tgp._rode(ctx)[1]
-        e0 = m0.compute_log_likelihood(X0, Y0, zs=dr.make_noise(plain, N))
+        e0 = m0.compute_log_likelihood(X0, Y0, zs=ss.make_noise(plain, N))
         rode = tgp._rode(ctx)
         print("undilated layer: %d rows rode, ELBO %.9f" % (rode[0], e0))
         assert rode[0] > 0 and rode[1] == n0 + 1, rode                    # the premise: this head rides an undilated layer
         m0.close()
         X, Y = syn.make_batch((28, 28, 1), N, seed=7)
-        zs = dr.make_noise(spec, N)
+        zs = ss.make_noise(spec, N)
         model = build_from_spec(spec, X, Y)
         got = model.compute_log_likelihood(X, Y, zs=zs, return_parts=True)
         assert tgp._rode(ctx) == (0, n0 + 1), tgp._rode(ctx)              # no launch of the dilated model carried a row
@@ -449,7 +451,7 @@ def test_a_dilated_last_conv_layer_keeps_the_heads_rows_off_its_launch(ctx):
         got2 = m2.compute_log_likelihood(X2, Y2, zs=z2, return_parts=True)
         assert tgp._rode(ctx) == (0, n0 + 1), tgp._rode(ctx)
         m2.close()
-    want = dr.torch_reference(spec, X, Y, zs)["parts"]
+    want = tr.reference(spec, X, Y, zs)["parts"]
     for what, g, w in zip(("elbo", "data", "kl"), got, want):
         print("dilated layer under the ride's options %-4s device %.9f torch %.9f rel %.3e" % (what, g, w, abs(g - w) / max(abs(w), 1.0)))
         assert abs(g - w) <= RTOL * max(abs(w), 1.0), (what, g, w)

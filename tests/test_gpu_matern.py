@@ -32,6 +32,7 @@ from deepcgp_amd import synthetic as syn
 from deepcgp_amd.models import build_from_spec
 import live_specs as ls
 import matern_ref as mr
+import torch_ref as tr
 
 pytestmark = pytest.mark.gpu
 
@@ -136,7 +137,8 @@ def _case(name, base):
     """(spec, X, Y, zs, e_t, want): the case with Matern conv layers and its torch reference, computed once per process."""
     pytest.importorskip("torch")
     spec, X, Y, zs = mr.matern_case(name, base)
-    e_t, want = mr.torch_reference(spec, X, Y, zs)
+    ref = tr.reference(spec, X, Y, zs)
+    e_t, want = ref["parts"][0], ref["want"]
     ls.assert_live(name, want)
     return spec, X, Y, zs, e_t, want
 
@@ -191,7 +193,8 @@ def test_adam_steps_match_numpy_on_torch_gradients(ctx):
     for t in range(1, 4):
         z = syn.make_noise(spec, N, seed=100 + t)
         e = model.train_step(X, Y, lr, zs=z, t=t)
-        e_t, g = mr.torch_reference(spec, X, Y, z)
+        ref = tr.reference(spec, X, Y, z)
+        e_t, g = ref["parts"][0], ref["want"]
         print("adam t%d elbo rel %.3e" % (t, abs(e - e_t) / abs(e_t)))
         assert abs(e - e_t) <= 1e-8 * abs(e_t), (t, e, e_t)
         ls.adam_numpy_step(spec, g, state, lr, t)
@@ -257,7 +260,7 @@ def test_prediction_evaluation_and_input_gradient(ctx):
     import test_oracle_autograd as toa
     spec, X, Y, zs, _, _ = _case("small3_M20", "matern32")
     S, N = spec["S"], X.shape[0]
-    out = mr.torch_forward(spec, X, Y, zs, x_leaf=True)
+    out = tr.forward(spec, X, Y, zs, x_leaf=True)
     (gX,) = torch.autograd.grad(out["data"].sum(), out["X"])
     mean, var = out["mean"].detach(), out["var"].detach()
     model = build_from_spec(spec, X, Y)
@@ -282,7 +285,7 @@ def test_gaussian_likelihood_elbo(ctx):
     from deepcgp_amd.likelihoods import Gaussian
     spec, X, _, zs, _, _ = _case("small3_M20", "matern52")
     Yf = np.random.default_rng(2).standard_normal((X.shape[0], spec["head"]["R"]))
-    e_t = mr.torch_forward(spec, X, Yf, zs, likelihood="gaussian", s2=0.7)["elbo"].item()
+    e_t = tr.forward(spec, X, Yf, zs, ve=tr.gaussian_rule(Yf, 0.7))["elbo"].item()
     model = build_from_spec(spec, X, Yf, likelihood=Gaussian(0.7))
     e = model.compute_log_likelihood(X, Yf, zs=zs)
     print("gaussian elbo rel %.3e" % (abs(e - e_t) / abs(e_t)))

@@ -21,12 +21,14 @@ from deepcgp_amd.models import build_from_spec
 import compose_ref
 import live_specs as ls
 import mixing_ref as R
+import stack_specs as ss
 import test_gpu_grad_clip as clip
 import test_gpu_grad_large_m as large_m
 import test_gpu_grad_m256 as m256
 from test_gpu_evaluate import RTOL as RTOL_EVAL
 from test_gpu_model import RTOL
 from test_gpu_ops import RTOL as RTOL_OPS
+import torch_ref as tr
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(120, method="thread")]   # a hung launch ends the run instead of holding the device
 
@@ -60,12 +62,8 @@ def _ref(name, base=None):
     """ONE torch forward per case: ELBO parts, every gradient group, the layers' samples and marginals, the head's marginals, J and dX."""
     import torch
     spec, X, Y, zs = _case(name, base)
-    out = R.torch_forward(spec, X, Y, zs, x_leaf=True)
-    flat = [(li, k, t) for li, p in enumerate(out["leaves"]) for k, t in p.items()]
-    tg = torch.autograd.grad(out["elbo"], [t for _, _, t in flat], retain_graph=True)
-    want = [{} for _ in out["leaves"]]
-    for (li, k, _), g in zip(flat, tg):
-        want[li][k] = np.tril(g.numpy()) if k == "q_sqrt" else g.numpy().copy()
+    out = tr.forward(spec, X, Y, zs, x_leaf=True)
+    want, _ = tr.gradients(out)
     (dX,) = torch.autograd.grad(out["data"].sum(), out["X"])
     S, N = spec["S"], X.shape[0]
     n = lambda ts: [t.detach().numpy().reshape(S, N, -1) for t in ts]      # noqa: E731
@@ -260,7 +258,7 @@ def test_input_gradient_both_objectives(ctx, name, dedup):
     err = np.abs(got - o["dX"]).max()
     print("%s dedup=%d elbo: |dX - autograd| %.3e  |want|max %.3e  J rel %.3e" % (name, dedup, err, np.abs(o["dX"]).max(), rel(J, o["J"])))
     assert got.shape == X.shape and rel(J, o["J"]) <= RTOL and err <= INPUT_GRAD_TOL * max(1.0, np.abs(o["dX"]).max())
-    Jw, want = R.torch_input_gradient(spec, X, Y, zs, objective="density")
+    Jw, want = tr.input_gradient(spec, X, Y, zs, tr.robustmax_density(Y))
     J, got = model.input_gradient(X, Y, objective="density", zs=zs)
     err = np.abs(got - want).max()
     print("%s dedup=%d density: |dX - autograd| %.3e  |want|max %.3e  J rel %.3e" % (name, dedup, err, np.abs(want).max(), rel(J, Jw)))
@@ -358,7 +356,7 @@ def test_a_frozen_mixing_stays_put_and_everything_else_moves(ctx):
     a.set_trainable(0, "mixing", False)
     assert a.layers[0].mixing_trainable is False
     start = dict(_values(a))
-    zs = R.make_noise(spec, 4, seed=3)
+    zs = ss.make_noise(spec, 4, seed=3)
     for _ in range(3):
         a.train_step(X[:4], Y[:4], 0.01, zs=zs)
     now = dict(_values(a))
@@ -431,7 +429,7 @@ def test_sgd_and_natgrad_steps(ctx):
 # ---- 6. state ------------------------------------------------------------------------------------------------------------------------------------
 def test_optimizer_state_round_trip_with_the_new_keys(ctx):
     spec, X, Y, (a, b) = _train_models("pad_lin", True)
-    zs = R.make_noise(spec, 4, seed=3)
+    zs = ss.make_noise(spec, 4, seed=3)
     for _ in range(2):
         a.train_step(X[:4], Y[:4], 0.01, zs=zs)
     st = a.optimizer_state()
@@ -493,9 +491,9 @@ def test_evaluate_predict_y_and_the_full_cov_refusal(ctx):
     spec, _, _, _ = _case("pad_lin")
     X, Y = syn.make_batch(R.CASES["pad_lin"]["hwc"], N, seed=23)
     spec = dict(copy.deepcopy(spec), S=S)
-    zs = R.make_noise(spec, N, seed=23)
+    zs = ss.make_noise(spec, N, seed=23)
     with torch.no_grad():
-        out = R.torch_forward(spec, X, Y, zs)
+        out = tr.forward(spec, X, Y, zs)
     m, v = out["mean"].numpy(), out["var"].numpy()
     om, _, want = compose_ref.predictions(("robustmax", 10), m, v, Y)
     model = build_from_spec(spec, X, Y)
@@ -513,10 +511,10 @@ def test_evaluate_predict_y_and_the_full_cov_refusal(ctx):
     assert np.array_equal(t["log_density"], r["log_density"])                   # the identity view alone is the plain evaluation
     views = np.array([[0, 0, 0], [1, 0, 0], [0, -1, 1]], np.int32)
     V = len(views)
-    zf = R.make_noise(spec, V * N, seed=31)
+    zf = ss.make_noise(spec, V * N, seed=31)
     Xv = _views_of(X, R.CASES["pad_lin"]["hwc"], views)
     with torch.no_grad():
-        ov = R.torch_forward(spec, Xv, np.tile(Y.reshape(-1), V), zf)
+        ov = tr.forward(spec, Xv, np.tile(Y.reshape(-1), V), zf)
     pv, _, _ = compose_ref.predictions(("robustmax", 10), ov["mean"].numpy(), ov["var"].numpy(), np.tile(Y.reshape(-1), V))
     mem = _members(pv, V)
     pbar, logdens = mem.mean(axis=0), _lse_mean(np.log(mem[:, np.arange(N), Y.reshape(-1)]))

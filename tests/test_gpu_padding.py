@@ -19,11 +19,13 @@ from deepcgp_amd import synthetic as syn
 from deepcgp_amd.models import build_from_spec
 import live_specs as ls
 import padding_ref as pr
+import stack_specs as ss
 import test_gpu_grad_large_m as large_m
 import test_gpu_grad_m256 as m256
 from test_gpu_evaluate import RTOL as RTOL_EVAL, oracle_log_density
 from test_gpu_model import RTOL
 from test_gpu_ops import RTOL as RTOL_OPS
+import torch_ref as tr
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(120, method="thread")]   # a hung launch ends the run instead of holding the device
 
@@ -61,7 +63,7 @@ def _oracle(name):
 def _torch(name):
     pytest.importorskip("torch")
     spec, X, Y, zs = _case(name)
-    return pr.torch_reference(spec, X, Y, zs)
+    return tr.reference(spec, X, Y, zs)
 
 
 # ---- 1. oracle parity -------------------------------------------------------------------------------------------------------------------
@@ -83,7 +85,7 @@ def test_padded_stacks_match_the_padded_oracle(ctx, name, dedup):
     print("%s predict_y %.3e" % (name, rel(p, o["p"])))
     e, data, kl = o["parts"]
     assert abs(got[0] - e) <= RTOL * abs(e) and abs(got[1] - data) <= RTOL * abs(data) and abs(got[2] - kl) <= RTOL * max(abs(kl), 1.0), (got, o["parts"])
-    assert [m.shape[-1] for m in Fm] == pr.output_dims(spec)
+    assert [m.shape[-1] for m in Fm] == [o for _, o in ss.output_dims(spec)]
     for i in range(len(Fm)):
         assert rel(Fm[i], o["Fm"][i]) < RTOL_OPS and rel(Fv[i], o["Fv"][i]) < RTOL_OPS and rel(Fs[i], o["Fs"][i]) < RTOL_OPS, (name, i)
     assert rel(p, o["p"]) < RTOL
@@ -98,11 +100,11 @@ def test_padding_at_layer_0_is_the_unpadded_model_on_padded_images(ctx, name):
     On the MI355X both stacks came out bit-identical, tiled and de-duplicated: ELBO, data term, KL and every layer's mean and variance (the
     padded copy is an ordinary image to every kernel behind it); the assertion stays at RTOL, which is what the layers promise."""
     if name == "res3_first_only":
-        k = dict(pr.STACKS["res3"], convs=[(3, 1, 2, 1), (3, 2, 2, 0)], head=(3, 1, 0))
+        k = dict(pr.STACKS["res3"], convs=[(3, 1, 2, 1, 1), (3, 2, 2, 0, 1)], head=(3, 1, 0))
         N = k.pop("N")
-        spec = pr.padded_spec(**k)
+        spec = ss.stack_spec(**k)
         X, Y = syn.make_batch(k["hwc"], N, seed=7)
-        zs = pr.make_noise(spec, N, seed=7)
+        zs = ss.make_noise(spec, N, seed=7)
     else:
         spec, X, Y, zs = _case(name)
     assert [l.get("pad", 0) for l in spec["convs"] + [spec["head"]]][1:] == [0] * len(spec["convs"])
@@ -173,7 +175,7 @@ def test_model_builder_with_paddings_from_flags(ctx):
     for e, v in zip(spec["convs"] + [spec["head"]], views):
         e["pad"] = v.padding
     Xb, Yb = X[:8].reshape(8, -1), Y[:8].reshape(-1)
-    zs = pr.make_noise(spec, 8, seed=3)
+    zs = ss.make_noise(spec, 8, seed=3)
     e = model.compute_log_likelihood(Xb, Yb, zs=zs)
     ref = pr.oracle_model(spec, Xb, Yb).compute_log_likelihood(Xb, Yb, zs=zs)
     print("--paddings 1,1,0: ELBO %.9f oracle %.9f rel %.3e" % (e, ref, abs(e - ref) / abs(ref)))
@@ -191,7 +193,8 @@ GRAD = [(n, False) for n in STACKS] + [("res3", True), ("ch_264_72", True)]
 def test_gradient_matches_torch_autograd_of_the_padded_forward(ctx, name, dedup):
     """Every group of every layer, group-wise and entry-wise over the floor (tests/live_specs.py: errors); the ELBO parts against torch."""
     spec, X, Y, zs = _case(name)
-    (e_t, data_t, kl_t), want = _torch(name)
+    t = _torch(name)
+    (e_t, data_t, kl_t), want = t["parts"], t["want"]
     ls.assert_live(name, want)
     tol_group, tol_e = grad_bounds(spec)
     tag = name + ("-dedup" if dedup else "")
@@ -227,7 +230,7 @@ def test_input_gradient_is_in_the_unpadded_geometry(ctx, name, objective, dedup)
     """dX [N, H W C] of the caller's images (the crop and the replica sum of a tiled batch are one pass) against autograd through the pad."""
     pytest.importorskip("torch")
     spec, X, Y, zs = _case(name)
-    Jw, want = pr.torch_input_gradient(spec, X, Y, zs, objective=objective)
+    Jw, want = tr.input_gradient(spec, X, Y, zs, tr.robustmax_objective(Y, objective))
     model = build_from_spec(spec, X, Y)
     model.dedup_layer0 = dedup
     J, got = model.input_gradient(X, Y, objective=objective, zs=zs)
@@ -250,7 +253,7 @@ def test_two_steps_in_flight_on_a_model_padded_at_layer_0(ctx, name):
     take another route than the synchronous one, so the bound is RTOL, the project's bound between two routes of one model."""
     spec, X, Y, zs = _case(name)
     X2, Y2 = syn.make_batch(pr.STACKS[name]["hwc"], X.shape[0], seed=19)
-    zs2 = pr.make_noise(spec, X.shape[0], seed=19)
+    zs2 = ss.make_noise(spec, X.shape[0], seed=19)
     model = build_from_spec(spec, X, Y)
     want = [model.compute_log_likelihood(X, Y, zs=zs, return_parts=True), model.compute_log_likelihood(X2, Y2, zs=zs2, return_parts=True)]
     assert want[0] != want[1]
@@ -280,17 +283,17 @@ def test_a_padded_head_keeps_its_rows_off_the_layer_launch(ctx):
     k = dict(hwc=(28, 28, 1), Ms=32, S=2, c=1.0, a=0.1)
     N = 3
     X, Y = syn.make_batch(k["hwc"], N, seed=7)
-    plain = pr.padded_spec(convs=[(5, 2, 10, 0)], head=(5, 1, 0), **k)
-    spec = pr.padded_spec(convs=[(5, 2, 10, 0)], head=(5, 1, 1), **k)
+    plain = ss.stack_spec(convs=[(5, 2, 10, 0, 1)], head=(5, 1, 0), **k)
+    spec = ss.stack_spec(convs=[(5, 2, 10, 0, 1)], head=(5, 1, 1), **k)
     with ctx.options(**opts):
         m0 = build_from_spec(plain, X, Y)
         n0 = _rode(ctx)[1]
-        e0 = m0.compute_log_likelihood(X, Y, zs=pr.make_noise(plain, N))
+        e0 = m0.compute_log_likelihood(X, Y, zs=ss.make_noise(plain, N))
         rode = _rode(ctx)
         print("unpadded head: %d rows rode, ELBO %.9f" % (rode[0], e0))
         assert rode == (N * 2, n0 + 1), rode                              # the premise: this shape rides
         m0.close()
-        zs = pr.make_noise(spec, N)
+        zs = ss.make_noise(spec, N)
         model = build_from_spec(spec, X, Y)
         got = model.compute_log_likelihood(X, Y, zs=zs, return_parts=True)
         assert _rode(ctx) == (0, n0 + 1), _rode(ctx)                      # no launch of the padded model carried a row
@@ -315,7 +318,7 @@ def test_evaluation_calls_on_a_padded_stack(ctx):
     spec, _, _, _ = _case("res3")
     hwc = pr.STACKS["res3"]["hwc"]
     X, Y = syn.make_batch(hwc, N, seed=23)
-    zs = pr.make_noise(spec, N, seed=23)
+    zs = ss.make_noise(spec, N, seed=23)
     ref = pr.oracle_model(spec, X, Y)
     model = build_from_spec(spec, X, Y)
     want, om = oracle_log_density(ref, X, Y, S, zs)

@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 
 import bernoulli_ref as br
-import padding_ref as pr
+import stack_specs as ss
 import uncertainty_ref as ur
 from deepcgp_amd import augment
 from deepcgp_amd import device as dev
@@ -79,7 +79,7 @@ def head_only_spec(S=2):
 def padded_spec(S=2):
     """--paddings 1,0: the first layer pads its 10 x 10 x 1 input by 1, the head does not."""
     hwc = (10, 10, 1)
-    return hwc, pr.padded_spec(hwc=hwc, convs=[(3, 1, 2, 1)], head=(3, 1, 0), Ms=12, S=S)
+    return hwc, ss.stack_spec(hwc=hwc, convs=[(3, 1, 2, 1, 1)], head=(3, 1, 0), Ms=12, S=S)
 
 
 # ---- 1: the gather -----------------------------------------------------------------------------------------------------------------------

@@ -9,6 +9,7 @@ import pytest
 
 import ard_ref as ar
 import live_specs as ls
+import torch_ref as tr
 
 
 class _NoPrior:
@@ -170,7 +171,7 @@ def test_reference_gradients_are_live(case):
     pytest.importorskip("torch")
     import matern_ref as mr
     spec, X, Y, zs = ar.ard_case(case)
-    _, want = mr.torch_reference(spec, X, Y, zs)
+    want = tr.reference(spec, X, Y, zs)["want"]
     for li, c in enumerate(spec["convs"]):
         assert want[li]["lengthscales"].shape == (c["f"] * c["f"] * c["C"],)
     ar.assert_live(case, want)
@@ -194,6 +195,6 @@ def test_mixing_reference_gradients_are_live(name):
     import mixing_ref as mx
     spec, X, Y, zs = mx.make_case(name)
     ar.ardify(spec)
-    _, want = mx.torch_reference(spec, X, Y, zs)
+    want = tr.reference(spec, X, Y, zs)["want"]
     assert all(np.ndim(want[li]["lengthscales"]) == 1 for li in range(len(spec["convs"])))
     ar.assert_live(name, want)

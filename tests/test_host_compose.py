@@ -1,8 +1,8 @@
 """No GPU: the covering table of tests/compose_cases.py and the composed torch reference of tests/compose_ref.py, before anything runs on a device.
 
 * the table covers every pair of levels of two different factors, or names the pair in ``EXCLUDED``, in at most 60 cases;
-* under RobustMax the composed reference IS tests/conv_mean_ref.py's (the same code path: bit for bit on ch_res / m264 / valid2), and it
-  agrees with tests/padding_ref.py's own forward on the padded Conv2dMean stacks;
+* under RobustMax the composed reference is tests/torch_ref.py's forward with its own tail (tests/test_host_torch_ref.py pins that forward to
+  the per-feature copies it replaced);
 * each likelihood rule on the plain stack agrees with the reference its own test file uses, to 1e-12 relative: float64 restatements of one
   formula.  Seen on the CPU: quad_ref.torch_elbo 0 (StudentT), 0 (Poisson); _torch_softmax_elbo 0; _torch_gauss 0; bernoulli_ref.elbo 4.4e-16
   (the NumPy oracle's forward under a SciPy tail: the only one that is not the same torch operations in the same order);
@@ -20,7 +20,6 @@ import compose_cases as cc          # noqa: E402
 import compose_ref as cr            # noqa: E402
 import conv_mean_ref as cmr         # noqa: E402
 import live_specs as ls             # noqa: E402
-import padding_ref as pr            # noqa: E402
 
 RULE_RTOL = 1e-12
 
@@ -44,7 +43,7 @@ def test_excluded_pairs_are_the_ones_the_library_refuses():
     asserted in tests/test_gpu_compose.py (building the layers already factors K_uu on the device, so no call without a GPU can know).
     Here: each excluded stack does hold a conv layer with an even filter, and no other stack does -- so no other (stack, conv2d) pair
     belongs in the list -- and the spec of such a case does ask for Conv2dMean on that layer."""
-    even = {name for name, k in cc.STACKS.items() if any(f % 2 == 0 for f, _, _, _ in k["convs"])}
+    even = {name for name, k in cc.STACKS.items() if any(f % 2 == 0 for f, *_ in k["convs"])}
     assert even == {a[1] for a, b, _ in cc.EXCLUDED} and all(b == ("mean", "conv2d") for _, b, _ in cc.EXCLUDED)
     for (_, stack), _, text in cc.EXCLUDED:
         assert text == "Conv2dMean supports odd filter sizes only"
@@ -52,42 +51,7 @@ def test_excluded_pairs_are_the_ones_the_library_refuses():
         assert any(c["f"] % 2 == 0 and c["mean_function"] == "conv2d" for c in spec["convs"])
 
 
-# ---- 2. RobustMax: the existing references on their own cases ---------------------------------------------------------------------------
-def _same_bits(a, b):
-    assert a[0] == b[0], (a[0], b[0])
-    assert len(a[1]) == len(b[1])
-    for ga, gb in zip(a[1], b[1]):
-        assert set(ga) == set(gb)
-        for k in ga:
-            assert np.array_equal(ga[k], gb[k]), k
-
-
-@pytest.mark.parametrize("name", ["ch_res", "m264", "valid2"])
-def test_robustmax_is_conv_mean_refs_own_path_bit_for_bit(name):
-    spec, X, Y, zs = cmr.make_case(name)
-    parts, want, dlik = cr.torch_reference(spec, X, Y, zs, ("robustmax", 10))
-    assert dlik is None
-    _same_bits((parts, want), cmr.torch_reference(spec, X, Y, zs))
-    J, dX = cr.torch_input_gradient(spec, X, Y, zs, ("robustmax", 10))
-    Jw, dXw = cmr.torch_input_gradient(spec, X, Y, zs)
-    assert np.array_equal(J, Jw) and np.array_equal(dX, dXw)
-
-
-@pytest.mark.parametrize("name", ["res3", "res3_white"])
-def test_conv2d_mean_and_padding_agree_with_padding_ref(name):
-    """tests/padding_ref.py's own forward (Conv2dMean on layer 0 of a padded stack) against the composed one: the same operations."""
-    spec, X, Y, zs = pr.make_stack(name)
-    parts, want, _ = cr.torch_reference(spec, X, Y, zs, ("robustmax", 10))
-    pw, gw = pr.torch_reference(spec, X, Y, zs)
-    worst = max(abs(a - b) / abs(b) for a, b in zip(parts, pw))
-    for ga, gb in zip(want, gw):
-        assert set(ga) == set(gb)
-        worst = max([worst] + [float(np.abs(ga[k] - gb[k]).max() / np.abs(gb[k]).max()) for k in ga])
-    print("%s: composed vs padding_ref, largest relative difference %.3e" % (name, worst))
-    assert worst <= RULE_RTOL
-
-
-# ---- 3. the likelihood rules on the plain stack -----------------------------------------------------------------------------------------
+# ---- 2. the likelihood rules on the plain stack -----------------------------------------------------------------------------------------
 def _leaf_grads(e, leaves, extra=()):
     flat = [t for p in leaves for t in p.values()] + [t for t in extra if t is not None]
     return [g.numpy() for g in torch.autograd.grad(e, flat)]
@@ -143,7 +107,7 @@ def test_bernoulli_rule_matches_bernoulli_ref(D, white):
         _agree("bernoulli D=%d %s" % (D, what), g, w)
 
 
-# ---- 4. liveness of every case ----------------------------------------------------------------------------------------------------------
+# ---- 3. liveness of every case ----------------------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def reference(cid):
     spec, X, Y, zs, lik = cc.make_case(cc.BY_ID[cid])

@@ -11,6 +11,8 @@ import numpy as np
 import pytest
 
 import dilation_ref as dr
+import stack_specs as ss
+import torch_ref as tr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # (H, W, C, f, d) of the issue's identity check; d^2 P' / P is 1 where d divides both sides, 1.19 for 17 x 17 d3, 1.6 for 9 x 7 d2
@@ -195,7 +197,7 @@ def test_torch_forward_of_the_stacks_is_live_and_has_the_dilated_sizes(name):
     pytest.importorskip("torch")
     import live_specs as ls
     spec, X, Y, zs = dr.make_stack(name)
-    ref = dr.torch_reference(spec, X, Y, zs)
+    ref = tr.reference(spec, X, Y, zs)
     assert all(np.isfinite(ref["parts"]))
-    assert [m.shape[-1] for m in ref["means"]] == [o for _, o in dr.output_dims(spec)]
+    assert [m.shape[-1] for m in ref["means"]] == [o for _, o in ss.output_dims(spec)]
     ls.assert_live(name, ref["want"])

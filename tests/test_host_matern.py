@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import matern_ref as mr
+import torch_ref as tr
 
 GPU_CASES = ("small3_M20", "small3_white_M20", "odd_M33", "mnist3_M72", "ch_M200", "ch_M384")
 
@@ -150,7 +151,7 @@ def test_make_spec_records_the_base_and_leaves_rbf_and_acos_alone():
 
 @pytest.mark.parametrize("base", ["matern32", "matern52"])
 def test_the_helper_is_the_textbook_forward_with_another_gram(base, monkeypatch):
-    """tests/matern_ref.py's forward against a stand-in written here: tests/test_oracle_autograd.py's _torch_elbo with its conv layers'
+    """tests/torch_ref.py's forward (with tests/matern_ref.py's Gram function) against a stand-in written here: tests/test_oracle_autograd.py's _torch_elbo with its conv layers'
     Gram function replaced (the head keeps the RBF).  Value and one gradient group."""
     torch = pytest.importorskip("torch")
     import test_oracle_autograd as toa
@@ -158,7 +159,8 @@ def test_the_helper_is_the_textbook_forward_with_another_gram(base, monkeypatch)
     _stand_in(monkeypatch, toa, spec, mr.NU2[base])
     e_s, leaves = toa._torch_elbo(spec, X, Y, zs)
     (g_s,) = torch.autograd.grad(e_s, [leaves[0]["lengthscales"]])
-    e_h, want = mr.torch_reference(spec, X, Y, zs)
+    ref = tr.reference(spec, X, Y, zs)
+    e_h, want = ref["parts"][0], ref["want"]
     assert abs(e_h - e_s.item()) <= 1e-13 * abs(e_h)
     assert abs(want[0]["lengthscales"] - g_s.item()) <= 1e-11 * abs(g_s.item())
 

@@ -7,6 +7,7 @@ import pytest
 
 import live_specs as ls
 import mixing_ref as R
+import torch_ref as tr
 
 
 class _NoPrior:
@@ -205,7 +206,7 @@ def test_mirror_backward_against_central_differences(K, G, Rm):
 
 
 def test_the_two_torch_loops_agree_on_an_unmixed_layer():
-    """mixing_ref's layer loop with W = I against conv_mean_ref.torch_forward on the same spec without the mixing: ELBO parts to 1e-13."""
+    """torch_ref.forward's mixed branch with W = I against its unmixed branch on the same spec without the mixing: ELBO parts to 1e-13."""
     torch = pytest.importorskip("torch")
     for name in ("a_3_3", "pad_lin"):
         spec, X, Y, zs = R.make_case(name, **({"G": 5} if name == "pad_lin" else {}))
@@ -214,7 +215,7 @@ def test_the_two_torch_loops_agree_on_an_unmixed_layer():
         plain = R.copy.deepcopy(eye)
         del plain["convs"][0]["mix_W"]
         with torch.no_grad():
-            a, b = R.torch_forward(eye, X, Y, zs), R.cmr.torch_forward(plain, X, Y, zs)
+            a, b = tr.forward(eye, X, Y, zs), tr.forward(plain, X, Y, zs)
         for k in ("elbo", "kl"):
             assert abs(a[k].item() - b[k].item()) <= 1e-13 * abs(b[k].item()), (name, k)
         assert torch.allclose(a["F"][0], b["F"][0], rtol=1e-13, atol=1e-13)
@@ -232,7 +233,8 @@ def gpu_cases():
 def test_gpu_cases_are_live(cid, kw):
     pytest.importorskip("torch")
     spec, X, Y, zs = R.make_case(**kw)
-    (elbo, _, _), want = R.torch_reference(spec, X, Y, zs)
+    t = tr.reference(spec, X, Y, zs)
+    elbo, want = t["parts"][0], t["want"]
     mixed = [li for li, c in enumerate(spec["convs"]) if c.get("mix_W") is not None]
     assert mixed
     for li in mixed:
@@ -240,7 +242,7 @@ def test_gpu_cases_are_live(cid, kw):
         print("%s layer %d |gW|max %.3e" % (cid, li, top))
         assert top >= ls.LIVE_MAX, (cid, li, top)
     ls.assert_live(cid, want)
-    (other, _, _), _ = R.torch_reference(R.reseeded(spec), X, Y, zs)
+    other = tr.reference(R.reseeded(spec), X, Y, zs)["parts"][0]
     rel = abs(other - elbo) / abs(elbo)
     print("%s ELBO %.9g, with the next seed's W %.9g: %.3e" % (cid, elbo, other, rel))
     assert rel > 1e-3, (cid, elbo, other)

@@ -10,6 +10,8 @@ import numpy as np
 import pytest
 
 import padding_ref as pr
+import stack_specs as ss
+import torch_ref as tr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -100,7 +102,7 @@ def test_model_builder_spec_chains_the_padded_geometry(monkeypatch):
     spec = ModelBuilder(_flags("--paddings", "1,1,1", "--identity-mean"), X, rng.integers(0, 10, (30, 1))).spec()
     got = [(c["H"], c["W"], c["C"], c["pad"]) for c in spec["convs"]] + [tuple(spec["head"][k] for k in ("H", "W", "C", "pad"))]
     assert got == [(10, 10, 1, 1), (10, 10, 2, 1), (5, 5, 2, 1)], got
-    sizes, P = pr.chain((10, 10, 1), [(3, 1, 2, 1), (3, 2, 2, 1)], (3, 1, 1))
+    sizes, P = ss.chain((10, 10, 1), [(3, 1, 2, 1, 1), (3, 2, 2, 1, 1)], (3, 1, 1))
     assert sizes == [g[:3] for g in got] and P == 25
     assert [c["Z"].shape for c in spec["convs"]] == [(5, 9), (6, 18)] and spec["head"]["Z"].shape == (7, 18)
     from deepcgp_amd.views import FullView
@@ -151,13 +153,13 @@ def test_padded_oracle_matches_the_torch_forward(name):
     spec, X, Y, zs = pr.make_stack(name)
     ref = pr.oracle_model(spec, X, Y)
     with torch.no_grad():
-        e, data, kl, _ = pr.torch_elbo(spec, X, Y, zs)
+        out = tr.forward(spec, X, Y, zs)
     got = (ref.compute_log_likelihood(X, Y, zs=zs), ref.data_term(X, Y, zs=zs), ref.KL())
-    for what, g, w in zip(("elbo", "data", "kl"), got, (e.item(), data.item(), kl.item())):
+    for what, g, w in zip(("elbo", "data", "kl"), got, (out["elbo"].item(), out["data"].sum().item(), out["kl"].item())):
         print("%s %-4s oracle %.12g torch %.12g rel %.3e" % (name, what, g, w, abs(g - w) / abs(w)))
         assert np.isfinite(g) and abs(g - w) <= 1e-9 * abs(w), (name, what, g, w)
     _, Fm, _ = ref.propagate(X, S=spec["S"], zs=zs)
-    assert [m.shape[-1] for m in Fm] == pr.output_dims(spec)
+    assert [m.shape[-1] for m in Fm] == [o for _, o in ss.output_dims(spec)]
     # the layer-0 identity on the CPU: the VALID model of the same parameters on np.pad(X) gives layer 0's outputs
     c0 = spec["convs"][0]
     phys = pr.physical(spec)

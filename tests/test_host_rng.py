@@ -13,6 +13,7 @@ from deepcgp_amd import augment
 import dilation_ref as dr
 import padding_ref as pr
 import rng_ref as rr
+import stack_specs as ss
 
 N_DRAWS = 1 << 20
 PAIRS = [(1, 1), (77, 2), ((5 << 32) | 3, 65)]
@@ -85,10 +86,10 @@ def test_counters_are_disjoint_across_layers_ranks_and_the_augmentation():
         for li, (stream, idx) in enumerate(rr.layer_counters(spec, N, S, rank=rank)):
             assert stream == li + 1 + 64 * rank and stream not in seen and li < 63
             seen.add(stream)
-            assert np.unique(idx).size == idx.size == S * N * pr.output_dims(spec)[li]
+            assert np.unique(idx).size == idx.size == S * N * ss.output_dims(spec)[li][0]
             assert np.array_equal(idx.reshape(-1), np.arange(idx.size, dtype=np.uint64))      # the element's offset in [S, N, P G]
     zs = rr.device_noise(spec, N, S, 5)
-    assert zs[-1] is None and [z.shape for z in zs[:-1]] == [(S, N, d) for d in pr.output_dims(spec)[:-1]]
+    assert zs[-1] is None and [z.shape for z in zs[:-1]] == [(S, N, d) for d, _ in ss.output_dims(spec)[:-1]]
     assert not np.array_equal(zs[0][0], zs[0][1])                                   # the replicas of an image draw their own noise
     assert not np.array_equal(zs[0].reshape(-1)[:zs[1].size], zs[1].reshape(-1))    # two layers at the same idx
     assert not np.array_equal(zs[0], rr.device_noise(spec, N, S, 5, rank=1)[0])
